@@ -7,6 +7,10 @@ regularisation step (regularize=:unbiased, :error_estimate), B=512 columns per G
 resident in HBM.  Metric: NFE/s = vector-field evaluations (of one 512-column shard) per second,
 summed over ranks.  Launch: `python bench.py --gpus 1` or, for N>1,
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`.
+
+A plain run sets up, warms up, times --steps passes and prints the result line.  Everything else (the sustained leg,
+forward + adjoint, the roofline launches, the conv / SDE side measurements, the CPU baselines and the oracle comparisons)
+runs with --full.  --dump-outputs DIR writes what the last timed pass returned as DIR/<name>.npy (float32 / float64).
 """
 import argparse
 import json
@@ -112,6 +116,28 @@ def measured_traffic(key):
     return None
 
 
+DUMP_MAX_BYTES = 48 << 20  # per dump: each workload returns one large array, so with the scalars a dump stays under 64 MB
+
+
+def dump_outputs(d, arrays, writers=1):
+    """--dump-outputs: each array as d/<name>.npy, float32 arrays as they are, every other number as float64.  An array
+    larger than DUMP_MAX_BYTES / writers (the ranks that write into d) is cut to a fixed, seeded sample of its rows (the
+    row indices go to <name>_rows.npy)."""
+    os.makedirs(d, exist_ok=True)
+    cap = DUMP_MAX_BYTES // writers
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        a = a if a.dtype == np.float32 else a.astype(np.float64)
+        if a.nbytes > cap:
+            keep = max(cap // (a.nbytes // a.shape[0]), 1)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(d, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -121,12 +147,17 @@ def main():
     ap.add_argument("--tol", type=float, default=1.4e-8)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=512)
-    ap.add_argument("--no-conv", action="store_true", help="skip the 28x28 conv-field side measurement of the default run")
+    ap.add_argument("--no-conv", action="store_true", help="with --full: skip the conv-field and SDE-layer side measurements (a plain run has none)")
     ap.add_argument("--adjoint-steps", type=int, default=30, help="timed forward+adjoint passes (single GPU)")
     ap.add_argument("--sustain-s", type=float, default=1.0, help="length of the sustained leg (seconds of forward passes)")
     ap.add_argument("--workload", default="mlp", choices=["mlp", "cifar_conv_bf16", "cifar_conv_f32", "cifar_conv_f32_split", "mnist_conv_f32", "mnist_conv_f32_split", "mnist_sde"],  # *_split: opt-in fast mode, never part of the default line
                     help="mlp: the headline MNIST-ODE MLP field (default).  The conv workloads time the CIFAR10 node_core "
                          "(BASELINE.json configs 4 and 2-ii); single GPU.")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (sustained leg, forward + adjoint, roofline, conv / SDE "
+                         "configs, CPU baselines, oracle comparisons); a plain run times the --steps passes only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass returned as DIR/<name>.npy")
     args = ap.parse_args()
     if args.workload == "mnist_sde":
         return sde_main(args)
@@ -186,7 +217,8 @@ def main():
         r = one_pass(args.warmup + i)
         nfe_total += r["nfe"]
         steps_total += r["stats"]["naccept"] + r["stats"]["nreject"] + 1
-        sign(r)
+        if dist:
+            sign(r)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -195,6 +227,12 @@ def main():
         tt = torch.tensor([el], device="cuda", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    if args.dump_outputs:
+        # what node_forward returned for the last timed pass; with N > 1 ranks each rank writes its own column shard
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {f"{k}{sfx}": v for k, v in
+                                         [("u_end", r["u_end"]), ("reg_val", r["reg_val"]), ("nfe", r["nfe"]), ("t1", r["t1"])] +
+                                         [(f"stats_{k}", v) for k, v in r["stats"].items()]}, writers=world)
 
     # Self-verification of the N > 1 run (the first RCCL run with more than one rank is the driver's): the communicator the
     # library built has WORLD_SIZE ranks, and every rank took the SAME steps in every timed pass (nfe, accepted, rejected,
@@ -209,7 +247,8 @@ def main():
         dist.all_gather(allsig, mine)
         same = all(bool(torch.equal(a, allsig[0])) for a in allsig)
         verify["ranks_took_identical_steps"] = same
-        verify["allreduce_us_per_step"] = h.bench_exchange(args.batch, reps=100)  # collective: every rank calls it
+        if args.full:
+            verify["allreduce_us_per_step"] = h.bench_exchange(args.batch, reps=100)  # collective: every rank calls it
         if rccl_nranks != world or comm_kind != 1 or not same:
             if rank == 0:
                 print(json.dumps({"error": "sharded run failed its self-check", "world": world, **verify}), file=sys.stderr)
@@ -218,7 +257,7 @@ def main():
 
     # sustained leg: >= --sustain-s seconds of forward passes in one timed region (the driver's --steps 20 is a 34-ms sample)
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         npass = max(int(np.ceil(args.sustain_s / (el / args.steps))), args.steps)
         if dist:
             dist.barrier()
@@ -242,7 +281,7 @@ def main():
     # through Chain(neural_ode, classifier Dense(784=>10)); fwd/bwd split timed as there.  Timed on one GPU only
     # (the scaling metric is the forward NFE/s; the sharded adjoint is exercised by tests/ and tools/bench/sharded_check.py).
     fwd_adj_ms, bwd_stats = None, None
-    if world == 1 and args.adjoint_steps > 0:
+    if args.full and world == 1 and args.adjoint_steps > 0:
         node = P.NeuralODE(model, regularize="unbiased", regularize_type="error_estimate", abstol=args.tol, reltol=args.tol,
                            save_start=False, maxiters=10000)
         node._handle = h  # reuse the bench handle; run_training_step repacks the parameters on every call (inside fwd_time)
@@ -282,16 +321,30 @@ def main():
     #      speculative launches that find the solve finished), divided by its full steps — what a per-dispatch profile of
     #      the same command averages to for FULL steps, minus the profiler's own per-dispatch overhead
     #      (profiles/r2/README.md compares the three).
-    k1 = h.rhs(x, 0.0)
-    dt_typ = float(r["stats"]["dt_final"]) if r["stats"]["dt_final"] > 0 else 0.02
-    us_batches = sorted(h.bench_step(x, k1, 0.0, dt_typ, args.tol, args.tol, reps=100) for _ in range(5))
-    us = us_batches[2]  # median of five batches of 100 launches (each batch: one HIP-event pair, mean over its launches)
-    flop_per_launch = 6 * FLOP_PER_FEVAL_PER_COL * args.batch
-    achieved = flop_per_launch / (us * 1e-6) / 1e12
-    h.last_solve_kernel_ms()  # arms the solve's event pair (off in the timed passes above: two marker packets per solve)
-    rs = one_pass(args.warmup + args.steps - 1)
-    solve_ms, solve_launches = h.last_solve_kernel_ms()
-    full_steps = rs["stats"]["naccept"] + rs["stats"]["nreject"]
+    roofline = None
+    if args.full:
+        k1 = h.rhs(x, 0.0)
+        dt_typ = float(r["stats"]["dt_final"]) if r["stats"]["dt_final"] > 0 else 0.02
+        us_batches = sorted(h.bench_step(x, k1, 0.0, dt_typ, args.tol, args.tol, reps=100) for _ in range(5))
+        us = us_batches[2]  # median of five batches of 100 launches (each batch: one HIP-event pair, mean over its launches)
+        flop_per_launch = 6 * FLOP_PER_FEVAL_PER_COL * args.batch
+        achieved = flop_per_launch / (us * 1e-6) / 1e12
+        h.last_solve_kernel_ms()  # arms the solve's event pair (off in the timed passes above: two marker packets per solve)
+        rs = one_pass(args.warmup + args.steps - 1)
+        solve_ms, solve_launches = h.last_solve_kernel_ms()
+        full_steps = rs["stats"]["naccept"] + rs["stats"]["nreject"]
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / PEAK_F32_MFMA_TFLOPS,
+                    # HBM/fabric bytes per launch: read from the committed PMC summary of this round (measured_traffic),
+                    # null for any workload that has no committed measurement
+                    "traffic": measured_traffic(f"k_step_q_b{args.batch}") if world == 1 else None,
+                    "kernel": "k_step_q<false, 1> (one attempted Tsit5 step: 6 f-evals, fused stage combination, error norm)"
+                              if args.batch <= 2048 else "k_step<4,false>",
+                    "us_per_launch": us, "us_per_launch_batches": us_batches, "flop_per_launch": flop_per_launch,
+                    "in_solve": {"solve_kernel_ms": solve_ms, "step_launches": solve_launches, "full_steps": full_steps,
+                                 "us_per_full_step": solve_ms * 1e3 / max(full_steps, 1),
+                                 "what": "HIP events around all kernels of one adaptive solve (2 init + steps + terminal/"
+                                         "speculative launches) / full steps: an upper bound of the step kernel's in-solve duration"}}
 
     out = {
         "metric": "NFE/s (vector-field evals/s inside the adaptive Tsit5 NeuralODE forward, MNIST-ODE B=512/GPU)",
@@ -319,20 +372,9 @@ def main():
                                "the summation order of the dense layers - this kernel order 35 steps, OpenBLAS sgemm 40, a float64 "
                                "field 20, all with sol.u[end] equal to 5e-7 (DESIGN.md 2); the Julia reference would count its "
                                "own BLAS's number"},
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / PEAK_F32_MFMA_TFLOPS,
-                     # HBM/fabric bytes per launch: read from the committed PMC summary of this round (measured_traffic),
-                     # null for any workload that has no committed measurement
-                     "traffic": measured_traffic(f"k_step_q_b{args.batch}") if world == 1 else None,
-                     "kernel": "k_step_q<false, 1> (one attempted Tsit5 step: 6 f-evals, fused stage combination, error norm)"
-                               if args.batch <= 2048 else "k_step<4,false>",
-                     "us_per_launch": us, "us_per_launch_batches": us_batches, "flop_per_launch": flop_per_launch,
-                     "in_solve": {"solve_kernel_ms": solve_ms, "step_launches": solve_launches, "full_steps": full_steps,
-                                  "us_per_full_step": solve_ms * 1e3 / max(full_steps, 1),
-                                  "what": "HIP events around all kernels of one adaptive solve (2 init + steps + terminal/"
-                                          "speculative launches) / full steps: an upper bound of the step kernel's in-solve duration"}},
+        "roofline": roofline,
     }
-    if rank == 0 and world == 1 and not args.no_conv:
+    if args.full and rank == 0 and world == 1 and not args.no_conv:
         # BASELINE.json configs[1] read literally ("28x28 conv vector field, batch=512 fp32"): the CIFAR block topology on a
         # 28x28x8 state (not a model of the reference) — measured alongside, `--workload
         # mnist_conv_f32` gives its full line
@@ -343,7 +385,7 @@ def main():
         out["config"]["cifar_conv_f32_b256"] = conv_measure(args, "cifar_conv_f32", brief=True)
         # BASELINE.json configs[4] (MNIST-SDE, B=512): the NeuralDSDE layer's forward and pullback; `--workload mnist_sde` gives its line
         out["config"]["mnist_sde_layer_b512"] = sde_layer_side_measurement(512)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the GPU box gives one GPU's share of the host: 16 cores (os.cpu_count() reports the whole host)
         cores = int(os.environ.get("LRNDE_CPU_CORES", min(len(os.sched_getaffinity(0)), 16)))
         cb = min(args.cpu_batch, args.batch)
@@ -417,7 +459,7 @@ def conv_measure(args, workload, brief=False):
                                "mnist_conv_f32_split": (28, 28, 512, "f32_split", 1e-4, False)}[workload]
     if args.batch != 512 and not brief:
         B = args.batch
-    steps, warmup = (3, 1) if brief else (min(args.steps, 10), min(args.warmup, 2))
+    steps, warmup = (3, 1) if brief else (args.steps, args.warmup)
     params = P.glorot_conv_params(8, 64, seed=0)
     xh = np.random.default_rng(0).standard_normal((B, 8, H, W)).astype(np.float32)  # u0 ~ N(0,1)
     x = torch.from_numpy(xh).cuda()
@@ -440,8 +482,11 @@ def conv_measure(args, workload, brief=False):
         steps_total += r["stats"]["naccept"] + r["stats"]["nreject"] + 1
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs and not brief:  # what node_forward returned for the last timed pass
+        dump_outputs(args.dump_outputs, dict([("u_end", r["u_end"]), ("reg_val", r["reg_val"]), ("nfe", r["nfe"]), ("t1", r["t1"])] +
+                                             [(f"stats_{k}", v) for k, v in r["stats"].items()]))
     fwd_adj_ms, bwd = None, None
-    if args.adjoint_steps > 0 and not brief:  # (bf16: bf16 forward re-solve, fp32 adjoint) pullback of <g, sol.u[end]> + 2.5*reg_val, g ~ 1e-3*N(0,1) (a mean-loss cotangent's size)
+    if args.full and args.adjoint_steps > 0 and not brief:  # (bf16: bf16 forward re-solve, fp32 adjoint) pullback of <g, sol.u[end]> + 2.5*reg_val, g ~ 1e-3*N(0,1) (a mean-loss cotangent's size)
         g = torch.from_numpy((np.random.default_rng(2).standard_normal(xh.shape) * 1e-3).astype(np.float32)).cuda()
         nb = min(args.adjoint_steps, 3)
         h.node_backward(x, 0.0, 1.0, tol, tol, g, mode="unbiased", t1_or_rand=float(t1s[0]), w_reg=2.5, maxiters=10000)
@@ -454,11 +499,19 @@ def conv_measure(args, workload, brief=False):
         fwd_adj_ms = (time.perf_counter() - tb) / nb * 1e3
         bwd = {"adjoint_naccept": rb["stats_bwd"]["naccept"], "adjoint_nreject": rb["stats_bwd"]["nreject"],
                "adjoint_nf": rb["stats_bwd"]["nf"]}
-    us = h.bench_rhs(x, 0.3, reps=20)  # HIP events on the handle's stream around 20 f-evals
     flop = CONV_FLOP_PER_PIXEL * W * H * B
     # f32_split: three fp16 MFMAs per product -> a third of the fp16 (= bf16) dense rate bounds conv2/conv3
     peak = {"bf16": PEAK_BF16_MFMA_TFLOPS, "f32_split": PEAK_BF16_MFMA_TFLOPS / 3.0}.get(dt, PEAK_F32_MFMA_TFLOPS)
-    achieved = flop / (us * 1e-6) / 1e12
+    roofline = None
+    if args.full or brief:
+        us = h.bench_rhs(x, 0.3, reps=20)  # HIP events on the handle's stream around 20 f-evals
+        achieved = flop / (us * 1e-6) / 1e12
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                    # HBM/fabric bytes per f-eval from the committed PMC summary (profiles/r<N>/traffic.json, separate rocprofv3
+                    # --pmc passes: 2 x FETCH_SIZE + WRITE_SIZE over the five launches) or null: never a literal
+                    "traffic": measured_traffic(f"conv_feval_{workload}_b{B}"), "kernel": "one f-eval = k_conv_wide(conv1) + k_bn_finalize + k_conv_wide(conv2) + "
+                                               "k_bn_finalize + k_conv_out(conv3)",
+                    "us_per_launch": us, "flop_per_launch": flop}
     out = {
         "metric": f"NFE/s (vector-field evals/s inside the adaptive Tsit5 NeuralODE forward, conv field {W}x{W}x8, B={B})",
         "value": nfe_total / el, "unit": "NFE/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
@@ -470,18 +523,13 @@ def conv_measure(args, workload, brief=False):
                    "global_batch": B, "parallelism": "single GPU", "nfe_per_pass": nfe_total / steps,
                    "rk_steps_per_sec": steps_total / el, "fwd_ms_per_batch": el / steps * 1e3,
                    "fwd_plus_adjoint_ms_per_batch": fwd_adj_ms, "adjoint": bwd},
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                     # HBM/fabric bytes per f-eval from the committed PMC summary (profiles/r<N>/traffic.json, separate rocprofv3
-                     # --pmc passes: 2 x FETCH_SIZE + WRITE_SIZE over the five launches) or null: never a literal
-                     "traffic": measured_traffic(f"conv_feval_{workload}_b{B}"), "kernel": "one f-eval = k_conv_wide(conv1) + k_bn_finalize + k_conv_wide(conv2) + "
-                                                "k_bn_finalize + k_conv_out(conv3)",
-                     "us_per_launch": us, "flop_per_launch": flop},
+        "roofline": roofline,
     }
     if brief:
         return {"workload": out["config"]["workload"], "value": out["value"], "unit": "NFE/s", "nfe_per_pass": nfe_total / steps,
                 "fwd_ms_per_batch": el / steps * 1e3, "us_per_feval": us, "achieved_tflops": achieved, "roofline_frac": achieved / peak,
                 "dtype": dt}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O
         cores = int(os.environ.get("LRNDE_CPU_CORES", min(len(os.sched_getaffinity(0)), 16)))
@@ -566,8 +614,7 @@ def sde_main(args):
     ud, dWd = torch.from_numpy(u0).cuda(), torch.from_numpy(dW).cuda()
 
     def one_pass():  # lrnde_sde_solve_fixed: the grid's steps in one launch + one for their records, one host sync per solve
-        tr = h.solve_fixed(ud, dWd, 0.0, dt, 0.14, 0.14, 1.0 / 6.0)  # abstol=reltol=0.14 (mnist_sde/mlp.yml)
-        return dict(eest=tr["eest"][-1], reg_val=tr["reg_val"][-1])
+        return h.solve_fixed(ud, dWd, 0.0, dt, 0.14, 0.14, 1.0 / 6.0)  # abstol=reltol=0.14 (mnist_sde/mlp.yml)
 
     for _ in range(args.warmup):
         one_pass()
@@ -577,6 +624,8 @@ def sde_main(args):
         r = one_pass()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:  # what solve_fixed returned for the last timed pass
+        dump_outputs(args.dump_outputs, r)
     nst = args.steps * nsteps
     flop = 3 * (2 * B * 2 * D * H) + 3 * (2 * B * D * D)
     out = {
@@ -588,15 +637,16 @@ def sde_main(args):
                                "one pass = one solve (lrnde_sde_solve_fixed: ONE launch marches the grid's steps, a second forms their records); every step's "
                                "state, error estimate and residual are returned with the solve",
                    "global_batch": B, "parallelism": "single GPU", "us_per_sde_step": el / nst * 1e6, "flop_per_step": flop,
-                   "last_eest": float(r["eest"]), "last_reg_val": float(r["reg_val"])},
+                   "last_eest": float(r["eest"][-1]), "last_reg_val": float(r["reg_val"][-1])},
         "roofline": {"bound": "mfma", "achieved": flop / (el / nst) / 1e12, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                      "frac": flop / (el / nst) / 1e12 / PEAK_F32_MFMA_TFLOPS, "traffic": None,
                      "kernel": f"k_sde_eh_fast, march mode: the {nsteps} steps of the solve in ONE launch (weights resident in registers, no step waits for another "
                                "workgroup; k_sde_march_records forms the records); 15.7 MFLOP per step: latency bound by construction; wall clock per solve incl. the host's part",
                      "us_per_launch": el / args.steps * 1e6, "flop_per_launch": flop * nsteps},
     }
-    out["config"]["layer"] = sde_layer_leg(h, ud, rng, B, D)
-    if not args.no_cpu_baseline:
+    if args.full:
+        out["config"]["layer"] = sde_layer_leg(h, ud, rng, B, D)
+    if args.full and not args.no_cpu_baseline:
         import oracle as O
         cores = int(os.environ.get("LRNDE_CPU_CORES", min(len(os.sched_getaffinity(0)), 16)))
         p2 = np.concatenate([np.eye(D, dtype=np.float32).ravel(), np.zeros(D, np.float32), pg])

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/mlp_bwd_pmc; mkdir -p $O
 i=0
 for ctrs in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/$i -o p -- python3 $R/bench.py --no-conv --no-cpu-baseline --steps 2 --warmup 1 --adjoint-steps 2 > $O/run$i.log 2>&1 || { tail -3 $O/run$i.log; exit 1; }
+  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/$i -o p -- python3 $R/bench.py --full --no-conv --no-cpu-baseline --steps 2 --warmup 1 --adjoint-steps 2 > $O/run$i.log 2>&1 || { tail -3 $O/run$i.log; exit 1; }
 done
 python3 - <<PY
 import csv,re,collections

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/icache_pmc; mkdir -p $O
 i=0
 for ctrs in "SQC_ICACHE_HITS SQC_ICACHE_MISSES" "SQC_ICACHE_REQ SQC_ICACHE_MISSES_DUPLICATE" "SQ_IFETCH SQ_BUSY_CYCLES" "SQC_TC_INST_REQ SQC_ICACHE_BUSY_CYCLES"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/$i -o p -- python3 $R/bench.py --no-conv --no-cpu-baseline --steps 3 --warmup 1 --adjoint-steps 1 > $O/run$i.log 2>&1 || { tail -3 $O/run$i.log; exit 1; }
+  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/$i -o p -- python3 $R/bench.py --full --no-conv --no-cpu-baseline --steps 3 --warmup 1 --adjoint-steps 1 > $O/run$i.log 2>&1 || { tail -3 $O/run$i.log; exit 1; }
 done
 python3 - <<PY
 import csv,re,collections,glob

@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/mlp_lds_pmc; mkdir -p $O
 i=0
 for ctrs in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_INSTS_LDS SQ_WAIT_INST_LDS" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" "SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_ACTIVE_INST_VMEM SQ_INSTS_VMEM_RD"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/$i -o p -- python3 $R/bench.py --no-conv --no-cpu-baseline --steps 3 --warmup 1 --adjoint-steps 1 > $O/run$i.log 2>&1 || { tail -3 $O/run$i.log; exit 1; }
+  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/$i -o p -- python3 $R/bench.py --full --no-conv --no-cpu-baseline --steps 3 --warmup 1 --adjoint-steps 1 > $O/run$i.log 2>&1 || { tail -3 $O/run$i.log; exit 1; }
 done
 python3 - <<PY
 import csv,re,collections,glob

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/conv_r1; mkdir -p $O
 cd $R
 for w in cifar_conv_bf16 cifar_conv_f32 cifar_conv_f32_split mnist_conv_f32 mnist_conv_f32_split; do
-  timeout -k 10 400 python bench.py --workload $w 2>/dev/null | tail -1 > $O/bench_${w}.json || exit 1
+  timeout -k 10 400 python bench.py --full --workload $w 2>/dev/null | tail -1 > $O/bench_${w}.json || exit 1
   echo "$w done"
 done
 cd /tmp && export TMPDIR=/tmp

@@ -5,14 +5,14 @@
 #      -> pmc/*.csv, pmc_summary.txt, traffic.json (what bench.py's roofline.traffic reads)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r2prof; mkdir -p $O/pmc
 cd $R
-timeout -k 10 400 python bench.py 2>/dev/null | tail -1 > $O/bench_r2.json || exit 1
+timeout -k 10 400 python bench.py --full 2>/dev/null | tail -1 > $O/bench_r2.json || exit 1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py > $O/bench_prof.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 $R/bench.py --full > $O/bench_prof.log 2>&1 || exit 1
 tail -1 $O/bench_prof.log | cut -c1-200
 i=0
 for ctrs in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES" "GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/pmc/$i -o p -- python3 $R/bench.py --no-conv --no-cpu-baseline --steps 5 --warmup 1 --adjoint-steps 0 > $O/pmc/run$i.log 2>&1 || { tail -3 $O/pmc/run$i.log; exit 1; }
+  rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $O/pmc/$i -o p -- python3 $R/bench.py --full --no-conv --no-cpu-baseline --steps 5 --warmup 1 --adjoint-steps 0 > $O/pmc/run$i.log 2>&1 || { tail -3 $O/pmc/run$i.log; exit 1; }
 done
 cd $R
 python3 profiles/pmc_summary.py $O/pmc "k_step_q<false" > $O/pmc_summary.txt
