@@ -73,7 +73,7 @@ struct ModelDev {
   const float* b2;   // [Dp]
   // 4-column tile family (lrnde_qtile.hpp)
   const float* W1q;  // [RG1][KQ1p][64][4]
-  const float* W2q;  // [RG2][KQ2p][64][4]
+  const float* W2q;  // [2*nseg1][KQ2p][64][4] (lrnde_qtile.hpp q_w2_groups)
   int KQ1p, KQ2p, RG1, RG2;
 };
 
@@ -2263,7 +2263,7 @@ int lrnde_create(lrnde_ctx** out, const lrnde_model_desc* d, int device, void* s
   m.RG1 = (d->hidden_dim + 63) / 64;
   m.RG2 = (d->state_dim + 63) / 64;
   ok = ok && hipMalloc(&c->W1q, sizeof(float) * (size_t)m.RG1 * m.KQ1p * 256) == hipSuccess &&
-       hipMalloc(&c->W2q, sizeof(float) * (size_t)m.RG2 * m.KQ2p * 256) == hipSuccess &&
+       hipMalloc(&c->W2q, sizeof(float) * (size_t)q_w2_groups(m.KQ1p) * m.KQ2p * 256) == hipSuccess &&
        hipMalloc(&c->V1q, sizeof(float) * (size_t)m.RG1 * m.KQ1p * 256) == hipSuccess &&
        hipMalloc(&c->U2q, sizeof(float) * (size_t)m.RG2 * m.KQ2p * 256) == hipSuccess;
   if (!ok) { lrnde_destroy(c); return LRNDE_HIP_ERROR; }
@@ -2331,8 +2331,8 @@ int lrnde_set_params(lrnde_ctx* c, const float* p, size_t n) {
   hipLaunchKernelGGL(k_pack, dim3(256), dim3(256), 0, c->stream, p, m.D, m.H, m.td, m.Dp, m.Hp, c->W1p,
                      c->w1t, c->b1, c->W2p, c->w2t, c->b2);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(k_pack_q, dim3(256), dim3(256), 0, c->stream, p, m.D, m.H, m.td, m.KQ1p, m.KQ2p, m.RG1, m.RG2,
-                     c->W1q, c->W2q);
+  hipLaunchKernelGGL(k_pack_q, dim3(256), dim3(256), 0, c->stream, p, m.D, m.H, m.td, m.KQ1p, m.KQ2p, m.RG1,
+                     q_w2_groups(m.KQ1p), c->W1q, c->W2q);
   hipLaunchKernelGGL(k_pack_t, dim3(256), dim3(256), 0, c->stream, p, m.D, m.H, m.td, m.Dp, m.Hp, c->V1p, c->U2p);
   hipLaunchKernelGGL(k_pack_tq, dim3(256), dim3(256), 0, c->stream, p, m.D, m.H, m.td, m.KQ1p, m.KQ2p, m.RG1, m.RG2,
                      c->V1q, c->U2q);

@@ -36,6 +36,10 @@ struct SmemQ {
 };
 
 __device__ __forceinline__ int q_nseg1(const ModelDev& m) { return (m.KQ1p + QSEG - 1) / QSEG; }
+// Dense-2 row ownership: wave w produces the rows of its own Dense-1 segment, [112w, 112w + 112), as two 64-row groups
+// starting at 112w and 112w + 64 (packed groups 2w and 2w + 1 of W2q); rows 112w + 112 .. + 127 of the second group are
+// the next wave's.  So the x rows a wave writes in a stage epilogue are the ones it reads in the next Dense-1.
+__host__ __device__ __forceinline__ int q_w2_groups(int KQ1p) { return 2 * ((KQ1p + QSEG - 1) / QSEG); }
 
 // sum of the nseg (<= QNW) K-segment partials of C-fragment element e, in segment order (the canonical order), with all
 // LDS reads issued before the first add: a loop with the runtime trip count read, waited and added one segment at a time
@@ -97,21 +101,18 @@ __device__ __forceinline__ void smem_init_q(const ModelDev& m, const SmemQ& s) {
 struct TileIOQ {
   __amdgpu_buffer_rsrc_t rs;
   int voff;  // ((b0 + s) * D + 4q) * 4, or out of range for columns beyond the batch
-  int row_limit_bytes;  // D*4: rows at/after it (last row group) are masked
-  int q4;    // 16 * q: byte offset of this lane's row quad inside a row group
 };
 __device__ __forceinline__ TileIOQ make_tile_io_q(const StepArgs& a, int b0, int nvalid) {
   const int lane = threadIdx.x & 63, sidx = lane & 3, q = lane >> 2;
   TileIOQ io;
   io.rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.state, 0, (int)(a.n_local * 40), 0x00020000);
   io.voff = (sidx < nvalid) ? ((b0 + sidx) * a.m.D + q * 4) * 4 : 0x7ffffff0;
-  io.row_limit_bytes = a.m.D * 4;
-  io.q4 = q * 16;
   return io;
 }
-// offset of row group rg for this lane (out of range when the lane's rows are beyond D)
-__device__ __forceinline__ int q_voff(const TileIOQ& io, int rg) {
-  return (rg * 256 + io.q4 < io.row_limit_bytes) ? io.voff + rg * 256 : 0x7ffffff0;
+// offset of the Dense-2 row group starting at row rb for this lane (out of range when the lane's rows are not its wave's:
+// beyond D, or the 16 rows of the next wave's segment in a wave's second group)
+__device__ __forceinline__ int q_voff(const TileIOQ& io, int rb, bool own) {
+  return own ? io.voff + rb * 4 : 0x7ffffff0;
 }
 __device__ __forceinline__ f32x4 qload(const TileIOQ& io, int voff_rg, int soff) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(io.rs, voff_rg, soff, 0));
@@ -121,21 +122,23 @@ __device__ __forceinline__ void qstore(const TileIOQ& io, int voff_rg, int soff,
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), io.rs, voff_rg + soff, 0, 0);
 }
 
-// ---- Dense-2 epilogue policies (same contract as the 16-column ones; tile index = row group) ----
+// ---- Dense-2 epilogue policies (same contract as the 16-column ones; tile index = first row rb of the 64-row group,
+// own = this lane's row quad belongs to the wave: below D, and not one of the 16 rows of the next wave's segment that a
+// wave's second group covers — those lanes compute a discarded value and write nothing) ----
 struct EpiStoreKQ {
   static constexpr int NPRE = 1;
   const ModelDev* m; float* kout; int b0, nvalid;
-  __device__ __forceinline__ void pre(int, f32x4 (&)[NPRE]) const {}
-  __device__ __forceinline__ void post(int rg, const f32x4& kv, f32x4 (&)[NPRE]) const {
+  __device__ __forceinline__ void pre(int, bool, f32x4 (&)[NPRE]) const {}
+  __device__ __forceinline__ void post(int rb, bool own, const f32x4& kv, f32x4 (&)[NPRE]) const {
     const int lane = threadIdx.x & 63, sidx = lane & 3, q = lane >> 2;
-    const int row0 = rg * 64 + q * 4;
-    if (sidx < nvalid && row0 < m->D) *reinterpret_cast<f32x4*>(kout + (size_t)(b0 + sidx) * m->D + row0) = kv;
+    const int row0 = rb + q * 4;
+    if (sidx < nvalid && own) *reinterpret_cast<f32x4*>(kout + (size_t)(b0 + sidx) * m->D + row0) = kv;
   }
 };
 
-// The stage operands (uprev, k1 .. k_{S-1}) of a workgroup's tile stay in LDS for the whole launch: kl[slot][rg*64+lane],
-// slot 0 = uprev, slot j = k_j.  The wave that owns row groups w and w+8 in Dense-2 is the one that wrote those quads
-// (the x2 tile load walks the tile in the same order), so no barrier orders these accesses.  Re-reading them from
+// The stage operands (uprev, k1 .. k_{S-1}) of a workgroup's tile stay in LDS for the whole launch: kl[slot][quad*4+sample],
+// slot 0 = uprev, slot j = k_j.  Slots 4.. are written and read only by the Dense-2 wave that owns the rows (the rows of its
+// Dense-1 segment); the preloaded pairs are ordered by the __syncthreads() ahead of the x2 pass.  Re-reading them from
 // global memory went through the same L2->L1 path as the weight stream (Dense-2 streamed at 36 B/clk against
 // Dense-1's 56); the k vectors are still stored to global memory for the next launch and the dense record.
 template <int S> struct EpiStageQ {
@@ -143,24 +146,25 @@ template <int S> struct EpiStageQ {
   TileIOQ io;
   int off_up, off_k[6], off_out, off_x;
   float dt;
-  f32x4* xl; int KQ1;
+  f32x4* xl;
   f32x4* kl; int KL;
   const f32x4* klu; const f32x4* klk;  // uprev / k1 of THIS step (one of the two preloaded candidate pairs, k_step_q)
   int store_k;  // Bcast::store_k: 0 = k_S stays in LDS (its global store gets an out-of-range offset and is dropped)
-  __device__ __forceinline__ void pre(int rg, f32x4 (&pb)[NPRE]) const {
-    const int li = rg * 64 + (threadIdx.x & 63);
+  // (lanes that are not `own` read another wave's quads or, in the last group, up to 15 quads past the slot — inside the
+  //  launch's slack: the value is discarded)
+  __device__ __forceinline__ void pre(int rb, bool, f32x4 (&pb)[NPRE]) const {
+    const int li = rb + (threadIdx.x & 63);
     pb[0] = klu[li];
     if (S > 1) pb[S > 1 ? 1 : 0] = klk[li];
 #pragma unroll
     for (int j = 2; j < S; ++j) pb[j] = kl[(size_t)(j + 2) * KL + li];
   }
-  __device__ __forceinline__ void post(int rg, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
+  __device__ __forceinline__ void post(int rb, bool own, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
     const int lane = threadIdx.x & 63, sidx = lane & 3, q = lane >> 2;
     constexpr int off = (S - 1) * S / 2;
-    const int vo = q_voff(io, rg);
+    const int vo = q_voff(io, rb, own);
     qstore(io, store_k ? vo : 0x7ffffff0, off_out, kv);
-    kl[(size_t)(S + 2) * KL + rg * 64 + lane] = kv;  // (row groups are padded to 64 quads: the last one spills into the next slot's head, which
-                                                     //  is written later — the slot order is the stage order, the two preloaded pairs come first)
+    if (own) kl[(size_t)(S + 2) * KL + rb + lane] = kv;
     f32x4 x;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -174,8 +178,7 @@ template <int S> struct EpiStageQ {
       x[r] = pb[0][r] + dt * sum;
     }
     if (off_x >= 0) qstore(io, vo, off_x, x);
-    const int kq = rg * 16 + q;
-    if (kq < KQ1) xl[kq * 4 + sidx] = x;  // one quad = the B operand of 4 Dense-1 k-steps
+    if (own) xl[(rb / 4 + q) * 4 + sidx] = x;  // one quad = the B operand of 4 Dense-1 k-steps, in this wave's own segment
   }
 };
 
@@ -191,18 +194,18 @@ struct EpiFinalQ {
   // dense record written by the step itself (StepArgs::dense_direct): descriptor over the slot [uprev,k1,P2,P3,P4] of this
   // attempt, voff out of range when there is none
   __amdgpu_buffer_rsrc_t rsD; int nstB; bool rec;
-  __device__ __forceinline__ void pre(int rg, f32x4 (&pb)[NPRE]) const {
-    const int li = rg * 64 + (threadIdx.x & 63);
+  __device__ __forceinline__ void pre(int rb, bool own, f32x4 (&pb)[NPRE]) const {
+    const int li = rb + (threadIdx.x & 63);
     pb[0] = klu[li];
     pb[1] = xl[li];
     pb[2] = klk[li];
 #pragma unroll
     for (int j = 1; j < 6; ++j) pb[2 + j] = kl[(size_t)(3 + j) * KL + li];
-    if (want_stiff) pb[8] = qload(io, q_voff(io, rg), off_g6);
+    if (want_stiff) pb[8] = qload(io, q_voff(io, rb, own), off_g6);
   }
-  __device__ __forceinline__ void post(int rg, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
-    const int lane = threadIdx.x & 63, sidx = lane & 3, q = lane >> 2;
-    const int vo = q_voff(io, rg);
+  __device__ __forceinline__ void post(int rb, bool own, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
+    const int lane = threadIdx.x & 63, sidx = lane & 3;
+    const int vo = q_voff(io, rb, own);
     qstore(io, vo, off_out, kv);
     if (rec) {
       // the attempt's record slot, straight from the operands this lane already holds: uprev (pb[0]), k1..k6 (pb[2..7]),
@@ -223,7 +226,7 @@ struct EpiFinalQ {
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, P3), rsD, vd + 3 * nstB, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, P4), rsD, vd + 4 * nstB, 0, 0);
     }
-    if (sidx >= nvalid || rg * 64 + q * 4 >= D) return;
+    if (sidx >= nvalid || !own) return;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float sum = (float)Tsit5::BT[0] * pb[2][r] + (float)Tsit5::BT[1] * pb[3][r];
@@ -248,8 +251,8 @@ struct EpiFinalQ {
 };
 
 // W1q: [RG1][KQ1p][64][4]   element (rg,kq,l,j) = W1[row 64rg+l][k 4kq+j],  KQ1p = 28 * nseg1
-// W2q: [RG2][KQ2p][64][4]   KQ2p = 28
-// Loads for row groups beyond RG1 / RG2, and lanes whose weight row is beyond the real matrix,
+// W2q: [2*nseg1][KQ2p][64][4]   KQ2p = 28; group 2w+c holds rows 112w + 64c + l (l < 48 when c = 1), zero elsewhere
+// Loads for row groups beyond RG1 / 2*nseg1, and lanes whose weight row is beyond the real matrix (or another wave's),
 // are outside the descriptor's range: they return 0 without touching memory.
 
 // ===========================================================================================
@@ -339,7 +342,7 @@ __device__ __forceinline__ void stream_init_q(const ModelDev& m, StreamQ& st) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int voff = lane * 16;
   st.rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)m.W1q, 0, m.RG1 * m.KQ1p * 1024, 0x00020000);
-  st.rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)m.W2q, 0, m.RG2 * m.KQ2p * 1024, 0x00020000);
+  st.rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)m.W2q, 0, q_w2_groups(m.KQ1p) * m.KQ2p * 1024, 0x00020000);
   const bool has1 = wave < q_nseg1(m);
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
@@ -349,9 +352,11 @@ __device__ __forceinline__ void stream_init_q(const ModelDev& m, StreamQ& st) {
     st.v1[c] = (has1 && c < m.RG1 && c * 64 + lane < m.H) ? voff : 0x7ffffff0;
 #endif
     st.s1[c] = (c * m.KQ1p + (has1 ? wave * QSEG : 0)) * 1024;
-    const int g = wave + c * QNW;
-    st.v2[c] = (g < m.RG2 && g * 64 + lane < m.D) ? voff : 0x7ffffff0;
-    st.s2[c] = (g < m.RG2 ? g : 0) * m.KQ2p * 1024;
+    // Dense-2: packed groups 2w, 2w+1 = rows 112w + 64c + lane (q_w2_row); the second group's last 16 rows are the next
+    // wave's, packed as zeros and out of range here as well
+    const int rb = wave * (QSEG * 4) + c * 64;
+    st.v2[c] = (has1 && (c == 0 || lane < QSEG * 4 - 64) && rb + lane < m.D) ? voff : 0x7ffffff0;
+    st.s2[c] = (has1 ? 2 * wave + c : 0) * m.KQ2p * 1024;
   }
   st.kq2_real = (m.H + 3) / 4;
   static_for<0, QAHEAD>([&](auto Bc) { constexpr int B = decltype(Bc)::value; q_stream_load<B, B>(st); });
@@ -448,11 +453,13 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
   STAMPW(2);
   q_barrier();
   STAMP(4); STAMPW(3);
-  // ---- Dense 2: stream blocks 7..13 (row groups wave and wave + QNW, one chain over K = H) ----
+  // ---- Dense 2: stream blocks 7..13 (the rows of the wave's Dense-1 segment as two 64-row groups, q_w2_groups; one
+  // chain over K = H) ----
   {
     const f32x4* hp = sm.hl + sidx;
     acc0 = zero4; acc1 = zero4;
-    const int g0 = wave, g1 = wave + QNW;
+    const int g0 = wave * (QSEG * 4), g1 = g0 + 64;  // first rows of the two groups
+    const bool own0 = g0 + q * 4 < m.D, own1 = q < (QSEG * 4 - 64) / 4 && g1 + q * 4 < m.D;
     f32x4 pb0[Epi::NPRE], pb1[Epi::NPRE];
     f32x4 bq[2][QSQ];
 #pragma unroll
@@ -464,8 +471,8 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
       q_stream_load<(QSB1 + B + QAHEAD) % QSB, NSL>(st);  // wraps into the next f-eval's Dense-1 blocks
 #endif
       if constexpr (B == QSB2 - 3) {  // epilogue operands: issued ~3 blocks before they are needed
-        if (g0 < m.RG2) epi.pre(g0, pb0);
-        if (g1 < m.RG2) epi.pre(g1, pb1);
+        if (g0 < m.D) epi.pre(g0, own0, pb0);
+        if (g1 < m.D) epi.pre(g1, own1, pb1);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (B + 1 < QSB2) {
@@ -490,8 +497,8 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
       });
       __builtin_amdgcn_sched_barrier(0);
     });
-    auto finish = [&](int rg, const f32x4& tot) {
-      const int row0 = rg * 64 + q * 4;
+    auto finish = [&](int rb, bool own, const f32x4& tot) {
+      const int row0 = own ? rb + q * 4 : 0;  // (other lanes' rows may lie past the bias vectors; their value is discarded)
       const f32x4 wt = *reinterpret_cast<const f32x4*>(w2t + row0);
       const f32x4 bb = *reinterpret_cast<const f32x4*>(b2 + row0);
       f32x4 kv;
@@ -502,11 +509,16 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
       }
       return kv;
     };
-    if (g0 < m.RG2) epi.post(g0, finish(g0, acc0), pb0);
-    if (g1 < m.RG2) epi.post(g1, finish(g1, acc1), pb1);
+    if (g0 < m.D) epi.post(g0, own0, finish(g0, own0, acc0), pb0);
+    if (g1 < m.D) epi.post(g1, own1, finish(g1, own1, acc1), pb1);
   }
   STAMP(5); STAMPW(4);
-  q_barrier();
+  // No workgroup barrier here: the x quads a wave has just written are its own Dense-1 segment, read next by the same
+  // wave, and a wavefront's LDS accesses are performed in program order — only the compiler must not move the next
+  // f-eval's reads above these stores.  Every other LDS region keeps its order through the two barriers inside the
+  // f-eval: h and the Dense-1 partials are rewritten only after every wave has passed the next barrier, i.e. after
+  // every wave's reads of them; the stage-operand slots are written and read by their owning wave only.
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   STAMP(6);
 }
 
@@ -823,7 +835,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     _Pragma("unroll") for (int qq = 0; qq < 5; ++qq) e.off_k[1 + qq] = arr_off(a, 4 + qq); \
     e.off_out = arr_off(a, 4 + (S - 2));                                                \
     e.off_x = (S == 6) ? o_un : ((S == 5 && a.want_stiff) ? o_g6 : -1);                 \
-    e.dt = dt; e.xl = s.xl; e.KQ1 = KQ1; e.kl = kl; e.KL = KL; e.klu = klu; e.klk = klk; e.store_k = bc.store_k;  \
+    e.dt = dt; e.xl = s.xl; e.kl = kl; e.KL = KL; e.klu = klu; e.klk = klk; e.store_k = bc.store_k;  \
     feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT>(a.m, s, fc, (TS), e);                 \
     STAMP(11 + S);                                                                      \
   } while (0)
@@ -884,10 +896,11 @@ __device__ __forceinline__ void bias_write_q(const ModelDev& m, const SmemQ& s, 
   }
 }
 
-// flat Lux parameter vector -> quad-tile A layouts (zero padded in k; row groups NOT padded)
-__global__ void k_pack_q(const float* p, int D, int H, int td, int KQ1p, int KQ2p, int RG1, int RG2,
+// flat Lux parameter vector -> quad-tile A layouts (zero padded in k; W1q row groups NOT padded; W2q in the groups of
+// q_w2_groups, G2 = 2 * nseg1 of them)
+__global__ void k_pack_q(const float* p, int D, int H, int td, int KQ1p, int KQ2p, int RG1, int G2,
                          float* W1q, float* W2q) {
-  const size_t n1 = (size_t)RG1 * KQ1p * 256, n2 = (size_t)RG2 * KQ2p * 256;
+  const size_t n1 = (size_t)RG1 * KQ1p * 256, n2 = (size_t)G2 * KQ2p * 256;
   const size_t base2 = (size_t)H * (D + td) + H;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n1 + n2; i += (size_t)gridDim.x * blockDim.x) {
     if (i < n1) {
@@ -900,9 +913,10 @@ __global__ void k_pack_q(const float* p, int D, int H, int td, int KQ1p, int KQ2
       const size_t e = i - n1;
       const int jj = e & 3, l = (e >> 2) & 63;
       const size_t blk = e >> 8;
-      const int kq = blk % KQ2p, rg = blk / KQ2p;
-      const int o = rg * 64 + l, k = kq * 4 + jj;
-      W2q[e] = (o < D && k < H) ? p[base2 + (size_t)o + (size_t)D * k] : 0.f;
+      const int kq = blk % KQ2p, g = blk / KQ2p;
+      const int c = g & 1, o = (g >> 1) * (QSEG * 4) + c * 64 + l, k = kq * 4 + jj;
+      const bool mine = c == 0 || l < QSEG * 4 - 64;  // the second group's last 16 rows belong to the next wave
+      W2q[e] = (mine && o < D && k < H) ? p[base2 + (size_t)o + (size_t)D * k] : 0.f;
     }
   }
 }
