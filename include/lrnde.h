@@ -91,6 +91,39 @@ const char* lrnde_last_error(const lrnde_ctx* ctx);
 size_t lrnde_param_count(const lrnde_model_desc* desc);
 const char* lrnde_version(void);
 
+/* Small Dense-chain vector field: any `Chain` / `TDChain` of `Dense` layers, optionally led by an input activation
+ * `Base.Fix1(broadcast, act)` / `WrappedFunction` (the PhysioNet latent ODE's gen_dynamics,
+ * experiments/src/construct.jl:236-244: Chain(tanh.(u), Dense(20=>40, tanh), Dense(40=>20, tanh), ...)).
+ *   nlayers    1..LRNDE_CHAIN_MAX_LAYERS Dense layers;
+ *   time_dep   1: TDChain, t is appended as the last input row of EVERY Dense;
+ *   input_act  LRNDE_ACT_* applied to u before the first Dense (identity: none);
+ *   dims       the state widths, dims[0] == dims[nlayers] == D, every entry <= LRNDE_CHAIN_MAX_WIDTH
+ *              (the input of a TDChain layer is dims[l] + 1);
+ *   act        LRNDE_ACT_* after each Dense (the output layer may have one too).
+ * Parameters: the flat Lux ComponentArray in layer order, per layer vec(W) (out x (in+td), column-major, the t column
+ * last) followed by b.  The input activation has none.
+ * Limits (checked by lrnde_create_chain, LRNDE_UNSUPPORTED with a message from lrnde_last_error(NULL)): the widths above
+ * and the forward weight image, sum over layers of (in + td + 1) * (out rounded up to even) fp32 (rounded up to a
+ * multiple of 4), at most LRNDE_CHAIN_MAX_WEIGHT_BYTES: the step kernel keeps it in LDS for the whole launch.
+ * lrnde_chain_param_count applies no limits (0 for a malformed desc).
+ * A chain handle is accepted by lrnde_set_params, lrnde_rhs, lrnde_init_dt, lrnde_perform_step, lrnde_solve,
+ * lrnde_node_forward, lrnde_vjp, lrnde_step_reg_grad, lrnde_node_forward_record(_ts), lrnde_node_backward_recorded(_ts),
+ * lrnde_node_backward, lrnde_record_generation and lrnde_destroy.  It is refused with LRNDE_UNSUPPORTED by the
+ * communicator entry points (lrnde_comm_init, lrnde_comm_init_local: chain handles are one rank), by lrnde_set_solver
+ * with VCAB3 / VCABM3 (Tsit5 only), and by the hooks lrnde_set_overlap, lrnde_bench_step and lrnde_bench_exchange. */
+#define LRNDE_CHAIN_MAX_LAYERS 16
+#define LRNDE_CHAIN_MAX_WIDTH 128
+#define LRNDE_CHAIN_MAX_WEIGHT_BYTES (128 * 1024)
+typedef struct {
+  int32_t nlayers;
+  int32_t time_dep;
+  int32_t input_act;
+  int32_t dims[LRNDE_CHAIN_MAX_LAYERS + 1];
+  int32_t act[LRNDE_CHAIN_MAX_LAYERS];
+} lrnde_chain_desc;   /* 144 bytes */
+int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* desc, int device, void* stream);
+size_t lrnde_chain_param_count(const lrnde_chain_desc* desc);
+
 /* Hands the flat parameter vector `ps` (what ODEProblem(dudt, x, tspan, ps)
  * carries, src/layers/neural_ode.jl:50) to the library; repacked on device
  * into the MFMA operand layout.  Call again whenever ps changes. */

@@ -72,6 +72,27 @@ function create(D, H, time_dep::Bool, act::Int32; device=0, stream=C_NULL)
     return ctx[]
 end
 destroy(ctx) = ccall((:lrnde_destroy, lib), Cint, (Ptr{Cvoid},), ctx)
+
+# ---- small Dense-chain field (lrnde_chain_desc): Chain / TDChain of Dense layers, optionally led by act.(u) ----
+# (the PhysioNet latent ODE's gen_dynamics, experiments/src/construct.jl:236-244; limits in include/lrnde.h)
+const CHAIN_MAX_LAYERS = 16
+struct ChainDesc
+    nlayers::Int32; time_dep::Int32; input_act::Int32
+    dims::NTuple{17, Int32}
+    act::NTuple{16, Int32}
+end
+function ChainDesc(dims::Vector{Int}, acts::Vector{Int32}, time_dep::Bool, input_act::Int32)
+    L = length(acts)
+    ChainDesc(Int32(L), Int32(time_dep), input_act, ntuple(i -> i <= L + 1 ? Int32(dims[i]) : Int32(0), 17),
+              ntuple(i -> i <= L ? acts[i] : Int32(0), 16))
+end
+function create_chain(desc::ChainDesc; device=0, stream=C_NULL)
+    ctx = Ref{Ptr{Cvoid}}()
+    rc = ccall((:lrnde_create_chain, lib), Cint, (Ptr{Ptr{Cvoid}}, Ref{ChainDesc}, Cint, Ptr{Cvoid}), ctx, desc, device, stream)
+    rc == 0 || error("lrnde_create_chain: status $rc: " * unsafe_string(ccall((:lrnde_last_error, lib), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return ctx[]
+end
+chain_param_count(desc::ChainDesc) = ccall((:lrnde_chain_param_count, lib), Csize_t, (Ref{ChainDesc},), desc)
 set_params!(ctx, ps) = check(ctx, ccall((:lrnde_set_params, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t),
                                         ctx, pointer(ps), length(ps)))
 

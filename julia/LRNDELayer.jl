@@ -60,6 +60,30 @@ function lrnde_field_shape(model)
     return (D, H, td, _LRNDE_ACT[l1.activation])
 end
 
+"lrnde_chain_desc of any other Chain / TDChain of Dense layers (a plain Chain may open with `Base.Fix1(broadcast, act)` /
+`WrappedFunction`), or nothing: the Dense-chain handle (lrnde_create_chain), Tsit5 only"
+function lrnde_chain_shape(model)
+    layers = model isa TDChain ? collect(values(model.layers)) : (model isa Lux.Chain ? collect(values(model.layers)) : nothing)
+    layers === nothing && return nothing
+    td = model isa TDChain
+    in_act = Int32(0)
+    if !td && !isempty(layers) && !(first(layers) isa Lux.Dense)
+        l0 = first(layers)
+        f = l0 isa Lux.WrappedFunction ? l0.func : l0
+        f isa Base.Fix1 && f.f === broadcast && haskey(_LRNDE_ACT, f.x) || return nothing
+        in_act = _LRNDE_ACT[f.x]
+        layers = layers[2:end]
+    end
+    (1 <= length(layers) <= LRNDEBackend.CHAIN_MAX_LAYERS && all(l -> l isa Lux.Dense && l.use_bias, layers)) || return nothing
+    dims = [first(layers).in_dims - td]
+    for l in layers
+        (l.in_dims == dims[end] + td && haskey(_LRNDE_ACT, l.activation)) || return nothing
+        push!(dims, l.out_dims)
+    end
+    (dims[end] == dims[1] && maximum(dims) <= 128) || return nothing
+    return LRNDEBackend.ChainDesc(dims, Int32[_LRNDE_ACT[l.activation] for l in layers], td, in_act)
+end
+
 const _lrnde_handles = IdDict{Any, Ptr{Cvoid}}()   # one handle per layer object (one task, one stream: SURVEY.md §8b)
 # n.solver -> lrnde_set_solver's code: the three choices of experiments/src/construct.jl:154-164 (`_ode_solver`)
 _lrnde_alg(solver) = solver isa Tsit5 ? Int32(0) : nameof(typeof(solver)) === :VCAB3 ? Int32(1) :
@@ -67,6 +91,9 @@ _lrnde_alg(solver) = solver isa Tsit5 ? Int32(0) : nameof(typeof(solver)) === :V
 
 function lrnde_handle(n::NeuralODE)
     get!(_lrnde_handles, n) do
+        if lrnde_field_shape(n.model) === nothing   # any other Dense chain: the Dense-chain handle (Tsit5 only)
+            return LRNDEBackend.create_chain(lrnde_chain_shape(n.model))
+        end
         D, H, td, act = lrnde_field_shape(n.model)
         ctx = LRNDEBackend.create(D, H, td, act)
         LRNDEBackend.set_solver!(ctx, _lrnde_alg(n.solver))   # the global solve's method; the local step stays Tsit5 (:75, :93)
@@ -74,7 +101,9 @@ function lrnde_handle(n::NeuralODE)
     end
 end
 
-lrnde_supported(n::NeuralODE, x) = _lrnde_alg(n.solver) !== nothing && lrnde_field_shape(n.model) !== nothing &&
+lrnde_supported(n::NeuralODE, x) = _lrnde_alg(n.solver) !== nothing &&
+                                   (lrnde_field_shape(n.model) !== nothing ||
+                                    (_lrnde_alg(n.solver) == 0 && lrnde_chain_shape(n.model) !== nothing)) &&
                                    nameof(typeof(x)) === :ROCArray && eltype(x) === Float32
 
 _lrnde_opts(n::NeuralODE) = SolveOpts(Float32(get(n.kwargs, :abstol, 1f-6)), Float32(get(n.kwargs, :reltol, 1f-3)),

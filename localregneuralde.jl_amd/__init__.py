@@ -6,9 +6,9 @@ src/layers/common.jl:2-45; diffeqsol_to_array / diffeqsol_to_timeseries —
 src/utils.jl:37-46.  PyTorch is used only for device memory and streams.
 """
 from ._lib import LIB_PATH, LrndeError, set_option  # noqa: F401  (raises if liblrnde.so is missing)
-from .layers import (Chain, Dense, Handle, NeuralODE, ODESolution, TDChain,  # noqa: F401
-                     diffeqsol_to_array, diffeqsol_to_timeseries, flatten_params,
-                     glorot_params)
+from .layers import (Activation, Chain, Dense, Handle, NeuralODE, ODESolution, TDChain,  # noqa: F401
+                     diffeqsol_to_array, diffeqsol_to_timeseries, flatten_chain_params, flatten_params,
+                     glorot_chain_params, glorot_params)
 from .sde import NeuralDSDE, SdeHandle  # noqa: F401
 from .conv import BatchNorm, Conv, ConvHandle, glorot_conv_params  # noqa: F401
 from .training import run_cifar_training_step, run_training_step  # noqa: F401

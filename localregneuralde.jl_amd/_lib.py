@@ -19,6 +19,21 @@ class ModelDesc(C.Structure):
                 ("act", C.c_int32)]
 
 
+CHAIN_MAX_LAYERS, CHAIN_MAX_WIDTH, CHAIN_MAX_WEIGHT_BYTES = 16, 128, 128 * 1024   # include/lrnde.h LRNDE_CHAIN_*
+
+
+class ChainDesc(C.Structure):
+    """lrnde_chain_desc: nlayers, time_dep, input_act, dims[nlayers+1], act[nlayers] (fixed-size arrays)"""
+    _fields_ = [("nlayers", C.c_int32), ("time_dep", C.c_int32), ("input_act", C.c_int32),
+                ("dims", C.c_int32 * (CHAIN_MAX_LAYERS + 1)), ("act", C.c_int32 * CHAIN_MAX_LAYERS)]
+
+
+def chain_weight_image_bytes(dims, time_dep):
+    """bytes of the forward weight image the chain step kernel keeps in LDS (include/lrnde.h, lrnde_create_chain)"""
+    n = sum((dims[l] + int(time_dep) + 1) * (dims[l + 1] + dims[l + 1] % 2) for l in range(len(dims) - 1))
+    return 4 * ((n + 3) // 4 * 4)
+
+
 SRI_FIELDS = ("a021 a031 a032 a041 a042 a043 a121 a131 a132 a141 a142 a143 "
               "b021 b031 b032 b041 b042 b043 b121 b131 b132 b141 b142 b143 "
               "c02 c03 c04 c11 c12 c13 c14 alpha1 alpha2 alpha3 alpha4 "
@@ -66,6 +81,8 @@ SYMBOLS = [
     ("lrnde_destroy", C.c_int, [_vp]),
     ("lrnde_last_error", C.c_char_p, [_vp]),
     ("lrnde_param_count", C.c_size_t, [C.POINTER(ModelDesc)]),
+    ("lrnde_create_chain", C.c_int, [C.POINTER(_vp), C.POINTER(ChainDesc), C.c_int, _vp]),
+    ("lrnde_chain_param_count", C.c_size_t, [C.POINTER(ChainDesc)]),
     ("lrnde_version", C.c_char_p, []),
     ("lrnde_set_params", C.c_int, [_vp, _vp, C.c_size_t]),
     ("lrnde_set_solver", C.c_int, [_vp, _i32]),

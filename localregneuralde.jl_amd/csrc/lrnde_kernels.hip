@@ -1660,6 +1660,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 #include "lrnde_qtile.hpp"
 #include "lrnde_adjoint.hpp"
 #include "lrnde_backward.hpp"
+#include "lrnde_chain.hpp"
 
 // single-step modes: EEst and the two regularisation values from the partial sums
 __global__ void k_finalize(StepArgs a, int j) {
@@ -1869,6 +1870,15 @@ struct lrnde_ctx {
   std::function<int()> final_hook;
   bool final_hook_fired = false, last_u_end_done = false;
   bool adj_stage7_reused = false;   // the last stage-7 launch of the adjoint loop took y / h from stage 6's scratch set (its GEMM must too)
+  // field kind: 0 the two-layer MLP (lrnde_create), 1 the small Dense chain (lrnde_create_chain, lrnde_chain.hpp).  A
+  // chain handle keeps desc.state_dim = D (every state-sized buffer) and its own layer table / weight images here.
+  int field = 0;
+  lrnde_chain_desc chain{};
+  ChainDev cd{};
+  int* ch_meta = nullptr; float *ch_wf = nullptr, *ch_wg = nullptr;  // layer table, forward / backward weight images
+  int ch_gfloats = 0;
+  size_t ch_vjp_lds = 0;                                             // dynamic LDS of k_vjp_chain
+  float* ch_part = nullptr; size_t ch_part_n = 0;                    // per-workgroup parameter cotangents of k_vjp_chain
   int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp)
   bool hung = false;         // a host loop waited LRNDE_SPIN_DEADLINE_S for a report while the queue stayed busy: only lrnde_destroy is safe
   bool reports_off = false;  // lrnde_set_reports(ctx, 0): the solve loop polls by copies (its fall-back when no report arrives)
@@ -1986,6 +1996,7 @@ inline int vecw(const lrnde_ctx* c) { return (c->desc.state_dim % 4 == 0) ? 4 : 
 // Which tile shape runs this batch: the 4-column family (lrnde_qtile.hpp) when there would be too
 // few 16-column workgroups to fill the chip, the 16-column family otherwise.
 bool use_qtile(const lrnde_ctx* c, int B) {
+  if (c->field) return false;  // a chain handle has its own kernels (lrnde_chain.hpp)
   const int qmax = opt(OPT_QTILE_MAX_B);  // two rounds of 4-column workgroups (97 us at B=2048) beat one of 16-column ones (114 us)
   const int D = c->desc.state_dim, H = c->desc.hidden_dim;
   // streaming path shape limits: one Dense-1 segment and one Dense-2 pass per wave
@@ -1994,7 +2005,11 @@ bool use_qtile(const lrnde_ctx* c, int B) {
   const bool no_qtile = opt(OPT_NO_QTILE) != 0;
   return shape_ok && ((double)B * D * 40.0 < 2147483000.0) && B <= qmax && !no_qtile;
 }
-inline int tile_nb(const lrnde_ctx* c, int B) { return use_qtile(c, B) ? QNB : NB; }
+inline int tile_nb(const lrnde_ctx* c, int B) { return c->field ? CNB : (use_qtile(c, B) ? QNB : NB); }
+// parameters of the handle's field (the flat Lux vector)
+size_t param_count(const lrnde_ctx* c) {
+  return c->field ? lrnde_chain_param_count(&c->chain) : lrnde_param_count(&c->desc);
+}
 
 int ensure_workspace(lrnde_ctx* c, int B) {
   const size_t n = (size_t)B * c->desc.state_dim;
@@ -2075,6 +2090,14 @@ template <class K> int launch_tile_kernel(lrnde_ctx* c, K kern, int B, const Ste
 }
 
 int launch_step(lrnde_ctx* c, int B, const StepArgs& a, int j, bool spec = false) {
+  if (c->field) {
+    const int nwg = (B + CNB - 1) / CNB;
+    const size_t sm = chain_smem_bytes(c->cd.wfloats);
+    if (spec) hipLaunchKernelGGL(k_step_chain<true>, dim3(nwg), dim3(NT), sm, c->stream, a, c->cd, j);
+    else hipLaunchKernelGGL(k_step_chain<false>, dim3(nwg), dim3(NT), sm, c->stream, a, c->cd, j);
+    HIPCHK(c, hipGetLastError());
+    return LRNDE_OK;
+  }
   if (use_qtile(c, B)) {
     const int nq = (B + QNB - 1) / QNB;
     const size_t smq = smem_q(c) + (size_t)9 * c->m.KQ1p * 4 * 16 + 64 * 16 + 16;  // + the LDS-resident stage operands (both candidate (uprev, k1) pairs, k2..k6; one padded row group of slack)
@@ -2115,6 +2138,16 @@ int run_init(lrnde_ctx* c, int B, const StepArgs& a) {
   const size_t cnt = (size_t)a.nwg_global * PSTRIDE;
   const bool qt = use_qtile(c, B);
   const int nq = (B + QNB - 1) / QNB;
+  if (c->field) {
+    const int nwg = (B + CNB - 1) / CNB;
+    const size_t sm = chain_smem_bytes(c->cd.wfloats);
+    hipLaunchKernelGGL(k_init1_chain, dim3(nwg), dim3(NT), sm, c->stream, a, c->cd);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = exchange(c, c->pinit, c->pinit_rx, cnt))) return rc;
+    hipLaunchKernelGGL(k_init2_chain, dim3(nwg), dim3(NT), sm, c->stream, a, c->cd);
+    HIPCHK(c, hipGetLastError());
+    return exchange(c, c->pinit + cnt, c->pinit_rx + cnt, cnt);
+  }
   if (qt) { hipLaunchKernelGGL(k_init1_q, dim3(nq), dim3(QNT), smem_q(c), c->stream, a); rc = LRNDE_OK; HIPCHK(c, hipGetLastError()); }
   else if (vecw(c) == 4) rc = launch_tile_kernel(c, k_init1<4>, B, a);
   else rc = launch_tile_kernel(c, k_init1<1>, B, a);
@@ -2154,6 +2187,12 @@ int set_smem_attr() {
   hipFuncSetAttribute((const void*)k_sde_step<1>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_sde_rkmil<4>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_sde_rkmil<1>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_step_chain<false>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_step_chain<true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_init1_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_init2_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_rhs_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_vjp_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   done = true;
   return 0;
 }
@@ -2193,6 +2232,8 @@ int side_get(lrnde_ctx* c, int B, lrnde_ctx** out) {
   s->desc = c->desc; s->m = c->m; s->have_params = c->have_params;
   s->W1p = c->W1p; s->W2p = c->W2p; s->w1t = c->w1t; s->b1 = c->b1; s->w2t = c->w2t; s->b2 = c->b2;
   s->W1q = c->W1q; s->W2q = c->W2q; s->V1p = c->V1p; s->U2p = c->U2p; s->V1q = c->V1q; s->U2q = c->U2q;
+  s->field = c->field; s->chain = c->chain; s->cd = c->cd; s->ch_meta = c->ch_meta; s->ch_wf = c->ch_wf; s->ch_wg = c->ch_wg;
+  s->ch_gfloats = c->ch_gfloats; s->ch_vjp_lds = c->ch_vjp_lds;
   const int rc = ensure_workspace(s, B);
   if (rc) { c->err = s->err; return rc; }
   *out = s;
@@ -2224,7 +2265,12 @@ size_t lrnde_param_count(const lrnde_model_desc* d) {
   return H * (D + td) + H + D * (H + td) + D;
 }
 
-const char* lrnde_last_error(const lrnde_ctx* c) { return c ? c->err.c_str() : "null context"; }
+// (a failed lrnde_create_chain has no handle to carry its message: lrnde_last_error(NULL) returns it, per thread)
+static thread_local std::string g_create_err;
+const char* lrnde_last_error(const lrnde_ctx* c) {
+  if (c) return c->err.c_str();
+  return g_create_err.empty() ? "null context" : g_create_err.c_str();
+}
 
 int lrnde_create(lrnde_ctx** out, const lrnde_model_desc* d, int device, void* stream) {
   if (!out || !d) return LRNDE_BADARG;
@@ -2275,6 +2321,100 @@ int lrnde_create(lrnde_ctx** out, const lrnde_model_desc* d, int device, void* s
   return LRNDE_OK;
 }
 
+size_t lrnde_chain_param_count(const lrnde_chain_desc* d) {
+  if (!d || d->nlayers < 1 || d->nlayers > LRNDE_CHAIN_MAX_LAYERS) return 0;
+  const size_t td = d->time_dep ? 1 : 0;
+  size_t n = 0;
+  for (int l = 0; l < d->nlayers; ++l) {
+    if (d->dims[l] <= 0 || d->dims[l + 1] <= 0) return 0;
+    n += (size_t)d->dims[l + 1] * ((size_t)d->dims[l] + td) + (size_t)d->dims[l + 1];
+  }
+  return n;
+}
+
+static int chain_refuse(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_create_err = buf;
+  return code;
+}
+
+int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int device, void* stream) {
+  if (!out || !d) return chain_refuse(LRNDE_BADARG, "null pointer");
+  *out = nullptr;
+  g_create_err.clear();
+  const int L = d->nlayers;
+  if (L < 1 || L > LRNDE_CHAIN_MAX_LAYERS)
+    return chain_refuse(LRNDE_UNSUPPORTED, "nlayers = %d: a Dense chain has 1..%d layers", L, LRNDE_CHAIN_MAX_LAYERS);
+  if (d->time_dep != 0 && d->time_dep != 1) return chain_refuse(LRNDE_BADARG, "time_dep must be 0 or 1");
+  if (d->input_act < 0 || d->input_act > 2) return chain_refuse(LRNDE_BADARG, "input_act must be identity, tanh or gelu");
+  if (d->dims[0] != d->dims[L])
+    return chain_refuse(LRNDE_BADARG, "dims[0] = %d != dims[nlayers] = %d: the field must map the state onto itself", d->dims[0], d->dims[L]);
+  for (int l = 0; l <= L; ++l) {
+    if (d->dims[l] <= 0) return chain_refuse(LRNDE_BADARG, "dims[%d] = %d must be positive", l, d->dims[l]);
+    if (d->dims[l] > LRNDE_CHAIN_MAX_WIDTH)
+      return chain_refuse(LRNDE_UNSUPPORTED, "dims[%d] = %d exceeds the chain kernels' width limit of %d (+1 for the t row)", l, d->dims[l],
+                          LRNDE_CHAIN_MAX_WIDTH);
+  }
+  for (int l = 0; l < L; ++l)
+    if (d->act[l] < 0 || d->act[l] > 2) return chain_refuse(LRNDE_BADARG, "act[%d] must be identity, tanh or gelu", l);
+  const int td = d->time_dep;
+  // the layer table and the two weight images (lrnde_chain.hpp); the forward image must fit LDS for the whole launch
+  std::vector<int> meta((size_t)L * CMETA, 0);
+  size_t wf = 0, wg = 0, poff = 0, aoff = 0, zsum = 0;
+  for (int l = 0; l < L; ++l) {
+    const int in = d->dims[l], o = d->dims[l + 1], outp = (o + 1) & ~1;
+    int* m = meta.data() + (size_t)l * CMETA;
+    m[CM_IN] = in; m[CM_OUT] = o; m[CM_OUTP] = outp; m[CM_ACT] = d->act[l];
+    m[CM_WOFF] = (int)wf; m[CM_GOFF] = (int)wg; m[CM_POFF] = (int)poff; m[CM_AOFF] = (int)aoff;
+    wf += (size_t)(in + td + 1) * outp; wg += (size_t)in * o; poff += (size_t)o * (in + td) + o; aoff += (size_t)in * CNB;
+    zsum += (size_t)o * CNB;
+  }
+  wf = (wf + 3) & ~(size_t)3;
+  if (wf * sizeof(float) > LRNDE_CHAIN_MAX_WEIGHT_BYTES)
+    return chain_refuse(LRNDE_UNSUPPORTED, "weight image of %zu bytes exceeds the %d bytes the chain kernels keep in LDS", wf * sizeof(float),
+                        LRNDE_CHAIN_MAX_WEIGHT_BYTES);
+  size_t zoff = aoff;
+  for (int l = 0; l < L; ++l) { meta[(size_t)l * CMETA + CM_ZOFF] = (int)zoff; zoff += (size_t)d->dims[l + 1] * CNB; }
+  const size_t uoff = zoff, gboff = uoff + (size_t)d->dims[0] * CNB;
+  const size_t vjp_lds = (gboff + 2 * (size_t)CMAXW * CNB) * sizeof(float);
+  if (vjp_lds > 160 * 1024) return chain_refuse(LRNDE_UNSUPPORTED, "the VJP's activation record (%zu bytes) does not fit LDS", vjp_lds);
+  (void)zsum;
+  lrnde_ctx* c = new lrnde_ctx();
+  c->device = device;
+  c->stream = (hipStream_t)stream;
+  c->field = 1;
+  c->chain = *d;
+  int maxw = 0;
+  for (int l = 0; l <= L; ++l) maxw = std::max(maxw, d->dims[l]);
+  // (desc: D for every state-sized buffer; hidden_dim = the widest layer, only ever used to size scratch)
+  c->desc.state_dim = d->dims[0]; c->desc.hidden_dim = maxw; c->desc.time_dep = td; c->desc.act = d->act[0];
+  ModelDev& m = c->m;
+  m.D = d->dims[0]; m.H = maxw; m.Dp = ceil16(m.D); m.Hp = ceil16(maxw); m.td = td; m.act = d->act[0];
+  m.MT1 = m.Hp / 16; m.KG1 = m.Dp / 16; m.MT2 = m.Dp / 16; m.KG2 = m.Hp / 16;
+  if (hipSetDevice(device) != hipSuccess) { delete c; return chain_refuse(LRNDE_HIP_ERROR, "hipSetDevice(%d) failed", device); }
+  set_smem_attr();
+  c->ch_gfloats = (int)wg;
+  c->ch_vjp_lds = vjp_lds;
+  bool ok = hipMalloc(&c->ch_meta, sizeof(int) * meta.size()) == hipSuccess &&
+            hipMalloc(&c->ch_wf, sizeof(float) * wf) == hipSuccess &&
+            hipMalloc(&c->ch_wg, sizeof(float) * (wg > 0 ? wg : 1)) == hipSuccess &&
+            hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
+            hipEventCreate(&c->evp[0]) == hipSuccess && hipEventCreate(&c->evp[1]) == hipSuccess;
+  ok = ok && hipMemcpy(c->ch_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) { lrnde_destroy(c); return chain_refuse(LRNDE_HIP_ERROR, "device allocation failed"); }
+  ChainDev& cd = c->cd;
+  cd.L = L; cd.td = td; cd.in_act = d->input_act; cd.D = d->dims[0];
+  cd.wfloats = (int)wf; cd.P = (int)lrnde_chain_param_count(d);
+  cd.uoff = (int)uoff; cd.gboff = (int)gboff;
+  cd.meta = c->ch_meta; cd.wf = c->ch_wf; cd.wg = c->ch_wg;
+  *out = c;
+  return LRNDE_OK;
+}
+
 int lrnde_destroy(lrnde_ctx* c) {
   if (!c) return LRNDE_OK;
   hipSetDevice(c->device);
@@ -2284,6 +2424,7 @@ int lrnde_destroy(lrnde_ctx* c) {
     hipStream_t ss = s->stream;
     hipStreamSynchronize(ss);
     s->W1p = s->W2p = s->w1t = s->b1 = s->w2t = s->b2 = s->W1q = s->W2q = s->V1p = s->U2p = s->V1q = s->U2q = nullptr;
+    s->ch_wf = s->ch_wg = nullptr; s->ch_meta = nullptr;
     lrnde_destroy(s);
     hipStreamDestroy(ss);
     if (c->ev_side_local) hipEventDestroy(c->ev_side_local);
@@ -2294,7 +2435,7 @@ int lrnde_destroy(lrnde_ctx* c) {
   if (c->adj_part_host) hipHostFree(c->adj_part_host);
   void* ptrs[] = {c->dense, c->dense_t, c->dense_dt, c->adj, c->adj_part, c->V1p, c->U2p, c->V1q, c->U2q, c->bw_y, c->bw_h, c->bw_dp, c->bw_da, c->W1q, c->W2q, c->W1p, c->W2p, c->w1t, c->b1, c->w2t, c->b2, c->state, c->ctrl, c->part,
                   c->part_rx, c->pinit, c->pinit_rx, c->arrive, c->tile_part, c->tile_pinit, c->rec_gr, c->saveat_dev, c->trace_dev,
-                  c->usave};
+                  c->usave, c->ch_meta, c->ch_wf, c->ch_wg, c->ch_part};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->ctrl_host) hipHostFree(c->ctrl_host);
   if (c->tsaved_host) hipHostFree(c->tsaved_host);
@@ -2322,11 +2463,17 @@ int lrnde_destroy(lrnde_ctx* c) {
 
 int lrnde_set_params(lrnde_ctx* c, const float* p, size_t n) {
   if (!c || !p) return LRNDE_BADARG;
-  if (n != lrnde_param_count(&c->desc))
-    return fail(c, LRNDE_BADARG, "parameter count %zu != expected %zu", n, lrnde_param_count(&c->desc));
+  if (n != param_count(c))
+    return fail(c, LRNDE_BADARG, "parameter count %zu != expected %zu", n, param_count(c));
   HIPCHK(c, hipSetDevice(c->device));
   { const int rq = side_quiesce(c); if (rq) return rq; }
   c->rec_gr_ready = false; c->sweep_pending = false;
+  if (c->field) {
+    hipLaunchKernelGGL(k_pack_chain, dim3(128), dim3(256), 0, c->stream, p, c->cd, c->ch_gfloats, c->ch_wf, c->ch_wg);
+    HIPCHK(c, hipGetLastError());
+    c->have_params = true;
+    return LRNDE_OK;
+  }
   const ModelDev& m = c->m;
   hipLaunchKernelGGL(k_pack, dim3(256), dim3(256), 0, c->stream, p, m.D, m.H, m.td, m.Dp, m.Hp, c->W1p,
                      c->w1t, c->b1, c->W2p, c->w2t, c->b2);
@@ -2344,6 +2491,7 @@ int lrnde_set_params(lrnde_ctx* c, const float* p, size_t n) {
 int lrnde_set_solver(lrnde_ctx* c, int32_t alg) {
   if (!c) return LRNDE_BADARG;
   if (alg < 0 || alg > 2) return fail(c, LRNDE_BADARG, "solver must be 0 (Tsit5), 1 (VCAB3) or 2 (VCABM3)");
+  if (c->field && alg != 0) return fail(c, LRNDE_UNSUPPORTED, "VCAB3 / VCABM3 are built for the MLP field's handle: a Dense-chain handle solves with Tsit5 only");
   c->solver_alg = alg;
   c->rec_valid = false;
   return LRNDE_OK;
@@ -2353,6 +2501,11 @@ int lrnde_rhs(lrnde_ctx* c, const float* u, float t, int32_t B, float* du) {
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!u || !du) return fail(c, LRNDE_BADARG, "null state pointer");
+  if (c->field) {
+    hipLaunchKernelGGL(k_rhs_chain, dim3((B + CNB - 1) / CNB), dim3(NT), chain_smem_bytes(c->cd.wfloats), c->stream, c->cd, B, u, t, du);
+    HIPCHK(c, hipGetLastError());
+    return LRNDE_OK;
+  }
   StepArgs a{};
   memset(&a, 0, sizeof(a));
   a.m = c->m; a.B = B;
@@ -2912,6 +3065,7 @@ int lrnde_comm_unique_id(void* out) {
 }
 
 int lrnde_comm_init(lrnde_ctx* c, const void* uid, int32_t rank, int32_t nranks) {
+  if (c && c->field) return fail(c, LRNDE_UNSUPPORTED, "a Dense-chain handle is not sharded: its kernels run one rank");
   if (!c || !uid || nranks < 1 || rank < 0 || rank >= nranks) return LRNDE_BADARG;
   HIPCHK(c, hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
@@ -2952,6 +3106,7 @@ int lrnde_comm_count(lrnde_ctx* c, int32_t* nranks_host, int32_t* kind_host) {
 // same buffers and count as inside a solve of batch B) between two HIP events on the handle's stream -> microseconds per
 // exchange.  Collective: every rank must call it.  An unsharded handle reports 0.
 int lrnde_bench_exchange(lrnde_ctx* c, int32_t B, int32_t reps, float* avg_us_host) {
+  if (c && c->field) return fail(c, LRNDE_UNSUPPORTED, "bench hooks are built for the MLP field's handle");
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (reps < 1 || !avg_us_host) return fail(c, LRNDE_BADARG, "bad bench arguments");
@@ -3000,6 +3155,7 @@ int lrnde_local_comm_destroy(lrnde_local_comm* lc) {
 }
 
 int lrnde_comm_init_local(lrnde_ctx* c, lrnde_local_comm* lc, int32_t rank) {
+  if (c && c->field) return fail(c, LRNDE_UNSUPPORTED, "a Dense-chain handle is not sharded: its kernels run one rank");
   if (!c || !lc || rank < 0 || rank >= lc->n) return LRNDE_BADARG;
   HIPCHK(c, hipSetDevice(c->device));
   if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
@@ -3024,6 +3180,7 @@ int lrnde_comm_init_local(lrnde_ctx* c, lrnde_local_comm* lc, int32_t rank) {
 
 int lrnde_set_overlap(lrnde_ctx* c, int32_t on) {
   if (!c) return LRNDE_BADARG;
+  if (c->field) return fail(c, LRNDE_UNSUPPORTED, "the overlap switch is a diagnostic of the MLP field's handle");
   const int rc = side_quiesce(c);
   if (rc) return rc;
   c->overlap_off = !on;
@@ -3032,6 +3189,7 @@ int lrnde_set_overlap(lrnde_ctx* c, int32_t on) {
 
 int lrnde_bench_step(lrnde_ctx* c, const float* uprev, const float* k1, int32_t B, float t, float dt,
                      float abstol, float reltol, int32_t reps, float* avg_us_host) {
+  if (c && c->field) return fail(c, LRNDE_UNSUPPORTED, "bench hooks are built for the MLP field's handle");
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!uprev || !k1 || reps < 1 || !avg_us_host) return fail(c, LRNDE_BADARG, "bad bench arguments");
@@ -3736,7 +3894,7 @@ static int launch_pgrad_args(lrnde_ctx* c, const PgradArgs& g0) {
   hipLaunchKernelGGL(k_pgrad, dim3(g.ntile1 + g.ntile2), dim3(256), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
   // batch-sharded run: the parameter cotangent is a sum over all samples (SURVEY.md §8e caveat 1)
-  if (sharded(c)) return comm_allreduce(c, g.gp, g.gp, lrnde_param_count(&c->desc), false);
+  if (sharded(c)) return comm_allreduce(c, g.gp, g.gp, param_count(c), false);
   return LRNDE_OK;
 }
 // the deferred GEMM, if one is waiting (before anything reads the mu part of its K vector)
@@ -3751,7 +3909,7 @@ static int launch_pgrad(lrnde_ctx* c, int B, float t, const float* lam, float* g
   hipLaunchKernelGGL(k_pgrad, dim3(g.ntile1 + g.ntile2), dim3(256), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
   // batch-sharded run: the parameter cotangent is a sum over all samples (SURVEY.md §8e caveat 1)
-  if (sharded(c)) return comm_allreduce(c, gp, gp, lrnde_param_count(&c->desc), false);
+  if (sharded(c)) return comm_allreduce(c, gp, gp, param_count(c), false);
   return LRNDE_OK;
 }
 
@@ -3763,8 +3921,34 @@ static bool vjp_uses_qtile(const lrnde_ctx* c, int B) {
   const bool no_qvjp = opt(OPT_NO_QVJP) != 0;
   return use_qtile(c, B) && !no_qvjp;
 }
+static int launch_vjp_chain(lrnde_ctx* c, const float* y, const float* dense, float theta, float dense_dt, float t,
+                            const float* lam, int B, float* dy, float* gp) {
+  const int nwg = (B + CNB - 1) / CNB;
+  const size_t P = param_count(c);
+  if (gp && c->ch_part_n < (size_t)nwg * P) {
+    if (c->ch_part) HIPCHK(c, hipFree(c->ch_part));
+    c->ch_part = nullptr; c->ch_part_n = 0;
+    HIPCHK(c, hipMalloc(&c->ch_part, sizeof(float) * (size_t)nwg * P));
+    c->ch_part_n = (size_t)nwg * P;
+  }
+  VjpChainArgs v{};
+  v.B = B; v.t = t; v.y = y; v.dense = dense; v.theta = theta; v.dense_dt = dense_dt; v.lam = lam; v.dy = dy;
+  v.gpart = gp ? c->ch_part : nullptr;
+  hipLaunchKernelGGL(k_vjp_chain, dim3(nwg), dim3(NT), c->ch_vjp_lds, c->stream, c->cd, v);
+  HIPCHK(c, hipGetLastError());
+  if (gp) {
+    hipLaunchKernelGGL(k_chain_pgsum, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->ch_part, nwg, (int)P, gp,
+                       c->pg_accumulate ? 1 : 0);
+    HIPCHK(c, hipGetLastError());
+  }
+  return LRNDE_OK;
+}
 static int launch_vjp(lrnde_ctx* c, const float* y, const float* dense, float theta, float dense_dt, float t,
                       const float* lam, int B, float* dy, float* gp, const StageIn* sin = nullptr) {
+  if (c->field) {
+    if (sin) return fail(c, LRNDE_BADARG, "fused stage input needs the 4-column VJP kernel");
+    return launch_vjp_chain(c, y, dense, theta, dense_dt, t, lam, B, dy, gp);
+  }
   int rc = ensure_bw(c, B);
   if (rc) return rc;
   if (vjp_uses_qtile(c, B)) {
@@ -3796,7 +3980,7 @@ static int launch_vjp(lrnde_ctx* c, const float* y, const float* dense, float th
         else hipLaunchKernelGGL(k_vjp_q<4>, dim3(nvjp), dim3(QNT), smq, c->stream, a);
       }
       HIPCHK(c, hipGetLastError());
-      if (had && sharded(c)) { const int rcc = comm_allreduce(c, prev.gp, prev.gp, lrnde_param_count(&c->desc), false); if (rcc) return rcc; }
+      if (had && sharded(c)) { const int rcc = comm_allreduce(c, prev.gp, prev.gp, param_count(c), false); if (rcc) return rcc; }
       c->pg_pending = gp != nullptr;
       if (gp) c->pg_args = pgrad_args(c, B, t, lam, gp, set, true);
       c->bw_cur ^= 1;
@@ -4440,7 +4624,7 @@ static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, 
                           int32_t reg_type, float eest, float stiff_num, float stiff_den, float* gp) {
   int rc;
   const size_t n = (size_t)B * c->desc.state_dim;
-  const size_t P = lrnde_param_count(&c->desc);
+  const size_t P = param_count(c);
   float* S = c->state;  // ubuf0 (uprev) ubuf1 (u) kfsal0 (k1) kfsal1 (k7) ks0..4 (k2..k6) g6
   const float* kk[7] = {S + 2 * n, S + 4 * n, S + 5 * n, S + 6 * n, S + 7 * n, S + 8 * n, S + 3 * n};
   const float* u = S + n; const float* g6 = S + 9 * n;
@@ -4511,7 +4695,7 @@ static int node_forward_record_impl(lrnde_ctx* c, const float* x, int32_t B, flo
     if ((rc = side_quiesce(c))) return rc;
     if (c->rec_gr) HIPCHK(c, hipFree(c->rec_gr));
     c->rec_gr = nullptr; c->rec_n = 0;
-    HIPCHK(c, hipMalloc(&c->rec_gr, sizeof(float) * lrnde_param_count(&c->desc)));
+    HIPCHK(c, hipMalloc(&c->rec_gr, sizeof(float) * param_count(c)));
     c->rec_n = n;
   }
   for (int attempt = 0;; ++attempt) {
@@ -4597,7 +4781,7 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   const float t0 = c->rec_t0, t2 = c->rec_t2, t1 = c->rec_t1;
   const int mode = c->rec_mode, reg_type = c->rec_reg_type;
   const size_t n = (size_t)B * c->desc.state_dim;
-  const size_t P = lrnde_param_count(&c->desc);
+  const size_t P = param_count(c);
   const int nsteps = c->rec_naccept;
   // adjoint solve on z = [lambda; mu] in s = -t from -t2 to -t0, tstops at the saved times
   const size_t N = n + P;

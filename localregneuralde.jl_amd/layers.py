@@ -49,6 +49,17 @@ class TDChain:
         self.layers = list(chain.layers if isinstance(chain, Chain) else chain)
 
 
+class Activation:
+    """`Base.Fix1(broadcast, act)` / `WrappedFunction(x -> act.(x))`: an elementwise activation with no parameters — the
+    `tanh.(u)` that opens the PhysioNet field (experiments/src/construct.jl:236-244).  Allowed only as the first element
+    of a plain `Chain` (the Dense-chain field, NeuralODE(field="dense_chain"))."""
+
+    def __init__(self, activation):
+        if activation not in L.ACT:
+            raise ValueError(f"unsupported activation {activation!r} (have {sorted(L.ACT)})")
+        self.activation = activation
+
+
 def _mlp_desc(model):
     td = isinstance(model, TDChain)
     if not isinstance(model, (Chain, TDChain)) or len(model.layers) != 2 or \
@@ -62,6 +73,76 @@ def _mlp_desc(model):
     if l2.activation != "identity":
         raise NotImplementedError("activation on the output Dense is not part of the reference fields")
     return L.ModelDesc(D, H, int(td), L.ACT[l1.activation])
+
+
+def _chain_desc(model):
+    """lrnde_chain_desc of a Chain / TDChain of Dense layers, optionally led by an Activation (plain Chain only); the
+    shape checks and limits of lrnde_create_chain (include/lrnde.h)."""
+    if not isinstance(model, (Chain, TDChain)):
+        raise NotImplementedError("the Dense-chain field takes a Chain or TDChain of Dense layers")
+    td = isinstance(model, TDChain)
+    layers = list(model.layers)
+    in_act = "identity"
+    for i, l in enumerate(layers):
+        if isinstance(l, Activation):
+            if td:
+                raise NotImplementedError("an Activation inside a TDChain would receive t: only a plain Chain may open with one")
+            if i != 0:
+                raise NotImplementedError("an Activation is supported only as the first element of the Chain")
+            in_act = l.activation
+        elif not isinstance(l, Dense):
+            raise NotImplementedError(f"the Dense-chain field takes Dense layers only (got {type(l).__name__})")
+    dense = [l for l in layers if isinstance(l, Dense)]
+    if not 1 <= len(dense) <= L.CHAIN_MAX_LAYERS:
+        raise NotImplementedError(f"a Dense chain has 1..{L.CHAIN_MAX_LAYERS} Dense layers (got {len(dense)})")
+    dims = [dense[0].in_dims - int(td)]
+    for i, l in enumerate(dense):
+        if l.in_dims != dims[-1] + int(td):
+            raise ValueError(f"Dense shapes do not chain: layer {i + 1} takes {l.in_dims} inputs, the previous layer gives "
+                             f"{dims[-1]}" + (" + t" if td else ""))
+        dims.append(l.out_dims)
+    if dims[-1] != dims[0]:
+        raise ValueError(f"the chain maps {dims[0]} states to {dims[-1]}: a vector field needs the same width")
+    if max(dims) > L.CHAIN_MAX_WIDTH or min(dims) < 1:
+        raise NotImplementedError(f"every width of a Dense chain must be in 1..{L.CHAIN_MAX_WIDTH} (+1 for the t row); got {dims}")
+    nb = L.chain_weight_image_bytes(dims, td)
+    if nb > L.CHAIN_MAX_WEIGHT_BYTES:
+        raise NotImplementedError(f"the chain's weight image ({nb} bytes) exceeds the {L.CHAIN_MAX_WEIGHT_BYTES} bytes its step "
+                                  "kernel keeps on chip")
+    d = L.ChainDesc()
+    d.nlayers, d.time_dep, d.input_act = len(dense), int(td), L.ACT[in_act]
+    for i, v in enumerate(dims):
+        d.dims[i] = v
+    for i, l in enumerate(dense):
+        d.act[i] = L.ACT[l.activation]
+    return d
+
+
+def chain_param_count(desc):
+    """lrnde_chain_param_count restated: per layer out * (in + td) + out"""
+    n = desc.nlayers
+    return sum(desc.dims[l + 1] * (desc.dims[l] + desc.time_dep) + desc.dims[l + 1] for l in range(n))
+
+
+def flatten_chain_params(layers):
+    """[(W, b), ...] with W (out, in+td) in layer order -> the flat Lux/ComponentArray vector of a Dense chain."""
+    parts = []
+    for W, b in layers:
+        parts += [torch.as_tensor(W).t().reshape(-1), torch.as_tensor(b).reshape(-1)]
+    return torch.cat([p.to(torch.float32) for p in parts]).contiguous()
+
+
+def glorot_chain_params(model, seed=0, scale=1.0):
+    """glorot_params for a Dense chain (same stream order: each layer's weight, then its zero bias); for the 2-layer
+    shape it equals glorot_params.  `scale` multiplies the weights (step-count tests at larger weight scales)."""
+    d = _chain_desc(model)
+    rng = np.random.default_rng(seed)
+    out = []
+    for l in range(d.nlayers):
+        inn, o = d.dims[l] + d.time_dep, d.dims[l + 1]
+        W = ((rng.random((inn, o), dtype=np.float32) - np.float32(0.5)) * np.float32(np.sqrt(24.0 / (inn + o)))).astype(np.float32)
+        out += [(W * np.float32(scale)).ravel(), np.zeros(o, np.float32)]
+    return np.concatenate(out)
 
 
 def flatten_params(W1, b1, W2, b2):
@@ -109,18 +190,28 @@ def _solver_name(solver):
 
 
 class Handle:
+    """lrnde_ctx of the MLP field (desc: ModelDesc, lrnde_create) or of a Dense chain (desc: ChainDesc,
+    lrnde_create_chain)."""
+
     def __init__(self, desc, device=None, stream=None):
         if not torch.cuda.is_available():
             raise RuntimeError("liblrnde needs a GPU (gfx950); there is no CPU fallback")
         self.desc = desc
-        self.D = desc.state_dim
+        self.is_chain = isinstance(desc, L.ChainDesc)
+        self.D = desc.dims[0] if self.is_chain else desc.state_dim
+        self.nparams = int(L.lib.lrnde_chain_param_count(C.byref(desc)) if self.is_chain else L.lib.lrnde_param_count(C.byref(desc)))
         self.device = torch.cuda.current_device() if device is None else int(device)
         self._stream = torch.cuda.current_stream(self.device) if stream is None else stream
         self._ctx = C.c_void_p()
-        rc = L.lib.lrnde_create(C.byref(self._ctx), C.byref(desc), self.device,
-                                C.c_void_p(self._stream.cuda_stream))
-        if rc != 0:
-            raise L.LrndeError(rc, "lrnde_create failed")
+        if self.is_chain:
+            rc = L.lib.lrnde_create_chain(C.byref(self._ctx), C.byref(desc), self.device, C.c_void_p(self._stream.cuda_stream))
+            if rc != 0:
+                raise L.LrndeError(rc, "lrnde_create_chain failed: " + L.lib.lrnde_last_error(None).decode())
+        else:
+            rc = L.lib.lrnde_create(C.byref(self._ctx), C.byref(desc), self.device,
+                                    C.c_void_p(self._stream.cuda_stream))
+            if rc != 0:
+                raise L.LrndeError(rc, "lrnde_create failed")
         self._params = None
 
     def close(self):
@@ -218,7 +309,7 @@ class Handle:
         """(J^T lam, (df/dp)^T lam) of the vector field at (y, t) — the adjoint RHS building block."""
         B = y.numel() // self.D
         dy = torch.empty_like(y)
-        gp = torch.zeros(int(L.lib.lrnde_param_count(C.byref(self.desc))), dtype=torch.float32, device=y.device) if want_gp else None
+        gp = torch.zeros(self.nparams, dtype=torch.float32, device=y.device) if want_gp else None
         self._chk(L.lib.lrnde_vjp(self._ctx, _dev_ptr(y, "y", self.D), float(t), _dev_ptr(lam, "lam", self.D), B,
                                   _dev_ptr(dy, "dy"), C.c_void_p(gp.data_ptr()) if want_gp else None))
         return dy, gp
@@ -226,7 +317,7 @@ class Handle:
     def step_reg_grad(self, uprev, k1, t, dt, abstol, reltol, reg_type="error_estimate"):
         """d reg_val / d ps of one local Tsit5 step (k1, dt, uprev constant)."""
         B = uprev.numel() // self.D
-        gp = torch.empty(int(L.lib.lrnde_param_count(C.byref(self.desc))), dtype=torch.float32, device=uprev.device)
+        gp = torch.empty(self.nparams, dtype=torch.float32, device=uprev.device)
         rv = C.c_float()
         self._chk(L.lib.lrnde_step_reg_grad(self._ctx, _dev_ptr(uprev, "uprev", self.D), _dev_ptr(k1, "k1", self.D), B,
                                             float(t), float(dt), float(abstol), float(reltol), L.REG_TYPE[reg_type],
@@ -239,7 +330,7 @@ class Handle:
         B = x.numel() // self.D
         o = L.SolveOpts(float(abstol), float(reltol), int(maxiters), int(save_start), 0, int(exact_pow))
         dx = torch.empty_like(x)
-        dp = torch.empty(int(L.lib.lrnde_param_count(C.byref(self.desc))), dtype=torch.float32, device=x.device)
+        dp = torch.empty(self.nparams, dtype=torch.float32, device=x.device)
         sf, sb = L.Stats(), L.Stats()
         self._chk(L.lib.lrnde_node_backward(self._ctx, _dev_ptr(x, "x", self.D), B, float(t0), float(t2), C.byref(o),
                                             L.MODE[mode], L.REG_TYPE[reg_type], float(t1_or_rand),
@@ -282,7 +373,7 @@ class Handle:
     def node_backward_recorded(self, du_end, w_reg=0.0):
         B = du_end.numel() // self.D
         dx = torch.empty_like(du_end)
-        dp = torch.empty(int(L.lib.lrnde_param_count(C.byref(self.desc))), dtype=torch.float32, device=du_end.device)
+        dp = torch.empty(self.nparams, dtype=torch.float32, device=du_end.device)
         sb = L.Stats()
         self._chk(L.lib.lrnde_node_backward_recorded(self._ctx, B, _dev_ptr(du_end, "du_end", self.D), float(w_reg),
                                                      _dev_ptr(dx, "dx"), C.c_void_p(dp.data_ptr()), C.byref(sb)))
@@ -313,7 +404,7 @@ class Handle:
         nser = int(du_series.shape[0])
         B = du_series[0].numel() // self.D
         dx = torch.empty_like(du_series[0])
-        dp = torch.empty(int(L.lib.lrnde_param_count(C.byref(self.desc))), dtype=torch.float32, device=du_series.device)
+        dp = torch.empty(self.nparams, dtype=torch.float32, device=du_series.device)
         sb = L.Stats()
         self._chk(L.lib.lrnde_node_backward_recorded_ts(self._ctx, B, _dev_ptr(du_series, "du_series", self.D), nser, float(w_reg),
                                                         _dev_ptr(dx, "dx"), C.c_void_p(dp.data_ptr()), C.byref(sb)))
@@ -426,7 +517,7 @@ class NeuralODE:
     """src/layers/neural_ode.jl:1-116.  `(sol, st) = node(x, ps, st)`."""
 
     def __init__(self, model, *, solver="Tsit5", sensealg=None, tspan=(0.0, 1.0), regularize=True,
-                 maxiters=1000, regularize_type="error_estimate", **kwargs):
+                 maxiters=1000, regularize_type="error_estimate", field="auto", **kwargs):
         if isinstance(regularize, bool):  # :14-16
             regularize = "unbiased" if regularize else "none"
         regularize, regularize_type = _sym(regularize), _sym(regularize_type)
@@ -437,6 +528,20 @@ class NeuralODE:
         self.maxiters, self.kwargs = int(maxiters), dict(kwargs)
         self.regularize, self.regularize_type = regularize, regularize_type
         from .conv import conv_topology
+        # field: "auto" routes the CIFAR node_core to the conv handle and the two-layer Dense field to the MLP handle (anything
+        # else raises); "dense_chain" sends any Chain / TDChain of Dense layers (optionally led by an Activation) to the
+        # Dense-chain handle (lrnde_create_chain), the two-layer shape included
+        if field not in ("auto", "dense_chain"):
+            raise ValueError(f"field must be 'auto' or 'dense_chain' (got {field!r})")
+        self.field = field
+        if field == "dense_chain":
+            self._conv = None
+            self.desc = _chain_desc(model)
+            if self.solver != "tsit5":
+                raise NotImplementedError("VCAB3 / VCABM3 are built for the MLP field's handle (csrc/lrnde_adams.hpp)")
+            self._handle = None
+            self._bound = False
+            return
         self._conv = conv_topology(model)  # (C, Hc, act, eps) for the CIFAR node_core, else None
         self.desc = None if self._conv else _mlp_desc(model)
         if self._conv and self.solver != "tsit5":

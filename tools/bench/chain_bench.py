@@ -1,0 +1,133 @@
+"""Dense-chain field bench: the PhysioNet latent ODE's gen_dynamics (Chain(tanh.(u), 8 Dense 20 <-> 40, tanh);
+experiments/src/construct.jl:236-244, physionet.yml) at B = 512, abstol = reltol = 1.4e-8, :unbiased, a saveat series.
+
+Prints one JSON line: attempted steps, step-kernel launches per attempted step and the solve's kernel time per attempt,
+the layer forward and forward + pullback in ms per batch (median of --reps), and the same adaptive Tsit5 solve written in
+eager torch fp32 on the same GPU (host-side controller, one EEst read-back per attempted step) as a baseline.
+
+    python tools/bench/chain_bench.py [--reps 5] [--B 512]
+    rocprofv3 --kernel-trace --stats -- python tools/bench/chain_bench.py      (us per k_step_chain launch)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import lrnde_amd as P  # noqa: E402
+
+TOL = 1.4e-8
+SAVEAT = [0.25, 0.5, 0.75, 1.0]
+C = [0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0]
+A = [[0.161], [-0.008480655492356989, 0.335480655492357], [2.8971530571054935, -6.359448489975075, 4.3622954328695815],
+     [5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525],
+     [5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383],
+     [0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774]]
+BT = [-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629,
+      0.5823571654525552, -0.45808210592918697, 0.015151515151515152]
+
+
+def physionet():
+    return P.Chain(P.Activation("tanh"), *[P.Dense(20, 40, "tanh") if i % 2 == 0 else P.Dense(40, 20, "tanh") for i in range(8)])
+
+
+def eager_solve(Ws, x, t0, t1, tol, maxiters=100000):
+    """adaptive Tsit5 (initdt, PI controller with the same constants) in eager torch fp32: the baseline"""
+    def f(u):
+        h = torch.tanh(u)
+        for W, b in Ws:
+            h = torch.tanh(torch.addmm(b, h, W.t()))
+        return h
+
+    def sc(a, b=None):
+        m = a.abs() if b is None else torch.maximum(a.abs(), b.abs())
+        return tol + m * tol
+    rms = lambda v: float(torch.sqrt((v * v).mean()))
+    u, t = x, t0
+    k1 = f(u)
+    d0, d1 = rms(u / sc(u)), rms(k1 / sc(u))
+    dt0 = 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
+    d2 = rms((f(u + dt0 * k1) - k1) / sc(u)) / dt0
+    dt = min(100 * dt0, 10 ** (-(2 + np.log10(max(d1, d2, 1e-15))) / 5), t1 - t0)
+    qold, nacc, nrej = 1e-4, 0, 0
+    for _ in range(maxiters):
+        if t >= t1:
+            break
+        dt = min(dt, t1 - t)
+        ks = [k1]
+        for s in range(6):
+            acc = ks[0] * A[s][0]
+            for j in range(1, s + 1):
+                acc = acc + ks[j] * A[s][j]
+            y = u + dt * acc
+            ks.append(f(y))
+        utilde = dt * sum(b * k for b, k in zip(BT, ks))
+        eest = rms(utilde / sc(u, y))
+        q = max(0.1, min(5.0, eest ** 0.14 / qold ** 0.08 / 0.9)) if eest > 0 else 0.1
+        if eest <= 1.0:
+            u, k1, t, qold, nacc = y, ks[6], t + dt, max(eest, 1e-4), nacc + 1
+            dt = dt / q
+        else:
+            nrej += 1
+            dt = dt / min(5.0, eest ** 0.14 / 0.9)
+    return u, nacc, nrej
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--B", type=int, default=512)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    B = args.B
+    model = physionet()
+    p = P.glorot_chain_params(model, seed=0)
+    x = (np.random.default_rng(2).random((B, 20), dtype=np.float32) - np.float32(0.5)) * np.float32(2)
+    xd, ps = torch.from_numpy(x).cuda(), torch.from_numpy(p).cuda()
+    node = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, saveat=SAVEAT, save_start=False, maxiters=100000,
+                       field="dense_chain")
+    st = node.initialstates(np.random.default_rng(0))
+    cots = torch.from_numpy(np.random.default_rng(1).standard_normal((len(SAVEAT), B, 20)).astype(np.float32)).cuda()
+    h = node._bind(ps)
+    # the plain solve: kernel time and launches of its attempted steps
+    h.solve(xd, 0.0, 1.0, TOL, TOL, saveat=SAVEAT, maxiters=100000)
+    h.last_solve_kernel_ms()   # (the first call switches the solve's event bracket on)
+    r = h.solve(xd, 0.0, 1.0, TOL, TOL, saveat=SAVEAT, maxiters=100000)
+    solve_ms, launches = h.last_solve_kernel_ms()
+    attempts = r["stats"]["naccept"] + r["stats"]["nreject"]
+    fwd, fb = [], []
+    for i in range(args.reps + 1):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        node(xd, ps, st)
+        torch.cuda.synchronize(); t1 = time.perf_counter()
+        node.pullback(xd, ps, st, cots, w_reg=10.0)
+        torch.cuda.synchronize(); t2 = time.perf_counter()
+        if i:
+            fwd.append((t1 - t0) * 1e3); fb.append((t2 - t0) * 1e3)
+    Ws, o = [], 0
+    for l in model.layers[1:]:
+        n, k = l.out_dims, l.in_dims
+        Ws.append((torch.from_numpy(p[o:o + n * k].reshape(k, n).T.copy()).cuda(), torch.from_numpy(p[o + n * k:o + n * k + n]).cuda()))
+        o += n * k + n
+    eager_solve(Ws, xd, 0.0, 1.0, TOL, maxiters=5)
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    ue, ena, enr = eager_solve(Ws, xd, 0.0, 1.0, TOL)
+    torch.cuda.synchronize(); eager_ms = (time.perf_counter() - t0) * 1e3
+    err = float((ue - r["u"][-1]).abs().max() / r["u"][-1].abs().max())
+    print(json.dumps(dict(
+        workload="physionet_gen_dynamics", B=B, tol=TOL, naccept=r["stats"]["naccept"], nreject=r["stats"]["nreject"],
+        solve_kernel_ms=round(solve_ms, 3), step_launches=launches, launches_per_attempt=round(launches / max(attempts, 1), 3),
+        us_per_attempt_solve=round(1e3 * solve_ms / max(attempts, 1), 2),
+        layer_forward_ms=round(statistics.median(fwd), 3), layer_forward_pullback_ms=round(statistics.median(fb), 3),
+        eager_torch_fp32_solve_ms=round(eager_ms, 2), eager_naccept=ena, eager_nreject=enr, eager_vs_hip_u_end=err)))
+
+
+if __name__ == "__main__":
+    main()
