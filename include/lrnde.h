@@ -450,6 +450,16 @@ int lrnde_record_generation(lrnde_ctx* ctx, uint64_t* gen_host);
 int lrnde_conv_record_generation(lrnde_conv* c, uint64_t* gen_host);
 int lrnde_sde_record_generation(lrnde_sde* sde, uint64_t* gen_host);
 
+/* Gaussian noise for the SDE layers, drawn on the handle's device and stream (no host sync).
+ * out (device): cumulative = 1 -> (nsteps+1) x B x D, out[0] = 0, the Brownian path on a uniform grid;
+ *               cumulative = 0 -> nsteps x B x D increments scale * z.  stream: 0 path W, 1 local-step z,
+ *               2 fixed-grid dW, 3 fixed-grid dZ (callers may use others).  scale = sqrt(h), computed by the caller.
+ * Normal j of column c = b*D + d is Box-Muller (float64, rounded once) on Philox-4x32-10 at counter (j >> 2, c, stream, 0),
+ * key (seed & 0xffffffff, seed >> 32): it depends on (seed, stream, b, d, j) only, not on B or nsteps.
+ * The path is the sequential fp32 sum of the fp32 products scale * z.  B x D may not exceed 2^30. */
+int lrnde_sde_draw_noise(lrnde_sde* sde, uint64_t seed, uint32_t stream, int32_t nsteps, int32_t B, float scale,
+                         int32_t cumulative, float* out);
+
 /* `_perform_step(integrator, cache::FourStageSRIConstantCache, p)`, src/perform_step.jl:49-106 — the step the
  * reference's default SDE solver SOSRI runs — diagonal noise: four drift and four diffusion evaluations, the
  * increments dW and dZ of the caller's noise process (device, B x D each), u, EEst from the 7-argument

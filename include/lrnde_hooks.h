@@ -68,6 +68,9 @@ int lrnde_host_phases(lrnde_ctx* ctx, double* us4_host, int32_t reset);
 int lrnde_set_overlap(lrnde_ctx* ctx, int32_t on);
 /* average microseconds of one f-eval (3 conv + 2 batch-norm statistics launches), HIP events */
 int lrnde_conv_bench_rhs(lrnde_conv* c, const float* u, float t, int32_t B, int32_t reps, float* us_host);
+/* Test hook: the device Philox-4x32-10 of lrnde_sde_draw_noise on ONE block (host arrays in and out; current device,
+ * synchronous), so the published known-answer vectors can be checked on the GPU. */
+int lrnde_hook_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
 #ifdef __cplusplus
 }

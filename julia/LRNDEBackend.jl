@@ -204,6 +204,16 @@ end
 sde_check(h, rc) = check(h, rc; last_error=:lrnde_sde_last_error)
 sde_set_params!(h, pd, pg) = sde_check(h, ccall((:lrnde_sde_set_params, lib), Cint,
     (Ptr{Cvoid}, Ptr{Float32}, Csize_t, Ptr{Float32}, Csize_t), h, pointer(pd), length(pd), pointer(pg), length(pg)))
+# Gaussian noise drawn on the handle's device and stream (lrnde_sde_draw_noise, counter-based: a column's noise does not depend
+# on B or nsteps): cumulative -> the path (D, B, nsteps+1) with W[:, :, 1] = 0, else the increments scale * z (D, B, nsteps).
+# stream: 0 path W, 1 local-step z, 2 fixed-grid dW, 3 fixed-grid dZ.  `like`: a device array of the state (D rows).
+function sde_draw_noise(h, like, seed::UInt64, stream, nsteps, B, scale, cumulative::Bool)
+    out = similar(like, Float32, size(like, 1), B, nsteps + (cumulative ? 1 : 0))
+    sde_check(h, ccall((:lrnde_sde_draw_noise, lib), Cint,
+        (Ptr{Cvoid}, UInt64, UInt32, Int32, Int32, Float32, Int32, Ptr{Float32}),
+        h, seed, UInt32(stream), Int32(nsteps), Int32(B), Float32(scale), Int32(cumulative), pointer(out)))
+    return out
+end
 function euler_heun_step(h, uprev, dW, t, dt, abstol, reltol, delta)
     u = similar(uprev); ee = Ref{Float32}(); rv = Ref{Float32}()
     sde_check(h, ccall((:lrnde_sde_euler_heun_step, lib), Cint,

@@ -302,6 +302,9 @@ lrnde_sde_supported(n::NeuralDSDE, x) = nameof(typeof(n.solver)) === :LambaEuler
                                          nameof(typeof(x)) === :ROCArray && eltype(x) === Float32 && ndims(x) == 2
 
 const LRNDE_SDE_NFINE = Ref(256)    # grid intervals of the Brownian path drawn per layer call
+# :host — W and z drawn with randn from st.rng and copied over; :device — one seed = rand(rng, UInt64), then W (stream 0) and
+# z (stream 1) drawn on the device by lrnde_sde_draw_noise (the same streams and scale as the Python layer's noise_source="device")
+const LRNDE_SDE_NOISE = Ref(:host)
 
 function lrnde_sde_layer_forward(n::NeuralDSDE, x, ps, st)
     h = lrnde_sde_handle(n)
@@ -312,10 +315,17 @@ function lrnde_sde_layer_forward(n::NeuralDSDE, x, ps, st)
     nfine = LRNDE_SDE_NFINE[]
     hh = (t2 - t0) / nfine
     # the Brownian path on the grid (W[0] = 0) and the local step's standard-normal draw, from the layer's own stream
-    inc = randn(rng, Float32, size(x)..., nfine) .* sqrt(hh)
-    Wh = cat(zeros(Float32, size(x)..., 1), cumsum(inc; dims=ndims(inc)); dims=ndims(inc))
-    W = copyto!(similar(x, size(Wh)...), Wh)
-    z = copyto!(similar(x), randn(rng, Float32, size(x)...))
+    if LRNDE_SDE_NOISE[] === :device
+        seed = rand(rng, UInt64)
+        B = Int(LRNDEBackend.nbatch(x))
+        W = LRNDEBackend.sde_draw_noise(h, x, seed, 0, nfine, B, sqrt(hh), true)
+        z = reshape(LRNDEBackend.sde_draw_noise(h, x, seed, 1, 1, B, 1f0, false), size(x))
+    else
+        inc = randn(rng, Float32, size(x)..., nfine) .* sqrt(hh)
+        Wh = cat(zeros(Float32, size(x)..., 1), cumsum(inc; dims=ndims(inc)); dims=ndims(inc))
+        W = copyto!(similar(x, size(Wh)...), Wh)
+        z = copyto!(similar(x), randn(rng, Float32, size(x)...))
+    end
     r = mode === :none ? 0f0 : rand(rng, Float32)
     t1_or_rand = mode === :unbiased ? r * (t2 - t0) + t0 : r
     saveat = Float32.(collect(get(n.kwargs, :saveat, Float32[])))

@@ -4016,6 +4016,7 @@ int lrnde_vjp(lrnde_ctx* c, const float* y, float t, const float* lam, int32_t B
 #include "lrnde_sde_bwd.hpp"
 #include "lrnde_sde_bwd_fused.hpp"
 #include "lrnde_sde_node.hpp"
+#include "lrnde_noise.hpp"
 extern "C" {
 // ---- backward drivers -----------------------------------------------------------------------
 }  // extern "C"

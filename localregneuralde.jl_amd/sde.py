@@ -122,6 +122,17 @@ class SdeHandle:
                          dtype=[("t", "f4"), ("dt", "f4"), ("eest", "f4"), ("accepted", "i4")])
         return dict(u_end=u_end, stats=st.asdict(), trace=trace)
 
+    def draw_noise(self, seed, stream, nsteps, B, scale, cumulative):
+        """Gaussian noise drawn on the device (lrnde_sde_draw_noise, counter-based: sample b's noise does not depend on B or
+        nsteps): cumulative -> the path (nsteps+1, B, D), row 0 zero, else the increments scale * z (nsteps, B, D)"""
+        rows = int(nsteps) + (1 if cumulative else 0)
+        out = torch.empty((max(rows, 0), int(B), self.D), dtype=torch.float32, device=f"cuda:{self.device}")
+        if out.numel() == 0 and rows == 0 and int(B) > 0:   # nothing to write (an empty tensor has no data pointer)
+            return out
+        self._chk(L.lib.lrnde_sde_draw_noise(self._h, int(seed), int(stream), int(nsteps), int(B), float(np.float32(scale)),
+                                             1 if cumulative else 0, C.c_void_p(out.data_ptr())))
+        return out
+
     def _pcounts(self):
         return self._keep[0].numel(), self._keep[1].numel()
 
@@ -227,13 +238,20 @@ class NeuralDSDE:
     """`(sol, st) = nsde(x, ps, st)`; ps = dict(drift=flat, diffusion=[vec(Wg); bg]).
     src/layers/neural_sde.jl:1-123.  Default (solver="EulerHeun", adaptive=True): the ADAPTIVE solve on a Brownian path of
     `nfine` grid intervals drawn from st["rng"] (or given as `noise=` / `path=`), kwargs `abstol`, `reltol`, `saveat`, `save_start`
-    as the reference's; `adaptive=False` (and the Milstein / SRI steps): the fixed grid of `nsteps` steps."""
+    as the reference's; `adaptive=False` (and the Milstein / SRI steps): the fixed grid of `nsteps` steps.
+    noise_source="device": the noise is drawn on the device (SdeHandle.draw_noise) from one uint64 seed taken from st["rng"]
+    before its other draws — streams 0 (path W), 1 (local-step z), 2 (fixed-grid dW), 3 (fixed-grid dZ); arrays given
+    explicitly still win."""
 
     def __init__(self, drift, diffusion, *, solver="EulerHeun", sensealg=None, tspan=(0.0, 1.0),
                  regularize="unbiased", maxiters=1000, nsteps=20, delta=1.0 / 6.0, tableau=None, adaptive=None, nfine=256,
-                 dt0=0.0, **kwargs):
+                 dt0=0.0, noise_source="host", **kwargs):
         regularize = _sym(regularize)
         _check_valid_regularize(regularize)
+        if noise_source not in ("host", "device"):
+            raise ValueError("noise_source must be 'host' (numpy draws from st['rng']) or 'device' (lrnde_sde_draw_noise from a "
+                             "seed drawn from st['rng'])")
+        self.noise_source = noise_source
         if solver in ("SRI", "FourStageSRI"):
             if tableau is None:
                 raise ValueError("solver='SRI' (src/perform_step.jl:49-106) needs tableau=: the 51 coefficients of the "
@@ -279,12 +297,24 @@ class NeuralDSDE:
         z = rng.standard_normal(tuple(shape)).astype(np.float32)
         return torch.from_numpy(W).to(device), torch.from_numpy(z).to(device)
 
+    def _draw_seed(self, rng):
+        """the device streams' seed: one uint64 from the layer's host stream"""
+        return int(rng.integers(0, 2 ** 64, dtype=np.uint64))
+
     def _call_adaptive(self, x, ps, st, path=None, z_local=None):
         h = self.handle()
         h.set_params(ps["drift"], ps["diffusion"])
         t0, t2 = self.tspan
         abstol, reltol = self.kwargs.get("abstol", 1e-2), self.kwargs.get("reltol", 1e-2)
         rng = copy.deepcopy(st["rng"])
+        if self.noise_source == "device":   # W (stream 0) and z (stream 1) on the device; node_forward_record keeps W alive
+            seed = self._draw_seed(rng)
+            B = x.numel() // h.D
+            if path is None:
+                hh = np.float32((t2 - t0) / np.float32(self.nfine))
+                path = h.draw_noise(seed, 0, self.nfine, B, np.float32(np.sqrt(hh)), True).view((self.nfine + 1,) + tuple(x.shape))
+            if z_local is None:
+                z_local = h.draw_noise(seed, 1, 1, B, 1.0, False)[0].view(tuple(x.shape))
         if path is None:
             path, z_draw = self._draw_path(rng, x.shape, x.device)
             z_local = z_draw if z_local is None else z_local
@@ -315,12 +345,19 @@ class NeuralDSDE:
         n = self.nsteps
         dt = np.float32((t2 - t0) / np.float32(n))
         rng = copy.deepcopy(st["rng"])
+        seed = self._draw_seed(rng) if self.noise_source == "device" else None
+        B = x.numel() // h.D
+        if noise is None and seed is not None:   # dW (stream 2) on the device
+            noise = h.draw_noise(seed, 2, n + 1, B, np.float32(np.sqrt(dt)), False).view((n + 1,) + tuple(x.shape))
         if noise is None:  # W.dW ~ sqrt(dt) N(0,1), drawn on the host stream
             noise = (rng.standard_normal((n + 1,) + tuple(x.shape)).astype(np.float32) * np.float32(np.sqrt(dt)))
         noise = torch.as_tensor(noise, dtype=torch.float32).to(x.device)
         # step(u, i, t): one step with the i-th increments of the noise process
-        if self.solver == "SRI":  # second increment dZ (W.dZ), drawn after dW from the same host stream
-            dz = torch.as_tensor(rng.standard_normal((n + 1,) + tuple(x.shape)).astype(np.float32) * np.float32(np.sqrt(dt))).to(x.device)
+        if self.solver == "SRI":  # second increment dZ (W.dZ): stream 3 on the device, or drawn after dW from the same host stream
+            if seed is not None:
+                dz = h.draw_noise(seed, 3, n + 1, B, np.float32(np.sqrt(dt)), False).view((n + 1,) + tuple(x.shape))
+            else:
+                dz = torch.as_tensor(rng.standard_normal((n + 1,) + tuple(x.shape)).astype(np.float32) * np.float32(np.sqrt(dt))).to(x.device)
             step = lambda uu, i, tt: h.sri_step(self.tableau, uu, noise[i].contiguous(), dz[i].contiguous(), tt, dt, abstol, reltol, self.delta)
             us, u = [], x
             for i in range(n):
