@@ -58,6 +58,14 @@ int lrnde_set_option(const char* name, int32_t value);
  * tests/test_gpu_backward.py holds the adjoint's controller to the oracle's step sequence attempt by attempt. */
 int lrnde_set_adjoint_trace(lrnde_ctx* ctx, lrnde_trace_row* rows_host, int32_t cap);
 int lrnde_adjoint_trace_rows(lrnde_ctx* ctx, int32_t* n_host);
+/* Diagnostic: how the reversed solve of the last lrnde_node_backward_recorded(_ts) / lrnde_node_backward ran.
+ * kind: 0 the host-controlled loop (vec_tsit5_solve; LRNDE_ADJ_HOST=1, sharded handles, shapes outside the device loops'
+ * gates), 1 the MLP handle's device-controlled loop, 2 the chain handle's (lrnde_chain_adjoint.hpp).  launches: kernels the
+ * solve enqueued, from its first launch to k_adj_out (the regulariser's sweep is not counted).  host_waits: stream
+ * synchronisations and blocking copies the host made before the solve's end with nothing enqueued behind them, i.e. waits
+ * during which the GPU idles; the final wait is not counted, and polling the pinned progress word while an attempt is
+ * still queued is not a wait. */
+int lrnde_last_adjoint_info(lrnde_ctx* ctx, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host);
 /* Diagnostic: mean host-side microseconds per lrnde_node_forward call since the last reset, by phase: [0] entry -> the main
  * solve's init launches enqueued, [1] -> its last report read (the feed loop: the GPU is busy throughout), [2] -> the final
  * synchronisation returned, [3] -> the call returned (local-step results, bookkeeping).  tools/bench/host_phases.py */

@@ -1661,6 +1661,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 #include "lrnde_adjoint.hpp"
 #include "lrnde_backward.hpp"
 #include "lrnde_chain.hpp"
+#include "lrnde_chain_adjoint.hpp"
 
 // single-step modes: EEst and the two regularisation values from the partial sums
 __global__ void k_finalize(StepArgs a, int j) {
@@ -1879,6 +1880,16 @@ struct lrnde_ctx {
   int ch_gfloats = 0;
   size_t ch_vjp_lds = 0;                                             // dynamic LDS of k_vjp_chain
   float* ch_part = nullptr; size_t ch_part_n = 0;                    // per-workgroup parameter cotangents of k_vjp_chain
+  // the chain handle's device-controlled adjoint loop (lrnde_chain_adjoint.hpp): control blocks, per-(stage, workgroup)
+  // parameter cotangents, norm partials, tstop / impulse tables — allocated on first use, regrown only for a larger batch
+  ChAdjCtrl* cha_ctl = nullptr;
+  float* cha_gpart = nullptr; size_t cha_gpart_n = 0;
+  double* cha_dpart = nullptr; size_t cha_dpart_n = 0;
+  float* cha_stops = nullptr; int cha_stops_cap = 0;
+  ChAdjImp* cha_imp = nullptr; int cha_imp_cap = 0;
+  // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device), the kernels it
+  // enqueued and the waits the host made with nothing enqueued behind them
+  int adj_kind = 0, adj_launches = 0, adj_waits = 0;
   int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp)
   bool hung = false;         // a host loop waited LRNDE_SPIN_DEADLINE_S for a report while the queue stayed busy: only lrnde_destroy is safe
   bool reports_off = false;  // lrnde_set_reports(ctx, 0): the solve loop polls by copies (its fall-back when no report arrives)
@@ -2193,6 +2204,7 @@ int set_smem_attr() {
   hipFuncSetAttribute((const void*)k_init2_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_rhs_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_vjp_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_chadj_step, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   done = true;
   return 0;
 }
@@ -2435,7 +2447,8 @@ int lrnde_destroy(lrnde_ctx* c) {
   if (c->adj_part_host) hipHostFree(c->adj_part_host);
   void* ptrs[] = {c->dense, c->dense_t, c->dense_dt, c->adj, c->adj_part, c->V1p, c->U2p, c->V1q, c->U2q, c->bw_y, c->bw_h, c->bw_dp, c->bw_da, c->W1q, c->W2q, c->W1p, c->W2p, c->w1t, c->b1, c->w2t, c->b2, c->state, c->ctrl, c->part,
                   c->part_rx, c->pinit, c->pinit_rx, c->arrive, c->tile_part, c->tile_pinit, c->rec_gr, c->saveat_dev, c->trace_dev,
-                  c->usave, c->ch_meta, c->ch_wf, c->ch_wg, c->ch_part};
+                  c->usave, c->ch_meta, c->ch_wf, c->ch_wg, c->ch_part,
+                  c->cha_ctl, c->cha_gpart, c->cha_dpart, c->cha_stops, c->cha_imp};
   for (void* p : ptrs) if (p) hipFree(p);
   if (c->ctrl_host) hipHostFree(c->ctrl_host);
   if (c->tsaved_host) hipHostFree(c->tsaved_host);
@@ -3893,6 +3906,7 @@ static int launch_pgrad_args(lrnde_ctx* c, const PgradArgs& g0) {
   pgrad_shape(g, false);   // (a deferred GEMM that no VJP launch came to carry: the shape of a launch of its own)
   hipLaunchKernelGGL(k_pgrad, dim3(g.ntile1 + g.ntile2), dim3(256), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   // batch-sharded run: the parameter cotangent is a sum over all samples (SURVEY.md §8e caveat 1)
   if (sharded(c)) return comm_allreduce(c, g.gp, g.gp, param_count(c), false);
   return LRNDE_OK;
@@ -3908,6 +3922,7 @@ static int launch_pgrad(lrnde_ctx* c, int B, float t, const float* lam, float* g
   const PgradArgs g = pgrad_args(c, B, t, lam, gp, 0);
   hipLaunchKernelGGL(k_pgrad, dim3(g.ntile1 + g.ntile2), dim3(256), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   // batch-sharded run: the parameter cotangent is a sum over all samples (SURVEY.md §8e caveat 1)
   if (sharded(c)) return comm_allreduce(c, gp, gp, param_count(c), false);
   return LRNDE_OK;
@@ -3936,6 +3951,7 @@ static int launch_vjp_chain(lrnde_ctx* c, const float* y, const float* dense, fl
   v.gpart = gp ? c->ch_part : nullptr;
   hipLaunchKernelGGL(k_vjp_chain, dim3(nwg), dim3(NT), c->ch_vjp_lds, c->stream, c->cd, v);
   HIPCHK(c, hipGetLastError());
+  c->adj_launches += gp ? 2 : 1;
   if (gp) {
     hipLaunchKernelGGL(k_chain_pgsum, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->ch_part, nwg, (int)P, gp,
                        c->pg_accumulate ? 1 : 0);
@@ -3980,6 +3996,7 @@ static int launch_vjp(lrnde_ctx* c, const float* y, const float* dense, float th
         else hipLaunchKernelGGL(k_vjp_q<4>, dim3(nvjp), dim3(QNT), smq, c->stream, a);
       }
       HIPCHK(c, hipGetLastError());
+      ++c->adj_launches;
       if (had && sharded(c)) { const int rcc = comm_allreduce(c, prev.gp, prev.gp, param_count(c), false); if (rcc) return rcc; }
       c->pg_pending = gp != nullptr;
       if (gp) c->pg_args = pgrad_args(c, B, t, lam, gp, set, true);
@@ -3989,6 +4006,7 @@ static int launch_vjp(lrnde_ctx* c, const float* y, const float* dense, float th
     if (kt1) hipLaunchKernelGGL(k_vjp_q<1>, dim3(nvjp), dim3(QNT), smq, c->stream, a);
     else hipLaunchKernelGGL(k_vjp_q<4>, dim3(nvjp), dim3(QNT), smq, c->stream, a);
     HIPCHK(c, hipGetLastError());
+    ++c->adj_launches;
     return launch_pgrad(c, B, t, lam, gp);
   }
   if (sin) return fail(c, LRNDE_BADARG, "fused stage input needs the 4-column VJP kernel");
@@ -4002,6 +4020,7 @@ static int launch_vjp(lrnde_ctx* c, const float* y, const float* dense, float th
   if (vecw(c) == 4) hipLaunchKernelGGL(k_vjp<4>, dim3(nwg), dim3(NT), sm, c->stream, a);
   else hipLaunchKernelGGL(k_vjp<1>, dim3(nwg), dim3(NT), sm, c->stream, a);
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   return launch_pgrad(c, B, t, lam, gp);
 }
 
@@ -4051,6 +4070,7 @@ int vec_axpy(lrnde_ctx* c, float* out, const float* base, float dt, int nk, cons
   int nb = (int)((n + 255) / 256); if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(k_axpy, dim3(nb), dim3(256), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   return LRNDE_OK;
 }
 
@@ -4071,6 +4091,7 @@ int vec_norm(lrnde_ctx* c, const float* num, const float* num2, const float* sa,
     hipLaunchKernelGGL(k_norm, dim3(256), dim3(256), 0, c->stream, a);
   }
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   return norm_readback(c, n_lam, P, out);
 }
 // the per-block sums in c->adj_part (lambda part [0,256), mu part [256,512)) -> the rms over [lambda of all ranks; mu]
@@ -4085,6 +4106,7 @@ int norm_readback(lrnde_ctx* c, size_t n_lam, size_t P, float* out) {
   // the controller waits for this read-back once per adjoint step: poll an event instead of a blocking stream wait
   if (!c->ev_norm) HIPCHK(c, hipEventCreateWithFlags(&c->ev_norm, hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->ev_norm, c->stream));
+  ++c->adj_waits;
   for (;;) {
     const hipError_t q = hipEventQuery(c->ev_norm);
     if (q == hipSuccess) break;
@@ -4313,6 +4335,7 @@ int adj_enqueue_eval(lrnde_ctx* c, int B, const AdjArgs& g, int mode, int stage,
     else hipLaunchKernelGGL(k_vjp_q<4>, dim3(nvjp), dim3(QNT), smq, st, a);
   }
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   c->bw_cur = rot3 ? (set + 1) % 3 : set ^ 1;
   return LRNDE_OK;
 }
@@ -4332,6 +4355,7 @@ int adj_enqueue_pgrad(lrnde_ctx* c, int B, const AdjArgs& g, int mode, int stage
   if (mode == ADJ_STAGE && stage == 7) pgrad_stage7_operands(c, B, pg);
   hipLaunchKernelGGL(k_pgrad_adj, dim3(pg.ntile1 + pg.ntile2), dim3(256), 0, c->stream, pg, g);
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   return LRNDE_OK;
 }
 
@@ -4351,6 +4375,7 @@ int adj_norm_into(lrnde_ctx* c, const float* num, const float* num2, const float
   b.num = num + n_lam; b.num2 = num2 ? num2 + n_lam : nullptr; b.sa = sa + n_lam; b.n = P; b.part = part + 256;
   hipLaunchKernelGGL(k_norm2, dim3(512), dim3(256), 0, c->stream, a, b);
   HIPCHK(c, hipGetLastError());
+  ++c->adj_launches;
   return adj_enqueue_slots(c, part);
 }
 
@@ -4440,6 +4465,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     }
     hipLaunchKernelGGL(k_adj_ctrl_init, dim3(1), dim3(1), 0, c->stream, c->adj_ctl, s0);
   }
+  ++c->adj_launches;
   c->adj_init_src = nullptr;
   size_t iseg = 0;
   while (iseg < impulses.size() && impulses[iseg].s <= s0) ++iseg;  // a cotangent at the start time is the caller's lambda(s0)
@@ -4511,6 +4537,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
         if (!fold_mu) hipLaunchKernelGGL(k_adj_err_dev, dim3(256), dim3(256), 0, c->stream, e, g, jj, 1);
       }
       HIPCHK(c, hipGetLastError());
+      c->adj_launches += (split_off || fold_mu) ? 1 : 2;
       return LRNDE_OK;
     };
     while (!done) {
@@ -4578,7 +4605,9 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     float* zc = c->adj + (size_t)fin.cur * N;
     if ((rc = vec_axpy(c, zc, zc, 1.0f, 1, gi, &one, n))) return rc;
     ++iseg;
+    ++c->adj_waits;   // (the segment's end was waited for with nothing enqueued behind it)
     hipLaunchKernelGGL(k_adj_ctrl_continue, dim3(1), dim3(1), 0, c->stream, c->adj_ctl, j & 1);
+    ++c->adj_launches;
   }
   st->retcode = (fin.status == ST_DONE) ? LRNDE_OK : (fin.status == ST_RUNNING ? LRNDE_MAXITERS : fin.status);
   st->nf = fin.nf + extra_nf; st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iter;
@@ -4591,6 +4620,193 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
       if ((rc = vec_axpy(c, zend, zend, 1.0f, 1, gi, &one, n))) return rc;
     }
   v.z = zend;  // (the caller copies dx / dp out of it; no move to the first buffer)
+  if (st->retcode != LRNDE_OK) hipStreamSynchronize(c->stream);  // nothing of a failed solve is left in flight
+  return st->retcode;
+}
+
+// ---- the chain handle's adjoint solve with the controller on the device (lrnde_chain_adjoint.hpp) -----------------
+// The gate, stated once: the step kernel's LDS (forward image + activation record + reduction scratch; the backward image
+// rides along when it fits too) within CHADJ_LDS_MAX, at most CHADJ_MAX_WG workgroups, and the per-(stage, workgroup)
+// parameter cotangents (7 x workgroups x P floats) within CHADJ_SCRATCH_MAX.  Outside it the host loop runs.
+struct ChAdjPlan { int nwg, nmu, wg_lds; size_t lds; };
+bool chadj_fits(const lrnde_ctx* c, int B, ChAdjPlan* pl) {
+  if (!c->field) return false;
+  const size_t P = param_count(c);
+  const int nwg = (B + CNB - 1) / CNB;
+  const size_t lds0 = chadj_smem_bytes(c->cd.wfloats, 0, c->ch_vjp_lds);
+  const size_t lds1 = chadj_smem_bytes(c->cd.wfloats, c->ch_gfloats, c->ch_vjp_lds);
+  if (lds0 > CHADJ_LDS_MAX || nwg > CHADJ_MAX_WG) return false;
+  if (7 * (size_t)nwg * P * sizeof(float) > CHADJ_SCRATCH_MAX) return false;
+  if (pl) {
+    pl->nwg = nwg;
+    pl->nmu = (int)std::min<size_t>((P + 63) / 64, CHADJ_MAX_MU_BLOCKS);
+    pl->wg_lds = lds1 <= CHADJ_LDS_MAX ? 1 : 0;
+    pl->lds = pl->wg_lds ? lds1 : lds0;
+  }
+  return true;
+}
+
+// Launches: 1 (k_chadj_begin; one more per 64 further tstops / impulses) + 4 (initdt: two evaluations, each a step-family
+// and a mu-family launch) + 2 per attempted step + 2 (the launch pair whose prologue reports the end) here; the caller
+// adds k_adj_out and at most two k_axpy for cotangents at the two end points of the solve.
+int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float abstol, float reltol, int maxiters, int exact_pow,
+                       const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st) {
+  int rc;
+  memset(st, 0, sizeof(*st));
+  ChAdjPlan pl{};
+  if (!chadj_fits(c, B, &pl)) return fail(c, LRNDE_UNSUPPORTED, "chain adjoint loop: shape outside the gate");
+  const size_t P = v.P, N = v.N, n = v.n_lam;
+  const int np = pl.nwg + pl.nmu;
+  if (!c->cha_ctl) HIPCHK(c, hipMalloc(&c->cha_ctl, sizeof(ChAdjCtrl) * 2));
+  if (!c->adj_hstat) {
+    HIPCHK(c, hipHostMalloc(&c->adj_hstat, sizeof(int) * 16, hipHostMallocMapped));
+    memset(c->adj_hstat, 0, sizeof(int) * 16);
+    HIPCHK(c, hipHostGetDevicePointer((void**)&c->adj_hstat_dev, c->adj_hstat, 0));
+  }
+  if (c->cha_gpart_n < 7 * (size_t)pl.nwg * P) {
+    if (c->cha_gpart) HIPCHK(c, hipFree(c->cha_gpart));
+    c->cha_gpart = nullptr; c->cha_gpart_n = 0;
+    HIPCHK(c, hipMalloc(&c->cha_gpart, sizeof(float) * 7 * (size_t)pl.nwg * P));
+    c->cha_gpart_n = 7 * (size_t)pl.nwg * P;
+  }
+  if (c->cha_dpart_n < 5 * (size_t)np) {
+    if (c->cha_dpart) HIPCHK(c, hipFree(c->cha_dpart));
+    c->cha_dpart = nullptr; c->cha_dpart_n = 0;
+    HIPCHK(c, hipMalloc(&c->cha_dpart, sizeof(double) * 5 * (size_t)np));
+    c->cha_dpart_n = 5 * (size_t)np;
+  }
+  // impulses strictly inside (s0, s1) go to the device table; those at the end time are added after the solve (a cotangent
+  // at the start time is the caller's lambda(s0))
+  std::vector<ChAdjImp> tab;
+  std::vector<const float*> at_end;
+  for (const AdjImpulse& im : impulses) {
+    if (im.s <= s0) continue;
+    if (im.s < s1) tab.push_back(ChAdjImp{im.s, im.du});
+    else at_end.push_back(im.du);
+  }
+  if ((int)tstops.size() > c->cha_stops_cap || !c->cha_stops) {
+    if (c->cha_stops) HIPCHK(c, hipFree(c->cha_stops));
+    c->cha_stops = nullptr; c->cha_stops_cap = 0;
+    HIPCHK(c, hipMalloc(&c->cha_stops, sizeof(float) * (tstops.size() + 64)));
+    c->cha_stops_cap = (int)tstops.size() + 64;
+  }
+  if ((int)tab.size() > c->cha_imp_cap || !c->cha_imp) {
+    if (c->cha_imp) HIPCHK(c, hipFree(c->cha_imp));
+    c->cha_imp = nullptr; c->cha_imp_cap = 0;
+    HIPCHK(c, hipMalloc(&c->cha_imp, sizeof(ChAdjImp) * (tab.size() + 64)));
+    c->cha_imp_cap = (int)tab.size() + 64;
+  }
+  {
+    size_t so = 0, io = 0;
+    bool first = true;
+    while (first || so < tstops.size() || io < tab.size()) {
+      ChAdjBegin b{};
+      memset(&b, 0, sizeof(b));
+      b.cc = c->cha_ctl; b.s0 = s0; b.init = first ? 1 : 0;
+      b.stops = c->cha_stops; b.soff = (int)so; b.nstops = (int)std::min<size_t>(64, tstops.size() - so);
+      b.imp = c->cha_imp; b.ioff = (int)io; b.nimp = (int)std::min<size_t>(64, tab.size() - io);
+      for (int k = 0; k < b.nstops; ++k) b.sv[k] = tstops[so + k];
+      for (int k = 0; k < b.nimp; ++k) b.iv[k] = tab[io + k];
+      hipLaunchKernelGGL(k_chadj_begin, dim3(1), dim3(64), 0, c->stream, b);
+      HIPCHK(c, hipGetLastError());
+      ++c->adj_launches;
+      so += b.nstops; io += b.nimp;
+      first = false;
+    }
+  }
+  ChAdjArgs a{};
+  memset(&a, 0, sizeof(a));
+  AdjArgs& g = a.g;
+  g.base = c->adj; g.N = N; g.n_lam = n; g.P = P;
+  g.dense = c->dense; g.dense_t = c->dense_t; g.dense_dt = c->dense_dt; g.nrec = nrec;
+  g.stops = c->cha_stops; g.nstops = (int)tstops.size();
+  g.s0 = s0; g.s1 = s1; g.dtmax = s1 - s0; g.dtmin = fmaxf(eps_f(s1), eps_f(s0));
+  g.abstol = abstol; g.reltol = reltol; g.maxiters = maxiters; g.exact_pow = exact_pow;
+  g.nranks = 1;
+  g.hstat = c->adj_hstat_dev; g.seq0 = c->adj_seq;
+  a.cc = c->cha_ctl; a.imp = c->cha_imp; a.nimp = (int)tab.size();
+  a.gpart = c->cha_gpart; a.dpart = c->cha_dpart;
+  a.B = B; a.nwg = pl.nwg; a.nmu = pl.nmu; a.np = np; a.wg_lds = pl.wg_lds; a.gfloats = c->ch_gfloats;
+  auto enqueue = [&](int jj, int mode) -> int {
+    hipLaunchKernelGGL(k_chadj_step, dim3(pl.nwg), dim3(NT), pl.lds, c->stream, a, c->cd, jj, mode);
+    hipLaunchKernelGGL(k_chadj_mu, dim3(pl.nmu), dim3(CHADJ_MU_NT), 0, c->stream, a, jj, mode);
+    HIPCHK(c, hipGetLastError());
+    c->adj_launches += 2;
+    return LRNDE_OK;
+  };
+  if ((rc = enqueue(0, CHADJ_INIT_A))) return rc;
+  if ((rc = enqueue(0, CHADJ_INIT_B))) return rc;
+  // Attempts are enqueued ONE ahead of what the device has decided (adj_solve_device's scheme): the step launch of
+  // attempt j publishes the integrator's state in pinned host memory, and attempt j + 1 is enqueued while attempt j runs.
+  volatile int* hs = c->adj_hstat;
+  int j = 0;
+  bool done = false;
+  // every early exit: nothing stays in flight, and the sequence numbers the launches may still have written are retired
+  auto bail = [&](int code) -> int {
+    hipStreamSynchronize(c->stream);
+    c->adj_seq += j + 1;
+    c->after_first_attempt = nullptr;
+    return code;
+  };
+  int trace_prev = -1, trace_nacc = 0;
+  while (!done) {
+    if ((rc = enqueue(j, CHADJ_STEP))) return bail(rc);
+    if (c->after_first_attempt) {
+      auto fn = std::move(c->after_first_attempt);
+      c->after_first_attempt = nullptr;
+      if ((rc = fn())) return bail(rc);
+    }
+    ++j;
+    const int want = g.seq0 + j;
+    long spins = 0;
+    const SpinDeadline deadline;
+    while ((int)(__atomic_load_n(hs, __ATOMIC_ACQUIRE) - want) < 0) {
+      if (((++spins) & 0xFFFFF) == 0) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q != hipSuccess && q != hipErrorNotReady) return bail(fail(c, LRNDE_HIP_ERROR, "chain adjoint loop: %s", hipGetErrorString(q)));
+        if (q == hipSuccess && (int)(__atomic_load_n(hs, __ATOMIC_ACQUIRE) - want) < 0)
+          return bail(fail(c, LRNDE_HIP_ERROR, "chain adjoint loop: the stream drained without the status of attempt %d", j - 1));
+        if (q == hipErrorNotReady && deadline.expired()) { c->adj_seq += j + 1; return LRNDE_HUNG(c, "chain adjoint loop"); }
+      }
+    }
+    if (c->adj_trace) {
+      // the report of attempt j-1's prologue: its (s, dt), and the error estimate / decision of the attempt before it
+      if (j > 1 && trace_prev >= 0) {
+        lrnde_trace_row& r = c->adj_trace[trace_prev];
+        r.eest = __builtin_bit_cast(float, (int)hs[9]); r.accepted = (hs[6] > trace_nacc);
+      }
+      trace_prev = -1; trace_nacc = hs[6];
+      if (hs[1] == ST_RUNNING && c->adj_trace_n < c->adj_trace_cap) {
+        trace_prev = c->adj_trace_n++;
+        lrnde_trace_row& r = c->adj_trace[trace_prev];
+        r.t = __builtin_bit_cast(float, (int)hs[2]); r.dt = __builtin_bit_cast(float, (int)hs[3]); r.eest = 0.f; r.accepted = -1;
+      }
+    }
+    if (hs[1] != ST_RUNNING) done = true;
+    if (j > maxiters + 16) break;
+  }
+  c->adj_seq += j;
+  AdjCtrl fin;
+  memset(&fin, 0, sizeof(fin));
+  if (done) {
+    fin.status = hs[1]; fin.t = __builtin_bit_cast(float, (int)hs[2]); fin.dt = __builtin_bit_cast(float, (int)hs[3]);
+    fin.cur = hs[4]; fin.nf = hs[5]; fin.naccept = hs[6]; fin.nreject = hs[7]; fin.iter = hs[8];
+    fin.eest_last = __builtin_bit_cast(float, (int)hs[9]); fin.dt_init = __builtin_bit_cast(float, (int)hs[10]);
+  } else {  // launch cap reached with the solve still running
+    ChAdjCtrl hc;
+    HIPCHK(c, hipMemcpy(&hc, c->cha_ctl + (j & 1), sizeof(ChAdjCtrl), hipMemcpyDeviceToHost));
+    fin = hc.c;
+  }
+  st->retcode = (fin.status == ST_DONE) ? LRNDE_OK : (fin.status == ST_RUNNING ? LRNDE_MAXITERS : fin.status);
+  st->nf = fin.nf; st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iter;
+  st->t_final = fin.t; st->dt_final = fin.dt; st->eest_last = fin.eest_last; st->dt_init = fin.dt_init;
+  float* zend = c->adj + (size_t)fin.cur * N;
+  if (st->retcode == LRNDE_OK)
+    for (const float* du : at_end) {
+      const float* gi[1] = {du}; const float one = 1.0f;
+      if ((rc = vec_axpy(c, zend, zend, 1.0f, 1, gi, &one, n))) return rc;
+    }
+  v.z = zend;
   if (st->retcode != LRNDE_OK) hipStreamSynchronize(c->stream);  // nothing of a failed solve is left in flight
   return st->retcode;
 }
@@ -4790,7 +5006,9 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   if ((rc = adj_alloc(c, N, v))) return rc;
   v.n_lam = n; v.P = P;
   const bool adj_host = opt(OPT_ADJ_HOST) != 0;  // diagnostic: the round-1 host-controlled loop
+  const bool chain_loop = c->field && chadj_fits(c, B, nullptr) && !sharded(c) && !adj_host;
   const bool dev_loop = vjp_uses_qtile(c, B) && !sharded(c) && !adj_host;
+  c->adj_kind = chain_loop ? 2 : (dev_loop ? 1 : 0); c->adj_launches = 0; c->adj_waits = 0;
   const bool begin_in_solve = dev_loop && !du_series;  // the device loop's first launch sets z = [du_end; 0] itself
   if (!begin_in_solve) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
   std::vector<AdjImpulse> impulses;  // ascending in s = -t
@@ -4831,7 +5049,9 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     if (vjp_uses_qtile(c, B) && !sharded(c) && !adj_host) c->after_first_attempt = pending_sweep;
     else if ((rc = pending_sweep())) return rc;
   }
-  if (dev_loop) {
+  if (chain_loop) {
+    rc = chadj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd);
+  } else if (dev_loop) {
     c->adj_init_src = begin_in_solve ? du_end : nullptr;
     rc = adj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd);
     c->adj_init_src = nullptr;
@@ -4839,12 +5059,15 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     std::vector<float> dts(nsteps), dds(nsteps);
     HIPCHK(c, hipMemcpy(dts.data(), c->dense_t, sizeof(float) * nsteps, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(dds.data(), c->dense_dt, sizeof(float) * nsteps, hipMemcpyDeviceToHost));
+    c->adj_waits += 2;
     auto rhs = [&](const float* zs, float sg, float* K) { return adj_rhs(c, dts, dds, B, n, zs, sg, K); };
     auto rhs_fused = [&](const StageIn& sin, float sg, float* K) { return adj_rhs(c, dts, dds, B, n, nullptr, sg, K, &sin); };
     rc = vec_tsit5_solve(c, v, rhs, rhs_fused, vjp_uses_qtile(c, B), -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow,
                          stops, impulses, st_bwd);
   }
   c->after_first_attempt = nullptr;
+  // (+ k_adj_out; what the regulariser's sweep enqueues behind the solve is not the solve's)
+  struct InfoGuard { lrnde_ctx* c; int n; ~InfoGuard() { c->adj_launches = n; } } info_guard{c, c->adj_launches + 1};
   if (rc) return fail(c, rc, "adjoint solve stopped with retcode %d", rc);
   auto adj_out = [&](const float* grad_reg) -> int {   // dx = lambda, dp = mu [+ w_reg * grad_reg]: one launch
     int nb = (int)((N + 255) / 256); if (nb > 2048) nb = 2048;
@@ -5063,6 +5286,12 @@ int lrnde_opt_update(int32_t kind, float* x, const float* grad, float* state1, f
 int lrnde_set_adjoint_trace(lrnde_ctx* c, lrnde_trace_row* rows_host, int32_t cap) {
   if (!c || cap < 0) return LRNDE_BADARG;
   c->adj_trace = cap > 0 ? rows_host : nullptr; c->adj_trace_cap = cap; c->adj_trace_n = 0;
+  return LRNDE_OK;
+}
+
+int lrnde_last_adjoint_info(lrnde_ctx* c, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host) {
+  if (!c || !kind_host || !launches_host || !host_waits_host) return LRNDE_BADARG;
+  *kind_host = c->adj_kind; *launches_host = c->adj_launches; *host_waits_host = c->adj_waits;
   return LRNDE_OK;
 }
 

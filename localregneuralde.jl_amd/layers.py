@@ -350,6 +350,15 @@ class Handle:
         r = self._adj_rows
         return [(r[i].t, r[i].dt, r[i].eest, r[i].accepted) for i in range(int(n.value))]
 
+    ADJOINT_LOOPS = ("host", "device", "chain_device")
+
+    def last_adjoint_info(self):
+        """how the last reversed solve ran (lrnde_last_adjoint_info): kind 0 host loop / 1 the MLP device loop / 2 the
+        chain device loop, the kernels it enqueued, and the host waits during which the GPU idled"""
+        k, n, w = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(L.lib.lrnde_last_adjoint_info(self._ctx, C.byref(k), C.byref(n), C.byref(w)))
+        return dict(kind=int(k.value), launches=int(n.value), host_waits=int(w.value))
+
     def node_forward_record(self, x, t0, t2, abstol, reltol, mode="unbiased", reg_type="error_estimate",
                             t1_or_rand=0.5, maxiters=1000, save_start=False, exact_pow=False):
         """node_forward that keeps the dense record for one `node_backward_recorded`."""
@@ -654,7 +663,9 @@ class NeuralODE:
         cotangent per state of the returned solution, stacked (nseries, B, D) (`diffeqsol_to_timeseries` consumers,
         src/utils.jl:42-46, experiments/src/construct.jl:244-249).  One forward with the dense record, then the backward
         from it; t1 comes from the same single draw of st['rng'] as in `__call__` (biased_index), so info['reg_val'] /
-        info['t1'] are `__call__`'s."""
+        info['t1'] are `__call__`'s.  info['adjoint_loop'] names the loop that ran the reversed solve: "host" (the
+        host-controlled loop), "device" (the MLP handle's device-controlled loop) or "chain_device" (the Dense-chain
+        handle's); the conv field's own backward reports None."""
         h = self._bind(ps, x)
         t0, t2 = self.tspan
         kw = self.kwargs
@@ -682,5 +693,6 @@ class NeuralODE:
             fw = h.node_forward_record(x, t0, t2, abstol, reltol, **common)
             bw = h.node_backward_recorded(du, w_reg=w_reg) if not self._conv else h.node_backward_recorded(x.shape[0], du, w_reg=w_reg)
         info = dict(bw, reg_val=fw["reg_val"], t1=fw["t1"], nfe=fw["nfe"], u_end=fw["u_end"], stats_fwd=fw["stats"],
-                    sol_t=fw.get("t"), sol_u=fw.get("u"))
+                    sol_t=fw.get("t"), sol_u=fw.get("u"),
+                    adjoint_loop=None if self._conv else Handle.ADJOINT_LOOPS[h.last_adjoint_info()["kind"]])
         return bw["dx"], bw["dp"], info

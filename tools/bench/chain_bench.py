@@ -5,7 +5,12 @@ Prints one JSON line: attempted steps, step-kernel launches per attempted step a
 the layer forward and forward + pullback in ms per batch (median of --reps), and the same adaptive Tsit5 solve written in
 eager torch fp32 on the same GPU (host-side controller, one EEst read-back per attempted step) as a baseline.
 
-    python tools/bench/chain_bench.py [--reps 5] [--B 512]
+The pullback legs (4-time series and the experiment's 49-time series): node.pullback alone (recorded forward + backward)
+and the backward alone from a record, ms per batch (median of --bwd-reps after warm-up) with the run's min / max, the
+reversed solve's attempted steps, us per attempt of the backward alone, which loop ran it (adjoint_loop), its launches per
+attempt and host waits.  LRNDE_ADJ_HOST=1 in the environment selects the host-controlled loop: the comparison path.
+
+    python tools/bench/chain_bench.py [--reps 5] [--B 512] [--bwd-reps 30]
     rocprofv3 --kernel-trace --stats -- python tools/bench/chain_bench.py      (us per k_step_chain launch)
 """
 import argparse
@@ -80,9 +85,36 @@ def eager_solve(Ws, x, t0, t1, tol, maxiters=100000):
     return u, nacc, nrej
 
 
+def pullback_leg(node, h, xd, ps, st, times, B, reps):
+    """node.pullback alone and the backward alone over a saveat series with a cotangent at every time"""
+    cots = torch.from_numpy(np.random.default_rng(1).standard_normal((len(times), B, 20)).astype(np.float32)).cuda()
+    full, bwd, info = [], [], None
+    for i in range(reps + 3):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        _, _, info = node.pullback(xd, ps, st, cots, w_reg=10.0)
+        torch.cuda.synchronize(); t1 = time.perf_counter()
+        h.node_forward_record_ts(xd, 0.0, 1.0, TOL, TOL, times, mode="unbiased", t1_or_rand=0.37, maxiters=100000)
+        torch.cuda.synchronize(); t2 = time.perf_counter()
+        h.node_backward_recorded_ts(cots, w_reg=10.0)
+        torch.cuda.synchronize(); t3 = time.perf_counter()
+        if i >= 3:
+            full.append((t1 - t0) * 1e3); bwd.append((t3 - t2) * 1e3)
+    sb = info["stats_bwd"]
+    attempts = sb["naccept"] + sb["nreject"]
+    ai = h.last_adjoint_info() if hasattr(h, "last_adjoint_info") else None
+    med = statistics.median
+    return dict(ntimes=len(times), pullback_ms=round(med(full), 3), pullback_ms_min=round(min(full), 3), pullback_ms_max=round(max(full), 3),
+                backward_ms=round(med(bwd), 3), backward_ms_min=round(min(bwd), 3), backward_ms_max=round(max(bwd), 3),
+                adjoint_naccept=sb["naccept"], adjoint_nreject=sb["nreject"], adjoint_attempts=attempts,
+                us_per_adjoint_attempt=round(1e3 * med(bwd) / max(attempts, 1), 2), adjoint_loop=info.get("adjoint_loop"),
+                launches_per_attempt=round(ai["launches"] / max(attempts, 1), 3) if ai else None,
+                host_waits=ai["host_waits"] if ai else None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--bwd-reps", type=int, default=30)
     ap.add_argument("--B", type=int, default=512)
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -111,6 +143,11 @@ def main():
         torch.cuda.synchronize(); t2 = time.perf_counter()
         if i:
             fwd.append((t1 - t0) * 1e3); fb.append((t2 - t0) * 1e3)
+    legs = []
+    for times in (SAVEAT, [(i + 1) / 49.0 for i in range(49)]):
+        nd = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, saveat=times, save_start=False, maxiters=100000,
+                         field="dense_chain")
+        legs.append(pullback_leg(nd, nd._bind(ps), xd, ps, st, times, B, args.bwd_reps))
     Ws, o = [], 0
     for l in model.layers[1:]:
         n, k = l.out_dims, l.in_dims
@@ -126,7 +163,8 @@ def main():
         solve_kernel_ms=round(solve_ms, 3), step_launches=launches, launches_per_attempt=round(launches / max(attempts, 1), 3),
         us_per_attempt_solve=round(1e3 * solve_ms / max(attempts, 1), 2),
         layer_forward_ms=round(statistics.median(fwd), 3), layer_forward_pullback_ms=round(statistics.median(fb), 3),
-        eager_torch_fp32_solve_ms=round(eager_ms, 2), eager_naccept=ena, eager_nreject=enr, eager_vs_hip_u_end=err)))
+        eager_torch_fp32_solve_ms=round(eager_ms, 2), eager_naccept=ena, eager_nreject=enr, eager_vs_hip_u_end=err,
+        adj_host=bool(os.environ.get("LRNDE_ADJ_HOST")), pullback_series4=legs[0], pullback_series49=legs[1])))
 
 
 if __name__ == "__main__":
