@@ -112,11 +112,17 @@ def rel(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
-def mk(P, model, B, scale=1.0, seed=0, noise=0.01):
-    from localregneuralde_jl_amd.layers import Handle, _chain_desc
+def mk_inputs(P, model, B, scale=1.0, seed=0, noise=0.01):
+    """(p, x) of mk, without a handle (the CPU tests of the restatement use the same inputs)"""
     p = P.glorot_chain_params(model, seed=seed, scale=scale)
     p = (p + np.random.default_rng(seed + 1).standard_normal(p.size).astype(np.float32) * np.float32(noise)).astype(np.float32)
     x = (np.random.default_rng(seed + 2).random((B, spec(model)[2][0][0]), dtype=np.float32) - np.float32(0.5)) * np.float32(2)
+    return p, x
+
+
+def mk(P, model, B, scale=1.0, seed=0, noise=0.01):
+    from localregneuralde_jl_amd.layers import Handle, _chain_desc
+    p, x = mk_inputs(P, model, B, scale, seed, noise)
     h = Handle(_chain_desc(model))
     h.set_params(torch.from_numpy(p))
     return h, p, x
@@ -132,11 +138,19 @@ def shapes(P):
         "sixteen": P.Chain(P.Activation("gelu"), *[P.Dense(24, 24, "tanh") for _ in range(16)]),
         "w128_td": P.TDChain(P.Chain(P.Dense(129, 128, "tanh"))),
         "w128_64_td": P.TDChain(P.Chain(P.Dense(129, 64, "gelu"), P.Dense(65, 128))),
+        # odd widths: the second row of chain_layer's float2 pair is k_pack_chain's zero padding; D = 1
+        "odd_21_37": P.Chain(P.Activation("tanh"), P.Dense(21, 37, "tanh"), P.Dense(37, 21, "tanh")),
+        "odd_td_127_33": P.TDChain(P.Chain(P.Dense(128, 33, "tanh"), P.Dense(34, 127))),
+        "width_1": P.Chain(P.Dense(1, 5, "tanh"), P.Dense(5, 1)),
     }
 
 
+ODD = ("odd_21_37", "odd_td_127_33", "width_1")
+
+
 @pytest.mark.parametrize("name,B", [("physionet", 1), ("physionet", 37), ("physionet", 512), ("td3_tanh", 19), ("td3_gelu", 19),
-                                    ("one_layer", 5), ("sixteen", 9), ("w128_td", 11), ("w128_64_td", 13)])
+                                    ("one_layer", 5), ("sixteen", 9), ("w128_td", 11), ("w128_64_td", 13),
+                                    ("odd_21_37", 9), ("odd_td_127_33", 11), ("width_1", 7), ("width_1", 1)])
 def test_rhs_and_vjp_vs_float64(gpu_pkg, name, B):
     P = gpu_pkg
     model = shapes(P)[name]
@@ -156,9 +170,10 @@ def test_rhs_and_vjp_vs_float64(gpu_pkg, name, B):
     assert err(gp.cpu().numpy(), pt.grad.numpy()) <= 1e-5, (name, "gp", err(gp.cpu().numpy(), pt.grad.numpy()))
 
 
-def test_columns_are_independent_and_runs_repeat_bitwise(gpu_pkg):
+@pytest.mark.parametrize("name", ("physionet",) + ODD)
+def test_columns_are_independent_and_runs_repeat_bitwise(gpu_pkg, name):
     P = gpu_pkg
-    model = physionet(P)
+    model = shapes(P)[name]
     h, p, x = mk(P, model, 512)
     xd = torch.from_numpy(x).cuda()
     k1 = torch.from_numpy(Chain64(model, p)(x, 0.2)).cuda()
@@ -178,14 +193,15 @@ def test_columns_are_independent_and_runs_repeat_bitwise(gpu_pkg):
                        field="dense_chain")
     st = node.initialstates(np.random.default_rng(1))
     ps = torch.from_numpy(p).cuda()
-    cots = torch.from_numpy(np.random.default_rng(4).standard_normal((3, 512, 20)).astype(np.float32)).cuda()
+    cots = torch.from_numpy(np.random.default_rng(4).standard_normal((3, 512, x.shape[1])).astype(np.float32)).cuda()
     runs = [node.pullback(xd, ps, st, cots, w_reg=2.0) for _ in range(2)]
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
     assert torch.equal(runs[0][2]["sol_u"], runs[1][2]["sol_u"])
 
 
 @pytest.mark.parametrize("name,scale", [("physionet", 1.0), ("physionet", 3.0), ("td3_tanh", 1.0), ("td3_tanh", 3.0),
-                                        ("td3_gelu", 3.0), ("sixteen", 1.0)])
+                                        ("td3_gelu", 3.0), ("sixteen", 1.0), ("odd_21_37", 1.0), ("odd_td_127_33", 1.0),
+                                        ("odd_td_127_33", 3.0), ("width_1", 1.0)])
 def test_perform_step_vs_float64(gpu_pkg, name, scale):
     P = gpu_pkg
     model = shapes(P)[name]
