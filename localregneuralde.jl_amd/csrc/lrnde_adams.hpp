@@ -90,8 +90,7 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
   const size_t n = (size_t)B * c->desc.state_dim;
   const bool moulton = c->solver_alg == 2;
   const float abstol = o->abstol, reltol = o->reltol;
-  const float gamma = 0.9f, qmin = 0.2f, qmax = 10.0f, qoldinit = 1e-4f;
-  const float beta1 = (float)(7.0 / 30.0), beta2 = (float)(2.0 / 15.0);
+  const PiConsts pi = pi_order3();
   // workspace: 16 vectors of the state's size in the adjoint's allocation (a backward pass overwrites them; nothing of the
   // forward lives there once this returns)
   AdjVec v;
@@ -122,25 +121,15 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
     if ((rc = lrnde_rhs(c, uprev, t0, B, k1))) return rc;
     if ((rc = vec_norm(c, uprev, nullptr, uprev, nullptr, abstol, reltol, n, 0, &d0))) return rc;
     if ((rc = vec_norm(c, k1, nullptr, uprev, nullptr, abstol, reltol, n, 0, &d1))) return rc;
-    float dt0 = ((double)d0 < 1e-5 || (double)d1 < 1e-5) ? 1e-6f : (d0 / d1) / 100.0f;
-    dt0 = fminf(dt0, dtmax);
+    const float dt0 = initdt_dt0(d0, d1, dtmax);
     const float one = 1.0f; const float* kk[1] = {k1};
     if ((rc = vec_axpy(c, tmp, uprev, dt0, 1, kk, &one, n))) return rc;
     if ((rc = lrnde_rhs(c, tmp, t0 + dt0, B, kb2))) return rc;
     if ((rc = vec_norm(c, kb2, k1, uprev, nullptr, abstol, reltol, n, 0, &d2))) return rc;
-    d2 = d2 / dt0;
-    const float maxd = fmaxf(d1, d2);
-    float dt1;
-    if ((double)maxd <= 1e-15) dt1 = fmaxf(1e-6f, dt0 * 1e-3f);
-    else {
-      const float l10 = (float)log10((double)maxd);
-      const float e = (-(2.0f + l10)) / 3.0f;
-      dt1 = (float)pow(10.0, (double)e);
-    }
-    dt = fminf(fminf(100.0f * dt0, dt1), dtmax);
+    dt = initdt_tail(dt0, d1, d2, 3.0f, dtmax);
   }
   st->nf = 3; st->dt_init = dt;
-  float qold = qoldinit, q11 = 1.0f, dtpropose = dt;
+  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
   float h1 = 0.0f, h2 = 0.0f;
   int accept = 0, iter = 0, status = LRNDE_OK;
   if (o->save_start && (rc = push_save(t0, u0))) return rc;
@@ -158,16 +147,12 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
         std::swap(sp2, s2);
         dt = dtpropose;
       } else {
-        dt = dt / fminf(1.0f / qmin, q11 / gamma);
+        dt = pi_reject_dt(pi, dt, q11);
       }
     }
     ++iter;
-    dt = fminf(dtmax, dt);
-    dt = fmaxf(dt, dtmin);
-    dt = fminf(fabsf(dt), fabsf(t1 - t));
-    if (iter > o->maxiters) { status = LRNDE_MAXITERS; break; }
-    if (dt != dt) { status = LRNDE_DT_NAN; break; }
-    if (fabsf(dt) <= fabsf(dtmin)) { status = LRNDE_DT_LESS_THAN_MIN; break; }
+    dt = header_clamp(dt, dtmax, dtmin, t, t1);
+    if ((status = header_status(iter, o->maxiters, dt, dtmin))) break;
     const int nacc = st->naccept;
     const float b2 = nacc >= 1 ? dt / h1 : 0.0f;
     const float b3 = nacc >= 2 ? b2 * ((dt + h1) / (h1 + h2)) : 0.0f;
@@ -219,25 +204,18 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
       launches += moulton ? 4 : 3;
     }
     if (eest != eest) { status = LRNDE_DT_NAN; st->eest_last = eest; break; }
-    const float ttmp = t + dt;
-    float q;
-    if (eest == 0.0f) q = 1.0f / qmax;
-    else {
-      if (o->exact_pow) { q11 = (float)pow((double)eest, (double)beta1); q = q11 / (float)pow((double)qold, (double)beta2); }
-      else { q11 = fastpow(eest, beta1); q = q11 / fastpow(qold, beta2); }
-      q = fmaxf(1.0f / qmax, fminf(1.0f / qmin, q / gamma));
-    }
+    const PiStep ps = pi_step(pi, o->exact_pow, eest, pi_pow(o->exact_pow, qold, pi.beta2), q11);
+    q11 = ps.q11;
     accept = (eest <= 1.0f);
     if (trace_host && ntrace < cap_trace) { trace_host[ntrace].t = t; trace_host[ntrace].dt = dt; trace_host[ntrace].eest = eest; trace_host[ntrace].accepted = accept; ++ntrace; }
     st->eest_last = eest;
     if (accept) {
       const int idx = st->naccept;
       st->naccept++;
-      const float dtnew = dt / q;
-      qold = fmaxf(eest, qoldinit);
+      qold = pi_qold(eest);
       const float tprev = t;
-      t = (fabsf(ttmp - t1) < 100.0f * eps_f(fmaxf(fabsf(t), fabsf(t1)))) ? t1 : ttmp;
-      dtpropose = fmaxf(fminf(dtmax, dtnew), fmaxf(eps_f(t), dtmin));
+      t = snap_magnitude(t, dt, t1);
+      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
       h2 = h1; h1 = dt;
       bool need_poly = c->dense_on;
       for (int i = isave; i < nsave && saveat_host[i] <= t; ++i) if (saveat_host[i] != t) need_poly = true;

@@ -180,11 +180,6 @@ __device__ __forceinline__ AdjStage adj_lookup_lanes(const AdjArgs& g, const Adj
   return s;
 }
 
-__device__ __forceinline__ float adj_dt0(float d0, float d1, float dtmax) {
-  float dt0 = ((double)d0 < 1e-5 || (double)d1 < 1e-5) ? 1e-6f : (d0 / d1) / 100.0f;
-  return fminf_(dt0, dtmax);
-}
-
 // the pinned progress block (host view: volatile int hs[16]): [0] seq (written last, release), [1] status, [2] t, [3] dt,
 // [4] cur, [5] nf, [6] naccept, [7] nreject, [8] iter, [9] eest_last, [10] dt_init — everything the host driver needs of
 // the integrator's state, so that a finished solve costs no read-back copy and no synchronisation of its own
@@ -213,6 +208,41 @@ __device__ __forceinline__ void adj_publish(const AdjArgs& g, AdjCtrl* cout, con
   stwt(g.sync, g.seq0 + j + 1);
 }
 
+// The header of an attempt that starts at reversed time t with the controller's dt, for both device adjoint loops (wave
+// 0): the end of the solve, the next tstop (stop_l: lane i holds stops[i]), loopheader!'s clamp and status, and the
+// dense-record position of each of the six stage times.  Leaves t, the clamped dt and first = 0 in c.
+__device__ __forceinline__ void adj_header(const AdjArgs& g, AdjCtrl& c, const AdjRecLanes& rec, float stop_l, float t, float dt) {
+  const int lane = threadIdx.x & 63;
+  if (c.status == ST_RUNNING) {
+    if (!(t < g.s1)) {
+      c.status = ST_DONE;
+    } else {
+      float tstop = g.s1;
+      if (g.nstops <= 64) {   // (ascending: the entries from istop on that t has reached are a prefix)
+        c.istop += __popcll(__ballot(lane >= c.istop && lane < g.nstops && stop_l <= t));
+        if (c.istop < g.nstops) {
+          const float sv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, stop_l), c.istop));
+          if (sv < g.s1) tstop = sv;
+        }
+      } else {
+        while (c.istop < g.nstops && g.stops[c.istop] <= t) ++c.istop;
+        if (c.istop < g.nstops && g.stops[c.istop] < g.s1) tstop = g.stops[c.istop];
+      }
+      c.iter++;
+      dt = header_clamp(dt, g.dtmax, g.dtmin, t, tstop);
+      const int hs = header_status(c.iter, g.maxiters, dt, g.dtmin);
+      if (hs != STEP_OK) c.status = hs;
+      else {
+        c.do_step = 1; c.nf += 6; c.tstop = tstop;
+        const float cs[6] = {(float)Tsit5::C[0], (float)Tsit5::C[1], (float)Tsit5::C[2], (float)Tsit5::C[3], 1.0f, 1.0f};
+#pragma unroll
+        for (int q = 0; q < 6; ++q) c.st[q] = adj_lookup_lanes(g, rec, -(t + cs[q] * dt));
+      }
+    }
+  }
+  c.t = t; c.dt = dt; c.first = 0;
+}
+
 // footer of attempt j-1 + header of attempt j (wave 0 of every workgroup; identical inputs => identical results).
 // Returns the control block of attempt j; block 0 also publishes it to ctl[(j+1)&1].
 __device__ __forceinline__ AdjCtrl adj_prologue(const AdjArgs& g, int j) {
@@ -237,27 +267,17 @@ __device__ __forceinline__ AdjCtrl adj_prologue(const AdjArgs& g, int j) {
     }
     return c;
   }
-  const float gamma = 0.9f, qmin = 0.2f, qmax = 10.0f, qoldinit = 1e-4f;
-  const float beta1 = (float)(7.0 / 50.0), beta2 = (float)(2.0 / 25.0);
+  const PiConsts pi = pi_tsit5();
   const float dtmax = g.dtmax, dtmin = g.dtmin;
   const double ntot = (double)g.n_lam * (double)(g.use_slots ? g.nranks : 1) + (double)g.P;
   float t = c.t, dt = c.dt;
-  int accepted = 0;
   if (c.first) {
     // ode_determine_initdt from the partial sums of d1 and d2; dt0 was fixed by init phase B
     const float d1 = (float)sqrt(adj_norm_sum(g.ipart + 576, g.use_slots, g.nranks, g.P != 0) / ntot);
-    const float d2 = (float)sqrt(adj_norm_sum(g.ipart + 2 * 576, g.use_slots, g.nranks, g.P != 0) / ntot) / c.dt0;
-    const float maxd = fmaxf_(d1, d2);
-    float dt1;
-    if ((double)maxd <= 1e-15) dt1 = fmaxf_(1e-6f, c.dt0 * 1e-3f);
-    else {
-      const float l10 = (float)log10((double)maxd);
-      const float e = (-(2.0f + l10)) / 5.0f;
-      dt1 = (float)pow(10.0, (double)e);
-    }
-    dt = fminf_(fminf_(100.0f * c.dt0, dt1), dtmax);
+    const float d2 = (float)sqrt(adj_norm_sum(g.ipart + 2 * 576, g.use_slots, g.nranks, g.P != 0) / ntot);
+    dt = initdt_tail(c.dt0, d1, d2, 5.0f, dtmax);
     c.nf = 3; c.dt_init = dt; c.dtpropose = dt;
-    c.qold = qoldinit; c.q11 = 1.0f;
+    c.qold = QOLDINIT; c.q11 = 1.0f;
   } else if (c.resume) {
     dt = c.dtpropose;
     c.resume = 0;
@@ -267,61 +287,22 @@ __device__ __forceinline__ AdjCtrl adj_prologue(const AdjArgs& g, int j) {
     if (eest != eest) {
       c.status = LRNDE_DT_NAN;
     } else {
-      float q;
-      if (eest == 0.0f) q = 1.0f / qmax;
-      else {
-        if (g.exact_pow) { c.q11 = (float)pow((double)eest, (double)beta1); q = c.q11 / (float)pow((double)c.qold, (double)beta2); }
-        else { c.q11 = fastpow(eest, beta1); q = c.q11 / fastpow(c.qold, beta2); }
-        q = fmaxf_(1.0f / qmax, fminf_(1.0f / qmin, q / gamma));
-      }
-      accepted = (eest <= 1.0f);
-      if (accepted) {
+      const PiStep ps = pi_step(pi, g.exact_pow, eest, pi_pow(g.exact_pow, c.qold, pi.beta2), c.q11);
+      c.q11 = ps.q11;
+      if (eest <= 1.0f) {
         c.naccept++;
-        const float dtnew = c.dt / q;
-        c.qold = fmaxf_(eest, qoldinit);
-        const float ttmp = c.t + c.dt;
-        // (magnitudes: see vec_tsit5_solve)
-        t = (__builtin_fabsf(ttmp - c.tstop) < 100.0f * eps_f(fmaxf_(__builtin_fabsf(c.t), __builtin_fabsf(c.tstop)))) ? c.tstop : ttmp;
-        c.dtpropose = fmaxf_(fminf_(dtmax, dtnew), fmaxf_(eps_f(t), dtmin));
+        c.qold = pi_qold(eest);
+        t = snap_magnitude(c.t, c.dt, c.tstop);
+        c.dtpropose = pi_propose(c.dt, ps.q, dtmax, dt_floor(t, dtmin));
         c.cur ^= 1;  // z <- z_new, K1 <- K7 (FSAL)
         dt = c.dtpropose;
       } else {
         c.nreject++;
-        dt = c.dt / fminf_(1.0f / qmin, c.q11 / gamma);
+        dt = pi_reject_dt(pi, c.dt, c.q11);
       }
     }
   }
-  if (c.status == ST_RUNNING) {
-    if (!(t < g.s1)) {
-      c.status = ST_DONE;
-    } else {
-      float tstop = g.s1;
-      if (g.nstops <= 64) {   // (ascending: the entries from istop on that t has reached are a prefix)
-        c.istop += __popcll(__ballot(lane >= c.istop && lane < g.nstops && stop_l <= t));
-        if (c.istop < g.nstops) {
-          const float sv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, stop_l), c.istop));
-          if (sv < g.s1) tstop = sv;
-        }
-      } else {
-        while (c.istop < g.nstops && g.stops[c.istop] <= t) ++c.istop;
-        if (c.istop < g.nstops && g.stops[c.istop] < g.s1) tstop = g.stops[c.istop];
-      }
-      c.iter++;
-      dt = fminf_(dtmax, dt);
-      dt = fmaxf_(dt, dtmin);
-      dt = fminf_(__builtin_fabsf(dt), __builtin_fabsf(tstop - t));
-      if (c.iter > g.maxiters) c.status = LRNDE_MAXITERS;
-      else if (dt != dt) c.status = LRNDE_DT_NAN;
-      else if (__builtin_fabsf(dt) <= __builtin_fabsf(dtmin)) c.status = LRNDE_DT_LESS_THAN_MIN;
-      else {
-        c.do_step = 1; c.nf += 6; c.tstop = tstop;
-        const float cs[6] = {(float)Tsit5::C[0], (float)Tsit5::C[1], (float)Tsit5::C[2], (float)Tsit5::C[3], 1.0f, 1.0f};
-#pragma unroll
-        for (int q = 0; q < 6; ++q) c.st[q] = adj_lookup_lanes(g, rec, -(t + cs[q] * dt));
-      }
-    }
-  }
-  c.t = t; c.dt = dt; c.first = 0;
+  adj_header(g, c, rec, stop_l, t, dt);
   if (blockIdx.x == 0 && lane == 0) {
     if (g.sync) adj_publish(g, cout, c, j);
     else *cout = c;
@@ -338,7 +319,7 @@ __global__ void k_adj_ctrl_init(AdjCtrl* ctl, float s0) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   AdjCtrl c;
   memset(&c, 0, sizeof(c));
-  c.status = ST_RUNNING; c.first = 1; c.t = s0; c.qold = 1e-4f; c.q11 = 1.0f;
+  c.status = ST_RUNNING; c.first = 1; c.t = s0; c.qold = QOLDINIT; c.q11 = 1.0f;
   ctl[0] = c; ctl[1] = c;
 }
 
@@ -351,7 +332,7 @@ __global__ __launch_bounds__(256) void k_adj_begin(AdjBegin a) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   AdjCtrl c;
   memset(&c, 0, sizeof(c));
-  c.status = ST_RUNNING; c.first = 1; c.t = a.s0; c.qold = 1e-4f; c.q11 = 1.0f;
+  c.status = ST_RUNNING; c.first = 1; c.t = a.s0; c.qold = QOLDINIT; c.q11 = 1.0f;
   a.ctl[0] = c; a.ctl[1] = c;
   for (int k = 0; k < a.nstops; ++k) a.stops[k] = a.sv[k];
 }

@@ -938,7 +938,7 @@ __device__ __forceinline__ bool vjp_q_resolve(VjpQArgs& a, const AdjEarly& early
         const double ntot = (double)g.n_lam * (double)(g.use_slots ? g.nranks : 1) + (double)g.P;
         const float d0 = (float)sqrt(adj_norm_sum(g.ipart, g.use_slots, g.nranks, g.P != 0) / ntot);
         const float d1 = (float)sqrt(adj_norm_sum(g.ipart + 576, g.use_slots, g.nranks, g.P != 0) / ntot);
-        c.dt0 = adj_dt0(d0, d1, g.dtmax);
+        c.dt0 = initdt_dt0(d0, d1, g.dtmax);
         c.st[0] = adj_lookup(g, -(c.t + c.dt0));
       }
       c.do_step = 1;

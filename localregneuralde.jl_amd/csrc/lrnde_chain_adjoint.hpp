@@ -74,7 +74,7 @@ __device__ __forceinline__ void chadj_report(const ChAdjArgs& a, const ChAdjCtrl
 }
 
 // footer of attempt j-1 + header of attempt j (wave 0 of every workgroup, identical inputs => identical results):
-// adj_prologue's controller (vec_tsit5_solve's arithmetic) with the impulses handled in place
+// adj_prologue's, with the cotangent impulses handled in place
 __device__ __forceinline__ ChAdjCtrl chadj_prologue(const ChAdjArgs& a, int j) {
   const AdjArgs& g = a.g;
   const int lane = threadIdx.x & 63;
@@ -88,8 +88,7 @@ __device__ __forceinline__ ChAdjCtrl chadj_prologue(const ChAdjArgs& a, int j) {
     if (pub) chadj_report(a, cc, j);
     return cc;
   }
-  const float gamma = 0.9f, qmin = 0.2f, qmax = 10.0f, qoldinit = 1e-4f;
-  const float beta1 = (float)(7.0 / 50.0), beta2 = (float)(2.0 / 25.0);
+  const PiConsts pi = pi_tsit5();
   const float dtmax = g.dtmax, dtmin = g.dtmin;
   const double ntot = (double)g.n_lam + (double)g.P;
   float t = c.t, dt = c.dt;
@@ -97,39 +96,24 @@ __device__ __forceinline__ ChAdjCtrl chadj_prologue(const ChAdjArgs& a, int j) {
     // ode_determine_initdt from the partial sums of d0, d1 (dt0, as init phase B formed it) and d2
     const float d0 = (float)sqrt(chadj_sum(chadj_set(a, 0), a.np) / ntot);
     const float d1 = (float)sqrt(chadj_sum(chadj_set(a, 1), a.np) / ntot);
-    const float dt0 = adj_dt0(d0, d1, dtmax);
-    const float d2 = (float)sqrt(chadj_sum(chadj_set(a, 2), a.np) / ntot) / dt0;
-    const float maxd = fmaxf_(d1, d2);
-    float dt1;
-    if ((double)maxd <= 1e-15) dt1 = fmaxf_(1e-6f, dt0 * 1e-3f);
-    else {
-      const float l10 = (float)log10((double)maxd);
-      const float e = (-(2.0f + l10)) / 5.0f;
-      dt1 = (float)pow(10.0, (double)e);
-    }
-    dt = fminf_(fminf_(100.0f * dt0, dt1), dtmax);
+    const float d2 = (float)sqrt(chadj_sum(chadj_set(a, 2), a.np) / ntot);
+    const float dt0 = initdt_dt0(d0, d1, dtmax);
+    dt = initdt_tail(dt0, d1, d2, 5.0f, dtmax);
     c.dt0 = dt0; c.nf = 3; c.dt_init = dt; c.dtpropose = dt;
-    c.qold = qoldinit; c.q11 = 1.0f;
+    c.qold = QOLDINIT; c.q11 = 1.0f;
   } else {
     const float eest = (float)sqrt(chadj_sum(chadj_set(a, 3 + ((j + 1) & 1)), a.np) / ntot);
     c.eest_last = eest;
     if (eest != eest) {
       c.status = LRNDE_DT_NAN;
     } else {
-      float q;
-      if (eest == 0.0f) q = 1.0f / qmax;
-      else {
-        if (g.exact_pow) { c.q11 = (float)pow((double)eest, (double)beta1); q = c.q11 / (float)pow((double)c.qold, (double)beta2); }
-        else { c.q11 = fastpow(eest, beta1); q = c.q11 / fastpow(c.qold, beta2); }
-        q = fmaxf_(1.0f / qmax, fminf_(1.0f / qmin, q / gamma));
-      }
+      const PiStep ps = pi_step(pi, g.exact_pow, eest, pi_pow(g.exact_pow, c.qold, pi.beta2), c.q11);
+      c.q11 = ps.q11;
       if (eest <= 1.0f) {
         c.naccept++;
-        const float dtnew = c.dt / q;
-        c.qold = fmaxf_(eest, qoldinit);
-        const float ttmp = c.t + c.dt;
-        t = (__builtin_fabsf(ttmp - c.tstop) < 100.0f * eps_f(fmaxf_(__builtin_fabsf(c.t), __builtin_fabsf(c.tstop)))) ? c.tstop : ttmp;
-        c.dtpropose = fmaxf_(fminf_(dtmax, dtnew), fmaxf_(eps_f(t), dtmin));
+        c.qold = pi_qold(eest);
+        t = snap_magnitude(c.t, c.dt, c.tstop);
+        c.dtpropose = pi_propose(c.dt, ps.q, dtmax, dt_floor(t, dtmin));
         c.cur ^= 1;  // z <- z_new, K1 <- K7 (FSAL)
         dt = c.dtpropose;
         // a cotangent impulse at the saved time just reached (vec_tsit5_solve: lambda += du, K1 re-evaluated, nf += 1)
@@ -140,42 +124,12 @@ __device__ __forceinline__ ChAdjCtrl chadj_prologue(const ChAdjArgs& a, int j) {
         if (cc.imp1 > cc.imp0) { cc.hit = 1; c.nf += 1; cc.st_hit = adj_lookup_lanes(g, rec, -t); }
       } else {
         c.nreject++;
-        dt = c.dt / fminf_(1.0f / qmin, c.q11 / gamma);
+        dt = pi_reject_dt(pi, c.dt, c.q11);
       }
     }
   }
-  if (c.status == ST_RUNNING) {
-    if (!(t < g.s1)) {
-      c.status = ST_DONE;
-      cc.hit = 0;
-    } else {
-      float tstop = g.s1;
-      if (g.nstops <= 64) {
-        c.istop += __popcll(__ballot(lane >= c.istop && lane < g.nstops && stop_l <= t));
-        if (c.istop < g.nstops) {
-          const float sv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, stop_l), c.istop));
-          if (sv < g.s1) tstop = sv;
-        }
-      } else {
-        while (c.istop < g.nstops && g.stops[c.istop] <= t) ++c.istop;
-        if (c.istop < g.nstops && g.stops[c.istop] < g.s1) tstop = g.stops[c.istop];
-      }
-      c.iter++;
-      dt = fminf_(dtmax, dt);
-      dt = fmaxf_(dt, dtmin);
-      dt = fminf_(__builtin_fabsf(dt), __builtin_fabsf(tstop - t));
-      if (c.iter > g.maxiters) c.status = LRNDE_MAXITERS;
-      else if (dt != dt) c.status = LRNDE_DT_NAN;
-      else if (__builtin_fabsf(dt) <= __builtin_fabsf(dtmin)) c.status = LRNDE_DT_LESS_THAN_MIN;
-      else {
-        c.do_step = 1; c.nf += 6; c.tstop = tstop;
-        const float cs[6] = {(float)Tsit5::C[0], (float)Tsit5::C[1], (float)Tsit5::C[2], (float)Tsit5::C[3], 1.0f, 1.0f};
-#pragma unroll
-        for (int q = 0; q < 6; ++q) c.st[q] = adj_lookup_lanes(g, rec, -(t + cs[q] * dt));
-      }
-    }
-  }
-  c.t = t; c.dt = dt; c.first = 0;
+  adj_header(g, c, rec, stop_l, t, dt);
+  if (c.status == ST_DONE) cc.hit = 0;
   if (pub) chadj_report(a, cc, j);
   return cc;
 }
@@ -297,7 +251,7 @@ __global__ __launch_bounds__(NT) void k_chadj_step(ChAdjArgs a, ChainDev cd, int
         const double ntot = (double)g.n_lam + (double)g.P;
         const float d0 = (float)sqrt(chadj_sum(chadj_set(a, 0), a.np) / ntot);
         const float d1 = (float)sqrt(chadj_sum(chadj_set(a, 1), a.np) / ntot);
-        cc.c.dt0 = adj_dt0(d0, d1, g.dtmax);
+        cc.c.dt0 = initdt_dt0(d0, d1, g.dtmax);
         ts = g.s0 + cc.c.dt0;
       }
       cc.st_hit = adj_lookup_lanes(g, rec, -ts);
@@ -526,6 +480,6 @@ __global__ __launch_bounds__(64) void k_chadj_begin(ChAdjBegin b) {
   if (lane != 0 || !b.init) return;
   ChAdjCtrl c;
   memset(&c, 0, sizeof(c));
-  c.c.status = ST_RUNNING; c.c.first = 1; c.c.t = b.s0; c.c.qold = 1e-4f; c.c.q11 = 1.0f;
+  c.c.status = ST_RUNNING; c.c.first = 1; c.c.t = b.s0; c.c.qold = QOLDINIT; c.c.q11 = 1.0f;
   b.cc[0] = c; b.cc[1] = c;
 }

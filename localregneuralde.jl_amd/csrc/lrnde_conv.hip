@@ -42,6 +42,10 @@
 #include "lrnde.h"
 #include "lrnde_hooks.h"
 #include "lrnde_math.hpp"
+#include "lrnde_stepctl.hpp"
+static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
+              (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
+              "header_status returns lrnde_status values");
 
 using namespace lrnde;
 
@@ -2029,19 +2033,13 @@ int init_dt_g(lrnde_conv* c, size_t n, RHS&& rhs, const float* u0, float t0, flo
   hipLaunchKernelGGL(k_sums_init, dim3(NSUMB), dim3(256), 0, c->stream, u0, f0, (const float*)nullptr, abstol, reltol, n, c->sums);
   if ((rc = fetch_sums(c, s))) return rc;
   const float d0 = (float)sqrt(s[0] / (double)n), d1 = (float)sqrt(s[1] / (double)n);
-  float dt0 = ((double)d0 < 1e-5 || (double)d1 < 1e-5) ? 1e-6f : (d0 / d1) / 100.0f;
-  dt0 = fminf(dt0, dtmax);
+  const float dt0 = initdt_dt0(d0, d1, dtmax);
   const float* kk[1] = {f0};
   if ((rc = lincomb(c, tmp, u0, 0.f, 1, kk, &dt0, n))) return rc;
   if ((rc = rhs(tmp, t0 + dt0, f1))) return rc;
   hipLaunchKernelGGL(k_sums_init, dim3(NSUMB), dim3(256), 0, c->stream, u0, f0, (const float*)f1, abstol, reltol, n, c->sums);
   if ((rc = fetch_sums(c, s))) return rc;
-  const float d2 = (float)sqrt(s[2] / (double)n) / dt0;
-  const float maxd = fmaxf(d1, d2);
-  float dt1;
-  if ((double)maxd <= 1e-15) dt1 = fmaxf(1e-6f, dt0 * 1e-3f);
-  else { const float l10 = (float)log10((double)maxd); const float e = (-(2.0f + l10)) / 5.0f; dt1 = (float)pow(10.0, (double)e); }
-  *dt_out = fminf(fminf(100.0f * dt0, dt1), dtmax);
+  *dt_out = initdt_tail(dt0, d1, (float)sqrt(s[2] / (double)n), 5.0f, dtmax);
   return LRNDE_OK;
 }
 
@@ -2298,8 +2296,7 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
   for (int i = 1; i < nsave; ++i) if (!(saveat[i] >= saveat[i - 1])) return cfail(c, LRNDE_BADARG, "saveat must be sorted");
   const size_t n = state_n(c, B);
   const float abstol = o->abstol, reltol = o->reltol;
-  const float gamma = 0.9f, qmin = 0.2f, qmax = 10.0f, qoldinit = 1e-4f;
-  const float beta1 = (float)(7.0 / 50.0), beta2 = (float)(2.0 / 25.0);
+  const PiConsts pi = pi_tsit5();
   float* V = c->vec;
   float *uprev = V, *u = V + n, *k1 = V + 2 * n, *ks = V + 3 * n, *k7 = V + 8 * n, *g6 = V + 9 * n, *tmp = V + 10 * n;
   int nsaved = 0, isave = 0, ntrace = 0;
@@ -2321,7 +2318,7 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
   float dt;
   if ((rc = init_dt(c, uprev, B, t0, t1, abstol, reltol, k1, tmp, g6, &dt))) return rc;
   st->nf = 3; st->dt_init = dt;
-  float qold = qoldinit, q11 = 1.0f, dtpropose = dt;
+  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
   int accept = 0, iter = 0;
   if (o->save_start && (rc = push(t0, uprev))) return rc;
   while (isave < nsave && saveat[isave] <= t0) isave++;
@@ -2329,13 +2326,11 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
   while (t < t1) {
     if (iter > 0) {
       if (accept) { std::swap(uprev, u); std::swap(k1, k7); dt = dtpropose; }
-      else dt = dt / fminf(1.0f / qmin, q11 / gamma);
+      else dt = pi_reject_dt(pi, dt, q11);
     }
     iter++;
-    dt = fminf(dtmax, dt); dt = fmaxf(dt, dtmin); dt = fminf(fabsf(dt), fabsf(t1 - t));
-    if (iter > o->maxiters) { rc = LRNDE_MAXITERS; break; }
-    if (dt != dt) { rc = LRNDE_DT_NAN; break; }
-    if (fabsf(dt) <= fabsf(dtmin)) { rc = LRNDE_DT_LESS_THAN_MIN; break; }
+    dt = header_clamp(dt, dtmax, dtmin, t, t1);
+    if ((rc = header_status(iter, o->maxiters, dt, dtmin))) break;
     double s[3];
     int r2;
     if ((r2 = tsit5_step(c, uprev, k1, B, t, dt, abstol, reltol, u, k7, ks, g6, tmp, s))) return r2;
@@ -2343,23 +2338,16 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
     const float eest = (float)sqrt(s[0] / (double)n);
     st->eest_last = eest;
     if (eest != eest) { rc = LRNDE_DT_NAN; break; }
-    const float ttmp = t + dt;
-    float q;
-    if (eest == 0.0f) q = 1.0f / qmax;
-    else {
-      if (o->exact_pow) { q11 = (float)pow((double)eest, (double)beta1); q = q11 / (float)pow((double)qold, (double)beta2); }
-      else { q11 = fastpow(eest, beta1); q = q11 / fastpow(qold, beta2); }
-      q = fmaxf(1.0f / qmax, fminf(1.0f / qmin, q / gamma));
-    }
+    const PiStep ps = pi_step(pi, o->exact_pow, eest, pi_pow(o->exact_pow, qold, pi.beta2), q11);
+    q11 = ps.q11;
     accept = (eest <= 1.0f);
     if (trace && ntrace < cap_trace) { trace[ntrace].t = t; trace[ntrace].dt = dt; trace[ntrace].eest = eest; trace[ntrace].accepted = accept; ntrace++; }
     if (accept) {
       st->naccept++;
-      const float dtnew = dt / q;
-      qold = fmaxf(eest, qoldinit);
+      qold = pi_qold(eest);
       const float tprev = t;
-      t = (fabsf(ttmp - t1) < 100.0f * eps_f(fmaxf(t, t1))) ? t1 : ttmp;
-      dtpropose = fmaxf(fminf(dtmax, dtnew), fmaxf(eps_f(t), dtmin));
+      t = snap_signed(t, dt, t1);
+      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
       if (c->dense_on) {  // [uprev, k1, k2..k6, k7] of this step, for the adjoint's interpolant
         const size_t idx = c->dense_t.size();
         if (c->dense_n != n) { for (float* d : c->dense) if (d) hipFree(d); c->dense.clear(); c->dense_n = n; }
@@ -2569,8 +2557,7 @@ template <class RHS>
 int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float s1, const lrnde_solve_opts* o,
                   const std::vector<float>& tstops, lrnde_stats* st) {
   const float abstol = o->abstol, reltol = o->reltol;
-  const float gamma = 0.9f, qmin = 0.2f, qmax = 10.0f, qoldinit = 1e-4f;
-  const float beta1 = (float)(7.0 / 50.0), beta2 = (float)(2.0 / 25.0);
+  const PiConsts pi = pi_tsit5();
   memset(st, 0, sizeof(*st));
   float *z = Z, *zn = Z + N, *k1 = Z + 2 * N, *ks = Z + 3 * N, *k7 = Z + 8 * N, *g6 = Z + 9 * N, *tmp = Z + 10 * N;
   int rc;
@@ -2580,7 +2567,7 @@ int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float 
   float dt;
   if ((rc = init_dt_g(c, N, rhs, z, s0, s1, abstol, reltol, k1, tmp, g6, &dt))) return rc;
   st->nf = 3; st->dt_init = dt;
-  float qold = qoldinit, q11 = 1.0f, dtpropose = dt;
+  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
   int accept = 0, iter = 0;
   size_t istop = 0;
   while (istop < tstops.size() && tstops[istop] <= s0) ++istop;
@@ -2590,13 +2577,11 @@ int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float 
     const float tstop = (istop < tstops.size() && tstops[istop] < s1) ? tstops[istop] : s1;
     if (iter > 0) {
       if (accept) { std::swap(z, zn); std::swap(k1, k7); dt = dtpropose; }
-      else dt = dt / fminf(1.0f / qmin, q11 / gamma);
+      else dt = pi_reject_dt(pi, dt, q11);
     }
     ++iter;
-    dt = fminf(dtmax, dt); dt = fmaxf(dt, dtmin); dt = fminf(fabsf(dt), fabsf(tstop - t));
-    if (iter > o->maxiters) { rc = LRNDE_MAXITERS; break; }
-    if (dt != dt) { rc = LRNDE_DT_NAN; break; }
-    if (fabsf(dt) <= fabsf(dtmin)) { rc = LRNDE_DT_LESS_THAN_MIN; break; }
+    dt = header_clamp(dt, dtmax, dtmin, t, tstop);
+    if ((rc = header_status(iter, o->maxiters, dt, dtmin))) break;
     double sm[3];
     int r2;
     // g6 doubles as the stage-6 state; its stiffness sums are not used here
@@ -2605,21 +2590,14 @@ int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float 
     const float eest = (float)sqrt(sm[0] / (double)N);
     st->eest_last = eest;
     if (eest != eest) { rc = LRNDE_DT_NAN; break; }
-    const float ttmp = t + dt;
-    float q;
-    if (eest == 0.0f) q = 1.0f / qmax;
-    else {
-      if (o->exact_pow) { q11 = (float)pow((double)eest, (double)beta1); q = q11 / (float)pow((double)qold, (double)beta2); }
-      else { q11 = fastpow(eest, beta1); q = q11 / fastpow(qold, beta2); }
-      q = fmaxf(1.0f / qmax, fminf(1.0f / qmin, q / gamma));
-    }
+    const PiStep ps = pi_step(pi, o->exact_pow, eest, pi_pow(o->exact_pow, qold, pi.beta2), q11);
+    q11 = ps.q11;
     accept = (eest <= 1.0f);
     if (accept) {
       st->naccept++;
-      const float dtnew = dt / q;
-      qold = fmaxf(eest, qoldinit);
-      t = (fabsf(ttmp - tstop) < 100.0f * eps_f(fmaxf(fabsf(t), fabsf(tstop)))) ? tstop : ttmp;  // (magnitudes: reversed time)
-      dtpropose = fmaxf(fminf(dtmax, dtnew), fmaxf(eps_f(t), dtmin));
+      qold = pi_qold(eest);
+      t = snap_magnitude(t, dt, tstop);  // (reversed time)
+      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
     } else st->nreject++;
   }
   if (accept && rc == LRNDE_OK) std::swap(z, zn);

@@ -47,7 +47,11 @@
 #include "lrnde.h"
 #include "lrnde_hooks.h"
 #include "lrnde_math.hpp"
+#include "lrnde_stepctl.hpp"
 #include "lrnde_comm.hpp"
+static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
+              (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
+              "header_status returns lrnde_status values");
 
 namespace {
 
@@ -203,7 +207,7 @@ __device__ __forceinline__ void solve_init_body(Ctrl* ctrl, float t0, int nsaved
   Ctrl c;
   memset(&c, 0, sizeof(c));
   c.status = ST_RUNNING; c.first = 1; c.cur = 0; c.nsaved = nsaved;
-  c.t = t0; c.dt = 0.f; c.qold = 1e-4f; c.q11 = 1.0f; c.dtpropose = 0.f;
+  c.t = t0; c.dt = 0.f; c.qold = QOLDINIT; c.q11 = 1.0f; c.dtpropose = 0.f;
   ctrl[0] = c;
   ctrl[1] = c;
   for (int i = 0; i < si.n; ++i) si.saveat[i] = si.v[i];
@@ -939,47 +943,13 @@ struct Bcast {
 };
 
 __device__ __forceinline__ float init_dt0(const double s[3], double n, float dtmax) {
-  const float d0 = rms_from(s[0], n), d1 = rms_from(s[1], n);
-  float dt0;
-  if ((double)d0 < 1e-5 || (double)d1 < 1e-5) dt0 = 1e-6f;
-  else dt0 = (d0 / d1) / 100.0f;
-  return fminf_(dt0, dtmax);
-}
-
-__device__ __forceinline__ float init_dt_final(const double s1[3], const double s2[3], double n,
-                                               float dtmax) {
-  const float d1 = rms_from(s1[1], n);
-  const float dt0 = init_dt0(s1, n, dtmax);
-  const float d2 = rms_from(s2[0], n) / dt0;
-  const float maxd = fmaxf_(d1, d2);
-  float dt1;
-  if ((double)maxd <= 1e-15) {
-    dt1 = fmaxf_(1e-6f, dt0 * 1e-3f);
-  } else {
-    const float l10 = (float)log10((double)maxd);
-    const float e = (-(2.0f + l10)) / 5.0f;
-    dt1 = (float)pow(10.0, (double)e);
-  }
-  return fminf_(fminf_(100.0f * dt0, dt1), dtmax);
+  return initdt_dt0(rms_from(s[0], n), rms_from(s[1], n), dtmax);
 }
 
 __device__ __forceinline__ float init_dt_final3(const Sum3& r1, const Sum3& r2, double n, float dtmax) {
-  const float d0 = rms_from(r1.a, n), d1 = rms_from(r1.b, n);
-  float dt0;
-  if ((double)d0 < 1e-5 || (double)d1 < 1e-5) dt0 = 1e-6f;
-  else dt0 = (d0 / d1) / 100.0f;
-  dt0 = fminf_(dt0, dtmax);
-  const float d2 = rms_from(r2.a, n) / dt0;
-  const float maxd = fmaxf_(d1, d2);
-  float dt1;
-  if ((double)maxd <= 1e-15) {
-    dt1 = fmaxf_(1e-6f, dt0 * 1e-3f);
-  } else {
-    const float l10 = (float)log10((double)maxd);
-    const float e = (-(2.0f + l10)) / 5.0f;
-    dt1 = (float)pow(10.0, (double)e);
-  }
-  return fminf_(fminf_(100.0f * dt0, dt1), dtmax);
+  const float d1 = rms_from(r1.b, n);
+  const float dt0 = initdt_dt0(rms_from(r1.a, n), d1, dtmax);
+  return initdt_tail(dt0, d1, rms_from(r2.a, n), 5.0f, dtmax);
 }
 
 // Progress of a solve, for the host loop that keeps the stream fed (lrnde_solve): ONE 64-bit store per launch into
@@ -1054,8 +1024,7 @@ __device__ __forceinline__ void step_prologue(const StepArgs& a_, int j, Bcast* 
     if (lane == 0) bc->do_step = 0, bc->accepted_prev = 0;
     return;
   }
-  const float gamma = 0.9f, qmin = 0.2f, qmax = 10.0f, qoldinit = 1e-4f;
-  const float beta1 = (float)(7.0 / 50.0), beta2 = (float)(2.0 / 25.0);
+  const PiConsts pi = pi_tsit5();
   const float dtmax = a.t1 - a.t0;
   const float dtmin = fmaxf_(eps_f(a.t1), eps_f(a.t0));
   int accepted = 0, do_step = 0;
@@ -1077,11 +1046,10 @@ __device__ __forceinline__ void step_prologue(const StepArgs& a_, int j, Bcast* 
     PSTAMP(1);
     // What does not depend on the error norm is computed while the partial sums are still on their way: the controller's
     // qold^beta2, and everything the ACCEPTED branch needs about the new time (the snap onto t1, its eps floor, the saveat
-    // points it passes).  Same expressions as before, earlier.
-    const float pq = a.exact_pow ? (float)pow((double)c.qold, (double)beta2) : fastpow(c.qold, beta2);
-    const float ttmp = c.t + c.dt;
-    const float t_acc = (__builtin_fabsf(ttmp - a.t1) < 100.0f * eps_f(fmaxf_(c.t, a.t1))) ? a.t1 : ttmp;
-    const float floor_acc = fmaxf_(eps_f(t_acc), dtmin);
+    // points it passes).
+    const float pq = pi_pow(a.exact_pow, c.qold, pi.beta2);
+    const float t_acc = snap_signed(c.t, c.dt, a.t1);
+    const float floor_acc = dt_floor(t_acc, dtmin);
     int is_acc = c.isave, ns_acc = c.nsaved;
     while (is_acc < a.nsave && saveat_at(is_acc) <= t_acc) { ++is_acc; ++ns_acc; }
     if (a.save_everystep) ++ns_acc;
@@ -1091,14 +1059,8 @@ __device__ __forceinline__ void step_prologue(const StepArgs& a_, int j, Bcast* 
     const float eest = rms_from(sr.a, a.n_global);
     PSTAMP(3);
     c.eest_last = eest;
-    float q;
-    if (eest == 0.0f) {
-      q = 1.0f / qmax;
-    } else {
-      c.q11 = a.exact_pow ? (float)pow((double)eest, (double)beta1) : fastpow(eest, beta1);
-      q = c.q11 / pq;
-      q = fmaxf_(1.0f / qmax, fminf_(1.0f / qmin, q / gamma));
-    }
+    const PiStep ps = pi_step(pi, a.exact_pow, eest, pq, c.q11);
+    c.q11 = ps.q11;
     accepted = (eest <= 1.0f);
     const int ntr = c.naccept + c.nreject;
     if (blockIdx.x == 0 && lane == 0 && a.trace && ntr < a.cap_trace) {
@@ -1109,11 +1071,10 @@ __device__ __forceinline__ void step_prologue(const StepArgs& a_, int j, Bcast* 
       c.status = LRNDE_DT_NAN;
     } else if (accepted) {
       c.naccept++;
-      const float dtnew = c.dt / q;
-      c.qold = fmaxf_(eest, qoldinit);
+      c.qold = pi_qold(eest);
       b.tprev = c.t; b.dt_prev = c.dt;
       t = t_acc;
-      c.dtpropose = fmaxf_(fminf_(dtmax, dtnew), floor_acc);
+      c.dtpropose = pi_propose(c.dt, ps.q, dtmax, floor_acc);
       b.accepted_prev = 1; b.t_new = t;
       if (a.dense) {
         b.dense_idx = c.naccept - 1;
@@ -1135,15 +1096,12 @@ __device__ __forceinline__ void step_prologue(const StepArgs& a_, int j, Bcast* 
       // loopheader!
       if (!c.first) {
         if (accepted) { c.cur ^= 1; dt = c.dtpropose; }
-        else dt = c.dt / fminf_(1.0f / qmin, c.q11 / gamma);
+        else dt = pi_reject_dt(pi, c.dt, c.q11);
       }
       c.iter++;
-      dt = fminf_(dtmax, dt);
-      dt = fmaxf_(dt, dtmin);
-      dt = fminf_(__builtin_fabsf(dt), __builtin_fabsf(a.t1 - t));
-      if (c.iter > a.maxiters) c.status = LRNDE_MAXITERS;
-      else if (dt != dt) c.status = LRNDE_DT_NAN;
-      else if (__builtin_fabsf(dt) <= __builtin_fabsf(dtmin)) c.status = LRNDE_DT_LESS_THAN_MIN;
+      dt = header_clamp(dt, dtmax, dtmin, t, a.t1);
+      const int hs = header_status(c.iter, a.maxiters, dt, dtmin);
+      if (hs != STEP_OK) c.status = hs;
       else { do_step = 1; c.nf += 6; }
     }
   } else if (c.status == ST_RUNNING) {  // single-step modes: integrator.dt as is
@@ -1705,7 +1663,7 @@ __global__ void k_ctrl_init(Ctrl* ctrl, float t0, float dt, int cur, int nsaved)
   Ctrl c;
   memset(&c, 0, sizeof(c));
   c.status = ST_RUNNING; c.first = 1; c.cur = cur; c.nsaved = nsaved;
-  c.t = t0; c.dt = dt; c.qold = 1e-4f; c.q11 = 1.0f; c.dtpropose = dt;
+  c.t = t0; c.dt = dt; c.qold = QOLDINIT; c.q11 = 1.0f; c.dtpropose = dt;
   ctrl[0] = c;
   ctrl[1] = c;
 }
@@ -2577,18 +2535,8 @@ int lrnde_init_dt(lrnde_ctx* c, const float* u0, int32_t B, float t0, float tend
   {
     const float dtmax = tend - t0;
     const float d0 = (float)sqrt(s1[0] / a.n_global), d1 = (float)sqrt(s1[1] / a.n_global);
-    float dt0 = ((double)d0 < 1e-5 || (double)d1 < 1e-5) ? 1e-6f : (d0 / d1) / 100.0f;
-    dt0 = fminf(dt0, dtmax);
-    const float d2 = (float)sqrt(s2[0] / a.n_global) / dt0;
-    const float maxd = fmaxf(d1, d2);
-    float dt1;
-    if ((double)maxd <= 1e-15) dt1 = fmaxf(1e-6f, dt0 * 1e-3f);
-    else {
-      const float l10 = (float)log10((double)maxd);
-      const float e = (-(2.0f + l10)) / 5.0f;
-      dt1 = (float)pow(10.0, (double)e);
-    }
-    *dt_host = fminf(fminf(100.0f * dt0, dt1), dtmax);
+    const float dt0 = initdt_dt0(d0, d1, dtmax);
+    *dt_host = initdt_tail(dt0, d1, (float)sqrt(s2[0] / a.n_global), 5.0f, dtmax);
   }
   return LRNDE_OK;
 }
@@ -3493,7 +3441,7 @@ __global__ void k_sde_ctl_init(SdeCtl* ctl, int m0, float dtc0) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   SdeCtl c;
   c.status = ST_RUNNING; c.i = 0; c.m = m0; c.cur = 0; c.naccept = 0; c.nreject = 0; c.iters = 1; c.nf = 0;
-  c.qold = 1e-4f; c.eest_last = 0.f; c.dtc = dtc0;
+  c.qold = QOLDINIT; c.eest_last = 0.f; c.dtc = dtc0;
   *ctl = c;
 }
 
@@ -3506,7 +3454,7 @@ __global__ void k_sde_ctl_init_dtdev(SdeCtl* ctl, const float* dt_dev, float h, 
   if (m0 > nfine) m0 = nfine;
   SdeCtl c;
   c.status = ST_RUNNING; c.i = 0; c.m = m0; c.cur = 0; c.naccept = 0; c.nreject = 0; c.iters = 1; c.nf = 0;
-  c.qold = 1e-4f; c.eest_last = 0.f; c.dtc = dt0;
+  c.qold = QOLDINIT; c.eest_last = 0.f; c.dtc = dt0;
   *ctl = c;
 }
 // the end state of a device-controlled solve (the control block says which of the two buffers holds it) -> out
@@ -3690,10 +3638,10 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
   }
   HIPCHK(c, hipMemcpyAsync(ua, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   const float h = (t1 - t0) / (float)nfine;
-  const float gamma = o->gamma, qmin = o->qmin, qmax = o->qmax, qoldinit = 1e-4f;
+  const PiConsts pi = {o->gamma, o->qmin, o->qmax, o->beta1, o->beta2};
   int i = 0;                                                  // position on the path's grid
   int m = (int)(o->dt0 / h); if (m < 1) m = 1;                // step length in grid intervals
-  float qold = qoldinit;
+  float qold = QOLDINIT;
   float dtc = o->dt0;   // the controller's proposal as a real number; the step taken is its floor on the grid (SdeCtl::dtc)
   int nb = (int)((n + 255) / 256); if (nb > 1024) nb = 1024;
   while (i < nfine) {
@@ -3707,13 +3655,7 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
     st->nf += 3; st->eest_last = eest;
     if (eest != eest) { st->retcode = LRNDE_DT_NAN; break; }
     // PI controller on EEst (the form of SURVEY.md 3.5; StochasticDiffEq's constants are the caller's options)
-    float q;
-    if (eest == 0.0f) q = 1.0f / qmax;
-    else {
-      const float q11 = fastpow(eest, o->beta1);
-      q = q11 / fastpow(qold, o->beta2);
-      q = fmaxf(1.0f / qmax, fminf(1.0f / qmin, q / gamma));
-    }
+    const float q = pi_step(pi, 0, eest, pi_pow(0, qold, pi.beta2), 1.0f).q;
     const int accepted = eest <= 1.0f;
     const int ntr = st->naccept + st->nreject;
     if (trace_host && ntr < cap_trace) { trace_host[ntr].t = t; trace_host[ntr].dt = dt; trace_host[ntr].eest = eest; trace_host[ntr].accepted = accepted; }
@@ -3727,7 +3669,7 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
         rec_im_host[st->naccept] = make_int2(i, m);
       }
       st->naccept++;
-      qold = fmaxf(eest, qoldinit);
+      qold = pi_qold(eest);
       i += m;
       std::swap(ua, ub);
       m = mnew;
@@ -4141,8 +4083,7 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
                     float reltol, int maxiters, int exact_pow, const std::vector<float>& tstops,
                     const std::vector<AdjImpulse>& impulses, lrnde_stats* st) {
   const size_t N = v.N;
-  const float gamma = 0.9f, qmin = 0.2f, qmax = 10.0f, qoldinit = 1e-4f;
-  const float beta1 = (float)(7.0 / 50.0), beta2 = (float)(2.0 / 25.0);
+  const PiConsts pi = pi_tsit5();
   float A[21], BT[7];
   for (int i = 0; i < 21; ++i) A[i] = (float)Tsit5::A[i];
   for (int i = 0; i < 7; ++i) BT[i] = (float)Tsit5::BT[i];
@@ -4162,21 +4103,15 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
     float d0, d1, d2;
     if ((rc = vec_norm(c, z, nullptr, z, nullptr, abstol, reltol, v.n_lam, v.P, &d0))) return rc;
     if ((rc = vec_norm(c, K[0], nullptr, z, nullptr, abstol, reltol, v.n_lam, v.P, &d1))) return rc;
-    float dt0 = ((double)d0 < 1e-5 || (double)d1 < 1e-5) ? 1e-6f : (d0 / d1) / 100.0f;
-    dt0 = fminf(dt0, dtmax);
+    const float dt0 = initdt_dt0(d0, d1, dtmax);
     const float one = 1.0f; const float* kk[1] = {K[0]};
     if ((rc = vec_axpy(c, v.zs, z, dt0, 1, kk, &one, N))) return rc;
     if ((rc = rhs(v.zs, t + dt0, K[1]))) return rc;
     if ((rc = vec_norm(c, K[1], K[0], z, nullptr, abstol, reltol, v.n_lam, v.P, &d2))) return rc;
-    d2 = d2 / dt0;
-    const float maxd = fmaxf(d1, d2);
-    float dt1;
-    if ((double)maxd <= 1e-15) dt1 = fmaxf(1e-6f, dt0 * 1e-3f);
-    else { const float l10 = (float)log10((double)maxd); const float e = (-(2.0f + l10)) / 5.0f; dt1 = (float)pow(10.0, (double)e); }
-    dt = fminf(fminf(100.0f * dt0, dt1), dtmax);
+    dt = initdt_tail(dt0, d1, d2, 5.0f, dtmax);
     st->nf = 3; st->dt_init = dt;
   }
-  float qold = qoldinit, q11 = 1.0f, dtpropose = dt;
+  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
   int accept = 0, iter = 0;
   size_t istop = 0, iimp = 0;
   while (iimp < impulses.size() && impulses[iimp].s <= s0) ++iimp;
@@ -4198,13 +4133,11 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
         }
         if (hit) { if ((rc = rhs(z, t, K[0]))) return rc; st->nf += 1; }
       }
-      else dt = dt / fminf(1.0f / qmin, q11 / gamma);
+      else dt = pi_reject_dt(pi, dt, q11);
     }
     ++iter;
-    dt = fminf(dtmax, dt); dt = fmaxf(dt, dtmin); dt = fminf(fabsf(dt), fabsf(tstop - t));
-    if (iter > maxiters) { rc = LRNDE_MAXITERS; break; }
-    if (dt != dt) { rc = LRNDE_DT_NAN; break; }
-    if (fabsf(dt) <= fabsf(dtmin)) { rc = LRNDE_DT_LESS_THAN_MIN; break; }
+    dt = header_clamp(dt, dtmax, dtmin, t, tstop);
+    if ((rc = header_status(iter, maxiters, dt, dtmin))) break;
     // stages 2..7 (src/perform_step.jl:11-20 on the augmented state)
     c->pg_defer = fuse_stage;
     for (int sidx = 2; sidx <= 7; ++sidx) {
@@ -4244,14 +4177,8 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
     }
     st->eest_last = eest;
     if (eest != eest) { rc = LRNDE_DT_NAN; break; }
-    const float ttmp = t + dt;
-    float q;
-    if (eest == 0.0f) q = 1.0f / qmax;
-    else {
-      if (exact_pow) { q11 = (float)pow((double)eest, (double)beta1); q = q11 / (float)pow((double)qold, (double)beta2); }
-      else { q11 = fastpow(eest, beta1); q = q11 / fastpow(qold, beta2); }
-      q = fmaxf(1.0f / qmax, fminf(1.0f / qmin, q / gamma));
-    }
+    const PiStep ps = pi_step(pi, exact_pow, eest, pi_pow(exact_pow, qold, pi.beta2), q11);
+    q11 = ps.q11;
     accept = (eest <= 1.0f);
     if (c->adj_trace && c->adj_trace_n < c->adj_trace_cap) {
       lrnde_trace_row& r = c->adj_trace[c->adj_trace_n++];
@@ -4259,12 +4186,10 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
     }
     if (accept) {
       st->naccept++;
-      const float dtnew = dt / q;
-      qold = fmaxf(eest, qoldinit);
-      // (magnitudes: reversed time s = -t <= 0 — a signed max would take the time nearer zero, and with it an eps far below
-      //  the rounding of t + dt; the reference's adjoint runs t from t2 down to t0 with positive times)
-      t = (fabsf(ttmp - tstop) < 100.0f * eps_f(fmaxf(fabsf(t), fabsf(tstop)))) ? tstop : ttmp;
-      dtpropose = fmaxf(fminf(dtmax, dtnew), fmaxf(eps_f(t), dtmin));
+      qold = pi_qold(eest);
+      // (reversed time s = -t <= 0; the reference's adjoint runs t from t2 down to t0 with positive times)
+      t = snap_magnitude(t, dt, tstop);
+      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
     } else {
       st->nreject++;
     }

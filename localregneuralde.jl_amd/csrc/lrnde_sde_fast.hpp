@@ -94,22 +94,15 @@ __device__ __forceinline__ f32x4 sf_chain(const f32x4 (&frag)[NKG], const f32x4*
   return acc;
 }
 
-// The controller of lrnde_sde_solve_adaptive's host loop, expression for expression, on a copy of the control block: PI
-// step factor from EEst, the proposal kept as a real number, position on the caller's grid, buffer flip.  `writer` (one
-// thread of the whole grid) also leaves the trace row and the accepted step's (start, length).
+// The controller of lrnde_sde_solve_adaptive's host loop on a copy of the control block: PI step factor from EEst
+// (lrnde_stepctl.hpp, the caller's constants), the proposal kept as a real number, position on the caller's grid, buffer
+// flip.  `writer` (one thread of the whole grid) also leaves the trace row and the accepted step's (start, length).
 // qpow = fastpow(c.qold, a.beta2): does not depend on this step's EEst — the cooperative form computes it while the partial
 // sums are still in flight.
 __device__ __forceinline__ void sde_ctl_update(SdeCtl& c, float eest, float dt, const SdeFastArgs& a, bool writer, float qpow) {
-  const float qoldinit = 1e-4f;
   c.nf += 3; c.eest_last = eest;
   if (eest != eest) { c.status = LRNDE_DT_NAN; return; }
-  float q;
-  if (eest == 0.0f) q = 1.0f / a.qmax;
-  else {
-    const float q11 = fastpow(eest, a.beta1);
-    q = q11 / qpow;
-    q = fmaxf_(1.0f / a.qmax, fminf_(1.0f / a.qmin, q / a.gamma));
-  }
+  const float q = pi_step({a.gamma, a.qmin, a.qmax, a.beta1, a.beta2}, 0, eest, qpow, 1.0f).q;
   const int accepted = eest <= 1.0f;
   const int ntr = c.naccept + c.nreject;
   if (writer && a.trace && ntr < a.cap_trace) {
@@ -125,7 +118,7 @@ __device__ __forceinline__ void sde_ctl_update(SdeCtl& c, float eest, float dt, 
       else c.status = LRNDE_CAPACITY;
     }
     c.naccept++;
-    c.qold = fmaxf_(eest, qoldinit);
+    c.qold = pi_qold(eest);
     c.i += c.m;
     c.cur ^= 1;
     c.m = mnew;
@@ -303,8 +296,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
           const Sum3 s = reduce_partials3(a.idt_part, (int)gridDim.x);
           if (lane == 0) {
             const float d0 = (float)sqrt(s.a / a.n_norm), d1 = (float)sqrt(s.b / a.n_norm);
-            float dt0 = ((double)d0 < 1e-5 || (double)d1 < 1e-5) ? 1e-6f : (d0 / d1) / 100.0f;
-            dt0 = fminf_(dt0, a.idt_dtmax);
+            const float dt0 = initdt_dt0(d0, d1, a.idt_dtmax);
             sh_dt0 = dt0;
             if (blockIdx.x == 0) { a.idt_scal[0] = dt0; a.idt_scal[1] = d1; }
           }

@@ -97,8 +97,7 @@ int sde_init_dt(lrnde_sde* s, const float* u, int B, float t, float tend, float 
   double s0 = 0.0, s1 = 0.0;
   for (int i = 0; i < 64; ++i) { s0 += s->idt_part_host[i]; s1 += s->idt_part_host[64 + i]; }
   const float d0 = (float)sqrt(s0 / (double)n), d1 = (float)sqrt(s1 / (double)n);
-  float dt0 = ((double)d0 < 1e-5 || (double)d1 < 1e-5) ? 1e-6f : (d0 / d1) / 100.0f;
-  dt0 = fminf(dt0, dtmax);
+  const float dt0 = initdt_dt0(d0, d1, dtmax);
   HIPCHK(c, hipMemcpyAsync(u1, u, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   hipLaunchKernelGGL(k_sde_axpy, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, u1, (const float*)f0, dt0);  // u1 = u + dt0 * f0
   if ((rc = lrnde_rhs(c, u1, t + dt0, B, f1))) return rc;
@@ -109,16 +108,7 @@ int sde_init_dt(lrnde_sde* s, const float* u, int B, float t, float tend, float 
   HIPCHK(c, hipStreamSynchronize(c->stream));
   double s2 = 0.0;
   for (int i = 0; i < 64; ++i) s2 += s->idt_part_host[i];
-  const float d2 = (float)sqrt(s2 / (double)n) / dt0;
-  const float maxd = fmaxf(d1, d2);
-  float dt1;
-  if ((double)maxd <= 1e-15) dt1 = fmaxf(1e-6f, dt0 * 1e-3f);
-  else {
-    const float l10 = (float)log10((double)maxd);
-    const float e = (-(2.0f + l10)) / (order + 0.5f);
-    dt1 = (float)pow(10.0, (double)e);
-  }
-  *dt_out = fminf(fminf(100.0f * dt0, dt1), dtmax);
+  *dt_out = initdt_tail(dt0, d1, (float)sqrt(s2 / (double)n), order + 0.5f, dtmax);
   return LRNDE_OK;
 }
 
@@ -134,30 +124,21 @@ __global__ void k_sde_initdt_fin(const double* part2, int nwg, double n, float d
   const Sum3 s = reduce_partials3(part2, nwg);
   if (threadIdx.x != 0) return;
   const float dt0 = scal[0], d1 = scal[1];
-  const float d2 = (float)sqrt(s.a / n) / dt0;
-  const float maxd = fmaxf_(d1, d2);
-  float dt1;
-  if ((double)maxd <= 1e-15) dt1 = fmaxf_(1e-6f, dt0 * 1e-3f);
-  else {
-    const float l10 = (float)log10((double)maxd);
-    const float e = (-(2.0f + l10)) / (order + 0.5f);
-    dt1 = (float)pow(10.0, (double)e);
-  }
-  const float dt = fminf_(fminf_(100.0f * dt0, dt1), dtmax);
+  const float dt = initdt_tail(dt0, d1, (float)sqrt(s.a / n), order + 0.5f, dtmax);
   scal[2] = dt;
   if (ctl) {      // k_sde_ctl_init with the host's quantisation of dt to the path's grid
     int m0 = (int)(dt / h); if (m0 < 1) m0 = 1;
     if (m0 > nfine) m0 = nfine;
     SdeCtl c;
     c.status = ST_RUNNING; c.i = 0; c.m = m0; c.cur = 0; c.naccept = 0; c.nreject = 0; c.iters = 1; c.nf = 0;
-    c.qold = 1e-4f; c.eest_last = 0.f; c.dtc = dt;
+    c.qold = QOLDINIT; c.eest_last = 0.f; c.dtc = dt;
     *ctl = c;
   }
   if (ctrl) {     // k_ctrl_init
     Ctrl c;
     memset(&c, 0, sizeof(c));
     c.status = ST_RUNNING; c.first = 1;
-    c.t = t0; c.dt = dt; c.qold = 1e-4f; c.q11 = 1.0f; c.dtpropose = dt;
+    c.t = t0; c.dt = dt; c.qold = QOLDINIT; c.q11 = 1.0f; c.dtpropose = dt;
     ctrl[0] = c;
     ctrl[1] = c;
   }
