@@ -370,7 +370,8 @@ int lrnde_sde_solve_fixed(lrnde_sde* sde, int32_t which, const float* u0, const 
                           int32_t nsteps, float abstol, float reltol, float delta, float* u_traj, float* eest_host,
                           float* reg_val_host);
 
-/* Adaptive Euler-Heun solve: the loop that consumes the step's error estimate (src/perform_step.jl:200-205), which the
+/* Adaptive solve (Euler-Heun here; Milstein and the four-stage SRI step through lrnde_sde_solve_adaptive_alg below): the
+ * loop that consumes the step's error estimate (src/perform_step.jl:200-205), which the
  * reference reaches through `solve(prob, solver; ...)` in src/layers/neural_sde.jl:60-72 (StochasticDiffEq, un-vendored).
  * The Brownian path is the CALLER's: W (device, (nfine+1) x B x D) holds it on a uniform grid of nfine intervals over
  * (t0, t1), W[0] = 0.  Steps are whole numbers of grid intervals, so every increment dW = W[j] - W[i] is the path's own
@@ -381,7 +382,7 @@ int lrnde_sde_solve_fixed(lrnde_sde* sde, int32_t which, const float* u0, const 
  * (may be NULL) gets one row per attempted step.  On the MNIST-SDE shape (state 32, hidden 64, no time input, unsharded)
  * the controller runs on the device — in the footer of the one-launch step kernel; the host keeps launches enqueued and
  * watches a pinned progress word (12 us per attempted step) — elsewhere the loop is host-controlled, one stream sync per
- * attempted step. */
+ * attempted step.  The grid-quantised loop itself is UPSTREAM-RECALL, like the controller's constants. */
 typedef struct {
   float abstol, reltol, delta;   /* integrator.opts.abstol / reltol / delta */
   float dt0;                     /* first step (rounded down to whole grid intervals, at least one) */
@@ -453,7 +454,8 @@ int lrnde_sde_record_generation(lrnde_sde* sde, uint64_t* gen_host);
 /* Gaussian noise for the SDE layers, drawn on the handle's device and stream (no host sync).
  * out (device): cumulative = 1 -> (nsteps+1) x B x D, out[0] = 0, the Brownian path on a uniform grid;
  *               cumulative = 0 -> nsteps x B x D increments scale * z.  stream: 0 path W, 1 local-step z,
- *               2 fixed-grid dW, 3 fixed-grid dZ (callers may use others).  scale = sqrt(h), computed by the caller.
+ *               2 fixed-grid dW, 3 fixed-grid dZ, 4 the adaptive SRI solve's second path Z, 5 its local-step z2
+ *               (callers may use others).  scale = sqrt(h), computed by the caller.
  * Normal j of column c = b*D + d is Box-Muller (float64, rounded once) on Philox-4x32-10 at counter (j >> 2, c, stream, 0),
  * key (seed & 0xffffffff, seed >> 32): it depends on (seed, stream, b, d, j) only, not on B or nsteps.
  * The path is the sequential fp32 sum of the fp32 products scale * z.  B x D may not exceed 2^30. */
@@ -474,6 +476,39 @@ typedef struct lrnde_sri_tableau {
 int lrnde_sde_sri_step(lrnde_sde* sde, const lrnde_sri_tableau* tab, const float* uprev, const float* dW, const float* dZ,
                        int32_t B, float t, float dt, float abstol, float reltol, float delta, float* u, float* eest_host,
                        float* reg_val_host);
+
+/* The adaptive solve and the layer's recorded forward with the step as a parameter — the reference passes whatever n.solver
+ * is to `solve` and to the local step (src/layers/neural_sde.jl:68-69,96,116).  The arguments of lrnde_sde_solve_adaptive /
+ * lrnde_sde_node_forward_record, then:
+ *   which    : 0 Euler-Heun (src/perform_step.jl:172-206), 1 Milstein (:108-170), 2 four-stage SRI (:49-106) — the codes of
+ *              lrnde_sde_solve_fixed, extended by 2.  The two older entry points are these with which = 0: same launches, same bits.
+ *   tab      : SRI only — the caller's tableau.
+ *   Z        : SRI only — the second Brownian path on the same uniform grid, (nfine+1) x B x D, Z[0] = 0 (device, alive until
+ *              the backward call); a step's dZ = Z[i+m] - Z[i].
+ *   z2_local : SRI only, the recorded forward only — the local step's dZ = sqrt(dt_local) * z2_local (B x D, device).
+ * SRI without tab or Z (or without z2_local when regularising) and which outside 0..2 return LRNDE_BADARG with a message.
+ * Evaluations per attempted step, (drift, diffusion): Euler-Heun (3, 3), Milstein (1, 2), SRI (4, 4); the automatic initial dt
+ * adds (2, 2).  lrnde_stats.nf is the drift count.
+ * Where the controller runs: Euler-Heun and Milstein at the one-launch kernels' shape (D <= 64, H <= 128, no time input,
+ * unsharded) on the device — Milstein in the footer of k_sde_mil_fast, one launch per attempted step, no stream sync inside
+ * the solve.  Host-controlled, one stream sync per attempted step: Milstein outside that shape (or with LRNDE_SDE_HOST_LOOP=1)
+ * and SRI at every shape — a device controller for SRI is not provided.
+ * UPSTREAM-RECALL (StochasticDiffEq is not vendored; beside the controller's constants, which stay the caller's options):
+ * the strong orders the automatic initial dt takes — 1/2 Euler-Heun, 1 Milstein, 3/2 SRI.
+ * lrnde_sde_node_backward_recorded sweeps a record with the reverse kernels of the kind that made it: per recorded step the
+ * kernels behind lrnde_sde_solve_fixed_backward_rkmil / lrnde_sde_sri_step_backward, one launch sequence per step; the
+ * regulariser's parameter gradient from lrnde_sde_rkmil_reg_grad's kernels / the SRI reverse with du_new = NULL, dx = NULL. */
+int lrnde_sde_solve_adaptive_alg(lrnde_sde* sde, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
+                                 const lrnde_sde_adapt_opts* opts, float* u_end, lrnde_stats* stats_host,
+                                 lrnde_trace_row* trace_host, int32_t cap_trace, int32_t which, const lrnde_sri_tableau* tab,
+                                 const float* Z);
+int lrnde_sde_node_forward_record_alg(lrnde_sde* sde, const float* x, const float* W, int32_t nfine, int32_t B, float t0, float t2,
+                                      const lrnde_sde_adapt_opts* opts, int32_t mode, float t1_or_rand, const float* z_local,
+                                      int32_t save_start, const float* saveat_host, int32_t nsave, float* u_series,
+                                      float* t_series_host, int32_t cap_series, int32_t* nseries_host, float* reg_val_host,
+                                      int32_t* nfe_drift_host, int32_t* nfe_diffusion_host, lrnde_stats* stats_host,
+                                      float* t1_used_host, int32_t which, const lrnde_sri_tableau* tab, const float* Z,
+                                      const float* z2_local);
 /* Reverse sweep of ONE four-stage SRI step (src/perform_step.jl:49-106; lrnde_sde_sri_step with the same arguments):
  * loss = <du_new, u'> + w_reg * EEst*dt.  du_new (device, may be NULL = 0): cotangent of the step's result; dx (device, may be
  * NULL): cotangent of uprev — NULL when uprev is a constant of the tape, as for the local step's regulariser

@@ -280,4 +280,32 @@ function sde_sri_step_backward!(h, tab::SriTableau, uprev, dW, dZ, t, dt, abstol
     return dx, rv[]
 end
 
+# The adaptive solve and the layer's recorded forward with the step as a parameter (lrnde.h: lrnde_sde_solve_adaptive_alg,
+# lrnde_sde_node_forward_record_alg): which = 0 Euler-Heun, 1 Milstein, 2 four-stage SRI (tab, the second path Z and — for the
+# recorded forward when regularising — the second local draw z2 are SRI's; pass `nothing` otherwise).  opts: an isbits struct
+# with lrnde_sde_adapt_opts' ten fields (LRNDELayer.jl's SdeAdaptOpts).  UN-RUN like the rest of this binding.
+_optr(a) = a === nothing ? Ptr{Float32}(C_NULL) : pointer(a)
+function sde_solve_adaptive_alg(h, u0, W, nfine, t0, t1, opts, which; tab=nothing, Z=nothing)
+    u_end = similar(u0); stats = Stats()
+    tabref = tab === nothing ? Ref(SriTableau(ntuple(_ -> 0f0, 51)...)) : Ref(tab)
+    GC.@preserve tabref sde_check(h, ccall((:lrnde_sde_solve_adaptive_alg, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Float32, Float32, Ptr{Cvoid}, Ptr{Float32}, Ref{Stats}, Ptr{Cvoid}, Int32,
+         Int32, Ptr{Cvoid}, Ptr{Float32}),
+        h, pointer(u0), pointer(W), Int32(nfine), nbatch(u0), t0, t1, Ref(opts), pointer(u_end), stats, C_NULL, Int32(0),
+        Int32(which), tab === nothing ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, tabref), _optr(Z)))
+    return u_end, stats
+end
+function sde_node_forward_record_alg(h, x, W, nfine, t0, t2, opts, mode, t1_or_rand, z, save_start, saveat, useries, tseries, cap,
+                                     ns, reg, nf, ng, stats, t1u, which; tab=nothing, Z=nothing, z2=nothing)
+    tabref = tab === nothing ? Ref(SriTableau(ntuple(_ -> 0f0, 51)...)) : Ref(tab)
+    GC.@preserve tabref sde_check(h, ccall((:lrnde_sde_node_forward_record_alg, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Float32, Float32, Ptr{Cvoid}, Int32, Float32, Ptr{Float32}, Int32,
+         Ptr{Float32}, Int32, Ptr{Float32}, Ptr{Float32}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Ref{Stats}, Ptr{Float32},
+         Int32, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(x), pointer(W), Int32(nfine), nbatch(x), t0, t2, Ref(opts), mode, t1_or_rand, _optr(z), save_start,
+        saveat, Int32(length(saveat)), pointer(useries), tseries, Int32(cap), ns, reg, nf, ng, stats, t1u,
+        Int32(which), tab === nothing ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, tabref), _optr(Z), _optr(z2)))
+    return nothing
+end
+
 end # module

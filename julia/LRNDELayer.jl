@@ -19,7 +19,8 @@
 #     on W×H×8×B arrays — BatchNorm running statistics travel in `st.model` exactly as the reference's closure leaves them
 #     (src/layers/neural_ode.jl:44-48);
 #   * `NeuralDSDE(Chain(Dense(D => H, act), Dense(H => D)), Dense(D => D); solver = LambaEulerHeun())` — the adaptive
-#     Euler-Heun solve on a Brownian path drawn from `st.rng` on a uniform grid (see lrnde.h, lrnde_sde_node_forward_record).
+#     Euler-Heun solve on a Brownian path drawn from `st.rng` on a uniform grid (see lrnde.h, lrnde_sde_node_forward_record);
+#     `solver = RKMilCommute()`: the same adaptive layer with the Milstein step (lrnde_sde_node_forward_record_alg, which = 1).
 # The pullback closures check the handle's RECORD GENERATION (lrnde_record_generation) and re-run their forward when another
 # forward of the same layer has replaced the record in between (an evaluation pass, a second pullback in flight).
 
@@ -296,9 +297,13 @@ function lrnde_sde_handle(n::NeuralDSDE)
         LRNDEBackend.sde_create(D, H, act; diffusion_bias=gbias)
     end
 end
-# LambaEulerHeun is the solver whose step the library integrates with (src/perform_step.jl:172-206); the reference's
-# default SOSRI needs StochasticDiffEq's tableau and RSWM and stays on the reference's own path
-lrnde_sde_supported(n::NeuralDSDE, x) = nameof(typeof(n.solver)) === :LambaEulerHeun && lrnde_sde_shape(n) !== nothing &&
+# LambaEulerHeun (src/perform_step.jl:172-206) and RKMilCommute (:108-170) are the solvers whose steps the library's adaptive
+# layer integrates with from here (the step kind of lrnde_sde_node_forward_record_alg); the four-stage SRI step is in the
+# library too (which = 2) but needs a tableau: the reference's default SOSRI keeps StochasticDiffEq's own tableau and RSWM and
+# stays on the reference's own path
+_lrnde_sde_which(solver) = nameof(typeof(solver)) === :LambaEulerHeun ? Int32(0) :
+                           nameof(typeof(solver)) in (:RKMilCommute, :RKMil) ? Int32(1) : nothing
+lrnde_sde_supported(n::NeuralDSDE, x) = _lrnde_sde_which(n.solver) !== nothing && lrnde_sde_shape(n) !== nothing &&
                                          nameof(typeof(x)) === :ROCArray && eltype(x) === Float32 && ndims(x) == 2
 
 const LRNDE_SDE_NFINE = Ref(256)    # grid intervals of the Brownian path drawn per layer call
@@ -335,11 +340,17 @@ function lrnde_sde_layer_forward(n::NeuralDSDE, x, ps, st)
     useries = similar(x, size(x)..., cap); tseries = zeros(Float32, cap)
     ns = Ref{Int32}(); reg = Ref{Float32}(); nf = Ref{Int32}(); ng = Ref{Int32}(); stats = Stats(); t1u = Ref{Float32}()
     save_start = haskey(n.kwargs, :save_start) ? Int32(n.kwargs[:save_start]) : Int32(-1)
+    which = _lrnde_sde_which(n.solver)
+    if which != 0    # the step kind goes with the call; Euler-Heun keeps the older entry point (the same launches)
+        LRNDEBackend.sde_node_forward_record_alg(h, x, W, nfine, t0, t2, opts, MODE[mode], t1_or_rand, z, save_start, saveat, useries,
+                                                 tseries, cap, ns, reg, nf, ng, stats, t1u, which)
+    else
     LRNDEBackend.sde_check(h, ccall((:lrnde_sde_node_forward_record, LRNDEBackend.lib), Cint,
         (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Float32, Float32, Ref{SdeAdaptOpts}, Int32, Float32, Ptr{Float32}, Int32,
          Ptr{Float32}, Int32, Ptr{Float32}, Ptr{Float32}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Ref{Stats}, Ptr{Float32}),
         h, pointer(x), pointer(W), Int32(nfine), LRNDEBackend.nbatch(x), t0, t2, opts, MODE[mode], t1_or_rand, pointer(z), save_start,
         saveat, Int32(length(saveat)), pointer(useries), tseries, Int32(cap), ns, reg, nf, ng, stats, t1u))
+    end
     k = Int(ns[])
     us = [copy(selectdim(useries, ndims(useries), i)) for i in 1:k]
     sol = LRNDESolution(us, tseries[1:k], LRNDEDestats(Int(nf[]), stats.naccept, stats.nreject), :Success)

@@ -1615,6 +1615,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 }
 
 #include "lrnde_sde_fast.hpp"
+#include "lrnde_sde_mil_fast.hpp"
 #include "lrnde_qtile.hpp"
 #include "lrnde_adjoint.hpp"
 #include "lrnde_backward.hpp"
@@ -3192,7 +3193,7 @@ struct lrnde_sde {
   float* pdr = nullptr; float* bwf_part = nullptr; size_t bwf_part_n = 0; int* bwf_meta = nullptr; int* bwf_meta_pin = nullptr; size_t bwf_meta_n = 0;
   float* bwf_hist = nullptr; size_t bwf_hist_n = 0;   // the deferred sweep's history records
   int* arrive = nullptr;                      // arrival counter of the one-launch step's footer (lrnde_sde_fast.hpp)
-  float* ad_ws = nullptr; size_t ad_n = 0;    // lrnde_sde_solve_adaptive: two states + the current increment
+  float* ad_ws = nullptr; size_t ad_n = 0;    // lrnde_sde_solve_adaptive: two states + the current increments (dW, and SRI's dZ)
   SdeCtl* ad_ctl = nullptr; SdeCtl* ad_ctl_host = nullptr;             // device-controlled adaptive loop: control block (device / pinned), heading ...
   int ad_blob_cap = 0;                                                 // ... room for this many (start, length) pairs 64 bytes in
   unsigned long long* ad_prog = nullptr; unsigned long long* ad_prog_dev = nullptr;  // its pinned progress word
@@ -3432,7 +3433,7 @@ int lrnde_sde_solve_fixed(lrnde_sde* s, int32_t which, const float* u0, const fl
   return LRNDE_OK;
 }
 
-// ---- adaptive Euler-Heun solve on a caller-supplied Brownian path ----
+// ---- adaptive solve (Euler-Heun, Milstein or four-stage SRI step) on a caller-supplied Brownian path ----
 __global__ void k_sde_dw(size_t n, const float* Wlo, const float* Whi, float* dW) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dW[i] = Whi[i] - Wlo[i];
 }
@@ -3491,8 +3492,10 @@ static int sde_adaptive_prepare(lrnde_sde* s, int rec_cap = 0) {
 static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
                                const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                                int32_t cap_trace, float* ua, float* ub, float* rec_u = nullptr, int2* rec_im = nullptr,
-                               int rec_cap = 0, int2* rec_im_host = nullptr, const float* dt0_dev = nullptr, bool no_persist = false) {
+                               int rec_cap = 0, int2* rec_im_host = nullptr, const float* dt0_dev = nullptr, bool no_persist = false,
+                               int which = 0) {
   lrnde_ctx* c = s->drift;
+  if (which == 1) no_persist = true;   // (the Milstein step has the launch-per-attempt form only: lrnde_sde_mil_fast.hpp)
   const size_t n = (size_t)B * c->desc.state_dim;
   const bool pairs_home = rec_im_host && rec_im && rec_cap > 0;   // the layer's record: its pairs live behind the control block
   int rc0 = sde_adaptive_prepare(s, pairs_home ? rec_cap : 0);
@@ -3557,7 +3560,8 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   while (!done && j <= cap) {
     for (int k = 0; k < 8; ++k, ++j) {
       f.jlaunch = j;
-      sde_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
+      if (which == 1) sde_mil_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
+      else sde_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
     }
     HIPCHK(c, hipGetLastError());
     const unsigned want = (unsigned)(j - 4);
@@ -3585,7 +3589,7 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const SdeCtl fin = *s->ad_ctl_host;
   if (persisted && plain && (fin.status == LRNDE_HIP_ERROR || fin.status == ST_RUNNING))   // the barrier gave up waiting (busy device): the loop
-    return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true);
+    return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true, which);
   if (pairs_home && fin.naccept > 0)
     memcpy(rec_im_host, reinterpret_cast<const char*>(s->ad_ctl_host) + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
   st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iters; st->nf = fin.nf; st->eest_last = fin.eest_last;
@@ -3605,17 +3609,34 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
 static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
                                    const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                                    int32_t cap_trace, float* rec_u, int2* rec_im_dev, int2* rec_im_host, int rec_cap,
-                                   const float* dt0_dev = nullptr);
+                                   const float* dt0_dev = nullptr, int which = 0, const lrnde_sri_tableau* tab = nullptr,
+                                   const float* Z = nullptr);
+// the step kinds of the adaptive entry points: 0 Euler-Heun, 1 Milstein, 2 four-stage SRI (which needs its tableau and the
+// second Brownian path)
+static int sde_alg_check(lrnde_sde* s, int32_t which, const lrnde_sri_tableau* tab, const float* Z) {
+  if (!s) return LRNDE_BADARG;
+  if (which < 0 || which > 2) return fail(s->drift, LRNDE_BADARG, "which: 0 Euler-Heun, 1 Milstein, 2 SRI");
+  if (which == 2 && (!tab || !Z)) return fail(s->drift, LRNDE_BADARG, "the SRI step needs its tableau and the second Brownian path Z");
+  return LRNDE_OK;
+}
+int lrnde_sde_solve_adaptive_alg(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
+                                 const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
+                                 int32_t cap_trace, int32_t which, const lrnde_sri_tableau* tab, const float* Z) {
+  int rc = sde_alg_check(s, which, tab, Z);
+  if (rc) return rc;
+  if (!u_end) return fail(s->drift, LRNDE_BADARG, "null pointer");
+  return sde_solve_adaptive_impl(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, nullptr, nullptr, nullptr, 0, nullptr,
+                                 which, tab, Z);
+}
 int lrnde_sde_solve_adaptive(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
                              const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                              int32_t cap_trace) {
-  if (s && !u_end) return fail(s->drift, LRNDE_BADARG, "null pointer");
-  return sde_solve_adaptive_impl(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, nullptr, nullptr, nullptr, 0);
+  return lrnde_sde_solve_adaptive_alg(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, 0, nullptr, nullptr);
 }
 static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
                                    const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                                    int32_t cap_trace, float* rec_u, int2* rec_im_dev, int2* rec_im_host, int rec_cap,
-                                   const float* dt0_dev) {
+                                   const float* dt0_dev, int which, const lrnde_sri_tableau* tab, const float* Z) {
   int rc = sde_check(s, u0, W, u_end ? u_end : u0, B, 1.0f);   // (u_end may be NULL from the layer: no end state asked for)
   if (rc) return rc;
   lrnde_ctx* c = s->drift;
@@ -3625,17 +3646,20 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
   if (s->ad_n != n) {
     if (s->ad_ws) HIPCHK(c, hipFree(s->ad_ws));
     s->ad_ws = nullptr; s->ad_n = 0;
-    HIPCHK(c, hipMalloc(&s->ad_ws, sizeof(float) * 3 * n));
+    HIPCHK(c, hipMalloc(&s->ad_ws, sizeof(float) * 4 * n));
     s->ad_n = n;
   }
-  float *ua = s->ad_ws, *ub = s->ad_ws + n, *dW = s->ad_ws + 2 * n;
+  float *ua = s->ad_ws, *ub = s->ad_ws + n, *dW = s->ad_ws + 2 * n, *dZ = s->ad_ws + 3 * n;
   {
+    // the controller on the device: Euler-Heun (k_sde_eh_fast) and Milstein (k_sde_mil_fast) at the one-launch kernels' shape.
+    // SRI at any shape, and everything outside that shape, runs the host-controlled loop below
     const bool host_loop = opt(OPT_SDE_HOST_LOOP) != 0;  // diagnostic: the host-controlled loop below
-    if (sde_uses_fast(s) && !host_loop) {
+    if (which != 2 && sde_uses_fast(s) && !host_loop) {
       return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im_dev, rec_cap,
-                                 rec_im_host, dt0_dev);
+                                 rec_im_host, dt0_dev, false, which);
     }
   }
+  const int nfa = which == 2 ? 4 : (which == 1 ? 1 : 3);   // drift evaluations of one attempted step
   HIPCHK(c, hipMemcpyAsync(ua, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   const float h = (t1 - t0) / (float)nfine;
   const PiConsts pi = {o->gamma, o->qmin, o->qmax, o->beta1, o->beta2};
@@ -3649,10 +3673,16 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
     if (++st->iters > o->maxiters) { st->retcode = LRNDE_MAXITERS; break; }
     const float t = t0 + (float)i * h, dt = (float)m * h;
     hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, W + (size_t)i * n, W + (size_t)(i + m) * n, dW);
-    if ((rc = sde_step_enqueue(s, 0, ua, dW, B, t, dt, o->abstol, o->reltol, o->delta, ub, c->ctrl_host))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const float eest = c->ctrl_host[0].eest_last;
-    st->nf += 3; st->eest_last = eest;
+    float eest = 0.f;
+    if (which == 2) {   // k_sri_chi / k_sri_stage / k_sri_final around the eight evaluations; the call ends in the attempt's synchronisation
+      hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, Z + (size_t)i * n, Z + (size_t)(i + m) * n, dZ);
+      if ((rc = lrnde_sde_sri_step(s, tab, ua, dW, dZ, B, t, dt, o->abstol, o->reltol, o->delta, ub, &eest, nullptr))) return rc;
+    } else {
+      if ((rc = sde_step_enqueue(s, which, ua, dW, B, t, dt, o->abstol, o->reltol, o->delta, ub, c->ctrl_host))) return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      eest = c->ctrl_host[0].eest_last;
+    }
+    st->nf += nfa; st->eest_last = eest;
     if (eest != eest) { st->retcode = LRNDE_DT_NAN; break; }
     // PI controller on EEst (the form of SURVEY.md 3.5; StochasticDiffEq's constants are the caller's options)
     const float q = pi_step(pi, 0, eest, pi_pow(0, qold, pi.beta2), 1.0f).q;

@@ -99,8 +99,9 @@ __device__ __forceinline__ f32x4 sf_chain(const f32x4 (&frag)[NKG], const f32x4*
 // flip.  `writer` (one thread of the whole grid) also leaves the trace row and the accepted step's (start, length).
 // qpow = fastpow(c.qold, a.beta2): does not depend on this step's EEst — the cooperative form computes it while the partial
 // sums are still in flight.
-__device__ __forceinline__ void sde_ctl_update(SdeCtl& c, float eest, float dt, const SdeFastArgs& a, bool writer, float qpow) {
-  c.nf += 3; c.eest_last = eest;
+// nfa: drift evaluations of one attempted step (Euler-Heun 3, Milstein 1): what SdeCtl::nf counts.
+__device__ __forceinline__ void sde_ctl_update(SdeCtl& c, float eest, float dt, const SdeFastArgs& a, bool writer, float qpow, int nfa) {
+  c.nf += nfa; c.eest_last = eest;
   if (eest != eest) { c.status = LRNDE_DT_NAN; return; }
   const float q = pi_step({a.gamma, a.qmin, a.qmax, a.beta1, a.beta2}, 0, eest, qpow, 1.0f).q;
   const int accepted = eest <= 1.0f;
@@ -470,7 +471,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
       else {
         const Sum3 s3 = part_finish<false>(L, blk, nwg);   // (the fixed order of every reduction of these partials)
         const float eest = rms_from(s3.a, a.n_norm);
-        sde_ctl_update(c2, eest, dt, a, blockIdx.x == 0 && lane == 0, qpow);
+        sde_ctl_update(c2, eest, dt, a, blockIdx.x == 0 && lane == 0, qpow, 3);
       }
       if (lane == 0) sh_cc = c2;
     }
@@ -534,7 +535,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
         a.rec->status = ST_DONE;
       } else {
         SdeCtl c = *a.ctl;
-        sde_ctl_update(c, eest, dt, a, true, fastpow(c.qold, a.beta2));
+        sde_ctl_update(c, eest, dt, a, true, fastpow(c.qold, a.beta2), 3);
         *a.ctl = c;
         __hip_atomic_store(a.prog, (unsigned long long)(unsigned)(a.jlaunch + 1) | ((unsigned long long)(unsigned)c.status << 32),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

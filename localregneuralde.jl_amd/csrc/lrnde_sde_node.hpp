@@ -1,13 +1,14 @@
 // lrnde_sde_node.hpp — the NeuralDSDE layer as the reference runs it (src/layers/neural_sde.jl:50-123): ADAPTIVE solve of
-// dudt / g from x over tspan, sol(t1) / `saveat` values, a fresh integrator at (sol(t1), t1) and one local Euler-Heun step
-// for reg_val (:88-105, :109-123) — and its pullback (the reference tapes the solver's own arithmetic with TrackerAdjoint,
+// dudt / g from x over tspan, sol(t1) / `saveat` values, a fresh integrator at (sol(t1), t1) and one local step of the layer's
+// solver (Euler-Heun, Milstein or the four-stage SRI step: `which`) for reg_val (:88-105, :109-123) — and its pullback (the reference tapes the solver's own arithmetic with TrackerAdjoint,
 // :12; reg_val is differentiated w.r.t. the parameters only, :42).  Included by lrnde_kernels.hip after lrnde_sde_bwd.hpp.
 //
 // What is restated from un-vendored StochasticDiffEq (UPSTREAM-RECALL, not readable in this image):
 //   * the adaptive loop: PI controller on the step's EEst (lrnde_sde_solve_adaptive), on the CALLER's Brownian path given on
 //     a uniform grid — steps are whole grid intervals, a rejected step retries a shorter piece of the same path;
 //   * saveat values between steps by the SDE solvers' linear interpolant  (1 - theta) uprev + theta u ;
-//   * the automatic initial dt (sde_determine_initdt: the ODE heuristic with the diffusion entering as +-3 g).
+//   * the automatic initial dt (sde_determine_initdt: the ODE heuristic with the diffusion entering as +-3 g), with the
+//     solver's strong order as recalled: 1/2 Euler-Heun, 1 Milstein, 3/2 SRI.
 // The forward keeps a dense record of the accepted steps (start index and length on the grid, end state); the backward is
 // the reverse sweep over exactly those steps with their own dt and dW = W[i + m] - W[i] (discretise-then-differentiate:
 // what a tape of the solve gives), cotangents of interpolated saveat values split (1 - theta, theta) onto the two step ends.
@@ -29,6 +30,9 @@ struct SdeNodeRecord {
   float* u1 = nullptr; float* dWloc = nullptr; float* tmp = nullptr; size_t n_alloc = 0;
   float t1 = 0.f, dt_loc = 0.f, ee_loc = 0.f;   // the local step: its time, dt and EEst (u_new stays in tmp)
   float* gdr = nullptr; float* gdf = nullptr; size_t pf = 0, pg = 0;
+  // the step kind the record was made with (0 Euler-Heun, 1 Milstein, 2 SRI): the backward sweeps it with that kind's
+  // reverse kernels.  SRI: its tableau, the second path (the caller's, alive until the backward) and the local step's dZ
+  int which = 0; lrnde_sri_tableau tab{}; const float* Z = nullptr; float* dZloc = nullptr;
 };
 
 // out = (1 - theta) * a + theta * b   (StochasticDiffEq's linear sde_interpolant)
@@ -173,8 +177,9 @@ int sde_node_alloc(lrnde_sde* s, SdeNodeRecord& r, int B, int nfine) {
   lrnde_ctx* c = s->drift;
   const size_t n = (size_t)B * c->desc.state_dim;
   if (r.n_alloc != n) {
-    for (float** p : {&r.x, &r.u1, &r.dWloc, &r.tmp}) { if (*p) hipFree(*p); *p = nullptr; }
+    for (float** p : {&r.x, &r.u1, &r.dWloc, &r.tmp, &r.dZloc}) { if (*p) hipFree(*p); *p = nullptr; }
     r.n_alloc = 0;
+    HIPCHK(c, hipMalloc(&r.dZloc, sizeof(float) * n));
     HIPCHK(c, hipMalloc(&r.x, sizeof(float) * n));
     HIPCHK(c, hipMalloc(&r.u1, sizeof(float) * n));
     HIPCHK(c, hipMalloc(&r.dWloc, sizeof(float) * n));
@@ -205,7 +210,7 @@ unsigned long long sde_node_generation(const lrnde_sde* s) { return (s->node && 
 void sde_node_release(lrnde_sde* s) {
   if (!s->node) return;
   SdeNodeRecord& r = *s->node;
-  for (float** p : {&r.x, &r.u1, &r.dWloc, &r.tmp, &r.rec_u, &r.gdr, &r.gdf}) { if (*p) hipFree(*p); *p = nullptr; }
+  for (float** p : {&r.x, &r.u1, &r.dWloc, &r.tmp, &r.dZloc, &r.rec_u, &r.gdr, &r.gdf}) { if (*p) hipFree(*p); *p = nullptr; }
   if (r.rec_im_dev) hipFree(r.rec_im_dev);
   delete s->node;
   s->node = nullptr;
@@ -220,10 +225,27 @@ int lrnde_sde_node_forward_record(lrnde_sde* s, const float* x, const float* W, 
                                   int32_t save_start, const float* saveat_host, int32_t nsave, float* u_series,
                                   float* t_series_host, int32_t cap_series, int32_t* nseries_host, float* reg_val_host,
                                   int32_t* nfe_drift_host, int32_t* nfe_diffusion_host, lrnde_stats* st, float* t1_used_host) {
+  return lrnde_sde_node_forward_record_alg(s, x, W, nfine, B, t0, t2, o, mode, t1_or_rand, z_local, save_start, saveat_host, nsave, u_series,
+                                           t_series_host, cap_series, nseries_host, reg_val_host, nfe_drift_host, nfe_diffusion_host, st,
+                                           t1_used_host, 0, nullptr, nullptr, nullptr);
+}
+
+int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float* W, int32_t nfine, int32_t B, float t0, float t2,
+                                      const lrnde_sde_adapt_opts* o, int32_t mode, float t1_or_rand, const float* z_local,
+                                      int32_t save_start, const float* saveat_host, int32_t nsave, float* u_series,
+                                      float* t_series_host, int32_t cap_series, int32_t* nseries_host, float* reg_val_host,
+                                      int32_t* nfe_drift_host, int32_t* nfe_diffusion_host, lrnde_stats* st, float* t1_used_host,
+                                      int32_t which, const lrnde_sri_tableau* tab, const float* Z, const float* z2_local) {
   if (!s) return LRNDE_BADARG;
   lrnde_ctx* c = s->drift;
-  int rc = sde_check(s, x, W, u_series, B, 1.0f);
+  int rc = sde_alg_check(s, which, tab, Z);
   if (rc) return rc;
+  if ((rc = sde_check(s, x, W, u_series, B, 1.0f))) return rc;
+  if (which == 2 && mode != LRNDE_MODE_NONE && !z2_local)
+    return fail(c, LRNDE_BADARG, "z2_local (the local SRI step's second standard-normal draw) is required when regularising");
+  // per attempted step: (drift, diffusion) evaluations, and the strong order the automatic initial dt takes (UPSTREAM-RECALL)
+  const int nfa = which == 2 ? 4 : (which == 1 ? 1 : 3), nga = which == 2 ? 4 : (which == 1 ? 2 : 3);
+  const float order = which == 2 ? 1.5f : (which == 1 ? 1.0f : 0.5f);
   if (!o || !st || !t_series_host || !nseries_host || !reg_val_host || nfine < 1 || !(t2 > t0) || nsave < 0 || cap_series < 1)
     return fail(c, LRNDE_BADARG, "bad arguments (nfine >= 1, t2 > t0, non-null outputs)");
   if (mode < LRNDE_MODE_NONE || mode > LRNDE_MODE_BIASED) return fail(c, LRNDE_BADARG, "mode");
@@ -241,9 +263,10 @@ int lrnde_sde_node_forward_record(lrnde_sde* s, const float* x, const float* W, 
   int nfe_f = 0, nfe_g = 0;
   HIPCHK(c, hipMemcpyAsync(r.x, x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   // the main solve (src/layers/neural_sde.jl:50-72): dt0 <= 0 -> automatic initial dt
-  // (the one-launch step's shape keeps both automatic initial dts on the device: two host synchronisations per call — the
-  //  end of the solve and the end of this function — instead of nine; LRNDE_SDE_HOST_INITDT=1: the host form)
-  const bool devdt = sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT);
+  // (the one-launch Euler-Heun step's shape keeps both automatic initial dts on the device: two host synchronisations per call —
+  //  the end of the solve and the end of this function — instead of nine; LRNDE_SDE_HOST_INITDT=1: the host form.  Milstein and
+  //  SRI take the host form: their local step runs the generic step kernels, which take dt from the host)
+  const bool devdt = which == 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT);
   if (devdt && !s->idt_scal) {
     HIPCHK(c, hipMalloc(&s->idt_scal, sizeof(float) * 8));
     HIPCHK(c, hipHostMalloc(&s->idt_scal_host, sizeof(float) * 8));
@@ -256,19 +279,20 @@ int lrnde_sde_node_forward_record(lrnde_sde* s, const float* x, const float* W, 
       if ((rc = sde_init_dt_dev(s, r.x, B, t0, t2, oo.abstol, oo.reltol, 0.5f, s->idt_scal, s->ad_ctl, h, nfine, nullptr))) return rc;
       dt0_dev = s->idt_scal + 2;
       oo.dt0 = t2 - t0;   // (placeholder for the argument checks; the control block is initialised from the device value)
-    } else if ((rc = sde_init_dt(s, r.x, B, t0, t2, oo.abstol, oo.reltol, 0.5f, r.tmp, &oo.dt0))) return rc;
+    } else if ((rc = sde_init_dt(s, r.x, B, t0, t2, oo.abstol, oo.reltol, order, r.tmp, &oo.dt0))) return rc;
     nfe_f += 2; nfe_g += 2;
   }
   r.im.assign((size_t)nfine, make_int2(0, 0));
   // No regulariser, no saveat, no start value: the caller's series is the end state alone — the solve leaves it in u_series itself
   // (picked on the device) and its closing synchronisation is the call's only one.  Otherwise the end state is not asked for
   // (it is the record's last slot).
-  const bool end_only = mode == LRNDE_MODE_NONE && nsave == 0 && save_start <= 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP);
+  const bool end_only = which == 0 && mode == LRNDE_MODE_NONE && nsave == 0 && save_start <= 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP);
   float* u_end = end_only ? u_series : nullptr;
-  rc = sde_solve_adaptive_impl(s, r.x, W, nfine, B, t0, t2, &oo, u_end, st, nullptr, 0, r.rec_u, r.rec_im_dev, r.im.data(), r.rec_cap, dt0_dev);
+  rc = sde_solve_adaptive_impl(s, r.x, W, nfine, B, t0, t2, &oo, u_end, st, nullptr, 0, r.rec_u, r.rec_im_dev, r.im.data(), r.rec_cap, dt0_dev,
+                               which, tab, Z);
   if (rc) return rc;
   const int K = st->naccept;
-  nfe_f += 3 * (st->naccept + st->nreject); nfe_g += 3 * (st->naccept + st->nreject);
+  nfe_f += nfa * (st->naccept + st->nreject); nfe_g += nga * (st->naccept + st->nreject);
   // sol.t / sol.u as StochasticDiffEq would hold them (UPSTREAM-RECALL): saveat values by linear interpolation inside the
   // accepted step that contains them; saveat = [] saves every step; save_start < 0: DiffEq's default rule
   auto tk = [&](int k) { return t0 + (float)r.im[k].x * h; };                       // start of accepted step k
@@ -324,8 +348,8 @@ int lrnde_sde_node_forward_record(lrnde_sde* s, const float* x, const float* W, 
     HIPCHK(c, hipGetLastError());
     return LRNDE_OK;
   };
-  // the local step (:94-98, :116-118): fresh integrator at (sol(t1), t1) on (t1, t2) -> its own initial dt; one Euler-Heun
-  // step with a fresh increment sqrt(dt) z
+  // the local step (:94-98, :116-118): fresh integrator at (sol(t1), t1) on (t1, t2) -> its own initial dt; one step of the
+  // solve's kind with a fresh increment sqrt(dt) z (SRI: and a second one, sqrt(dt) z2)
   *reg_val_host = 0.f;
   r.t1 = t1; r.dt_loc = 0.f;
   bool local_pending = false;   // the local step's record is still in flight (device-side initial dt)
@@ -346,18 +370,22 @@ int lrnde_sde_node_forward_record(lrnde_sde* s, const float* x, const float* W, 
       local_pending = true;
     } else {
       if (!(dtl > 0.f)) {
-        if ((rc = sde_init_dt(s, r.u1, B, t1, t2, o->abstol, o->reltol, 0.5f, r.tmp, &dtl))) return rc;
+        if ((rc = sde_init_dt(s, r.u1, B, t1, t2, o->abstol, o->reltol, order, r.tmp, &dtl))) return rc;
         nfe_f += 2; nfe_g += 2;
       }
       dtl = fminf(dtl, t2 - t1);
       hipLaunchKernelGGL(k_sde_scale, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, z_local, sqrtf(dtl), r.dWloc);
       float ee = 0.f, rv = 0.f;
-      if ((rc = sde_step_impl(s, 0, r.u1, r.dWloc, B, t1, dtl, o->abstol, o->reltol, o->delta, r.tmp, &ee, &rv))) return rc;
+      if (which == 2) {
+        hipLaunchKernelGGL(k_sde_scale, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, z2_local, sqrtf(dtl), r.dZloc);
+        if ((rc = lrnde_sde_sri_step(s, tab, r.u1, r.dWloc, r.dZloc, B, t1, dtl, o->abstol, o->reltol, o->delta, r.tmp, &ee, &rv))) return rc;
+      } else
+      if ((rc = sde_step_impl(s, which, r.u1, r.dWloc, B, t1, dtl, o->abstol, o->reltol, o->delta, r.tmp, &ee, &rv))) return rc;
       *reg_val_host = rv;
       r.ee_loc = ee;
       r.dt_loc = dtl;
     }
-    nfe_f += 3; nfe_g += 3;
+    nfe_f += nfa; nfe_g += nga;
   }
   // the caller's view: _CorrectedDESolution drops the entries at t1 (src/utils.jl:31-33: `sol.u[t1 .!= sol.t]`)
   r.series.clear();
@@ -380,6 +408,8 @@ int lrnde_sde_node_forward_record(lrnde_sde* s, const float* x, const float* W, 
   if (nfe_diffusion_host) *nfe_diffusion_host = nfe_g;
   if (t1_used_host) *t1_used_host = t1;
   r.valid = true; ++r.gen; r.B = B; r.nfine = nfine; r.K = K; r.mode = mode; r.t0 = t0; r.t2 = t2; r.h = h; r.o = *o; r.W = W;
+  r.which = which; r.Z = Z;
+  if (which == 2) r.tab = *tab;
   return LRNDE_OK;
 }
 
@@ -524,6 +554,69 @@ int sde_node_reg_fused(lrnde_sde* s, SdeNodeRecord& r, int B, float w_reg, float
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LRNDE_OK;
 }
+int sde_sri_step_backward_core(lrnde_sde* s, const lrnde_sri_tableau* tab, const float* uprev, const float* dW, const float* dZ, int32_t B,
+                               float t, float dt, float abstol, float reltol, float delta, const float* du_new, float w_reg, float* dx,
+                               float* dp_drift, float* dp_diff, float* reg_val_host, float* un);
+// The reverse sweep of a record made with the Milstein (which = 1) or the four-stage SRI step (which = 2): the recorded
+// accepted steps newest first, each with its own dt = m h and increments from the path(s), through the per-step reverse
+// kernels of lrnde_sde_solve_fixed_backward_rkmil / lrnde_sde_sri_step_backward (w_reg = 0, dx wanted); cotangents of
+// interpolated series values split (1 - theta, theta) onto the two step ends as in the Euler-Heun sweep.  Then the
+// regulariser's parameter gradient scaled by w_reg (no dx from it).  One launch sequence per recorded step.
+int sde_node_backward_alg(lrnde_sde* s, SdeNodeRecord& r, int B, const float* du_series, int nseries, float w_reg, float* dx,
+                          float* dp_drift, float* dp_diff) {
+  lrnde_ctx* c = s->drift; lrnde_ctx* cg = s->diff;
+  const int D = c->desc.state_dim;
+  const size_t n = (size_t)B * D, Pf = lrnde_param_count(&c->desc), Pg2 = lrnde_param_count(&cg->desc);
+  const size_t Pg = (size_t)D * D + (s->diff_bias ? D : 0);
+  const int nb = sde_nb(n);
+  int rc;
+  float* v[10]; float* gpf[2]; float* gpg[2];
+  // increments of the step being swept: Milstein in the sweep's own workspace; SRI in the record's scratch (its per-step
+  // call lays the workspace out for itself), behind the slot that call uses for the recomputed u'
+  float *w = nullptr, *z = r.tmp + 2 * n;
+  if (r.which == 1) { if ((rc = sde_bwd_ws(s, n, Pf, Pg2, v, 10, gpf, gpg))) return rc; w = v[9]; }
+  else w = r.tmp + n;
+  HIPCHK(c, hipMemsetAsync(dx, 0, sizeof(float) * n, c->stream));   // dx doubles as the cotangent of the current step's end state
+  HIPCHK(c, hipMemsetAsync(dp_drift, 0, sizeof(float) * Pf, c->stream));
+  HIPCHK(c, hipMemsetAsync(dp_diff, 0, sizeof(float) * Pg, c->stream));
+  for (int k = r.K - 1; k >= 0; --k) {
+    for (int j = 0; j < nseries; ++j)
+      if (r.series[j].k == k && r.series[j].theta != 0.f)
+        hipLaunchKernelGGL(k_sde_axpy, dim3(nb), dim3(256), 0, c->stream, n, dx, du_series + (size_t)j * n, r.series[j].theta);
+    const int i0 = r.im[k].x, m = r.im[k].y;
+    const float t = r.t0 + (float)i0 * r.h, dt = (float)m * r.h;
+    const float* u = (k == 0) ? r.x : r.rec_u + (size_t)(k - 1) * n;
+    hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.W + (size_t)i0 * n, r.W + (size_t)(i0 + m) * n, w);
+    if (r.which == 1) {
+      if ((rc = sde_rkmil_step_sweep(s, u, w, B, t, dt, dx, v, gpf, gpg, dp_drift, dp_diff))) return rc;
+    } else {
+      hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.Z + (size_t)i0 * n, r.Z + (size_t)(i0 + m) * n, z);
+      if ((rc = sde_sri_step_backward_core(s, &r.tab, u, w, z, B, t, dt, r.o.abstol, r.o.reltol, r.o.delta, dx, 0.f, dx, dp_drift, dp_diff,
+                                           nullptr, r.tmp))) return rc;
+    }
+    for (int j = 0; j < nseries; ++j)
+      if (r.series[j].k == k && r.series[j].theta != 1.0f)
+        hipLaunchKernelGGL(k_sde_axpy, dim3(nb), dim3(256), 0, c->stream, n, dx, du_series + (size_t)j * n, 1.0f - r.series[j].theta);
+    HIPCHK(c, hipGetLastError());
+  }
+  for (int j = 0; j < nseries; ++j)   // a saved start value is the input itself
+    if (r.series[j].k < 0) hipLaunchKernelGGL(k_sde_axpy, dim3(nb), dim3(256), 0, c->stream, n, dx, du_series + (size_t)j * n, 1.0f);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  // the regulariser (w.r.t. the parameters only: the local step's integrator is a constant of the tape, neural_sde.jl:42)
+  if (r.mode != LRNDE_MODE_NONE && w_reg != 0.0f) {
+    float rv = 0.f;
+    if (r.which == 1) {
+      if ((rc = lrnde_sde_rkmil_reg_grad(s, r.u1, r.dWloc, B, r.t1, r.dt_loc, r.o.abstol, r.o.reltol, r.gdr, r.gdf, &rv))) return rc;
+      hipLaunchKernelGGL(k_sde_axpy, dim3(sde_nb(Pf)), dim3(256), 0, c->stream, Pf, dp_drift, (const float*)r.gdr, w_reg);
+      hipLaunchKernelGGL(k_sde_axpy, dim3(sde_nb(Pg)), dim3(256), 0, c->stream, Pg, dp_diff, (const float*)r.gdf, w_reg);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if ((rc = sde_sri_step_backward_core(s, &r.tab, r.u1, r.dWloc, r.dZloc, B, r.t1, r.dt_loc, r.o.abstol, r.o.reltol, r.o.delta, nullptr,
+                                                w_reg, nullptr, dp_drift, dp_diff, &rv, r.tmp))) return rc;
+  }
+  return LRNDE_OK;
+}
 bool sde_bwd_fused_ok(const lrnde_sde* s, int nseries) {
   const lrnde_ctx* c = s->drift;
   const int D = c->desc.state_dim, H = c->desc.hidden_dim;
@@ -545,6 +638,8 @@ int lrnde_sde_node_backward_recorded(lrnde_sde* s, int32_t B, const float* du_se
   if (!r.valid || r.B != B) return fail(c, LRNDE_BADARG, "no forward record for this batch (call lrnde_sde_node_forward_record first)");
   if (nseries != (int)r.series.size()) return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nseries, r.series.size());
   if (cg->stream != c->stream) return fail(c, LRNDE_BADARG, "drift and diffusion contexts must share a stream");
+  // a record is swept by the kind that made it (the Euler-Heun sweeps below never see a Milstein or SRI record)
+  if (r.which != 0) return sde_node_backward_alg(s, r, B, du_series, nseries, w_reg, dx, dp_drift, dp_diff);
   const int D = c->desc.state_dim;
   const size_t n = (size_t)B * D, Pf = lrnde_param_count(&c->desc), Pg2 = lrnde_param_count(&cg->desc);
   const size_t Pg = (size_t)D * D + (s->diff_bias ? D : 0), goff = (size_t)D * D + D;
@@ -687,15 +782,23 @@ extern "C" int lrnde_sde_sri_step_backward(lrnde_sde* s, const lrnde_sri_tableau
   lrnde_ctx* c = s->drift; lrnde_ctx* cg = s->diff;
   if (!tab || !dZ || !dp_drift || !dp_diff) return fail(c, LRNDE_BADARG, "null pointer");
   if (cg->stream != c->stream) return fail(c, LRNDE_BADARG, "drift and diffusion contexts must share a stream");
+  if (!s->node) s->node = new SdeNodeRecord();
+  SdeNodeRecord& r = *s->node;
+  if ((rc = sde_node_alloc(s, r, B, r.rec_cap > 0 ? r.rec_cap : 1))) return rc;
+  r.valid = false;   // (u' goes to scratch of the layer record: a recorded adaptive forward and this call do not interleave)
+  return sde_sri_step_backward_core(s, tab, uprev, dW, dZ, B, t, dt, abstol, reltol, delta, du_new, w_reg, dx, dp_drift, dp_diff, reg_val_host, r.u1);
+}
+namespace {
+// un: a state-sized scratch vector for the recomputed u'.  du_new may alias dx (read by the seeds, written last).
+int sde_sri_step_backward_core(lrnde_sde* s, const lrnde_sri_tableau* tab, const float* uprev, const float* dW, const float* dZ, int32_t B,
+                               float t, float dt, float abstol, float reltol, float delta, const float* du_new, float w_reg, float* dx,
+                               float* dp_drift, float* dp_diff, float* reg_val_host, float* un) {
+  int rc;
+  lrnde_ctx* c = s->drift; lrnde_ctx* cg = s->diff;
   const int D = c->desc.state_dim;
   const size_t n = (size_t)B * D, Pf = lrnde_param_count(&c->desc), Pg2 = lrnde_param_count(&cg->desc);
   const size_t Pg = (size_t)D * D + (s->diff_bias ? D : 0), goff = (size_t)D * D + D;
   // the step itself (u', EEst) through the forward entry point, then its stages again keeping every H0 / H1
-  if (!s->node) s->node = new SdeNodeRecord();
-  SdeNodeRecord& r = *s->node;
-  if ((rc = sde_node_alloc(s, r, B, r.rec_cap > 0 ? r.rec_cap : 1))) return rc;
-  float* un = r.u1;   // (scratch of the layer record: a recorded adaptive forward and this sweep do not interleave)
-  r.valid = false;
   float ee = 0.f, rv = 0.f;
   if ((rc = lrnde_sde_sri_step(s, tab, uprev, dW, dZ, B, t, dt, abstol, reltol, delta, un, &ee, &rv))) return rc;
   if (reg_val_host) *reg_val_host = rv;
@@ -738,3 +841,4 @@ extern "C" int lrnde_sde_sri_step_backward(lrnde_sde* s, const lrnde_sri_tableau
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LRNDE_OK;
 }
+}  // namespace

@@ -1,12 +1,16 @@
 """NeuralDSDE mirror (src/layers/neural_sde.jl) on the liblrnde SDE entry points.
 
-The layer runs what the reference's runs (src/layers/neural_sde.jl:50-123): an ADAPTIVE solve — the Lamba Euler-Heun step
-(`_perform_step(::LambaEulerHeunConstantCache)`, src/perform_step.jl:172-206) under a PI controller on its error estimate,
-on a Brownian path drawn up front on a uniform grid (`lrnde_sde_node_forward_record`) — the local step at (sol(t1), t1) for
-reg_val, user `saveat` with the `_CorrectedDESolution` filter, and the pullback as the reverse sweep over the recorded
-accepted steps (`lrnde_sde_node_backward_recorded`).  `adaptive=False` keeps the fixed-grid integrator of rounds 1-2 (also the
-only mode of the Milstein and four-stage SRI steps, :108-170 and :49-106).  SOSRI's tableau and its RSWM noise process live in
-un-vendored StochasticDiffEq and are not restated: `solver="SOSRI"` raises, `solver="SRI"` takes the tableau from the caller.
+The layer runs what the reference's runs (src/layers/neural_sde.jl:50-123): an ADAPTIVE solve — the step of the layer's solver
+under a PI controller on its error estimate, on a Brownian path drawn up front on a uniform grid
+(`lrnde_sde_node_forward_record_alg`) — the local step of the same kind at (sol(t1), t1) for reg_val, user `saveat` with the
+`_CorrectedDESolution` filter, and the pullback as the reverse sweep over the recorded accepted steps
+(`lrnde_sde_node_backward_recorded`).  The step is the Lamba Euler-Heun step (`_perform_step(::LambaEulerHeunConstantCache)`,
+src/perform_step.jl:172-206; the default, adaptive unless told otherwise), the Milstein step (:108-170) or the four-stage SRI
+step (:49-106); the last two are adaptive with `adaptive=True` and march the fixed grid of rounds 1-2 otherwise
+(`adaptive=False` gives Euler-Heun that grid too).  The controller runs on the device for Euler-Heun and Milstein at the
+one-launch kernels' shape (D <= 64, H <= 128); SRI, and Milstein outside that shape, are host-controlled (one stream sync per
+attempted step).  SOSRI's tableau and its RSWM noise process live in un-vendored StochasticDiffEq and are not restated:
+`solver="SOSRI"` raises, `solver="SRI"` takes the tableau from the caller.
 """
 import copy
 import ctypes as C
@@ -16,6 +20,25 @@ import torch
 
 from . import _lib as L
 from .layers import (Chain, Dense, ODESolution, _check_valid_regularize, _dev_ptr, _mlp_desc, _sym)
+
+
+WHICH = {"EulerHeun": 0, "RKMil": 1, "SRI": 2}   # the step kinds of the `_alg` entry points (include/lrnde.h)
+
+
+def _which(solver):
+    if solver in ("SRI", "FourStageSRI"):
+        return 2
+    if solver in ("EulerHeun", "LambaEulerHeun"):
+        return 0
+    if solver.startswith("RKMil"):
+        return 1
+    raise ValueError(f"solver {solver!r}: EulerHeun, RKMil or SRI")
+
+
+def _sri_tab(tableau):
+    if isinstance(tableau, L.SriTableau):
+        return tableau
+    return L.SriTableau(*[float(tableau[k]) for k in L.SRI_FIELDS]) if isinstance(tableau, dict) else L.SriTableau(*[float(v) for v in tableau])
 
 
 class SdeHandle:
@@ -104,9 +127,10 @@ class SdeHandle:
 
 
     def solve_adaptive(self, u0, W, t0, t1, abstol, reltol, delta=1.0 / 6.0, dt0=None, gamma=0.9, qmin=0.2, qmax=1.125,
-                       beta1=7.0 / 50.0, beta2=2.0 / 25.0, maxiters=10000):
-        """adaptive Euler-Heun on the caller's Brownian path W ((nfine+1, B, D), W[0] = 0, uniform grid over (t0, t1)):
-        dict(u_end, stats, trace) — steps are whole grid intervals, EEst drives a PI controller (lrnde.h)"""
+                       beta1=7.0 / 50.0, beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None):
+        """adaptive solve on the caller's Brownian path W ((nfine+1, B, D), W[0] = 0, uniform grid over (t0, t1)):
+        dict(u_end, stats, trace) — steps are whole grid intervals, EEst drives a PI controller (lrnde.h).  solver: "EulerHeun",
+        "RKMil" or "SRI" (with tableau= and the second path path_z=, same shape as W)"""
         nfine = int(W.shape[0]) - 1
         B = u0.numel() // self.D
         o = L.SdeAdaptOpts(float(abstol), float(reltol), float(delta), float((t1 - t0) / nfine if dt0 is None else dt0),
@@ -115,8 +139,16 @@ class SdeHandle:
         st = L.Stats()
         ntr = int(maxiters) + 4
         tr = (L.TraceRow * ntr)()
-        self._chk(L.lib.lrnde_sde_solve_adaptive(self._h, _dev_ptr(u0, "u0", self.D), _dev_ptr(W.contiguous(), "W"), nfine, B,
-                                                 float(t0), float(t1), C.byref(o), _dev_ptr(u_end, "u_end"), C.byref(st), tr, ntr))
+        which = _which(solver)
+        if which == 0:
+            self._chk(L.lib.lrnde_sde_solve_adaptive(self._h, _dev_ptr(u0, "u0", self.D), _dev_ptr(W.contiguous(), "W"), nfine, B,
+                                                     float(t0), float(t1), C.byref(o), _dev_ptr(u_end, "u_end"), C.byref(st), tr, ntr))
+        else:
+            tab = None if tableau is None else C.byref(_sri_tab(tableau))
+            Z = None if path_z is None else _dev_ptr(path_z.contiguous(), "path_z")
+            self._chk(L.lib.lrnde_sde_solve_adaptive_alg(self._h, _dev_ptr(u0, "u0", self.D), _dev_ptr(W.contiguous(), "W"), nfine, B,
+                                                         float(t0), float(t1), C.byref(o), _dev_ptr(u_end, "u_end"), C.byref(st), tr, ntr,
+                                                         which, tab, Z))
         nt = st.naccept + st.nreject
         trace = np.array([(tr[i].t, tr[i].dt, tr[i].eest, tr[i].accepted) for i in range(nt)],
                          dtype=[("t", "f4"), ("dt", "f4"), ("eest", "f4"), ("accepted", "i4")])
@@ -138,10 +170,11 @@ class SdeHandle:
 
     def node_forward_record(self, x, W, t0, t2, abstol, reltol, mode="unbiased", t1_or_rand=0.5, z_local=None, saveat=(),
                             save_start=-1, delta=1.0 / 6.0, dt0=0.0, gamma=0.9, qmin=0.2, qmax=1.125, beta1=7.0 / 50.0,
-                            beta2=2.0 / 25.0, maxiters=10000):
-        """the NeuralDSDE layer forward (lrnde_sde_node_forward_record): adaptive solve on the path W ((nfine+1, B, D), W[0] = 0),
-        sol.u / sol.t as the layer's caller sees them, reg_val of the local step; keeps the record for one
-        `node_backward_recorded`.  dt0 = 0: automatic initial dt."""
+                            beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, z_local2=None):
+        """the NeuralDSDE layer forward (lrnde_sde_node_forward_record[_alg]): adaptive solve on the path W ((nfine+1, B, D),
+        W[0] = 0), sol.u / sol.t as the layer's caller sees them, reg_val of the local step; keeps the record for one
+        `node_backward_recorded`.  dt0 = 0: automatic initial dt.  solver: "EulerHeun", "RKMil" or "SRI" (with tableau=, the
+        second path path_z= and the local step's second draw z_local2=)."""
         nfine = int(W.shape[0]) - 1
         B = x.numel() // self.D
         W = W.contiguous()
@@ -154,12 +187,20 @@ class SdeHandle:
         ns, reg, nf, ng, st, t1u = C.c_int32(), C.c_float(), C.c_int32(), C.c_int32(), L.Stats(), C.c_float()
         if z_local is not None:
             z_local = z_local.contiguous()
-        self._chk(L.lib.lrnde_sde_node_forward_record(
-            self._h, _dev_ptr(x, "x", self.D), _dev_ptr(W, "W"), nfine, B, float(t0), float(t2), C.byref(o), L.MODE[mode],
-            float(t1_or_rand), None if z_local is None else _dev_ptr(z_local, "z_local", self.D), int(save_start),
-            sv.ctypes.data_as(C.POINTER(C.c_float)) if sv.size else None, int(sv.size), C.c_void_p(us.data_ptr()),
-            ts.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns), C.byref(reg), C.byref(nf), C.byref(ng), C.byref(st), C.byref(t1u)))
-        self._node_keep = (W, x)   # the record refers to the caller's path: keep it alive until the backward
+        args = (self._h, _dev_ptr(x, "x", self.D), _dev_ptr(W, "W"), nfine, B, float(t0), float(t2), C.byref(o), L.MODE[mode],
+                float(t1_or_rand), None if z_local is None else _dev_ptr(z_local, "z_local", self.D), int(save_start),
+                sv.ctypes.data_as(C.POINTER(C.c_float)) if sv.size else None, int(sv.size), C.c_void_p(us.data_ptr()),
+                ts.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns), C.byref(reg), C.byref(nf), C.byref(ng), C.byref(st), C.byref(t1u))
+        which = _which(solver)
+        if which == 0:
+            self._chk(L.lib.lrnde_sde_node_forward_record(*args))
+        else:
+            path_z = None if path_z is None else path_z.contiguous()
+            z_local2 = None if z_local2 is None else z_local2.contiguous()
+            self._chk(L.lib.lrnde_sde_node_forward_record_alg(
+                *args, which, None if tableau is None else C.byref(_sri_tab(tableau)),
+                None if path_z is None else _dev_ptr(path_z, "path_z"), None if z_local2 is None else _dev_ptr(z_local2, "z_local2", self.D)))
+        self._node_keep = (W, x, path_z)   # the record refers to the caller's path(s): keep them alive until the backward
         n = int(ns.value)
         return dict(u=us[:n], t=ts[:n].copy(), u_end=us[n - 1], reg_val=np.float32(reg.value), nfe_drift=int(nf.value),
                     nfe_diffusion=int(ng.value), stats=st.asdict(), t1=np.float32(t1u.value))
@@ -238,10 +279,12 @@ class NeuralDSDE:
     """`(sol, st) = nsde(x, ps, st)`; ps = dict(drift=flat, diffusion=[vec(Wg); bg]).
     src/layers/neural_sde.jl:1-123.  Default (solver="EulerHeun", adaptive=True): the ADAPTIVE solve on a Brownian path of
     `nfine` grid intervals drawn from st["rng"] (or given as `noise=` / `path=`), kwargs `abstol`, `reltol`, `saveat`, `save_start`
-    as the reference's; `adaptive=False` (and the Milstein / SRI steps): the fixed grid of `nsteps` steps.
+    as the reference's; `adaptive=False`: the fixed grid of `nsteps` steps.  solver="RKMil" / "SRI" (with tableau=): the fixed
+    grid unless `adaptive=True`, which runs the same adaptive layer with that step (SRI: a second path Z and a second local
+    draw z2, given as `path_z=` / `z_local2=` or drawn after W and z).
     noise_source="device": the noise is drawn on the device (SdeHandle.draw_noise) from one uint64 seed taken from st["rng"]
-    before its other draws — streams 0 (path W), 1 (local-step z), 2 (fixed-grid dW), 3 (fixed-grid dZ); arrays given
-    explicitly still win."""
+    before its other draws — streams 0 (path W), 1 (local-step z), 2 (fixed-grid dW), 3 (fixed-grid dZ), 4 (adaptive SRI: path
+    Z), 5 (adaptive SRI: local-step z2); arrays given explicitly still win."""
 
     def __init__(self, drift, diffusion, *, solver="EulerHeun", sensealg=None, tspan=(0.0, 1.0),
                  regularize="unbiased", maxiters=1000, nsteps=20, delta=1.0 / 6.0, tableau=None, adaptive=None, nfine=256,
@@ -271,12 +314,11 @@ class NeuralDSDE:
         self.tspan = (np.float32(tspan[0]), np.float32(tspan[1]))
         self.regularize, self.maxiters, self.nsteps, self.delta = regularize, int(maxiters), int(nsteps), float(delta)
         self.adaptive = (self.solver == "EulerHeun") if adaptive is None else bool(adaptive)
-        if self.adaptive and self.solver != "EulerHeun":
-            raise NotImplementedError("the adaptive solve is built on the Euler-Heun step (src/perform_step.jl:172-206)")
         self.nfine, self.dt0 = int(nfine), float(dt0)
         self.kwargs = dict(kwargs)
         self._handle = None
         self._last_adaptive = None
+        self._last_path_z = None   # adaptive SRI: the second path of the last forward
 
     def initialstates(self, rng):
         rng.standard_normal()  # :23
@@ -301,7 +343,7 @@ class NeuralDSDE:
         """the device streams' seed: one uint64 from the layer's host stream"""
         return int(rng.integers(0, 2 ** 64, dtype=np.uint64))
 
-    def _call_adaptive(self, x, ps, st, path=None, z_local=None):
+    def _call_adaptive(self, x, ps, st, path=None, z_local=None, path_z=None, z_local2=None):
         h = self.handle()
         h.set_params(ps["drift"], ps["diffusion"])
         t0, t2 = self.tspan
@@ -315,6 +357,12 @@ class NeuralDSDE:
                 path = h.draw_noise(seed, 0, self.nfine, B, np.float32(np.sqrt(hh)), True).view((self.nfine + 1,) + tuple(x.shape))
             if z_local is None:
                 z_local = h.draw_noise(seed, 1, 1, B, 1.0, False)[0].view(tuple(x.shape))
+            if self.solver == "SRI":   # the second path (stream 4) and the local step's second draw (stream 5)
+                if path_z is None:
+                    hh = np.float32((t2 - t0) / np.float32(self.nfine))
+                    path_z = h.draw_noise(seed, 4, self.nfine, B, np.float32(np.sqrt(hh)), True).view((self.nfine + 1,) + tuple(x.shape))
+                if z_local2 is None:
+                    z_local2 = h.draw_noise(seed, 5, 1, B, 1.0, False)[0].view(tuple(x.shape))
         if path is None:
             path, z_draw = self._draw_path(rng, x.shape, x.device)
             z_local = z_draw if z_local is None else z_local
@@ -322,22 +370,32 @@ class NeuralDSDE:
             path = torch.as_tensor(path, dtype=torch.float32).to(x.device)
             if z_local is None:
                 z_local = torch.from_numpy(rng.standard_normal(tuple(x.shape)).astype(np.float32)).to(x.device)
+        if self.solver == "SRI":   # host draws of Z, then z2, AFTER W and z (the other solvers' draw sequences are unchanged)
+            if path_z is None:
+                path_z, z2_draw = self._draw_path(rng, x.shape, x.device)
+                z_local2 = z2_draw if z_local2 is None else z_local2
+            else:
+                path_z = torch.as_tensor(path_z, dtype=torch.float32).to(x.device)
+                if z_local2 is None:
+                    z_local2 = torch.from_numpy(rng.standard_normal(tuple(x.shape)).astype(np.float32)).to(x.device)
+            self._last_path_z = path_z
         mode = self.regularize if st["training"] else "none"
         r01 = np.float32(rng.random(dtype=np.float32)) if mode != "none" else np.float32(0)
         t1_or_rand = np.float32(r01 * (t2 - t0) + t0) if mode == "unbiased" else r01     # :92 / :114
         saveat = self.kwargs.get("saveat", ())
         r = h.node_forward_record(x, path, t0, t2, abstol, reltol, mode=mode, t1_or_rand=float(t1_or_rand), z_local=z_local,
                                   saveat=() if saveat is None else saveat, save_start=int(self.kwargs.get("save_start", -1)),
-                                  delta=self.delta, dt0=self.dt0, maxiters=self.maxiters)
+                                  delta=self.delta, dt0=self.dt0, maxiters=self.maxiters, solver=self.solver,
+                                  tableau=self.tableau if self.solver == "SRI" else None, path_z=path_z, z_local2=z_local2)
         self._last_adaptive = dict(nseries=int(r["u"].shape[0]), mode=mode)
         sol = ODESolution([r["u"][i] for i in range(r["u"].shape[0])], [np.float32(t) for t in r["t"]], r["nfe_drift"])
         sol.stats = r["stats"]
         return sol, dict(drift=st["drift"], diffusion=st["diffusion"], nfe_drift=r["nfe_drift"], nfe_diffusion=r["nfe_diffusion"],
                          reg_val=r["reg_val"], rng=rng, training=st["training"])
 
-    def __call__(self, x, ps, st, noise=None, path=None, z_local=None):
+    def __call__(self, x, ps, st, noise=None, path=None, z_local=None, path_z=None, z_local2=None):
         if self.adaptive:
-            return self._call_adaptive(x, ps, st, path=path if path is not None else noise, z_local=z_local)
+            return self._call_adaptive(x, ps, st, path=path if path is not None else noise, z_local=z_local, path_z=path_z, z_local2=z_local2)
         h = self.handle()
         h.set_params(ps["drift"], ps["diffusion"])
         t0, t2 = self.tspan
@@ -411,6 +469,8 @@ class NeuralDSDE:
         (test/runtests.jl:361-365, 386-397): (dx, dict(drift=, diffusion=), info).  The forward is re-run with the same
         draws as `__call__` (st['rng']; `noise` if given); the solve is differentiated through its own steps, reg_val
         w.r.t. the parameters only (info['dx_reg'] is None: `gs_x === nothing` in the reference)."""
+        if self.adaptive:   # every solver's adaptive layer: the reverse sweep over its record
+            return self.pullback_series(x, ps, st, None, du_end=du_end, w_reg=w_reg, path=noise)
         if self.solver == "SRI":   # the fixed-grid loop of four-stage SRI steps, newest first (lrnde_sde_sri_step_backward)
             sol, st2 = self(x, ps, st, noise=noise)
             h = self.handle()
@@ -430,8 +490,6 @@ class NeuralDSDE:
                                          du_new=None, w_reg=w_reg, want_dx=False, dp_drift=dpf, dp_diff=dpg)
                 assert rg["reg_val"] == st2["reg_val"]
             return ub, dict(drift=dpf, diffusion=dpg), dict(sol=sol, st=st2, dx_reg=None)
-        if self.adaptive:
-            return self.pullback_series(x, ps, st, None, du_end=du_end, w_reg=w_reg, path=noise)
         sol, st2 = self(x, ps, st, noise=noise)
         h = self.handle()
         fs = self._last_solve
@@ -449,11 +507,11 @@ class NeuralDSDE:
             dpg = dpg + np.float32(w_reg) * rg["dp_diff"]
         return bw["dx"], dict(drift=dpf, diffusion=dpg), dict(sol=sol, st=st2, dx_reg=None)
 
-    def pullback_series(self, x, ps, st, du_series, du_end=None, w_reg=0.0, path=None, z_local=None):
+    def pullback_series(self, x, ps, st, du_series, du_end=None, w_reg=0.0, path=None, z_local=None, path_z=None, z_local2=None):
         """adaptive layer: pullback of  sum_j <du_series[j], sol.u[j]> + w_reg * reg_val  (du_end alone = a cotangent on
         sol.u[end], what `diffeqsol_to_array` passes back).  The forward is re-run with the same draws; the backward is the
         reverse sweep over its recorded accepted steps (lrnde_sde_node_backward_recorded)."""
-        sol, st2 = self._call_adaptive(x, ps, st, path=path, z_local=z_local)
+        sol, st2 = self._call_adaptive(x, ps, st, path=path, z_local=z_local, path_z=path_z, z_local2=z_local2)
         ns = self._last_adaptive["nseries"]
         if du_series is None:
             du_series = torch.zeros((ns,) + tuple(x.shape), dtype=torch.float32, device=x.device)
