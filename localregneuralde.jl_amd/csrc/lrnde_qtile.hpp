@@ -128,20 +128,137 @@ __device__ __forceinline__ void qstore(const TileIOQ& io, int voff_rg, int soff,
 struct EpiStoreKQ {
   static constexpr int NPRE = 1;
   const ModelDev* m; float* kout; int b0, nvalid;
-  __device__ __forceinline__ void pre(int, bool, f32x4 (&)[NPRE]) const {}
-  __device__ __forceinline__ void post(int rb, bool own, const f32x4& kv, f32x4 (&)[NPRE]) const {
+  template <class G> __device__ __forceinline__ void pre(G, int, bool, f32x4 (&)[NPRE]) const {}
+  template <class G> __device__ __forceinline__ void post(G, int rb, bool own, const f32x4& kv, f32x4 (&)[NPRE]) const {
     const int lane = threadIdx.x & 63, sidx = lane & 3, q = lane >> 2;
     const int row0 = rb + q * 4;
     if (sidx < nvalid && own) *reinterpret_cast<f32x4*>(kout + (size_t)(b0 + sidx) * m->D + row0) = kv;
   }
 };
 
+// The stage operands (uprev, k1 .. k6) of a lane's two Dense-2 row groups stay in registers for the whole launch, in the
+// D-fragment layout of the MFMA: element r of group G = row 112w + 64G + 4q + r of sample s.  A row's operands are written
+// (post) and read (the next stages' post) by the same lane, so they never leave it; through an LDS buffer they cost 2 x S
+// ds_read_b128 and 2 ds_write_b128 per lane and stage, 113 KB of LDS, and a cross-wave preload and x2 pass with a workgroup
+// barrier each at the head of the launch.  The k vectors are still stored to global memory for the next launch and the
+// dense record.  Lanes that are not `own` carry values that are discarded.
+// Which k_step_q<SPEC, KT> keep them there: the specialised Dense-2 tail (KT < 4, MNIST-ODE's H = 100), whose last stream
+// block leaves ring registers free; the generic form (KT = 4) keeps the LDS buffer (EpiStageQL / EpiFinalQL below)
+__host__ __device__ constexpr bool q_regops(int KT) { return KT < 4; }
+struct RegOpsQ {
+  f32x4 up[2];    // uprev
+  f32x4 k[6][2];  // k1 .. k6
+};
+// (the group index G of pre / post is a type, IC<0> or IC<1>: every register of RegOpsQ is addressed at compile time)
+template <int S> struct EpiStageQ {
+  static constexpr int NPRE = 1;
+  TileIOQ io;
+  int off_out, off_x;
+  float dt;
+  f32x4* xl;
+  RegOpsQ* R;
+  int store_k;  // Bcast::store_k: 0 = k_S stays in registers only (its global store gets an out-of-range offset and is dropped)
+  template <class G> __device__ __forceinline__ void pre(G, int, bool, f32x4 (&)[NPRE]) const {}
+  template <class G> __device__ __forceinline__ void post(G, int rb, bool own, const f32x4& kv, f32x4 (&)[NPRE]) const {
+    constexpr int g = G::value;
+    const int lane = threadIdx.x & 63, sidx = lane & 3, q = lane >> 2;
+    constexpr int off = (S - 1) * S / 2;
+    const int vo = q_voff(io, rb, own);
+    qstore(io, store_k ? vo : 0x7ffffff0, off_out, kv);
+    R->k[S - 1][g] = kv;
+    f32x4 x;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float o[S];
+#pragma unroll
+      for (int j = 0; j < S - 1; ++j) o[j] = R->k[j][g][r];
+      o[S - 1] = kv[r];
+      float sum = (float)Tsit5::A[off] * o[0] + (float)Tsit5::A[off + 1] * o[1];
+#pragma unroll
+      for (int j = 2; j < S; ++j) sum = sum + (float)Tsit5::A[off + j] * o[j];
+      x[r] = R->up[g][r] + dt * sum;
+    }
+    if (off_x >= 0) qstore(io, vo, off_x, x);
+    if (own) xl[(rb / 4 + q) * 4 + sidx] = x;  // one quad = the B operand of 4 Dense-1 k-steps, in this wave's own segment
+  }
+};
+
+struct EpiFinalQ {
+  static constexpr int NPRE = 2;  // u (the x tile of this, the last, f-eval: the wave's own xl rows) and g6
+  TileIOQ io;
+  int off_g6, off_out;
+  float dt, abstol, reltol;
+  int want_stiff, nvalid;
+  double *aerr, *anum, *aden;
+  const f32x4* xl;
+  const RegOpsQ* R;  // uprev, k1..k6 as in EpiStageQ
+  // dense record written by the step itself (StepArgs::dense_direct): descriptor over the slot [uprev,k1,P2,P3,P4] of this
+  // attempt, voff out of range when there is none
+  __amdgpu_buffer_rsrc_t rsD; int nstB; bool rec;
+  // (lanes that are not `own` read another wave's x quads or, in the last group, up to 15 quads past the tile — inside the
+  //  h tile behind it: the value is discarded)
+  template <class G> __device__ __forceinline__ void pre(G, int rb, bool own, f32x4 (&pb)[NPRE]) const {
+    pb[0] = xl[rb + (threadIdx.x & 63)];
+    if (want_stiff) pb[1] = qload(io, q_voff(io, rb, own), off_g6);
+  }
+  template <class G> __device__ __forceinline__ void post(G, int rb, bool own, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
+    constexpr int g = G::value;
+    const int lane = threadIdx.x & 63, sidx = lane & 3;
+    const int vo = q_voff(io, rb, own);
+    const f32x4 up = R->up[g];
+    const f32x4 k1 = R->k[0][g], k2 = R->k[1][g], k3 = R->k[2][g], k4 = R->k[3][g], k5 = R->k[4][g], k6 = R->k[5][g];
+    qstore(io, vo, off_out, kv);
+    if (rec) {
+      // the attempt's record slot, straight from the operands this lane already holds: uprev, k1..k6, k7 (kv) — instead
+      // of a 25-MB copy through global memory in the next prologue
+      // (polynomial form, lrnde_math.hpp tsit5_rec_poly: [uprev, k1, P2, P3, P4] — five stores, were eight)
+      const int vd = vo;  // the slot's arrays have the state arrays' (column, row) layout
+      f32x4 P2, P3, P4;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float kk[6] = {k2[r], k3[r], k4[r], k5[r], k6[r], kv[r]};
+        float P[3];
+        tsit5_rec_poly(k1[r], kk, P);
+        P2[r] = P[0]; P3[r] = P[1]; P4[r] = P[2];
+      }
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, up), rsD, vd, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, k1), rsD, vd + nstB, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, P2), rsD, vd + 2 * nstB, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, P3), rsD, vd + 3 * nstB, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, P4), rsD, vd + 4 * nstB, 0, 0);
+    }
+    if (sidx >= nvalid || !own) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float sum = (float)Tsit5::BT[0] * k1[r] + (float)Tsit5::BT[1] * k2[r];
+      sum = sum + (float)Tsit5::BT[2] * k3[r];
+      sum = sum + (float)Tsit5::BT[3] * k4[r];
+      sum = sum + (float)Tsit5::BT[4] * k5[r];
+      sum = sum + (float)Tsit5::BT[5] * k6[r];
+      sum = sum + (float)Tsit5::BT[6] * kv[r];
+      const float utilde = dt * sum;
+      const float sc = abstol + fmaxf_(__builtin_fabsf(up[r]), __builtin_fabsf(pb[0][r])) * reltol;
+      const float rr = utilde / sc;
+      const float sq = rr * rr;
+      *aerr += (double)sq;
+      if (want_stiff) {
+        const float d1 = pb[0][r] - pb[1][r];
+        const float d2 = kv[r] - k6[r];
+        const float q1 = d1 * d1, q2 = d2 * d2;
+        *aden += (double)q1; *anum += (double)q2;
+      }
+    }
+  }
+};
+
+// The LDS form of the same epilogues, for the generic Dense-2 tail (KT = 4, q_regops): there the last stream block keeps
+// all of its 24 ring registers to the end of the f-eval and the register form does not fit 256 VGPRs (it spilled 12).
 // The stage operands (uprev, k1 .. k_{S-1}) of a workgroup's tile stay in LDS for the whole launch: kl[slot][quad*4+sample],
 // slot 0 = uprev, slot j = k_j.  Slots 4.. are written and read only by the Dense-2 wave that owns the rows (the rows of its
 // Dense-1 segment); the preloaded pairs are ordered by the __syncthreads() ahead of the x2 pass.  Re-reading them from
 // global memory went through the same L2->L1 path as the weight stream (Dense-2 streamed at 36 B/clk against
 // Dense-1's 56); the k vectors are still stored to global memory for the next launch and the dense record.
-template <int S> struct EpiStageQ {
+template <int S> struct EpiStageQL {
   static constexpr int NPRE = S;
   TileIOQ io;
   int off_up, off_k[6], off_out, off_x;
@@ -152,14 +269,14 @@ template <int S> struct EpiStageQ {
   int store_k;  // Bcast::store_k: 0 = k_S stays in LDS (its global store gets an out-of-range offset and is dropped)
   // (lanes that are not `own` read another wave's quads or, in the last group, up to 15 quads past the slot — inside the
   //  launch's slack: the value is discarded)
-  __device__ __forceinline__ void pre(int rb, bool, f32x4 (&pb)[NPRE]) const {
+  template <class G> __device__ __forceinline__ void pre(G, int rb, bool, f32x4 (&pb)[NPRE]) const {
     const int li = rb + (threadIdx.x & 63);
     pb[0] = klu[li];
     if (S > 1) pb[S > 1 ? 1 : 0] = klk[li];
 #pragma unroll
     for (int j = 2; j < S; ++j) pb[j] = kl[(size_t)(j + 2) * KL + li];
   }
-  __device__ __forceinline__ void post(int rb, bool own, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
+  template <class G> __device__ __forceinline__ void post(G, int rb, bool own, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
     const int lane = threadIdx.x & 63, sidx = lane & 3, q = lane >> 2;
     constexpr int off = (S - 1) * S / 2;
     const int vo = q_voff(io, rb, own);
@@ -182,7 +299,7 @@ template <int S> struct EpiStageQ {
   }
 };
 
-struct EpiFinalQ {
+struct EpiFinalQL {
   static constexpr int NPRE = 9;
   TileIOQ io;
   int off_up, off_u, off_k[6], off_g6, off_out;
@@ -194,7 +311,7 @@ struct EpiFinalQ {
   // dense record written by the step itself (StepArgs::dense_direct): descriptor over the slot [uprev,k1,P2,P3,P4] of this
   // attempt, voff out of range when there is none
   __amdgpu_buffer_rsrc_t rsD; int nstB; bool rec;
-  __device__ __forceinline__ void pre(int rb, bool own, f32x4 (&pb)[NPRE]) const {
+  template <class G> __device__ __forceinline__ void pre(G, int rb, bool own, f32x4 (&pb)[NPRE]) const {
     const int li = rb + (threadIdx.x & 63);
     pb[0] = klu[li];
     pb[1] = xl[li];
@@ -203,7 +320,7 @@ struct EpiFinalQ {
     for (int j = 1; j < 6; ++j) pb[2 + j] = kl[(size_t)(3 + j) * KL + li];
     if (want_stiff) pb[8] = qload(io, q_voff(io, rb, own), off_g6);
   }
-  __device__ __forceinline__ void post(int rb, bool own, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
+  template <class G> __device__ __forceinline__ void post(G, int rb, bool own, const f32x4& kv, f32x4 (&pb)[NPRE]) const {
     const int lane = threadIdx.x & 63, sidx = lane & 3;
     const int vo = q_voff(io, rb, own);
     qstore(io, vo, off_out, kv);
@@ -471,8 +588,8 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
       q_stream_load<(QSB1 + B + QAHEAD) % QSB, NSL>(st);  // wraps into the next f-eval's Dense-1 blocks
 #endif
       if constexpr (B == QSB2 - 3) {  // epilogue operands: issued ~3 blocks before they are needed
-        if (g0 < m.D) epi.pre(g0, own0, pb0);
-        if (g1 < m.D) epi.pre(g1, own1, pb1);
+        if (g0 < m.D) epi.pre(IC<0>{}, g0, own0, pb0);
+        if (g1 < m.D) epi.pre(IC<1>{}, g1, own1, pb1);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (B + 1 < QSB2) {
@@ -509,15 +626,15 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
       }
       return kv;
     };
-    if (g0 < m.D) epi.post(g0, own0, finish(g0, own0, acc0), pb0);
-    if (g1 < m.D) epi.post(g1, own1, finish(g1, own1, acc1), pb1);
+    if (g0 < m.D) epi.post(IC<0>{}, g0, own0, finish(g0, own0, acc0), pb0);
+    if (g1 < m.D) epi.post(IC<1>{}, g1, own1, finish(g1, own1, acc1), pb1);
   }
   STAMP(5); STAMPW(4);
   // No workgroup barrier here: the x quads a wave has just written are its own Dense-1 segment, read next by the same
   // wave, and a wavefront's LDS accesses are performed in program order — only the compiler must not move the next
   // f-eval's reads above these stores.  Every other LDS region keeps its order through the two barriers inside the
   // f-eval: h and the Dense-1 partials are rewritten only after every wave has passed the next barrier, i.e. after
-  // every wave's reads of them; the stage-operand slots are written and read by their owning wave only.
+  // every wave's reads of them; the stage operands are in the lanes' registers (RegOpsQ).
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   STAMP(6);
 }
@@ -665,9 +782,6 @@ __global__ __launch_bounds__(QNT) void k_init2_q(StepArgs a) {
 }
 
 // one attempted Tsit5 step, 4 columns per workgroup (same flow as k_step's fused path)
-#ifdef LRNDE_DBG_RELOAD
-__device__ int g_dbg_bad[8] = {0, 0, 1 << 30, 0, 0, 0, 0, 0};
-#endif
 template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(StepArgs a, int j) {
   STAMP(9);
   const SmemQ s = carve_q(a.m);
@@ -678,18 +792,42 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
   STAMP(10);
   // wave 0 runs the device prologue (a chain of dependent global loads: control block, partial sums) while the other
   // six waves clear the LDS tiles and stage the bias vectors: the two used to run one after the other
-  // ... and load BOTH candidate pairs (ubuf[p], kfsal[p]), p = 0, 1, of this tile into LDS: which pair is (uprev, k1)
-  // is what the prologue is deciding, and its round trip to memory plus the controller arithmetic is time in which the
-  // tile would otherwise sit unread (then one more round trip, after the decision, at the head of the step).
-  f32x4* kl = q_extra_smem(s);  // [9][KL]: 0,1 = pair 0; 2,3 = pair 1; 4..8 = k2..k6
+  // ... and every wave loads BOTH candidate pairs (ubuf[p], kfsal[p]), p = 0, 1, of its own Dense-2 rows into registers:
+  // which pair is (uprev, k1) is what the prologue is deciding, and its round trip to memory plus the controller
+  // arithmetic is time in which the tile would otherwise sit unread (then one more round trip, after the decision, at
+  // the head of the step).  Columns past the batch and lanes that are not `own` load from an out-of-range offset: zeros.
+  const TileIOQ io = make_tile_io_q(a, b0, nvalid);
+  const int qlane = (threadIdx.x & 63) >> 2;
+  const int g0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (QSEG * 4), g1 = g0 + 64;  // as in feval_qs
+  const bool own0 = g0 + qlane * 4 < a.m.D, own1 = qlane < (QSEG * 4 - 64) / 4 && g1 + qlane * 4 < a.m.D;
+  const int vo0 = q_voff(io, g0, own0), vo1 = q_voff(io, g1, own1);
+  RegOpsQ R;
+#ifndef LRNDE_NO_PRELOAD  // (diagnostic builds: the pair is read after the decision)
+  f32x4 cu[2][2], ck[2][2];  // [parity][row group]
+  auto preload = [&]() {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      cu[p][0] = qload(io, vo0, arr_off(a, p)); cu[p][1] = qload(io, vo1, arr_off(a, p));
+      ck[p][0] = qload(io, vo0, arr_off(a, 2 + p)); ck[p][1] = qload(io, vo1, arr_off(a, 2 + p));
+    }
+  };
+#else
+  auto preload = [&]() {};
+#endif
+  constexpr bool REGS = q_regops(KT);
+  f32x4* kl = REGS ? nullptr : q_extra_smem(s);  // LDS form: [9][KL]: 0,1 = pair 0; 2,3 = pair 1; 4..8 = k2..k6
   const int KL = a.m.KQ1p * 4;
   if (threadIdx.x < 64) {
+    if constexpr (REGS) preload();  // in flight while the wave decides
     step_prologue(a, j, s.bc);
   } else {
-    // (LDS init first: the prologue's own loads are already on their way when these 72 wave-loads reach the CU's
-    //  address path, which takes them one every ~16 cycles)
+    // (LDS init first: the prologue's own loads are already on their way when these 48 (LDS form: 72) wave-loads reach
+    //  the CU's address path, which takes them one every ~16 cycles)
     smem_init_q<true>(a.m, s);
-#ifndef LRNDE_NO_PRELOAD  // (diagnostic builds: the pair is read after the decision, in the x2 pass below)
+    if constexpr (REGS) {
+      preload();
+    } else {  // LDS form: the six waves load both pairs of the whole tile into kl, ordered by the barrier below
+#ifndef LRNDE_NO_PRELOAD
     constexpr int NTH = QNT - 64;
     const int tid = (int)threadIdx.x - 64;
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -710,8 +848,9 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
       if (i < KQ1 * 4) { kl[i] = v[r][0]; kl[KL + i] = v[r][1]; kl[2 * KL + i] = v[r][2]; kl[3 * KL + i] = v[r][3]; }
     }
 #endif
+    }
   }
-  __syncthreads();
+  __syncthreads();  // Bcast is written, the LDS tiles are clear, the biases staged (register form: the only barrier of the head)
   STAMP(11);
   const Bcast bc = *s.bc;
 
@@ -792,51 +931,77 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
   const float c1 = (float)Tsit5::C[0], c2 = (float)Tsit5::C[1], c3 = (float)Tsit5::C[2],
               c4 = (float)Tsit5::C[3];
   double aerr = 0.0, anum = 0.0, aden = 0.0;
-  const TileIOQ io = make_tile_io_q(a, b0, nvalid);
-  const f32x4* klu = kl + (bc.cur ? 2 : 0) * KL;  // the pair the prologue chose
-  const f32x4* klk = kl + (bc.cur ? 3 : 1) * KL;
-  const int o_up = arr_off(a, bc.cur), o_un = arr_off(a, bc.cur ^ 1);
-  const int o_k1 = arr_off(a, 2 + bc.cur), o_k7 = arr_off(a, 2 + (bc.cur ^ 1));
+  const int o_un = arr_off(a, bc.cur ^ 1), o_k7 = arr_off(a, 2 + (bc.cur ^ 1));
   const int o_g6 = arr_off(a, 9);
-  __syncthreads();  // smem_init_q is complete before the x tile is written
-  {  // x2 = uprev + (dt*a21)*k1   (src/perform_step.jl:11-12)
-    const float a21dt = dt * (float)Tsit5::A[0];
-    q_tile_foreach(a.m, b0, nvalid, KQ1, [&](int kq, int sidx, bool valid, size_t g) {
-#ifdef LRNDE_DBG_RELOAD
-      {  // diagnostic: compare the preloaded pair with what global memory holds now; count the quads that differ
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        const f32x4 ug = valid ? ld4(ubuf_at(a, bc.cur) + g) : z, fg = valid ? ld4(kfsal_at(a, bc.cur) + g) : z;
-        const f32x4 ul = klu[kq * 4 + sidx], fl = klk[kq * 4 + sidx];
-        bool bad = false;
-        for (int h = 0; h < 4; ++h) bad = bad || __builtin_bit_cast(unsigned, ug[h]) != __builtin_bit_cast(unsigned, ul[h]) || __builtin_bit_cast(unsigned, fg[h]) != __builtin_bit_cast(unsigned, fl[h]);
-        if (bad) { atomicAdd(&g_dbg_bad[0], 1); atomicMax(&g_dbg_bad[1], kq * 4 + sidx); atomicMin(&g_dbg_bad[2], kq * 4 + sidx); atomicAdd(&g_dbg_bad[3 + (bc.cur & 1)], 1); }
-      }
+  const int o_up = arr_off(a, bc.cur), o_k1 = arr_off(a, 2 + bc.cur);
+  const f32x4* klu = nullptr; const f32x4* klk = nullptr;
+  if constexpr (REGS) {
+#ifndef LRNDE_NO_PRELOAD
+    {  // the pair the prologue chose (bc.cur is workgroup-uniform); the other one is dropped
+      const bool odd = bc.cur != 0;
+      R.up[0] = odd ? cu[1][0] : cu[0][0]; R.up[1] = odd ? cu[1][1] : cu[0][1];
+      R.k[0][0] = odd ? ck[1][0] : ck[0][0]; R.k[0][1] = odd ? ck[1][1] : ck[0][1];
+    }
+#else
+    R.up[0] = qload(io, vo0, o_up); R.up[1] = qload(io, vo1, o_up);
+    R.k[0][0] = qload(io, vo0, o_k1); R.k[0][1] = qload(io, vo1, o_k1);
 #endif
-#ifdef LRNDE_NO_PRELOAD
-      {
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        const_cast<f32x4*>(klu)[kq * 4 + sidx] = valid ? ld4(ubuf_at(a, bc.cur) + g) : z;
-        const_cast<f32x4*>(klk)[kq * 4 + sidx] = valid ? ld4(kfsal_at(a, bc.cur) + g) : z;
-      }
-#endif
-      const f32x4 u = klu[kq * 4 + sidx], f = klk[kq * 4 + sidx];  // (zeros in the columns past the batch)
-      f32x4 x;
+    {  // x2 = uprev + (dt*a21)*k1   (src/perform_step.jl:11-12): each lane forms the quads of its own rows and writes them
+       // to its wave's own segment of the x tile, which only this wave reads (Dense-1 of stage 2) — no workgroup barrier,
+       // the wavefront-scope fence keeps the compiler from moving those reads above the stores (see the end of feval_qs)
+      const float a21dt = dt * (float)Tsit5::A[0];
+      const int sidx = threadIdx.x & 3;
+      f32x4 x0, x1;
 #pragma unroll
-      for (int h = 0; h < 4; ++h) x[h] = u[h] + a21dt * f[h];
-      s.xl[kq * 4 + sidx] = x;
-    });
+      for (int h = 0; h < 4; ++h) {
+        x0[h] = R.up[0][h] + a21dt * R.k[0][0][h];
+        x1[h] = R.up[1][h] + a21dt * R.k[0][1][h];
+      }
+      if (own0) s.xl[(g0 / 4 + qlane) * 4 + sidx] = x0;  // (zeros in the columns past the batch)
+      if (own1) s.xl[(g1 / 4 + qlane) * 4 + sidx] = x1;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+  } else {  // LDS form: a cross-wave pass over the tile between two workgroup barriers
+    klu = kl + (bc.cur ? 2 : 0) * KL;  // the pair the prologue chose
+    klk = kl + (bc.cur ? 3 : 1) * KL;
+    __syncthreads();  // smem_init_q is complete before the x tile is written
+    {  // x2 = uprev + (dt*a21)*k1   (src/perform_step.jl:11-12)
+      const float a21dt = dt * (float)Tsit5::A[0];
+      q_tile_foreach(a.m, b0, nvalid, KQ1, [&](int kq, int sidx, bool valid, size_t g) {
+#ifdef LRNDE_NO_PRELOAD
+        {
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          const_cast<f32x4*>(klu)[kq * 4 + sidx] = valid ? ld4(ubuf_at(a, bc.cur) + g) : z;
+          const_cast<f32x4*>(klk)[kq * 4 + sidx] = valid ? ld4(kfsal_at(a, bc.cur) + g) : z;
+        }
+#endif
+        const f32x4 u = klu[kq * 4 + sidx], f = klk[kq * 4 + sidx];  // (zeros in the columns past the batch)
+        f32x4 x;
+#pragma unroll
+        for (int h = 0; h < 4; ++h) x[h] = u[h] + a21dt * f[h];
+        s.xl[kq * 4 + sidx] = x;
+      });
+    }
+    __syncthreads();
   }
-  __syncthreads();
   STAMP(12);
 #define LRNDE_QSTAGE(S, TS)                                                             \
   do {                                                                                  \
-    EpiStageQ<S> e;                                                                     \
-    e.io = io; e.off_up = o_up; e.off_k[0] = o_k1;                                      \
-    _Pragma("unroll") for (int qq = 0; qq < 5; ++qq) e.off_k[1 + qq] = arr_off(a, 4 + qq); \
-    e.off_out = arr_off(a, 4 + (S - 2));                                                \
-    e.off_x = (S == 6) ? o_un : ((S == 5 && a.want_stiff) ? o_g6 : -1);                 \
-    e.dt = dt; e.xl = s.xl; e.kl = kl; e.KL = KL; e.klu = klu; e.klk = klk; e.store_k = bc.store_k;  \
-    feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT>(a.m, s, fc, (TS), e);                 \
+    const int off_out = arr_off(a, 4 + (S - 2));                                        \
+    const int off_x = (S == 6) ? o_un : ((S == 5 && a.want_stiff) ? o_g6 : -1);         \
+    if constexpr (REGS) {                                                               \
+      EpiStageQ<S> e;                                                                   \
+      e.io = io; e.off_out = off_out; e.off_x = off_x;                                  \
+      e.dt = dt; e.xl = s.xl; e.R = &R; e.store_k = bc.store_k;                         \
+      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT>(a.m, s, fc, (TS), e);         \
+    } else {                                                                            \
+      EpiStageQL<S> e;                                                                  \
+      e.io = io; e.off_up = o_up; e.off_k[0] = o_k1;                                    \
+      _Pragma("unroll") for (int qq = 0; qq < 5; ++qq) e.off_k[1 + qq] = arr_off(a, 4 + qq); \
+      e.off_out = off_out; e.off_x = off_x;                                             \
+      e.dt = dt; e.xl = s.xl; e.kl = kl; e.KL = KL; e.klu = klu; e.klk = klk; e.store_k = bc.store_k; \
+      feval_qs<EpiStageQL<S>, (QSB * (S - 2)) % QRING, KT>(a.m, s, fc, (TS), e);        \
+    }                                                                                   \
     STAMP(11 + S);                                                                      \
   } while (0)
   LRNDE_QSTAGE(2, t + c1 * dt);
@@ -845,19 +1010,30 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
   LRNDE_QSTAGE(5, t + c4 * dt);
   LRNDE_QSTAGE(6, t + dt);
 #undef LRNDE_QSTAGE
-  EpiFinalQ ef;
-  ef.io = io; ef.off_up = o_up; ef.off_u = o_un; ef.off_k[0] = o_k1;
+  const bool rec = a.dense != nullptr && a.dense_direct && bc.dense_slot >= 0;
+  const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(a.dense + (size_t)(rec ? bc.dense_slot : 0) * REC_ARRAYS * (size_t)a.n_local), 0, (int)(a.n_local * 4 * REC_ARRAYS), 0x00020000);
+  if constexpr (REGS) {
+    EpiFinalQ ef;
+    ef.io = io; ef.off_g6 = o_g6; ef.off_out = o_k7;
+    ef.dt = dt; ef.abstol = a.abstol; ef.reltol = a.reltol; ef.want_stiff = a.want_stiff; ef.nvalid = nvalid;
+    ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
+    ef.xl = s.xl; ef.R = &R;
+    ef.rec = rec; ef.nstB = (int)(a.n_local * 4); ef.rsD = rsD;
+    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT>(a.m, s, fc, t + dt, ef);
+  } else {
+    EpiFinalQL ef;
+    ef.io = io; ef.off_up = o_up; ef.off_u = o_un; ef.off_k[0] = o_k1;
 #pragma unroll
-  for (int qq = 0; qq < 5; ++qq) ef.off_k[1 + qq] = arr_off(a, 4 + qq);
-  ef.off_g6 = o_g6; ef.off_out = o_k7;
-  ef.dt = dt; ef.abstol = a.abstol; ef.reltol = a.reltol; ef.want_stiff = a.want_stiff; ef.nvalid = nvalid;
-  ef.D = a.m.D;
-  ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
-  ef.xl = s.xl; ef.kl = kl; ef.KL = KL; ef.klu = klu; ef.klk = klk;
-  ef.rec = a.dense != nullptr && a.dense_direct && bc.dense_slot >= 0; ef.nstB = (int)(a.n_local * 4);
-  ef.rsD = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dense + (size_t)(ef.rec ? bc.dense_slot : 0) * REC_ARRAYS * (size_t)a.n_local), 0,
-                                             (int)(a.n_local * 4 * REC_ARRAYS), 0x00020000);
-  feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT>(a.m, s, fc, t + dt, ef);
+    for (int qq = 0; qq < 5; ++qq) ef.off_k[1 + qq] = arr_off(a, 4 + qq);
+    ef.off_g6 = o_g6; ef.off_out = o_k7;
+    ef.dt = dt; ef.abstol = a.abstol; ef.reltol = a.reltol; ef.want_stiff = a.want_stiff; ef.nvalid = nvalid;
+    ef.D = a.m.D;
+    ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
+    ef.xl = s.xl; ef.kl = kl; ef.KL = KL; ef.klu = klu; ef.klk = klk;
+    ef.rec = rec; ef.nstB = (int)(a.n_local * 4); ef.rsD = rsD;
+    feval_qs<EpiFinalQL, (QSB * 5) % QRING, KT>(a.m, s, fc, t + dt, ef);
+  }
   STAMP(18);
   block_sum3_q(s.red, aerr, anum, aden, a.want_stiff != 0);
   STAMP(19);
