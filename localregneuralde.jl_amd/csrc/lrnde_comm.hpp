@@ -13,6 +13,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
+#include "lrnde_buf.hpp"
 
 constexpr int LRNDE_LC_MAXR = 16;
 
@@ -25,8 +26,7 @@ struct lrnde_local_comm {
   bool broken = false;  // a rank timed out or failed: every later barrier fails at once instead of hanging
   // per-rank slots of the collective in flight
   const void* send[LRNDE_LC_MAXR] = {};
-  void* tmp[LRNDE_LC_MAXR] = {};
-  size_t tmp_bytes[LRNDE_LC_MAXR] = {};
+  DevBuf<char> tmp[LRNDE_LC_MAXR];   // (each on its rank's device: lrnde_local_comm_destroy resets it with that device current)
   hipEvent_t ready[LRNDE_LC_MAXR] = {};  // rank's send buffer is complete (recorded on its stream)
   hipEvent_t done[LRNDE_LC_MAXR] = {};   // rank has finished READING every peer's send buffer
   int device[LRNDE_LC_MAXR] = {};
@@ -71,12 +71,7 @@ template <class T> __global__ void k_lc_sum(LcPtrs s, int n, size_t count, T* ou
 inline int lc_allreduce(lrnde_local_comm* lc, int rank, hipStream_t stream, const void* send, void* recv, size_t count,
                         bool is_double) {
   const size_t bytes = count * (is_double ? sizeof(double) : sizeof(float));
-  if (lc->tmp_bytes[rank] < bytes) {
-    if (lc->tmp[rank]) (void)hipFree(lc->tmp[rank]);
-    lc->tmp[rank] = nullptr; lc->tmp_bytes[rank] = 0;
-    if (hipMalloc(&lc->tmp[rank], bytes) != hipSuccess) return LRNDE_HIP_ERROR;
-    lc->tmp_bytes[rank] = bytes;
-  }
+  if (lc->tmp[rank].grow(bytes) != hipSuccess) return LRNDE_HIP_ERROR;
   lc->send[rank] = send;
   if (hipEventRecord(lc->ready[rank], stream) != hipSuccess) return LRNDE_HIP_ERROR;
   if (!lc_barrier(lc)) return LRNDE_NCCL_ERROR;
@@ -86,8 +81,8 @@ inline int lc_allreduce(lrnde_local_comm* lc, int rank, hipStream_t stream, cons
     if (r != rank && hipStreamWaitEvent(stream, lc->ready[r], 0) != hipSuccess) return LRNDE_HIP_ERROR;
   }
   int nb = (int)((count + 255) / 256); if (nb > 1024) nb = 1024; if (nb < 1) nb = 1;
-  if (is_double) hipLaunchKernelGGL(k_lc_sum<double>, dim3(nb), dim3(256), 0, stream, s, lc->n, count, (double*)lc->tmp[rank]);
-  else hipLaunchKernelGGL(k_lc_sum<float>, dim3(nb), dim3(256), 0, stream, s, lc->n, count, (float*)lc->tmp[rank]);
+  if (is_double) hipLaunchKernelGGL(k_lc_sum<double>, dim3(nb), dim3(256), 0, stream, s, lc->n, count, (double*)lc->tmp[rank].get());
+  else hipLaunchKernelGGL(k_lc_sum<float>, dim3(nb), dim3(256), 0, stream, s, lc->n, count, (float*)lc->tmp[rank].get());
   if (hipGetLastError() != hipSuccess) return LRNDE_HIP_ERROR;
   if (hipEventRecord(lc->done[rank], stream) != hipSuccess) return LRNDE_HIP_ERROR;
   if (!lc_barrier(lc)) return LRNDE_NCCL_ERROR;

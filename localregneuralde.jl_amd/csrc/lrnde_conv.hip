@@ -42,6 +42,7 @@
 #include "lrnde.h"
 #include "lrnde_hooks.h"
 #include "lrnde_math.hpp"
+#include "lrnde_buf.hpp"
 #include "lrnde_stepctl.hpp"
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
@@ -1676,37 +1677,37 @@ struct lrnde_conv {
   bool have_params = false;
   int NG1 = 0, NG2 = 0;
   // parameters
-  void *w1h = nullptr, *w1l = nullptr, *w2h = nullptr, *w2l = nullptr, *w3h = nullptr, *w3l = nullptr; bool split = false;  // f32 split packs (fp16 hi / lo)
-  void *w1 = nullptr, *w2 = nullptr, *w3 = nullptr, *w1b = nullptr;  // w1b: conv1 in bf16 fragments (bf16 mode)
-  void *w2f = nullptr, *w3f = nullptr;  // bf16 mode: fp32 fragments of conv2 / conv3 for the backward pass (fp32 adjoint)
+  DevBuf<char> w1h, w1l, w2h, w2l, w3h, w3l; bool split = false;  // f32 split packs (fp16 hi / lo)
+  DevBuf<char> w1, w2, w3, w1b;  // w1b: conv1 in bf16 fragments (bf16 mode)
+  DevBuf<char> w2f, w3f;  // bf16 mode: fp32 fragments of conv2 / conv3 for the backward pass (fp32 adjoint)
   bool force_f32 = false;               // bf16 mode: run the fp32 kernels (set for the duration of a VJP)
-  float *ts1 = nullptr, *ts2 = nullptr, *ts3 = nullptr;
-  float *bn = nullptr;       // scale1 bias1 scale2 bias2 (4*Hc)
-  float *stat = nullptr;     // mean1 inv1 mean2 inv2 (4*Hc)
-  float *bn_state = nullptr; // running mean1 var1 mean2 var2 (test mode), or null
+  DevBuf<float> ts1, ts2, ts3;
+  DevBuf<float> bn;       // scale1 bias1 scale2 bias2 (4*Hc)
+  DevBuf<float> stat;     // mean1 inv1 mean2 inv2 (4*Hc)
+  DevBuf<float> bn_state; // running mean1 var1 mean2 var2 (test mode), or null
   // workspace (per batch size)
   int wsB = 0;
-  float *y1 = nullptr, *y2 = nullptr;
-  double* part = nullptr; int nwg = 0;
-  float* vec = nullptr;      // 11 state-sized vectors
-  double *sums = nullptr, *sums_host = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevBuf<float> y1, y2;
+  DevBuf<double> part; int nwg = 0;
+  DevBuf<float> vec;      // 11 state-sized vectors
+  DevBuf<double> sums; PinBuf<double> sums_host;
+  HipEvent ev0, ev1;
   int num_cu = 256;
   std::vector<float> last_ts;
   // backward pass
-  float *w1t = nullptr, *w2t = nullptr, *w3t = nullptr;  // transposed-conv weight packs
-  float* params = nullptr; bool w_t_valid = false;        // device copy of the flat parameters
-  float *zeros = nullptr;                                  // 9*64 zeros (no t-plane term in a cotangent)
-  float *bwm = nullptr;                                    // m1_2 m2_2 m1_1 m2_1 (4*Hc)
-  float *g1 = nullptr, *g2 = nullptr;                      // NHWC cotangents of the hidden layers
-  double* part_bw = nullptr; float *pw = nullptr, *pt = nullptr; int bwB = 0;
+  DevBuf<float> w1t, w2t, w3t;  // transposed-conv weight packs
+  DevBuf<float> params; bool w_t_valid = false;       // device copy of the flat parameters
+  DevBuf<float> zeros;                                  // 9*64 zeros (no t-plane term in a cotangent)
+  DevBuf<float> bwm;                                    // m1_2 m2_2 m1_1 m2_1 (4*Hc)
+  DevBuf<float> g1, g2;                      // NHWC cotangents of the hidden layers
+  DevBuf<double> part_bw; DevBuf<float> pw, pt; int bwB = 0;
   // dense record of the accepted forward steps ([uprev, k1..k7] each) and what else the backward pass needs
   bool dense_on = false; size_t dense_n = 0;
-  std::vector<float*> dense; std::vector<float> dense_t, dense_dt;
-  float* rec_u1 = nullptr; size_t rec_n = 0;
+  std::vector<DevBuf<float>> dense; std::vector<float> dense_t, dense_dt;
+  DevBuf<float> rec_u1;
   unsigned long long rec_gen = 0;
   bool rec_valid = false; int rec_B = 0, rec_mode = 0, rec_reg_type = 0; float rec_t0 = 0.f, rec_t2 = 0.f, rec_t1 = 0.f; lrnde_solve_opts rec_opts;
-  float* adj = nullptr; size_t adj_elems = 0;
+  DevBuf<float> adj;
 };
 
 namespace {
@@ -1727,17 +1728,6 @@ int cfail(lrnde_conv* c, int code, const char* fmt, ...) {
       return cfail(c, LRNDE_HIP_ERROR, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-// scoped device allocation for per-call temporaries (freed on every return path)
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-  template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 inline size_t state_n(const lrnde_conv* c, int B) { return (size_t)B * c->d.width * c->d.height * c->d.channels; }
 inline int strip_rows(const lrnde_conv* c) {
   // largest TR dividing H with TR*W <= 128 pixels (8 M tiles)
@@ -1751,14 +1741,15 @@ inline int cinp_of(int cin) { return cin == 8 ? 12 : cin; }  // 64-channel tiles
 
 int ensure_ws(lrnde_conv* c, int B) {
   if (B == c->wsB) return LRNDE_OK;
-  for (void* p : {(void*)c->y1, (void*)c->y2, (void*)c->part, (void*)c->vec}) if (p) CHK(c, hipFree(p));
-  c->y1 = c->y2 = nullptr; c->part = nullptr; c->vec = nullptr; c->wsB = 0;
+  c->wsB = 0;
+  for (DevBuf<float>* b : {&c->y1, &c->y2, &c->vec}) CHK(c, b->reset());
+  CHK(c, c->part.reset());
   const size_t px = (size_t)B * c->d.width * c->d.height;
   c->nwg = B * (c->d.height / strip_rows(c));
-  CHK(c, hipMalloc(&c->y1, sizeof(float) * px * c->d.hidden));
-  CHK(c, hipMalloc(&c->y2, sizeof(float) * px * c->d.hidden));
-  CHK(c, hipMalloc(&c->part, sizeof(double) * (size_t)c->nwg * c->d.hidden * 2));
-  CHK(c, hipMalloc(&c->vec, sizeof(float) * 11 * state_n(c, B)));
+  CHK(c, c->y1.once(px * c->d.hidden));
+  CHK(c, c->y2.once(px * c->d.hidden));
+  CHK(c, c->part.once((size_t)c->nwg * c->d.hidden * 2));
+  CHK(c, c->vec.once(11 * state_n(c, B)));
   c->wsB = B;
   return LRNDE_OK;
 }
@@ -1839,7 +1830,7 @@ int launch_rhs_ex(lrnde_conv* c, const float* u, float t, int B, float* du, bool
   a.CIN = C; a.CINP = cinp_of(C); a.COUT = Hc; a.in = u; a.out = c->y1; a.wpk = c->w1; a.tsum = c->ts1; a.t = t;
   const bool bf = c->d.compute_dtype == LRNDE_BF16 && !c->force_f32;
   const bool f32_of_bf = c->d.compute_dtype == LRNDE_BF16 && c->force_f32;  // fp32 kernels on a bf16 handle (VJP recompute)
-  a.wpk2 = bf ? c->w1b : nullptr;
+  a.wpk2 = bf ? c->w1b.get() : nullptr;
   if (c->split) { a.wpk = c->w1h; a.wpk2 = c->w1l; }
   a.part = train ? c->part : nullptr;
   const size_t stg_bytes = sizeof(float) * (size_t)a.TP * 68;  // epilogue transpose buffer (aliases the tile)
@@ -1877,15 +1868,15 @@ constexpr int NWGW = 256;    // workgroups of the weight-gradient kernels
 int ensure_bw(lrnde_conv* c, int B) {
   const int Hc = c->d.hidden, C = c->d.channels;
   if (!c->w2t) {
-    CHK(c, hipMalloc(&c->w3t, (size_t)((9 * C + 15) / 16) * 4 * 1024));
-    CHK(c, hipMalloc(&c->w2t, (size_t)((9 * Hc + 15) / 16) * 4 * 1024));
-    CHK(c, hipMalloc(&c->w1t, (size_t)((9 * Hc + 15) / 16) * 1 * 1024));
-    CHK(c, hipMalloc(&c->zeros, sizeof(float) * 9 * 64));
+    CHK(c, c->w3t.once((size_t)((9 * C + 15) / 16) * 4 * 1024 / sizeof(float)));
+    CHK(c, c->w2t.once((size_t)((9 * Hc + 15) / 16) * 4 * 1024 / sizeof(float)));
+    CHK(c, c->w1t.once((size_t)((9 * Hc + 15) / 16) * 1 * 1024 / sizeof(float)));
+    CHK(c, c->zeros.once(9 * 64));
     CHK(c, hipMemsetAsync(c->zeros, 0, sizeof(float) * 9 * 64, c->stream));
-    CHK(c, hipMalloc(&c->bwm, sizeof(float) * 4 * Hc));
-    CHK(c, hipMalloc(&c->part_bw, sizeof(double) * NBW1 * 64 * 2));
-    CHK(c, hipMalloc(&c->pw, sizeof(float) * (size_t)2 * NWGW * 9 * 64 * 64));
-    CHK(c, hipMalloc(&c->pt, sizeof(float) * (size_t)2 * NWGW * 9 * 64));
+    CHK(c, c->bwm.once(4 * Hc));
+    CHK(c, c->part_bw.once(NBW1 * 64 * 2));
+    CHK(c, c->pw.once((size_t)2 * NWGW * 9 * 64 * 64));
+    CHK(c, c->pt.once((size_t)2 * NWGW * 9 * 64));
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_wgrad<1, 1, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_wgrad<1, 0, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_wgrad<0, 1, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1902,12 +1893,12 @@ int ensure_bw(lrnde_conv* c, int B) {
     c->w_t_valid = true;
   }
   if (c->bwB != B) {
-    if (c->g1) CHK(c, hipFree(c->g1));
-    if (c->g2) CHK(c, hipFree(c->g2));
-    c->g1 = c->g2 = nullptr; c->bwB = 0;
+    c->bwB = 0;
+    CHK(c, c->g1.reset());
+    CHK(c, c->g2.reset());
     const size_t px = (size_t)B * c->d.width * c->d.height;
-    CHK(c, hipMalloc(&c->g1, sizeof(float) * px * Hc));
-    CHK(c, hipMalloc(&c->g2, sizeof(float) * px * Hc));
+    CHK(c, c->g1.once(px * Hc));
+    CHK(c, c->g2.once(px * Hc));
     c->bwB = B;
   }
   return LRNDE_OK;
@@ -2121,24 +2112,24 @@ int lrnde_conv_create(lrnde_conv** out, const lrnde_conv_desc* d, int device, vo
   const int C = d->channels, Hc = d->hidden;
   c->NG1 = (9 * C + 15) / 16;
   c->NG2 = d->compute_dtype == LRNDE_BF16 ? (9 * Hc + 31) / 32 : (9 * Hc + 15) / 16;
-  bool ok = hipMalloc(&c->w1, (size_t)c->NG1 * 4 * 1024) == hipSuccess && hipMalloc(&c->w1b, (size_t)3 * 4 * 1024) == hipSuccess &&
-            hipMalloc(&c->w2, (size_t)c->NG2 * 4 * 1024) == hipSuccess &&
-            hipMalloc(&c->w3, (size_t)c->NG2 * 1 * 1024) == hipSuccess &&
-            hipMalloc(&c->ts1, sizeof(float) * 9 * 64) == hipSuccess && hipMalloc(&c->ts2, sizeof(float) * 9 * 64) == hipSuccess &&
-            hipMalloc(&c->ts3, sizeof(float) * 9 * 16) == hipSuccess &&
-            hipMalloc(&c->bn, sizeof(float) * 4 * Hc) == hipSuccess && hipMalloc(&c->stat, sizeof(float) * 4 * Hc) == hipSuccess &&
-            hipMalloc(&c->bn_state, sizeof(float) * 4 * Hc) == hipSuccess &&
-            hipMalloc(&c->sums, sizeof(double) * NSUMB * 3) == hipSuccess &&
-            hipHostMalloc(&c->sums_host, sizeof(double) * NSUMB * 3) == hipSuccess &&
-            hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess;
+  bool ok = c->w1.once((size_t)c->NG1 * 4 * 1024) == hipSuccess && c->w1b.once((size_t)3 * 4 * 1024) == hipSuccess &&
+            c->w2.once((size_t)c->NG2 * 4 * 1024) == hipSuccess &&
+            c->w3.once((size_t)c->NG2 * 1 * 1024) == hipSuccess &&
+            c->ts1.once(9 * 64) == hipSuccess && c->ts2.once(9 * 64) == hipSuccess &&
+            c->ts3.once(9 * 16) == hipSuccess &&
+            c->bn.once(4 * Hc) == hipSuccess && c->stat.once(4 * Hc) == hipSuccess &&
+            c->bn_state.once(4 * Hc) == hipSuccess &&
+            c->sums.once(NSUMB * 3) == hipSuccess &&
+            c->sums_host.once(NSUMB * 3) == hipSuccess &&
+            c->ev0.create() == hipSuccess && c->ev1.create() == hipSuccess;
   if (ok && d->compute_dtype == LRNDE_BF16) {
     const size_t ng = (size_t)(9 * Hc + 15) / 16;
-    ok = hipMalloc(&c->w2f, ng * 4 * 1024) == hipSuccess && hipMalloc(&c->w3f, ng * 1 * 1024) == hipSuccess;
+    ok = c->w2f.once(ng * 4 * 1024) == hipSuccess && c->w3f.once(ng * 1 * 1024) == hipSuccess;
   }
   if (ok && d->compute_dtype == LRNDE_F32_SPLIT) {
-    ok = hipMalloc(&c->w1h, (size_t)3 * 4 * 1024) == hipSuccess && hipMalloc(&c->w1l, (size_t)3 * 4 * 1024) == hipSuccess &&
-         hipMalloc(&c->w2h, (size_t)18 * 4 * 1024) == hipSuccess && hipMalloc(&c->w2l, (size_t)18 * 4 * 1024) == hipSuccess &&
-         hipMalloc(&c->w3h, (size_t)18 * 1024) == hipSuccess && hipMalloc(&c->w3l, (size_t)18 * 1024) == hipSuccess;
+    ok = c->w1h.once((size_t)3 * 4 * 1024) == hipSuccess && c->w1l.once((size_t)3 * 4 * 1024) == hipSuccess &&
+         c->w2h.once((size_t)18 * 4 * 1024) == hipSuccess && c->w2l.once((size_t)18 * 4 * 1024) == hipSuccess &&
+         c->w3h.once((size_t)18 * 1024) == hipSuccess && c->w3l.once((size_t)18 * 1024) == hipSuccess;
     c->split = ok;
   }
   if (!ok) { lrnde_conv_destroy(c); return LRNDE_HIP_ERROR; }
@@ -2151,14 +2142,6 @@ int lrnde_conv_destroy(lrnde_conv* c) {
   if (!c) return LRNDE_OK;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream); else hipDeviceSynchronize();
-  void* ptrs[] = {c->params, c->w1t, c->w2t, c->w3t, c->zeros, c->bwm, c->g1, c->g2, c->part_bw, c->pw, c->pt, c->w1h, c->w1l, c->w2h, c->w2l, c->w3h, c->w3l, c->w1, c->w1b, c->w2, c->w3, c->ts1, c->ts2, c->ts3, c->bn, c->stat, c->bn_state, c->y1, c->y2, c->part, c->vec, c->sums, c->w2f, c->w3f};
-  for (void* p : ptrs) if (p) hipFree(p);
-  for (float* d : c->dense) if (d) hipFree(d);
-  if (c->rec_u1) hipFree(c->rec_u1);
-  if (c->adj) hipFree(c->adj);
-  if (c->sums_host) hipHostFree(c->sums_host);
-  if (c->ev0) hipEventDestroy(c->ev0);
-  if (c->ev1) hipEventDestroy(c->ev1);
   delete c;
   return LRNDE_OK;
 }
@@ -2183,9 +2166,9 @@ int lrnde_conv_set_params(lrnde_conv* c, const float* p, size_t n) {
     hipLaunchKernelGGL(k_pack_conv, dim3(64), dim3(256), 0, c->stream, w3, Hc, C, (9 * Hc + 15) / 16, 1, 0, c->w3f, c->ts3);
   }
   if (c->split) {
-    hipLaunchKernelGGL(k_pack_conv_split, dim3(64), dim3(256), 0, c->stream, w1, C, Hc, 3, 4, (_Float16*)c->w1h, (_Float16*)c->w1l);
-    hipLaunchKernelGGL(k_pack_conv_split, dim3(64), dim3(256), 0, c->stream, w2, Hc, Hc, 18, 4, (_Float16*)c->w2h, (_Float16*)c->w2l);
-    hipLaunchKernelGGL(k_pack_conv_split, dim3(64), dim3(256), 0, c->stream, w3, Hc, C, 18, 1, (_Float16*)c->w3h, (_Float16*)c->w3l);
+    hipLaunchKernelGGL(k_pack_conv_split, dim3(64), dim3(256), 0, c->stream, w1, C, Hc, 3, 4, (_Float16*)c->w1h.get(), (_Float16*)c->w1l.get());
+    hipLaunchKernelGGL(k_pack_conv_split, dim3(64), dim3(256), 0, c->stream, w2, Hc, Hc, 18, 4, (_Float16*)c->w2h.get(), (_Float16*)c->w2l.get());
+    hipLaunchKernelGGL(k_pack_conv_split, dim3(64), dim3(256), 0, c->stream, w3, Hc, C, 18, 1, (_Float16*)c->w3h.get(), (_Float16*)c->w3l.get());
   }
   CHK(c, hipGetLastError());
   CHK(c, hipMemcpyAsync(c->bn, g1, sizeof(float) * 2 * Hc, hipMemcpyDeviceToDevice, c->stream));
@@ -2196,7 +2179,7 @@ int lrnde_conv_set_params(lrnde_conv* c, const float* p, size_t n) {
     hipLaunchKernelGGL(k_bn_from_state, dim3(1), dim3(64), 0, c->stream, st ? st + 2 * Hc : nullptr, Hc, c->d.bn_eps, c->stat + 2 * Hc, c->stat + 3 * Hc);
     CHK(c, hipGetLastError());
   }
-  if (!c->params) CHK(c, hipMalloc(&c->params, sizeof(float) * n));
+  CHK(c, c->params.once(n));
   CHK(c, hipMemcpyAsync(c->params, p, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   c->w_t_valid = false;
   c->have_params = true;
@@ -2350,8 +2333,8 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
       dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
       if (c->dense_on) {  // [uprev, k1, k2..k6, k7] of this step, for the adjoint's interpolant
         const size_t idx = c->dense_t.size();
-        if (c->dense_n != n) { for (float* d : c->dense) if (d) hipFree(d); c->dense.clear(); c->dense_n = n; }
-        if (idx >= c->dense.size()) { float* d = nullptr; CHK(c, hipMalloc(&d, sizeof(float) * 8 * n)); c->dense.push_back(d); }
+        if (c->dense_n != n) { c->dense.clear(); c->dense_n = n; }
+        if (idx >= c->dense.size()) { DevBuf<float> d; CHK(c, d.once(8 * n)); c->dense.push_back(std::move(d)); }
         float* d = c->dense[idx];
         CHK(c, hipMemcpyAsync(d, uprev, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
         CHK(c, hipMemcpyAsync(d + n, k1, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
@@ -2391,27 +2374,24 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
   lrnde_solve_opts oo = *o;
   *reg_val = 0.0f;
   if (t1_used) *t1_used = t2;
-  float* us = nullptr;
-  auto done = [&](int code) { if (us) hipFree(us); return code; };
+  DevBuf<float> us, u1;   // this call's save slots and u(t1): released on every return path
   if (mode == LRNDE_MODE_NONE) {  // src/layers/neural_ode.jl:56-60
     oo.save_everystep = 0;
-    CHK(c, hipMalloc(&us, sizeof(float) * n * 2));
+    CHK(c, us.once(n * 2));
     float sv[1] = {t2}, ts[2];
-    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, 1, us, ts, 2, st, nullptr, 0))) return done(rc);
+    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, 1, us, ts, 2, st, nullptr, 0))) return rc;
     CHK(c, hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
     *nfe = st->nf;
-    return done(LRNDE_OK);
+    return LRNDE_OK;
   }
   float t1;
-  float* u1 = nullptr;
-  CHK(c, hipMalloc(&u1, sizeof(float) * n));
-  auto done2 = [&](int code) { hipFree(u1); return done(code); };
+  CHK(c, u1.once(n));
   if (mode == LRNDE_MODE_UNBIASED) {  // :68-84, saveat = [t1, t2]
     t1 = t1_or_rand;
     oo.save_everystep = 0;
-    if (hipMalloc(&us, sizeof(float) * n * 3) != hipSuccess) return done2(cfail(c, LRNDE_HIP_ERROR, "allocation failed"));
+    if (us.once(n * 3) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
     float sv[2] = {t1, t2}, ts[3];
-    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, 2, us, ts, 3, st, nullptr, 0))) return done2(rc);
+    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, 2, us, ts, 3, st, nullptr, 0))) return rc;
     const int i1 = oo.save_start ? 1 : 0;
     hipMemcpy(u1, us + (size_t)i1 * n, sizeof(float) * n, hipMemcpyDeviceToDevice);
     hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice);
@@ -2420,22 +2400,22 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
     // every accepted step is kept: start with room for 32 and re-solve with more if that overflows (a state is
     // 8 MB at the CIFAR shape, B=256; the running statistics are rewound so the retry does not count twice)
     std::vector<float> ts;
-    float* bn0 = nullptr;
+    DevBuf<float> bn0;
     const int Hc4b = 4 * c->d.hidden;
-    if (hipMalloc(&bn0, sizeof(float) * Hc4b) != hipSuccess) return done2(cfail(c, LRNDE_HIP_ERROR, "allocation failed"));
+    if (bn0.once(Hc4b) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
     hipMemcpyAsync(bn0, c->bn_state, sizeof(float) * Hc4b, hipMemcpyDeviceToDevice, c->stream);
     for (int cap = 32;; cap *= 4) {
       if (cap > oo.maxiters + 2) cap = oo.maxiters + 2;
-      if (us) { hipFree(us); us = nullptr; }
-      if (hipMalloc(&us, sizeof(float) * n * cap) != hipSuccess) { hipFree(bn0); return done2(cfail(c, LRNDE_HIP_ERROR, "allocation failed")); }
+      (void)us.reset();
+      if (us.once(n * cap) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
       ts.assign(cap, 0.f);
       rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, nullptr, 0, us, ts.data(), cap, st, nullptr, 0);
       if (rc == LRNDE_CAPACITY && cap < oo.maxiters + 2) { hipMemcpyAsync(c->bn_state, bn0, sizeof(float) * Hc4b, hipMemcpyDeviceToDevice, c->stream); continue; }
       break;
     }
-    hipFree(bn0);
-    if (rc) return done2(rc);
-    if (st->nsaved < 2) return done2(cfail(c, LRNDE_BADARG, "biased mode needs at least two saved steps"));
+    (void)bn0.reset();
+    if (rc) return rc;
+    if (st->nsaved < 2) return cfail(c, LRNDE_BADARG, "biased mode needs at least two saved steps");
     const int m = st->nsaved - 1;
     int idx = (int)(t1_or_rand * (float)m);
     if (idx >= m) idx = m - 1;
@@ -2446,7 +2426,7 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
   }
   if (t1_used) *t1_used = t1;
   if (c->dense_on) {
-    if (c->rec_n != n) { if (c->rec_u1) hipFree(c->rec_u1); c->rec_u1 = nullptr; if (hipMalloc(&c->rec_u1, sizeof(float) * n) != hipSuccess) return done2(cfail(c, LRNDE_HIP_ERROR, "allocation failed")); c->rec_n = n; }
+    if (c->rec_u1.resize_exact(n) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
     hipMemcpy(c->rec_u1, u1, sizeof(float) * n, hipMemcpyDeviceToDevice);
   }
   // _get_ode_integrator :33-38 => init on (t1,t2); _perform_step :77.  The layer returns the model state as it was
@@ -2455,15 +2435,15 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
   float dtl, ee, re, rs;
   const int Hc4 = 4 * c->d.hidden;
   hipMemcpyAsync(V, c->bn_state, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream);  // V[0..n) is free here
-  if ((rc = init_dt(c, u1, B, t1, t2, oo.abstol, oo.reltol, V + 2 * n, V + 10 * n, V + 9 * n, &dtl))) return done2(rc);
+  if ((rc = init_dt(c, u1, B, t1, t2, oo.abstol, oo.reltol, V + 2 * n, V + 10 * n, V + 9 * n, &dtl))) return rc;
   double s[3];
-  if ((rc = tsit5_step(c, u1, V + 2 * n, B, t1, dtl, oo.abstol, oo.reltol, V + n, V + 8 * n, V + 3 * n, V + 9 * n, V + 10 * n, s))) return done2(rc);
+  if ((rc = tsit5_step(c, u1, V + 2 * n, B, t1, dtl, oo.abstol, oo.reltol, V + n, V + 8 * n, V + 3 * n, V + 9 * n, V + 10 * n, s))) return rc;
   reg_values(s, n, dtl, &ee, &re, &rs);
   hipMemcpyAsync(c->bn_state, V, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream);
   hipStreamSynchronize(c->stream);
   *reg_val = (reg_type == LRNDE_REG_STIFFNESS_ESTIMATE) ? rs : re;
   *nfe = st->nf + (6 + 3);
-  return done2(LRNDE_OK);
+  return LRNDE_OK;
 }
 
 int lrnde_conv_bench_rhs(lrnde_conv* c, const float* u, float t, int32_t B, int32_t reps, float* us_host) {
@@ -2488,11 +2468,7 @@ int lrnde_conv_bench_rhs(lrnde_conv* c, const float* u, float t, int32_t B, int3
 namespace {
 
 int ensure_adj(lrnde_conv* c, size_t elems) {
-  if (c->adj_elems >= elems) return LRNDE_OK;
-  if (c->adj) CHK(c, hipFree(c->adj));
-  c->adj = nullptr; c->adj_elems = 0;
-  CHK(c, hipMalloc(&c->adj, sizeof(float) * elems));
-  c->adj_elems = elems;
+  CHK(c, c->adj.grow(elems));
   return LRNDE_OK;
 }
 
@@ -2650,11 +2626,11 @@ int lrnde_conv_node_backward(lrnde_conv* c, const float* x, int32_t B, float t0,
   if (rc) return rc;
   if (!x || !o || !du_end || !dx || !dp || !st_fwd || !st_bwd) return cfail(c, LRNDE_BADARG, "null pointer");
   // 1. forward with the dense record
-  float* u_end = nullptr;
-  CHK(c, hipMalloc(&u_end, sizeof(float) * state_n(c, B)));
+  DevBuf<float> u_end;   // scratch of this call: released as soon as the forward has returned
+  CHK(c, u_end.once(state_n(c, B)));
   float regv = 0.f; int nfe = 0;
   rc = lrnde_conv_node_forward_record(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, u_end, &regv, &nfe, st_fwd, nullptr);
-  hipFree(u_end);
+  (void)u_end.reset();
   if (rc) return rc;
   return lrnde_conv_node_backward_recorded(c, B, du_end, w_reg, dx, dp, st_bwd);
 }
@@ -2706,16 +2682,15 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
   CHK(c, hipStreamSynchronize(c->stream));
   // 3. regulariser: dp += w_reg * d reg_val / d p
   if (mode != LRNDE_MODE_NONE && w_reg != 0.0f) {
-    float *k1 = nullptr, *gr = nullptr;
-    CHK(c, hipMalloc(&k1, sizeof(float) * n));
-    CHK(c, hipMalloc(&gr, sizeof(float) * P));
+    DevBuf<float> k1, gr;
+    CHK(c, k1.once(n));
+    CHK(c, gr.once(P));
     float dtl = 0.f, rv = 0.f;
     float* V = c->vec;
     rc = init_dt(c, c->rec_u1, B, t1, t2, o->abstol, o->reltol, k1, V + 10 * n, V + 9 * n, &dtl);
     if (!rc) rc = step_reg_grad(c, c->rec_u1, k1, B, t1, dtl, o->abstol, o->reltol, reg_type, gr, &rv);
     if (!rc) { const float* g1[1] = {gr}; rc = lincomb(c, dp, dp, 0.f, 1, g1, &w_reg, P); }
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LRNDE_HIP_ERROR;
-    hipFree(k1); hipFree(gr);
     if (rc) return rc;
   }
   return LRNDE_OK;
@@ -2960,9 +2935,8 @@ int lrnde_cifar_stem_forward(lrnde_conv* c, const float* x, int32_t B, const flo
   const int H = c->d.height, W = c->d.width;
   const long plane = (long)H * W, total = (long)B * 8 * plane;
   const int nblk = (int)(((long)B * plane + SH_T - 1) / SH_T);
-  DevBuf ba0, bmi, bpart;
-  CHK(c, ba0.alloc(sizeof(float) * total)); CHK(c, bmi.alloc(sizeof(float) * 16)); CHK(c, bpart.alloc(sizeof(double) * nblk * 16));
-  float *a0 = ba0.as<float>(), *mi = bmi.as<float>(); double* part = bpart.as<double>();
+  DevBuf<float> a0, mi; DevBuf<double> part;
+  CHK(c, a0.once(total)); CHK(c, mi.once(16)); CHK(c, part.once(nblk * 16));
   if (bn_state_out) hipLaunchKernelGGL(k_stem_state_copy, dim3(1), dim3(64), 0, c->stream, bn_state, bn_state_out);
   int rc = stem_common(c, x, B, ps, bn_state, a0, mi, part, nblk, bn_state_out);
   if (!rc) {
@@ -2978,10 +2952,9 @@ int lrnde_cifar_stem_backward(lrnde_conv* c, const float* x, int32_t B, const fl
   const int H = c->d.height, W = c->d.width;
   const long plane = (long)H * W, total = (long)B * 8 * plane;
   const int nblk = (int)(((long)B * plane + SH_T - 1) / SH_T);
-  DevBuf ba0, bmi, bmm, bpart, bpartw;
-  CHK(c, ba0.alloc(sizeof(float) * total)); CHK(c, bmi.alloc(sizeof(float) * 16)); CHK(c, bmm.alloc(sizeof(float) * 16));
-  CHK(c, bpart.alloc(sizeof(double) * nblk * 16)); CHK(c, bpartw.alloc(sizeof(float) * (size_t)nblk * 140));
-  float *a0 = ba0.as<float>(), *mi = bmi.as<float>(), *mm = bmm.as<float>(), *partw = bpartw.as<float>(); double* part = bpart.as<double>();
+  DevBuf<float> a0, mi, mm, partw; DevBuf<double> part;
+  CHK(c, a0.once(total)); CHK(c, mi.once(16)); CHK(c, mm.once(16));
+  CHK(c, part.once(nblk * 16)); CHK(c, partw.once((size_t)nblk * 140));
   int rc = stem_common(c, x, B, ps, bn_state, a0, mi, part, nblk);
   if (!rc) {
     hipLaunchKernelGGL(k_stem_bwd1, dim3(nblk), dim3(SH_T), 0, c->stream, (const float*)a0, du0, (const float*)mi, (const float*)(mi + 8), B, plane, part);
@@ -3002,10 +2975,9 @@ int lrnde_cifar_head_ce(lrnde_conv* c, const float* u, int32_t B, const float* p
   const long plane = D, npx = (long)B * plane;
   const int nblk = (int)((npx + SH_T - 1) / SH_T);
   const float* pd = ph + 73;
-  DevBuf bz, bv, bdl, blb, bdv, bpartw;
-  CHK(c, bz.alloc(sizeof(float) * npx)); CHK(c, bv.alloc(sizeof(float) * npx)); CHK(c, bdl.alloc(sizeof(float) * (size_t)B * K));
-  CHK(c, blb.alloc(sizeof(float) * B)); CHK(c, bdv.alloc(sizeof(float) * npx)); CHK(c, bpartw.alloc(sizeof(float) * (size_t)nblk * 73));
-  float *z = bz.as<float>(), *v = bv.as<float>(), *dl = bdl.as<float>(), *lb = blb.as<float>(), *dv = bdv.as<float>(), *partw = bpartw.as<float>();
+  DevBuf<float> z, v, dl, lb, dv, partw;
+  CHK(c, z.once(npx)); CHK(c, v.once(npx)); CHK(c, dl.once((size_t)B * K));
+  CHK(c, lb.once(B)); CHK(c, dv.once(npx)); CHK(c, partw.once((size_t)nblk * 73));
   hipLaunchKernelGGL(k_head_conv, dim3(nblk), dim3(SH_T), 0, c->stream, u, ph, B, H, W, z, v);
   hipLaunchKernelGGL(k_cls_fwd, dim3((B + 3) / 4), dim3(256), 0, c->stream, (const float*)v, pd, labels, B, D, K, logits, dl, lb);
   if (du || dph) {

@@ -48,6 +48,7 @@
 #include "lrnde_hooks.h"
 #include "lrnde_math.hpp"
 #include "lrnde_stepctl.hpp"
+#include "lrnde_buf.hpp"
 #include "lrnde_comm.hpp"
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
@@ -1738,33 +1739,33 @@ struct lrnde_ctx {
   ModelDev m{};
   bool have_params = false;
   // packed weights
-  float *W1p = nullptr, *W2p = nullptr, *w1t = nullptr, *b1 = nullptr, *w2t = nullptr, *b2 = nullptr;
-  float *W1q = nullptr, *W2q = nullptr;
-  float *V1p = nullptr, *U2p = nullptr;          // transposed weights for the backward pass
-  float *V1q = nullptr, *U2q = nullptr;          // the same in the 4-column layouts
-  float *bw_y = nullptr, *bw_h = nullptr, *bw_dp = nullptr, *bw_da = nullptr;  // VJP scratch (B*D, B*Hp, B*Hp, B*Hp), three sets each
+  DevBuf<float> W1p, W2p, w1t, b1, w2t, b2;
+  DevBuf<float> W1q, W2q;
+  DevBuf<float> V1p, U2p;          // transposed weights for the backward pass
+  DevBuf<float> V1q, U2q;          // the same in the 4-column layouts
+  DevBuf<float> bw_y, bw_h, bw_dp, bw_da;  // VJP scratch (B*D, B*Hp, B*Hp, B*Hp), three sets each
   // deferred parameter-gradient GEMM (adjoint Tsit5 loop): the GEMM of RHS evaluation e rides in the launch of the VJP
   // of evaluation e+1 (k_vjp_q_pg); scratch set bw_cur is the one the next VJP writes
   bool pg_defer = false, pg_pending = false; int bw_cur = 0; PgradArgs pg_args;
   bool pg_accumulate = false;  // the next parameter-gradient GEMM adds to gp instead of overwriting it (regulariser sweep)
   int bwB = 0;
   // dense forward record + adjoint work vectors
-  float *dense = nullptr, *dense_t = nullptr, *dense_dt = nullptr;
+  DevBuf<float> dense, dense_t, dense_dt;
   int dense_cap = 0; size_t dense_n = 0; bool dense_on = false;
-  float* adj = nullptr; size_t adj_elems = 0;   // 11 vectors of N = B*D + P floats
-  double* adj_part = nullptr; double* adj_part_host = nullptr;
+  DevBuf<float> adj;   // 11 vectors of N = B*D + P floats
+  DevBuf<double> adj_part; PinBuf<double> adj_part_host;
   // device-side adjoint controller (lrnde_adjoint.hpp): control blocks, initdt partial sums, tstops, pinned read-back slots
-  AdjCtrl* adj_ctl = nullptr; AdjCtrl* adj_ctl_host = nullptr; double* adj_ipart = nullptr; float* adj_stops = nullptr; int adj_stops_cap = 0;
-  hipEvent_t adj_ev[2] = {nullptr, nullptr};
+  DevBuf<AdjCtrl> adj_ctl; PinBuf<AdjCtrl> adj_ctl_host; DevBuf<double> adj_ipart; DevBuf<float> adj_stops;
+  HipEvent adj_ev[2];
   // overlapped stage launches of the adjoint loop (LRNDE_ADJ_OVERLAP): second stream, cross-stream events, device sync words
-  hipStream_t adj_stream2 = nullptr; hipEvent_t adj_evA[2] = {nullptr, nullptr}, adj_evB[2] = {nullptr, nullptr};
-  int* adj_sync = nullptr; int adj_launch_id = 0;
-  int* adj_hstat = nullptr; int* adj_hstat_dev = nullptr; int adj_seq = 0;  // pinned progress word of the adjoint loop (host / device view)
+  hipStream_t adj_stream2 = nullptr; HipEvent adj_evA[2], adj_evB[2];
+  DevBuf<int> adj_sync; int adj_launch_id = 0;
+  PinBuf<int> adj_hstat; int adj_seq = 0;  // pinned, mapped progress word of the adjoint loop
   std::vector<float> last_ts;  // sol.t of the last node_forward (cotangent times of the adjoint)
   std::vector<int> series_idx; std::vector<float> series_t;  // the caller's view of that solution: save slots and times
   float last_t1 = 0.f; int last_i1 = 0;
   // backward workspace kept across calls: u(t1) of the recorded forward, k1 and the regulariser's gradient
-  float* rec_gr = nullptr; size_t rec_n = 0;
+  DevBuf<float> rec_gr; size_t rec_n = 0;
   float rec_dt1 = 0.f, rec_eest = 0.f, rec_snum = 0.f, rec_sden = 0.f;  // the local step's dt and scalars (forward's)
   float loc_dt = 0.f, loc_eest = 0.f, loc_snum = 0.f, loc_sden = 0.f;    // the same of the LAST layer forward
   // arguments of the last lrnde_node_forward_record (what lrnde_node_backward_recorded differentiates)
@@ -1774,26 +1775,22 @@ struct lrnde_ctx {
   int wsNB = 0;  // tile width the workspace (partial-sum vectors) was sized for
   // workspace
   int wsB = 0;
-  float* state = nullptr;  // 10 * B * D floats: ubuf[2], kfsal[2], ks[5], g6
-  Ctrl* ctrl = nullptr;
-  double* part = nullptr;      // send [2][nwg_global*PSTRIDE]
-  double* part_rx = nullptr;   // recv (nranks > 1)
-  double* pinit = nullptr;
-  double* pinit_rx = nullptr;
-  float* saveat_dev = nullptr;
-  int saveat_cap = 0;
-  float* tsaved_dev = nullptr;   // saved times: pinned host array (tsaved_host) as the device sees it
-  float* tsaved_host = nullptr;
-  int tsaved_cap = 0;
+  DevBuf<float> state;  // 10 * B * D floats: ubuf[2], kfsal[2], ks[5], g6
+  DevBuf<Ctrl> ctrl;
+  DevBuf<double> part;      // send [2][nwg_global*PSTRIDE]
+  DevBuf<double> part_rx;   // recv (nranks > 1)
+  DevBuf<double> pinit;
+  DevBuf<double> pinit_rx;
+  DevBuf<float> saveat_dev;
+  PinBuf<float> tsaved_host;   // saved times: pinned, mapped (the step kernels write through its device view)
   // pinned host block the step prologue reports to (solve_progress): [0] the progress word, +64 B the final control block
-  unsigned long long* prog_host = nullptr; unsigned long long* prog_dev = nullptr;
-  lrnde_trace_row* trace_dev = nullptr;
-  int trace_cap = 0;
-  float* usave = nullptr;  // internal save slots for node_forward
+  PinBuf<unsigned long long> prog_host;
+  DevBuf<lrnde_trace_row> trace_dev;
+  DevBuf<float> usave;  // internal save slots for node_forward
   size_t usave_slots = 0, usave_slot_elems = 0;
-  Ctrl* ctrl_host = nullptr;  // pinned [2]
-  hipEvent_t ev_norm = nullptr;  // vec_norm's read-back
-  void* cls_ws = nullptr; size_t cls_ws_bytes = 0; void* cls_host = nullptr;  // lrnde_classifier_ce workspace (device / pinned)
+  PinBuf<Ctrl> ctrl_host;  // pinned [2]
+  HipEvent ev_norm;  // vec_norm's read-back
+  DevBuf<char> cls_ws; PinBuf<char> cls_host;  // lrnde_classifier_ce workspace (device / pinned)
   // comm
   ncclComm_t comm = nullptr;           // RCCL communicator (one process per GPU)
   lrnde_local_comm* lcomm = nullptr;   // or: in-process local communicator (lrnde_hooks.h), never both
@@ -1801,9 +1798,9 @@ struct lrnde_ctx {
   // per-rank pre-reduction of the error-norm partial sums (StepArgs::prered): default for sharded handles; with
   // LRNDE_GATHER_TILES=1 in the environment every tile's partial is exchanged instead (the exact gather)
   bool prered = false;
-  int* arrive = nullptr; double* tile_part = nullptr; double* tile_pinit = nullptr;
+  DevBuf<int> arrive; DevBuf<double> tile_part, tile_pinit;
   // timing
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, evp[2] = {nullptr, nullptr};
+  HipEvent ev0, ev1, evp[2];
   float last_ms = 0.f;
   bool time_solves = false;  // lrnde_last_solve_kernel_ms has been called once: solves bracket their kernels with events
   int last_launches = 0;
@@ -1817,7 +1814,7 @@ struct lrnde_ctx {
   // spend the sweep's ~30 launch calls inside the forward, with the device idle)
   bool sweep_pending = false; int sw_B = 0, sw_reg_type = 0; float sw_t1 = 0.f, sw_abstol = 0.f, sw_reltol = 0.f;
   std::function<int()> after_first_attempt;  // adj_solve_device calls it once, after enqueuing its first attempt
-  hipEvent_t ev_side_local = nullptr, ev_side_sweep = nullptr;
+  HipEvent ev_side_local, ev_side_sweep;
   // host-side phase clock of the layer forward (lrnde_host_phases, diagnostics): time points of the call in flight, sums over calls
   std::chrono::steady_clock::time_point hp_t[8];
   double hp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long hp_n = 0;
@@ -1835,17 +1832,17 @@ struct lrnde_ctx {
   int field = 0;
   lrnde_chain_desc chain{};
   ChainDev cd{};
-  int* ch_meta = nullptr; float *ch_wf = nullptr, *ch_wg = nullptr;  // layer table, forward / backward weight images
+  DevBuf<int> ch_meta; DevBuf<float> ch_wf, ch_wg;  // layer table, forward / backward weight images
   int ch_gfloats = 0;
   size_t ch_vjp_lds = 0;                                             // dynamic LDS of k_vjp_chain
-  float* ch_part = nullptr; size_t ch_part_n = 0;                    // per-workgroup parameter cotangents of k_vjp_chain
+  DevBuf<float> ch_part;                   // per-workgroup parameter cotangents of k_vjp_chain
   // the chain handle's device-controlled adjoint loop (lrnde_chain_adjoint.hpp): control blocks, per-(stage, workgroup)
   // parameter cotangents, norm partials, tstop / impulse tables — allocated on first use, regrown only for a larger batch
-  ChAdjCtrl* cha_ctl = nullptr;
-  float* cha_gpart = nullptr; size_t cha_gpart_n = 0;
-  double* cha_dpart = nullptr; size_t cha_dpart_n = 0;
-  float* cha_stops = nullptr; int cha_stops_cap = 0;
-  ChAdjImp* cha_imp = nullptr; int cha_imp_cap = 0;
+  DevBuf<ChAdjCtrl> cha_ctl;
+  DevBuf<float> cha_gpart;
+  DevBuf<double> cha_dpart;
+  DevBuf<float> cha_stops;
+  DevBuf<ChAdjImp> cha_imp;
   // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device), the kernels it
   // enqueued and the waits the host made with nothing enqueued behind them
   int adj_kind = 0, adj_launches = 0, adj_waits = 0;
@@ -1986,37 +1983,31 @@ int ensure_workspace(lrnde_ctx* c, int B) {
   const int nwg = (B + QNB - 1) / QNB;  // sized for the finer tile: covers both shapes
   const int nwg_global = nwg * c->nranks;
   if (B != c->wsB) {
-    if (c->state) HIPCHK(c, hipFree(c->state));
-    if (c->part) HIPCHK(c, hipFree(c->part));
-    if (c->part_rx) HIPCHK(c, hipFree(c->part_rx));
-    if (c->pinit) HIPCHK(c, hipFree(c->pinit));
-    if (c->pinit_rx) HIPCHK(c, hipFree(c->pinit_rx));
-    if (c->tile_part) HIPCHK(c, hipFree(c->tile_part));
-    if (c->tile_pinit) HIPCHK(c, hipFree(c->tile_pinit));
-    c->state = nullptr; c->part = c->part_rx = c->pinit = c->pinit_rx = c->tile_part = c->tile_pinit = nullptr;
-    HIPCHK(c, hipMalloc(&c->state, sizeof(float) * n * 10));
-    const size_t pb = sizeof(double) * 2 * (size_t)nwg_global * PSTRIDE;
-    HIPCHK(c, hipMalloc(&c->part, pb));
-    HIPCHK(c, hipMalloc(&c->pinit, pb));
+    // every buffer sized by B is dropped first, then allocated anew: B changed, so none can be kept
+    for (DevBuf<double>* b : {&c->part, &c->part_rx, &c->pinit, &c->pinit_rx, &c->tile_part, &c->tile_pinit}) HIPCHK(c, b->reset());
+    HIPCHK(c, c->state.resize_exact(n * 10));
+    const size_t pn = 2 * (size_t)nwg_global * PSTRIDE, pb = sizeof(double) * pn;
+    HIPCHK(c, c->part.resize_exact(pn));
+    HIPCHK(c, c->pinit.resize_exact(pn));
     HIPCHK(c, hipMemsetAsync(c->part, 0, pb, c->stream));
     HIPCHK(c, hipMemsetAsync(c->pinit, 0, pb, c->stream));
     if (sharded(c)) {  // nranks > 1 (or LRNDE_FORCE_COMM: the same path on one rank)
-      HIPCHK(c, hipMalloc(&c->part_rx, pb));
-      HIPCHK(c, hipMalloc(&c->pinit_rx, pb));
+      HIPCHK(c, c->part_rx.resize_exact(pn));
+      HIPCHK(c, c->pinit_rx.resize_exact(pn));
       HIPCHK(c, hipMemsetAsync(c->part_rx, 0, pb, c->stream));
       HIPCHK(c, hipMemsetAsync(c->pinit_rx, 0, pb, c->stream));
       if (c->prered) {
-        const size_t tb = sizeof(double) * 2 * (size_t)nwg * PSTRIDE;
-        HIPCHK(c, hipMalloc(&c->tile_part, tb));
-        HIPCHK(c, hipMalloc(&c->tile_pinit, tb));
-        if (!c->arrive) HIPCHK(c, hipMalloc(&c->arrive, sizeof(int) * 4));
+        const size_t tn = 2 * (size_t)nwg * PSTRIDE;
+        HIPCHK(c, c->tile_part.resize_exact(tn));
+        HIPCHK(c, c->tile_pinit.resize_exact(tn));
+        HIPCHK(c, c->arrive.once(4));
         HIPCHK(c, hipMemsetAsync(c->arrive, 0, sizeof(int) * 4, c->stream));
       }
     }
     c->wsB = B;
   }
-  if (!c->ctrl) HIPCHK(c, hipMalloc(&c->ctrl, sizeof(Ctrl) * 2));
-  if (!c->ctrl_host) HIPCHK(c, hipHostMalloc(&c->ctrl_host, sizeof(Ctrl) * 2));
+  HIPCHK(c, c->ctrl.once(2));
+  HIPCHK(c, c->ctrl_host.once(2));
   return LRNDE_OK;
 }
 
@@ -2194,8 +2185,9 @@ int side_get(lrnde_ctx* c, int B, lrnde_ctx** out) {
     lrnde_ctx* s = new lrnde_ctx();
     s->is_side = true; s->device = c->device;
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_side_local, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_side_sweep, hipEventDisableTiming) != hipSuccess) {
+        c->ev_side_local.create(hipEventDisableTiming) != hipSuccess ||
+        c->ev_side_sweep.create(hipEventDisableTiming) != hipSuccess) {
+      if (s->stream) hipStreamDestroy(s->stream);
       delete s;
       return fail(c, LRNDE_HIP_ERROR, "companion stream / events could not be created");
     }
@@ -2203,9 +2195,9 @@ int side_get(lrnde_ctx* c, int B, lrnde_ctx** out) {
   }
   lrnde_ctx* s = c->side;
   s->desc = c->desc; s->m = c->m; s->have_params = c->have_params;
-  s->W1p = c->W1p; s->W2p = c->W2p; s->w1t = c->w1t; s->b1 = c->b1; s->w2t = c->w2t; s->b2 = c->b2;
-  s->W1q = c->W1q; s->W2q = c->W2q; s->V1p = c->V1p; s->U2p = c->U2p; s->V1q = c->V1q; s->U2q = c->U2q;
-  s->field = c->field; s->chain = c->chain; s->cd = c->cd; s->ch_meta = c->ch_meta; s->ch_wf = c->ch_wf; s->ch_wg = c->ch_wg;
+  s->W1p.borrow(c->W1p); s->W2p.borrow(c->W2p); s->w1t.borrow(c->w1t); s->b1.borrow(c->b1); s->w2t.borrow(c->w2t); s->b2.borrow(c->b2);
+  s->W1q.borrow(c->W1q); s->W2q.borrow(c->W2q); s->V1p.borrow(c->V1p); s->U2p.borrow(c->U2p); s->V1q.borrow(c->V1q); s->U2q.borrow(c->U2q);
+  s->field = c->field; s->chain = c->chain; s->cd = c->cd; s->ch_meta.borrow(c->ch_meta); s->ch_wf.borrow(c->ch_wf); s->ch_wg.borrow(c->ch_wg);
   s->ch_gfloats = c->ch_gfloats; s->ch_vjp_lds = c->ch_vjp_lds;
   const int rc = ensure_workspace(s, B);
   if (rc) { c->err = s->err; return rc; }
@@ -2267,28 +2259,24 @@ int lrnde_create(lrnde_ctx** out, const lrnde_model_desc* d, int device, void* s
   m.act = d->act; m.td = d->time_dep ? 1 : 0;
   const size_t nW1 = (size_t)(((Hp / 16 + TG - 1) / TG) * TG) * (Dp / 16) * 256;
   const size_t nW2 = (size_t)(Dp / 16) * (((Hp / 16 + SEGK - 1) / SEGK) * SEGK) * 256;
-  bool ok = hipMalloc(&c->W1p, sizeof(float) * nW1) == hipSuccess &&
-            hipMalloc(&c->W2p, sizeof(float) * nW2) == hipSuccess &&
-            hipMalloc(&c->V1p, sizeof(float) * nW1) == hipSuccess &&
-            hipMalloc(&c->U2p, sizeof(float) * nW2) == hipSuccess &&
-            hipMalloc(&c->w1t, sizeof(float) * Hp) == hipSuccess &&
-            hipMalloc(&c->b1, sizeof(float) * Hp) == hipSuccess &&
-            hipMalloc(&c->w2t, sizeof(float) * Dp) == hipSuccess &&
-            hipMalloc(&c->b2, sizeof(float) * Dp) == hipSuccess &&
-            hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
-            hipEventCreate(&c->evp[0]) == hipSuccess && hipEventCreate(&c->evp[1]) == hipSuccess;
+  bool ok = c->W1p.once(nW1) == hipSuccess && c->W2p.once(nW2) == hipSuccess &&
+            c->V1p.once(nW1) == hipSuccess && c->U2p.once(nW2) == hipSuccess &&
+            c->w1t.once(Hp) == hipSuccess && c->b1.once(Hp) == hipSuccess &&
+            c->w2t.once(Dp) == hipSuccess && c->b2.once(Dp) == hipSuccess &&
+            c->ev0.create() == hipSuccess && c->ev1.create() == hipSuccess &&
+            c->evp[0].create() == hipSuccess && c->evp[1].create() == hipSuccess;
   m.KQ1p = (((d->state_dim + 3) / 4 + QSEG - 1) / QSEG) * QSEG;  // whole canonical segments
   m.KQ2p = QSEG;                                                  // H <= 112 (q-tile eligibility)
   m.RG1 = (d->hidden_dim + 63) / 64;
   m.RG2 = (d->state_dim + 63) / 64;
-  ok = ok && hipMalloc(&c->W1q, sizeof(float) * (size_t)m.RG1 * m.KQ1p * 256) == hipSuccess &&
-       hipMalloc(&c->W2q, sizeof(float) * (size_t)q_w2_groups(m.KQ1p) * m.KQ2p * 256) == hipSuccess &&
-       hipMalloc(&c->V1q, sizeof(float) * (size_t)m.RG1 * m.KQ1p * 256) == hipSuccess &&
-       hipMalloc(&c->U2q, sizeof(float) * (size_t)m.RG2 * m.KQ2p * 256) == hipSuccess;
+  ok = ok && c->W1q.once((size_t)m.RG1 * m.KQ1p * 256) == hipSuccess &&
+       c->W2q.once((size_t)q_w2_groups(m.KQ1p) * m.KQ2p * 256) == hipSuccess &&
+       c->V1q.once((size_t)m.RG1 * m.KQ1p * 256) == hipSuccess &&
+       c->U2q.once((size_t)m.RG2 * m.KQ2p * 256) == hipSuccess;
   if (!ok) { lrnde_destroy(c); return LRNDE_HIP_ERROR; }
   m.W1q = c->W1q; m.W2q = c->W2q;
-  m.W1p = reinterpret_cast<const f32x4*>(c->W1p);
-  m.W2p = reinterpret_cast<const f32x4*>(c->W2p);
+  m.W1p = reinterpret_cast<const f32x4*>(c->W1p.get());
+  m.W2p = reinterpret_cast<const f32x4*>(c->W2p.get());
   m.w1t = c->w1t; m.b1 = c->b1; m.w2t = c->w2t; m.b2 = c->b2;
   *out = c;
   return LRNDE_OK;
@@ -2372,11 +2360,10 @@ int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int device, v
   set_smem_attr();
   c->ch_gfloats = (int)wg;
   c->ch_vjp_lds = vjp_lds;
-  bool ok = hipMalloc(&c->ch_meta, sizeof(int) * meta.size()) == hipSuccess &&
-            hipMalloc(&c->ch_wf, sizeof(float) * wf) == hipSuccess &&
-            hipMalloc(&c->ch_wg, sizeof(float) * (wg > 0 ? wg : 1)) == hipSuccess &&
-            hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
-            hipEventCreate(&c->evp[0]) == hipSuccess && hipEventCreate(&c->evp[1]) == hipSuccess;
+  bool ok = c->ch_meta.once(meta.size()) == hipSuccess && c->ch_wf.once(wf) == hipSuccess &&
+            c->ch_wg.once(wg > 0 ? wg : 1) == hipSuccess &&
+            c->ev0.create() == hipSuccess && c->ev1.create() == hipSuccess &&
+            c->evp[0].create() == hipSuccess && c->evp[1].create() == hipSuccess;
   ok = ok && hipMemcpy(c->ch_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { lrnde_destroy(c); return chain_refuse(LRNDE_HIP_ERROR, "device allocation failed"); }
   ChainDev& cd = c->cd;
@@ -2392,45 +2379,15 @@ int lrnde_destroy(lrnde_ctx* c) {
   if (!c) return LRNDE_OK;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream); else hipDeviceSynchronize();
-  if (c->side) {  // the companion borrows the packed weights: drop the borrowed pointers, free what it owns
-    lrnde_ctx* s = c->side;
-    hipStream_t ss = s->stream;
+  if (c->side) {  // the companion's weights are borrowed (DevBuf::borrow): deleting it frees only what it owns
+    hipStream_t ss = c->side->stream;
     hipStreamSynchronize(ss);
-    s->W1p = s->W2p = s->w1t = s->b1 = s->w2t = s->b2 = s->W1q = s->W2q = s->V1p = s->U2p = s->V1q = s->U2q = nullptr;
-    s->ch_wf = s->ch_wg = nullptr; s->ch_meta = nullptr;
-    lrnde_destroy(s);
+    lrnde_destroy(c->side);
     hipStreamDestroy(ss);
-    if (c->ev_side_local) hipEventDestroy(c->ev_side_local);
-    if (c->ev_side_sweep) hipEventDestroy(c->ev_side_sweep);
     c->side = nullptr;
   }
   if (c->comm) ncclCommDestroy(c->comm);
-  if (c->adj_part_host) hipHostFree(c->adj_part_host);
-  void* ptrs[] = {c->dense, c->dense_t, c->dense_dt, c->adj, c->adj_part, c->V1p, c->U2p, c->V1q, c->U2q, c->bw_y, c->bw_h, c->bw_dp, c->bw_da, c->W1q, c->W2q, c->W1p, c->W2p, c->w1t, c->b1, c->w2t, c->b2, c->state, c->ctrl, c->part,
-                  c->part_rx, c->pinit, c->pinit_rx, c->arrive, c->tile_part, c->tile_pinit, c->rec_gr, c->saveat_dev, c->trace_dev,
-                  c->usave, c->ch_meta, c->ch_wf, c->ch_wg, c->ch_part,
-                  c->cha_ctl, c->cha_gpart, c->cha_dpart, c->cha_stops, c->cha_imp};
-  for (void* p : ptrs) if (p) hipFree(p);
-  if (c->ctrl_host) hipHostFree(c->ctrl_host);
-  if (c->tsaved_host) hipHostFree(c->tsaved_host);
-  if (c->prog_host) hipHostFree(c->prog_host);
-  if (c->adj_ctl) hipFree(c->adj_ctl);
-  if (c->adj_ctl_host) hipHostFree(c->adj_ctl_host);
-  if (c->adj_hstat) hipHostFree(c->adj_hstat);
   if (c->adj_stream2) hipStreamDestroy(c->adj_stream2);
-  for (int i = 0; i < 2; ++i) { if (c->adj_evA[i]) hipEventDestroy(c->adj_evA[i]); if (c->adj_evB[i]) hipEventDestroy(c->adj_evB[i]); }
-  if (c->adj_sync) hipFree(c->adj_sync);
-  if (c->adj_ipart) hipFree(c->adj_ipart);
-  if (c->adj_stops) hipFree(c->adj_stops);
-  if (c->adj_ev[0]) hipEventDestroy(c->adj_ev[0]);
-  if (c->adj_ev[1]) hipEventDestroy(c->adj_ev[1]);
-  if (c->cls_ws) hipFree(c->cls_ws);
-  if (c->cls_host) hipHostFree(c->cls_host);
-  if (c->ev_norm) hipEventDestroy(c->ev_norm);
-  if (c->ev0) hipEventDestroy(c->ev0);
-  if (c->ev1) hipEventDestroy(c->ev1);
-  if (c->evp[0]) hipEventDestroy(c->evp[0]);
-  if (c->evp[1]) hipEventDestroy(c->evp[1]);
   delete c;
   return LRNDE_OK;
 }
@@ -2593,29 +2550,17 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
   if (c->solver_alg != 0)   // n.solver = VCAB3() / VCABM3() (experiments/src/construct.jl:154-164)
     return adams_solve(c, u0, B, t0, t1, o, saveat_host, nsave, u_saved, t_saved_host, cap_saved, st, trace_host, cap_trace);
   const size_t n = (size_t)B * c->desc.state_dim;
-  if (nsave > c->saveat_cap) {
-    if (c->saveat_dev) HIPCHK(c, hipFree(c->saveat_dev));
-    HIPCHK(c, hipMalloc(&c->saveat_dev, sizeof(float) * nsave));
-    c->saveat_cap = nsave;
-  }
-  if (cap_saved > c->tsaved_cap || !c->tsaved_host) {
-    if (c->tsaved_host) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipHostFree(c->tsaved_host)); }
-    c->tsaved_host = nullptr; c->tsaved_cap = 0;
-    const int cap = cap_saved > 16 ? cap_saved : 16;
-    HIPCHK(c, hipHostMalloc(&c->tsaved_host, sizeof(float) * cap, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->tsaved_dev, c->tsaved_host, 0));
-    c->tsaved_cap = cap;
+  HIPCHK(c, c->saveat_dev.grow(nsave));
+  if ((size_t)std::max(cap_saved, 0) > c->tsaved_host.size() || !c->tsaved_host) {
+    if (c->tsaved_host) HIPCHK(c, hipStreamSynchronize(c->stream));   // a queued step may still write the old block
+    HIPCHK(c, c->tsaved_host.grow(cap_saved > 16 ? cap_saved : 16, hipHostMallocMapped));
   }
   if (!c->prog_host) {
-    HIPCHK(c, hipHostMalloc(&c->prog_host, PROG_RING * 8 + sizeof(Ctrl), hipHostMallocMapped));
+    static_assert(sizeof(Ctrl) % 8 == 0, "the final control block follows the ring of 8-byte progress words");
+    HIPCHK(c, c->prog_host.once(PROG_RING + sizeof(Ctrl) / 8, hipHostMallocMapped));
     memset(c->prog_host, 0, PROG_RING * 8 + sizeof(Ctrl));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->prog_dev, c->prog_host, 0));
   }
-  if (trace_host && cap_trace > c->trace_cap) {
-    if (c->trace_dev) HIPCHK(c, hipFree(c->trace_dev));
-    HIPCHK(c, hipMalloc(&c->trace_dev, sizeof(lrnde_trace_row) * cap_trace));
-    c->trace_cap = cap_trace;
-  }
+  if (trace_host) HIPCHK(c, c->trace_dev.grow(std::max(cap_trace, 0)));
   StepArgs a{};
   fill_args(c, a, B);
   a.t0 = t0; a.t1 = t1; a.abstol = o->abstol; a.reltol = o->reltol;
@@ -2626,7 +2571,7 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
     const bool no_direct = opt(OPT_DENSE_COPY) != 0;  // diagnostic: round 1's prologue copy
     a.dense_direct = (use_qtile(c, B) && !no_direct) ? 1 : 0;
   }
-  a.cap_saved = cap_saved; a.u_saved = u_saved; a.t_saved = c->tsaved_dev;
+  a.cap_saved = cap_saved; a.u_saved = u_saved; a.t_saved = c->tsaved_host.dev();
   // (round 2 enqueued a D2D copy of that slot once the last report was in: 30 us of host latency plus a blit kernel
   //  between the last launch and the caller's synchronisation)
   a.also_dst = c->tail_copy_dst; a.also_slot = c->tail_copy_dst ? c->tail_copy_slot : -1;
@@ -2638,7 +2583,7 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
   a.saveat = c->saveat_dev;
   SaveInit si;
   memset(&si, 0, sizeof(si));
-  si.saveat = c->saveat_dev; si.tsaved = c->tsaved_dev;
+  si.saveat = c->saveat_dev; si.tsaved = c->tsaved_host.dev();
   if (a.nsave > 8)
     HIPCHK(c, hipMemcpyAsync(c->saveat_dev, saveat_host + skip, sizeof(float) * a.nsave,
                              hipMemcpyHostToDevice, c->stream));
@@ -2654,10 +2599,10 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
   // the prologue reports to pinned host memory (solve_progress) and the loop below steers by those reports, one per
   // launch, read in launch order — the same sequence of decisions on every rank of a sharded run
   volatile unsigned long long* pw = c->prog_host;
-  Ctrl* fin_host = reinterpret_cast<Ctrl*>(reinterpret_cast<char*>(c->prog_host) + PROG_RING * 8);
+  Ctrl* fin_host = reinterpret_cast<Ctrl*>(reinterpret_cast<char*>(c->prog_host.get()) + PROG_RING * 8);
   for (int i = 0; i < PROG_RING; ++i) pw[i] = 0ull;
-  a.prog = c->reports_off ? nullptr : c->prog_dev;
-  a.fin_host = reinterpret_cast<Ctrl*>(reinterpret_cast<char*>(c->prog_dev) + PROG_RING * 8);
+  a.prog = c->reports_off ? nullptr : c->prog_host.dev();
+  a.fin_host = reinterpret_cast<Ctrl*>(reinterpret_cast<char*>(c->prog_host.dev()) + PROG_RING * 8);
   if (c->time_solves) HIPCHK(c, hipEventRecord(c->ev0, c->stream));  // (an event is a marker packet in the queue: only on request)
   if (use_qtile(c, B)) {
     // (4-column family: the first init launch reads the caller's array, copies it to ubuf[0] and writes the control blocks)
@@ -2827,9 +2772,8 @@ static int node_forward_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, 
   }
   c->series_idx.clear(); c->series_t.clear();
   if (c->usave_slots < need || c->usave_slot_elems != n) {
-    if (c->usave) HIPCHK(c, hipFree(c->usave));
-    c->usave = nullptr;
-    HIPCHK(c, hipMalloc(&c->usave, sizeof(float) * n * need));
+    HIPCHK(c, c->usave.reset());
+    HIPCHK(c, c->usave.once(n * need));
     c->usave_slots = need; c->usave_slot_elems = n;
   }
   if (reg_val_host) *reg_val_host = 0.0f;
@@ -3110,7 +3054,7 @@ int lrnde_local_comm_destroy(lrnde_local_comm* lc) {
   for (int r = 0; r < lc->n; ++r) {
     if (!lc->joined[r]) continue;
     hipSetDevice(lc->device[r]);
-    if (lc->tmp[r]) hipFree(lc->tmp[r]);
+    (void)lc->tmp[r].reset();
     if (lc->ready[r]) hipEventDestroy(lc->ready[r]);
     if (lc->done[r]) hipEventDestroy(lc->done[r]);
   }
@@ -3179,27 +3123,28 @@ int lrnde_bench_step(lrnde_ctx* c, const float* uprev, const float* k1, int32_t 
 namespace { struct SdeNodeRecord; }   // the layer's forward record (lrnde_sde_node.hpp)
 struct lrnde_sde {
   SdeNodeRecord* node = nullptr;
-  double *idt_part = nullptr, *idt_part_host = nullptr;   // sde_init_dt's norm partials (device / pinned)
-  double* march_part = nullptr; size_t march_part_n = 0;   // marched fixed-grid solve: [step][workgroup] partial sums
-  double* idt_pp = nullptr; int idt_pp_nwg = 0;           // sde_init_dt_dev's per-workgroup partial sums (two phases)
-  float *idt_scal = nullptr, *idt_scal_host = nullptr;    // sde_init_dt_dev's results: {dt0, d1, dt} of the solve, then of the local step
+  DevBuf<double> idt_part; PinBuf<double> idt_part_host;   // sde_init_dt's norm partials (device / pinned)
+  DevBuf<double> march_part;                               // marched fixed-grid solve: [step][workgroup] partial sums
+  DevBuf<double> idt_pp; int idt_pp_nwg = 0;               // sde_init_dt_dev's per-workgroup partial sums (two phases)
+  DevBuf<float> idt_scal; PinBuf<float> idt_scal_host;     // sde_init_dt_dev's results: {dt0, d1, dt} of the solve, then of the local step
   lrnde_ctx* drift = nullptr;
   lrnde_ctx* diff = nullptr;
-  float* p2 = nullptr;  // expanded diffusion parameters
+  DevBuf<float> p2;  // expanded diffusion parameters
   int diff_bias = 1;
-  Ctrl *traj_host = nullptr, *traj_dev = nullptr; int traj_cap = 0;  // per-step records of lrnde_sde_solve_fixed (pinned / device)
-  float* sri_ws = nullptr; size_t sri_n = 0; double *sri_part = nullptr, *sri_part_host = nullptr;  // lrnde_sde_sri_step scratch
-  float* bwd_ws = nullptr; size_t bwd_n = 0;  // lrnde_sde_*_backward / _reg_grad scratch
+  PinBuf<Ctrl> traj_host; DevBuf<Ctrl> traj_dev;  // per-step records of lrnde_sde_solve_fixed (pinned / device)
+  DevBuf<float> sri_ws; DevBuf<double> sri_part; PinBuf<double> sri_part_host;  // lrnde_sde_sri_step scratch
+  DevBuf<float> bwd_ws;  // lrnde_sde_*_backward / _reg_grad scratch
   // the one-launch reverse sweep (lrnde_sde_bwd_fused.hpp): raw drift parameters as the caller gave them, the workgroups'
   // parameter-cotangent partials, the recorded steps and the series table on the device
-  float* pdr = nullptr; float* bwf_part = nullptr; size_t bwf_part_n = 0; int* bwf_meta = nullptr; int* bwf_meta_pin = nullptr; size_t bwf_meta_n = 0;
-  float* bwf_hist = nullptr; size_t bwf_hist_n = 0;   // the deferred sweep's history records
-  int* arrive = nullptr;                      // arrival counter of the one-launch step's footer (lrnde_sde_fast.hpp)
-  float* ad_ws = nullptr; size_t ad_n = 0;    // lrnde_sde_solve_adaptive: two states + the current increments (dW, and SRI's dZ)
-  SdeCtl* ad_ctl = nullptr; SdeCtl* ad_ctl_host = nullptr;             // device-controlled adaptive loop: control block (device / pinned), heading ...
-  int ad_blob_cap = 0;                                                 // ... room for this many (start, length) pairs 64 bytes in
-  unsigned long long* ad_prog = nullptr; unsigned long long* ad_prog_dev = nullptr;  // its pinned progress word
-  lrnde_trace_row* ad_trace = nullptr; int ad_trace_cap = 0;
+  DevBuf<float> pdr, bwf_part; DevBuf<int> bwf_meta; PinBuf<int> bwf_meta_pin;
+  DevBuf<float> bwf_hist;   // the deferred sweep's history records
+  DevBuf<int> arrive;       // arrival counter of the one-launch step's footer (lrnde_sde_fast.hpp)
+  DevBuf<float> ad_ws;      // lrnde_sde_solve_adaptive: two states + the current increments (dW, and SRI's dZ)
+  DevBuf<char> ad_ctl; PinBuf<char> ad_ctl_host;   // device-controlled adaptive loop: an SdeCtl (device / pinned), heading ...
+  int ad_blob_cap = 0;                             // ... room for this many (start, length) pairs 64 bytes in
+  PinBuf<unsigned long long> ad_prog;              // its pinned, mapped progress word
+  DevBuf<lrnde_trace_row> ad_trace;
+  SdeCtl* ctl() const { return reinterpret_cast<SdeCtl*>(ad_ctl.get()); }
 };
 
 int lrnde_sde_create(lrnde_sde** out, const lrnde_model_desc* drift, int32_t diffusion_bias, int device, void* stream) {
@@ -3213,7 +3158,7 @@ int lrnde_sde_create(lrnde_sde** out, const lrnde_model_desc* drift, int32_t dif
   rc = lrnde_create(&s->diff, &dd, device, stream);
   if (rc) { lrnde_destroy(s->drift); delete s; return rc; }
   const size_t n2 = lrnde_param_count(&dd);
-  if (hipMalloc(&s->p2, sizeof(float) * n2) != hipSuccess) { lrnde_destroy(s->drift); lrnde_destroy(s->diff); delete s; return LRNDE_HIP_ERROR; }
+  if (s->p2.once(n2) != hipSuccess) { lrnde_destroy(s->drift); lrnde_destroy(s->diff); delete s; return LRNDE_HIP_ERROR; }
   *out = s;
   return LRNDE_OK;
 }
@@ -3222,32 +3167,8 @@ namespace { void sde_node_release(lrnde_sde* s); unsigned long long sde_node_gen
 int lrnde_sde_destroy(lrnde_sde* s) {
   if (!s) return LRNDE_OK;
   sde_node_release(s);
-  if (s->idt_part) hipFree(s->idt_part);
-  if (s->idt_part_host) hipHostFree(s->idt_part_host);
-  if (s->idt_pp) hipFree(s->idt_pp);
-  if (s->march_part) hipFree(s->march_part);
-  if (s->idt_scal) hipFree(s->idt_scal);
-  if (s->idt_scal_host) hipHostFree(s->idt_scal_host);
   lrnde_destroy(s->drift);
   lrnde_destroy(s->diff);
-  if (s->p2) hipFree(s->p2);
-  if (s->traj_host) hipHostFree(s->traj_host);
-  if (s->traj_dev) hipFree(s->traj_dev);
-  if (s->sri_ws) hipFree(s->sri_ws);
-  if (s->bwd_ws) hipFree(s->bwd_ws);
-  if (s->pdr) hipFree(s->pdr);
-  if (s->bwf_part) hipFree(s->bwf_part);
-  if (s->bwf_meta) hipFree(s->bwf_meta);
-  if (s->bwf_meta_pin) hipHostFree(s->bwf_meta_pin);
-  if (s->bwf_hist) hipFree(s->bwf_hist);
-  if (s->ad_ctl) hipFree(s->ad_ctl);
-  if (s->ad_ctl_host) hipHostFree(s->ad_ctl_host);
-  if (s->ad_prog) hipHostFree(s->ad_prog);
-  if (s->ad_trace) hipFree(s->ad_trace);
-  if (s->arrive) hipFree(s->arrive);
-  if (s->ad_ws) hipFree(s->ad_ws);
-  if (s->sri_part) hipFree(s->sri_part);
-  if (s->sri_part_host) hipHostFree(s->sri_part_host);
   delete s;
   return LRNDE_OK;
 }
@@ -3261,7 +3182,7 @@ int lrnde_sde_set_params(lrnde_sde* s, const float* p_drift, size_t n_drift, con
     return fail(s->drift, LRNDE_BADARG, "diffusion parameter count %zu != %zu", n_diff, (size_t)D * D + (s->diff_bias ? D : 0));
   int rc = lrnde_set_params(s->drift, p_drift, n_drift);
   if (rc) return rc;
-  if (!s->pdr) HIPCHK(s->drift, hipMalloc(&s->pdr, sizeof(float) * n_drift));
+  HIPCHK(s->drift, s->pdr.once(n_drift));
   HIPCHK(s->drift, hipMemcpyAsync(s->pdr, p_drift, sizeof(float) * n_drift, hipMemcpyDeviceToDevice, s->drift->stream));
   hipLaunchKernelGGL(k_diff_expand, dim3(64), dim3(256), 0, s->diff->stream, p_diff, D, s->diff_bias, s->p2);
   return lrnde_set_params(s->diff, s->p2, lrnde_param_count(&s->diff->desc));
@@ -3314,7 +3235,7 @@ static int sde_step_enqueue(lrnde_sde* s, int which, const float* uprev, const f
     f.n_norm = a.n_global;
     f.dt_dev = dt_dev; f.dW_scaled = dW_scaled;   // (the layer's local step: dt from the device, dW = sqrt(dt) z formed in the launch)
     if (rec_dev) {  // fixed-grid solve / the layer's local step: the step writes its own record (no footer launch)
-      if (!s->arrive) { HIPCHK(c, hipMalloc(&s->arrive, sizeof(int))); HIPCHK(c, hipMemsetAsync(s->arrive, 0, sizeof(int), c->stream)); }
+      if (!s->arrive) { HIPCHK(c, s->arrive.once(1)); HIPCHK(c, hipMemsetAsync(s->arrive, 0, sizeof(int), c->stream)); }
       f.arrive = s->arrive; f.rec = rec_dev;
       sde_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
       HIPCHK(c, hipGetLastError());
@@ -3392,26 +3313,15 @@ int lrnde_sde_solve_fixed(lrnde_sde* s, int32_t which, const float* u0, const fl
   lrnde_ctx* c = s->drift;
   if (nsteps <= 0) return fail(c, LRNDE_BADARG, "nsteps must be positive");
   if (which != 0 && which != 1) return fail(c, LRNDE_BADARG, "which: 0 Euler-Heun, 1 Milstein");
-  if (s->traj_cap < nsteps) {
-    if (s->traj_host) hipHostFree(s->traj_host);
-    if (s->traj_dev) hipFree(s->traj_dev);
-    s->traj_host = nullptr; s->traj_dev = nullptr; s->traj_cap = 0;
-    HIPCHK(c, hipHostMalloc(&s->traj_host, sizeof(Ctrl) * (size_t)nsteps));
-    HIPCHK(c, hipMalloc(&s->traj_dev, sizeof(Ctrl) * (size_t)nsteps));
-    s->traj_cap = nsteps;
-  }
+  HIPCHK(c, s->traj_host.grow(nsteps));
+  HIPCHK(c, s->traj_dev.grow(nsteps));
   const size_t n = (size_t)B * c->desc.state_dim;
   if (which == 0 && sde_uses_fast(s) && !opt(OPT_SDE_NO_MARCH)) {
     // the one-launch step's shape: the whole grid in ONE launch, no step waiting for another workgroup (lrnde_sde_fast.hpp,
     // march_n), then one launch for the nsteps records.  LRNDE_SDE_NO_MARCH=1: a launch per step (same bits)
     const int nwg = (B + NB - 1) / NB;
     const size_t need = (size_t)nsteps * nwg * PSTRIDE;
-    if (s->march_part_n < need) {
-      if (s->march_part) HIPCHK(c, hipFree(s->march_part));
-      s->march_part = nullptr; s->march_part_n = 0;
-      HIPCHK(c, hipMalloc(&s->march_part, sizeof(double) * need));
-      s->march_part_n = need;
-    }
+    HIPCHK(c, s->march_part.grow(need));
     SdeFastArgs f{};
     sde_fast_args(s, f);
     f.u = u0; f.dW = dW; f.un = u_traj; f.B = B; f.dt = dt; f.abstol = abstol; f.reltol = reltol; f.delta = delta;
@@ -3476,17 +3386,14 @@ __global__ void k_sde_pick_end(size_t n, const SdeCtl* ctl, const float* ua, con
 static int sde_adaptive_prepare(lrnde_sde* s, int rec_cap = 0) {
   static_assert(sizeof(SdeCtl) <= 64, "the pairs start 64 bytes in");
   lrnde_ctx* c = s->drift;
-  if (!s->ad_prog) {
-    HIPCHK(c, hipHostMalloc(&s->ad_prog, 64, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void**)&s->ad_prog_dev, s->ad_prog, 0));
-  }
-  if (!s->ad_ctl || s->ad_blob_cap < rec_cap) {
-    if (s->ad_ctl) HIPCHK(c, hipFree(s->ad_ctl));
-    if (s->ad_ctl_host) HIPCHK(c, hipHostFree(s->ad_ctl_host));
-    s->ad_ctl = nullptr; s->ad_ctl_host = nullptr; s->ad_blob_cap = 0;
+  HIPCHK(c, s->ad_prog.once(64 / sizeof(unsigned long long), hipHostMallocMapped));
+  if (!s->ad_ctl || s->ad_blob_cap < rec_cap) {   // device and pinned block are replaced together
+    s->ad_blob_cap = 0;
+    HIPCHK(c, s->ad_ctl.reset());
+    HIPCHK(c, s->ad_ctl_host.reset());
     const size_t bytes = 64 + sizeof(int2) * (size_t)rec_cap;
-    HIPCHK(c, hipMalloc((void**)&s->ad_ctl, bytes));
-    HIPCHK(c, hipHostMalloc((void**)&s->ad_ctl_host, bytes));
+    HIPCHK(c, s->ad_ctl.once(bytes));
+    HIPCHK(c, s->ad_ctl_host.once(bytes));
     s->ad_blob_cap = rec_cap;
   }
   return LRNDE_OK;
@@ -3502,22 +3409,17 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   const bool pairs_home = rec_im_host && rec_im && rec_cap > 0;   // the layer's record: its pairs live behind the control block
   int rc0 = sde_adaptive_prepare(s, pairs_home ? rec_cap : 0);
   if (rc0) return rc0;
-  if (pairs_home) rec_im = reinterpret_cast<int2*>(reinterpret_cast<char*>(s->ad_ctl) + 64);
-  if (trace_host && cap_trace > s->ad_trace_cap) {
-    if (s->ad_trace) HIPCHK(c, hipFree(s->ad_trace));
-    s->ad_trace = nullptr; s->ad_trace_cap = 0;
-    HIPCHK(c, hipMalloc(&s->ad_trace, sizeof(lrnde_trace_row) * cap_trace));
-    s->ad_trace_cap = cap_trace;
-  }
-  if (!s->arrive) { HIPCHK(c, hipMalloc(&s->arrive, sizeof(int))); HIPCHK(c, hipMemsetAsync(s->arrive, 0, sizeof(int), c->stream)); }
+  if (pairs_home) rec_im = reinterpret_cast<int2*>(s->ad_ctl + 64);
+  if (trace_host) HIPCHK(c, s->ad_trace.grow(std::max(cap_trace, 0)));
+  if (!s->arrive) { HIPCHK(c, s->arrive.once(1)); HIPCHK(c, hipMemsetAsync(s->arrive, 0, sizeof(int), c->stream)); }
   const float h = (t1 - t0) / (float)nfine;
   int m0 = (int)(o->dt0 / h); if (m0 < 1) m0 = 1;
   if (m0 > nfine) m0 = nfine;
   if (1 > o->maxiters) { st->iters = 1; st->retcode = LRNDE_MAXITERS; return fail(c, LRNDE_MAXITERS, "adaptive SDE solve stopped with retcode %d at t=%g", LRNDE_MAXITERS, (double)t0); }
   HIPCHK(c, hipMemcpyAsync(ua, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  if (dt0_dev && no_persist) hipLaunchKernelGGL(k_sde_ctl_init_dtdev, dim3(1), dim3(1), 0, c->stream, s->ad_ctl, dt0_dev, h, nfine);  // (the rerun)
+  if (dt0_dev && no_persist) hipLaunchKernelGGL(k_sde_ctl_init_dtdev, dim3(1), dim3(1), 0, c->stream, s->ctl(), dt0_dev, h, nfine);  // (the rerun)
   else if (!dt0_dev)   // (dt0_dev: sde_init_dt_dev's closing launch has initialised the control block from its dt)
-    hipLaunchKernelGGL(k_sde_ctl_init, dim3(1), dim3(1), 0, c->stream, s->ad_ctl, m0, o->dt0);
+    hipLaunchKernelGGL(k_sde_ctl_init, dim3(1), dim3(1), 0, c->stream, s->ctl(), m0, o->dt0);
   volatile unsigned long long* pw = s->ad_prog;
   *pw = 0ull;
   StepArgs a{};
@@ -3529,10 +3431,10 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   f.part = c->part + (size_t)a.nwg_global * PSTRIDE;
   f.n_norm = a.n_global;
   f.arrive = s->arrive;
-  f.ctl = s->ad_ctl; f.Wpath = W; f.ua = ua; f.ub = ub; f.nfine = nfine; f.t0 = t0; f.h = h;
+  f.ctl = s->ctl(); f.Wpath = W; f.ua = ua; f.ub = ub; f.nfine = nfine; f.t0 = t0; f.h = h;
   f.gamma = o->gamma; f.qmin = o->qmin; f.qmax = o->qmax; f.beta1 = o->beta1; f.beta2 = o->beta2; f.maxiters = o->maxiters;
   f.trace = trace_host ? s->ad_trace : nullptr; f.cap_trace = trace_host ? cap_trace : 0;
-  f.prog = s->ad_prog_dev;
+  f.prog = s->ad_prog.dev();
   const int nwg = (B + NB - 1) / NB;
   // The whole solve as ONE cooperative launch (k_sde_eh_fast<DT, HT, true>: state and weights stay in registers, a grid barrier
   // per step) when every workgroup fits on the chip at once; LRNDE_SDE_NO_PERSIST=1, a launch the runtime refuses or more than
@@ -3585,15 +3487,15 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   HIPCHK(c, hipMemcpyAsync(s->ad_ctl_host, s->ad_ctl, 64 + (pairs_home ? sizeof(int2) * (size_t)rec_cap : 0), hipMemcpyDeviceToHost, c->stream));
   if (u_end) {   // (the layer does not ask for it: the end state is its record's last slot)
     int nb = (int)((n + 255) / 256); if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(k_sde_pick_end, dim3(nb), dim3(256), 0, c->stream, n, (const SdeCtl*)s->ad_ctl, (const float*)ua, (const float*)ub, u_end);
+    hipLaunchKernelGGL(k_sde_pick_end, dim3(nb), dim3(256), 0, c->stream, n, (const SdeCtl*)s->ctl(), (const float*)ua, (const float*)ub, u_end);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const SdeCtl fin = *s->ad_ctl_host;
+  const SdeCtl fin = *reinterpret_cast<const SdeCtl*>(s->ad_ctl_host.get());
   if (persisted && plain && (fin.status == LRNDE_HIP_ERROR || fin.status == ST_RUNNING))   // the barrier gave up waiting (busy device): the loop
     return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true, which);
   if (pairs_home && fin.naccept > 0)
-    memcpy(rec_im_host, reinterpret_cast<const char*>(s->ad_ctl_host) + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
+    memcpy(rec_im_host, s->ad_ctl_host + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
   st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iters; st->nf = fin.nf; st->eest_last = fin.eest_last;
   st->t_final = t0 + (float)fin.i * h; st->dt_final = (float)fin.m * h;
   st->retcode = (fin.status == ST_DONE) ? LRNDE_OK : (fin.status == ST_RUNNING ? LRNDE_MAXITERS : fin.status);
@@ -3645,12 +3547,7 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
   if (!o || !st || nfine < 1 || !(t1 > t0)) return fail(c, LRNDE_BADARG, "bad arguments (nfine >= 1, t1 > t0)");
   memset(st, 0, sizeof(*st));
   const size_t n = (size_t)B * c->desc.state_dim;
-  if (s->ad_n != n) {
-    if (s->ad_ws) HIPCHK(c, hipFree(s->ad_ws));
-    s->ad_ws = nullptr; s->ad_n = 0;
-    HIPCHK(c, hipMalloc(&s->ad_ws, sizeof(float) * 4 * n));
-    s->ad_n = n;
-  }
+  HIPCHK(c, s->ad_ws.resize_exact(4 * n));
   float *ua = s->ad_ws, *ub = s->ad_ws + n, *dW = s->ad_ws + 2 * n, *dZ = s->ad_ws + 3 * n;
   {
     // the controller on the device: Euler-Heun (k_sde_eh_fast) and Milstein (k_sde_mil_fast) at the one-launch kernels' shape.
@@ -3792,16 +3689,9 @@ int lrnde_sde_sri_step(lrnde_sde* s, const lrnde_sri_tableau* tab, const float* 
   if (!tab || !dZ) return fail(c, LRNDE_BADARG, "null pointer");
   if (s->diff->stream != c->stream) return fail(c, LRNDE_BADARG, "drift and diffusion contexts must share a stream");
   const size_t n = (size_t)B * c->desc.state_dim;
-  if (s->sri_n != n) {
-    if (s->sri_ws) HIPCHK(c, hipFree(s->sri_ws));
-    s->sri_ws = nullptr; s->sri_n = 0;
-    HIPCHK(c, hipMalloc(&s->sri_ws, sizeof(float) * 13 * n));
-    s->sri_n = n;
-  }
-  if (!s->sri_part) {
-    HIPCHK(c, hipMalloc(&s->sri_part, sizeof(double) * SRI_NB));
-    HIPCHK(c, hipHostMalloc(&s->sri_part_host, sizeof(double) * SRI_NB));
-  }
+  HIPCHK(c, s->sri_ws.resize_exact(13 * n));
+  HIPCHK(c, s->sri_part.once(SRI_NB));
+  HIPCHK(c, s->sri_part_host.once(SRI_NB));
   SriPtrs p;
   p.uprev = uprev; p.dW = dW; p.dZ = dZ;
   float* w = s->sri_ws;
@@ -3834,16 +3724,12 @@ int lrnde_sde_sri_step(lrnde_sde* s, const lrnde_sri_tableau* tab, const float* 
 // ---- backward building blocks ----
 static int ensure_bw(lrnde_ctx* c, int B) {
   if (B == c->bwB) return LRNDE_OK;
-  if (c->bw_y) HIPCHK(c, hipFree(c->bw_y));
-  if (c->bw_h) HIPCHK(c, hipFree(c->bw_h));
-  if (c->bw_dp) HIPCHK(c, hipFree(c->bw_dp));
-  if (c->bw_da) HIPCHK(c, hipFree(c->bw_da));
-  c->bw_y = c->bw_h = c->bw_dp = c->bw_da = nullptr;
+  for (DevBuf<float>* b : {&c->bw_y, &c->bw_h, &c->bw_dp, &c->bw_da}) HIPCHK(c, b->reset());
   // (three sets: two alternate between consecutive evaluations; overlapped stage launches rotate through all three)
-  HIPCHK(c, hipMalloc(&c->bw_y, sizeof(float) * 3 * (size_t)B * c->desc.state_dim));
-  HIPCHK(c, hipMalloc(&c->bw_h, sizeof(float) * 3 * (size_t)B * c->m.Hp));
-  HIPCHK(c, hipMalloc(&c->bw_dp, sizeof(float) * 3 * (size_t)B * c->m.Hp));
-  HIPCHK(c, hipMalloc(&c->bw_da, sizeof(float) * 3 * (size_t)B * c->m.Hp));   // act'(pre) of a stage-6 evaluation, for stage 7
+  HIPCHK(c, c->bw_y.once(3 * (size_t)B * c->desc.state_dim));
+  HIPCHK(c, c->bw_h.once(3 * (size_t)B * c->m.Hp));
+  HIPCHK(c, c->bw_dp.once(3 * (size_t)B * c->m.Hp));
+  HIPCHK(c, c->bw_da.once(3 * (size_t)B * c->m.Hp));   // act'(pre) of a stage-6 evaluation, for stage 7
   c->bwB = B;
   return LRNDE_OK;
 }
@@ -3914,12 +3800,7 @@ static int launch_vjp_chain(lrnde_ctx* c, const float* y, const float* dense, fl
                             const float* lam, int B, float* dy, float* gp) {
   const int nwg = (B + CNB - 1) / CNB;
   const size_t P = param_count(c);
-  if (gp && c->ch_part_n < (size_t)nwg * P) {
-    if (c->ch_part) HIPCHK(c, hipFree(c->ch_part));
-    c->ch_part = nullptr; c->ch_part_n = 0;
-    HIPCHK(c, hipMalloc(&c->ch_part, sizeof(float) * (size_t)nwg * P));
-    c->ch_part_n = (size_t)nwg * P;
-  }
+  if (gp) HIPCHK(c, c->ch_part.grow((size_t)nwg * P));
   VjpChainArgs v{};
   v.B = B; v.t = t; v.y = y; v.dense = dense; v.theta = theta; v.dense_dt = dense_dt; v.lam = lam; v.dy = dy;
   v.gpart = gp ? c->ch_part : nullptr;
@@ -3986,7 +3867,7 @@ static int launch_vjp(lrnde_ctx* c, const float* y, const float* dense, float th
   if (sin) return fail(c, LRNDE_BADARG, "fused stage input needs the 4-column VJP kernel");
   VjpArgs a{};
   memset(&a, 0, sizeof(a));
-  a.m = c->m; a.V1p = reinterpret_cast<const f32x4*>(c->V1p); a.U2p = reinterpret_cast<const f32x4*>(c->U2p);
+  a.m = c->m; a.V1p = reinterpret_cast<const f32x4*>(c->V1p.get()); a.U2p = reinterpret_cast<const f32x4*>(c->U2p.get());
   a.B = B; a.t = t; a.y = y; a.dense = dense; a.theta = theta; a.dense_dt = dense_dt; a.lam = lam; a.dy = dy;
   a.ysc = c->bw_y; a.hsc = c->bw_h; a.dpsc = c->bw_dp;
   const int nwg = (B + NB - 1) / NB;
@@ -4022,16 +3903,10 @@ struct AdjVec {  // device vectors of the augmented adjoint state [lambda (local
 };
 
 int adj_alloc(lrnde_ctx* c, size_t N, AdjVec& v) {
-  if (c->adj_elems < 12 * N) {   // (the 12th vector: third stage-lambda buffer of the overlapped launches)
-    if (c->adj) HIPCHK(c, hipFree(c->adj));
-    c->adj = nullptr;
-    HIPCHK(c, hipMalloc(&c->adj, sizeof(float) * 12 * N));
-    c->adj_elems = 12 * N;
-  }
-  if (!c->adj_part) {  // [256 lambda partials][256 mu partials][64 per-rank lambda sums]
-    HIPCHK(c, hipMalloc(&c->adj_part, sizeof(double) * (512 + 64 + ADJ_MU_TILE_MAX)));  // + the per-tile mu partials (ADJ_MU_TILE_OFF)
-    HIPCHK(c, hipHostMalloc(&c->adj_part_host, sizeof(double) * (512 + 64)));
-  }
+  HIPCHK(c, c->adj.grow(12 * N));   // (the 12th vector: third stage-lambda buffer of the overlapped launches)
+  // [256 lambda partials][256 mu partials][64 per-rank lambda sums] + the per-tile mu partials (ADJ_MU_TILE_OFF)
+  HIPCHK(c, c->adj_part.once(512 + 64 + ADJ_MU_TILE_MAX));
+  HIPCHK(c, c->adj_part_host.once(512 + 64));
   v.N = N; v.n_lam = N; v.P = 0; v.z = c->adj; v.zn = c->adj + N; v.zs = c->adj + 2 * N; v.ut = c->adj + 3 * N;
   for (int j = 0; j < 7; ++j) v.K[j] = c->adj + (4 + j) * N;
   return LRNDE_OK;
@@ -4078,7 +3953,7 @@ int norm_readback(lrnde_ctx* c, size_t n_lam, size_t P, float* out) {
   }
   HIPCHK(c, hipMemcpyAsync(c->adj_part_host, c->adj_part, sizeof(double) * (512 + 64), hipMemcpyDeviceToHost, c->stream));
   // the controller waits for this read-back once per adjoint step: poll an event instead of a blocking stream wait
-  if (!c->ev_norm) HIPCHK(c, hipEventCreateWithFlags(&c->ev_norm, hipEventDisableTiming));
+  HIPCHK(c, c->ev_norm.create(hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->ev_norm, c->stream));
   ++c->adj_waits;
   for (;;) {
@@ -4342,22 +4217,16 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
   memset(st, 0, sizeof(*st));
   if (sharded(c)) return fail(c, LRNDE_UNSUPPORTED, "sharded handles use the host-controlled adjoint loop");
   if ((rc = ensure_bw(c, B))) return rc;
-  if (!c->adj_ctl) {
-    HIPCHK(c, hipMalloc(&c->adj_ctl, sizeof(AdjCtrl) * 2));
-    HIPCHK(c, hipHostMalloc(&c->adj_ctl_host, sizeof(AdjCtrl) * 2));
-    HIPCHK(c, hipMalloc(&c->adj_ipart, sizeof(double) * 3 * 576));
-    HIPCHK(c, hipEventCreateWithFlags(&c->adj_ev[0], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->adj_ev[1], hipEventDisableTiming));
-    HIPCHK(c, hipHostMalloc(&c->adj_hstat, sizeof(int) * 16, hipHostMallocMapped));
+  HIPCHK(c, c->adj_ctl.once(2));
+  HIPCHK(c, c->adj_ctl_host.once(2));
+  HIPCHK(c, c->adj_ipart.once(3 * 576));
+  HIPCHK(c, c->adj_ev[0].create(hipEventDisableTiming));
+  HIPCHK(c, c->adj_ev[1].create(hipEventDisableTiming));
+  if (!c->adj_hstat) {
+    HIPCHK(c, c->adj_hstat.once(16, hipHostMallocMapped));
     memset(c->adj_hstat, 0, sizeof(int) * 16);
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->adj_hstat_dev, c->adj_hstat, 0));
   }
-  if ((int)tstops.size() > c->adj_stops_cap) {
-    if (c->adj_stops) HIPCHK(c, hipFree(c->adj_stops));
-    c->adj_stops = nullptr; c->adj_stops_cap = 0;
-    HIPCHK(c, hipMalloc(&c->adj_stops, sizeof(float) * (tstops.size() + 8)));
-    c->adj_stops_cap = (int)tstops.size() + 8;
-  }
+  if (tstops.size() > c->adj_stops.size()) HIPCHK(c, c->adj_stops.grow(tstops.size() + 8));
   const bool one_begin = c->adj_init_src != nullptr && tstops.size() <= 8;
   if (!tstops.empty() && !one_begin)
     HIPCHK(c, hipMemcpyAsync(c->adj_stops, tstops.data(), sizeof(float) * tstops.size(), hipMemcpyHostToDevice, c->stream));
@@ -4388,10 +4257,10 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     if (!c->adj_stream2) {
       HIPCHK(c, hipStreamCreateWithFlags(&c->adj_stream2, hipStreamNonBlocking));
       for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipEventCreateWithFlags(&c->adj_evA[i], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->adj_evB[i], hipEventDisableTiming));
+        HIPCHK(c, c->adj_evA[i].create(hipEventDisableTiming));
+        HIPCHK(c, c->adj_evB[i].create(hipEventDisableTiming));
       }
-      HIPCHK(c, hipMalloc(&c->adj_sync, sizeof(int) * 32));
+      HIPCHK(c, c->adj_sync.once(32));
     }
     HIPCHK(c, hipMemsetAsync(c->adj_sync, 0, sizeof(int) * 32, c->stream));
     g.sync = c->adj_sync;
@@ -4451,7 +4320,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     // integrator's status in pinned host memory (AdjArgs::hstat), and attempt j+1 is enqueued when attempt j is known
     // to be running (its remaining seven launches, ~130 us, cover the host's enqueue); no copy packet sits between the
     // kernels, and an attempt that would end the segment is followed by the next one's first launch only (maybe_last).
-    g.hstat = c->adj_hstat_dev; g.seq0 = c->adj_seq;
+    g.hstat = c->adj_hstat.dev(); g.seq0 = c->adj_seq;
     volatile int* hs = c->adj_hstat;
     int j = 0;
     bool done = false;
@@ -4614,24 +4483,13 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
   if (!chadj_fits(c, B, &pl)) return fail(c, LRNDE_UNSUPPORTED, "chain adjoint loop: shape outside the gate");
   const size_t P = v.P, N = v.N, n = v.n_lam;
   const int np = pl.nwg + pl.nmu;
-  if (!c->cha_ctl) HIPCHK(c, hipMalloc(&c->cha_ctl, sizeof(ChAdjCtrl) * 2));
+  HIPCHK(c, c->cha_ctl.once(2));
   if (!c->adj_hstat) {
-    HIPCHK(c, hipHostMalloc(&c->adj_hstat, sizeof(int) * 16, hipHostMallocMapped));
+    HIPCHK(c, c->adj_hstat.once(16, hipHostMallocMapped));
     memset(c->adj_hstat, 0, sizeof(int) * 16);
-    HIPCHK(c, hipHostGetDevicePointer((void**)&c->adj_hstat_dev, c->adj_hstat, 0));
   }
-  if (c->cha_gpart_n < 7 * (size_t)pl.nwg * P) {
-    if (c->cha_gpart) HIPCHK(c, hipFree(c->cha_gpart));
-    c->cha_gpart = nullptr; c->cha_gpart_n = 0;
-    HIPCHK(c, hipMalloc(&c->cha_gpart, sizeof(float) * 7 * (size_t)pl.nwg * P));
-    c->cha_gpart_n = 7 * (size_t)pl.nwg * P;
-  }
-  if (c->cha_dpart_n < 5 * (size_t)np) {
-    if (c->cha_dpart) HIPCHK(c, hipFree(c->cha_dpart));
-    c->cha_dpart = nullptr; c->cha_dpart_n = 0;
-    HIPCHK(c, hipMalloc(&c->cha_dpart, sizeof(double) * 5 * (size_t)np));
-    c->cha_dpart_n = 5 * (size_t)np;
-  }
+  HIPCHK(c, c->cha_gpart.grow(7 * (size_t)pl.nwg * P));
+  HIPCHK(c, c->cha_dpart.grow(5 * (size_t)np));
   // impulses strictly inside (s0, s1) go to the device table; those at the end time are added after the solve (a cotangent
   // at the start time is the caller's lambda(s0))
   std::vector<ChAdjImp> tab;
@@ -4641,18 +4499,8 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
     if (im.s < s1) tab.push_back(ChAdjImp{im.s, im.du});
     else at_end.push_back(im.du);
   }
-  if ((int)tstops.size() > c->cha_stops_cap || !c->cha_stops) {
-    if (c->cha_stops) HIPCHK(c, hipFree(c->cha_stops));
-    c->cha_stops = nullptr; c->cha_stops_cap = 0;
-    HIPCHK(c, hipMalloc(&c->cha_stops, sizeof(float) * (tstops.size() + 64)));
-    c->cha_stops_cap = (int)tstops.size() + 64;
-  }
-  if ((int)tab.size() > c->cha_imp_cap || !c->cha_imp) {
-    if (c->cha_imp) HIPCHK(c, hipFree(c->cha_imp));
-    c->cha_imp = nullptr; c->cha_imp_cap = 0;
-    HIPCHK(c, hipMalloc(&c->cha_imp, sizeof(ChAdjImp) * (tab.size() + 64)));
-    c->cha_imp_cap = (int)tab.size() + 64;
-  }
+  if (tstops.size() > c->cha_stops.size() || !c->cha_stops) HIPCHK(c, c->cha_stops.grow(tstops.size() + 64));
+  if (tab.size() > c->cha_imp.size() || !c->cha_imp) HIPCHK(c, c->cha_imp.grow(tab.size() + 64));
   {
     size_t so = 0, io = 0;
     bool first = true;
@@ -4680,7 +4528,7 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
   g.s0 = s0; g.s1 = s1; g.dtmax = s1 - s0; g.dtmin = fmaxf(eps_f(s1), eps_f(s0));
   g.abstol = abstol; g.reltol = reltol; g.maxiters = maxiters; g.exact_pow = exact_pow;
   g.nranks = 1;
-  g.hstat = c->adj_hstat_dev; g.seq0 = c->adj_seq;
+  g.hstat = c->adj_hstat.dev(); g.seq0 = c->adj_seq;
   a.cc = c->cha_ctl; a.imp = c->cha_imp; a.nimp = (int)tab.size();
   a.gpart = c->cha_gpart; a.dpart = c->cha_dpart;
   a.B = B; a.nwg = pl.nwg; a.nmu = pl.nmu; a.np = np; a.wg_lds = pl.wg_lds; a.gfloats = c->ch_gfloats;
@@ -4867,18 +4715,17 @@ static int node_forward_record_impl(lrnde_ctx* c, const float* x, int32_t B, flo
   float t1 = t2;
   if (c->rec_n != n) {  // the regulariser's parameter gradient (written by the forward's overlapped sweep, or by the backward)
     if ((rc = side_quiesce(c))) return rc;
-    if (c->rec_gr) HIPCHK(c, hipFree(c->rec_gr));
-    c->rec_gr = nullptr; c->rec_n = 0;
-    HIPCHK(c, hipMalloc(&c->rec_gr, sizeof(float) * param_count(c)));
+    c->rec_n = 0;
+    HIPCHK(c, c->rec_gr.reset());
+    HIPCHK(c, c->rec_gr.once(param_count(c)));
     c->rec_n = n;
   }
   for (int attempt = 0;; ++attempt) {
     if (c->dense_cap == 0 || c->dense_n != n) {
-      if (c->dense) { hipFree(c->dense); hipFree(c->dense_t); hipFree(c->dense_dt); c->dense = nullptr; }
+      for (DevBuf<float>* b : {&c->dense, &c->dense_t, &c->dense_dt}) (void)b->reset();
       if (c->dense_cap == 0) c->dense_cap = 64;
-      if (hipMalloc(&c->dense, sizeof(float) * (size_t)c->dense_cap * REC_ARRAYS * n) != hipSuccess ||
-          hipMalloc(&c->dense_t, sizeof(float) * c->dense_cap) != hipSuccess ||
-          hipMalloc(&c->dense_dt, sizeof(float) * c->dense_cap) != hipSuccess)
+      if (c->dense.once((size_t)c->dense_cap * REC_ARRAYS * n) != hipSuccess ||
+          c->dense_t.once(c->dense_cap) != hipSuccess || c->dense_dt.once(c->dense_cap) != hipSuccess)
         return fail(c, LRNDE_HIP_ERROR, "dense record allocation failed");
       c->dense_n = n;
     }
@@ -4917,13 +4764,13 @@ int lrnde_node_forward_record_ts(lrnde_ctx* c, const float* x, int32_t B, float 
   if (!c) return LRNDE_BADARG;
   if (nsave < 0 || !u_series || !t_series_host || !nseries_host) return fail(c, LRNDE_BADARG, "null pointer / negative count");
   const size_t n = (size_t)B * c->desc.state_dim;
-  float* u_end = nullptr;
+  DevBuf<float> u_end;   // scratch of this call: released as soon as the forward has returned
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMalloc(&u_end, sizeof(float) * n));
+  HIPCHK(c, u_end.once(n));
   float regv = 0.f; int nfe = 0;
   int rc = node_forward_record_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, saveat_host, nsave, u_end, &regv, &nfe, st,
                                     t1_used_host);
-  hipFree(u_end);
+  (void)u_end.reset();
   if (rc) return rc;
   if (reg_val_host) *reg_val_host = regv;
   if (nfe_host) *nfe_host = nfe;
@@ -5082,11 +4929,11 @@ int lrnde_node_backward(lrnde_ctx* c, const float* x, int32_t B, float t0, float
   if (rc) return rc;
   if (!x || !o || !du_end || !dx || !dp || !st_fwd || !st_bwd) return fail(c, LRNDE_BADARG, "null pointer");
   const size_t n = (size_t)B * c->desc.state_dim;
-  float* u_end = nullptr;
-  HIPCHK(c, hipMalloc(&u_end, sizeof(float) * n));
+  DevBuf<float> u_end;   // scratch of this call: released as soon as the forward has returned
+  HIPCHK(c, u_end.once(n));
   float regv = 0.f; int nfe = 0;
   rc = lrnde_node_forward_record(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, u_end, &regv, &nfe, st_fwd, nullptr);
-  hipFree(u_end);
+  (void)u_end.reset();
   if (rc) return rc;
   return lrnde_node_backward_recorded(c, B, du_end, w_reg, dx, dp, st_bwd);
 }
@@ -5111,15 +4958,10 @@ int cls_enqueue(lrnde_ctx* c, const float* u, int32_t B, const float* pc, int32_
   const int D = c->desc.state_dim;
   // cached workspace: dl (B x K), per-sample losses (B), {double loss sum, int bad-label flag}
   const size_t need = sizeof(float) * ((size_t)B * K + (size_t)B) + 64;
-  if (c->cls_ws_bytes < need) {
-    if (c->cls_ws) HIPCHK(c, hipFree(c->cls_ws));
-    c->cls_ws = nullptr; c->cls_ws_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->cls_ws, need));
-    c->cls_ws_bytes = need;
-  }
-  if (!c->cls_host) HIPCHK(c, hipHostMalloc(&c->cls_host, sizeof(ClsOut)));
-  ClsOut* out = reinterpret_cast<ClsOut*>(c->cls_ws);
-  float* dl = reinterpret_cast<float*>(reinterpret_cast<char*>(c->cls_ws) + 64);
+  HIPCHK(c, c->cls_ws.grow(need));
+  HIPCHK(c, c->cls_host.once(sizeof(ClsOut)));
+  ClsOut* out = reinterpret_cast<ClsOut*>(c->cls_ws.get());
+  float* dl = reinterpret_cast<float*>(c->cls_ws + 64);
   float* lb = dl + (size_t)B * K;
   // the loss is the mean over the GLOBAL batch: on a sharded handle every rank normalises by B * nranks, and the loss
   // and the classifier cotangent (sums over all samples) are all-reduced; du stays sharded like dx
@@ -5152,7 +4994,7 @@ int cls_enqueue(lrnde_ctx* c, const float* u, int32_t B, const float* pc, int32_
 // after the stream has been synchronised
 int cls_finish(lrnde_ctx* c, int32_t B, int32_t K, float* loss_host) {
   const int nr = sharded(c) ? c->nranks : 1;
-  const ClsOut* ho = reinterpret_cast<const ClsOut*>(c->cls_host);
+  const ClsOut* ho = reinterpret_cast<const ClsOut*>(c->cls_host.get());
   if (ho->bad_label) return fail(c, LRNDE_BADARG, "a label is outside [0, %d)", K);
   *loss_host = (float)(ho->loss_sum / ((double)B * (double)nr));
   return LRNDE_OK;

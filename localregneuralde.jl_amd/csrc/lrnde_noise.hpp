@@ -110,13 +110,11 @@ int lrnde_sde_draw_noise(lrnde_sde* s, uint64_t seed, uint32_t stream, int32_t n
 
 int lrnde_hook_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
   if (!ctr || !key || !out) return LRNDE_BADARG;
-  uint32_t* d = nullptr;
-  if (hipMalloc(&d, 4 * sizeof(uint32_t)) != hipSuccess) return LRNDE_HIP_ERROR;
-  hipLaunchKernelGGL(k_philox_hook, dim3(1), dim3(64), 0, 0, ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], d);
-  const int rc = hipGetLastError() == hipSuccess && hipMemcpy(out, d, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess
-                     ? LRNDE_OK : LRNDE_HIP_ERROR;
-  hipFree(d);
-  return rc;
+  DevBuf<uint32_t> d;
+  if (d.once(4) != hipSuccess) return LRNDE_HIP_ERROR;
+  hipLaunchKernelGGL(k_philox_hook, dim3(1), dim3(64), 0, 0, ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], d.get());
+  return hipGetLastError() == hipSuccess && hipMemcpy(out, d, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess
+             ? LRNDE_OK : LRNDE_HIP_ERROR;
 }
 
 }  // extern "C"

@@ -142,12 +142,7 @@ inline int sde_nb(size_t n) { int nb = (int)((n + 255) / 256); return nb > 1024 
 int sde_bwd_ws(lrnde_sde* s, size_t n, size_t Pf, size_t Pg2, float** st, int cnt, float** gpf, float** gpg) {
   lrnde_ctx* c = s->drift;
   const size_t need = (size_t)cnt * n + 2 * Pf + 2 * Pg2;
-  if (s->bwd_n < need) {
-    if (s->bwd_ws) HIPCHK(c, hipFree(s->bwd_ws));
-    s->bwd_ws = nullptr; s->bwd_n = 0;
-    HIPCHK(c, hipMalloc(&s->bwd_ws, sizeof(float) * need));
-    s->bwd_n = need;
-  }
+  HIPCHK(c, s->bwd_ws.grow(need));
   for (int i = 0; i < cnt; ++i) st[i] = s->bwd_ws + (size_t)i * n;
   gpf[0] = s->bwd_ws + (size_t)cnt * n; gpf[1] = gpf[0] + Pf;
   gpg[0] = gpf[1] + Pf; gpg[1] = gpg[0] + Pg2;

@@ -23,16 +23,16 @@ struct SdeNodeRecord {
   float t0 = 0.f, t2 = 0.f, h = 0.f;
   lrnde_sde_adapt_opts o{};
   const float* W = nullptr;        // the caller's path (must stay alive until the backward call)
-  float* x = nullptr;              // copy of the input state
-  float* rec_u = nullptr; int2* rec_im_dev = nullptr; size_t rec_floats = 0; int rec_cap = 0;
+  DevBuf<float> x;                 // copy of the input state
+  DevBuf<float> rec_u; DevBuf<int2> rec_im_dev; int rec_cap = 0;
   std::vector<int2> im;            // (i, m) of every accepted step
   std::vector<SdeSeriesEntry> series;  // the caller's view of the solution (after the _CorrectedDESolution filter)
-  float* u1 = nullptr; float* dWloc = nullptr; float* tmp = nullptr; size_t n_alloc = 0;
+  DevBuf<float> u1, dWloc, tmp; size_t n_alloc = 0;
   float t1 = 0.f, dt_loc = 0.f, ee_loc = 0.f;   // the local step: its time, dt and EEst (u_new stays in tmp)
-  float* gdr = nullptr; float* gdf = nullptr; size_t pf = 0, pg = 0;
+  DevBuf<float> gdr, gdf;
   // the step kind the record was made with (0 Euler-Heun, 1 Milstein, 2 SRI): the backward sweeps it with that kind's
   // reverse kernels.  SRI: its tableau, the second path (the caller's, alive until the backward) and the local step's dZ
-  int which = 0; lrnde_sri_tableau tab{}; const float* Z = nullptr; float* dZloc = nullptr;
+  int which = 0; lrnde_sri_tableau tab{}; const float* Z = nullptr; DevBuf<float> dZloc;
 };
 
 // out = (1 - theta) * a + theta * b   (StochasticDiffEq's linear sde_interpolant)
@@ -87,10 +87,8 @@ int sde_init_dt(lrnde_sde* s, const float* u, int B, float t, float tend, float 
   const size_t n = (size_t)B * c->desc.state_dim;
   float *f0 = ws, *g0 = ws + n, *u1 = ws + 2 * n, *f1 = ws + 3 * n, *g1 = ws + 4 * n;
   int rc;
-  if (!s->idt_part) {
-    HIPCHK(c, hipMalloc(&s->idt_part, sizeof(double) * 128));
-    HIPCHK(c, hipHostMalloc(&s->idt_part_host, sizeof(double) * 128));
-  }
+  HIPCHK(c, s->idt_part.once(128));
+  HIPCHK(c, s->idt_part_host.once(128));
   const float dtmax = tend - t;
   if ((rc = lrnde_rhs(c, u, t, B, f0))) return rc;
   if ((rc = lrnde_rhs(cg, u, t, B, g0))) return rc;
@@ -151,12 +149,7 @@ int sde_init_dt_dev(lrnde_sde* s, const float* u, int B, float t, float tend, fl
                     SdeCtl* ctl, float h, int nfine, Ctrl* ctrl) {
   lrnde_ctx* c = s->drift;
   const int nwg = (B + NB - 1) / NB;
-  if (s->idt_pp_nwg < nwg) {
-    if (s->idt_pp) HIPCHK(c, hipFree(s->idt_pp));
-    s->idt_pp = nullptr; s->idt_pp_nwg = 0;
-    HIPCHK(c, hipMalloc(&s->idt_pp, sizeof(double) * 2 * (size_t)nwg * PSTRIDE));
-    s->idt_pp_nwg = nwg;
-  }
+  HIPCHK(c, s->idt_pp.grow(2 * (size_t)nwg * PSTRIDE));
   SdeFastArgs f{};
   sde_fast_args(s, f);
   f.u = u; f.B = B; f.abstol = abstol; f.reltol = reltol;
@@ -177,41 +170,30 @@ int sde_node_alloc(lrnde_sde* s, SdeNodeRecord& r, int B, int nfine) {
   lrnde_ctx* c = s->drift;
   const size_t n = (size_t)B * c->desc.state_dim;
   if (r.n_alloc != n) {
-    for (float** p : {&r.x, &r.u1, &r.dWloc, &r.tmp, &r.dZloc}) { if (*p) hipFree(*p); *p = nullptr; }
+    for (DevBuf<float>* b : {&r.x, &r.u1, &r.dWloc, &r.tmp, &r.dZloc}) (void)b->reset();
     r.n_alloc = 0;
-    HIPCHK(c, hipMalloc(&r.dZloc, sizeof(float) * n));
-    HIPCHK(c, hipMalloc(&r.x, sizeof(float) * n));
-    HIPCHK(c, hipMalloc(&r.u1, sizeof(float) * n));
-    HIPCHK(c, hipMalloc(&r.dWloc, sizeof(float) * n));
-    HIPCHK(c, hipMalloc(&r.tmp, sizeof(float) * 6 * n));
+    HIPCHK(c, r.dZloc.once(n));
+    HIPCHK(c, r.x.once(n));
+    HIPCHK(c, r.u1.once(n));
+    HIPCHK(c, r.dWloc.once(n));
+    HIPCHK(c, r.tmp.once(6 * n));
     r.n_alloc = n;
   }
-  if (r.rec_floats < (size_t)nfine * n || r.rec_cap < nfine) {
-    if (r.rec_u) hipFree(r.rec_u);
-    if (r.rec_im_dev) hipFree(r.rec_im_dev);
-    r.rec_u = nullptr; r.rec_im_dev = nullptr; r.rec_floats = 0; r.rec_cap = 0;
-    HIPCHK(c, hipMalloc(&r.rec_u, sizeof(float) * (size_t)nfine * n));
-    HIPCHK(c, hipMalloc(&r.rec_im_dev, sizeof(int2) * (size_t)nfine));
-    r.rec_floats = (size_t)nfine * n; r.rec_cap = nfine;
+  if (r.rec_u.size() < (size_t)nfine * n || r.rec_cap < nfine) {   // the states and their (i, m) pairs are replaced together
+    r.rec_cap = 0;
+    (void)r.rec_u.reset(); (void)r.rec_im_dev.reset();
+    HIPCHK(c, r.rec_u.once((size_t)nfine * n));
+    HIPCHK(c, r.rec_im_dev.once(nfine));
+    r.rec_cap = nfine;
   }
   const size_t Pf = lrnde_param_count(&c->desc), Pg = (size_t)c->desc.state_dim * c->desc.state_dim + (s->diff_bias ? c->desc.state_dim : 0);
-  if (r.pf != Pf || r.pg != Pg) {
-    if (r.gdr) hipFree(r.gdr);
-    if (r.gdf) hipFree(r.gdf);
-    r.gdr = r.gdf = nullptr;
-    HIPCHK(c, hipMalloc(&r.gdr, sizeof(float) * Pf));
-    HIPCHK(c, hipMalloc(&r.gdf, sizeof(float) * Pg));
-    r.pf = Pf; r.pg = Pg;
-  }
+  HIPCHK(c, r.gdr.resize_exact(Pf));
+  HIPCHK(c, r.gdf.resize_exact(Pg));
   return LRNDE_OK;
 }
 
 unsigned long long sde_node_generation(const lrnde_sde* s) { return (s->node && s->node->valid) ? s->node->gen : 0ull; }
 void sde_node_release(lrnde_sde* s) {
-  if (!s->node) return;
-  SdeNodeRecord& r = *s->node;
-  for (float** p : {&r.x, &r.u1, &r.dWloc, &r.tmp, &r.dZloc, &r.rec_u, &r.gdr, &r.gdf}) { if (*p) hipFree(*p); *p = nullptr; }
-  if (r.rec_im_dev) hipFree(r.rec_im_dev);
   delete s->node;
   s->node = nullptr;
 }
@@ -267,16 +249,16 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   //  the end of the solve and the end of this function — instead of nine; LRNDE_SDE_HOST_INITDT=1: the host form.  Milstein and
   //  SRI take the host form: their local step runs the generic step kernels, which take dt from the host)
   const bool devdt = which == 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT);
-  if (devdt && !s->idt_scal) {
-    HIPCHK(c, hipMalloc(&s->idt_scal, sizeof(float) * 8));
-    HIPCHK(c, hipHostMalloc(&s->idt_scal_host, sizeof(float) * 8));
+  if (devdt) {
+    HIPCHK(c, s->idt_scal.once(8));
+    HIPCHK(c, s->idt_scal_host.once(8));
   }
   lrnde_sde_adapt_opts oo = *o;
   const float* dt0_dev = nullptr;
   if (!(oo.dt0 > 0.f)) {
     if (devdt) {
       if ((rc = sde_adaptive_prepare(s, r.rec_cap))) return rc;   // (before the initial dt initialises the control block)
-      if ((rc = sde_init_dt_dev(s, r.x, B, t0, t2, oo.abstol, oo.reltol, 0.5f, s->idt_scal, s->ad_ctl, h, nfine, nullptr))) return rc;
+      if ((rc = sde_init_dt_dev(s, r.x, B, t0, t2, oo.abstol, oo.reltol, 0.5f, s->idt_scal, s->ctl(), h, nfine, nullptr))) return rc;
       dt0_dev = s->idt_scal + 2;
       oo.dt0 = t2 - t0;   // (placeholder for the argument checks; the control block is initialised from the device value)
     } else if ((rc = sde_init_dt(s, r.x, B, t0, t2, oo.abstol, oo.reltol, order, r.tmp, &oo.dt0))) return rc;
@@ -438,22 +420,10 @@ int sde_sweep_fused_core(lrnde_sde* s, const SdeSweepSrc& r, int B, const float*
   const int Pf = (int)lrnde_param_count(&c->desc), Pg = D * D + (s->diff_bias ? D : 0), Ptot = Pf + D * D + D;
   const int nwg = (B + SBF_NS - 1) / SBF_NS;
   const size_t need = (size_t)nwg * Ptot;
-  if (s->bwf_part_n < need) {
-    if (s->bwf_part) HIPCHK(c, hipFree(s->bwf_part));
-    s->bwf_part = nullptr; s->bwf_part_n = 0;
-    HIPCHK(c, hipMalloc(&s->bwf_part, sizeof(float) * need));
-    s->bwf_part_n = need;
-  }
+  HIPCHK(c, s->bwf_part.grow(need));
   const size_t meta = (size_t)2 * SBF_MAXSER + 2 * (size_t)(r.K > 0 ? r.K : 1);
-  if (s->bwf_meta_n < meta) {
-    if (s->bwf_meta) HIPCHK(c, hipFree(s->bwf_meta));
-    s->bwf_meta = nullptr; s->bwf_meta_n = 0;
-    HIPCHK(c, hipMalloc(&s->bwf_meta, sizeof(int) * meta));
-    if (s->bwf_meta_pin) HIPCHK(c, hipHostFree(s->bwf_meta_pin));
-    s->bwf_meta_pin = nullptr;
-    HIPCHK(c, hipHostMalloc(&s->bwf_meta_pin, sizeof(int) * meta));
-    s->bwf_meta_n = meta;
-  }
+  HIPCHK(c, s->bwf_meta.grow(meta));
+  HIPCHK(c, s->bwf_meta_pin.grow(meta));
   // [series k (MAXSER ints)][series theta (MAXSER floats)][(i, m) of the K steps], staged in pinned memory: the copy needs no
   // wait (every call that uses the buffer ends in a synchronisation of this stream before the next one fills it)
   int* hm = s->bwf_meta_pin;
@@ -473,21 +443,11 @@ int sde_sweep_fused_core(lrnde_sde* s, const SdeSweepSrc& r, int B, const float*
   bool defer = D <= 32 && H <= 64 && !opt(OPT_SDE_BWD_LDSACC) && !opt(OPT_SDE_BWD_NO_DEFER) && r.K > 0;
   const size_t nrec_sweep = (size_t)r.K * B * 2, nrec = nrec_sweep + (reg ? (size_t)4 * B : 0), nh = nrec * SbfR<32, 64>::HREC;
   if (defer && (nh * sizeof(float) > ((size_t)4 << 30) || nrec > (size_t)0x7fffffff)) defer = false;
-  if (defer && s->bwf_hist_n < nh) {
-    if (s->bwf_hist) HIPCHK(c, hipFree(s->bwf_hist));
-    s->bwf_hist = nullptr; s->bwf_hist_n = 0;
-    if (hipMalloc(&s->bwf_hist, sizeof(float) * nh) == hipSuccess) s->bwf_hist_n = nh;
-    else { (void)hipGetLastError(); s->bwf_hist = nullptr; defer = false; }
-  }
+  if (defer && !s->bwf_hist.try_grow(nh)) defer = false;
   if (defer) {
     const int ngw = 512;   // (two resident workgroups per CU take turns waiting for their batches)
-    if (s->bwf_part_n < (size_t)ngw * Ptot) {
-      HIPCHK(c, hipFree(s->bwf_part));
-      s->bwf_part = nullptr; s->bwf_part_n = 0;
-      HIPCHK(c, hipMalloc(&s->bwf_part, sizeof(float) * (size_t)ngw * Ptot));
-      s->bwf_part_n = (size_t)ngw * Ptot;
-      a.part = s->bwf_part;
-    }
+    HIPCHK(c, s->bwf_part.grow((size_t)ngw * Ptot));
+    a.part = s->bwf_part;
     a.hist = s->bwf_hist; a.nrec = (int)nrec;
     const size_t smr = SbfR<32, 64>::smem_bytes(2, 1, 1);   // (no cotangent vector in this kernel)
     if (opt(OPT_SDE_BWD_NO_RESIDENT)) hipLaunchKernelGGL((k_sde_eh_bwd_fused_r<32, 64, true>), dim3(nwg), dim3(SBF_NT), smr, c->stream, a);

@@ -136,3 +136,126 @@ def test_conv_and_sde_handles_release_their_memory(gpu_pkg):
     gc.collect()
     after = _free_bytes()
     assert before - after < (4 << 20), f"device memory fell by {(before - after) / 2**20:.1f} MiB over 25 conv + SDE rounds"
+
+
+# ---- handle kinds and paths the rounds above do not reach ---------------------------------------------------------
+def _rounds(one_round, warm, n, what):
+    for i in range(warm):
+        one_round(i)
+    gc.collect()
+    before = _free_bytes()
+    for i in range(n):
+        one_round(10 + i)
+    gc.collect()
+    after = _free_bytes()
+    print(f"{what}: free memory changed by {(after - before) / 2**20:+.2f} MiB over {n} rounds")
+    assert before - after < (4 << 20), f"device memory fell by {(before - after) / 2**20:.1f} MiB over {n} rounds of {what}"
+
+
+def test_chain_handle_and_its_device_adjoint_release_their_memory(gpu_pkg):
+    """create, recorded forward with a two-point saveat, pullback through the device-controlled adjoint, close"""
+    import torch
+    P = gpu_pkg
+    B = 12
+    model = P.Chain(P.Activation("tanh"), P.Dense(20, 40, "tanh"), P.Dense(40, 20, "tanh"), P.Dense(20, 40, "tanh"), P.Dense(40, 20, "tanh"))
+    ps = torch.from_numpy(P.glorot_chain_params(model, seed=0)).cuda()
+    x = (torch.rand((B, 20), device="cuda") - 0.5) * 2
+    cots = torch.ones((2, B, 20), device="cuda")
+
+    def one_round(i):
+        node = P.NeuralODE(model, regularize="unbiased", abstol=1e-6, reltol=1e-6, maxiters=10000, field="dense_chain",
+                           saveat=[0.5, 1.0], save_start=False)
+        st = node.initialstates(np.random.default_rng(i))
+        dx, dp, info = node.pullback(x, ps, st, cots, w_reg=1.0)
+        assert torch.isfinite(dx).all() and torch.isfinite(dp).all()
+        assert node.handle(x).last_adjoint_info()["kind"] == 2, "the chain handle's device-controlled loop"
+        node._handle.close()
+
+    _rounds(one_round, 3, 20, "chain handle + device adjoint")
+
+
+@pytest.mark.parametrize("solver", ["RKMil", "SRI"])
+def test_milstein_and_sri_records_release_their_memory(oracle, gpu_pkg, solver):
+    import torch
+    import sde_adaptive_np as S
+    from localregneuralde_jl_amd import _lib as L
+    P = gpu_pkg
+    D, H, B = 32, 64, 64
+    pd, pg = S.sde_params(D, H, 3)
+    ps = dict(drift=torch.from_numpy(pd).cuda(), diffusion=torch.from_numpy(pg).cuda())
+    x = torch.from_numpy(np.random.default_rng(1).standard_normal((B, D)).astype(np.float32)).cuda()
+    T = S.sri_tableau(oracle, 41, 0.1)
+    kw = dict(tableau=[T[k] for k in L.SRI_FIELDS]) if solver == "SRI" else {}
+
+    def one_round(i):
+        node = P.NeuralDSDE(P.Chain(P.Dense(D, H, "tanh"), P.Dense(H, D)), P.Dense(D, D), noise_source="device", adaptive=True,
+                            solver=solver, regularize="unbiased", abstol=0.8, reltol=0.8, nfine=32, **kw)
+        st = node.initialstates(np.random.default_rng(i))
+        dx, dps, info = node.pullback(x, ps, st, torch.ones_like(x), w_reg=1.0)
+        assert torch.isfinite(dx).all() and torch.isfinite(dps["drift"]).all()
+        node._handle.close()
+
+    _rounds(one_round, 3, 15, f"NeuralDSDE {solver} record")
+
+
+def test_one_handle_with_a_changing_batch(gpu_pkg):
+    """B = 64, 16, 128, 64, ... on one handle: the workspaces sized by B are replaced, the grow-only ones stop growing, and
+    every loss has the bits a fresh handle gives at that B (regrowth leaves no stale state)"""
+    import torch
+    P = gpu_pkg
+    D, H = 784, 100
+    model = P.TDChain(P.Chain(P.Dense(D + 1, H, "tanh"), P.Dense(H + 1, D)))
+    ps = torch.from_numpy(P.glorot_params(model, seed=0)).cuda()
+    pc = torch.zeros(10 * (D + 1), device="cuda")
+    xs = {B: torch.rand((B, D), device="cuda") for B in (64, 16, 128)}
+    labs = {B: torch.randint(0, 10, (B,), device="cuda", dtype=torch.int32) for B in xs}
+
+    def mk():
+        return P.NeuralODE(model, regularize="unbiased", regularize_type="error_estimate", abstol=1e-4, reltol=1e-4,
+                           save_start=False, maxiters=10000)
+
+    def step(node, B):
+        st = node.initialstates(np.random.default_rng(5))
+        loss, *_ = P.run_training_step(node, ps, pc, st, xs[B], labs[B], 2.5)
+        return float(loss)
+
+    fresh = {}
+    for B in xs:
+        node = mk()
+        fresh[B] = step(node, B)
+        node._handle.close()
+    node = mk()
+    order = [64, 16, 128] * 10
+    before = None
+    for i, B in enumerate(order):
+        if i == 3:
+            before = _free_bytes()     # after the first full cycle
+        got = step(node, B)
+        assert np.float32(got).view(np.int32) == np.float32(fresh[B]).view(np.int32) and np.isfinite(got), (i, B, got, fresh[B])
+    after = _free_bytes()
+    print(f"changing batch: free memory changed by {(after - before) / 2**20:+.2f} MiB over {len(order) - 3} steps")
+    assert before - after < (48 << 20), f"device memory fell by {(before - after) / 2**20:.1f} MiB with a changing batch"
+    node._handle.close()
+
+
+def test_companion_context_borrows_the_weights(gpu_pkg):
+    """an :unbiased layer forward makes the companion context, which borrows the packed weights; set_params repacks them
+    under it; close frees each of them once"""
+    import torch
+    from localregneuralde_jl_amd.layers import Handle, _mlp_desc
+    P = gpu_pkg
+    D, H, B = 784, 100, 64
+    model = P.TDChain(P.Chain(P.Dense(D + 1, H, "tanh"), P.Dense(H + 1, D)))
+    p = torch.from_numpy(P.glorot_params(model, seed=0))
+    x = torch.rand((B, D), device="cuda")
+
+    def one_round(i):
+        h = Handle(_mlp_desc(model))
+        h.set_params(p)
+        a = h.node_forward(x, 0.0, 1.0, 1e-4, 1e-4, mode="unbiased", reg_type="error_estimate", t1_or_rand=0.37, maxiters=1000)
+        h.set_params(p)
+        b = h.node_forward(x, 0.0, 1.0, 1e-4, 1e-4, mode="unbiased", reg_type="error_estimate", t1_or_rand=0.37, maxiters=1000)
+        assert torch.equal(a["u_end"], b["u_end"]) and a["reg_val"] == b["reg_val"] != 0
+        h.close()
+
+    _rounds(one_round, 3, 20, "companion context")
