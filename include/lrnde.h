@@ -552,6 +552,63 @@ enum { LRNDE_OPT_DESCENT = 0, LRNDE_OPT_MOMENTUM = 1, LRNDE_OPT_NESTEROV = 2, LR
 int lrnde_opt_update(int32_t kind, float* x, const float* grad, float* state1, float* state2, size_t n, float eta,
                      float rho_or_beta1, float beta2, float eps, int32_t step, float weight_decay, int device, void* stream);
 
+/* ---- Latent ODE (the PhysioNet experiment): the layers `_construct_time_series` puts around the NeuralODE,
+ * experiments/src/construct.jl:230-252.  The `neural_ode` block itself is a Dense-chain handle (lrnde_create_chain).
+ *   gru          Recurrence(LatentGRUCell(in_dims, hidden_dims, latent_dims)), src/layers/latent_ode.jl:1-48;
+ *   rec_to_gen   Chain(Dense(2L => L, tanh), Dense(L => 2N)), construct.jl:232-233;
+ *   reparam      ReparameterizeLayer, src/layers/common.jl:47-77;
+ *   gen_to_data  Dense(N => in_dims), construct.jl:250;
+ *   loss         construct.jl:36-76 with log_likelihood_loss and kl_divergence, experiments/src/utils.jl:94-101.
+ * I = in_dims, F = 2I + 1 (rows of x = vcat(data, mask, dt), construct.jl:40), H = hidden_dims, L = latent_dims,
+ * N = node_dims.  Parameters: the flat Lux ComponentArray in the order gru.update_gate (layer_1 W (H x (2L+F)), b;
+ * layer_2 W (L x H), b), gru.reset_gate (the same), gru.new_state (layer_2: 2L x H), rec_to_gen (L x 2L, b; 2N x L, b),
+ * gen_to_data (I x N, b); every W column-major out x in, the input rows of a gate's first layer in the order of
+ * vcat(y_mean, y_std, x) (latent_ode.jl:26).  latent_ode.jl:37 builds new_y_mean from new_state_std: rows 0..L-1 of
+ * new_state's second layer are parameters without effect, and their cotangent is exactly zero.
+ * Arrays: x (B, T, F), data / mask (B, T, I) contiguous (Julia's (F, T, B) / (I, T, B)); y (B, 2L); mu, logvar, z0,
+ * eps (B, N); series (T, B, N) as lrnde_node_forward_record_ts returns it (diffeqsol_to_timeseries, src/utils.jl:42-46).
+ * Limits (LRNDE_UNSUPPORTED with a message from lrnde_latent_last_error(NULL) / (h)): 3 * hidden_dims <= 128, and the
+ * gates' weight image plus the backward's activations within the 160 KiB of LDS of a CU; 37/40/50/20 needs 143 KiB. */
+typedef struct {
+  int32_t in_dims, hidden_dims, latent_dims, node_dims;   /* cfg.ts_in_dims, ts_hidden_dims, ts_latent_dims, ts_node_dims */
+} lrnde_latent_desc;
+typedef struct lrnde_latent lrnde_latent;
+/* construct.jl:230-252 (the layers' construction) / Lux.setup's parameter count for them / the ComponentArray itself */
+int lrnde_latent_create(lrnde_latent** out, const lrnde_latent_desc* desc, int device, void* stream);
+int lrnde_latent_destroy(lrnde_latent* h);
+const char* lrnde_latent_last_error(const lrnde_latent* h);
+size_t lrnde_latent_param_count(const lrnde_latent_desc* desc);
+int lrnde_latent_set_params(lrnde_latent* h, const float* p, size_t n);
+/* gru, rec_to_gen and reparam of the Chain, construct.jl:251, in ONE launch: Recurrence with return_sequence = false
+ * walks the T steps (latent_ode.jl:19-47, the first call with y_mean = 0, y_std = 1) and returns the last y (B, 2L);
+ * training != 0: z0 = mu + exp(logvar / 2) .* eps (common.jl:61-71) with the caller's normal draws eps; training = 0:
+ * z0 = mu and logvar := mu as written in common.jl:73-77 (eps may be NULL).  y / mu / logvar / z0 may be NULL.  The call
+ * is stream-ordered and keeps the record of ONE lrnde_latent_encode_backward. */
+int lrnde_latent_encode(lrnde_latent* h, const float* x, int32_t B, int32_t T, int32_t training, const float* eps, float* y,
+                        float* mu, float* logvar, float* z0);
+/* The pullback of the above (what Zygote.pullback gives, experiments/src/utils.jl:104-115) for cotangents of z0 and of
+ * st.reparam's mu / logvar (the KL term sends those, construct.jl:48), and optionally of y itself (dy (B, 2L): Recurrence
+ * used outside the model); any of the four may be NULL (zero).  x: the array
+ * the recorded encode read.  dx (B, T, F) may be NULL; dp: the first lrnde_latent_param_count - (I*N + I) entries of the
+ * flat vector (gru, rec_to_gen).  Two launches: the reverse walk and the workgroup-order sum of its partials. */
+int lrnde_latent_encode_backward(lrnde_latent* h, const float* x, int32_t B, int32_t T, const float* dy, const float* dz0,
+                                 const float* dmu, const float* dlogvar, float* dx, float* dp);
+/* gen_to_data, the last layer of the Chain (construct.jl:250-251): pred (B, T, I) = Dense(N => I) on every state of
+ * series (T, B, N).  Stream-ordered. */
+int lrnde_latent_decode(lrnde_latent* h, const float* series, int32_t T, int32_t B, float* pred);
+/* gen_to_data on every saved state and the loss without the regulariser, construct.jl:43-50: ll (B) =
+ * log_likelihood_loss(pred .* mask .- data .* mask, mask) (utils.jl:94-98, sigma = 0.01, summed over every (feature, time)
+ * entry and divided by the column's mask sum), kl (B) = kl_divergence(mu, logvar) (utils.jl:101),
+ * loss_host[0] = -mean(ll .- w_kl .* kl), loss_host[1] = -mean(ll), loss_host[2] = mean(kl) (the stats of
+ * construct.jl:71-73).  Where non-NULL: the cotangents of the loss for series (T, B, N), mu, logvar (B, N) and
+ * gen_to_data's parameters dpg (I*N + I).  Synchronises the stream. */
+int lrnde_latent_decode_loss(lrnde_latent* h, const float* series, int32_t T, int32_t B, const float* data, const float* mask,
+                             const float* mu, const float* logvar, float w_kl, float* loss_host, float* ll, float* kl,
+                             float* dseries, float* dmu, float* dlogvar, float* dpg);
+/* lrnde_record_generation for this handle: counts the encodes; 0 = no usable record (none yet, consumed by a backward, or
+ * the parameters were set again). */
+int lrnde_latent_record_generation(lrnde_latent* h, uint64_t* gen_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,10 @@ int lrnde_conv_bench_rhs(lrnde_conv* c, const float* u, float t, int32_t B, int3
  * synchronous), so the published known-answer vectors can be checked on the GPU. */
 int lrnde_hook_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 
+/* Diagnostic: kernels the last lrnde_latent_encode / lrnde_latent_encode_backward enqueued (1; 2 = the reverse walk and
+ * the sum of its per-workgroup partials). */
+int lrnde_latent_last_launches(lrnde_latent* h, int32_t* encode_host, int32_t* backward_host);
+
 #ifdef __cplusplus
 }
 #endif

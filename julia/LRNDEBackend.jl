@@ -308,4 +308,75 @@ function sde_node_forward_record_alg(h, x, W, nfine, t0, t2, opts, mode, t1_or_r
     return nothing
 end
 
+# ---- Latent ODE around the Dense-chain NeuralODE (experiments/src/construct.jl:230-252; DESIGN.md 4.9.2) ----
+# gru = Recurrence(LatentGRUCell) (src/layers/latent_ode.jl), rec_to_gen, reparam (src/layers/common.jl:47-77), gen_to_data and
+# the loss (construct.jl:36-76).  ps: the flat ComponentArray (gru.update_gate, gru.reset_gate, gru.new_state, rec_to_gen,
+# gen_to_data) on the device; x (F, T, B), data / mask (I, T, B), series (N, B, T) as diffeqsol_to_timeseries stacks it.
+struct LatentDesc
+    in_dims::Int32
+    hidden_dims::Int32
+    latent_dims::Int32
+    node_dims::Int32
+end
+latent_check(h, rc) = check(h, rc; last_error=:lrnde_latent_last_error)
+latent_param_count(d::LatentDesc) = Int(ccall((:lrnde_latent_param_count, lib), Csize_t, (Ref{LatentDesc},), d))
+function latent_create(d::LatentDesc; device=0, stream=C_NULL)
+    h = Ref{Ptr{Cvoid}}()
+    rc = ccall((:lrnde_latent_create, lib), Cint, (Ptr{Ptr{Cvoid}}, Ref{LatentDesc}, Cint, Ptr{Cvoid}), h, d, device, stream)
+    rc == 0 || error("lrnde_latent_create: status $rc: " * unsafe_string(ccall((:lrnde_latent_last_error, lib), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return h[]
+end
+latent_destroy(h) = ccall((:lrnde_latent_destroy, lib), Cint, (Ptr{Cvoid},), h)
+latent_set_params!(h, ps) = latent_check(h, ccall((:lrnde_latent_set_params, lib), Cint,
+    (Ptr{Cvoid}, Ptr{Float32}, Csize_t), h, pointer(ps), length(ps)))
+# (y, μ₀, logσ², z0) of Chain(gru, rec_to_gen, reparam); ε: the caller's randn_like draw (common.jl:68), training::Bool = st.training
+function latent_encode(h, d::LatentDesc, x, ε, training::Bool)
+    T, B = size(x, 2), size(x, 3)
+    y = similar(x, Float32, 2 * d.latent_dims, B)
+    μ = similar(x, Float32, d.node_dims, B); logσ² = similar(μ); z0 = similar(μ)
+    latent_check(h, ccall((:lrnde_latent_encode, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(x), Int32(B), Int32(T), Int32(training), training ? pointer(ε) : C_NULL, pointer(y), pointer(μ), pointer(logσ²), pointer(z0)))
+    return y, μ, logσ², z0
+end
+# the pullback of latent_encode for cotangents of z0, μ₀, logσ² (`nothing` = zero); dp covers gru and rec_to_gen
+function latent_encode_backward(h, d::LatentDesc, x, dz0, dμ, dlogσ²; want_dx=false)
+    T, B = size(x, 2), size(x, 3)
+    np = latent_param_count(d) - (d.in_dims * d.node_dims + d.in_dims)
+    dp = similar(x, Float32, np)
+    dx = want_dx ? similar(x) : nothing
+    p(a) = a === nothing ? Ptr{Float32}(C_NULL) : pointer(a)
+    latent_check(h, ccall((:lrnde_latent_encode_backward, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(x), Int32(B), Int32(T), Ptr{Float32}(C_NULL), p(dz0), p(dμ), p(dlogσ²), p(dx), pointer(dp)))
+    return dx, dp
+end
+# gen_to_data on the stacked solution
+function latent_decode(h, d::LatentDesc, series)
+    B, T = size(series, 2), size(series, 3)
+    pred = similar(series, Float32, d.in_dims, T, B)
+    latent_check(h, ccall((:lrnde_latent_decode, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Ptr{Float32}),
+        h, pointer(series), Int32(T), Int32(B), pointer(pred)))
+    return pred
+end
+# loss = -mean(ll .- w_kl .* kl) (construct.jl:50) with its stats and the cotangents of series, μ₀, logσ² and gen_to_data
+function latent_decode_loss(h, d::LatentDesc, series, data, mask, μ, logσ², w_kl)
+    B, T = size(series, 2), size(series, 3)
+    out = zeros(Float32, 3)
+    ll = similar(μ, Float32, B); kl = similar(ll)
+    dseries = similar(series); dμ = similar(μ); dlogσ² = similar(μ)
+    dpg = similar(μ, Float32, d.in_dims * d.node_dims + d.in_dims)
+    latent_check(h, ccall((:lrnde_latent_decode_loss, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Float32, Ptr{Float32}, Ptr{Float32},
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(series), Int32(T), Int32(B), pointer(data), pointer(mask), pointer(μ), pointer(logσ²), Float32(w_kl), out, pointer(ll),
+        pointer(kl), pointer(dseries), pointer(dμ), pointer(dlogσ²), pointer(dpg)))
+    return (; loss=out[1], neg_log_likelihood=out[2], kl_div=out[3], ll, kl, dseries, dμ, dlogσ², dpg)
+end
+function latent_record_generation(h)
+    g = Ref{UInt64}(0)
+    latent_check(h, ccall((:lrnde_latent_record_generation, lib), Cint, (Ptr{Cvoid}, Ptr{UInt64}), h, g))
+    return g[]
+end
+
 end # module

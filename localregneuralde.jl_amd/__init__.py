@@ -15,3 +15,6 @@ from .training import run_cifar_training_step, run_training_step  # noqa: F401
 from .optim import (Constant, CosineAnneal, ExponentialDecay, InverseDecay, Optimiser, Step,  # noqa: F401
                     construct_scheduler)
 from .sharding import LocalComm, init_comm, run_ranks, shard_columns  # noqa: F401
+from .latent import (LatentGRUCell, LatentHandle, LatentODE, Recurrence, ReparameterizeLayer,  # noqa: F401
+                     construct_time_series, glorot_latent_params, join_latent_params, latent_block_sizes, latent_ode_loss,
+                     run_latent_training_step, split_latent_params)

@@ -55,6 +55,11 @@ class SdeAdaptOpts(C.Structure):
                 ("qmin", C.c_float), ("qmax", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("maxiters", C.c_int32)]
 
 
+class LatentDesc(C.Structure):
+    """lrnde_latent_desc: cfg.ts_in_dims, ts_hidden_dims, ts_latent_dims, ts_node_dims"""
+    _fields_ = [("in_dims", C.c_int32), ("hidden_dims", C.c_int32), ("latent_dims", C.c_int32), ("node_dims", C.c_int32)]
+
+
 class SolveOpts(C.Structure):
     _fields_ = [("abstol", C.c_float), ("reltol", C.c_float), ("maxiters", C.c_int32),
                 ("save_start", C.c_int32), ("save_everystep", C.c_int32), ("exact_pow", C.c_int32)]
@@ -180,6 +185,17 @@ SYMBOLS = [
     ("lrnde_adjoint_trace_rows", C.c_int, [_vp, C.POINTER(_i32)]),
     ("lrnde_host_phases", C.c_int, [_vp, C.POINTER(C.c_double), _i32]),
     ("lrnde_last_solve_kernel_ms", C.c_int, [_vp, _fp, C.POINTER(_i32)]),
+    ("lrnde_latent_create", C.c_int, [C.POINTER(_vp), C.POINTER(LatentDesc), C.c_int, _vp]),
+    ("lrnde_latent_destroy", C.c_int, [_vp]),
+    ("lrnde_latent_last_error", C.c_char_p, [_vp]),
+    ("lrnde_latent_param_count", C.c_size_t, [C.POINTER(LatentDesc)]),
+    ("lrnde_latent_set_params", C.c_int, [_vp, _vp, C.c_size_t]),
+    ("lrnde_latent_encode", C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    ("lrnde_latent_encode_backward", C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lrnde_latent_decode", C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    ("lrnde_latent_decode_loss", C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _f, _fp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("lrnde_latent_record_generation", C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    ("lrnde_latent_last_launches", C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
 ]
 
 if not os.path.exists(LIB_PATH):

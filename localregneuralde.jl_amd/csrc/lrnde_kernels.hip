@@ -5145,3 +5145,6 @@ int lrnde_last_solve_kernel_ms(lrnde_ctx* c, float* ms, int32_t* launches) {
 }
 
 }  // extern "C"
+
+// ---- Latent ODE: Recurrence(LatentGRUCell) encoder, rec_to_gen, reparameterisation, gen_to_data and the loss ----
+#include "lrnde_latent.hpp"

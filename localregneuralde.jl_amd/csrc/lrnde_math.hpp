@@ -113,6 +113,12 @@ LRNDE_HD float geluf_c(float x) {
   return x / (1.0f + expf_c(-arg));
 }
 
+// NNlib.sigmoid of the LatentGRUCell gates (src/layers/latent_ode.jl:12-13).  Not an LRNDE_ACT_* code: only
+// lrnde_latent.hpp calls it.  expf_c clamps its argument at +-87, so the result stays in [1/(1+e^87), 1].
+LRNDE_HD float sigmoid_c(float x) { return 1.0f / (1.0f + expf_c(-x)); }
+// d sigmoid / dx from the function's value s
+LRNDE_HD float sigmoid_deriv_c(float s) { return s * (1.0f - s); }
+
 LRNDE_HD float act_apply(int act, float v) {
   if (act == 1) return tanhf_c(v);
   if (act == 2) return geluf_c(v);
