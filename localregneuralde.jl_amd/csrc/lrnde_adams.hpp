@@ -90,7 +90,6 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
   const size_t n = (size_t)B * c->desc.state_dim;
   const bool moulton = c->solver_alg == 2;
   const float abstol = o->abstol, reltol = o->reltol;
-  const PiConsts pi = pi_order3();
   // workspace: 16 vectors of the state's size in the adjoint's allocation (a backward pass overwrites them; nothing of the
   // forward lives there once this returns)
   AdjVec v;
@@ -111,11 +110,9 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
     ++nsaved;
     return LRNDE_OK;
   };
-  float t = t0;
   const float dtmax = t1 - t0;
-  const float dtmin = fmaxf(eps_f(t1), eps_f(t0));
   // ode_determine_initdt with order 3; k1 = f(u0, t0) is the first step's fsalfirst
-  float dt;
+  float dt_init;
   {
     float d0, d1, d2;
     if ((rc = lrnde_rhs(c, uprev, t0, B, k1))) return rc;
@@ -126,12 +123,12 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
     if ((rc = vec_axpy(c, tmp, uprev, dt0, 1, kk, &one, n))) return rc;
     if ((rc = lrnde_rhs(c, tmp, t0 + dt0, B, kb2))) return rc;
     if ((rc = vec_norm(c, kb2, k1, uprev, nullptr, abstol, reltol, n, 0, &d2))) return rc;
-    dt = initdt_tail(dt0, d1, d2, 3.0f, dtmax);
+    dt_init = initdt_tail(dt0, d1, d2, 3.0f, dtmax);
   }
-  st->nf = 3; st->dt_init = dt;
-  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
+  st->nf = 3; st->dt_init = dt_init;
+  AttemptLoop L = attempt_begin(pi_order3(), o->exact_pow, o->maxiters, 1, t0, t1, dt_init);
+  const float &t = L.t, &dt = L.dt;
   float h1 = 0.0f, h2 = 0.0f;
-  int accept = 0, iter = 0, status = LRNDE_OK;
   if (o->save_start && (rc = push_save(t0, u0))) return rc;
   while (isave < nsave && saveat_host[isave] <= t0) ++isave;
   const float a21 = 0.5f, a32 = 0.75f;
@@ -140,19 +137,12 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
   const float c21 = 0.5f, c22 = (float)(1.0 / 6.0), c23 = (float)(1.0 / 12.0);
   int launches = 0;
   while (t < t1) {
-    if (iter > 0) {
-      if (accept) {
-        std::swap(uprev, u);
-        float* sw = kprev; kprev = k1; k1 = kend; kend = sw;
-        std::swap(sp2, s2);
-        dt = dtpropose;
-      } else {
-        dt = pi_reject_dt(pi, dt, q11);
-      }
+    if (L.iter > 0 && L.accept) {
+      std::swap(uprev, u);
+      float* sw = kprev; kprev = k1; k1 = kend; kend = sw;
+      std::swap(sp2, s2);
     }
-    ++iter;
-    dt = header_clamp(dt, dtmax, dtmin, t, t1);
-    if ((status = header_status(iter, o->maxiters, dt, dtmin))) break;
+    if (!attempt_header(L, t1)) break;
     const int nacc = st->naccept;
     const float b2 = nacc >= 1 ? dt / h1 : 0.0f;
     const float b3 = nacc >= 2 ? b2 * ((dt + h1) / (h1 + h2)) : 0.0f;
@@ -203,19 +193,14 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
       if ((rc = norm_readback(c, n, 0, &eest))) return rc;
       launches += moulton ? 4 : 3;
     }
-    if (eest != eest) { status = LRNDE_DT_NAN; st->eest_last = eest; break; }
-    const PiStep ps = pi_step(pi, o->exact_pow, eest, pi_pow(o->exact_pow, qold, pi.beta2), q11);
-    q11 = ps.q11;
-    accept = (eest <= 1.0f);
-    if (trace_host && ntrace < cap_trace) { trace_host[ntrace].t = t; trace_host[ntrace].dt = dt; trace_host[ntrace].eest = eest; trace_host[ntrace].accepted = accept; ++ntrace; }
     st->eest_last = eest;
+    const float tprev = t;
+    const bool accept = attempt_judge(L, eest);
+    if (L.status) break;  // a NaN estimate
+    if (trace_host && ntrace < cap_trace) { trace_host[ntrace].t = tprev; trace_host[ntrace].dt = dt; trace_host[ntrace].eest = eest; trace_host[ntrace].accepted = accept; ++ntrace; }
     if (accept) {
       const int idx = st->naccept;
       st->naccept++;
-      qold = pi_qold(eest);
-      const float tprev = t;
-      t = snap_magnitude(t, dt, t1);
-      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
       h2 = h1; h1 = dt;
       bool need_poly = c->dense_on;
       for (int i = isave; i < nsave && saveat_host[i] <= t; ++i) if (saveat_host[i] != t) need_poly = true;
@@ -255,8 +240,9 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
     HIPCHK(c, hipMemcpyAsync(c->tail_copy_dst, u_saved + (size_t)c->tail_copy_slot * n, sizeof(float) * n, hipMemcpyDeviceToDevice, sq));
   c->tail_copy_dst = nullptr;
   HIPCHK(c, hipStreamSynchronize(sq));
-  st->retcode = status; st->iters = iter; st->nsaved = nsaved; st->t_final = t; st->dt_final = dt;
+  const int status = L.status;
+  st->retcode = status; st->iters = L.iter; st->nsaved = nsaved; st->t_final = t; st->dt_final = dt;
   c->last_launches = launches;
-  if (status != LRNDE_OK) return fail(c, status, "solve stopped with retcode %d at t=%g (iter %d)", status, (double)t, iter);
+  if (status != LRNDE_OK) return fail(c, status, "solve stopped with retcode %d at t=%g (iter %d)", status, (double)t, L.iter);
   return LRNDE_OK;
 }

@@ -2044,9 +2044,8 @@ int init_dt(lrnde_conv* c, const float* u0, int B, float t0, float tend, float a
 template <class RHS>
 int tsit5_step_g(lrnde_conv* c, size_t n, RHS&& rhs, const float* uprev, const float* k1, float t, float dt, float abstol,
                  float reltol, float* u, float* k7, float* ks, float* g6, float* tmp, double* sums3) {
-  float A[21];
-  for (int i = 0; i < 21; ++i) A[i] = (float)Tsit5::A[i];
-  const float cs[6] = {(float)Tsit5::C[0], (float)Tsit5::C[1], (float)Tsit5::C[2], (float)Tsit5::C[3], 1.0f, 1.0f};
+  const Tsit5F tb = tsit5_f32();
+  const float *A = tb.A, *cs = tb.cs;
   const float* K[7] = {k1, ks, ks + n, ks + 2 * n, ks + 3 * n, ks + 4 * n, k7};
   float* Kw[7] = {nullptr, ks, ks + n, ks + 2 * n, ks + 3 * n, ks + 4 * n, k7};
   int rc;
@@ -2279,7 +2278,6 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
   for (int i = 1; i < nsave; ++i) if (!(saveat[i] >= saveat[i - 1])) return cfail(c, LRNDE_BADARG, "saveat must be sorted");
   const size_t n = state_n(c, B);
   const float abstol = o->abstol, reltol = o->reltol;
-  const PiConsts pi = pi_tsit5();
   float* V = c->vec;
   float *uprev = V, *u = V + n, *k1 = V + 2 * n, *ks = V + 3 * n, *k7 = V + 8 * n, *g6 = V + 9 * n, *tmp = V + 10 * n;
   int nsaved = 0, isave = 0, ntrace = 0;
@@ -2295,42 +2293,28 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
     return LRNDE_OK;
   };
   CHK(c, hipMemcpyAsync(uprev, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  float t = t0;
-  const float dtmax = t1 - t0;
-  const float dtmin = fmaxf(eps_f(t1), eps_f(t0));
-  float dt;
-  if ((rc = init_dt(c, uprev, B, t0, t1, abstol, reltol, k1, tmp, g6, &dt))) return rc;
-  st->nf = 3; st->dt_init = dt;
-  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
-  int accept = 0, iter = 0;
+  float dt0;
+  if ((rc = init_dt(c, uprev, B, t0, t1, abstol, reltol, k1, tmp, g6, &dt0))) return rc;
+  st->nf = 3; st->dt_init = dt0;
+  AttemptLoop L = attempt_begin(pi_tsit5(), o->exact_pow, o->maxiters, 0, t0, t1, dt0);
+  const float &t = L.t, &dt = L.dt;
   if (o->save_start && (rc = push(t0, uprev))) return rc;
   while (isave < nsave && saveat[isave] <= t0) isave++;
-  rc = LRNDE_OK;
   while (t < t1) {
-    if (iter > 0) {
-      if (accept) { std::swap(uprev, u); std::swap(k1, k7); dt = dtpropose; }
-      else dt = pi_reject_dt(pi, dt, q11);
-    }
-    iter++;
-    dt = header_clamp(dt, dtmax, dtmin, t, t1);
-    if ((rc = header_status(iter, o->maxiters, dt, dtmin))) break;
+    if (L.iter > 0 && L.accept) { std::swap(uprev, u); std::swap(k1, k7); }
+    if (!attempt_header(L, t1)) break;
     double s[3];
     int r2;
     if ((r2 = tsit5_step(c, uprev, k1, B, t, dt, abstol, reltol, u, k7, ks, g6, tmp, s))) return r2;
     st->nf += 6;
     const float eest = (float)sqrt(s[0] / (double)n);
     st->eest_last = eest;
-    if (eest != eest) { rc = LRNDE_DT_NAN; break; }
-    const PiStep ps = pi_step(pi, o->exact_pow, eest, pi_pow(o->exact_pow, qold, pi.beta2), q11);
-    q11 = ps.q11;
-    accept = (eest <= 1.0f);
-    if (trace && ntrace < cap_trace) { trace[ntrace].t = t; trace[ntrace].dt = dt; trace[ntrace].eest = eest; trace[ntrace].accepted = accept; ntrace++; }
+    const float tprev = t;
+    const bool accept = attempt_judge(L, eest);
+    if (L.status) break;  // a NaN estimate
+    if (trace && ntrace < cap_trace) { trace[ntrace].t = tprev; trace[ntrace].dt = dt; trace[ntrace].eest = eest; trace[ntrace].accepted = accept; ntrace++; }
     if (accept) {
       st->naccept++;
-      qold = pi_qold(eest);
-      const float tprev = t;
-      t = snap_signed(t, dt, t1);
-      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
       if (c->dense_on) {  // [uprev, k1, k2..k6, k7] of this step, for the adjoint's interpolant
         const size_t idx = c->dense_t.size();
         if (c->dense_n != n) { c->dense.clear(); c->dense_n = n; }
@@ -2358,8 +2342,9 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
     } else st->nreject++;
   }
   CHK(c, hipStreamSynchronize(c->stream));
-  st->retcode = rc; st->iters = iter; st->nsaved = nsaved; st->t_final = t; st->dt_final = dt;
-  if (rc) return cfail(c, rc, "solve stopped with retcode %d at t=%g (dt=%g, %d iterations)", rc, (double)t, (double)dt, iter);
+  rc = L.status;
+  st->retcode = rc; st->iters = L.iter; st->nsaved = nsaved; st->t_final = t; st->dt_final = dt;
+  if (rc) return cfail(c, rc, "solve stopped with retcode %d at t=%g (dt=%g, %d iterations)", rc, (double)t, (double)dt, L.iter);
   return LRNDE_OK;
 }
 
@@ -2393,8 +2378,8 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
     float sv[2] = {t1, t2}, ts[3];
     if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, 2, us, ts, 3, st, nullptr, 0))) return rc;
     const int i1 = oo.save_start ? 1 : 0;
-    hipMemcpy(u1, us + (size_t)i1 * n, sizeof(float) * n, hipMemcpyDeviceToDevice);
-    hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice);
+    CHK(c, hipMemcpy(u1, us + (size_t)i1 * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
+    CHK(c, hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
   } else {  // :88-100 biased, saveat = [] => every accepted step
     oo.save_everystep = 1;
     // every accepted step is kept: start with room for 32 and re-solve with more if that overflows (a state is
@@ -2403,14 +2388,14 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
     DevBuf<float> bn0;
     const int Hc4b = 4 * c->d.hidden;
     if (bn0.once(Hc4b) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
-    hipMemcpyAsync(bn0, c->bn_state, sizeof(float) * Hc4b, hipMemcpyDeviceToDevice, c->stream);
+    CHK(c, hipMemcpyAsync(bn0, c->bn_state, sizeof(float) * Hc4b, hipMemcpyDeviceToDevice, c->stream));
     for (int cap = 32;; cap *= 4) {
       if (cap > oo.maxiters + 2) cap = oo.maxiters + 2;
       (void)us.reset();
       if (us.once(n * cap) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
       ts.assign(cap, 0.f);
       rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, nullptr, 0, us, ts.data(), cap, st, nullptr, 0);
-      if (rc == LRNDE_CAPACITY && cap < oo.maxiters + 2) { hipMemcpyAsync(c->bn_state, bn0, sizeof(float) * Hc4b, hipMemcpyDeviceToDevice, c->stream); continue; }
+      if (rc == LRNDE_CAPACITY && cap < oo.maxiters + 2) { CHK(c, hipMemcpyAsync(c->bn_state, bn0, sizeof(float) * Hc4b, hipMemcpyDeviceToDevice, c->stream)); continue; }
       break;
     }
     (void)bn0.reset();
@@ -2421,26 +2406,26 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
     if (idx >= m) idx = m - 1;
     if (idx < 0) idx = 0;
     t1 = ts[idx];
-    hipMemcpy(u1, us + (size_t)idx * n, sizeof(float) * n, hipMemcpyDeviceToDevice);
-    hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice);
+    CHK(c, hipMemcpy(u1, us + (size_t)idx * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
+    CHK(c, hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
   }
   if (t1_used) *t1_used = t1;
   if (c->dense_on) {
     if (c->rec_u1.resize_exact(n) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
-    hipMemcpy(c->rec_u1, u1, sizeof(float) * n, hipMemcpyDeviceToDevice);
+    CHK(c, hipMemcpy(c->rec_u1, u1, sizeof(float) * n, hipMemcpyDeviceToDevice));
   }
   // _get_ode_integrator :33-38 => init on (t1,t2); _perform_step :77.  The layer returns the model state as it was
   // when the solve returned (src/layers/neural_ode.jl:52): the local step's f-evals leave no trace in it.
   float* V = c->vec;
   float dtl, ee, re, rs;
   const int Hc4 = 4 * c->d.hidden;
-  hipMemcpyAsync(V, c->bn_state, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream);  // V[0..n) is free here
+  CHK(c, hipMemcpyAsync(V, c->bn_state, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream));  // V[0..n) is free here
   if ((rc = init_dt(c, u1, B, t1, t2, oo.abstol, oo.reltol, V + 2 * n, V + 10 * n, V + 9 * n, &dtl))) return rc;
   double s[3];
   if ((rc = tsit5_step(c, u1, V + 2 * n, B, t1, dtl, oo.abstol, oo.reltol, V + n, V + 8 * n, V + 3 * n, V + 9 * n, V + 10 * n, s))) return rc;
   reg_values(s, n, dtl, &ee, &re, &rs);
-  hipMemcpyAsync(c->bn_state, V, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream);
-  hipStreamSynchronize(c->stream);
+  CHK(c, hipMemcpyAsync(c->bn_state, V, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream));
+  CHK(c, hipStreamSynchronize(c->stream));
   *reg_val = (reg_type == LRNDE_REG_STIFFNESS_ESTIMATE) ? rs : re;
   *nfe = st->nf + (6 + 3);
   return LRNDE_OK;
@@ -2500,9 +2485,8 @@ int step_reg_grad(lrnde_conv* c, const float* uprev, const float* k1, int B, flo
   sa.eest = ee; sa.num = (float)sqrt(sm[1] / (double)n); sa.den = (float)sqrt(sm[2] / (double)n);
   { int nb = (int)((n + 255) / 256); if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_reg_seed, dim3(nb), dim3(256), 0, c->stream, sa); CHK(c, hipGetLastError()); }
-  float A[21];
-  for (int i = 0; i < 21; ++i) A[i] = (float)Tsit5::A[i];
-  const float cs[6] = {(float)Tsit5::C[0], (float)Tsit5::C[1], (float)Tsit5::C[2], (float)Tsit5::C[3], 1.0f, 1.0f};
+  const Tsit5F tb = tsit5_f32();
+  const float *A = tb.A, *cs = tb.cs;
   const float one = 1.0f;
   for (int sidx = 7; sidx >= 2; --sidx) {
     const int off = (sidx - 2) * (sidx - 1) / 2;
@@ -2533,31 +2517,19 @@ template <class RHS>
 int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float s1, const lrnde_solve_opts* o,
                   const std::vector<float>& tstops, lrnde_stats* st) {
   const float abstol = o->abstol, reltol = o->reltol;
-  const PiConsts pi = pi_tsit5();
   memset(st, 0, sizeof(*st));
   float *z = Z, *zn = Z + N, *k1 = Z + 2 * N, *ks = Z + 3 * N, *k7 = Z + 8 * N, *g6 = Z + 9 * N, *tmp = Z + 10 * N;
   int rc;
-  float t = s0;
-  const float dtmax = s1 - s0;
-  const float dtmin = fmaxf(eps_f(s1), eps_f(s0));
-  float dt;
-  if ((rc = init_dt_g(c, N, rhs, z, s0, s1, abstol, reltol, k1, tmp, g6, &dt))) return rc;
-  st->nf = 3; st->dt_init = dt;
-  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
-  int accept = 0, iter = 0;
-  size_t istop = 0;
-  while (istop < tstops.size() && tstops[istop] <= s0) ++istop;
-  rc = LRNDE_OK;
+  float dt0;
+  if ((rc = init_dt_g(c, N, rhs, z, s0, s1, abstol, reltol, k1, tmp, g6, &dt0))) return rc;
+  st->nf = 3; st->dt_init = dt0;
+  AttemptLoop L = attempt_begin(pi_tsit5(), o->exact_pow, o->maxiters, 1, s0, s1, dt0);  // (reversed time: magnitude snap)
+  const float &t = L.t, &dt = L.dt;
+  TstopCursor stops{tstops.data(), tstops.size(), 0};
   while (t < s1) {
-    while (istop < tstops.size() && tstops[istop] <= t) ++istop;
-    const float tstop = (istop < tstops.size() && tstops[istop] < s1) ? tstops[istop] : s1;
-    if (iter > 0) {
-      if (accept) { std::swap(z, zn); std::swap(k1, k7); dt = dtpropose; }
-      else dt = pi_reject_dt(pi, dt, q11);
-    }
-    ++iter;
-    dt = header_clamp(dt, dtmax, dtmin, t, tstop);
-    if ((rc = header_status(iter, o->maxiters, dt, dtmin))) break;
+    const float tstop = tstop_next(stops, t, s1);
+    if (L.iter > 0 && L.accept) { std::swap(z, zn); std::swap(k1, k7); }
+    if (!attempt_header(L, tstop)) break;
     double sm[3];
     int r2;
     // g6 doubles as the stage-6 state; its stiffness sums are not used here
@@ -2565,20 +2537,14 @@ int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float 
     st->nf += 6;
     const float eest = (float)sqrt(sm[0] / (double)N);
     st->eest_last = eest;
-    if (eest != eest) { rc = LRNDE_DT_NAN; break; }
-    const PiStep ps = pi_step(pi, o->exact_pow, eest, pi_pow(o->exact_pow, qold, pi.beta2), q11);
-    q11 = ps.q11;
-    accept = (eest <= 1.0f);
-    if (accept) {
-      st->naccept++;
-      qold = pi_qold(eest);
-      t = snap_magnitude(t, dt, tstop);  // (reversed time)
-      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
-    } else st->nreject++;
+    const bool accept = attempt_judge(L, eest);
+    if (L.status) break;  // a NaN estimate
+    if (accept) st->naccept++; else st->nreject++;
   }
-  if (accept && rc == LRNDE_OK) std::swap(z, zn);
+  rc = L.status;
+  if (L.accept && rc == LRNDE_OK) std::swap(z, zn);
   if (z != Z) CHK(c, hipMemcpyAsync(Z, z, sizeof(float) * N, hipMemcpyDeviceToDevice, c->stream));
-  st->retcode = rc; st->iters = iter; st->t_final = t; st->dt_final = dt;
+  st->retcode = rc; st->iters = L.iter; st->t_final = t; st->dt_final = dt;
   return rc;
 }
 
@@ -2664,11 +2630,10 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
   CHK(c, hipMemcpyAsync(Z, du_end, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   auto rhs = [&](const float* zs, float sg, float* K) -> int {
     const float t = -sg;
-    int lo = 0, hi = (int)dts.size() - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (dts[mid] <= t) lo = mid; else hi = mid - 1; }
-    const float theta = (t - dts[lo]) / dds[lo];
+    const RecAt at = rec_locate(dts.data(), dds.data(), (int)dts.size(), t);
+    const int lo = at.idx;
     float bw[7];
-    tsit5_bweights(theta, bw);
+    tsit5_bweights(at.theta, bw);
     const float* d = c->dense[lo];
     const float* K7[7] = {d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, d + 6 * n, d + 7 * n};
     int r;

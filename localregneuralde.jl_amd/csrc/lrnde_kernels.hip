@@ -3975,10 +3975,8 @@ int norm_readback(lrnde_ctx* c, size_t n_lam, size_t P, float* out) {
 int adj_rhs(lrnde_ctx* c, const std::vector<float>& dt_, const std::vector<float>& dd_, int B, size_t n,
             const float* zs, float sgt, float* K, const StageIn* sin = nullptr) {
   const float t = -sgt;
-  int lo = 0, hi = (int)dt_.size() - 1;
-  while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (dt_[mid] <= t) lo = mid; else hi = mid - 1; }
-  const float theta = (t - dt_[lo]) / dd_[lo];
-  return launch_vjp(c, nullptr, c->dense + (size_t)lo * REC_ARRAYS * n, theta, dd_[lo], t, zs, B, K, K + n, sin);
+  const RecAt at = rec_locate(dt_.data(), dd_.data(), (int)dt_.size(), t);
+  return launch_vjp(c, nullptr, c->dense + (size_t)at.idx * REC_ARRAYS * n, at.theta, dd_[at.idx], t, zs, B, K, K + n, sin);
 }
 
 struct AdjImpulse { float s; const float* du; };  // a cotangent added to lambda when the reversed solve reaches s = -t_saved
@@ -3990,61 +3988,50 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
                     float reltol, int maxiters, int exact_pow, const std::vector<float>& tstops,
                     const std::vector<AdjImpulse>& impulses, lrnde_stats* st) {
   const size_t N = v.N;
-  const PiConsts pi = pi_tsit5();
-  float A[21], BT[7];
-  for (int i = 0; i < 21; ++i) A[i] = (float)Tsit5::A[i];
-  for (int i = 0; i < 7; ++i) BT[i] = (float)Tsit5::BT[i];
-  const float cs[6] = {(float)Tsit5::C[0], (float)Tsit5::C[1], (float)Tsit5::C[2], (float)Tsit5::C[3], 1.0f, 1.0f};
+  const Tsit5F tb = tsit5_f32();
+  const float *A = tb.A, *cs = tb.cs, *BT = tb.BT;
   memset(st, 0, sizeof(*st));
   struct DeferGuard { lrnde_ctx* c; ~DeferGuard() { c->pg_defer = false; c->pg_pending = false; } } defer_guard{c};
   int rc;
-  float t = s0;
   const float dtmax = s1 - s0;
-  const float dtmin = fmaxf(eps_f(s1), eps_f(s0));
   float *z = v.z, *zn = v.zn;
   float* K[7]; for (int j = 0; j < 7; ++j) K[j] = v.K[j];
   // ode_determine_initdt
-  float dt;
+  float dt_init;
   {
-    if ((rc = rhs(z, t, K[0]))) return rc;
+    if ((rc = rhs(z, s0, K[0]))) return rc;
     float d0, d1, d2;
     if ((rc = vec_norm(c, z, nullptr, z, nullptr, abstol, reltol, v.n_lam, v.P, &d0))) return rc;
     if ((rc = vec_norm(c, K[0], nullptr, z, nullptr, abstol, reltol, v.n_lam, v.P, &d1))) return rc;
     const float dt0 = initdt_dt0(d0, d1, dtmax);
     const float one = 1.0f; const float* kk[1] = {K[0]};
     if ((rc = vec_axpy(c, v.zs, z, dt0, 1, kk, &one, N))) return rc;
-    if ((rc = rhs(v.zs, t + dt0, K[1]))) return rc;
+    if ((rc = rhs(v.zs, s0 + dt0, K[1]))) return rc;
     if ((rc = vec_norm(c, K[1], K[0], z, nullptr, abstol, reltol, v.n_lam, v.P, &d2))) return rc;
-    dt = initdt_tail(dt0, d1, d2, 5.0f, dtmax);
-    st->nf = 3; st->dt_init = dt;
+    dt_init = initdt_tail(dt0, d1, d2, 5.0f, dtmax);
+    st->nf = 3; st->dt_init = dt_init;
   }
-  float qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
-  int accept = 0, iter = 0;
-  size_t istop = 0, iimp = 0;
+  // (reversed time s = -t <= 0: the magnitude snap; the reference's adjoint runs t from t2 down to t0 with positive times)
+  AttemptLoop L = attempt_begin(pi_tsit5(), exact_pow, maxiters, 1, s0, s1, dt_init);
+  const float &t = L.t, &dt = L.dt;
+  TstopCursor stops{tstops.data(), tstops.size(), 0};
+  size_t iimp = 0;
   while (iimp < impulses.size() && impulses[iimp].s <= s0) ++iimp;
-  while (istop < tstops.size() && tstops[istop] <= s0) ++istop;
-  rc = LRNDE_OK;
   while (t < s1) {
-    while (istop < tstops.size() && tstops[istop] <= t) ++istop;
-    const float tstop = (istop < tstops.size() && tstops[istop] < s1) ? tstops[istop] : s1;
-    if (iter > 0) {
-      if (accept) {
-        std::swap(z, zn); std::swap(K[0], K[6]); dt = dtpropose;
-        // a cotangent impulse at the saved time just reached: lambda += du, K1 re-evaluated at the modified state
-        while (iimp < impulses.size() && impulses[iimp].s < t) ++iimp;
-        bool hit = false;
-        for (; iimp < impulses.size() && impulses[iimp].s == t && t < s1; ++iimp) {
-          const float* gi[1] = {impulses[iimp].du}; const float one = 1.0f;
-          if ((rc = vec_axpy(c, z, z, 1.0f, 1, gi, &one, v.n_lam))) return rc;
-          hit = true;
-        }
-        if (hit) { if ((rc = rhs(z, t, K[0]))) return rc; st->nf += 1; }
+    const float tstop = tstop_next(stops, t, s1);
+    if (L.iter > 0 && L.accept) {
+      std::swap(z, zn); std::swap(K[0], K[6]);
+      // a cotangent impulse at the saved time just reached: lambda += du, K1 re-evaluated at the modified state
+      while (iimp < impulses.size() && impulses[iimp].s < t) ++iimp;
+      bool hit = false;
+      for (; iimp < impulses.size() && impulses[iimp].s == t && t < s1; ++iimp) {
+        const float* gi[1] = {impulses[iimp].du}; const float one = 1.0f;
+        if ((rc = vec_axpy(c, z, z, 1.0f, 1, gi, &one, v.n_lam))) return rc;
+        hit = true;
       }
-      else dt = pi_reject_dt(pi, dt, q11);
+      if (hit) { if ((rc = rhs(z, t, K[0]))) return rc; st->nf += 1; }
     }
-    ++iter;
-    dt = header_clamp(dt, dtmax, dtmin, t, tstop);
-    if ((rc = header_status(iter, maxiters, dt, dtmin))) break;
+    if (!attempt_header(L, tstop)) break;
     // stages 2..7 (src/perform_step.jl:11-20 on the augmented state)
     c->pg_defer = fuse_stage;
     for (int sidx = 2; sidx <= 7; ++sidx) {
@@ -4083,25 +4070,17 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
       if ((rc = vec_norm(c, v.ut, nullptr, z, zn, abstol, reltol, v.n_lam, v.P, &eest))) return rc;
     }
     st->eest_last = eest;
-    if (eest != eest) { rc = LRNDE_DT_NAN; break; }
-    const PiStep ps = pi_step(pi, exact_pow, eest, pi_pow(exact_pow, qold, pi.beta2), q11);
-    q11 = ps.q11;
-    accept = (eest <= 1.0f);
+    const float tprev = t;
+    const bool accept = attempt_judge(L, eest);
+    if (L.status) break;  // a NaN estimate
     if (c->adj_trace && c->adj_trace_n < c->adj_trace_cap) {
       lrnde_trace_row& r = c->adj_trace[c->adj_trace_n++];
-      r.t = t; r.dt = dt; r.eest = eest; r.accepted = accept;
+      r.t = tprev; r.dt = dt; r.eest = eest; r.accepted = accept;
     }
-    if (accept) {
-      st->naccept++;
-      qold = pi_qold(eest);
-      // (reversed time s = -t <= 0; the reference's adjoint runs t from t2 down to t0 with positive times)
-      t = snap_magnitude(t, dt, tstop);
-      dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
-    } else {
-      st->nreject++;
-    }
+    if (accept) st->naccept++; else st->nreject++;
   }
-  if (accept && rc == LRNDE_OK) std::swap(z, zn);  // z now holds the end state
+  rc = L.status;
+  if (L.accept && rc == LRNDE_OK) std::swap(z, zn);  // z now holds the end state
   if (rc == LRNDE_OK)  // cotangents at the end time itself (a saved start value)
     for (; iimp < impulses.size(); ++iimp) {
       if (impulses[iimp].s < s1) continue;
@@ -4110,7 +4089,7 @@ int vec_tsit5_solve(lrnde_ctx* c, AdjVec& v, RHS rhs, RHSF rhs_fused, bool fuse_
       if (r2) return r2;
     }
   if (z != v.z) HIPCHK(c, hipMemcpyAsync(v.z, z, sizeof(float) * N, hipMemcpyDeviceToDevice, c->stream));
-  st->retcode = rc; st->iters = iter; st->t_final = t; st->dt_final = dt;
+  st->retcode = rc; st->iters = L.iter; st->t_final = t; st->dt_final = dt;
   return rc;
 }
 
@@ -4667,9 +4646,8 @@ static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, 
   sa.eest = eest; sa.num = stiff_num; sa.den = stiff_den;
   { int nb = (int)((n + 255) / 256); if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_reg_seed, dim3(nb), dim3(256), 0, c->stream, sa); HIPCHK(c, hipGetLastError()); }
-  float A[21];
-  for (int i = 0; i < 21; ++i) A[i] = (float)Tsit5::A[i];
-  const float cs[6] = {(float)Tsit5::C[0], (float)Tsit5::C[1], (float)Tsit5::C[2], (float)Tsit5::C[3], 1.0f, 1.0f};
+  const Tsit5F tb = tsit5_f32();
+  const float *A = tb.A, *cs = tb.cs;
   // per stage, newest first: stage input (one launch), vector-Jacobian product, parameter-gradient GEMM ACCUMULATING
   // into gp, and one fused join (xbar += ubar / g6bar; kbar_j += dt a_sj xbar for every earlier stage): 4 launches
   // (the sweep is launch-bound: it was 7..9 small launches per stage)

@@ -203,6 +203,16 @@ struct Tsit5 {
       0.0, 1.5, -4.0, 2.5};
 };
 
+// the tableau rounded to Float32, for host code that hands coefficient arrays to a launch (cs: the stage times c_2..c_7)
+struct Tsit5F { float A[21], cs[6], BT[7]; };
+inline Tsit5F tsit5_f32() {
+  Tsit5F f;
+  for (int i = 0; i < 21; ++i) f.A[i] = (float)Tsit5::A[i];
+  for (int i = 0; i < 6; ++i) f.cs[i] = (float)Tsit5::C[i];
+  for (int i = 0; i < 7; ++i) f.BT[i] = (float)Tsit5::BT[i];
+  return f;
+}
+
 // dense-output weights b_i(theta) (OrdinaryDiffEq Tsit5 interpolant)
 LRNDE_HD void tsit5_bweights(float th, float* b) {
   const float th2 = th * th;
@@ -240,6 +250,15 @@ LRNDE_HD float tsit5_rec_eval(float y0, float k1, float P2, float P3, float P4, 
   s = s * (th * th);
   s = s + th * k1;
   return y0 + ddt * s;
+}
+
+// Where a time lies in a dense record (host; t_rec ascending, nrec >= 1): the last recorded step with t_rec <= t, the
+// first one when t lies before them all, and theta = (t - t_rec) / dt_rec in it.
+struct RecAt { int idx; float theta; };
+inline RecAt rec_locate(const float* t_rec, const float* dt_rec, int nrec, float t) {
+  int lo = 0, hi = nrec - 1;
+  while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (t_rec[mid] <= t) lo = mid; else hi = mid - 1; }
+  return {lo, (t - t_rec[lo]) / dt_rec[lo]};
 }
 
 }  // namespace lrnde

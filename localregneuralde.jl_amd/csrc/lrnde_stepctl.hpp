@@ -4,9 +4,11 @@
 //
 // Like lrnde_math.hpp: fixed sequences of IEEE-754 fp32 operations (pow / log10 in fp64 where upstream calls libm),
 // compiled with -ffp-contract=off, so an expression has the same bits wherever it is inlined.  Everything takes and
-// returns values; counters, trace rows, save and record bookkeeping stay with the loops.
+// returns values (the host loops' AttemptLoop and TstopCursor are such values, advanced in place) and makes no HIP call;
+// counters, trace rows, save and record bookkeeping stay with the loops.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 
 #include "lrnde_math.hpp"
 
@@ -71,6 +73,64 @@ LRNDE_HD int header_status(int iter, int maxiters, float dt, float dtmin) {
   if (dt != dt) return STEP_DT_NAN;
   if (__builtin_fabsf(dt) <= __builtin_fabsf(dtmin)) return STEP_DT_LESS_THAN_MIN;
   return STEP_OK;
+}
+
+// ---- the attempt loop of a host-controlled solve, stated once ----
+// The state machine around the pieces above, in the order that matters to the bit: q11 survives a reject, qold changes
+// only on an accept, iter counts an attempt before header_status sees it, a NaN estimate stops the loop before the
+// controller runs.  A loop is
+//   AttemptLoop L = attempt_begin(...);
+//   while (L.t < t1) { [swap buffers if L.iter > 0 && L.accept]  if (!attempt_header(L, tend)) break;
+//                      [a step of L.dt from L.t -> eest]  attempt_judge(L, eest);  if (L.status) break;  [bookkeeping] }
+// and L.status is its retcode.  snap_mag: 0 = snap_signed (the forward loops), 1 = snap_magnitude (reversed time, Adams).
+// The device loops keep this state in their double-buffered control blocks and call the pieces themselves.
+struct AttemptLoop {
+  PiConsts pi; int exact_pow, maxiters; int snap_mag;
+  float t, dt, dtpropose, dtmax, dtmin, qold, q11;
+  float tend;   // the end time the last header clamped to: the one an accepted step snaps onto
+  int accept, iter, status;
+};
+LRNDE_HD AttemptLoop attempt_begin(const PiConsts pi, int exact_pow, int maxiters, int snap_mag, float t0, float t1, float dt_init) {
+  AttemptLoop L;
+  L.pi = pi; L.exact_pow = exact_pow; L.maxiters = maxiters; L.snap_mag = snap_mag;
+  L.t = t0; L.dt = L.dtpropose = dt_init;
+  L.dtmax = t1 - t0;
+  L.dtmin = fmaxf_(eps_f(t1), eps_f(t0));
+  L.qold = QOLDINIT; L.q11 = 1.0f;
+  L.tend = t1;
+  L.accept = L.iter = 0; L.status = STEP_OK;
+  return L;
+}
+// the dt of the next attempt towards tend (a tstop, or the end of the span); false: there is none, L.status says why
+LRNDE_HD bool attempt_header(AttemptLoop& L, float tend) {
+  if (L.iter > 0) L.dt = L.accept ? L.dtpropose : pi_reject_dt(L.pi, L.dt, L.q11);
+  ++L.iter;
+  L.tend = tend;
+  L.dt = header_clamp(L.dt, L.dtmax, L.dtmin, L.t, tend);
+  L.status = header_status(L.iter, L.maxiters, L.dt, L.dtmin);
+  return L.status == STEP_OK;
+}
+// the attempt's error estimate: accepted (L.t moves, L.dtpropose is the next dt) or not; L.dt stays the attempted step
+LRNDE_HD bool attempt_judge(AttemptLoop& L, float eest) {
+  if (eest != eest) { L.status = STEP_DT_NAN; L.accept = 0; return false; }
+  const PiStep ps = pi_step(L.pi, L.exact_pow, eest, pi_pow(L.exact_pow, L.qold, L.pi.beta2), L.q11);
+  L.q11 = ps.q11;
+  L.accept = (eest <= 1.0f);
+  if (L.accept) {
+    L.qold = pi_qold(eest);
+    L.t = L.snap_mag ? snap_magnitude(L.t, L.dt, L.tend) : snap_signed(L.t, L.dt, L.tend);
+    L.dtpropose = pi_propose(L.dt, ps.q, L.dtmax, dt_floor(L.t, L.dtmin));
+  }
+  return L.accept;
+}
+
+// ---- tstops of a solve over (s0, s1), ascending: the end time of the attempt that starts at t ----
+// Entries <= t are passed (so are those <= s0 on the first call, and equal ones together); the next one is the stop if
+// it lies strictly before s1, else s1 is.  t never decreases between calls.
+struct TstopCursor { const float* tstops; size_t n, i; };
+LRNDE_HD float tstop_next(TstopCursor& c, float t, float s1) {
+  while (c.i < c.n && c.tstops[c.i] <= t) ++c.i;
+  return (c.i < c.n && c.tstops[c.i] < s1) ? c.tstops[c.i] : s1;
 }
 
 // ---- ode_determine_initdt from its three norms ----

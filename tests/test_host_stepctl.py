@@ -30,44 +30,41 @@ SRC = textwrap.dedent(r'''
           printf("%08x %08x\n", bits(dt0), bits(initdt_tail(dt0, d1, d2, order, dtmax)));
           continue;
         }
-        // C set exact_pow snap maxiters n t0 t1 dt_init eest[n]: one row per attempt
+        if (kind[0] == 'S') {   // S n s0 s1 stops[n] m t[m] -> per t: the attempt's end time, the cursor's index
+          int n, m;
+          if (scanf("%d", &n) != 1) return 2;
+          const float s0 = rd(), s1 = rd();
+          std::vector<float> stops(n);
+          for (float& x : stops) x = rd();
+          if (scanf("%d", &m) != 1) return 2;
+          TstopCursor c{stops.data(), stops.size(), 0};
+          (void)s0;   // (the first t of a solve is s0: entries <= s0 are passed by that call)
+          for (int i = 0; i < m; ++i) {
+            const float e = tstop_next(c, rd(), s1);
+            printf("%08x %d\n", bits(e), (int)c.i);
+          }
+          continue;
+        }
+        // C set exact_pow snap maxiters n t0 t1 dt_init eest[n]: one row per attempt, every attempt towards t1
+        // T ... eest[n] tend[n + 1]: the same with attempt i towards tend[i] (a solve with tstops)
         int set, exact, snap, maxiters, n;
         if (scanf("%d %d %d %d %d", &set, &exact, &snap, &maxiters, &n) != 5) return 2;
-        const float t0 = rd(), t1 = rd();
-        float dt = rd();
-        std::vector<float> ee(n);
+        const float t0 = rd(), t1 = rd(), dt_init = rd();
+        std::vector<float> ee(n), tend(n + 1, t1);
         for (float& e : ee) e = rd();
-        const PiConsts k = set ? pi_order3() : pi_tsit5();
-        const float dtmax = t1 - t0, dtmin = fmaxf_(eps_f(t1), eps_f(t0));
-        float t = t0, qold = QOLDINIT, q11 = 1.0f, dtpropose = dt;
-        int iter = 1;
-        dt = header_clamp(dt, dtmax, dtmin, t, t1);
-        int status = header_status(iter, maxiters, dt, dtmin);
-        printf("%d %08x\n", status, bits(dt));
+        if (kind[0] == 'T') for (float& e : tend) e = rd();
+        AttemptLoop L = attempt_begin(set ? pi_order3() : pi_tsit5(), exact, maxiters, snap, t0, t1, dt_init);
+        attempt_header(L, tend[0]);
+        int status = L.status;
+        printf("%d %08x\n", status, bits(L.dt));
         for (int i = 0; i < n && status == 0; ++i) {
-          const float eest = ee[i];
-          int accept = 0;
-          if (eest != eest) {
-            status = STEP_DT_NAN;
-          } else {
-            const PiStep ps = pi_step(k, exact, eest, pi_pow(exact, qold, k.beta2), q11);
-            q11 = ps.q11;
-            accept = eest <= 1.0f;
-            if (accept) {
-              qold = pi_qold(eest);
-              t = snap ? snap_magnitude(t, dt, t1) : snap_signed(t, dt, t1);
-              dtpropose = pi_propose(dt, ps.q, dtmax, dt_floor(t, dtmin));
-            }
-            if (!(t < t1)) {
-              status = 100;
-            } else {
-              dt = accept ? dtpropose : pi_reject_dt(k, dt, q11);
-              ++iter;
-              dt = header_clamp(dt, dtmax, dtmin, t, t1);
-              status = header_status(iter, maxiters, dt, dtmin);
-            }
+          attempt_judge(L, ee[i]);
+          status = L.status;
+          if (status == 0) {
+            if (!(L.t < t1)) status = 100;
+            else { attempt_header(L, tend[i + 1]); status = L.status; }
           }
-          printf("%08x %d %08x %08x %08x %d\n", bits(q11), accept, bits(t), bits(dtpropose), bits(dt), status);
+          printf("%08x %d %08x %08x %08x %d\n", bits(L.q11), L.accept, bits(L.t), bits(L.dtpropose), bits(L.dt), status);
         }
         printf("end\n");
       }
@@ -128,18 +125,21 @@ def clamp_status(dt, dtmax, dtmin, t, t1, it, maxiters):
     return dt, OK
 
 
-def restate(cset, exact, snap, maxiters, t0, t1, dt, eests):
-    """the loops' recurrence: rows of (q11, accept, t, dtpropose, next dt, status)"""
+def restate(cset, exact, snap, maxiters, t0, t1, dt, eests, tends=None):
+    """the loops' recurrence: rows of (q11, accept, t, dtpropose, next dt, status).  tends: the end time
+    of each attempt (a tstop or t1; one more than eests), every one t1 when not given"""
     gamma, qmin, qmax, beta1, beta2 = CONSTS[cset]
     t0, t1, dt = f32(t0), f32(t1), f32(dt)
+    tends = [t1] * (len(eests) + 1) if tends is None else [f32(x) for x in tends]
     dtmax = f32(t1 - t0)
     dtmin = fmax(_eps(t1), _eps(t0))
     t, qold, q11, dtpropose, it = t0, f32(1e-4), ONE, dt, 1
-    dt, status = clamp_status(dt, dtmax, dtmin, t, t1, it, maxiters)
+    dt, status = clamp_status(dt, dtmax, dtmin, t, tends[0], it, maxiters)
     rows = [(status, bits(dt))]
-    for eest in eests:
+    for i, eest in enumerate(eests):
         if status != OK:
             break
+        tend = tends[i]
         eest = f32(eest)
         accept = False
         if np.isnan(eest):
@@ -155,22 +155,22 @@ def restate(cset, exact, snap, maxiters, t0, t1, dt, eests):
             if accept:
                 qold = fmax(eest, f32(1e-4))
                 ttmp = f32(t + dt)
-                ref = fmax(f32(abs(t)), f32(abs(t1))) if snap else fmax(t, t1)
-                t = t1 if abs(f32(ttmp - t1)) < f32(f32(100) * _eps(ref)) else ttmp
+                ref = fmax(f32(abs(t)), f32(abs(tend))) if snap else fmax(t, tend)
+                t = tend if abs(f32(ttmp - tend)) < f32(f32(100) * _eps(ref)) else ttmp
                 dtpropose = fmax(fmin(dtmax, f32(dt / q)), fmax(_eps(t), dtmin))
             if not t < t1:
                 status = DONE
             else:
                 dt = dtpropose if accept else f32(dt / fmin(f32(ONE / qmin), f32(q11 / gamma)))
                 it += 1
-                dt, status = clamp_status(dt, dtmax, dtmin, t, t1, it, maxiters)
+                dt, status = clamp_status(dt, dtmax, dtmin, t, tends[i + 1], it, maxiters)
         rows.append((bits(q11), int(accept), bits(t), bits(dtpropose), bits(dt), status))
     return rows
 
 
 NEXT1 = np.nextafter(f32(1), f32(2))
 NEAR = f32(1) - f32(2.0 ** -20)   # a step of this length from the start of a unit span ends 8 ulp(1) short of its end
-# name: (t0, t1, dt_init, maxiters, eests)
+# name: (t0, t1, dt_init, maxiters, eests[, tends])
 SCRIPTS = {
     # zero, exactly one, just above one (a reject), both growth clamps, three rejects in a row, NaN last
     "mixed": (0.0, 1.0, 0.01, 1000, [0.0, 1.0, NEXT1, 1e-30, 1e30, 2.0, 1.5, 0.5, 0.25, float("nan")]),
@@ -178,17 +178,21 @@ SCRIPTS = {
     "reversed": (-1.0, 0.0, NEAR, 1000, [0.5, 0.5, 0.5, 0.5, float("nan")]),
     "dtmin": (0.0, 1.0, 0.01, 1000, [1e30] * 14),
     "maxiters": (0.0, 1.0, 0.01, 3, [0.5] * 6),
+    # tstops at 1/4 and 1/2: a first step that ends 8 ulp short of 1/4, a reject and an accept on the way to 1/2, a step
+    # cut at 1/2, one towards the end of the span
+    "tstops": (0.0, 1.0, f32(0.25) * NEAR, 1000, [0.5, 2.0, 1e-30, 1e-30, 1e-30], [0.25, 0.5, 0.5, 0.5, 1.0, 1.0]),
 }
 
 
 def run_script(driver, name, cset, exact, snap):
-    t0, t1, dt, maxiters, eests = SCRIPTS[name]
-    text = "C %d %d %d %d %d %s %s %s %s\n" % (cset, exact, snap, maxiters, len(eests), hx(t0), hx(t1), hx(dt),
-                                                " ".join(hx(e) for e in eests))
+    t0, t1, dt, maxiters, eests = SCRIPTS[name][:5]
+    tends = SCRIPTS[name][5] if len(SCRIPTS[name]) > 5 else None
+    text = "%s %d %d %d %d %d %s %s %s %s\n" % ("C" if tends is None else "T", cset, exact, snap, maxiters, len(eests), hx(t0),
+                                                 hx(t1), hx(dt), " ".join(hx(e) for e in eests + (tends or [])))
     out = driver(text)
     end = out.index("end")
     got = [tuple(int(w, 16) if len(w) == 8 else int(w) for w in ln.split()) for ln in out[:end]]
-    want = restate(cset, exact, snap, maxiters, t0, t1, dt, eests)
+    want = restate(cset, exact, snap, maxiters, t0, t1, dt, eests, tends)
     assert len(got) == len(want), (name, got, want)
     for i, (g, w) in enumerate(zip(got, want)):
         assert len(g) == len(w) and all(same(a, b) for a, b in zip(g, w)), (name, cset, exact, snap, i, g, w)
@@ -212,11 +216,41 @@ def test_controller_recurrence(driver, cset, exact, snap):
     assert s[1][2] == bits(f32(1.0)) and s[1][5] == DONE and len(s) == 2, "t + dt within 100 eps of t1 lands on t1"
     assert rows["dtmin"][-1][-1] == DT_LESS_THAN_MIN
     assert rows["maxiters"][-1][-1] == MAXITERS and len(rows["maxiters"]) == 1 + 3
+    ts = rows["tstops"]
+    assert ts[1][2] == bits(f32(0.25)) and ts[1][5] == OK, "t + dt within 100 eps of the tstop lands on it, and the solve goes on"
+    assert [r[1] for r in ts[1:]] == [1, 0, 1, 1, 1] and ts[4][2] == bits(f32(0.5)), "the step after the reject is cut at the second tstop"
     r = rows["reversed"]
     if snap:
         assert r[1][2] == bits(f32(0.0)) and r[1][5] == DONE
     else:   # eps at the signed maximum (0) is the smallest subnormal: no snap, the solve goes on
         assert r[1][2] == bits(f32(f32(-1.0) + NEAR)) and r[1][5] == OK and len(r) > 2
+
+
+def next_stop(stops, t, s1):
+    """the end time of an attempt that starts at t: the first tstop after t if it lies before s1, else s1; and how many
+    of the (ascending) tstops lie at or before t"""
+    later = [x for x in stops if x > t]
+    return (later[0] if later and later[0] < s1 else s1), len(stops) - len(later)
+
+
+def test_tstop_cursor(driver):
+    s0, s1 = -1.0, 0.0
+    # name: (tstops, the times attempts start at)
+    cases = {
+        # a stop at s0, two equal stops, a stop at s1 and one past it; t on a stop, between stops, past two stops at once
+        "all": ([-1.0, -0.75, -0.75, -0.5, -0.25, 0.0, 0.5], [-1.0, -0.875, -0.75, -0.625, -0.125, -0.0625]),
+        "empty": ([], [-1.0, -0.5]),
+        "past_s1": ([0.5], [-1.0, -0.5]),
+        "at_s1": ([0.0], [-1.0, -0.5]),
+    }
+    for name, (stops, ts) in cases.items():
+        out = driver("S %d %s %s %s %d %s\n" % (len(stops), hx(s0), hx(s1), " ".join(hx(x) for x in stops), len(ts),
+                                                " ".join(hx(t) for t in ts)))
+        for t, ln in zip(ts, out):
+            e, i = next_stop(stops, t, s1)
+            assert ln.split() == [hx(e), str(i)], (name, t, ln, e, i)
+    want = [next_stop(cases["all"][0], t, s1) for t in cases["all"][1]]
+    assert want == [(-0.75, 1), (-0.75, 1), (-0.5, 3), (-0.5, 3), (0.0, 5), (0.0, 5)], want   # (a stop at s1 is not passed: s1 is returned as the end)
 
 
 def restate_initdt(d0, d1, d2, dtmax, order):
