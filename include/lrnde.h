@@ -513,7 +513,9 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* sde, const float* x, const floa
  * loss = <du_new, u'> + w_reg * EEst*dt.  du_new (device, may be NULL = 0): cotangent of the step's result; dx (device, may be
  * NULL): cotangent of uprev — NULL when uprev is a constant of the tape, as for the local step's regulariser
  * (src/layers/neural_sde.jl:42); dp_drift / dp_diff (device): the parameter cotangents are ADDED (zero them first; a solve's
- * pullback calls this once per step, newest first).  dW, dZ, dt are constants.  reg_val_host (may be NULL): EEst*dt. */
+ * pullback calls this once per step, newest first).  dW, dZ, dt are constants.  reg_val_host (may be NULL): EEst*dt.
+ * With w_reg != 0, dx holds the whole derivative of w_reg * EEst*dt with respect to uprev: through u', through the stages, and
+ * through the residual's scale abstol + max(|uprev|, |u'|) * reltol on whichever side carries the maximum (a tie: uprev). */
 int lrnde_sde_sri_step_backward(lrnde_sde* sde, const lrnde_sri_tableau* tab, const float* uprev, const float* dW, const float* dZ,
                                 int32_t B, float t, float dt, float abstol, float reltol, float delta, const float* du_new,
                                 float w_reg, float* dx, float* dp_drift, float* dp_diff, float* reg_val_host);

@@ -688,6 +688,7 @@ __global__ void k_sri_bseed(size_t n, SriBwd a, lrnde_sri_tableau T) {
     const float g1 = a.g[0][i], g2 = a.g[1][i], g3 = a.g[2][i], g4 = a.g[3][i];
     const float up = a.up[i], un = a.un[i];
     float unb = a.du_new ? a.du_new[i] : 0.f;
+    float upd = 0.f;                             // the scale's own term of uprev's cotangent (the u' side goes into unb)
     float numb = 0.f;
     if (a.w_reg != 0.f && a.eest > 0.f) {
       const float s3 = ((T.beta31 * g1 + T.beta32 * g2) + T.beta33 * g3) + T.beta34 * g4;
@@ -699,7 +700,10 @@ __global__ void k_sri_bseed(size_t n, SriBwd a, lrnde_sri_tableau T) {
       const float r = num / sc;
       const float rb = a.w_reg * a.dt * r / (a.nf * a.eest);     // reg = dt * sqrt(mean r^2)
       numb = rb / sc;
-      if (__builtin_fabsf(un) > __builtin_fabsf(up)) unb += (-rb * num / (sc * sc)) * a.reltol * (un >= 0.f ? 1.f : -1.f);
+      // d sc: the larger of |uprev| and |u'| carries it; a tie stays with uprev, as fmaxf_ and the forward have it
+      const float scb = (-rb * num / (sc * sc)) * a.reltol;
+      if (__builtin_fabsf(un) > __builtin_fabsf(up)) unb += scb * (un >= 0.f ? 1.f : -1.f);
+      else upd = scb * (up >= 0.f ? 1.f : -1.f);
     }
     const float e1b = a.delta * numb;            // cotangent of E1
     const float e2b = unb + numb;                // cotangent of E2 (u' contains E2)
@@ -710,7 +714,7 @@ __global__ void k_sri_bseed(size_t n, SriBwd a, lrnde_sri_tableau T) {
     a.gb[1][i] = ((T.beta12 * w1 + T.beta22 * w2) + T.beta32 * w3) + T.beta42 * w4;
     a.gb[2][i] = ((T.beta13 * w1 + T.beta23 * w2) + T.beta33 * w3) + T.beta43 * w4;
     a.gb[3][i] = ((T.beta14 * w1 + T.beta24 * w2) + T.beta34 * w3) + T.beta44 * w4;
-    a.upb[i] = unb;
+    a.upb[i] = unb + upd;
   }
 }
 // after the VJPs of stage st (k_{st+1} = f(H0_st), g_{st+1} = g(H1_st)): ha / hb = cotangents of H0_st / H1_st
