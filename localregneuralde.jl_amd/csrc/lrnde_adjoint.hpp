@@ -180,13 +180,12 @@ __device__ __forceinline__ AdjStage adj_lookup_lanes(const AdjArgs& g, const Adj
   return s;
 }
 
-// the pinned progress block (host view: volatile int hs[16]): [0] seq (written last, release), [1] status, [2] t, [3] dt,
-// [4] cur, [5] nf, [6] naccept, [7] nreject, [8] iter, [9] eest_last, [10] dt_init — everything the host driver needs of
-// the integrator's state, so that a finished solve costs no read-back copy and no synchronisation of its own
+// the pinned progress block (lrnde_report.hpp has its slots and the host's reader, adj_report_read); the caller stores
+// ADJ_R_SEQ last, with release
 __device__ __forceinline__ void adj_hstat_fill(int* hs, const AdjCtrl& c) {
-  hs[1] = c.status; hs[2] = __builtin_bit_cast(int, c.t); hs[3] = __builtin_bit_cast(int, c.dt);
-  hs[4] = c.cur; hs[5] = c.nf; hs[6] = c.naccept; hs[7] = c.nreject; hs[8] = c.iter;
-  hs[9] = __builtin_bit_cast(int, c.eest_last); hs[10] = __builtin_bit_cast(int, c.dt_init);
+  hs[ADJ_R_STATUS] = c.status; hs[ADJ_R_T] = __builtin_bit_cast(int, c.t); hs[ADJ_R_DT] = __builtin_bit_cast(int, c.dt);
+  hs[ADJ_R_CUR] = c.cur; hs[ADJ_R_NF] = c.nf; hs[ADJ_R_NACCEPT] = c.naccept; hs[ADJ_R_NREJECT] = c.nreject; hs[ADJ_R_ITER] = c.iter;
+  hs[ADJ_R_EEST_LAST] = __builtin_bit_cast(int, c.eest_last); hs[ADJ_R_DT_INIT] = __builtin_bit_cast(int, c.dt_init);
 }
 
 // overlapped launches: the control block of attempt j is read by the stage-3 launch WHILE this (stage-2) launch runs, from
@@ -261,8 +260,8 @@ __device__ __forceinline__ AdjCtrl adj_prologue(const AdjArgs& g, int j) {
       else *cout = c;
       if (g.hstat) {
         adj_hstat_fill(g.hstat, c);
-        if (g.sync) g.hstat[11] = ldcc(g.sync + 1);   // a wait of an overlapped launch timed out: the results are not to be used
-        __hip_atomic_store(g.hstat, g.seq0 + j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (g.sync) g.hstat[ADJ_R_OVL_TIMEOUT] = ldcc(g.sync + 1);   // a wait of an overlapped launch timed out: the results are not to be used
+        __hip_atomic_store(g.hstat + ADJ_R_SEQ, g.seq0 + j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
     return c;
@@ -308,8 +307,8 @@ __device__ __forceinline__ AdjCtrl adj_prologue(const AdjArgs& g, int j) {
     else *cout = c;
     if (g.hstat) {
       adj_hstat_fill(g.hstat, c);
-      if (g.sync) g.hstat[11] = ldcc(g.sync + 1);
-      __hip_atomic_store(g.hstat, g.seq0 + j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (g.sync) g.hstat[ADJ_R_OVL_TIMEOUT] = ldcc(g.sync + 1);
+      __hip_atomic_store(g.hstat + ADJ_R_SEQ, g.seq0 + j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
   return c;

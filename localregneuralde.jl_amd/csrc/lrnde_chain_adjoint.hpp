@@ -69,7 +69,7 @@ __device__ __forceinline__ void chadj_report(const ChAdjArgs& a, const ChAdjCtrl
   a.cc[(j + 1) & 1] = c;
   if (a.g.hstat) {
     adj_hstat_fill(a.g.hstat, c.c);
-    __hip_atomic_store(a.g.hstat, a.g.seq0 + j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(a.g.hstat + ADJ_R_SEQ, a.g.seq0 + j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 

@@ -48,6 +48,7 @@
 #include "lrnde_hooks.h"
 #include "lrnde_math.hpp"
 #include "lrnde_stepctl.hpp"
+#include "lrnde_report.hpp"
 #include "lrnde_buf.hpp"
 #include "lrnde_comm.hpp"
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
@@ -65,7 +66,6 @@ constexpr int PSTRIDE = 4;   // doubles per workgroup in a partial-sum vector
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum { ST_RUNNING = 0, ST_DONE = 100 };                // Ctrl.status: else an lrnde_status error
 enum { MODE_SOLVE = 0, MODE_SINGLE_GIVEN_DT = 1, MODE_SINGLE_INIT_DT = 2, MODE_BENCH = 3 };
 
 struct ModelDev {
@@ -954,17 +954,17 @@ __device__ __forceinline__ float init_dt_final3(const Sum3& r1, const Sum3& r2, 
 }
 
 // Progress of a solve, for the host loop that keeps the stream fed (lrnde_solve): ONE 64-bit store per launch into
-// pinned host memory — [launches run : 24][status : 8][saves completed : 16][steps still to go at this dt : 16] — into
+// pinned host memory — launches run, status, saves completed, steps still to go at this dt (lrnde_report.hpp) — into
 // slot (launch index mod PROG_RING) of a small ring, so the host can read the report of EVERY launch, in order: a
 // batch-sharded run needs that (all ranks must steer by the same launch's report or their collective counts drift
 // apart), and each entry validates itself by the launch count it carries.  A posted write: the wave does not wait for
 // it, and the host only steers by it (how many launches to enqueue next, when to start the companion's local step);
 // everything it reports is read after the stream has been synchronised.  A finished solve also leaves its control block
 // in host memory, so the host needs no copy packet on the stream.
-constexpr int PROG_RING = 32;  // > the deepest queue the host keeps (16 launches ahead of the last report it has read)
 template <class A> __device__ __forceinline__ void solve_progress(const A& a, int j, const CtrlHead& c, int nsaved_done, float steps_left) {
   if (!a.prog) return;
   if (c.status != ST_RUNNING) *reinterpret_cast<CtrlHead*>(a.fin_host) = c;
+  // solve_report_pack(solve_report(j, c.status, nsaved_done, steps_left)), kept as the flat expression the kernels were tuned with
   const unsigned long long cnt = (unsigned long long)(j + 1) & 0xffffffull;
   const unsigned long long stt = (unsigned long long)(c.status & 0xff);
   const unsigned long long nsv = (unsigned long long)(nsaved_done > 65535 ? 65535 : nsaved_done);
@@ -1919,26 +1919,13 @@ int fail(lrnde_ctx* c, int code, const char* fmt, ...) {
   } while (0)
 
 #define HPT(c, i) ((c)->hp_t[i] = std::chrono::steady_clock::now())
-// for the host loops that spin on a report word in pinned memory: true once a wait has lasted 20 ms (then every 20 ms) — the
-// caller then asks the runtime whether the queue is still alive.  `spin` is the caller's spin count of THIS wait.
-inline bool spin_stalled(long spin) {
-  thread_local std::chrono::steady_clock::time_point t_last;
-  const auto now = std::chrono::steady_clock::now();
-  if (spin <= 0x4000) { t_last = now; return false; }   // first check of this wait (the callers ask every 0x4000 spins): start the clock
-  if (now - t_last < std::chrono::milliseconds(20)) return false;
-  t_last = now;
-  return true;
+// The host loops that spin on a report in pinned memory wait with ReportWait (lrnde_report.hpp); this is its query.  The
+// loops spin while the queue says "not ready", which a hung queue says for ever: after LRNDE_SPIN_DEADLINE_S of one wait
+// the call fails, the handle is marked (check_ready refuses it) and nothing is restarted in place.
+inline int queue_state(hipStream_t s) {
+  const hipError_t q = hipStreamQuery(s);
+  return q == hipSuccess ? QUERY_DRAINED : (q == hipErrorNotReady ? QUERY_NOT_READY : (int)q);
 }
-
-// ... and the bound on such a wait: the loops spin while hipStreamQuery says "not ready", which a hung queue says for ever.
-// After LRNDE_SPIN_DEADLINE_S of one wait the call fails, the handle is marked (check_ready refuses it) and nothing is
-// restarted in place.
-constexpr int LRNDE_SPIN_DEADLINE_S = 90;  // (above the local communicator's 60-s rendezvous timeout)
-struct SpinDeadline {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  void restart() { t0 = std::chrono::steady_clock::now(); }
-  bool expired() const { return std::chrono::steady_clock::now() - t0 > std::chrono::seconds(LRNDE_SPIN_DEADLINE_S); }
-};
 #define LRNDE_HUNG(c, what) ((c)->hung = true, fail((c), LRNDE_HIP_ERROR, "%s: no report for %d s while the queue stayed busy (hung queue); destroy the handle", (what), LRNDE_SPIN_DEADLINE_S))
 
 // a batch-sharded handle: its collectives run (RCCL or the in-process local communicator, lrnde_comm.hpp)
@@ -2623,22 +2610,15 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
   bool done = false, word_ok = !c->reports_off;
   const long hard_cap = (long)o->maxiters + 8;
   if (word_ok) {
-    // Report-driven feed: after the report of launch `seen - 1` keep enqueued what it says is still to come at the current
-    // dt (an over-estimate while dt grows, exact for the last step, whose dt is clipped to t1 - t), the launch that will find
-    // the solve finished, and never fewer than two launches beyond the reporting one — so the stream neither runs dry nor
-    // ends with a tail of launches that have nothing to do.
+    // Report-driven feed: after the report of launch `seen - 1` keep enqueued what feed_rule makes of the steps it says
+    // are still to come at the current dt (an over-estimate while dt grows, exact for the last step, whose dt is clipped to
+    // t1 - t) — so the stream neither runs dry nor ends with a tail of launches that have nothing to do: every launch
+    // enqueued beyond the real end is a 6-us launch, seven of them per pass on the MNIST field before the rule.
     int seen = 0, rem = 3;
     while (!done) {
-      // (rem + 1 is exact when dt stays put; while the controller still grows dt the estimate is high and every launch
-      //  enqueued on its strength beyond the real end is a 6-us launch with nothing to do — seven of them per pass on the
-      //  MNIST field.  Far from the end half the estimate plus two keeps the queue two launches deep at the least.)
-      const int fT = opt(OPT_FEED_T), fE = opt(OPT_FEED_E), fM = opt(OPT_FEED_M);
-      int ahead = rem <= fT ? rem + fE : rem / 2 + fE + 1;
-      if (ahead < fM) ahead = fM;
-      if (ahead > 16) ahead = 16;
-      const int certain = seen + (rem > 1 ? rem / 2 : 1);  // launches beyond it carry the speculative kernel name
-      for (const int want = seen + ahead; j < want; ++j) {
-        if ((rc = launch_step(c, B, a, j, j >= certain))) return rc;
+      const Feed feed = feed_rule(rem, seen, opt(OPT_FEED_T), opt(OPT_FEED_E), opt(OPT_FEED_M));
+      for (const int want = seen + feed.ahead; j < want; ++j) {
+        if ((rc = launch_step(c, B, a, j, j >= feed.certain))) return rc;
         ++launches;
         const size_t par = (size_t)((j + 1) & 1);
         if ((rc = exchange(c, c->part + par * cnt, c->part_rx + par * cnt, cnt))) return rc;
@@ -2646,29 +2626,14 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
       if (j > hard_cap + 64) break;
       // the report of launch `seen` (it carries seen + 1 as its launch count)
       volatile unsigned long long* slot = pw + (seen & (PROG_RING - 1));
-      unsigned long long w = *slot;
-      const SpinDeadline deadline;
-      for (long spin = 1; (int)(w & 0xffffffull) != seen + 1; ++spin) {
-        // bounded: a faulted queue must not hang the caller.  The query is kept for a report that is LATE (the runtime
-        // answers it by putting a marker packet into the queue: asked every few thousand spins, one landed between two
-        // steps whenever the queue was only a launch or two deep — a 6-us bubble each, five per pass at the end of a solve)
-        if ((spin & 0x3fff) == 0 && spin_stalled(spin)) {
-          const hipError_t qe = hipStreamQuery(c->stream);
-          if (qe != hipSuccess && qe != hipErrorNotReady) return fail(c, LRNDE_HIP_ERROR, "solve loop: %s", hipGetErrorString(qe));
-          if (qe == hipErrorNotReady && deadline.expired()) return LRNDE_HUNG(c, "solve loop");
-          if (qe == hipSuccess) {
-            w = *slot;
-            if ((int)(w & 0xffffffull) != seen + 1) word_ok = false;  // the stream drained and no report came: poll by copies
-            break;
-          }
-        }
-        w = *slot;
-      }
-      if (!word_ok) break;
-      ++seen;
-      rem = (int)((w >> 48) & 0xffff);
-      if (c->poll_hook && (rc = c->poll_hook((int)((w >> 32) & 0xffff), nullptr))) return rc;
-      if ((int)((w >> 24) & 0xff) != (ST_RUNNING & 0xff)) done = true;
+      SolveReport r{}; ReportWait<> wait(WAIT_PER_LAUNCH);
+      const WaitResult wr = wait.await([&] { r = solve_report_unpack(*slot); return r.launches == seen + 1; }, [&] { return queue_state(c->stream); });
+      if (wr == WAIT_QUEUE_ERROR) return fail(c, LRNDE_HIP_ERROR, "solve loop: %s", hipGetErrorString((hipError_t)wait.code));
+      if (wr == WAIT_HUNG) return LRNDE_HUNG(c, "solve loop");
+      if (wr == WAIT_DRAINED) { word_ok = false; break; }  // the stream drained and no report came: poll by copies
+      ++seen; rem = r.rem;
+      if (c->poll_hook && (rc = c->poll_hook(r.nsaved, nullptr))) return rc;
+      if (r.status != ST_RUNNING) done = true;
     }
     target = j;
   }
@@ -3469,18 +3434,12 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
     }
     HIPCHK(c, hipGetLastError());
     const unsigned want = (unsigned)(j - 4);
-    const SpinDeadline deadline;
-    for (long spin = 1;; ++spin) {
-      const unsigned long long w = *pw;
-      if ((unsigned)(w >> 32) != (unsigned)ST_RUNNING) { done = true; break; }
-      if ((unsigned)(w & 0xffffffffull) >= want) break;
-      if ((spin & 0x3fff) == 0 && spin_stalled(spin)) {  // (a stream query is a marker packet in the queue: only when the report is late)
-        const hipError_t qe = hipStreamQuery(c->stream);
-        if (qe != hipSuccess && qe != hipErrorNotReady) return fail(c, LRNDE_HIP_ERROR, "adaptive SDE loop: %s", hipGetErrorString(qe));
-        if (qe == hipErrorNotReady && deadline.expired()) return LRNDE_HUNG(c, "adaptive SDE loop");
-        if (qe == hipSuccess) break;  // everything enqueued has run: look at the word again, enqueue more
-      }
-    }
+    ReportWait<> wait(WAIT_PER_LAUNCH);
+    const WaitResult wr = wait.await([&] { const SdeReport r = sde_report_unpack(*pw); done = r.status != (unsigned)ST_RUNNING; return done || r.count >= want; },
+                                     [&] { return queue_state(c->stream); });
+    // (ready, or drained: everything enqueued has run — the loop looks at `done` and enqueues more)
+    if (wr == WAIT_QUEUE_ERROR) return fail(c, LRNDE_HIP_ERROR, "adaptive SDE loop: %s", hipGetErrorString((hipError_t)wait.code));
+    if (wr == WAIT_HUNG) return LRNDE_HUNG(c, "adaptive SDE loop");
   }
   // one synchronisation ends the solve: the control block, the end state (picked on the device) and the record's
   // (start, length) pairs are all enqueued before it
@@ -3498,7 +3457,7 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
     memcpy(rec_im_host, s->ad_ctl_host + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
   st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iters; st->nf = fin.nf; st->eest_last = fin.eest_last;
   st->t_final = t0 + (float)fin.i * h; st->dt_final = (float)fin.m * h;
-  st->retcode = (fin.status == ST_DONE) ? LRNDE_OK : (fin.status == ST_RUNNING ? LRNDE_MAXITERS : fin.status);
+  st->retcode = status_retcode(fin.status);
   if (trace_host) {
     int nt = fin.naccept + fin.nreject;
     if (nt > cap_trace) nt = cap_trace;
@@ -4190,6 +4149,51 @@ int adj_norm_into(lrnde_ctx* c, const float* num, const float* num2, const float
   return adj_enqueue_slots(c, part);
 }
 
+// ---- what the two device-controlled adjoint drivers share (the report itself: lrnde_report.hpp) ----
+int adj_report_block(lrnde_ctx* c) {
+  if (c->adj_hstat) return LRNDE_OK;
+  HIPCHK(c, c->adj_hstat.once(ADJ_R_LEN, hipHostMallocMapped));
+  memset(c->adj_hstat, 0, sizeof(int) * ADJ_R_LEN);
+  return LRNDE_OK;
+}
+// the caller's side enqueues, once: the first attempt is enqueued and the handle's stream holds ~150 us of work
+int adj_after_first_attempt(lrnde_ctx* c) {
+  if (!c->after_first_attempt) return LRNDE_OK;
+  auto fn = std::move(c->after_first_attempt);
+  c->after_first_attempt = nullptr;
+  return fn();
+}
+// Await the report of attempt j - 1's first launch (seq0 + j): bounded, a faulted or hung queue must not hang the caller.
+// bail: the driver's early exit (nothing of it stays in flight, its sequence numbers retired).  A hung queue cannot be
+// synchronised: the numbers are retired and the handle is marked.  Then the trace row of the attempt, and *r.
+template <class Bail> int adj_await_report(lrnde_ctx* c, const char* what, int seq0, int j, Bail&& bail, AdjTraceCursor& tk, AdjReport* r) {
+  volatile int* hs = c->adj_hstat;
+  ReportWait<> wait(WAIT_PER_ATTEMPT);
+  const WaitResult wr = wait.await([&] { return (int)(__atomic_load_n(hs + ADJ_R_SEQ, __ATOMIC_ACQUIRE) - (seq0 + j)) >= 0; }, [&] { return queue_state(c->stream); });
+  if (wr == WAIT_DRAINED) return bail(fail(c, LRNDE_HIP_ERROR, "%s: the stream drained without the status of attempt %d", what, j - 1));
+  if (wr == WAIT_QUEUE_ERROR) return bail(fail(c, LRNDE_HIP_ERROR, "%s: %s", what, hipGetErrorString((hipError_t)wait.code)));
+  if (wr == WAIT_HUNG) { c->adj_seq += j + 1; return LRNDE_HUNG(c, what); }
+  *r = adj_report_read(hs);
+  if (c->adj_trace) adj_trace_report(tk, j, *r, c->adj_trace, c->adj_trace_n, c->adj_trace_cap);
+  return LRNDE_OK;
+}
+// a control block read back (the launch cap was reached with the solve still running) as the report it would have made
+AdjReport adj_report_of(const AdjCtrl& k) { return {k.status, k.t, k.dt, k.cur, k.nf, k.naccept, k.nreject, k.iter, k.eest_last, k.dt_init, 0}; }
+// The end of either solve from its final state: the stats; the end state zb[cur], to which the cotangents at the end
+// time itself (a saved start value) are added; nothing of a failed solve is left in flight.
+int adj_finish(lrnde_ctx* c, AdjVec& v, const AdjReport& fin, int extra_nf, const std::vector<const float*>& at_end, lrnde_stats* st) {
+  adj_stats_fill(fin, extra_nf, st);
+  float* zend = c->adj + (size_t)fin.cur * v.N;
+  if (st->retcode == LRNDE_OK)
+    for (const float* du : at_end) {
+      const float* gi[1] = {du}; const float one = 1.0f;
+      if (const int rc = vec_axpy(c, zend, zend, 1.0f, 1, gi, &one, v.n_lam)) return rc;
+    }
+  v.z = zend;  // (the caller copies dx / dp out of it; no move to the first buffer)
+  if (st->retcode != LRNDE_OK) hipStreamSynchronize(c->stream);
+  return st->retcode;
+}
+
 int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float abstol, float reltol, int maxiters, int exact_pow,
                      const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st) {
   int rc;
@@ -4201,10 +4205,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
   HIPCHK(c, c->adj_ipart.once(3 * 576));
   HIPCHK(c, c->adj_ev[0].create(hipEventDisableTiming));
   HIPCHK(c, c->adj_ev[1].create(hipEventDisableTiming));
-  if (!c->adj_hstat) {
-    HIPCHK(c, c->adj_hstat.once(16, hipHostMallocMapped));
-    memset(c->adj_hstat, 0, sizeof(int) * 16);
-  }
+  if ((rc = adj_report_block(c))) return rc;
   if (tstops.size() > c->adj_stops.size()) HIPCHK(c, c->adj_stops.grow(tstops.size() + 8));
   const bool one_begin = c->adj_init_src != nullptr && tstops.size() <= 8;
   if (!tstops.empty() && !one_begin)
@@ -4244,7 +4245,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     HIPCHK(c, hipMemsetAsync(c->adj_sync, 0, sizeof(int) * 32, c->stream));
     g.sync = c->adj_sync;
     c->adj_launch_id = 0;
-    c->adj_hstat[11] = 0;   // (the prologue copies sync[1], the timeout word, here)
+    c->adj_hstat[ADJ_R_OVL_TIMEOUT] = 0;   // (the prologue copies sync[1], the timeout word, here)
   }
   hipStream_t const sA = c->stream, sB = ovl_on ? c->adj_stream2 : c->stream;
   const size_t N = v.N, n = v.n_lam;
@@ -4276,8 +4277,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
   while (iseg < impulses.size() && impulses[iseg].s <= s0) ++iseg;  // a cotangent at the start time is the caller's lambda(s0)
   bool first_seg = true;
   int extra_nf = 0;
-  AdjCtrl fin;
-  memset(&fin, 0, sizeof(fin));
+  AdjReport fin{};
   for (;;) {
     const bool last_seg = iseg >= impulses.size() || !(impulses[iseg].s < s1);
     g.s1 = last_seg ? s1 : impulses[iseg].s;
@@ -4300,7 +4300,6 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     // to be running (its remaining seven launches, ~130 us, cover the host's enqueue); no copy packet sits between the
     // kernels, and an attempt that would end the segment is followed by the next one's first launch only (maybe_last).
     g.hstat = c->adj_hstat.dev(); g.seq0 = c->adj_seq;
-    volatile int* hs = c->adj_hstat;
     int j = 0;
     bool done = false;
     // every early exit of this segment: nothing of it stays in flight, and the sequence numbers its launches may still have
@@ -4317,7 +4316,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     // once the report says the solve goes on (a rejection: the stream idles for one host round trip) — otherwise the
     // solve would always end with eight launches that find nothing to do.
     bool maybe_last = false;
-    int trace_prev = -1, trace_nacc = 0;
+    AdjTraceCursor trace;
     auto enqueue_rest = [&](int jj) -> int {
       if (ovl_on) HIPCHK(c, hipStreamWaitEvent(sB, c->adj_evA[jj & 1], 0));   // (recorded on the handle's stream ahead of this attempt's stage 2)
       for (int sidx = 3; sidx <= 7; ++sidx) {
@@ -4350,58 +4349,24 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
       if ((rc = adj_enqueue_eval(c, B, g, ADJ_STAGE, 2, j, false, ADJ_STAGE, 1, sA, 0))) return bail(rc);
       const bool rest_ahead = !maybe_last;
       if (rest_ahead && (rc = enqueue_rest(j))) return bail(rc);
-      if (c->after_first_attempt) {  // (the handle's stream now holds ~150 us of work: time for the caller's side enqueues)
-        auto fn = std::move(c->after_first_attempt);
-        c->after_first_attempt = nullptr;
-        if ((rc = fn())) return bail(rc);
-      }
+      if ((rc = adj_after_first_attempt(c))) return bail(rc);
       ++j;
-      // wait for the prologue of the attempt just enqueued (bounded: a faulted or hung queue must not hang the caller)
-      const int want = g.seq0 + j;
-      long spins = 0;
-      const SpinDeadline deadline;
-      while ((int)(__atomic_load_n(hs, __ATOMIC_ACQUIRE) - want) < 0) {
-        if (((++spins) & 0xFFFFF) == 0) {
-          const hipError_t q = hipStreamQuery(c->stream);
-          if (q != hipSuccess && q != hipErrorNotReady) return bail(fail(c, LRNDE_HIP_ERROR, "adjoint loop: %s", hipGetErrorString(q)));
-          if (q == hipSuccess && (int)(__atomic_load_n(hs, __ATOMIC_ACQUIRE) - want) < 0)
-            return bail(fail(c, LRNDE_HIP_ERROR, "adjoint loop: the stream drained without the status of attempt %d", j - 1));
-          if (q == hipErrorNotReady && deadline.expired()) { c->adj_seq += j + 1; return LRNDE_HUNG(c, "adjoint loop"); }
-        }
-      }
-      if (c->adj_trace) {
-        // the report of attempt j-1's prologue: its (s, dt), and the error estimate / decision of the attempt before it
-        if (j > 1 && trace_prev >= 0) {
-          lrnde_trace_row& r = c->adj_trace[trace_prev];
-          r.eest = __builtin_bit_cast(float, (int)hs[9]); r.accepted = (hs[6] > trace_nacc);
-        }
-        trace_prev = -1; trace_nacc = hs[6];
-        if (hs[1] == ST_RUNNING && c->adj_trace_n < c->adj_trace_cap) {
-          trace_prev = c->adj_trace_n++;
-          lrnde_trace_row& r = c->adj_trace[trace_prev];
-          r.t = __builtin_bit_cast(float, (int)hs[2]); r.dt = __builtin_bit_cast(float, (int)hs[3]); r.eest = 0.f; r.accepted = -1;
-        }
-      }
-      if (hs[1] != ST_RUNNING) done = true;
+      if ((rc = adj_await_report(c, "adjoint loop", g.seq0, j, bail, trace, &fin))) return rc;
+      if (fin.status != ST_RUNNING) done = true;
       else {
         if (!rest_ahead && (rc = enqueue_rest(j - 1))) return bail(rc);
-        const float te = __builtin_bit_cast(float, (int)hs[2]) + __builtin_bit_cast(float, (int)hs[3]);
-        maybe_last = fabsf(te - g.s1) <= 100.0f * eps_f(fmaxf(fabsf(te), fabsf(g.s1)));
+        maybe_last = adj_maybe_last(fin.t, fin.dt, g.s1);
       }
       if (j > maxiters + 16) break;
     }
     c->adj_seq += j;
-    if (ovl_on && hs[11]) return bail(fail(c, LRNDE_HIP_ERROR, "adjoint loop: a wait between overlapped stage launches timed out"));
-    if (done) {
-      // the report of the last attempt's prologue carries the integrator's final state (adj_hstat_fill): no read-back
-      // copy on the stream, no synchronisation here — the caller's own, after its output copies, is the only one
-      fin.status = hs[1]; fin.t = __builtin_bit_cast(float, (int)hs[2]); fin.dt = __builtin_bit_cast(float, (int)hs[3]);
-      fin.cur = hs[4]; fin.nf = hs[5]; fin.naccept = hs[6]; fin.nreject = hs[7]; fin.iter = hs[8];
-      fin.eest_last = __builtin_bit_cast(float, (int)hs[9]); fin.dt_init = __builtin_bit_cast(float, (int)hs[10]);
-    } else {  // launch cap reached with the solve still running
+    if (ovl_on && c->adj_hstat[ADJ_R_OVL_TIMEOUT]) return bail(fail(c, LRNDE_HIP_ERROR, "adjoint loop: a wait between overlapped stage launches timed out"));
+    // the report of the last attempt's prologue (fin) carries the integrator's final state: no read-back copy on the
+    // stream, no synchronisation here — the caller's own, after its output copies, is the only one
+    if (!done) {  // launch cap reached with the solve still running
       HIPCHK(c, hipMemcpyAsync(c->adj_ctl_host, c->adj_ctl + (j & 1), sizeof(AdjCtrl), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      fin = c->adj_ctl_host[0];
+      fin = adj_report_of(c->adj_ctl_host[0]);
     }
     if (fin.status != ST_DONE) break;  // error status (or still running after the launch cap: MaxIters)
     if (last_seg) break;
@@ -4414,19 +4379,9 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
     hipLaunchKernelGGL(k_adj_ctrl_continue, dim3(1), dim3(1), 0, c->stream, c->adj_ctl, j & 1);
     ++c->adj_launches;
   }
-  st->retcode = (fin.status == ST_DONE) ? LRNDE_OK : (fin.status == ST_RUNNING ? LRNDE_MAXITERS : fin.status);
-  st->nf = fin.nf + extra_nf; st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iter;
-  st->t_final = fin.t; st->dt_final = fin.dt; st->eest_last = fin.eest_last; st->dt_init = fin.dt_init;
-  // the end state is zb[cur]; cotangents at the end time itself (a saved start value) are added to it
-  float* zend = c->adj + (size_t)fin.cur * N;
-  if (st->retcode == LRNDE_OK)
-    for (; iseg < impulses.size(); ++iseg) {
-      const float* gi[1] = {impulses[iseg].du}; const float one = 1.0f;
-      if ((rc = vec_axpy(c, zend, zend, 1.0f, 1, gi, &one, n))) return rc;
-    }
-  v.z = zend;  // (the caller copies dx / dp out of it; no move to the first buffer)
-  if (st->retcode != LRNDE_OK) hipStreamSynchronize(c->stream);  // nothing of a failed solve is left in flight
-  return st->retcode;
+  std::vector<const float*> at_end;
+  for (; iseg < impulses.size(); ++iseg) at_end.push_back(impulses[iseg].du);
+  return adj_finish(c, v, fin, extra_nf, at_end, st);
 }
 
 // ---- the chain handle's adjoint solve with the controller on the device (lrnde_chain_adjoint.hpp) -----------------
@@ -4463,10 +4418,7 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
   const size_t P = v.P, N = v.N, n = v.n_lam;
   const int np = pl.nwg + pl.nmu;
   HIPCHK(c, c->cha_ctl.once(2));
-  if (!c->adj_hstat) {
-    HIPCHK(c, c->adj_hstat.once(16, hipHostMallocMapped));
-    memset(c->adj_hstat, 0, sizeof(int) * 16);
-  }
+  if ((rc = adj_report_block(c))) return rc;
   HIPCHK(c, c->cha_gpart.grow(7 * (size_t)pl.nwg * P));
   HIPCHK(c, c->cha_dpart.grow(5 * (size_t)np));
   // impulses strictly inside (s0, s1) go to the device table; those at the end time are added after the solve (a cotangent
@@ -4522,7 +4474,6 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
   if ((rc = enqueue(0, CHADJ_INIT_B))) return rc;
   // Attempts are enqueued ONE ahead of what the device has decided (adj_solve_device's scheme): the step launch of
   // attempt j publishes the integrator's state in pinned host memory, and attempt j + 1 is enqueued while attempt j runs.
-  volatile int* hs = c->adj_hstat;
   int j = 0;
   bool done = false;
   // every early exit: nothing stays in flight, and the sequence numbers the launches may still have written are retired
@@ -4532,67 +4483,23 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
     c->after_first_attempt = nullptr;
     return code;
   };
-  int trace_prev = -1, trace_nacc = 0;
+  AdjTraceCursor trace;
+  AdjReport fin{};
   while (!done) {
     if ((rc = enqueue(j, CHADJ_STEP))) return bail(rc);
-    if (c->after_first_attempt) {
-      auto fn = std::move(c->after_first_attempt);
-      c->after_first_attempt = nullptr;
-      if ((rc = fn())) return bail(rc);
-    }
+    if ((rc = adj_after_first_attempt(c))) return bail(rc);
     ++j;
-    const int want = g.seq0 + j;
-    long spins = 0;
-    const SpinDeadline deadline;
-    while ((int)(__atomic_load_n(hs, __ATOMIC_ACQUIRE) - want) < 0) {
-      if (((++spins) & 0xFFFFF) == 0) {
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return bail(fail(c, LRNDE_HIP_ERROR, "chain adjoint loop: %s", hipGetErrorString(q)));
-        if (q == hipSuccess && (int)(__atomic_load_n(hs, __ATOMIC_ACQUIRE) - want) < 0)
-          return bail(fail(c, LRNDE_HIP_ERROR, "chain adjoint loop: the stream drained without the status of attempt %d", j - 1));
-        if (q == hipErrorNotReady && deadline.expired()) { c->adj_seq += j + 1; return LRNDE_HUNG(c, "chain adjoint loop"); }
-      }
-    }
-    if (c->adj_trace) {
-      // the report of attempt j-1's prologue: its (s, dt), and the error estimate / decision of the attempt before it
-      if (j > 1 && trace_prev >= 0) {
-        lrnde_trace_row& r = c->adj_trace[trace_prev];
-        r.eest = __builtin_bit_cast(float, (int)hs[9]); r.accepted = (hs[6] > trace_nacc);
-      }
-      trace_prev = -1; trace_nacc = hs[6];
-      if (hs[1] == ST_RUNNING && c->adj_trace_n < c->adj_trace_cap) {
-        trace_prev = c->adj_trace_n++;
-        lrnde_trace_row& r = c->adj_trace[trace_prev];
-        r.t = __builtin_bit_cast(float, (int)hs[2]); r.dt = __builtin_bit_cast(float, (int)hs[3]); r.eest = 0.f; r.accepted = -1;
-      }
-    }
-    if (hs[1] != ST_RUNNING) done = true;
+    if ((rc = adj_await_report(c, "chain adjoint loop", g.seq0, j, bail, trace, &fin))) return rc;
+    if (fin.status != ST_RUNNING) done = true;
     if (j > maxiters + 16) break;
   }
   c->adj_seq += j;
-  AdjCtrl fin;
-  memset(&fin, 0, sizeof(fin));
-  if (done) {
-    fin.status = hs[1]; fin.t = __builtin_bit_cast(float, (int)hs[2]); fin.dt = __builtin_bit_cast(float, (int)hs[3]);
-    fin.cur = hs[4]; fin.nf = hs[5]; fin.naccept = hs[6]; fin.nreject = hs[7]; fin.iter = hs[8];
-    fin.eest_last = __builtin_bit_cast(float, (int)hs[9]); fin.dt_init = __builtin_bit_cast(float, (int)hs[10]);
-  } else {  // launch cap reached with the solve still running
+  if (!done) {  // launch cap reached with the solve still running
     ChAdjCtrl hc;
     HIPCHK(c, hipMemcpy(&hc, c->cha_ctl + (j & 1), sizeof(ChAdjCtrl), hipMemcpyDeviceToHost));
-    fin = hc.c;
+    fin = adj_report_of(hc.c);
   }
-  st->retcode = (fin.status == ST_DONE) ? LRNDE_OK : (fin.status == ST_RUNNING ? LRNDE_MAXITERS : fin.status);
-  st->nf = fin.nf; st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iter;
-  st->t_final = fin.t; st->dt_final = fin.dt; st->eest_last = fin.eest_last; st->dt_init = fin.dt_init;
-  float* zend = c->adj + (size_t)fin.cur * N;
-  if (st->retcode == LRNDE_OK)
-    for (const float* du : at_end) {
-      const float* gi[1] = {du}; const float one = 1.0f;
-      if ((rc = vec_axpy(c, zend, zend, 1.0f, 1, gi, &one, n))) return rc;
-    }
-  v.z = zend;
-  if (st->retcode != LRNDE_OK) hipStreamSynchronize(c->stream);  // nothing of a failed solve is left in flight
-  return st->retcode;
+  return adj_finish(c, v, fin, 0, at_end, st);
 }
 
 }  // namespace

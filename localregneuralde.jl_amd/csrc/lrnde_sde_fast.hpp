@@ -65,7 +65,7 @@ struct SdeFastArgs {
   struct SdeCtl* ctl; const float* Wpath; float* ua; float* ub; int nfine; float t0, h;
   float gamma, qmin, qmax, beta1, beta2; int maxiters;
   lrnde_trace_row* trace; int cap_trace;
-  unsigned long long* prog;  // pinned host word: (launches whose footer ran) | status << 32
+  unsigned long long* prog;  // pinned host word: sde_report_pack(launches whose footer ran, status)
   int jlaunch;
   // the layer's recorded forward: end state of accepted step k -> rec_u[k] (slot = accepted steps so far; a rejected
   // attempt's slot is rewritten by the retry), its (i, m) -> rec_im[k]
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
       if (live) st4s(cc.cur ? a.ub : a.ua, u4);
       if (blockIdx.x == 0 && threadIdx.x == 0) {
         *a.ctl = cc;
-        __hip_atomic_store(a.prog, (unsigned long long)(unsigned)(it + 1) | ((unsigned long long)(unsigned)cc.status << 32),
+        __hip_atomic_store(a.prog, sde_report_pack((unsigned)(it + 1), (unsigned)cc.status),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
       return;
@@ -537,7 +537,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
         SdeCtl c = *a.ctl;
         sde_ctl_update(c, eest, dt, a, true, fastpow(c.qold, a.beta2), 3);
         *a.ctl = c;
-        __hip_atomic_store(a.prog, (unsigned long long)(unsigned)(a.jlaunch + 1) | ((unsigned long long)(unsigned)c.status << 32),
+        __hip_atomic_store(a.prog, sde_report_pack((unsigned)(a.jlaunch + 1), (unsigned)c.status),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
       __hip_atomic_store(a.arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_mil_fast(SdeFastArgs a) {
     SdeCtl c = *a.ctl;
     sde_ctl_update(c, eest, dt, a, true, fastpow(c.qold, a.beta2), 1);
     *a.ctl = c;
-    __hip_atomic_store(a.prog, (unsigned long long)(unsigned)(a.jlaunch + 1) | ((unsigned long long)(unsigned)c.status << 32),
+    __hip_atomic_store(a.prog, sde_report_pack((unsigned)(a.jlaunch + 1), (unsigned)c.status),
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(a.arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
