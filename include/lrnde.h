@@ -344,7 +344,9 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
  * head: Chain(Conv((3,3), 8=>1, gelu; pad=1), FlattenLayer(), Dense(H*W=>K)) + logitcrossentropy
  * (experiments/src/utils.jl:88); ph (device) = [conv.weight 3x3x8x1; conv.bias 1; dense.weight K x H*W column-major;
  * dense.bias K]; returns the mean loss on the host and, where non-NULL, logits (B,K), du (B,8,H,W), dph.
- * H, W are the handle's image size.  Run once per batch: simple direct kernels. */
+ * H, W are the handle's image size.  labels: device int32 (B), 0-based; a label outside [0, K) fails the call with
+ * LRNDE_BADARG ("a label is outside [0, K)" in lrnde_conv_last_error, as lrnde_classifier_ce) and *loss_host is left
+ * alone: whatever the device arrays then hold is not a result.  Run once per batch: simple direct kernels. */
 size_t lrnde_cifar_stem_param_count(void);
 size_t lrnde_cifar_head_param_count(int32_t H, int32_t W, int32_t K);
 int lrnde_cifar_stem_forward(lrnde_conv* c, const float* x, int32_t B, const float* ps, const float* bn_state, float* u0,

@@ -1,8 +1,10 @@
 // lrnde_cls.hpp — Dense(D => K) + logitcrossentropy kernels (experiments/src/construct.jl:199, utils.jl:88), included
 // inside the anonymous namespace of both translation units (MNIST head on the MLP handle, CIFAR head on the conv one).
 // one wave per sample: logits[c] = sum_k W[c][k] u[k] + b[c] (fixed lane-strided order, butterfly reduce)
+// a label outside [0, K) sets *bad_label (the caller zeroes it and refuses the call) and is treated as 0: lg[] is a
+// 16-entry private array, the label must not index it unchecked
 __global__ __launch_bounds__(256) void k_cls_fwd(const float* u, const float* pc, const int32_t* labels, int B, int D, int K,
-                                                 float* logits, float* dl, float* loss_b) {
+                                                 float* logits, float* dl, float* loss_b, int32_t* bad_label) {
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const float* ub = u + (size_t)b * D;
@@ -31,8 +33,11 @@ __global__ __launch_bounds__(256) void k_cls_fwd(const float* u, const float* pc
   float se = 0.f;
   for (int c = 0; c < K; ++c) se += expf_c(lg[c] - mx);
   const float lse = mx + logf(se);
-  const int y = labels[b];
+  int y = labels[b];
+  const bool bad = y < 0 || y >= K;
+  if (bad) y = 0;
   if (lane == 0) {
+    if (bad) atomicExch(bad_label, 1);
     for (int c = 0; c < K; ++c) {
       if (logits) logits[(size_t)b * K + c] = lg[c];
       const float sm = expf_c(lg[c] - lse);

@@ -2942,9 +2942,11 @@ int lrnde_cifar_head_ce(lrnde_conv* c, const float* u, int32_t B, const float* p
   const float* pd = ph + 73;
   DevBuf<float> z, v, dl, lb, dv, partw;
   CHK(c, z.once(npx)); CHK(c, v.once(npx)); CHK(c, dl.once((size_t)B * K));
-  CHK(c, lb.once(B)); CHK(c, dv.once(npx)); CHK(c, partw.once((size_t)nblk * 73));
+  CHK(c, lb.once((size_t)B + 1)); CHK(c, dv.once(npx)); CHK(c, partw.once((size_t)nblk * 73));   // (lb[B]: the bad-label flag, read back with the losses)
   hipLaunchKernelGGL(k_head_conv, dim3(nblk), dim3(SH_T), 0, c->stream, u, ph, B, H, W, z, v);
-  hipLaunchKernelGGL(k_cls_fwd, dim3((B + 3) / 4), dim3(256), 0, c->stream, (const float*)v, pd, labels, B, D, K, logits, dl, lb);
+  int32_t* bad = reinterpret_cast<int32_t*>(lb + B);
+  CHK(c, hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_cls_fwd, dim3((B + 3) / 4), dim3(256), 0, c->stream, (const float*)v, pd, labels, B, D, K, logits, dl, lb, bad);
   if (du || dph) {
     hipLaunchKernelGGL(k_cls_bwd_x, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, (const float*)dl, pd, B, D, K, dv);
     if (dph) hipLaunchKernelGGL(k_cls_bwd_w, dim3((K * (D + 1) + 255) / 256), dim3(256), 0, c->stream, (const float*)dl, (const float*)v, B, D, K, dph + 73);
@@ -2952,10 +2954,13 @@ int lrnde_cifar_head_ce(lrnde_conv* c, const float* u, int32_t B, const float* p
     hipLaunchKernelGGL(k_head_bwd, dim3(nblk), dim3(SH_T), 0, c->stream, u, (const float*)dv, ph, B, H, W, du, dph ? partw : (float*)nullptr);
     if (dph) hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const float*)partw, nblk, 73, dph);
   }
-  std::vector<float> hl(B);
-  hipError_t e = hipMemcpyAsync(hl.data(), lb, sizeof(float) * B, hipMemcpyDeviceToHost, c->stream);
+  std::vector<float> hl((size_t)B + 1);
+  hipError_t e = hipMemcpyAsync(hl.data(), lb, sizeof(float) * ((size_t)B + 1), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "head kernels failed: %s", hipGetErrorString(e));
+  int32_t bad_host;
+  memcpy(&bad_host, &hl[B], sizeof(bad_host));
+  if (bad_host) return cfail(c, LRNDE_BADARG, "a label is outside [0, %d)", K);
   double acc = 0.0;
   for (int b = 0; b < B; ++b) acc += (double)hl[b];
   *loss_host = (float)(acc / (double)B);

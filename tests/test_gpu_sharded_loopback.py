@@ -121,8 +121,10 @@ def _rel(a, b):
     return np.linalg.norm(a.astype(np.float64) - b.astype(np.float64)) / max(np.linalg.norm(b.astype(np.float64)), 1e-300)
 
 
-@pytest.mark.parametrize("nranks,Bl,gather", [(2, 48, False), (2, 48, True), (2, 512, False)])
-def test_sharded_backward_and_training_step(gpu_pkg, nranks, Bl, gather):
+# (the cases at K = 10, the compile-time form of the head, keep the ids they had; K = 7 runs the runtime-K form on the shards)
+@pytest.mark.parametrize("nranks,Bl,gather,K", [pytest.param(*c, K, id="-".join(map(str, c)) + ("" if K == 10 else f"-K{K}"))
+                                                for K in (10, 7) for c in [(2, 48, False), (2, 48, True), (2, 512, False)]])
+def test_sharded_backward_and_training_step(gpu_pkg, nranks, Bl, gather, K):
     """pullback of <g, sol.u[end]> + w_reg*reg_val on R shards: dx is the unsharded dx's block, dp (replicated) its dp —
     2e-4 of the norm: mu is summed over the batch per rank and then over ranks, the error norm adds one fp64 sum per rank;
     the adjoint takes the same number of steps.  Then the classifier head: loss and dpc of the GLOBAL mean loss."""
@@ -150,7 +152,6 @@ def test_sharded_backward_and_training_step(gpu_pkg, nranks, Bl, gather):
         assert _rel(q["dp"].cpu().numpy(), ref["dp"].cpu().numpy()) < 2e-4
         assert np.array_equal(q["dp"].cpu().numpy(), got[0]["dp"].cpu().numpy()), "dp must come out replicated"
     # classifier + logitcrossentropy on the shards: the mean over the global batch
-    K = 10
     rng = np.random.default_rng(7)
     pc = torch.from_numpy((rng.random(K * (D + 1), dtype=np.float32) - np.float32(0.5)) * np.float32(0.1)).cuda()
     labels = rng.integers(0, K, B).astype(np.int32)

@@ -11,9 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import oracle as O  # noqa: E402
 
-
-def _gelu(z):
-    return 0.5 * z * (1.0 + torch.tanh(np.sqrt(2.0 / np.pi) * (z + 0.044715 * z ** 3)))
+import head_cases as HC  # noqa: E402
 
 
 @pytest.mark.parametrize("train", [True, False])
@@ -75,15 +73,8 @@ def test_head_matches_torch():
     ph = (rng.standard_normal(n) * 0.2).astype(np.float32)
     lab = rng.integers(0, K, B)
     loss, logits, du, dph = O.cifar_head_ce(u, ph, K, lab)
-    pt = torch.tensor(ph.astype(np.float64), requires_grad=True)
-    ut = torch.tensor(u.astype(np.float64), requires_grad=True)
-    w = torch.flip(pt[:72].reshape(1, 8, 3, 3), dims=(2, 3))
-    v = _gelu(torch.nn.functional.conv2d(ut, w, bias=pt[72:73], padding=1)).reshape(B, H * W)  # Julia flatten of (W,H,1,B): w fastest
-    Wd = pt[73:73 + K * H * W].reshape(H * W, K).t()
-    lg = v @ Wd.t() + pt[73 + K * H * W:]
-    ce = torch.nn.functional.cross_entropy(lg, torch.tensor(lab))
-    ce.backward()
-    assert abs(float(loss) - ce.item()) < 2e-6 * max(1.0, abs(ce.item()))
-    np.testing.assert_allclose(logits, lg.detach().numpy(), rtol=0, atol=2e-5 * np.abs(lg.detach().numpy()).max())
-    assert np.abs(du - ut.grad.numpy()).max() <= 2e-5 * np.abs(ut.grad.numpy()).max()
-    assert np.abs(dph - pt.grad.numpy()).max() <= 2e-5 * np.abs(pt.grad.numpy()).max()
+    ref = HC.cifar_head_reference(u, ph, K, lab, torch.float64)      # the torch model this test held, now shared
+    assert abs(float(loss) - ref["loss"]) < 2e-6 * max(1.0, abs(ref["loss"]))
+    np.testing.assert_allclose(logits, ref["logits"], rtol=0, atol=2e-5 * np.abs(ref["logits"]).max())
+    assert np.abs(du - ref["du"]).max() <= 2e-5 * np.abs(ref["du"]).max()
+    assert np.abs(dph - ref["dph"]).max() <= 2e-5 * np.abs(ref["dph"]).max()
