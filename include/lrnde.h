@@ -522,6 +522,45 @@ int lrnde_sde_sri_step_backward(lrnde_sde* sde, const lrnde_sri_tableau* tab, co
                                 int32_t B, float t, float dt, float abstol, float reltol, float delta, const float* du_new,
                                 float w_reg, float* dx, float* dp_drift, float* dp_diff, float* reg_val_host);
 
+/* ---- the MNIST-SDE model around the layer (experiments/src/construct.jl:202-210):
+ *   Chain(flatten, downsample = Dense(Din => D), neural_dsde, sol_to_arr, classifier = Dense(D => K)),
+ *   loss = logitcrossentropy(y_pred, y) + w_reg * st.neural_dsde.reg_val (construct.jl:18-31).  D is the handle's state size.
+ *
+ * lrnde_sde_dense_forward — `downsample = Dense(784 => 32)` (construct.jl:203): u0[b][o] = sum_k W[o][k] x[b][k] + b[o].
+ *   x (B x Din, row-major = Julia's Din x B), pd = the flat Lux block [vec(W) (D x Din, column-major: W[o][k] at o + D*k); b (D)],
+ *   u0 (B x D): device.  One sample's result does not depend on B or on where the sample sits in the batch.
+ * lrnde_sde_dense_backward — that layer's pullback (what Zygote takes through construct.jl:203): dpd = [vec(dW); db] with
+ *   dW[o][k] = sum_b du0[b][o] x[b][k], db[o] = sum_b du0[b][o], summed over the batch in a fixed order (no atomics), and
+ *   dx = du0 W (B x Din) when dx is not NULL — the experiment never asks for it (x is data).
+ * lrnde_sde_classifier_ce — `classifier = Dense(32 => num_classes)` + logitcrossentropy (construct.jl:209, :18-31;
+ *   experiments/src/utils.jl:88) on the SDE handle: the arguments, layout, arithmetic and errors of lrnde_classifier_ce
+ *   (K in 1..16; a label outside [0, K) returns LRNDE_BADARG).
+ * lrnde_sde_model_forward_record_ce — the forward half of the training step (construct.jl:18-31 through :202-210): downsample ->
+ *   lrnde_sde_node_forward_record_alg -> head on sol.u[end]; the same values, bit for bit, as the three calls.  The arguments
+ *   are x, Din, pd, then those of lrnde_sde_node_forward_record_alg without its x, then pc, K, labels, loss_host, logits
+ *   (B x K, may be NULL), dpc (may be NULL) of the head.  The downsample is enqueued ahead of the layer, the head behind it, and
+ *   one final wait delivers the loss.  The record keeps what the pullback needs (the head's cotangent of sol.u[end] included)
+ *   and refers to x, pd, W (and Z): they stay alive until the backward call.  It counts in lrnde_sde_record_generation.
+ * lrnde_sde_model_backward_recorded — the pullback from that record (what `Zygote.pullback` of construct.jl:18-31 returns):
+ *   the series cotangent (zero but for the head's du on the last entry) -> lrnde_sde_node_backward_recorded with w_reg ->
+ *   lrnde_sde_dense_backward on its dx.  dpd, dp_drift, dp_diff: device; dx (B x Din) may be NULL.  One synchronisation at the
+ *   end.  Without a usable record — none yet, another batch size, or a later forward on the handle — LRNDE_BADARG.
+ * NULL handles and pointers, B < 1, Din < 1, K outside 1..16 return a status. */
+int lrnde_sde_dense_forward(lrnde_sde* sde, const float* x, int32_t B, int32_t Din, const float* pd, float* u0);
+int lrnde_sde_dense_backward(lrnde_sde* sde, const float* x, int32_t B, int32_t Din, const float* pd, const float* du0, float* dpd,
+                             float* dx);
+int lrnde_sde_classifier_ce(lrnde_sde* sde, const float* u, int32_t B, const float* pc, int32_t K, const int32_t* labels,
+                            float* loss_host, float* logits, float* du, float* dpc);
+int lrnde_sde_model_forward_record_ce(lrnde_sde* sde, const float* x, int32_t Din, const float* pd, const float* W, int32_t nfine,
+                                      int32_t B, float t0, float t2, const lrnde_sde_adapt_opts* opts, int32_t mode, float t1_or_rand,
+                                      const float* z_local, int32_t save_start, const float* saveat_host, int32_t nsave,
+                                      float* u_series, float* t_series_host, int32_t cap_series, int32_t* nseries_host,
+                                      float* reg_val_host, int32_t* nfe_drift_host, int32_t* nfe_diffusion_host,
+                                      lrnde_stats* stats_host, float* t1_used_host, int32_t which, const lrnde_sri_tableau* tab,
+                                      const float* Z, const float* z2_local, const float* pc, int32_t K, const int32_t* labels,
+                                      float* loss_host, float* logits, float* dpc);
+int lrnde_sde_model_backward_recorded(lrnde_sde* sde, int32_t B, float w_reg, float* dpd, float* dp_drift, float* dp_diff, float* dx);
+
 
 /* ---- backward pass ----
  * lrnde_vjp: the vector-Jacobian product Zygote.pullback(dudt, y, p, t) computes inside the adjoint

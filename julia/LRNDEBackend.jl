@@ -308,6 +308,52 @@ function sde_node_forward_record_alg(h, x, W, nfine, t0, t2, opts, mode, t1_or_r
     return nothing
 end
 
+# ---- the MNIST-SDE model around the layer (experiments/src/construct.jl:202-210; lrnde.h: lrnde_sde_dense_forward ...
+# lrnde_sde_model_backward_recorded).  x (Din, B), pd = the flat downsample block [vec(W); b], u0 / du0 (D, B), pc = the flat
+# classifier block, labels::Vector{Int32} on the device, zero-based.  UN-RUN like the rest of this binding.
+function sde_dense_forward(h, x, pd, D)
+    u0 = similar(x, Float32, D, size(x, 2))
+    sde_check(h, ccall((:lrnde_sde_dense_forward, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(x), Int32(size(x, 2)), Int32(size(x, 1)), pointer(pd), pointer(u0)))
+    return u0
+end
+function sde_dense_backward(h, x, pd, du0; want_dx=false)
+    dpd = similar(pd); dx = want_dx ? similar(x) : nothing
+    sde_check(h, ccall((:lrnde_sde_dense_backward, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int32, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(x), Int32(size(x, 2)), Int32(size(x, 1)), pointer(pd), pointer(du0), pointer(dpd), _optr(dx)))
+    return dpd, dx
+end
+function sde_classifier_ce(h, u, pc, K, labels)
+    logits = similar(u, Float32, K, size(u, 2)); du = similar(u); dpc = similar(pc); loss = Ref{Float32}()
+    sde_check(h, ccall((:lrnde_sde_classifier_ce, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Float32}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(u), Int32(size(u, 2)), pointer(pc), Int32(K), pointer(labels), loss, pointer(logits), pointer(du), pointer(dpc)))
+    return loss[], logits, du, dpc
+end
+# downsample -> sde_node_forward_record_alg -> head on sol.u[end]: that function's arguments with (x, pd) for its x, then the head's
+function sde_model_forward_record_ce(h, x, pd, W, nfine, t0, t2, opts, mode, t1_or_rand, z, save_start, saveat, useries, tseries, cap,
+                                     ns, reg, nf, ng, stats, t1u, which, pc, K, labels; tab=nothing, Z=nothing, z2=nothing)
+    logits = similar(x, Float32, K, size(x, 2)); dpc = similar(pc); loss = Ref{Float32}()
+    tabref = tab === nothing ? Ref(SriTableau(ntuple(_ -> 0f0, 51)...)) : Ref(tab)
+    GC.@preserve tabref sde_check(h, ccall((:lrnde_sde_model_forward_record_ce, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int32, Ptr{Float32}, Ptr{Float32}, Int32, Int32, Float32, Float32, Ptr{Cvoid}, Int32, Float32, Ptr{Float32}, Int32,
+         Ptr{Float32}, Int32, Ptr{Float32}, Ptr{Float32}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Ref{Stats}, Ptr{Float32},
+         Int32, Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int32, Ptr{Int32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h, pointer(x), Int32(size(x, 1)), pointer(pd), pointer(W), Int32(nfine), Int32(size(x, 2)), t0, t2, Ref(opts), mode, t1_or_rand,
+        _optr(z), save_start, saveat, Int32(length(saveat)), pointer(useries), tseries, Int32(cap), ns, reg, nf, ng, stats, t1u,
+        Int32(which), tab === nothing ? C_NULL : Base.unsafe_convert(Ptr{Cvoid}, tabref), _optr(Z), _optr(z2),
+        pointer(pc), Int32(K), pointer(labels), loss, pointer(logits), pointer(dpc)))
+    return loss[], logits, dpc
+end
+function sde_model_backward_recorded(h, B, w_reg, dpd, dp_drift, dp_diff; dx=nothing)
+    sde_check(h, ccall((:lrnde_sde_model_backward_recorded, lib), Cint,
+        (Ptr{Cvoid}, Int32, Float32, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+        h, Int32(B), Float32(w_reg), pointer(dpd), pointer(dp_drift), pointer(dp_diff), _optr(dx)))
+    return dpd, dp_drift, dp_diff, dx
+end
+
 # ---- Latent ODE around the Dense-chain NeuralODE (experiments/src/construct.jl:230-252; DESIGN.md 4.9.2) ----
 # gru = Recurrence(LatentGRUCell) (src/layers/latent_ode.jl), rec_to_gen, reparam (src/layers/common.jl:47-77), gen_to_data and
 # the loss (construct.jl:36-76).  ps: the flat ComponentArray (gru.update_gate, gru.reset_gate, gru.new_state, rec_to_gen,

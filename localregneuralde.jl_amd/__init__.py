@@ -11,7 +11,8 @@ from .layers import (Activation, Chain, Dense, Handle, NeuralODE, ODESolution, T
                      glorot_chain_params, glorot_params)
 from .sde import NeuralDSDE, SdeHandle  # noqa: F401
 from .conv import BatchNorm, Conv, ConvHandle, glorot_conv_params  # noqa: F401
-from .training import run_cifar_training_step, run_training_step  # noqa: F401
+from .sde_model import MlpSde, construct_mlp_sde, glorot_mlp_sde_params  # noqa: F401
+from .training import run_cifar_training_step, run_sde_training_step, run_training_step  # noqa: F401
 from .optim import (Constant, CosineAnneal, ExponentialDecay, InverseDecay, Optimiser, Step,  # noqa: F401
                     construct_scheduler)
 from .sharding import LocalComm, init_comm, run_ranks, shard_columns  # noqa: F401

@@ -134,6 +134,13 @@ SYMBOLS = [
     ("lrnde_sde_node_forward_record_alg", C.c_int, [_vp, _vp, _vp, _i32, _i32, _f, _f, C.POINTER(SdeAdaptOpts), _i32, _f, _vp, _i32, _fp, _i32,
                                                     _vp, _fp, _i32, C.POINTER(_i32), _fp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(Stats), _fp,
                                                     _i32, C.POINTER(SriTableau), _vp, _vp]),
+    ("lrnde_sde_dense_forward", C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    ("lrnde_sde_dense_backward", C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    ("lrnde_sde_classifier_ce", C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _fp, _vp, _vp, _vp]),
+    ("lrnde_sde_model_forward_record_ce", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _f, _f, C.POINTER(SdeAdaptOpts), _i32, _f, _vp, _i32,
+                                                    _fp, _i32, _vp, _fp, _i32, C.POINTER(_i32), _fp, C.POINTER(_i32), C.POINTER(_i32),
+                                                    C.POINTER(Stats), _fp, _i32, C.POINTER(SriTableau), _vp, _vp, _vp, _i32, _vp, _fp, _vp, _vp]),
+    ("lrnde_sde_model_backward_recorded", C.c_int, [_vp, _i32, _f, _vp, _vp, _vp, _vp]),
     ("lrnde_vjp", C.c_int, [_vp, _vp, _f, _vp, _i32, _vp, _vp]),
     ("lrnde_step_reg_grad", C.c_int, [_vp, _vp, _vp, _i32, _f, _f, _f, _f, _i32, _vp, _fp]),
     ("lrnde_node_backward", C.c_int, [_vp, _vp, _i32, _f, _f, C.POINTER(SolveOpts), _i32, _i32, _f, _vp, _f, _vp, _vp,

@@ -3110,6 +3110,15 @@ struct lrnde_sde {
   PinBuf<unsigned long long> ad_prog;              // its pinned, mapped progress word
   DevBuf<lrnde_trace_row> ad_trace;
   SdeCtl* ctl() const { return reinterpret_cast<SdeCtl*>(ad_ctl.get()); }
+  // the MNIST-SDE model around the layer (lrnde_sde_model.hpp): the downsample's output, the series cotangent the head's du
+  // goes into, the layer's dx; what the model's record refers to (the caller's x and downsample parameters, alive until the
+  // backward) and the generation of the layer record it belongs to (0: none)
+  DevBuf<float> mdl_u0, mdl_duser, mdl_dxn;
+  const float* mdl_x = nullptr; const float* mdl_pd = nullptr;
+  int mdl_Din = 0, mdl_B = 0, mdl_nser = 0;
+  unsigned long long mdl_gen = 0;
+  std::function<int(const float*, int)> fwd_hook;   // lrnde_sde_node_forward_record_alg: (sol.u[end], nseries), ahead of its closing wait
+  bool defer_wait = false;                          // lrnde_sde_node_backward_recorded's one-launch sweep: the caller waits
 };
 
 int lrnde_sde_create(lrnde_sde** out, const lrnde_model_desc* drift, int32_t diffusion_bias, int device, void* stream) {
@@ -5030,6 +5039,9 @@ int lrnde_last_solve_kernel_ms(lrnde_ctx* c, float* ms, int32_t* launches) {
 }
 
 }  // extern "C"
+
+// ---- the MNIST-SDE model: downsample Dense, the head on the SDE handle, recorded forward and pullback ----
+#include "lrnde_sde_model.hpp"
 
 // ---- Latent ODE: Recurrence(LatentGRUCell) encoder, rec_to_gen, reparameterisation, gen_to_data and the loss ----
 #include "lrnde_latent.hpp"

@@ -380,7 +380,10 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
     if (!series_done && (rc = value_of(r.series[i], u_series + (size_t)i * n))) return rc;
     t_series_host[i] = r.series[i].t;
   }
-  if (!series_done) HIPCHK(c, hipStreamSynchronize(c->stream));
+  // (the model's head goes into the queue here, behind the series and ahead of the one wait: lrnde_sde_model.hpp)
+  const bool hooked = (bool)s->fwd_hook;
+  if (hooked && (rc = s->fwd_hook(u_series + (size_t)(ns - 1) * n, ns))) return rc;
+  if (!series_done || hooked) HIPCHK(c, hipStreamSynchronize(c->stream));
   if (local_pending) {
     *reg_val_host = c->ctrl_host[0].reg_error;   // EEst * dt (src/perform_step.jl:205)
     r.ee_loc = c->ctrl_host[0].eest_last;
@@ -479,7 +482,7 @@ int sde_sweep_fused_core(lrnde_sde* s, const SdeSweepSrc& r, int B, const float*
   }
   hipLaunchKernelGGL(k_sde_bwd_reduce, dim3((Ptot + 31) / 32), dim3(256), 0, c->stream, (const float*)s->bwf_part, nwg_red, Ptot, Pf, Pg, dp_drift, dp_diff, 1.0f, 0);
   HIPCHK(c, hipGetLastError());
-  if (sync_after) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (sync_after && !s->defer_wait) HIPCHK(c, hipStreamSynchronize(c->stream));
   return LRNDE_OK;
 }
 int sde_node_sweep_fused(lrnde_sde* s, SdeNodeRecord& r, int B, const float* du_series, int nseries, float* dx, float* dp_drift,
@@ -511,7 +514,7 @@ int sde_node_reg_fused(lrnde_sde* s, SdeNodeRecord& r, int B, float w_reg, float
   }
   hipLaunchKernelGGL(k_sde_bwd_reduce, dim3((Ptot + 31) / 32), dim3(256), 0, c->stream, (const float*)s->bwf_part, nwg, Ptot, Pf, Pg, dp_drift, dp_diff, w_reg, 1);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!s->defer_wait) HIPCHK(c, hipStreamSynchronize(c->stream));
   return LRNDE_OK;
 }
 int sde_sri_step_backward_core(lrnde_sde* s, const lrnde_sri_tableau* tab, const float* uprev, const float* dW, const float* dZ, int32_t B,
@@ -614,7 +617,7 @@ int lrnde_sde_node_backward_recorded(lrnde_sde* s, int32_t B, const float* du_se
   bool reg_done = false;
   if (fused) {
     if ((rc = sde_node_sweep_fused(s, r, B, du_series, nseries, dx, dp_drift, dp_diff, !reg_fused, reg_fused, w_reg, &reg_done))) return rc;
-    if (reg_done) HIPCHK(c, hipStreamSynchronize(c->stream));   // (the sweep left the closing wait to the regulariser's part)
+    if (reg_done && !s->defer_wait) HIPCHK(c, hipStreamSynchronize(c->stream));   // (the sweep left the closing wait to the regulariser's part)
   }
   else {
   HIPCHK(c, hipMemsetAsync(dx, 0, sizeof(float) * n, c->stream));   // dx doubles as ub, the cotangent of the current step's end state

@@ -168,6 +168,105 @@ class SdeHandle:
     def _pcounts(self):
         return self._keep[0].numel(), self._keep[1].numel()
 
+    # ---- the MNIST-SDE model around the layer (experiments/src/construct.jl:202-210; lrnde_sde_model.hpp) ----
+    def dense_forward(self, x, pd):
+        """`downsample = Dense(Din => D)`: x (B, Din), pd = [vec(W) (D x Din, column-major); b] -> u0 (B, D)"""
+        B, Din = int(x.shape[0]), int(x.shape[1])
+        if pd.numel() != self.D * (Din + 1):
+            raise ValueError(f"downsample parameters must have {self.D * (Din + 1)} entries")
+        u0 = torch.empty((B, self.D), dtype=torch.float32, device=x.device)
+        self._chk(L.lib.lrnde_sde_dense_forward(self._h, _dev_ptr(x, "x"), B, Din, _dev_ptr(pd, "pd"), C.c_void_p(u0.data_ptr())))
+        return u0
+
+    def dense_backward(self, x, pd, du0, want_dx=False):
+        """that layer's pullback: dict(dpd, dx) (dx None unless asked for: x is data in the experiment)"""
+        B, Din = int(x.shape[0]), int(x.shape[1])
+        if pd.numel() != self.D * (Din + 1):
+            raise ValueError(f"downsample parameters must have {self.D * (Din + 1)} entries")
+        dpd = torch.empty_like(pd)
+        dx = torch.empty_like(x) if want_dx else None
+        self._chk(L.lib.lrnde_sde_dense_backward(self._h, _dev_ptr(x, "x"), B, Din, _dev_ptr(pd, "pd"), _dev_ptr(du0, "du0", self.D),
+                                                 C.c_void_p(dpd.data_ptr()), C.c_void_p(dx.data_ptr()) if want_dx else None))
+        return dict(dpd=dpd, dx=dx)
+
+    def _head_args(self, B, pc, K, labels):
+        if pc.numel() != K * (self.D + 1):
+            raise ValueError(f"classifier parameters must have {K * (self.D + 1)} entries")
+        if not (labels.is_cuda and labels.dtype == torch.int32 and labels.numel() == B):
+            raise ValueError("labels must be a CUDA int32 tensor of length B")
+
+    def classifier_ce(self, u, pc, K, labels, want_grads=True):
+        """`classifier = Dense(D => K)` + logitcrossentropy on the SDE handle: dict(loss, logits, du, dpc)"""
+        B = u.numel() // self.D
+        self._head_args(B, pc, K, labels)
+        logits = torch.empty((B, K), dtype=torch.float32, device=u.device)
+        du = torch.empty_like(u) if want_grads else None
+        dpc = torch.empty_like(pc) if want_grads else None
+        loss = C.c_float()
+        self._chk(L.lib.lrnde_sde_classifier_ce(self._h, _dev_ptr(u, "u", self.D), B, _dev_ptr(pc, "pc"), int(K),
+                                                C.c_void_p(labels.data_ptr()), C.byref(loss), C.c_void_p(logits.data_ptr()),
+                                                C.c_void_p(du.data_ptr()) if want_grads else None,
+                                                C.c_void_p(dpc.data_ptr()) if want_grads else None))
+        return dict(loss=np.float32(loss.value), logits=logits, du=du, dpc=dpc)
+
+    def record_generation(self):
+        g = C.c_uint64()
+        self._chk(L.lib.lrnde_sde_record_generation(self._h, C.byref(g)))
+        return int(g.value)
+
+    def model_forward_record_ce(self, x, pd, W, t0, t2, abstol, reltol, pc, K, labels, mode="unbiased", t1_or_rand=0.5, z_local=None,
+                                saveat=(), save_start=-1, delta=1.0 / 6.0, dt0=0.0, gamma=0.9, qmin=0.2, qmax=1.125, beta1=7.0 / 50.0,
+                                beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, z_local2=None):
+        """downsample -> `node_forward_record` -> head on sol.u[end] in one call with one wait (lrnde_sde_model_forward_record_ce):
+        the layer's dict plus loss, logits, dpc; keeps the record for one `model_backward_recorded`"""
+        B, Din = int(x.shape[0]), int(x.shape[1])
+        if pd.numel() != self.D * (Din + 1):
+            raise ValueError(f"downsample parameters must have {self.D * (Din + 1)} entries")
+        self._head_args(B, pc, K, labels)
+        nfine = int(W.shape[0]) - 1
+        W = W.contiguous()
+        sv = np.ascontiguousarray(saveat, dtype=np.float32)
+        o = L.SdeAdaptOpts(float(abstol), float(reltol), float(delta), float(dt0), float(gamma), float(qmin), float(qmax),
+                           float(beta1), float(beta2), int(maxiters))
+        cap = int(sv.size) + 3 + (nfine + 1 if (mode == "biased" and not sv.size) else 0)
+        us = torch.empty((cap, B, self.D), dtype=torch.float32, device=x.device)
+        ts = np.empty(cap, dtype=np.float32)
+        ns, reg, nf, ng, st, t1u, loss = C.c_int32(), C.c_float(), C.c_int32(), C.c_int32(), L.Stats(), C.c_float(), C.c_float()
+        logits = torch.empty((B, K), dtype=torch.float32, device=x.device)
+        dpc = torch.empty_like(pc)
+        z_local = None if z_local is None else z_local.contiguous()
+        path_z = None if path_z is None else path_z.contiguous()
+        z_local2 = None if z_local2 is None else z_local2.contiguous()
+        which = _which(solver)
+        self._chk(L.lib.lrnde_sde_model_forward_record_ce(
+            self._h, _dev_ptr(x, "x"), Din, _dev_ptr(pd, "pd"), _dev_ptr(W, "W"), nfine, B, float(t0), float(t2), C.byref(o), L.MODE[mode],
+            float(t1_or_rand), None if z_local is None else _dev_ptr(z_local, "z_local", self.D), int(save_start),
+            sv.ctypes.data_as(C.POINTER(C.c_float)) if sv.size else None, int(sv.size), C.c_void_p(us.data_ptr()),
+            ts.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns), C.byref(reg), C.byref(nf), C.byref(ng), C.byref(st), C.byref(t1u),
+            which, None if tableau is None or which != 2 else C.byref(_sri_tab(tableau)), None if path_z is None else _dev_ptr(path_z, "path_z"),
+            None if z_local2 is None else _dev_ptr(z_local2, "z_local2", self.D), _dev_ptr(pc, "pc"), int(K), C.c_void_p(labels.data_ptr()),
+            C.byref(loss), C.c_void_p(logits.data_ptr()), C.c_void_p(dpc.data_ptr())))
+        self._node_keep = (W, x, path_z, pd)   # the record refers to them: alive until the backward
+        self._model_shape = (B, Din)
+        n = int(ns.value)
+        return dict(u=us[:n], t=ts[:n].copy(), u_end=us[n - 1], reg_val=np.float32(reg.value), nfe_drift=int(nf.value),
+                    nfe_diffusion=int(ng.value), stats=st.asdict(), t1=np.float32(t1u.value), loss=np.float32(loss.value),
+                    logits=logits, dpc=dpc, generation=self.record_generation())
+
+    def model_backward_recorded(self, w_reg=0.0, want_dx=False):
+        """the pullback of  logitcrossentropy + w_reg * reg_val  from the record of `model_forward_record_ce`:
+        dict(dpd, dp_drift, dp_diff, dx)"""
+        B, Din = self._model_shape
+        nf, ng = self._pcounts()
+        dev = self._keep[0].device
+        dpd = torch.empty(self.D * (Din + 1), dtype=torch.float32, device=dev)
+        dpf = torch.empty(nf, dtype=torch.float32, device=dev)
+        dpg = torch.empty(ng, dtype=torch.float32, device=dev)
+        dx = torch.empty((B, Din), dtype=torch.float32, device=dev) if want_dx else None
+        self._chk(L.lib.lrnde_sde_model_backward_recorded(self._h, B, float(w_reg), C.c_void_p(dpd.data_ptr()), C.c_void_p(dpf.data_ptr()),
+                                                          C.c_void_p(dpg.data_ptr()), C.c_void_p(dx.data_ptr()) if want_dx else None))
+        return dict(dpd=dpd, dp_drift=dpf, dp_diff=dpg, dx=dx)
+
     def node_forward_record(self, x, W, t0, t2, abstol, reltol, mode="unbiased", t1_or_rand=0.5, z_local=None, saveat=(),
                             save_start=-1, delta=1.0 / 6.0, dt0=0.0, gamma=0.9, qmin=0.2, qmax=1.125, beta1=7.0 / 50.0,
                             beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, z_local2=None):
@@ -343,45 +442,53 @@ class NeuralDSDE:
         """the device streams' seed: one uint64 from the layer's host stream"""
         return int(rng.integers(0, 2 ** 64, dtype=np.uint64))
 
+    def _adaptive_draws(self, h, shape, device, st, path=None, z_local=None, path_z=None, z_local2=None):
+        """the adaptive layer's draws for an input of `shape` on `device`, from a copy of st["rng"]:
+        (rng, path, z_local, path_z, z_local2, mode, t1_or_rand) — arrays given explicitly win"""
+        shape = tuple(shape)
+        t0, t2 = self.tspan
+        rng = copy.deepcopy(st["rng"])
+        if self.noise_source == "device":   # W (stream 0) and z (stream 1) on the device; node_forward_record keeps W alive
+            seed = self._draw_seed(rng)
+            B = int(np.prod(shape)) // h.D
+            if path is None:
+                hh = np.float32((t2 - t0) / np.float32(self.nfine))
+                path = h.draw_noise(seed, 0, self.nfine, B, np.float32(np.sqrt(hh)), True).view((self.nfine + 1,) + shape)
+            if z_local is None:
+                z_local = h.draw_noise(seed, 1, 1, B, 1.0, False)[0].view(shape)
+            if self.solver == "SRI":   # the second path (stream 4) and the local step's second draw (stream 5)
+                if path_z is None:
+                    hh = np.float32((t2 - t0) / np.float32(self.nfine))
+                    path_z = h.draw_noise(seed, 4, self.nfine, B, np.float32(np.sqrt(hh)), True).view((self.nfine + 1,) + shape)
+                if z_local2 is None:
+                    z_local2 = h.draw_noise(seed, 5, 1, B, 1.0, False)[0].view(shape)
+        if path is None:
+            path, z_draw = self._draw_path(rng, shape, device)
+            z_local = z_draw if z_local is None else z_local
+        else:
+            path = torch.as_tensor(path, dtype=torch.float32).to(device)
+            if z_local is None:
+                z_local = torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(device)
+        if self.solver == "SRI":   # host draws of Z, then z2, AFTER W and z (the other solvers' draw sequences are unchanged)
+            if path_z is None:
+                path_z, z2_draw = self._draw_path(rng, shape, device)
+                z_local2 = z2_draw if z_local2 is None else z_local2
+            else:
+                path_z = torch.as_tensor(path_z, dtype=torch.float32).to(device)
+                if z_local2 is None:
+                    z_local2 = torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(device)
+            self._last_path_z = path_z
+        mode = self.regularize if st["training"] else "none"
+        r01 = np.float32(rng.random(dtype=np.float32)) if mode != "none" else np.float32(0)
+        t1_or_rand = np.float32(r01 * (t2 - t0) + t0) if mode == "unbiased" else r01     # :92 / :114
+        return rng, path, z_local, path_z, z_local2, mode, t1_or_rand
+
     def _call_adaptive(self, x, ps, st, path=None, z_local=None, path_z=None, z_local2=None):
         h = self.handle()
         h.set_params(ps["drift"], ps["diffusion"])
         t0, t2 = self.tspan
         abstol, reltol = self.kwargs.get("abstol", 1e-2), self.kwargs.get("reltol", 1e-2)
-        rng = copy.deepcopy(st["rng"])
-        if self.noise_source == "device":   # W (stream 0) and z (stream 1) on the device; node_forward_record keeps W alive
-            seed = self._draw_seed(rng)
-            B = x.numel() // h.D
-            if path is None:
-                hh = np.float32((t2 - t0) / np.float32(self.nfine))
-                path = h.draw_noise(seed, 0, self.nfine, B, np.float32(np.sqrt(hh)), True).view((self.nfine + 1,) + tuple(x.shape))
-            if z_local is None:
-                z_local = h.draw_noise(seed, 1, 1, B, 1.0, False)[0].view(tuple(x.shape))
-            if self.solver == "SRI":   # the second path (stream 4) and the local step's second draw (stream 5)
-                if path_z is None:
-                    hh = np.float32((t2 - t0) / np.float32(self.nfine))
-                    path_z = h.draw_noise(seed, 4, self.nfine, B, np.float32(np.sqrt(hh)), True).view((self.nfine + 1,) + tuple(x.shape))
-                if z_local2 is None:
-                    z_local2 = h.draw_noise(seed, 5, 1, B, 1.0, False)[0].view(tuple(x.shape))
-        if path is None:
-            path, z_draw = self._draw_path(rng, x.shape, x.device)
-            z_local = z_draw if z_local is None else z_local
-        else:
-            path = torch.as_tensor(path, dtype=torch.float32).to(x.device)
-            if z_local is None:
-                z_local = torch.from_numpy(rng.standard_normal(tuple(x.shape)).astype(np.float32)).to(x.device)
-        if self.solver == "SRI":   # host draws of Z, then z2, AFTER W and z (the other solvers' draw sequences are unchanged)
-            if path_z is None:
-                path_z, z2_draw = self._draw_path(rng, x.shape, x.device)
-                z_local2 = z2_draw if z_local2 is None else z_local2
-            else:
-                path_z = torch.as_tensor(path_z, dtype=torch.float32).to(x.device)
-                if z_local2 is None:
-                    z_local2 = torch.from_numpy(rng.standard_normal(tuple(x.shape)).astype(np.float32)).to(x.device)
-            self._last_path_z = path_z
-        mode = self.regularize if st["training"] else "none"
-        r01 = np.float32(rng.random(dtype=np.float32)) if mode != "none" else np.float32(0)
-        t1_or_rand = np.float32(r01 * (t2 - t0) + t0) if mode == "unbiased" else r01     # :92 / :114
+        rng, path, z_local, path_z, z_local2, mode, t1_or_rand = self._adaptive_draws(h, x.shape, x.device, st, path, z_local, path_z, z_local2)
         saveat = self.kwargs.get("saveat", ())
         r = h.node_forward_record(x, path, t0, t2, abstol, reltol, mode=mode, t1_or_rand=float(t1_or_rand), z_local=z_local,
                                   saveat=() if saveat is None else saveat, save_start=int(self.kwargs.get("save_start", -1)),

@@ -78,3 +78,48 @@ def run_cifar_training_step(node, params, st, x, labels, w_reg, num_classes=10):
     stats = dict(y_pred=head["logits"], nfe=fw["nfe"], ce_loss=head["loss"], reg_val=fw["reg_val"])
     grads = dict(stem=dstem, neural_ode=bw["dp"], head=head["dph"])
     return loss, st_, stats, grads, dict(fwd_time=fwd_time, bwd_time=bwd_time, adjoint=bw["stats_bwd"], forward=fw["stats"])
+
+
+def run_sde_training_step(model, ps, st, x, labels, w_reg, path=None, z_local=None, path_z=None, z_local2=None):
+    """The MNIST-SDE model's forward + pullback (experiments/src/construct.jl:18-31 on :202-210; the timing split of
+    experiments/src/utils.jl:104-123).  model: `sde_model.MlpSde`; ps: dict(downsample=, neural_dsde=dict(drift=, diffusion=),
+    classifier=); x (B, Din) or (B, 1, 28, 28) CUDA float32; labels CUDA int32 (B).  Returns (loss, st_, stats, grads, times):
+    stats = dict(y_pred, nfe=(nfe_drift, nfe_diffusion), ce_loss, reg_val) — the diffusion count is the layer's own (the
+    reference's harness reports nfe_drift twice, construct.jl:9,24) — and grads shaped like ps.
+    One forward solve (lrnde_sde_model_forward_record_ce) and the pullback from its record
+    (lrnde_sde_model_backward_recorded); `path`, `z_local` (`path_z`, `z_local2` for SRI) as on the layer."""
+    nsde = model.neural_dsde
+    if not nsde.adaptive:
+        raise NotImplementedError("run_sde_training_step runs the adaptive layer (the reference's; adaptive=True for RKMil / SRI)")
+    sn = st["neural_dsde"]
+    x = model.flatten(x)
+    B = int(x.shape[0])
+    t0, t2 = nsde.tspan
+    kw = nsde.kwargs
+    abstol, reltol = kw.get("abstol", 1e-2), kw.get("reltol", 1e-2)
+    saveat = kw.get("saveat", ())
+    torch.cuda.synchronize()
+    tic = time.perf_counter()
+    h = nsde.handle()
+    pd, pf, pg, pc = model.device_params(ps, x.device)
+    h.set_params(pf, pg)   # the repack of the (updated) parameters is part of the step
+    rng, path, z_local, path_z, z_local2, mode, t1_or_rand = nsde._adaptive_draws(h, (B, h.D), x.device, sn, path, z_local, path_z, z_local2)
+    fw = h.model_forward_record_ce(x, pd, path, t0, t2, abstol, reltol, pc, model.num_classes, labels, mode=mode,
+                                   t1_or_rand=float(t1_or_rand), z_local=z_local, saveat=() if saveat is None else saveat,
+                                   save_start=int(kw.get("save_start", -1)), delta=nsde.delta, dt0=nsde.dt0, maxiters=nsde.maxiters,
+                                   solver=nsde.solver, tableau=nsde.tableau if nsde.solver == "SRI" else None, path_z=path_z,
+                                   z_local2=z_local2)
+    loss = np.float32(fw["loss"] + np.float32(w_reg) * fw["reg_val"])
+    torch.cuda.synchronize()
+    fwd_time = time.perf_counter() - tic
+    tic = time.perf_counter()
+    if h.record_generation() != fw["generation"]:
+        raise RuntimeError("the layer's record was replaced between the forward and the pullback")
+    bw = h.model_backward_recorded(w_reg=w_reg)
+    torch.cuda.synchronize()
+    bwd_time = time.perf_counter() - tic
+    st_n = dict(drift=sn["drift"], diffusion=sn["diffusion"], nfe_drift=fw["nfe_drift"], nfe_diffusion=fw["nfe_diffusion"],
+                reg_val=fw["reg_val"], rng=rng, training=sn["training"])
+    stats = dict(y_pred=fw["logits"], nfe=(fw["nfe_drift"], fw["nfe_diffusion"]), ce_loss=fw["loss"], reg_val=fw["reg_val"])
+    grads = dict(downsample=bw["dpd"], neural_dsde=dict(drift=bw["dp_drift"], diffusion=bw["dp_diff"]), classifier=fw["dpc"])
+    return loss, dict(st, neural_dsde=st_n), stats, grads, dict(fwd_time=fwd_time, bwd_time=bwd_time, forward=fw["stats"])
