@@ -82,10 +82,10 @@ __global__ void k_adams_eval(AdamsEval a) {
 inline int adams_grid(size_t n) { int nb = (int)((n + 255) / 256); return nb > 2048 ? 2048 : (nb < 1 ? 1 : nb); }
 
 // lrnde_solve for c->solver_alg = 1 (VCAB3) | 2 (VCABM3): same arguments, same outputs, same side effects on the handle
-// (save slots, tail copy of sol.u[end], dense record when a recorded forward asked for one)
+// (save slots, tail copy of sol.u[end] when side asks for it, dense record when a recorded forward asked for one)
 int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, const lrnde_solve_opts* o,
                 const float* saveat_host, int32_t nsave, float* u_saved, float* t_saved_host, int32_t cap_saved,
-                lrnde_stats* st, lrnde_trace_row* trace_host, int32_t cap_trace) {
+                lrnde_stats* st, lrnde_trace_row* trace_host, int32_t cap_trace, SolveSide* side) {
   int rc;
   const size_t n = (size_t)B * c->desc.state_dim;
   const bool moulton = c->solver_alg == 2;
@@ -236,9 +236,8 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
     }
   }
   // sol.u[end] into the caller's array when node_forward asked for it (the Tsit5 solve does this in its last launch)
-  if (c->tail_copy_dst && c->tail_copy_slot >= 0 && c->tail_copy_slot == nsaved - 1)
-    HIPCHK(c, hipMemcpyAsync(c->tail_copy_dst, u_saved + (size_t)c->tail_copy_slot * n, sizeof(float) * n, hipMemcpyDeviceToDevice, sq));
-  c->tail_copy_dst = nullptr;
+  if (side && side->tail_dst && side->tail_slot >= 0 && side->tail_slot == nsaved - 1)
+    HIPCHK(c, hipMemcpyAsync(side->tail_dst, u_saved + (size_t)side->tail_slot * n, sizeof(float) * n, hipMemcpyDeviceToDevice, sq));
   HIPCHK(c, hipStreamSynchronize(sq));
   const int status = L.status;
   st->retcode = status; st->iters = L.iter; st->nsaved = nsaved; st->t_final = t; st->dt_final = dt;

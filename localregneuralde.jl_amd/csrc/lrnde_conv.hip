@@ -44,6 +44,7 @@
 #include "lrnde_math.hpp"
 #include "lrnde_buf.hpp"
 #include "lrnde_stepctl.hpp"
+#include "lrnde_layer_plan.hpp"
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
               "header_status returns lrnde_status values");
@@ -1693,7 +1694,6 @@ struct lrnde_conv {
   DevBuf<double> sums; PinBuf<double> sums_host;
   HipEvent ev0, ev1;
   int num_cu = 256;
-  std::vector<float> last_ts;
   // backward pass
   DevBuf<float> w1t, w2t, w3t;  // transposed-conv weight packs
   DevBuf<float> params; bool w_t_valid = false;       // device copy of the flat parameters
@@ -1705,8 +1705,7 @@ struct lrnde_conv {
   bool dense_on = false; size_t dense_n = 0;
   std::vector<DevBuf<float>> dense; std::vector<float> dense_t, dense_dt;
   DevBuf<float> rec_u1;
-  unsigned long long rec_gen = 0;
-  bool rec_valid = false; int rec_B = 0, rec_mode = 0, rec_reg_type = 0; float rec_t0 = 0.f, rec_t2 = 0.f, rec_t1 = 0.f; lrnde_solve_opts rec_opts;
+  LayerRecord rec;   // arguments and generation of the recorded forward; rec.ts: sol.t of the last solve, recorded or not
   DevBuf<float> adj;
 };
 
@@ -2281,14 +2280,14 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
   float* V = c->vec;
   float *uprev = V, *u = V + n, *k1 = V + 2 * n, *ks = V + 3 * n, *k7 = V + 8 * n, *g6 = V + 9 * n, *tmp = V + 10 * n;
   int nsaved = 0, isave = 0, ntrace = 0;
-  c->last_ts.clear();
+  c->rec.ts.clear();
   if (c->dense_on) { c->dense_t.clear(); c->dense_dt.clear(); }
-  else c->rec_valid = false;  // a plain solve overwrites the saved times the recorded backward pass reads
+  else c->rec.invalidate();  // a plain solve overwrites the saved times the recorded backward pass reads
   auto push = [&](float tt, const float* uu) -> int {
     if (nsaved >= cap_saved || !u_saved) return cfail(c, LRNDE_CAPACITY, "u_saved capacity %d exhausted", cap_saved);
     CHK(c, hipMemcpyAsync(u_saved + (size_t)nsaved * n, uu, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
     if (t_saved) t_saved[nsaved] = tt;
-    c->last_ts.push_back(tt);
+    c->rec.ts.push_back(tt);
     nsaved++;
     return LRNDE_OK;
   };
@@ -2360,28 +2359,29 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
   *reg_val = 0.0f;
   if (t1_used) *t1_used = t2;
   DevBuf<float> us, u1;   // this call's save slots and u(t1): released on every return path
+  float t1 = (mode == LRNDE_MODE_UNBIASED) ? t1_or_rand : t2;
+  const SolveSaveat plan = solve_saveat(mode, t1, t2, nullptr, 0);   // [t2] / [t1, t2] / every accepted step
+  const float* sv = plan.saveat.data(); const int nsv = (int)plan.saveat.size();
+  oo.save_everystep = plan.save_everystep;
   if (mode == LRNDE_MODE_NONE) {  // src/layers/neural_ode.jl:56-60
-    oo.save_everystep = 0;
     CHK(c, us.once(n * 2));
-    float sv[1] = {t2}, ts[2];
-    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, 1, us, ts, 2, st, nullptr, 0))) return rc;
+    float ts[2];
+    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, nsv, us, ts, 2, st, nullptr, 0))) return rc;
     CHK(c, hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
     *nfe = st->nf;
     return LRNDE_OK;
   }
-  float t1;
   CHK(c, u1.once(n));
   if (mode == LRNDE_MODE_UNBIASED) {  // :68-84, saveat = [t1, t2]
-    t1 = t1_or_rand;
-    oo.save_everystep = 0;
     if (us.once(n * 3) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
-    float sv[2] = {t1, t2}, ts[3];
-    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, 2, us, ts, 3, st, nullptr, 0))) return rc;
-    const int i1 = oo.save_start ? 1 : 0;
+    float ts[3];
+    if ((rc = lrnde_conv_solve(c, x, B, t0, t2, &oo, sv, nsv, us, ts, 3, st, nullptr, 0))) return rc;
+    // the slot of sol(t1); outside t0 < t1 < t2 this handle reads the first slot behind the start value
+    const int p1 = slot_of_t1(sv, nsv, t0, t1, oo.save_start);
+    const int i1 = (p1 >= 0 && t1 < t2) ? p1 : (oo.save_start ? 1 : 0);
     CHK(c, hipMemcpy(u1, us + (size_t)i1 * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
     CHK(c, hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
   } else {  // :88-100 biased, saveat = [] => every accepted step
-    oo.save_everystep = 1;
     // every accepted step is kept: start with room for 32 and re-solve with more if that overflows (a state is
     // 8 MB at the CIFAR shape, B=256; the running statistics are rewound so the retry does not count twice)
     std::vector<float> ts;
@@ -2401,10 +2401,7 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
     (void)bn0.reset();
     if (rc) return rc;
     if (st->nsaved < 2) return cfail(c, LRNDE_BADARG, "biased mode needs at least two saved steps");
-    const int m = st->nsaved - 1;
-    int idx = (int)(t1_or_rand * (float)m);
-    if (idx >= m) idx = m - 1;
-    if (idx < 0) idx = 0;
+    const int idx = biased_pick(t1_or_rand, st->nsaved - 1);
     t1 = ts[idx];
     CHK(c, hipMemcpy(u1, us + (size_t)idx * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
     CHK(c, hipMemcpy(u_end, us + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice));
@@ -2570,15 +2567,14 @@ int lrnde_conv_node_forward_record(lrnde_conv* c, const float* x, int32_t B, flo
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!x || !o || !u_end || !st) return cfail(c, LRNDE_BADARG, "null pointer");
-  c->rec_valid = false;
+  c->rec.invalidate();
   float t1 = t2;
   c->dense_on = true;
   rc = lrnde_conv_node_forward(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, u_end, reg_val_host, nfe_host, st, &t1);
   c->dense_on = false;
   if (rc) return rc;
   if (t1_used_host) *t1_used_host = t1;
-  c->rec_valid = true; ++c->rec_gen; c->rec_B = B; c->rec_t0 = t0; c->rec_t2 = t2; c->rec_t1 = t1; c->rec_opts = *o; c->rec_mode = mode;
-  c->rec_reg_type = reg_type;
+  c->rec.set(B, mode, reg_type, t0, t2, t1, *o);
   return LRNDE_OK;
 }
 
@@ -2604,7 +2600,7 @@ int lrnde_conv_node_backward(lrnde_conv* c, const float* x, int32_t B, float t0,
 // backward of  loss = <du_end, sol.u[end]> + w_reg * reg_val  from the record of the last lrnde_conv_node_forward_record
 int lrnde_conv_record_generation(lrnde_conv* c, uint64_t* gen_host) {   // see lrnde_record_generation
   if (!c || !gen_host) return LRNDE_BADARG;
-  *gen_host = c->rec_valid ? c->rec_gen : 0;
+  *gen_host = c->rec.generation();
   return LRNDE_OK;
 }
 int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_end, float w_reg, float* dx, float* dp,
@@ -2612,17 +2608,17 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!du_end || !dx || !dp || !st_bwd) return cfail(c, LRNDE_BADARG, "null pointer");
-  if (!c->rec_valid || c->rec_B != B) return cfail(c, LRNDE_BADARG, "no forward record for this batch (call lrnde_conv_node_forward_record first)");
-  const lrnde_solve_opts* o = &c->rec_opts;
-  const float t0 = c->rec_t0, t2 = c->rec_t2, t1 = c->rec_t1;
-  const int mode = c->rec_mode, reg_type = c->rec_reg_type;
+  const LayerRecord& R = c->rec;
+  if (!R.valid || R.B != B) return cfail(c, LRNDE_BADARG, "no forward record for this batch (call lrnde_conv_node_forward_record first)");
+  const lrnde_solve_opts* o = &R.opts;
+  const float t0 = R.t0, t2 = R.t2, t1 = R.t1;
+  const int mode = R.mode, reg_type = R.reg_type;
   const size_t n = state_n(c, B), P = lrnde_conv_param_count(&c->d), N = n + P;
-  // the local step of node_forward re-solved nothing: last_ts / dense_t describe the main solve (dense record is
+  // the local step of node_forward re-solved nothing: rec.ts / dense_t describe the main solve (dense record is
   // only appended inside lrnde_conv_solve)
   const std::vector<float> dts = c->dense_t, dds = c->dense_dt;
   std::vector<float> stops;
-  if (mode != LRNDE_MODE_NONE)
-    for (int i = (int)c->last_ts.size() - 1; i >= 0; --i) { const float tv = c->last_ts[i]; if (tv > t0 && tv < t2) stops.push_back(-tv); }
+  if (mode != LRNDE_MODE_NONE) stops = backward_stops(R.ts, t0, t2);
   // 2. adjoint solve
   if ((rc = ensure_adj(c, 11 * N + n))) return rc;
   float* Z = c->adj; float* ybuf = c->adj + 11 * N;

@@ -48,6 +48,7 @@
 #include "lrnde_hooks.h"
 #include "lrnde_math.hpp"
 #include "lrnde_stepctl.hpp"
+#include "lrnde_layer_plan.hpp"
 #include "lrnde_report.hpp"
 #include "lrnde_buf.hpp"
 #include "lrnde_comm.hpp"
@@ -1732,6 +1733,34 @@ __global__ void k_pack(const float* p, int D, int H, int td, int Dp, int Hp, flo
 // host side
 // ===========================================================================
 
+// What a recorded layer forward (lrnde_node_forward_record*) leaves for lrnde_node_backward_recorded*: the arguments, the
+// generation and sol.t (LayerRecord), and beside them the caller's series, the local step and the regulariser's gradient.
+struct LocalStep { float dt = 0.f, eest = 0.f, snum = 0.f, sden = 0.f; };  // the local step's dt and scalars (local_results)
+struct NodeRecord : lrnde::LayerRecord {
+  int naccept = 0;
+  std::vector<int> series_idx; std::vector<float> series_t;  // the caller's view of the solution: save slots and times
+  int i1 = 0;                  // the save slot of sol(t1)
+  LocalStep loc;
+  DevBuf<float> gr; size_t gr_n = 0;   // the regulariser's parameter gradient (sized for a batch of gr_n state elements)
+  bool gr_ready = false;       // the forward's sweep on the companion's stream has written gr (ev_side_sweep)
+  // a forward whose t1 came too late to enqueue the sweep beside the solve leaves it to the backward pass, which
+  // enqueues it on the companion's stream once its first adjoint attempt is on the handle's (the host would otherwise
+  // spend the sweep's ~30 launch calls inside the forward, with the device idle)
+  bool sweep_pending = false;
+  void reset_side_work() { gr_ready = false; sweep_pending = false; }
+};
+
+// What a layer forward asks of the solve it calls (solve_impl, adams_solve), on the caller's stack; null: a plain solve.
+struct SolveSide {
+  float* tail_dst = nullptr; int tail_slot = -1;   // the step that fills this save slot writes it to tail_dst too
+  std::function<int(int, hipEvent_t)> poll;        // called after every status poll (event: that poll's, or null)
+  // called once the last report is in and sol.u[end] is being written to tail_dst by the queued launches, BEFORE the
+  // final synchronisation: work enqueued here follows the solve without a host round trip and is covered by that
+  // synchronisation (lrnde_node_forward_record_ce: the classifier head)
+  std::function<int()> final;
+  bool final_fired = false, u_end_done = false;    // results: final was called; sol.u[end] reached the caller's array in the solve
+};
+
 struct lrnde_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -1761,17 +1790,7 @@ struct lrnde_ctx {
   hipStream_t adj_stream2 = nullptr; HipEvent adj_evA[2], adj_evB[2];
   DevBuf<int> adj_sync; int adj_launch_id = 0;
   PinBuf<int> adj_hstat; int adj_seq = 0;  // pinned, mapped progress word of the adjoint loop
-  std::vector<float> last_ts;  // sol.t of the last node_forward (cotangent times of the adjoint)
-  std::vector<int> series_idx; std::vector<float> series_t;  // the caller's view of that solution: save slots and times
-  float last_t1 = 0.f; int last_i1 = 0;
-  // backward workspace kept across calls: u(t1) of the recorded forward, k1 and the regulariser's gradient
-  DevBuf<float> rec_gr; size_t rec_n = 0;
-  float rec_dt1 = 0.f, rec_eest = 0.f, rec_snum = 0.f, rec_sden = 0.f;  // the local step's dt and scalars (forward's)
-  float loc_dt = 0.f, loc_eest = 0.f, loc_snum = 0.f, loc_sden = 0.f;    // the same of the LAST layer forward
-  // arguments of the last lrnde_node_forward_record (what lrnde_node_backward_recorded differentiates)
-  bool rec_valid = false; int rec_B = 0, rec_mode = 0, rec_reg_type = 0, rec_naccept = 0;
-  unsigned long long rec_gen = 0;  // counts the recorded forwards of this handle (lrnde_record_generation)
-  float rec_t0 = 0.f, rec_t2 = 0.f, rec_t1 = 0.f; lrnde_solve_opts rec_opts{};
+  NodeRecord rec;  // the last layer forward (what lrnde_node_backward_recorded differentiates)
   int wsNB = 0;  // tile width the workspace (partial-sum vectors) was sized for
   // workspace
   int wsB = 0;
@@ -1808,24 +1827,11 @@ struct lrnde_ctx {
   // layer forward runs its local step there (and, recording, the regulariser's reverse sweep) WHILE the main solve
   // finishes [t1, t2] on the handle's stream: at B <= 512 a step kernel is 128 workgroups, half of the chip.
   lrnde_ctx* side = nullptr;
-  bool is_side = false, side_busy = false, rec_gr_ready = false, overlap_off = false;
-  // a recorded forward whose t1 came too late to enqueue the sweep beside the solve leaves it to the backward pass, which
-  // enqueues it on the companion's stream once its first adjoint attempt is on the handle's (the host would otherwise
-  // spend the sweep's ~30 launch calls inside the forward, with the device idle)
-  bool sweep_pending = false; int sw_B = 0, sw_reg_type = 0; float sw_t1 = 0.f, sw_abstol = 0.f, sw_reltol = 0.f;
-  std::function<int()> after_first_attempt;  // adj_solve_device calls it once, after enqueuing its first attempt
+  bool is_side = false, side_busy = false, overlap_off = false;
   HipEvent ev_side_local, ev_side_sweep;
   // host-side phase clock of the layer forward (lrnde_host_phases, diagnostics): time points of the call in flight, sums over calls
   std::chrono::steady_clock::time_point hp_t[8];
   double hp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long hp_n = 0;
-  float* tail_copy_dst = nullptr; int tail_copy_slot = -1;  // lrnde_solve: the step that fills this save slot writes it to tail_copy_dst too
-  std::function<int(int, hipEvent_t)> poll_hook;  // lrnde_solve calls it after every status poll (event: that poll's)
-  // lrnde_solve calls it once its last report is in and sol.u[end] is being written to the caller's array by the queued
-  // launches (StepArgs::also_dst), BEFORE its final synchronisation: work enqueued here follows the solve without a host
-  // round trip and is covered by that synchronisation (lrnde_node_forward_record_ce: the classifier head)
-  const float* adj_init_src = nullptr;  // adj_solve_device: its first launch also sets z = [this; 0] (k_adj_begin)
-  std::function<int()> final_hook;
-  bool final_hook_fired = false, last_u_end_done = false;
   bool adj_stage7_reused = false;   // the last stage-7 launch of the adjoint loop took y / h from stage 6's scratch set (its GEMM must too)
   // field kind: 0 the two-layer MLP (lrnde_create), 1 the small Dense chain (lrnde_create_chain, lrnde_chain.hpp).  A
   // chain handle keeps desc.state_dim = D (every state-sized buffer) and its own layer table / weight images here.
@@ -2204,8 +2210,11 @@ int side_quiesce(lrnde_ctx* c) {
 namespace {  // (defined in lrnde_adams.hpp, behind the vector helpers)
 int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, const lrnde_solve_opts* o,
                 const float* saveat_host, int32_t nsave, float* u_saved, float* t_saved_host, int32_t cap_saved,
-                lrnde_stats* st, lrnde_trace_row* trace_host, int32_t cap_trace);
+                lrnde_stats* st, lrnde_trace_row* trace_host, int32_t cap_trace, SolveSide* side);
 }
+// the reverse sweep through the local step (defined behind the backward pass's helpers)
+static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, float dt, float abstol, float reltol,
+                          int32_t reg_type, float eest, float stiff_num, float stiff_den, float* gp);
 
 extern "C" {
 
@@ -2385,7 +2394,7 @@ int lrnde_set_params(lrnde_ctx* c, const float* p, size_t n) {
     return fail(c, LRNDE_BADARG, "parameter count %zu != expected %zu", n, param_count(c));
   HIPCHK(c, hipSetDevice(c->device));
   { const int rq = side_quiesce(c); if (rq) return rq; }
-  c->rec_gr_ready = false; c->sweep_pending = false;
+  c->rec.reset_side_work();
   if (c->field) {
     hipLaunchKernelGGL(k_pack_chain, dim3(128), dim3(256), 0, c->stream, p, c->cd, c->ch_gfloats, c->ch_wf, c->ch_wg);
     HIPCHK(c, hipGetLastError());
@@ -2411,7 +2420,7 @@ int lrnde_set_solver(lrnde_ctx* c, int32_t alg) {
   if (alg < 0 || alg > 2) return fail(c, LRNDE_BADARG, "solver must be 0 (Tsit5), 1 (VCAB3) or 2 (VCABM3)");
   if (c->field && alg != 0) return fail(c, LRNDE_UNSUPPORTED, "VCAB3 / VCABM3 are built for the MLP field's handle: a Dense-chain handle solves with Tsit5 only");
   c->solver_alg = alg;
-  c->rec_valid = false;
+  c->rec.invalidate();
   return LRNDE_OK;
 }
 
@@ -2447,7 +2456,7 @@ int lrnde_init_dt(lrnde_ctx* c, const float* u0, int32_t B, float t0, float tend
   if (!u0 || !dt_host) return fail(c, LRNDE_BADARG, "null pointer");
   if (!(tend > t0)) return fail(c, LRNDE_BADARG, "tspan must be increasing");
   if ((rc = ensure_workspace(c, B))) return rc;
-  c->rec_valid = false;
+  c->rec.invalidate();
   StepArgs a{};
   fill_args(c, a, B);
   a.t0 = t0; a.t1 = tend; a.abstol = abstol; a.reltol = reltol; a.mode = MODE_SINGLE_INIT_DT;
@@ -2495,7 +2504,7 @@ int lrnde_perform_step(lrnde_ctx* c, const float* uprev, const float* k1, int32_
   if (rc) return rc;
   if (!uprev || !k1) return fail(c, LRNDE_BADARG, "null state pointer");
   if ((rc = ensure_workspace(c, B))) return rc;
-  c->rec_valid = false;  // the state workspace a recorded forward left for its backward is overwritten
+  c->rec.invalidate();  // the state workspace a recorded forward left for its backward is overwritten
   StepArgs a{};
   fill_args(c, a, B);
   a.t0 = t; a.t1 = t + 1.0f; a.abstol = abstol; a.reltol = reltol; a.mode = MODE_SINGLE_GIVEN_DT;
@@ -2519,10 +2528,12 @@ int lrnde_perform_step(lrnde_ctx* c, const float* uprev, const float* k1, int32_
   return LRNDE_OK;
 }
 
-int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
-                const lrnde_solve_opts* o, const float* saveat_host, int32_t nsave, float* u_saved,
-                float* t_saved_host, int32_t cap_saved, lrnde_stats* st, lrnde_trace_row* trace_host,
-                int32_t cap_trace) {
+}  // extern "C"
+// lrnde_solve, and the layer forward's solve: side carries what the layer asks of it (null: a plain solve)
+static int solve_impl(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
+                      const lrnde_solve_opts* o, const float* saveat_host, int32_t nsave, float* u_saved,
+                      float* t_saved_host, int32_t cap_saved, lrnde_stats* st, lrnde_trace_row* trace_host,
+                      int32_t cap_trace, SolveSide* side) {
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!u0 || !o || !st) return fail(c, LRNDE_BADARG, "null pointer");
@@ -2533,9 +2544,9 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
     if (!(saveat_host[i] >= saveat_host[i - 1])) return fail(c, LRNDE_BADARG, "saveat must be ascending");
   if (cap_saved > 0 && !u_saved) return fail(c, LRNDE_BADARG, "null save buffer");
   if ((rc = ensure_workspace(c, B))) return rc;
-  if (!c->dense_on) c->rec_valid = false;
+  if (!c->dense_on) c->rec.invalidate();
   if (c->solver_alg != 0)   // n.solver = VCAB3() / VCABM3() (experiments/src/construct.jl:154-164)
-    return adams_solve(c, u0, B, t0, t1, o, saveat_host, nsave, u_saved, t_saved_host, cap_saved, st, trace_host, cap_trace);
+    return adams_solve(c, u0, B, t0, t1, o, saveat_host, nsave, u_saved, t_saved_host, cap_saved, st, trace_host, cap_trace, side);
   const size_t n = (size_t)B * c->desc.state_dim;
   HIPCHK(c, c->saveat_dev.grow(nsave));
   if ((size_t)std::max(cap_saved, 0) > c->tsaved_host.size() || !c->tsaved_host) {
@@ -2561,7 +2572,7 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
   a.cap_saved = cap_saved; a.u_saved = u_saved; a.t_saved = c->tsaved_host.dev();
   // (round 2 enqueued a D2D copy of that slot once the last report was in: 30 us of host latency plus a blit kernel
   //  between the last launch and the caller's synchronisation)
-  a.also_dst = c->tail_copy_dst; a.also_slot = c->tail_copy_dst ? c->tail_copy_slot : -1;
+  a.also_dst = side ? side->tail_dst : nullptr; a.also_slot = a.also_dst ? side->tail_slot : -1;
   a.trace = trace_host ? c->trace_dev : nullptr; a.cap_trace = trace_host ? cap_trace : 0;
   // saveat points at/before t0 are the start value (save_start), as in the oracle
   int skip = 0;
@@ -2632,7 +2643,7 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
       if (wr == WAIT_HUNG) return LRNDE_HUNG(c, "solve loop");
       if (wr == WAIT_DRAINED) { word_ok = false; break; }  // the stream drained and no report came: poll by copies
       ++seen; rem = r.rem;
-      if (c->poll_hook && (rc = c->poll_hook(r.nsaved, nullptr))) return rc;
+      if (side && side->poll && (rc = side->poll(r.nsaved, nullptr))) return rc;
       if (r.status != ST_RUNNING) done = true;
     }
     target = j;
@@ -2654,7 +2665,7 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
     if (pending >= 0) {
       HIPCHK(c, hipEventSynchronize(c->evp[pending]));
       const Ctrl& k = c->ctrl_host[pending];
-      if (c->poll_hook && (rc = c->poll_hook(k.nsaved, c->evp[pending]))) return rc;
+      if (side && side->poll && (rc = side->poll(k.nsaved, c->evp[pending]))) return rc;
       if (k.status != ST_RUNNING) done = true;
       else if (k.dt > 0.f) {
         double est = ceil((double)(t1 - k.t) / (double)k.dt);
@@ -2669,12 +2680,11 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
     if (target < j) target = j;  // never re-label launches already issued
     if (j > hard_cap + 64) break;
   }
-  c->tail_copy_dst = nullptr;
   if (c->time_solves) HIPCHK(c, hipEventRecord(c->ev1, c->stream));
   Ctrl fin;
-  if (word_ok && done && c->final_hook && a.also_dst) {
-    c->final_hook_fired = true;
-    if ((rc = c->final_hook())) return rc;
+  if (word_ok && done && side && side->final && a.also_dst) {
+    side->final_fired = true;
+    if ((rc = side->final())) return rc;
   }
   if (word_ok && done) {  // the finished solve left its control block in host memory (solve_progress)
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2699,20 +2709,25 @@ int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
     return fail(c, st->retcode, "solve stopped with retcode %d at t=%g (iter %d)", st->retcode, (double)fin.t, fin.iter);
   return LRNDE_OK;
 }
+extern "C" {
+
+int lrnde_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1,
+                const lrnde_solve_opts* o, const float* saveat_host, int32_t nsave, float* u_saved,
+                float* t_saved_host, int32_t cap_saved, lrnde_stats* st, lrnde_trace_row* trace_host,
+                int32_t cap_trace) {
+  return solve_impl(c, u0, B, t0, t1, o, saveat_host, nsave, u_saved, t_saved_host, cap_saved, st, trace_host, cap_trace, nullptr);
+}
 
 }  // extern "C"
 // `(n::NeuralODE)(x, ps, st)` for every mode, with or without a user `saveat` (src/layers/neural_ode.jl:56-116).
-// user_sv / nuser: the layer's `saveat` kwarg (ascending); nuser == 0 is the default of :102-116 ([t2] / [t1, t2] / every
-// step).  With a user saveat the :unbiased mode appends t1 for the solve and the returned series leaves every saved
-// time equal to t1 out again (_CorrectedDESolution, src/utils.jl:31-33: `sol.u[t1 .!= sol.t]`); :biased draws t1 from
-// the saved times but the last.  The series (the times the caller sees as sol.t) is kept in c->series_* for the caller
-// and for lrnde_node_backward_recorded_ts.
-static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, float dt, float abstol, float reltol,
-                          int32_t reg_type, float eest, float stiff_num, float stiff_den, float* gp);
+// user_sv / nuser: the layer's `saveat` kwarg (ascending); nuser == 0 is the default of :102-116.  Which saveat the solve
+// gets, which slot holds sol(t1) and what the caller's series leaves out: lrnde_layer_plan.hpp.  The series (the times
+// the caller sees as sol.t) is kept in c->rec.series_* for the caller and for lrnde_node_backward_recorded_ts.
+// ce (may be null): the caller's SolveSide, for its `final` callback and the two result flags.
 static int node_forward_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, float t2,
                              const lrnde_solve_opts* o, int32_t mode, int32_t reg_type, float t1_or_rand,
                              const float* user_sv, int nuser, float* u_end, float* reg_val_host, int32_t* nfe_host,
-                             lrnde_stats* st, float* t1_used_host) {
+                             lrnde_stats* st, float* t1_used_host, SolveSide* ce) {
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!x || !o || !u_end || !st) return fail(c, LRNDE_BADARG, "null pointer");
@@ -2722,20 +2737,19 @@ static int node_forward_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, 
   if (reg_type != LRNDE_REG_ERROR_ESTIMATE && reg_type != LRNDE_REG_STIFFNESS_ESTIMATE)
     return fail(c, LRNDE_BADARG, "regularize must be one of (:error_estimate, :stiffness_estimate)");
   const size_t n = (size_t)B * c->desc.state_dim;
-  // a plain forward overwrites what a recorded one left for lrnde_node_backward_recorded (usave, last_ts, the state
-  // workspace): the record is gone
-  if (!c->dense_on) c->rec_valid = false;
+  NodeRecord& R = c->rec;
+  // a plain forward overwrites what a recorded one left for lrnde_node_backward_recorded (usave, the saved times, the
+  // state workspace): the record is gone
+  if (!c->dense_on) R.invalidate();
   if ((rc = side_quiesce(c))) return rc;
-  c->rec_gr_ready = false; c->sweep_pending = false;
+  R.reset_side_work();
   lrnde_solve_opts oo = *o;
-  size_t need = 3;
-  if (mode == LRNDE_MODE_BIASED) need = (size_t)(oo.maxiters < 510 ? oo.maxiters + 2 : 512);
   if (nuser > 0) {
     if (!user_sv) return fail(c, LRNDE_BADARG, "null saveat");
     for (int i = 1; i < nuser; ++i) if (!(user_sv[i] >= user_sv[i - 1])) return fail(c, LRNDE_BADARG, "saveat must be ascending");
-    need = (size_t)nuser + 3;
   }
-  c->series_idx.clear(); c->series_t.clear();
+  const size_t need = slots_needed(mode, nuser, oo.maxiters);
+  R.series_idx.clear(); R.series_t.clear();
   if (c->usave_slots < need || c->usave_slot_elems != n) {
     HIPCHK(c, c->usave.reset());
     HIPCHK(c, c->usave.once(n * need));
@@ -2744,21 +2758,22 @@ static int node_forward_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, 
   if (reg_val_host) *reg_val_host = 0.0f;
   if (t1_used_host) *t1_used_host = t2;
   std::vector<float> ts(c->usave_slots);
-  float t1 = t2;
+  float t1 = (mode == LRNDE_MODE_UNBIASED) ? t1_or_rand : t2;
+  const SolveSaveat plan = solve_saveat(mode, t1, t2, user_sv, nuser);
+  const std::vector<float>& sv = plan.saveat;
+  oo.save_everystep = plan.save_everystep;
   const float* u1 = nullptr;
-  bool u_end_done = false;  // u_end already copied by the solve (early_slot)
-  c->final_hook_fired = false; c->last_u_end_done = false;
-  auto series_all = [&](int nsaved, float drop) {  // the caller's sol: every saved entry (drop: t1 of the corrected solution)
+  SolveSide own;
+  SolveSide& S = ce ? *ce : own;   // (u_end_done: u_end already copied by the solve, end_slot_known)
+  S.tail_dst = nullptr; S.tail_slot = -1; S.poll = nullptr; S.final_fired = false; S.u_end_done = false;
+  auto series_all = [&](int nsaved) {  // the caller's sol: every saved entry but those of the corrected solution
     for (int i = 0; i < nsaved; ++i)
-      if (!(ts[i] == drop)) { c->series_idx.push_back(i); c->series_t.push_back(ts[i]); }
+      if (series_keeps(plan.needs_correction, t1, ts[i])) { R.series_idx.push_back(i); R.series_t.push_back(ts[i]); }
   };
-  const float no_drop = nanf("");
-  // sol.u[end] is the last save slot; when every saveat time lies in (t0, t2] that slot is known before the solve and
-  // the solve itself copies it to u_end ahead of its final synchronisation (-1: not known, copy afterwards)
-  auto early_slot = [&](const float* sv_, int nsv_) -> int {
-    if (oo.save_start || nsv_ < 1) return -1;
-    for (int i = 0; i < nsv_; ++i) if (!(sv_[i] > t0 && sv_[i] <= t2)) return -1;
-    return nsv_ - 1;
+  auto solve = [&]() {   // (poll captures this function's locals: it does not outlive the solve)
+    const int r = solve_impl(c, x, B, t0, t2, &oo, sv.data(), (int)sv.size(), c->usave, ts.data(), (int)c->usave_slots, st, nullptr, 0, &S);
+    S.poll = nullptr;
+    return r;
   };
   // _get_ode_integrator (neural_ode.jl:33-38): fresh init on (t1, t2); then _perform_step (:77).  `L` is the context the
   // step runs on: the handle itself, or its companion (own stream) while the main solve is still going.
@@ -2785,35 +2800,33 @@ static int node_forward_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, 
     HIPCHK(c, hipMemcpyAsync(L->ctrl_host, L->ctrl + 1, sizeof(Ctrl), hipMemcpyDeviceToHost, L->stream));
     return LRNDE_OK;
   };
+  // the local step's operands (uprev = u(t1), u, k1..k7, g6) stay in the state workspace it ran in and its scalars are
+  // kept here: the regulariser's reverse sweep starts from them without re-running the step or asking the device again
   auto local_results = [&](const Ctrl& k) {
-    c->loc_dt = k.dt; c->loc_eest = k.eest_last; c->loc_snum = k.stiff_num; c->loc_sden = k.stiff_den;
+    R.loc = LocalStep{k.dt, k.eest_last, k.stiff_num, k.stiff_den};
     if (reg_val_host) *reg_val_host = a.want_stiff ? k.reg_stiff : k.reg_error;
     if (nfe_host) *nfe_host = st->nf + k.nf;  // sol.destats.nf + (6 + 3), perform_step.jl:31
   };
-  if (mode == LRNDE_MODE_NONE) {  // _vanilla_node_fallback, neural_ode.jl:56-60
-    const float sv1[1] = {t2};
-    oo.save_everystep = 0;
-    const int early = early_slot(nuser ? user_sv : sv1, nuser ? nuser : 1);
-    if (early >= 0) { c->tail_copy_dst = u_end; c->tail_copy_slot = early; }
-    rc = lrnde_solve(c, x, B, t0, t2, &oo, nuser ? user_sv : sv1, nuser ? nuser : 1, c->usave, ts.data(), (int)c->usave_slots, st, nullptr, 0);
-    c->tail_copy_dst = nullptr;
-    if (rc) return rc;
-    if (st->nsaved < 1) return fail(c, LRNDE_BADARG, "the solve saved nothing (saveat outside the time span)");
-    series_all(st->nsaved, no_drop);
-    c->last_ts.assign(ts.begin(), ts.begin() + st->nsaved);
-    if (nfe_host) *nfe_host = st->nf;
-    c->last_u_end_done = (st->nsaved - 1 == early);
-    if (st->nsaved - 1 != early) {
+  auto u_end_after = [&]() -> int {   // sol.u[end] from its save slot, when the solve did not copy it
+    if (!S.u_end_done)
       HIPCHK(c, hipMemcpyAsync(u_end, c->usave + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+    return LRNDE_OK;
+  };
+  if (mode == LRNDE_MODE_NONE) {  // _vanilla_node_fallback, neural_ode.jl:56-60
+    const int early = end_slot_known(sv.data(), (int)sv.size(), t0, t2, oo.save_start);
+    if (early >= 0) { S.tail_dst = u_end; S.tail_slot = early; }
+    if ((rc = solve())) return rc;
+    if (st->nsaved < 1) return fail(c, LRNDE_BADARG, "the solve saved nothing (saveat outside the time span)");
+    series_all(st->nsaved);
+    R.ts.assign(ts.begin(), ts.begin() + st->nsaved);
+    if (nfe_host) *nfe_host = st->nf;
+    S.u_end_done = (st->nsaved - 1 == early);
+    if (!S.u_end_done) {
+      if ((rc = u_end_after())) return rc;
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return LRNDE_OK;
   } else if (mode == LRNDE_MODE_UNBIASED) {  // neural_ode.jl:68-84, saveat = [t1, t2] or vcat(user saveat, t1)
-    t1 = t1_or_rand;
-    std::vector<float> sv;
-    if (nuser) { sv.assign(user_sv, user_sv + nuser); sv.insert(std::upper_bound(sv.begin(), sv.end(), t1), t1); }
-    else { sv.push_back(t1); sv.push_back(t2); }
-    oo.save_everystep = 0;
     // Overlap (unsharded handles): t1 is known before the solve, so as soon as a status poll shows sol(t1) in its save slot
     // the local step is enqueued on the companion's stream — and, recording, the regulariser's reverse sweep once the
     // step's scalars have come back — while this stream goes on with [t1, t2].  LRNDE_NO_OVERLAP=1: everything in order
@@ -2821,19 +2834,14 @@ static int node_forward_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, 
     const bool no_overlap = opt(OPT_NO_OVERLAP) != 0;
     lrnde_ctx* sd = nullptr;
     int side_state = 0;  // 0: nothing enqueued, 1: local step enqueued, 2: + sweep
-    // save slot of the LAST saveat entry equal to t1: its index among the entries inside the span (those at or before t0 are
-    // the start value and take no slot), behind the save_start slot if there is one
-    const int kpos = (int)(std::upper_bound(sv.begin(), sv.end(), t1) - sv.begin()) - 1;
-    int nskip = 0;
-    while (nskip < (int)sv.size() && sv[nskip] <= t0) ++nskip;
-    const int pos = (kpos >= nskip) ? kpos - nskip + (oo.save_start ? 1 : 0) : -1;
+    const int pos = slot_of_t1(sv.data(), (int)sv.size(), t0, t1, oo.save_start);
     auto enqueue_sweep = [&]() -> int {
       const Ctrl k = sd->ctrl_host[0];
       const int r = step_reg_sweep(sd, sd->state, B, t1, k.dt, oo.abstol, oo.reltol, reg_type, k.eest_last, k.stiff_num, k.stiff_den,
-                                   c->rec_gr);
+                                   R.gr);
       if (r) { c->err = sd->err; return r; }
       HIPCHK(c, hipEventRecord(c->ev_side_sweep, sd->stream));
-      c->rec_gr_ready = true;
+      R.gr_ready = true;
       side_state = 2;
       return LRNDE_OK;
     };
@@ -2850,60 +2858,47 @@ static int node_forward_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, 
       }
       return LRNDE_OK;
     };
-    if (!sharded(c) && !no_overlap && !c->overlap_off && pos >= 0 && sv[kpos] == t1) {
+    if (!sharded(c) && !no_overlap && !c->overlap_off && pos >= 0) {
       if ((rc = side_get(c, B, &sd))) return rc;
-      c->poll_hook = [&](int nsaved_done, hipEvent_t ev) { return side_advance(nsaved_done, ev); };
+      S.poll = [&](int nsaved_done, hipEvent_t ev) { return side_advance(nsaved_done, ev); };
     }
-    const int early = early_slot(sv.data(), (int)sv.size());
-    if (early >= 0) { c->tail_copy_dst = u_end; c->tail_copy_slot = early; }
-    rc = lrnde_solve(c, x, B, t0, t2, &oo, sv.data(), (int)sv.size(), c->usave, ts.data(), (int)c->usave_slots, st, nullptr, 0);
-    c->poll_hook = nullptr; c->tail_copy_dst = nullptr;
-    if (rc) return rc;
-    u_end_done = (st->nsaved - 1 == early);
-    c->last_u_end_done = u_end_done;
+    const int early = end_slot_known(sv.data(), (int)sv.size(), t0, t2, oo.save_start);
+    if (early >= 0) { S.tail_dst = u_end; S.tail_slot = early; }
+    if ((rc = solve())) return rc;
+    S.u_end_done = (st->nsaved - 1 == early);
     int i1 = -1;
     for (int i = 0; i < st->nsaved; ++i) if (ts[i] == t1) i1 = i;   // the last entry saved at t1 is sol(t1)
     if (i1 < 0) return fail(c, LRNDE_BADARG, "t1 = %g is not inside the time span", (double)t1);
     u1 = c->usave + (size_t)i1 * n;
-    c->last_i1 = i1;
-    series_all(st->nsaved, nuser ? t1 : no_drop);
+    R.i1 = i1;
+    series_all(st->nsaved);
     if (sd && i1 == pos) {
-      c->last_ts.assign(ts.begin(), ts.begin() + st->nsaved);
-      c->last_t1 = t1;
-      if (!u_end_done)
-        HIPCHK(c, hipMemcpyAsync(u_end, c->usave + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+      R.ts.assign(ts.begin(), ts.begin() + st->nsaved);
+      if ((rc = u_end_after())) return rc;
       if (t1_used_host) *t1_used_host = t1;
       if ((rc = side_advance(st->nsaved, nullptr))) return rc;   // (a t1 reported last: the handle's stream is idle by now)
       HIPCHK(c, hipEventSynchronize(c->ev_side_local));
       local_results(sd->ctrl_host[0]);
-      if (c->dense_on && side_state == 1) {  // too late to run beside the solve: the backward pass enqueues it (sweep_pending)
-        c->sweep_pending = true; c->sw_B = B; c->sw_reg_type = reg_type; c->sw_t1 = t1; c->sw_abstol = oo.abstol; c->sw_reltol = oo.reltol;
-      }
+      // too late to run beside the solve: the backward pass enqueues it (NodeRecord::sweep_pending)
+      if (c->dense_on && side_state == 1) R.sweep_pending = true;
       if (!c->dense_on || side_state == 1) c->side_busy = false;  // nothing of the companion's is left in flight
-      if (!u_end_done) HIPCHK(c, hipStreamSynchronize(c->stream));
+      if (!S.u_end_done) HIPCHK(c, hipStreamSynchronize(c->stream));
       return LRNDE_OK;
     }
     // (not reached with a companion step in flight unless the slot prediction was wrong: then nothing of it may be used)
     if ((rc = side_quiesce(c))) return rc;
-    c->rec_gr_ready = false; c->sweep_pending = false;
+    R.reset_side_work();
   } else {  // neural_ode.jl:88-100, saveat = [] => every accepted step (or the user's saveat)
-    oo.save_everystep = nuser ? 0 : 1;
-    rc = lrnde_solve(c, x, B, t0, t2, &oo, nuser ? user_sv : nullptr, nuser, c->usave, ts.data(), (int)c->usave_slots, st, nullptr, 0);
-    if (rc) return rc;
+    if ((rc = solve())) return rc;
     if (st->nsaved < 2) return fail(c, LRNDE_BADARG, "biased mode needs at least two saved times");
-    const int mm = st->nsaved - 1;
-    int idx = (int)(t1_or_rand * (float)mm);
-    if (idx >= mm) idx = mm - 1;
-    if (idx < 0) idx = 0;
+    const int idx = biased_pick(t1_or_rand, st->nsaved - 1);
     t1 = ts[idx];
     u1 = c->usave + (size_t)idx * n;
-    c->last_i1 = idx;
-    series_all(st->nsaved, no_drop);
+    R.i1 = idx;
+    series_all(st->nsaved);
   }
-  c->last_ts.assign(ts.begin(), ts.begin() + st->nsaved);
-  c->last_t1 = t1;
-  if (!u_end_done)
-    HIPCHK(c, hipMemcpyAsync(u_end, c->usave + (size_t)(st->nsaved - 1) * n, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+  R.ts.assign(ts.begin(), ts.begin() + st->nsaved);
+  if ((rc = u_end_after())) return rc;
   if (t1_used_host) *t1_used_host = t1;
   // the local step in order on the handle's stream (biased t1, sharded handles, LRNDE_NO_OVERLAP)
   if ((rc = enqueue_local(c, u1, t1))) return rc;
@@ -2919,7 +2914,7 @@ int lrnde_node_forward(lrnde_ctx* c, const float* x, int32_t B, float t0, float 
                        float* t1_used_host) {
   if (!c) return LRNDE_BADARG;
   HPT(c, 0);
-  const int rc = node_forward_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, nullptr, 0, u_end, reg_val_host, nfe_host, st, t1_used_host);
+  const int rc = node_forward_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, nullptr, 0, u_end, reg_val_host, nfe_host, st, t1_used_host, nullptr);
   HPT(c, 4);
   if (rc == LRNDE_OK) {
     for (int i = 1; i <= 4; ++i) c->hp_sum[i] += std::chrono::duration<double, std::micro>(c->hp_t[i] - c->hp_t[i - 1]).count();
@@ -4166,10 +4161,10 @@ int adj_report_block(lrnde_ctx* c) {
   return LRNDE_OK;
 }
 // the caller's side enqueues, once: the first attempt is enqueued and the handle's stream holds ~150 us of work
-int adj_after_first_attempt(lrnde_ctx* c) {
-  if (!c->after_first_attempt) return LRNDE_OK;
-  auto fn = std::move(c->after_first_attempt);
-  c->after_first_attempt = nullptr;
+int adj_after_first_attempt(std::function<int()>& after_first_attempt) {
+  if (!after_first_attempt) return LRNDE_OK;
+  auto fn = std::move(after_first_attempt);
+  after_first_attempt = nullptr;
   return fn();
 }
 // Await the report of attempt j - 1's first launch (seq0 + j): bounded, a faulted or hung queue must not hang the caller.
@@ -4203,8 +4198,11 @@ int adj_finish(lrnde_ctx* c, AdjVec& v, const AdjReport& fin, int extra_nf, cons
   return st->retcode;
 }
 
+// init_src (may be null): the first launch also sets z = [init_src; 0] (k_adj_begin).  after_first_attempt (may be empty):
+// called once, after the first attempt has been enqueued.
 int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float abstol, float reltol, int maxiters, int exact_pow,
-                     const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st) {
+                     const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st,
+                     const float* init_src, std::function<int()>& after_first_attempt) {
   int rc;
   memset(st, 0, sizeof(*st));
   if (sharded(c)) return fail(c, LRNDE_UNSUPPORTED, "sharded handles use the host-controlled adjoint loop");
@@ -4216,7 +4214,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
   HIPCHK(c, c->adj_ev[1].create(hipEventDisableTiming));
   if ((rc = adj_report_block(c))) return rc;
   if (tstops.size() > c->adj_stops.size()) HIPCHK(c, c->adj_stops.grow(tstops.size() + 8));
-  const bool one_begin = c->adj_init_src != nullptr && tstops.size() <= 8;
+  const bool one_begin = init_src != nullptr && tstops.size() <= 8;
   if (!tstops.empty() && !one_begin)
     HIPCHK(c, hipMemcpyAsync(c->adj_stops, tstops.data(), sizeof(float) * tstops.size(), hipMemcpyHostToDevice, c->stream));
   AdjArgs g{};
@@ -4268,20 +4266,19 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
   if (one_begin) {
     AdjBegin b{};
     memset(&b, 0, sizeof(b));
-    b.z = v.z; b.src = c->adj_init_src; b.n = v.n_lam; b.N = v.N; b.ctl = c->adj_ctl; b.s0 = s0;
+    b.z = v.z; b.src = init_src; b.n = v.n_lam; b.N = v.N; b.ctl = c->adj_ctl; b.s0 = s0;
     b.stops = c->adj_stops; b.nstops = (int)tstops.size();
     for (size_t k = 0; k < tstops.size(); ++k) b.sv[k] = tstops[k];
     int nb = (int)((v.N + 255) / 256); if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_adj_begin, dim3(nb), dim3(256), 0, c->stream, b);
   } else {
-    if (c->adj_init_src) {
+    if (init_src) {
       HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * v.N, c->stream));
-      HIPCHK(c, hipMemcpyAsync(v.z, c->adj_init_src, sizeof(float) * v.n_lam, hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(v.z, init_src, sizeof(float) * v.n_lam, hipMemcpyDeviceToDevice, c->stream));
     }
     hipLaunchKernelGGL(k_adj_ctrl_init, dim3(1), dim3(1), 0, c->stream, c->adj_ctl, s0);
   }
   ++c->adj_launches;
-  c->adj_init_src = nullptr;
   size_t iseg = 0;
   while (iseg < impulses.size() && impulses[iseg].s <= s0) ++iseg;  // a cotangent at the start time is the caller's lambda(s0)
   bool first_seg = true;
@@ -4317,7 +4314,6 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
       hipStreamSynchronize(c->stream);
       if (c->adj_stream2) hipStreamSynchronize(c->adj_stream2);
       c->adj_seq += j + 1;
-      c->after_first_attempt = nullptr;
       return code;
     };
     // maybe_last: the attempt whose prologue reported last reaches the end of the segment if it is accepted.  The next
@@ -4358,7 +4354,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
       if ((rc = adj_enqueue_eval(c, B, g, ADJ_STAGE, 2, j, false, ADJ_STAGE, 1, sA, 0))) return bail(rc);
       const bool rest_ahead = !maybe_last;
       if (rest_ahead && (rc = enqueue_rest(j))) return bail(rc);
-      if ((rc = adj_after_first_attempt(c))) return bail(rc);
+      if ((rc = adj_after_first_attempt(after_first_attempt))) return bail(rc);
       ++j;
       if ((rc = adj_await_report(c, "adjoint loop", g.seq0, j, bail, trace, &fin))) return rc;
       if (fin.status != ST_RUNNING) done = true;
@@ -4419,7 +4415,8 @@ bool chadj_fits(const lrnde_ctx* c, int B, ChAdjPlan* pl) {
 // and a mu-family launch) + 2 per attempted step + 2 (the launch pair whose prologue reports the end) here; the caller
 // adds k_adj_out and at most two k_axpy for cotangents at the two end points of the solve.
 int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float abstol, float reltol, int maxiters, int exact_pow,
-                       const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st) {
+                       const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st,
+                       std::function<int()>& after_first_attempt) {
   int rc;
   memset(st, 0, sizeof(*st));
   ChAdjPlan pl{};
@@ -4489,14 +4486,13 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
   auto bail = [&](int code) -> int {
     hipStreamSynchronize(c->stream);
     c->adj_seq += j + 1;
-    c->after_first_attempt = nullptr;
     return code;
   };
   AdjTraceCursor trace;
   AdjReport fin{};
   while (!done) {
     if ((rc = enqueue(j, CHADJ_STEP))) return bail(rc);
-    if ((rc = adj_after_first_attempt(c))) return bail(rc);
+    if ((rc = adj_after_first_attempt(after_first_attempt))) return bail(rc);
     ++j;
     if ((rc = adj_await_report(c, "chain adjoint loop", g.seq0, j, bail, trace, &fin))) return rc;
     if (fin.status != ST_RUNNING) done = true;
@@ -4516,12 +4512,6 @@ extern "C" {
 
 // gradient of the local regularisation value w.r.t. p (reverse sweep through one Tsit5 step with
 // k1, dt, uprev constant: src/layers/neural_ode.jl:40, src/perform_step.jl:3-47).  gp: device (P).
-}  // extern "C"
-// the reverse sweep proper, enqueued without a host synchronisation: the forward step's state (uprev, u, k1..k7, g6) is
-// in the state workspace (by stream order), its scalars (EEst, the two stiffness rms values) are given
-static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, float dt, float abstol, float reltol,
-                          int32_t reg_type, float eest, float stiff_num, float stiff_den, float* gp);
-extern "C" {
 int lrnde_step_reg_grad(lrnde_ctx* c, const float* uprev, const float* k1, int32_t B, float t, float dt,
                         float abstol, float reltol, int32_t reg_type, float* gp, float* reg_val_host) {
   int rc = check_ready(c, B);
@@ -4537,6 +4527,8 @@ int lrnde_step_reg_grad(lrnde_ctx* c, const float* uprev, const float* k1, int32
   return LRNDE_OK;
 }
 }  // extern "C"
+// the reverse sweep proper, enqueued without a host synchronisation: the forward step's state (uprev, u, k1..k7, g6) is
+// in the state workspace (by stream order), its scalars (EEst, the two stiffness rms values) are given
 static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, float dt, float abstol, float reltol,
                           int32_t reg_type, float eest, float stiff_num, float stiff_den, float* gp) {
   int rc;
@@ -4593,26 +4585,26 @@ static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, 
   }
   return LRNDE_OK;
 }
-extern "C" {
 
 // node_forward that also keeps what the backward pass needs: the dense record of every accepted
 // step (retry with a larger record if it overflows) and the solve's arguments.
-}  // extern "C"
 static int node_forward_record_impl(lrnde_ctx* c, const float* x, int32_t B, float t0, float t2, const lrnde_solve_opts* o,
                                     int32_t mode, int32_t reg_type, float t1_or_rand, const float* user_sv, int nuser,
-                                    float* u_end, float* reg_val_host, int32_t* nfe_host, lrnde_stats* st, float* t1_used_host) {
+                                    float* u_end, float* reg_val_host, int32_t* nfe_host, lrnde_stats* st, float* t1_used_host,
+                                    SolveSide* ce) {
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!x || !o || !u_end || !reg_val_host || !nfe_host || !st) return fail(c, LRNDE_BADARG, "null pointer");
   const size_t n = (size_t)B * c->desc.state_dim;
-  c->rec_valid = false;
+  NodeRecord& R = c->rec;
+  R.invalidate();
   float t1 = t2;
-  if (c->rec_n != n) {  // the regulariser's parameter gradient (written by the forward's overlapped sweep, or by the backward)
+  if (R.gr_n != n) {  // the regulariser's parameter gradient (written by the forward's overlapped sweep, or by the backward)
     if ((rc = side_quiesce(c))) return rc;
-    c->rec_n = 0;
-    HIPCHK(c, c->rec_gr.reset());
-    HIPCHK(c, c->rec_gr.once(param_count(c)));
-    c->rec_n = n;
+    R.gr_n = 0;
+    HIPCHK(c, R.gr.reset());
+    HIPCHK(c, R.gr.once(param_count(c)));
+    R.gr_n = n;
   }
   for (int attempt = 0;; ++attempt) {
     if (c->dense_cap == 0 || c->dense_n != n) {
@@ -4624,20 +4616,15 @@ static int node_forward_record_impl(lrnde_ctx* c, const float* x, int32_t B, flo
       c->dense_n = n;
     }
     c->dense_on = true;
-    rc = node_forward_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, user_sv, nuser, u_end, reg_val_host, nfe_host, st, &t1);
+    rc = node_forward_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, user_sv, nuser, u_end, reg_val_host, nfe_host, st, &t1, ce);
     c->dense_on = false;
     if (rc == LRNDE_CAPACITY && attempt < 8) { c->dense_cap *= 2; c->dense_n = 0; continue; }
     break;
   }
   if (rc) return rc;
   if (t1_used_host) *t1_used_host = t1;
-  if (mode != LRNDE_MODE_NONE) {
-    // the local step's operands (uprev = u(t1), u, k1..k7, g6) stay in the state workspace it ran in and its scalars are
-    // kept here: the regulariser's reverse sweep starts from them without re-running the step or asking the device again
-    c->rec_dt1 = c->loc_dt; c->rec_eest = c->loc_eest; c->rec_snum = c->loc_snum; c->rec_sden = c->loc_sden;
-  }
-  c->rec_valid = true; ++c->rec_gen; c->rec_B = B; c->rec_t0 = t0; c->rec_t2 = t2; c->rec_opts = *o; c->rec_mode = mode;
-  c->rec_reg_type = reg_type; c->rec_t1 = t1; c->rec_naccept = st->naccept;
+  R.set(B, mode, reg_type, t0, t2, t1, *o);
+  R.naccept = st->naccept;
   return LRNDE_OK;
 }
 extern "C" {
@@ -4646,7 +4633,7 @@ int lrnde_node_forward_record(lrnde_ctx* c, const float* x, int32_t B, float t0,
                               int32_t mode, int32_t reg_type, float t1_or_rand, float* u_end, float* reg_val_host,
                               int32_t* nfe_host, lrnde_stats* st, float* t1_used_host) {
   return node_forward_record_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, nullptr, 0, u_end, reg_val_host, nfe_host, st,
-                                  t1_used_host);
+                                  t1_used_host, nullptr);
 }
 
 // the recorded forward with the layer's `saveat` kwarg: the solution the caller sees (sol.u / sol.t after
@@ -4663,41 +4650,42 @@ int lrnde_node_forward_record_ts(lrnde_ctx* c, const float* x, int32_t B, float 
   HIPCHK(c, u_end.once(n));
   float regv = 0.f; int nfe = 0;
   int rc = node_forward_record_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, saveat_host, nsave, u_end, &regv, &nfe, st,
-                                    t1_used_host);
+                                    t1_used_host, nullptr);
   (void)u_end.reset();
   if (rc) return rc;
   if (reg_val_host) *reg_val_host = regv;
   if (nfe_host) *nfe_host = nfe;
-  const int ns = (int)c->series_idx.size();
+  const int ns = (int)c->rec.series_idx.size();
   *nseries_host = ns;
   if (ns > cap_series) return fail(c, LRNDE_CAPACITY, "series buffer too small (%d > %d)", ns, cap_series);
   for (int i = 0; i < ns; ++i) {
-    HIPCHK(c, hipMemcpyAsync(u_series + (size_t)i * n, c->usave + (size_t)c->series_idx[i] * n, sizeof(float) * n,
+    HIPCHK(c, hipMemcpyAsync(u_series + (size_t)i * n, c->usave + (size_t)c->rec.series_idx[i] * n, sizeof(float) * n,
                              hipMemcpyDeviceToDevice, c->stream));
-    t_series_host[i] = c->series_t[i];
+    t_series_host[i] = c->rec.series_t[i];
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return LRNDE_OK;
 }
 
+}  // extern "C"
 // backward of  loss = <du_end, sol.u[end]> + w_reg * reg_val  from the record of the last
 // lrnde_node_forward_record: continuous adjoint (InterpolatingAdjoint restatement) + the regulariser's
 // reverse sweep.  dx (B,D), dp (P): device.
-}  // extern "C"
 // du_end: the cotangent of sol.u[end] (nser == 0), or du_series: one cotangent per state of the caller's series
-// (c->series_t, ascending): each enters the reversed solve as an impulse on lambda at its time
+// (c->rec.series_t, ascending): each enters the reversed solve as an impulse on lambda at its time
 static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_end, const float* du_series, int nser,
                                        float w_reg, float* dx, float* dp, lrnde_stats* st_bwd) {
   int rc = check_ready(c, B);
   if (rc) return rc;
   if ((!du_end && !du_series) || !dx || !dp || !st_bwd) return fail(c, LRNDE_BADARG, "null pointer");
-  if (!c->rec_valid || c->rec_B != B) return fail(c, LRNDE_BADARG, "no forward record for this batch (call lrnde_node_forward_record first)");
-  const lrnde_solve_opts* o = &c->rec_opts;
-  const float t0 = c->rec_t0, t2 = c->rec_t2, t1 = c->rec_t1;
-  const int mode = c->rec_mode, reg_type = c->rec_reg_type;
+  NodeRecord& R = c->rec;
+  if (!R.valid || R.B != B) return fail(c, LRNDE_BADARG, "no forward record for this batch (call lrnde_node_forward_record first)");
+  const lrnde_solve_opts* o = &R.opts;
+  const float t0 = R.t0, t2 = R.t2, t1 = R.t1;
+  const int mode = R.mode, reg_type = R.reg_type;
   const size_t n = (size_t)B * c->desc.state_dim;
   const size_t P = param_count(c);
-  const int nsteps = c->rec_naccept;
+  const int nsteps = R.naccept;
   // adjoint solve on z = [lambda; mu] in s = -t from -t2 to -t0, tstops at the saved times
   const size_t N = n + P;
   AdjVec v;
@@ -4711,9 +4699,9 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   if (!begin_in_solve) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
   std::vector<AdjImpulse> impulses;  // ascending in s = -t
   if (du_series) {
-    if (nser != (int)c->series_t.size()) return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, c->series_t.size());
+    if (nser != (int)R.series_t.size()) return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
     for (int i = nser - 1; i >= 0; --i) {
-      const float tv = c->series_t[i];
+      const float tv = R.series_t[i];
       const float* du = du_series + (size_t)i * n;
       if (tv >= t2) {  // cotangents at the end time: lambda(s0)
         const float* gi[1] = {du}; const float one = 1.0f;
@@ -4726,33 +4714,31 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     HIPCHK(c, hipMemcpyAsync(v.z, du_end, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   }
   std::vector<float> stops;
-  if (mode != LRNDE_MODE_NONE || du_series)
-    for (int i = (int)c->last_ts.size() - 1; i >= 0; --i) {
-      const float tv = c->last_ts[i];
-      if (tv > t0 && tv < t2) stops.push_back(-tv);
-    }
-  auto pending_sweep = [c, t1]() -> int {  // the forward left the regulariser's sweep to us (lrnde_ctx::sweep_pending)
+  if (mode != LRNDE_MODE_NONE || du_series) stops = backward_stops(R.ts, t0, t2);
+  auto pending_sweep = [c]() -> int {  // the forward left the regulariser's sweep to us (NodeRecord::sweep_pending)
     lrnde_ctx* sd = c->side;
-    c->sweep_pending = false;
+    NodeRecord& R = c->rec;
+    R.sweep_pending = false;
     c->side_busy = true;
-    const int r = step_reg_sweep(sd, sd->state, c->sw_B, t1, c->rec_dt1, c->sw_abstol, c->sw_reltol, c->sw_reg_type, c->rec_eest,
-                                 c->rec_snum, c->rec_sden, c->rec_gr);
+    const int r = step_reg_sweep(sd, sd->state, R.B, R.t1, R.loc.dt, R.opts.abstol, R.opts.reltol, R.reg_type, R.loc.eest,
+                                 R.loc.snum, R.loc.sden, R.gr);
     if (r) { c->err = sd->err; return r; }
     HIPCHK(c, hipEventRecord(c->ev_side_sweep, sd->stream));
-    c->rec_gr_ready = true;
+    R.gr_ready = true;
     return LRNDE_OK;
   };
-  const bool want_sweep = mode != LRNDE_MODE_NONE && w_reg != 0.0f && c->sweep_pending && c->side != nullptr;
+  const bool want_sweep = mode != LRNDE_MODE_NONE && w_reg != 0.0f && R.sweep_pending && c->side != nullptr;
+  std::function<int()> after_first_attempt;  // the device loops call it once, after enqueuing their first attempt
   if (want_sweep) {
-    if (vjp_uses_qtile(c, B) && !sharded(c) && !adj_host) c->after_first_attempt = pending_sweep;
+    if (vjp_uses_qtile(c, B) && !sharded(c) && !adj_host) after_first_attempt = pending_sweep;
     else if ((rc = pending_sweep())) return rc;
   }
   if (chain_loop) {
-    rc = chadj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd);
+    rc = chadj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
+                            after_first_attempt);
   } else if (dev_loop) {
-    c->adj_init_src = begin_in_solve ? du_end : nullptr;
-    rc = adj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd);
-    c->adj_init_src = nullptr;
+    rc = adj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
+                          begin_in_solve ? du_end : nullptr, after_first_attempt);
   } else {
     std::vector<float> dts(nsteps), dds(nsteps);
     HIPCHK(c, hipMemcpy(dts.data(), c->dense_t, sizeof(float) * nsteps, hipMemcpyDeviceToHost));
@@ -4763,7 +4749,6 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     rc = vec_tsit5_solve(c, v, rhs, rhs_fused, vjp_uses_qtile(c, B), -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow,
                          stops, impulses, st_bwd);
   }
-  c->after_first_attempt = nullptr;
   // (+ k_adj_out; what the regulariser's sweep enqueues behind the solve is not the solve's)
   struct InfoGuard { lrnde_ctx* c; int n; ~InfoGuard() { c->adj_launches = n; } } info_guard{c, c->adj_launches + 1};
   if (rc) return fail(c, rc, "adjoint solve stopped with retcode %d", rc);
@@ -4779,8 +4764,8 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   }
   // regulariser: dp += w_reg * d reg_val / d p   (no gradient w.r.t. x: test/runtests.jl:129)
   if (mode != LRNDE_MODE_NONE && w_reg != 0.0f) {
-    float* gr = c->rec_gr;
-    if (c->rec_gr_ready) {
+    float* gr = R.gr;
+    if (R.gr_ready) {
       // the forward already ran the sweep on the companion's stream (it depends on the forward alone): wait for it there
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_side_sweep, 0));
       rc = adj_out(gr);
@@ -4790,15 +4775,15 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
       // them, nothing is re-run and nothing is read back.
       // (the sweep works in the adjoint vector's buffers: lambda and mu leave them first)
       if ((rc = adj_out(nullptr))) return rc;
-      rc = step_reg_sweep(c, c->state, B, t1, c->rec_dt1, o->abstol, o->reltol, reg_type, c->rec_eest, c->rec_snum, c->rec_sden, gr);
+      rc = step_reg_sweep(c, c->state, B, t1, R.loc.dt, o->abstol, o->reltol, reg_type, R.loc.eest, R.loc.snum, R.loc.sden, gr);
       if (!rc) { const float* g1[2] = {dp, gr}; const float cc[2] = {1.0f, w_reg}; rc = vec_axpy(c, dp, nullptr, 1.0f, 2, g1, cc, P); }
     }
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  if (c->rec_gr_ready && mode != LRNDE_MODE_NONE && w_reg != 0.0f) c->side_busy = false;  // waited for above, then synchronised
-  c->rec_gr_ready = false;
-  c->rec_valid = false;  // the regulariser sweep reused the state workspace
+  if (R.gr_ready && mode != LRNDE_MODE_NONE && w_reg != 0.0f) c->side_busy = false;  // waited for above, then synchronised
+  R.gr_ready = false;
+  R.invalidate();  // the regulariser sweep reused the state workspace
   return LRNDE_OK;
 }
 extern "C" {
@@ -4913,12 +4898,12 @@ int lrnde_node_forward_record_ce(lrnde_ctx* c, const float* x, int32_t B, float 
   if (!c) return LRNDE_BADARG;
   if (!loss_host || !u_end) return fail(c, LRNDE_BADARG, "null pointer");
   // the head's launches go into the queue as soon as the solve's last report is in, ahead of its final synchronisation
-  c->final_hook = [&]() { return cls_enqueue(c, u_end, B, pc, K, labels, logits, du, dpc); };
+  SolveSide ce;
+  ce.final = [&]() { return cls_enqueue(c, u_end, B, pc, K, labels, logits, du, dpc); };
   int rc = node_forward_record_impl(c, x, B, t0, t2, o, mode, reg_type, t1_or_rand, nullptr, 0, u_end, reg_val_host, nfe_host, st,
-                                    t1_used_host);
-  c->final_hook = nullptr;
+                                    t1_used_host, &ce);
   if (rc) return rc;
-  if (!(c->final_hook_fired && c->last_u_end_done)) {  // (sol.u[end] reached the caller's array by a copy after the solve)
+  if (!(ce.final_fired && ce.u_end_done)) {  // (sol.u[end] reached the caller's array by a copy after the solve)
     if ((rc = cls_enqueue(c, u_end, B, pc, K, labels, logits, du, dpc))) return rc;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));   // (returns at once when the solve's own synchronisation covered the head)
@@ -5000,7 +4985,7 @@ int lrnde_adjoint_trace_rows(lrnde_ctx* c, int32_t* n_host) {
 // return the gradients of the OTHER input without an error (the C side can only see that some record is valid).
 int lrnde_record_generation(lrnde_ctx* c, uint64_t* gen_host) {
   if (!c || !gen_host) return LRNDE_BADARG;
-  *gen_host = c->rec_valid ? c->rec_gen : 0;   // 0: no usable record
+  *gen_host = c->rec.generation();   // 0: no usable record
   return LRNDE_OK;
 }
 int lrnde_sde_record_generation(lrnde_sde* s, uint64_t* gen_host) {

@@ -289,16 +289,13 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
     return e;
   };
   float t1 = t2;
-  std::vector<float> sv;   // the solve's saveat
-  bool needs_correction = false, everystep = false;
   if (mode == LRNDE_MODE_UNBIASED) {
     t1 = t1_or_rand;
     if (!(t1 >= t0 && t1 <= t2)) return fail(c, LRNDE_BADARG, "t1 outside tspan");
-    if (nsave > 0) { sv.assign(saveat_host, saveat_host + nsave); sv.push_back(t1); std::stable_sort(sv.begin(), sv.end()); needs_correction = true; }
-    else { sv = {t1, t2}; }
-  } else if (nsave > 0) sv.assign(saveat_host, saveat_host + nsave);
-  else if (mode == LRNDE_MODE_BIASED) everystep = true;
-  else sv = {t2};
+  }
+  const SolveSaveat plan = solve_saveat(mode, t1, t2, saveat_host, nsave);
+  const std::vector<float>& sv = plan.saveat;   // the solve's saveat
+  const bool everystep = plan.save_everystep != 0;
   bool with_start = save_start > 0;
   if (save_start < 0) with_start = everystep || (!sv.empty() && sv.front() == t0);   // DiffEq: save_everystep || isempty(saveat) || tspan[1] in saveat
   std::vector<SdeSeriesEntry> sol;
@@ -313,10 +310,7 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   if (mode == LRNDE_MODE_BIASED) {      // :114-115  t1 = rand(rng, sol.t[1:(end - 1)])
     const int m = (int)sol.size() - 1;
     if (m < 1) return fail(c, LRNDE_BADARG, ":biased needs at least two saved times");
-    int idx = (int)(t1_or_rand * (float)m);
-    if (idx >= m) idx = m - 1;
-    if (idx < 0) idx = 0;
-    e1 = sol[idx]; t1 = e1.t;
+    e1 = sol[biased_pick(t1_or_rand, m)]; t1 = e1.t;
   } else if (mode == LRNDE_MODE_UNBIASED) {
     e1 = entry_at(t1);
   }
@@ -371,7 +365,7 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   }
   // the caller's view: _CorrectedDESolution drops the entries at t1 (src/utils.jl:31-33: `sol.u[t1 .!= sol.t]`)
   r.series.clear();
-  for (const SdeSeriesEntry& e : sol) if (!(needs_correction && e.t == t1)) r.series.push_back(e);
+  for (const SdeSeriesEntry& e : sol) if (series_keeps(plan.needs_correction, t1, e.t)) r.series.push_back(e);
   const int ns = (int)r.series.size();
   *nseries_host = ns;
   if (ns > cap_series) return fail(c, LRNDE_CAPACITY, "series buffer too small (%d > %d)", ns, cap_series);
