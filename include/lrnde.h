@@ -491,10 +491,10 @@ int lrnde_sde_sri_step(lrnde_sde* sde, const lrnde_sri_tableau* tab, const float
  * SRI without tab or Z (or without z2_local when regularising) and which outside 0..2 return LRNDE_BADARG with a message.
  * Evaluations per attempted step, (drift, diffusion): Euler-Heun (3, 3), Milstein (1, 2), SRI (4, 4); the automatic initial dt
  * adds (2, 2).  lrnde_stats.nf is the drift count.
- * Where the controller runs: Euler-Heun and Milstein at the one-launch kernels' shape (D <= 64, H <= 128, no time input,
- * unsharded) on the device — Milstein in the footer of k_sde_mil_fast, one launch per attempted step, no stream sync inside
- * the solve.  Host-controlled, one stream sync per attempted step: Milstein outside that shape (or with LRNDE_SDE_HOST_LOOP=1)
- * and SRI at every shape — a device controller for SRI is not provided.
+ * Where the controller runs: all three kinds at the one-launch kernels' shape (D <= 64, H <= 128, no time input,
+ * unsharded) on the device — Milstein in the footer of k_sde_mil_fast, SRI in the footer of k_sde_sri_fast, one launch per
+ * attempted step, no stream sync inside the solve.  Host-controlled, one stream sync per attempted step: Milstein and SRI
+ * outside that shape (or with LRNDE_SDE_HOST_LOOP=1).
  * UPSTREAM-RECALL (StochasticDiffEq is not vendored; beside the controller's constants, which stay the caller's options):
  * the strong orders the automatic initial dt takes — 1/2 Euler-Heun, 1 Milstein, 3/2 SRI.
  * lrnde_sde_node_backward_recorded sweeps a record with the reverse kernels of the kind that made it: per recorded step the

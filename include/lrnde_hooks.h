@@ -66,6 +66,16 @@ int lrnde_adjoint_trace_rows(lrnde_ctx* ctx, int32_t* n_host);
  * during which the GPU idles; the final wait is not counted, and polling the pinned progress word while an attempt is
  * still queued is not a wait. */
 int lrnde_last_adjoint_info(lrnde_ctx* ctx, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host);
+/* Diagnostic: how the last adaptive SDE solve of the handle ran (lrnde_sde_solve_adaptive(_alg); for
+ * lrnde_sde_node_forward_record(_alg) and the model's forward the MAIN solve including its automatic initial dt, not the
+ * local step).  kind: 0 the host-controlled loop (outside the one-launch kernels' shape, a time input, sharded handles,
+ * LRNDE_NO_SDE_FAST=1, LRNDE_SDE_HOST_LOOP=1), 1 the device controller with one launch per attempted step (k_sde_eh_fast /
+ * k_sde_mil_fast / k_sde_sri_fast), 2 the device controller in one persistent launch (Euler-Heun only).  launches: step
+ * launches enqueued (device loop: in batches of eight, those that find the solve finished included; host loop: one per
+ * attempt, SRI's launch sequence counting as one).  host_waits: stream synchronisations — the solve's closing one
+ * included — plus waits for a report that found the queue drained, i.e. with nothing enqueued behind them; polling the
+ * pinned progress word while launches are still queued is not a wait.  A device-controlled solve reports 1. */
+int lrnde_sde_last_solve_info(lrnde_sde* s, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host);
 /* Diagnostic: mean host-side microseconds per lrnde_node_forward call since the last reset, by phase: [0] entry -> the main
  * solve's init launches enqueued, [1] -> its last report read (the feed loop: the GPU is busy throughout), [2] -> the final
  * synchronisation returned, [3] -> the call returned (local-step results, bookkeeping).  tools/bench/host_phases.py */

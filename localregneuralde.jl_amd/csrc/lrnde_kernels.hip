@@ -1618,6 +1618,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 
 #include "lrnde_sde_fast.hpp"
 #include "lrnde_sde_mil_fast.hpp"
+#include "lrnde_sde_sri_fast.hpp"
 #include "lrnde_qtile.hpp"
 #include "lrnde_adjoint.hpp"
 #include "lrnde_backward.hpp"
@@ -3114,6 +3115,11 @@ struct lrnde_sde {
   unsigned long long mdl_gen = 0;
   std::function<int(const float*, int)> fwd_hook;   // lrnde_sde_node_forward_record_alg: (sol.u[end], nseries), ahead of its closing wait
   bool defer_wait = false;                          // lrnde_sde_node_backward_recorded's one-launch sweep: the caller waits
+  // lrnde_sde_last_solve_info: which loop ran the last adaptive solve (0 host-controlled, 1 device controller with a launch per
+  // attempt, 2 device controller in one persistent launch), the step-kernel launches it enqueued and the host's waits: stream
+  // synchronisations, and waits for a report that found the queue drained (nothing enqueued behind them).  The entry points
+  // reset it; a layer call's automatic initial dt of the main solve counts, its local step does not
+  int info_kind = 0, info_launches = 0, info_waits = 0;
 };
 
 int lrnde_sde_create(lrnde_sde** out, const lrnde_model_desc* drift, int32_t diffusion_bias, int device, void* stream) {
@@ -3371,9 +3377,9 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
                                const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                                int32_t cap_trace, float* ua, float* ub, float* rec_u = nullptr, int2* rec_im = nullptr,
                                int rec_cap = 0, int2* rec_im_host = nullptr, const float* dt0_dev = nullptr, bool no_persist = false,
-                               int which = 0) {
+                               int which = 0, const lrnde_sri_tableau* tab = nullptr, const float* Z = nullptr) {
   lrnde_ctx* c = s->drift;
-  if (which == 1) no_persist = true;   // (the Milstein step has the launch-per-attempt form only: lrnde_sde_mil_fast.hpp)
+  if (which != 0) no_persist = true;   // (the Milstein and SRI steps have the launch-per-attempt form only: lrnde_sde_mil_fast.hpp, lrnde_sde_sri_fast.hpp)
   const size_t n = (size_t)B * c->desc.state_dim;
   const bool pairs_home = rec_im_host && rec_im && rec_cap > 0;   // the layer's record: its pairs live behind the control block
   int rc0 = sde_adaptive_prepare(s, pairs_home ? rec_cap : 0);
@@ -3404,6 +3410,7 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   f.gamma = o->gamma; f.qmin = o->qmin; f.qmax = o->qmax; f.beta1 = o->beta1; f.beta2 = o->beta2; f.maxiters = o->maxiters;
   f.trace = trace_host ? s->ad_trace : nullptr; f.cap_trace = trace_host ? cap_trace : 0;
   f.prog = s->ad_prog.dev();
+  if (which == 2) { f.Zpath = Z; f.tab = *tab; }
   const int nwg = (B + NB - 1) / NB;
   // The whole solve as ONE cooperative launch (k_sde_eh_fast<DT, HT, true>: state and weights stay in registers, a grid barrier
   // per step) when every workgroup fits on the chip at once; LRNDE_SDE_NO_PERSIST=1, a launch the runtime refuses or more than
@@ -3422,7 +3429,7 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
     HIPCHK(c, hipMemsetAsync(c->part, 0, sizeof(double) * 2 * (size_t)nwg * PSTRIDE, c->stream));   // (tags of an earlier solve)
     f.jlaunch = 0;
     const hipError_t le = sde_persist_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f, !plain);
-    if (le == hipSuccess) persisted = true;
+    if (le == hipSuccess) { persisted = true; ++s->info_launches; }
     else (void)hipGetLastError();   // (not resident / not supported: fall through to the loop)
   }
   // launches are enqueued eight at a time, the next eight when four of them have reported; launches that find the solve
@@ -3433,10 +3440,12 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   while (!done && j <= cap) {
     for (int k = 0; k < 8; ++k, ++j) {
       f.jlaunch = j;
-      if (which == 1) sde_mil_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
+      if (which == 2) sde_sri_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
+      else if (which == 1) sde_mil_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
       else sde_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
     }
     HIPCHK(c, hipGetLastError());
+    s->info_launches += 8;
     const unsigned want = (unsigned)(j - 4);
     ReportWait<> wait(WAIT_PER_LAUNCH);
     const WaitResult wr = wait.await([&] { const SdeReport r = sde_report_unpack(*pw); done = r.status != (unsigned)ST_RUNNING; return done || r.count >= want; },
@@ -3444,6 +3453,7 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
     // (ready, or drained: everything enqueued has run — the loop looks at `done` and enqueues more)
     if (wr == WAIT_QUEUE_ERROR) return fail(c, LRNDE_HIP_ERROR, "adaptive SDE loop: %s", hipGetErrorString((hipError_t)wait.code));
     if (wr == WAIT_HUNG) return LRNDE_HUNG(c, "adaptive SDE loop");
+    if (wr == WAIT_DRAINED) ++s->info_waits;   // (the host waited with nothing enqueued behind the report)
   }
   // one synchronisation ends the solve: the control block, the end state (picked on the device) and the record's
   // (start, length) pairs are all enqueued before it
@@ -3454,9 +3464,11 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  ++s->info_waits;
+  s->info_kind = persisted ? 2 : 1;
   const SdeCtl fin = *reinterpret_cast<const SdeCtl*>(s->ad_ctl_host.get());
   if (persisted && plain && (fin.status == LRNDE_HIP_ERROR || fin.status == ST_RUNNING))   // the barrier gave up waiting (busy device): the loop
-    return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true, which);
+    return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true, which, tab, Z);
   if (pairs_home && fin.naccept > 0)
     memcpy(rec_im_host, s->ad_ctl_host + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
   st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iters; st->nf = fin.nf; st->eest_last = fin.eest_last;
@@ -3492,6 +3504,7 @@ int lrnde_sde_solve_adaptive_alg(lrnde_sde* s, const float* u0, const float* W, 
   int rc = sde_alg_check(s, which, tab, Z);
   if (rc) return rc;
   if (!u_end) return fail(s->drift, LRNDE_BADARG, "null pointer");
+  s->info_kind = s->info_launches = s->info_waits = 0;
   return sde_solve_adaptive_impl(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, nullptr, nullptr, nullptr, 0, nullptr,
                                  which, tab, Z);
 }
@@ -3513,14 +3526,15 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
   HIPCHK(c, s->ad_ws.resize_exact(4 * n));
   float *ua = s->ad_ws, *ub = s->ad_ws + n, *dW = s->ad_ws + 2 * n, *dZ = s->ad_ws + 3 * n;
   {
-    // the controller on the device: Euler-Heun (k_sde_eh_fast) and Milstein (k_sde_mil_fast) at the one-launch kernels' shape.
-    // SRI at any shape, and everything outside that shape, runs the host-controlled loop below
+    // the controller on the device: Euler-Heun (k_sde_eh_fast), Milstein (k_sde_mil_fast) and SRI (k_sde_sri_fast) at the
+    // one-launch kernels' shape.  Everything outside that shape runs the host-controlled loop below
     const bool host_loop = opt(OPT_SDE_HOST_LOOP) != 0;  // diagnostic: the host-controlled loop below
-    if (which != 2 && sde_uses_fast(s) && !host_loop) {
+    if (sde_uses_fast(s) && !host_loop) {
       return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im_dev, rec_cap,
-                                 rec_im_host, dt0_dev, false, which);
+                                 rec_im_host, dt0_dev, false, which, tab, Z);
     }
   }
+  s->info_kind = 0;
   const int nfa = which == 2 ? 4 : (which == 1 ? 1 : 3);   // drift evaluations of one attempted step
   HIPCHK(c, hipMemcpyAsync(ua, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   const float h = (t1 - t0) / (float)nfine;
@@ -3544,6 +3558,7 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
       HIPCHK(c, hipStreamSynchronize(c->stream));
       eest = c->ctrl_host[0].eest_last;
     }
+    ++s->info_launches; ++s->info_waits;   // (SRI: the step's launch sequence counts as one; its synchronisation is lrnde_sde_sri_step's)
     st->nf += nfa; st->eest_last = eest;
     if (eest != eest) { st->retcode = LRNDE_DT_NAN; break; }
     // PI controller on EEst (the form of SURVEY.md 3.5; StochasticDiffEq's constants are the caller's options)
@@ -3574,6 +3589,7 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
   st->t_final = t0 + (float)i * h; st->dt_final = (float)m * h;
   if (u_end) HIPCHK(c, hipMemcpyAsync(u_end, ua, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  ++s->info_waits;
   if (st->retcode != LRNDE_OK) return fail(c, st->retcode, "adaptive SDE solve stopped with retcode %d at t=%g", st->retcode, (double)st->t_final);
   return LRNDE_OK;
 }
@@ -4967,6 +4983,11 @@ int lrnde_set_adjoint_trace(lrnde_ctx* c, lrnde_trace_row* rows_host, int32_t ca
   return LRNDE_OK;
 }
 
+int lrnde_sde_last_solve_info(lrnde_sde* s, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host) {
+  if (!s || !kind_host || !launches_host || !host_waits_host) return LRNDE_BADARG;
+  *kind_host = s->info_kind; *launches_host = s->info_launches; *host_waits_host = s->info_waits;
+  return LRNDE_OK;
+}
 int lrnde_last_adjoint_info(lrnde_ctx* c, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host) {
   if (!c || !kind_host || !launches_host || !host_waits_host) return LRNDE_BADARG;
   *kind_host = c->adj_kind; *launches_host = c->adj_launches; *host_waits_host = c->adj_waits;

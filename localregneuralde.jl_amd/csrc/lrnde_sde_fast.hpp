@@ -73,6 +73,9 @@ struct SdeFastArgs {
   // persistent form (k_sde_eh_fast<DT, HT, true>, cooperative launch): the base of the TWO blocks of {partial sum, tag} slots the
   // steps alternate between (zero at launch: no slot carries a step's tag yet)
   double* part2;
+  // the four-stage SRI step (k_sde_sri_fast, lrnde_sde_sri_fast.hpp): the second Brownian path on W's grid and the caller's
+  // tableau, by value (last: the other kernels' argument offsets are what they were)
+  const float* Zpath; lrnde_sri_tableau tab;
 };
 // dtc: the controller's step proposal as a REAL number; the step taken is its floor on the path's grid (m intervals, at least
 // one).  Growth accumulates in dtc — with qmax = 1.125 a proposal quantised after every step could never leave m = 1.
@@ -99,7 +102,7 @@ __device__ __forceinline__ f32x4 sf_chain(const f32x4 (&frag)[NKG], const f32x4*
 // flip.  `writer` (one thread of the whole grid) also leaves the trace row and the accepted step's (start, length).
 // qpow = fastpow(c.qold, a.beta2): does not depend on this step's EEst — the cooperative form computes it while the partial
 // sums are still in flight.
-// nfa: drift evaluations of one attempted step (Euler-Heun 3, Milstein 1): what SdeCtl::nf counts.
+// nfa: drift evaluations of one attempted step (Euler-Heun 3, Milstein 1, SRI 4): what SdeCtl::nf counts.
 __device__ __forceinline__ void sde_ctl_update(SdeCtl& c, float eest, float dt, const SdeFastArgs& a, bool writer, float qpow, int nfa) {
   c.nf += nfa; c.eest_last = eest;
   if (eest != eest) { c.status = LRNDE_DT_NAN; return; }

@@ -245,10 +245,14 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   int nfe_f = 0, nfe_g = 0;
   HIPCHK(c, hipMemcpyAsync(r.x, x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   // the main solve (src/layers/neural_sde.jl:50-72): dt0 <= 0 -> automatic initial dt
-  // (the one-launch Euler-Heun step's shape keeps both automatic initial dts on the device: two host synchronisations per call —
-  //  the end of the solve and the end of this function — instead of nine; LRNDE_SDE_HOST_INITDT=1: the host form.  Milstein and
-  //  SRI take the host form: their local step runs the generic step kernels, which take dt from the host)
-  const bool devdt = which == 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT);
+  // (the one-launch steps' shape keeps the main solve's automatic initial dt on the device for all three step kinds, with the
+  //  kind's strong order: the solve's closing synchronisation is then the main solve's only one; LRNDE_SDE_HOST_INITDT=1: the
+  //  host form, two more.  Euler-Heun keeps its local step's initial dt there too (devdt_local): two host synchronisations per
+  //  call — the end of the solve and the end of this function.  The local step of Milstein and SRI takes the host form: it runs
+  //  the generic step kernels, which take dt from the host)
+  const bool devdt = sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT);
+  const bool devdt_local = devdt && which == 0;
+  s->info_kind = s->info_launches = s->info_waits = 0;   // (lrnde_sde_last_solve_info: the main solve with its initial dt)
   if (devdt) {
     HIPCHK(c, s->idt_scal.once(8));
     HIPCHK(c, s->idt_scal_host.once(8));
@@ -258,10 +262,13 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   if (!(oo.dt0 > 0.f)) {
     if (devdt) {
       if ((rc = sde_adaptive_prepare(s, r.rec_cap))) return rc;   // (before the initial dt initialises the control block)
-      if ((rc = sde_init_dt_dev(s, r.x, B, t0, t2, oo.abstol, oo.reltol, 0.5f, s->idt_scal, s->ctl(), h, nfine, nullptr))) return rc;
+      if ((rc = sde_init_dt_dev(s, r.x, B, t0, t2, oo.abstol, oo.reltol, order, s->idt_scal, s->ctl(), h, nfine, nullptr))) return rc;
       dt0_dev = s->idt_scal + 2;
       oo.dt0 = t2 - t0;   // (placeholder for the argument checks; the control block is initialised from the device value)
-    } else if ((rc = sde_init_dt(s, r.x, B, t0, t2, oo.abstol, oo.reltol, order, r.tmp, &oo.dt0))) return rc;
+    } else {
+      if ((rc = sde_init_dt(s, r.x, B, t0, t2, oo.abstol, oo.reltol, order, r.tmp, &oo.dt0))) return rc;
+      s->info_waits += 2;
+    }
     nfe_f += 2; nfe_g += 2;
   }
   r.im.assign((size_t)nfine, make_int2(0, 0));
@@ -333,7 +340,7 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
     if (!(t1 < t2)) return fail(c, LRNDE_BADARG, "t1 must lie before the end of tspan");
     if ((rc = value_of(e1, r.u1))) return rc;
     float dtl = o->dt0;
-    if (!(dtl > 0.f) && devdt) {
+    if (!(dtl > 0.f) && devdt_local) {
       // dt, sqrt(dt) z and the step itself from the device value (sde_init_dt_dev clamps to t2 - t1 as the line below does);
       // EEst, EEst * dt and dt come back with this function's closing synchronisation
       float* scal = s->idt_scal + 4;

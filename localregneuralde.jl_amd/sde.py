@@ -7,9 +7,10 @@ under a PI controller on its error estimate, on a Brownian path drawn up front o
 (`lrnde_sde_node_backward_recorded`).  The step is the Lamba Euler-Heun step (`_perform_step(::LambaEulerHeunConstantCache)`,
 src/perform_step.jl:172-206; the default, adaptive unless told otherwise), the Milstein step (:108-170) or the four-stage SRI
 step (:49-106); the last two are adaptive with `adaptive=True` and march the fixed grid of rounds 1-2 otherwise
-(`adaptive=False` gives Euler-Heun that grid too).  The controller runs on the device for Euler-Heun and Milstein at the
-one-launch kernels' shape (D <= 64, H <= 128); SRI, and Milstein outside that shape, are host-controlled (one stream sync per
-attempted step).  SOSRI's tableau and its RSWM noise process live in un-vendored StochasticDiffEq and are not restated:
+(`adaptive=False` gives Euler-Heun that grid too).  The controller runs on the device for all three steps at the one-launch
+kernels' shape (D <= 64, H <= 128, no time input, unsharded: one launch per attempted step, one stream sync per solve); outside
+that shape Milstein and SRI are host-controlled (one stream sync per attempted step).  `SdeHandle.last_solve_info()` says
+which loop ran.  SOSRI's tableau and its RSWM noise process live in un-vendored StochasticDiffEq and are not restated:
 `solver="SOSRI"` raises, `solver="SRI"` takes the tableau from the caller.
 """
 import copy
@@ -153,6 +154,17 @@ class SdeHandle:
         trace = np.array([(tr[i].t, tr[i].dt, tr[i].eest, tr[i].accepted) for i in range(nt)],
                          dtype=[("t", "f4"), ("dt", "f4"), ("eest", "f4"), ("accepted", "i4")])
         return dict(u_end=u_end, stats=st.asdict(), trace=trace)
+
+    SOLVE_LOOPS = ("host", "device", "device-persistent")
+
+    def last_solve_info(self):
+        """how the last adaptive solve of this handle ran (lrnde_sde_last_solve_info; for a layer call the main solve with its
+        automatic initial dt, not the local step): kind 0 the host-controlled loop / 1 the device controller, one launch per
+        attempted step / 2 the device controller in one persistent launch (Euler-Heun only); launches: step-kernel launches
+        enqueued; host_waits: stream synchronisations plus waits for a report with nothing enqueued behind them"""
+        k, n, w = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(L.lib.lrnde_sde_last_solve_info(self._h, C.byref(k), C.byref(n), C.byref(w)))
+        return dict(kind=int(k.value), launches=int(n.value), host_waits=int(w.value))
 
     def draw_noise(self, seed, stream, nsteps, B, scale, cumulative):
         """Gaussian noise drawn on the device (lrnde_sde_draw_noise, counter-based: sample b's noise does not depend on B or

@@ -3,7 +3,7 @@
 # after 3 warm-ups, in ONE session:
 #   * Milstein through the one-launch kernel with the controller in its footer (k_sde_mil_fast; the default at this shape),
 #   * the same inputs through the host-controlled loop on the generic kernel (LRNDE_SDE_HOST_LOOP=1) — the yardstick,
-#   * SRI (host-controlled at every shape).
+#   * SRI through its own one-launch kernel (k_sde_sri_fast; tools/bench/sde_sri_adaptive_bench.py compares it with its host loop).
 #   python tools/bench/sde_mil_adaptive_bench.py [out.json] [tol]
 # tol: 0.14 (config 5's) by default, for both kinds.
 import json, os, sys, time, numpy as np, torch
@@ -52,7 +52,7 @@ def measure(label, tol, host_loop, **kw):
 
 rows = [measure("milstein fused (k_sde_mil_fast, device controller)", tol, False, solver="RKMil"),
         measure("milstein host-controlled loop (k_sde_rkmil)", tol, True, solver="RKMil"),
-        measure("sri host-controlled loop", tol, False, solver="SRI", tableau=tab, path_z=Zd, z_local2=z2)]
+        measure("sri fused (k_sde_sri_fast, device controller)", tol, False, solver="SRI", tableau=tab, path_z=Zd, z_local2=z2)]
 assert rows[0]["u_end_sum"] == rows[1]["u_end_sum"] and rows[0]["attempted"] == rows[1]["attempted"]   # the same solve on both routes
 if out:
     with open(out, "w") as f:
