@@ -38,6 +38,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 #include <chrono>
 #include <mutex>
 #include <string>

@@ -5,16 +5,10 @@
 //
 // k_sde_step (the generic kernel) runs the step's six field evaluations through feval_tile: per evaluation it restages
 // the biases, reloads the resident weight fragments from L2, and passes every intermediate (du1, L, K, tmp, ...) through
-// global memory between evaluations — 28 us for 15.7 MFLOP.  Here a workgroup is four waves on 16 columns and nothing
-// leaves the CU between the first load of (u, dW) and the store of u_new:
-//   * the three weight matrices (24 KB at 32/64) are MFMA A fragments in registers for the whole launch: wave w holds the
-//     hidden tiles w, w + 4 of Dense-1; the 2 DT output-tile jobs of the second phase — DT tiles of Dense-2, DT tiles of
-//     the diffusion — go round-robin to the waves (job j = wave + 4 r: Dense-2 tile j for j < DT, diffusion tile j - DT
-//     otherwise; a wave owns at most one of each);
-//   * a round = [drift Dense-1 + activation, and this wave's diffusion tile] barrier [drift Dense-2 of this wave's tile +
-//     the elementwise algebra] barrier; the step is three rounds: (f,g)(u) -> (f,g)(tmp) -> f(K), g(utilde);
-//   * the elementwise algebra of the step stays in the C-fragment registers of the wave that owns the Dense-2 tile
-//     (4 rows x 1 column per lane).
+// global memory between evaluations — 28 us for 15.7 MFLOP.  Here nothing leaves the CU between the first load of (u, dW) and
+// the store of u_new: the weights are resident fragments of the workgroup frame (SdeFrame below, where the layout is described);
+// a round = [drift Dense-1 + activation, and this wave's diffusion tile] barrier [drift Dense-2 of this wave's tile + the
+// elementwise algebra] barrier; the step is three rounds: (f,g)(u) -> (f,g)(tmp) -> f(K), g(utilde).
 // Arithmetic: the canonical dot products (k-ordered fma chains = v_mfma_f32_16x16x4_f32 chains over the k-groups in
 // order, segments of 112 rows added left to right — H = 128 has two), the same activation polynomial and the same
 // elementwise expressions as k_sde_step, so results are bit-identical to it and to the oracle
@@ -138,14 +132,166 @@ __device__ __forceinline__ void sde_ctl_update(SdeCtl& c, float eest, float dt, 
   }
 }
 
+// ---- the workgroup frame of the one-launch step kernels (k_sde_eh_fast, k_sde_mil_fast, k_sde_sri_fast) ----
+// Layout: a workgroup is four waves on 16 columns (b0 .. b0 + 15; lane = 16 rq + n holds rows 4 rq .. 4 rq + 3 of column n of a
+// 16-row tile).  The three weight matrices are v_mfma_f32_16x16x4_f32 A fragments in registers for the whole launch: wave w
+// holds the hidden tiles w, w + 4 of Dense-1 (w1), Dense-2 tile t = w for w < DT (w2: `has_d2`) and at most one diffusion tile
+// tg (wg: job j = wave + 4 r is diffusion tile j - DT for j in [DT, 2 DT)); tiles past D / H are zero fragments.  The waves with
+// a Dense-2 tile own the elementwise algebra of their rows row0 .. row0 + 3 (C-fragment registers); `live` lanes are those whose
+// rows and column exist, g is the lane's offset into a (B, D) array and nn = B D one such array.  D % 4 != 0 takes the scalar
+// accesses of ld4s / st4s (rows past D stay zero / unwritten).  The kernel declares the LDS tiles — x tiles in B-operand layout
+// ([kg][64 lanes] float4), the h tile hl, the diffusion results gl in C-fragment order — and constructs the frame after them.
+template <int DT, int HT>
+struct SdeFrame {
+  static_assert(DT >= 1 && DT <= 4 && HT >= 1 && HT <= 8, "D <= 64, H <= 128");
+  static constexpr int NJ = (HT + 3) / 4;   // hidden tiles per wave
+  typedef __attribute__((address_space(3))) f32x4 lds4;
+  lds4 *hl, *gl;   // (as LDS pointers: carried as generic ones, the persistent step loop measured 1.2 % slower)
+  int lane, wave, n, rq, t, tg, act, D, row0;
+  bool has_d2, vec, live;
+  size_t g, nn;
+  f32x4 w1[NJ][DT], w2[HT], wg[DT], b1v[NJ], b2v, bgv;   // resident A fragments and this lane's bias rows
+
+  __device__ __forceinline__ SdeFrame(const SdeFastArgs& a, f32x4* hl_, f32x4* gl_) : hl((lds4*)hl_), gl((lds4*)gl_), act(a.act), D(a.D) {
+    lane = threadIdx.x & 63;
+    wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    n = lane & 15; rq = lane >> 4;
+    const int b0 = blockIdx.x * 16;
+    const bool colok = b0 + n < a.B;
+    // jobs of this wave: Dense-2 tile t (wave < DT), diffusion tile tg (job wave or wave + 4 in [DT, 2 DT))
+    has_d2 = wave < DT;
+    t = has_d2 ? wave : 0;
+    tg = (wave >= DT && wave < 2 * DT) ? wave - DT : ((wave + 4 >= DT && wave + 4 < 2 * DT) ? wave + 4 - DT : -1);
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int ht = wave + 4 * j;
+#pragma unroll
+      for (int kg = 0; kg < DT; ++kg) w1[j][kg] = ht < HT ? a.W1p[((size_t)ht * a.KG1 + kg) * 64 + lane] : zero4;
+      b1v[j] = ht < HT ? *reinterpret_cast<const f32x4*>(a.b1 + ht * 16 + rq * 4) : zero4;
+    }
+#pragma unroll
+    for (int kg = 0; kg < HT; ++kg) w2[kg] = has_d2 ? a.W2p[((size_t)t * a.KG2p + kg) * 64 + lane] : zero4;
+#pragma unroll
+    for (int kg = 0; kg < DT; ++kg) wg[kg] = tg >= 0 ? a.Wgp[((size_t)tg * a.KGgp + kg) * 64 + lane] : zero4;
+    b2v = has_d2 ? *reinterpret_cast<const f32x4*>(a.b2 + t * 16 + rq * 4) : zero4;
+    bgv = tg >= 0 ? *reinterpret_cast<const f32x4*>(a.bg + tg * 16 + rq * 4) : zero4;
+    row0 = t * 16 + rq * 4;
+    vec = (D & 3) == 0;                 // rows in whole quads: one 16-byte access per lane
+    live = has_d2 && colok && row0 < D;
+    g = (size_t)(b0 + n) * D + row0;
+    nn = (size_t)a.B * D;
+  }
+  // this lane's four rows of column n of the (B, D) array p (live lanes only)
+  __device__ __forceinline__ f32x4 ld4s(const float* p) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (vec) v = *reinterpret_cast<const f32x4*>(p + g);
+    else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) if (row0 + r < D) v[r] = p[g + r];
+    }
+    return v;
+  }
+  __device__ __forceinline__ void st4s(float* p, const f32x4& v) const {
+    if (vec) *reinterpret_cast<f32x4*>(p + g) = v;
+    else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) if (row0 + r < D) p[g + r] = v[r];
+    }
+  }
+  // the increment P[i + m] - P[i] of a path on the caller's grid (the expression of k_sde_dw)
+  __device__ __forceinline__ f32x4 dpath(const float* P, int i, int m) const {
+    const f32x4 lo = ld4s(P + (size_t)i * nn);
+    const f32x4 hi = ld4s(P + (size_t)(i + m) * nn);
+    f32x4 d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d[r] = hi[r] - lo[r];
+    return d;
+  }
+  // B-operand image of rows 16 t + 4 rq + r, column n: float4 index t*64 + r*16 + n, component rq (Dense-2 waves)
+  __device__ __forceinline__ void put(f32x4* x, const f32x4& v) const {
+    float* p = reinterpret_cast<float*>(x) + ((t * 64 + n) << 2) + rq;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) p[r * 64] = v[r];
+  }
+  // drift Dense-1 + activation of this wave's hidden tiles on the x tile xs -> hl
+  __device__ __forceinline__ void dense1(const f32x4* xs) const {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int ht = wave + 4 * j;
+      if (ht < HT) {
+        const f32x4 acc = sf_chain<DT>(w1[j], xs, lane);
+        __attribute__((address_space(3))) float* p = (__attribute__((address_space(3))) float*)hl + ((ht * 64 + n) << 2) + rq;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r * 64] = act_apply_sel(act, acc[r] + b1v[j][r]);   // (four independent elements: the select form interleaves them)
+      }
+    }
+  }
+  __device__ __forceinline__ void diffusion(const f32x4* xs) const {  // tile tg of g(xs) -> gl (C-fragment order)
+    if (tg < 0) return;
+    f32x4 acc = sf_chain<DT>(wg, xs, lane);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = acc[r] + bgv[r];
+    gl[tg * 64 + lane] = acc;
+  }
+  __device__ __forceinline__ f32x4 dense2() const {  // tile t of f = W2 h + b2 (Dense-2 waves)
+    f32x4 acc = sf_chain<HT>(w2, (const f32x4*)hl, lane);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = acc[r] + b2v[r];
+    return acc;
+  }
+};
+
+// this workgroup's sum of the waves' partial sums red[] (Dense-2 waves, in wave order)
+template <int DT> __device__ __forceinline__ double sde_wg_total(const double* red) {
+  double tot = red[0];
+#pragma unroll
+  for (int w = 1; w < DT; ++w) tot += red[w];
+  return tot;
+}
+
+// The footer of a launch that is one step (every thread calls it, after the barrier behind the red[] stores): the workgroup's
+// total goes to its partial slot; the last workgroup to arrive adds the partials in partial-vector order and either fills the
+// fixed-grid record (`adapt` false: EEst, EEst * dt) or runs the controller on the control block with nfa drift evaluations
+// per attempt (trace row, the layer's (start, length) record) and reports through the pinned progress word.
+template <int DT> __device__ __forceinline__ void sde_step_footer(const SdeFastArgs& a, const double* red, float dt, bool adapt, int nfa) {
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
+  const double tot = sde_wg_total<DT>(red);
+  int last = 0;
+  if (lane == 0) {
+    double* p = a.part + (size_t)blockIdx.x * PSTRIDE;
+    __hip_atomic_store(p + 0, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p + 1, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(p + 2, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = __hip_atomic_fetch_add(a.arrive, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+  }
+  last = __shfl(last, 0, 64);
+  if (!last) return;
+  const Sum3 s = reduce_partials3(a.part, (int)gridDim.x);
+  if (lane == 0) {
+    const float eest = rms_from(s.a, a.n_norm);
+    if (!adapt) {
+      a.rec->eest_last = eest;
+      a.rec->reg_error = eest * dt;
+      a.rec->status = ST_DONE;
+    } else {
+      SdeCtl c = *a.ctl;
+      sde_ctl_update(c, eest, dt, a, true, fastpow(c.qold, a.beta2), nfa);
+      *a.ctl = c;
+      __hip_atomic_store(a.prog, sde_report_pack((unsigned)(a.jlaunch + 1), (unsigned)c.status),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __hip_atomic_store(a.arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // PERSIST: the whole adaptive solve in ONE cooperative launch.  The workgroups stay resident with their weight fragments and
 // their columns' state in registers; a step ends in a grid barrier (tagged partial-sum slots + bounded polling) after which EVERY
 // workgroup adds the partial sums in the same fixed order and runs the same controller on its own copy of the control
 // block — the same decisions everywhere, no broadcast, and the arithmetic of a step is the code of the one-launch form.
 template <int DT, int HT, bool PERSIST = false>
 __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
-  static_assert(DT >= 1 && DT <= 4 && HT >= 1 && HT <= 8, "D <= 64, H <= 128");
-  constexpr int NJ = (HT + 3) / 4;   // hidden tiles per wave
   const bool adapt = a.ctl != nullptr;
   int ad_i = 0, ad_m = 0, ad_slot = 0;
   SdeCtl cc{};
@@ -162,112 +308,31 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
   // diffusion results in C-fragment order, the reduction scratch
   __shared__ f32x4 xA[DT * 64], xB[DT * 64], xC[DT * 64], hl[HT * 64], gl[DT * 64];
   __shared__ double red[4];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n = lane & 15, rq = lane >> 4;
-  const int b0 = blockIdx.x * 16;
-  const bool colok = b0 + n < a.B;
-  const int D = a.D;
-  // jobs of this wave: Dense-2 tile t (wave < DT), diffusion tile tg (job wave or wave + 4 in [DT, 2 DT))
-  const bool has_d2 = wave < DT;
-  const int t = has_d2 ? wave : 0;
-  const int tg = (wave >= DT && wave < 2 * DT) ? wave - DT : ((wave + 4 >= DT && wave + 4 < 2 * DT) ? wave + 4 - DT : -1);
-  // resident A fragments
-  f32x4 w1[NJ][DT], w2[HT], wg[DT];
+  const SdeFrame<DT, HT> F(a, hl, gl);
+  const int lane = F.lane, wave = F.wave, t = F.t, row0 = F.row0, D = F.D;
+  const bool has_d2 = F.has_d2, live = F.live;
+  const size_t nn = F.nn;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int ht = wave + 4 * j;
-#pragma unroll
-    for (int kg = 0; kg < DT; ++kg) w1[j][kg] = ht < HT ? a.W1p[((size_t)ht * a.KG1 + kg) * 64 + lane] : zero4;
-  }
-#pragma unroll
-  for (int kg = 0; kg < HT; ++kg) w2[kg] = has_d2 ? a.W2p[((size_t)t * a.KG2p + kg) * 64 + lane] : zero4;
-#pragma unroll
-  for (int kg = 0; kg < DT; ++kg) wg[kg] = tg >= 0 ? a.Wgp[((size_t)tg * a.KGgp + kg) * 64 + lane] : zero4;
-  f32x4 b1v[NJ];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) b1v[j] = (wave + 4 * j < HT) ? *reinterpret_cast<const f32x4*>(a.b1 + (wave + 4 * j) * 16 + rq * 4) : zero4;
-  const f32x4 b2v = has_d2 ? *reinterpret_cast<const f32x4*>(a.b2 + t * 16 + rq * 4) : zero4;
-  const f32x4 bgv = tg >= 0 ? *reinterpret_cast<const f32x4*>(a.bg + tg * 16 + rq * 4) : zero4;
-  // this lane's four rows (16 t + 4 rq + r) of column n: state and increments (the Dense-2 waves own the elementwise work)
-  const int row0 = t * 16 + rq * 4;
-  const bool vec = (D & 3) == 0;                 // rows in whole quads: one 16-byte access per lane
-  const bool live = has_d2 && colok && row0 < D;
-  const size_t g = (size_t)(b0 + n) * D + row0;
-  const size_t nn = (size_t)a.B * D;
-  auto ld4s = [&](const float* p) {
-    f32x4 v = zero4;
-    if (vec) v = *reinterpret_cast<const f32x4*>(p + g);
-    else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) if (row0 + r < D) v[r] = p[g + r];
-    }
-    return v;
-  };
-  auto st4s = [&](float* p, const f32x4& v) {
-    if (vec) *reinterpret_cast<f32x4*>(p + g) = v;
-    else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) if (row0 + r < D) p[g + r] = v[r];
-    }
-  };
   f32x4 u4 = zero4, w4 = zero4;
-  if (live) u4 = ld4s(a.u);
+  if (live) u4 = F.ld4s(a.u);
   for (int it = 0;; ++it) {   // (one trip unless PERSIST)
   SDE_STAMP(0);
   if (live) {
     if (adapt) {  // dW = W[i + m] - W[i], the path's own increment (the expression of k_sde_dw)
-      const f32x4 lo = ld4s(a.Wpath + (size_t)ad_i * nn);
-      const f32x4 hi = ld4s(a.Wpath + (size_t)(ad_i + ad_m) * nn);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w4[r] = hi[r] - lo[r];
+      w4 = F.dpath(a.Wpath, ad_i, ad_m);
     } else {
-      w4 = ld4s(a.dW);
+      w4 = F.ld4s(a.dW);
       if (a.dW_scaled) {
         const float cz = __builtin_sqrtf(a.dt);
 #pragma unroll
         for (int r = 0; r < 4; ++r) w4[r] = cz * w4[r];
-        st4s(a.dW_scaled, w4);
+        F.st4s(a.dW_scaled, w4);
       }
     }
   }
-  // B-operand image of rows 16 t + 4 rq + r, column n: float4 index t*64 + r*16 + n, component rq
-  auto put = [&](f32x4* x, const f32x4& v) {
-    float* p = reinterpret_cast<float*>(x) + ((t * 64 + n) << 2) + rq;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[r * 64] = v[r];
-  };
-  if (has_d2) put(xA, u4);
+  if (has_d2) F.put(xA, u4);
   __syncthreads();
   const float dt = a.dt, hdt = dt / 2.0f, sqdt = __builtin_sqrtf(dt);
-
-  // drift Dense-1 + activation of this wave's hidden tiles on the x tile xs -> hl
-  auto dense1 = [&](const f32x4* xs) {
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int ht = wave + 4 * j;
-      if (ht < HT) {
-        const f32x4 acc = sf_chain<DT>(w1[j], xs, lane);
-        float* p = reinterpret_cast<float*>(hl) + ((ht * 64 + n) << 2) + rq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) p[r * 64] = act_apply_sel(a.act, acc[r] + b1v[j][r]);   // (four independent elements: the select form interleaves them)
-      }
-    }
-  };
-  auto diffusion = [&](const f32x4* xs) {  // tile tg of g(xs) -> gl (C-fragment order)
-    if (tg < 0) return;
-    f32x4 acc = sf_chain<DT>(wg, xs, lane);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = acc[r] + bgv[r];
-    gl[tg * 64 + lane] = acc;
-  };
-  auto dense2 = [&]() {  // tile t of f = W2 h + b2
-    f32x4 acc = sf_chain<HT>(w2, hl, lane);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = acc[r] + b2v[r];
-    return acc;
-  };
 
   if constexpr (!PERSIST) {
     if (a.idt_phase) {
@@ -277,11 +342,11 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
       //          sum of (max(|df + dg|, |df - dg|) / sk)^2.  The launch ends here.
       __shared__ double red2[4];
       __shared__ float sh_dt0;
-      dense1(xA);
-      diffusion(xA);
+      F.dense1(xA);
+      F.diffusion(xA);
       __syncthreads();
       f32x4 f0 = zero4, g0 = zero4;
-      if (has_d2) { f0 = dense2(); g0 = gl[t * 64 + lane]; }
+      if (has_d2) { f0 = F.dense2(); g0 = gl[t * 64 + lane]; }
       double a0 = 0.0, a1 = 0.0;
       if (a.idt_phase == 1) {
         if (live) {
@@ -311,14 +376,14 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
           f32x4 u1;
 #pragma unroll
           for (int r = 0; r < 4; ++r) u1[r] = u4[r] + dt0 * f0[r];
-          put(xB, u1);
+          F.put(xB, u1);
         }
         __syncthreads();
-        dense1(xB);
-        diffusion(xB);
+        F.dense1(xB);
+        F.diffusion(xB);
         __syncthreads();
         if (has_d2) {
-          const f32x4 f1 = dense2();
+          const f32x4 f1 = F.dense2();
           const f32x4 g1 = gl[t * 64 + lane];
           if (live) {
 #pragma unroll
@@ -351,15 +416,15 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
   }
   SDE_STAMP(1);
   // ---- round 1: du1 = f(u), L = g(u) (:174-176) ----
-  dense1(xA);
+  F.dense1(xA);
   SDE_STAMP(8);
-  diffusion(xA);
+  F.diffusion(xA);
   SDE_STAMP(9);
   __syncthreads();
   SDE_STAMP(10);
   f32x4 du1 = zero4, L = zero4, Kv = zero4;
   if (has_d2) {
-    du1 = dense2();
+    du1 = F.dense2();
     SDE_STAMP(11);
     L = gl[t * 64 + lane];
     f32x4 tmp, ut;
@@ -369,18 +434,18 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
       tmp[r] = Kv[r] + L[r] * w4[r];        // :179,183
       ut[r] = u4[r] + L[r] * sqdt;          // :196
     }
-    put(xB, tmp); put(xC, ut);
+    F.put(xB, tmp); F.put(xC, ut);
   }
   SDE_STAMP(12);
   __syncthreads();
   SDE_STAMP(2);
   // ---- round 2: g(tmp), f(tmp) at t + dt (:184, :191) ----
-  dense1(xB);
-  diffusion(xB);
+  F.dense1(xB);
+  F.diffusion(xB);
   __syncthreads();
   f32x4 un = zero4;
   if (has_d2) {
-    const f32x4 f2 = dense2();
+    const f32x4 f2 = F.dense2();
     const f32x4 g2 = gl[t * 64 + lane];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -389,20 +454,20 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
       un[r] = (u4[r] + hdt * (du1[r] + f2[r])) + noise2;   // :191
     }
     if (live) {
-      if (!PERSIST) st4s(a.un, un);   // (PERSIST: the state lives in registers until the solve ends)
-      if (a.rec_u && ad_slot < a.rec_cap) st4s(a.rec_u + (size_t)ad_slot * nn, un);
+      if (!PERSIST) F.st4s(a.un, un);   // (PERSIST: the state lives in registers until the solve ends)
+      if (a.rec_u && ad_slot < a.rec_cap) F.st4s(a.rec_u + (size_t)ad_slot * nn, un);
     }
-    put(xA, Kv);   // xA is free: every wave has read it (barrier above)
+    F.put(xA, Kv);   // xA is free: every wave has read it (barrier above)
   }
   __syncthreads();
   SDE_STAMP(3);
   // ---- round 3: du2 = f(K, t + dt) (:193), g(utilde, t) (:197) ----
-  dense1(xA);
-  diffusion(xC);
+  F.dense1(xA);
+  F.diffusion(xC);
   __syncthreads();
   double acc = 0.0;
   if (has_d2) {
-    const f32x4 du2 = dense2();
+    const f32x4 du2 = F.dense2();
     const f32x4 g3 = gl[t * 64 + lane];
     if (live) {
 #pragma unroll
@@ -426,9 +491,6 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
     const int nwg = (int)gridDim.x + a.dbg_stall;
     double* blk = a.part2 + (size_t)(it & 1) * nwg * PSTRIDE;   // (two blocks: a fast workgroup's next step must not overwrite what a slow one still reads)
     if (threadIdx.x < 64) {
-      double tot = red[0];
-#pragma unroll
-      for (int w = 1; w < DT; ++w) tot += red[w];
       // The step's grid barrier IS the exchange of the partial sums: a workgroup publishes {sum, tag} as ONE 16-byte agent-scope
       // store — tag = step number and a checksum of the sum's bits, so that a reader can tell a slot of this step from a stale
       // or (should a 16-byte access ever be split) a torn one — and every workgroup polls all slots with 16-byte loads until
@@ -437,7 +499,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
       typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
       const unsigned step_tag = (unsigned)(it + 1);
       if (lane == 0) {
-        const unsigned long long vb = __builtin_bit_cast(unsigned long long, tot);
+        const unsigned long long vb = __builtin_bit_cast(unsigned long long, sde_wg_total<DT>(red));
         const u32x4_ w = {(unsigned)vb, (unsigned)(vb >> 32), (unsigned)(vb >> 32) ^ (unsigned)vb, step_tag};
         double* p = blk + (size_t)blockIdx.x * PSTRIDE;
         asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(w) : "memory");
@@ -484,7 +546,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
     cc = sh_cc;
     if (cc.naccept != nacc0) u4 = un;   // accepted: the end state is the next step's start state (rows of the Dense-2 waves)
     if (cc.status != ST_RUNNING) {
-      if (live) st4s(cc.cur ? a.ub : a.ua, u4);
+      if (live) F.st4s(cc.cur ? a.ub : a.ua, u4);
       if (blockIdx.x == 0 && threadIdx.x == 0) {
         *a.ctl = cc;
         __hip_atomic_store(a.prog, sde_report_pack((unsigned)(it + 1), (unsigned)cc.status),
@@ -498,11 +560,8 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
   } else {
   if (a.march_n > 0) {
     if (threadIdx.x == 0) {
-      double tot = red[0];
-#pragma unroll
-      for (int w = 1; w < DT; ++w) tot += red[w];
       double* p = a.march_part + ((size_t)it * gridDim.x + blockIdx.x) * PSTRIDE;
-      p[0] = tot; p[1] = 0.0; p[2] = 0.0;
+      p[0] = sde_wg_total<DT>(red); p[1] = 0.0; p[2] = 0.0;
     }
     if (it + 1 == a.march_n) return;
     u4 = un;                       // the end state is the next step's start state (rows of the Dense-2 waves)
@@ -510,98 +569,41 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
     __syncthreads();               // red and the tiles are rewritten by the next step
     continue;
   }
-  if (threadIdx.x < 64) {
-    double tot = red[0];
-#pragma unroll
-    for (int w = 1; w < DT; ++w) tot += red[w];
-    if (!a.arrive) {
-      if (lane == 0) { double* p = a.part + (size_t)blockIdx.x * PSTRIDE; p[0] = tot; p[1] = 0.0; p[2] = 0.0; }
-      return;
-    }
-    // the step's own footer — the last workgroup to arrive reduces the partials and fills the record / runs the controller
-    int last = 0;
-    if (lane == 0) {
-      double* p = a.part + (size_t)blockIdx.x * PSTRIDE;
-      __hip_atomic_store(p + 0, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(p + 1, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(p + 2, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = __hip_atomic_fetch_add(a.arrive, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
-    }
-    last = __shfl(last, 0, 64);
-    if (!last) return;
-    const Sum3 s = reduce_partials3(a.part, (int)gridDim.x);
-    if (lane == 0) {
-      const float eest = rms_from(s.a, a.n_norm);
-      if (!adapt) {
-        a.rec->eest_last = eest;
-        a.rec->reg_error = eest * dt;
-        a.rec->status = ST_DONE;
-      } else {
-        SdeCtl c = *a.ctl;
-        sde_ctl_update(c, eest, dt, a, true, fastpow(c.qold, a.beta2), 3);
-        *a.ctl = c;
-        __hip_atomic_store(a.prog, sde_report_pack((unsigned)(a.jlaunch + 1), (unsigned)c.status),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      __hip_atomic_store(a.arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+  if (!a.arrive) {   // (a single step whose caller reduces the partials)
+    if (threadIdx.x == 0) { double* p = a.part + (size_t)blockIdx.x * PSTRIDE; p[0] = sde_wg_total<DT>(red); p[1] = 0.0; p[2] = 0.0; }
+    return;
   }
+  sde_step_footer<DT>(a, red, dt, adapt, 3);   // fills the fixed-grid record / runs the controller
   return;
   }
   }   // for (it)
 }
 
-// launch by shape: DT = ceil(D / 16) in 1..4, HT = ceil(H / 16) in 1..8
+// the gate of the one-launch kernels
 inline bool sde_fast_shape(int D, int H) { return D >= 1 && D <= SF_MAXD && H >= 1 && H <= SF_MAXH; }
-template <int DT> inline void sde_fast_launch_h(int HT, int nwg, hipStream_t st, const SdeFastArgs& f) {
-  switch (HT) {
-    case 1: hipLaunchKernelGGL((k_sde_eh_fast<DT, 1>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-    case 2: hipLaunchKernelGGL((k_sde_eh_fast<DT, 2>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-    case 3: hipLaunchKernelGGL((k_sde_eh_fast<DT, 3>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-    case 4: hipLaunchKernelGGL((k_sde_eh_fast<DT, 4>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-    case 5: hipLaunchKernelGGL((k_sde_eh_fast<DT, 5>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-    case 6: hipLaunchKernelGGL((k_sde_eh_fast<DT, 6>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-    case 7: hipLaunchKernelGGL((k_sde_eh_fast<DT, 7>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-    default: hipLaunchKernelGGL((k_sde_eh_fast<DT, 8>), dim3(nwg), dim3(SF_NT), 0, st, f); break;
-  }
+// launch by shape: fn(integral_constant DT, integral_constant HT) with DT = ceil(D / 16) in 1..4, HT = ceil(H / 16) in 1..8;
+// false, and nothing called, for a shape outside sde_fast_shape (every caller checks the gate first)
+template <class F, int... I> inline bool sde_fast_dispatch_(int k, F& fn, std::integer_sequence<int, I...>) {
+  return ((k == I && (fn(std::integral_constant<int, I / 8 + 1>{}, std::integral_constant<int, I % 8 + 1>{}), true)) || ...);
+}
+template <class F> inline bool sde_fast_dispatch(int D, int H, F fn) {
+  if (!sde_fast_shape(D, H)) return false;
+  return sde_fast_dispatch_(((D + 15) / 16 - 1) * 8 + (H + 15) / 16 - 1, fn, std::make_integer_sequence<int, 32>{});
 }
 inline void sde_fast_launch(int D, int H, int nwg, hipStream_t st, const SdeFastArgs& f) {
-  const int DT = (D + 15) / 16, HT = (H + 15) / 16;
-  switch (DT) {
-    case 1: sde_fast_launch_h<1>(HT, nwg, st, f); break;
-    case 2: sde_fast_launch_h<2>(HT, nwg, st, f); break;
-    case 3: sde_fast_launch_h<3>(HT, nwg, st, f); break;
-    default: sde_fast_launch_h<4>(HT, nwg, st, f); break;
-  }
+  sde_fast_dispatch(D, H, [&](auto dt, auto ht) { hipLaunchKernelGGL((k_sde_eh_fast<dt.value, ht.value>), dim3(nwg), dim3(SF_NT), 0, st, f); });
 }
 
 // the persistent form.  coop: a cooperative launch (all workgroups resident, or the call fails and the caller takes the
 // launch-per-step loop) — the API's guarantee costs 25-30 us per launch; !coop: a plain launch, for grids far smaller than the
 // chip, whose barrier is bounded (a workgroup that waits 50 ms for the others ends the solve with an error and the caller runs
 // the loop instead).  Returns the launch's hipError_t.
-template <int DT, int HT> inline hipError_t sde_persist_launch_1(int nwg, hipStream_t st, SdeFastArgs& f, bool coop) {
-  void* args[] = {&f};
-  if (!coop) { hipLaunchKernelGGL((k_sde_eh_fast<DT, HT, true>), dim3(nwg), dim3(SF_NT), 0, st, f); return hipGetLastError(); }
-  return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k_sde_eh_fast<DT, HT, true>), dim3(nwg), dim3(SF_NT), args, 0, st);
-}
-template <int DT> inline hipError_t sde_persist_launch_h(int HT, int nwg, hipStream_t st, SdeFastArgs& f, bool coop) {
-  switch (HT) {
-    case 1: return sde_persist_launch_1<DT, 1>(nwg, st, f, coop);
-    case 2: return sde_persist_launch_1<DT, 2>(nwg, st, f, coop);
-    case 3: return sde_persist_launch_1<DT, 3>(nwg, st, f, coop);
-    case 4: return sde_persist_launch_1<DT, 4>(nwg, st, f, coop);
-    case 5: return sde_persist_launch_1<DT, 5>(nwg, st, f, coop);
-    case 6: return sde_persist_launch_1<DT, 6>(nwg, st, f, coop);
-    case 7: return sde_persist_launch_1<DT, 7>(nwg, st, f, coop);
-    default: return sde_persist_launch_1<DT, 8>(nwg, st, f, coop);
-  }
-}
 inline hipError_t sde_persist_launch(int D, int H, int nwg, hipStream_t st, SdeFastArgs& f, bool coop) {
-  const int DT = (D + 15) / 16, HT = (H + 15) / 16;
-  switch (DT) {
-    case 1: return sde_persist_launch_h<1>(HT, nwg, st, f, coop);
-    case 2: return sde_persist_launch_h<2>(HT, nwg, st, f, coop);
-    case 3: return sde_persist_launch_h<3>(HT, nwg, st, f, coop);
-    default: return sde_persist_launch_h<4>(HT, nwg, st, f, coop);
-  }
+  hipError_t e = hipErrorInvalidValue;   // (a shape outside the gate: nothing is launched)
+  sde_fast_dispatch(D, H, [&](auto dt, auto ht) {
+    void* args[] = {&f};
+    if (!coop) { hipLaunchKernelGGL((k_sde_eh_fast<dt.value, ht.value, true>), dim3(nwg), dim3(SF_NT), 0, st, f); e = hipGetLastError(); }
+    else e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k_sde_eh_fast<dt.value, ht.value, true>), dim3(nwg), dim3(SF_NT), args, 0, st);
+  });
+  return e;
 }
