@@ -124,6 +124,23 @@ typedef struct {
 int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* desc, int device, void* stream);
 size_t lrnde_chain_param_count(const lrnde_chain_desc* desc);
 
+/* Wide Dense-chain vector field: the same descriptor and parameter layout as the small chain, for chains it refuses —
+ * every width in 1..LRNDE_WIDE_CHAIN_MAX_WIDTH, any weight size (the MNIST field with mlp_num_hidden_layers > 1,
+ * experiments/src/construct.jl:183-189: TDChain(Dense(785=>100,tanh), Dense(101=>100,tanh), Dense(101=>784))).  The
+ * weights are streamed from L2 as MFMA operands, 16 batch columns per workgroup; every dot product is
+ * the canonical one of the MLP handle (fp32 fma chains over 112-row segments, partials added left to right), so a
+ * two-layer chain gives the MLP handle's lrnde_rhs bits and a chain of widths <= 112 the small chain handle's.
+ * Checked here (LRNDE_BADARG / LRNDE_UNSUPPORTED with a message from lrnde_last_error(NULL)): nlayers in
+ * 1..LRNDE_CHAIN_MAX_LAYERS, dims[0] == dims[nlayers], every width in 1..LRNDE_WIDE_CHAIN_MAX_WIDTH, activations
+ * LRNDE_ACT_*; a chain whose parameter vector plus one workgroup's activation record exceed 256 MiB is refused (the
+ * VJP's scratch is bounded by that figure: larger batches run as several launches).
+ * A wide-chain handle is accepted by every entry point listed above for a chain handle, and by
+ * lrnde_node_forward_record_ce and lrnde_classifier_ce; it is refused with LRNDE_UNSUPPORTED by the same calls that refuse
+ * a chain handle (communicator entry points, lrnde_set_solver with VCAB3 / VCABM3, lrnde_set_overlap, lrnde_bench_step,
+ * lrnde_bench_exchange).  Its continuous adjoint runs the host-controlled loop. */
+#define LRNDE_WIDE_CHAIN_MAX_WIDTH 1024
+int lrnde_create_wide_chain(lrnde_ctx** out, const lrnde_chain_desc* desc, int device, void* stream);
+
 /* Hands the flat parameter vector `ps` (what ODEProblem(dudt, x, tspan, ps)
  * carries, src/layers/neural_ode.jl:50) to the library; repacked on device
  * into the MFMA operand layout.  Call again whenever ps changes. */

@@ -92,6 +92,24 @@ function create_chain(desc::ChainDesc; device=0, stream=C_NULL)
     rc == 0 || error("lrnde_create_chain: status $rc: " * unsafe_string(ccall((:lrnde_last_error, lib), Cstring, (Ptr{Cvoid},), C_NULL)))
     return ctx[]
 end
+# wide Dense-chain field: the same descriptor for chains beyond the small handle's limits (widths up to 1024, weights
+# streamed from L2; include/lrnde.h lrnde_create_wide_chain)
+const CHAIN_MAX_WIDTH = 128
+const CHAIN_MAX_WEIGHT_BYTES = 128 * 1024
+const WIDE_CHAIN_MAX_WIDTH = 1024
+function create_wide_chain(desc::ChainDesc; device=0, stream=C_NULL)
+    ctx = Ref{Ptr{Cvoid}}()
+    rc = ccall((:lrnde_create_wide_chain, lib), Cint, (Ptr{Ptr{Cvoid}}, Ref{ChainDesc}, Cint, Ptr{Cvoid}), ctx, desc, device, stream)
+    rc == 0 || error("lrnde_create_wide_chain: status $rc: " * unsafe_string(ccall((:lrnde_last_error, lib), Cstring, (Ptr{Cvoid},), C_NULL)))
+    return ctx[]
+end
+"bytes of the forward weight image the small chain's step kernel keeps in LDS (include/lrnde.h)"
+function chain_weight_image_bytes(desc::ChainDesc)
+    n = sum((Int(desc.dims[l]) + Int(desc.time_dep) + 1) * (Int(desc.dims[l + 1]) + Int(desc.dims[l + 1]) % 2) for l in 1:Int(desc.nlayers))
+    return 4 * (cld(n, 4) * 4)
+end
+"true: the chain is within the small handle's limits (lrnde_create_chain); false: it takes the wide handle"
+chain_is_small(desc::ChainDesc) = maximum(desc.dims) <= CHAIN_MAX_WIDTH && chain_weight_image_bytes(desc) <= CHAIN_MAX_WEIGHT_BYTES
 chain_param_count(desc::ChainDesc) = ccall((:lrnde_chain_param_count, lib), Csize_t, (Ref{ChainDesc},), desc)
 set_params!(ctx, ps) = check(ctx, ccall((:lrnde_set_params, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t),
                                         ctx, pointer(ps), length(ps)))

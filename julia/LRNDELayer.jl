@@ -62,7 +62,8 @@ function lrnde_field_shape(model)
 end
 
 "lrnde_chain_desc of any other Chain / TDChain of Dense layers (a plain Chain may open with `Base.Fix1(broadcast, act)` /
-`WrappedFunction`), or nothing: the Dense-chain handle (lrnde_create_chain), Tsit5 only"
+`WrappedFunction`), or nothing: a Dense-chain handle, Tsit5 only — the small one (lrnde_create_chain) within its limits,
+the wide one (lrnde_create_wide_chain, widths up to 1024) beyond them"
 function lrnde_chain_shape(model)
     layers = model isa TDChain ? collect(values(model.layers)) : (model isa Lux.Chain ? collect(values(model.layers)) : nothing)
     layers === nothing && return nothing
@@ -81,7 +82,7 @@ function lrnde_chain_shape(model)
         (l.in_dims == dims[end] + td && haskey(_LRNDE_ACT, l.activation)) || return nothing
         push!(dims, l.out_dims)
     end
-    (dims[end] == dims[1] && maximum(dims) <= 128) || return nothing
+    (dims[end] == dims[1] && maximum(dims) <= LRNDEBackend.WIDE_CHAIN_MAX_WIDTH) || return nothing
     return LRNDEBackend.ChainDesc(dims, Int32[_LRNDE_ACT[l.activation] for l in layers], td, in_act)
 end
 
@@ -93,7 +94,8 @@ _lrnde_alg(solver) = solver isa Tsit5 ? Int32(0) : nameof(typeof(solver)) === :V
 function lrnde_handle(n::NeuralODE)
     get!(_lrnde_handles, n) do
         if lrnde_field_shape(n.model) === nothing   # any other Dense chain: the Dense-chain handle (Tsit5 only)
-            return LRNDEBackend.create_chain(lrnde_chain_shape(n.model))
+            desc = lrnde_chain_shape(n.model)   # beyond the small handle's width / weight-image limits: the wide handle
+            return LRNDEBackend.chain_is_small(desc) ? LRNDEBackend.create_chain(desc) : LRNDEBackend.create_wide_chain(desc)
         end
         D, H, td, act = lrnde_field_shape(n.model)
         ctx = LRNDEBackend.create(D, H, td, act)

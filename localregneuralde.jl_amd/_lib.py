@@ -28,6 +28,13 @@ class ChainDesc(C.Structure):
                 ("dims", C.c_int32 * (CHAIN_MAX_LAYERS + 1)), ("act", C.c_int32 * CHAIN_MAX_LAYERS)]
 
 
+WIDE_CHAIN_MAX_WIDTH = 1024   # include/lrnde.h LRNDE_WIDE_CHAIN_MAX_WIDTH
+
+
+class WideChainDesc(ChainDesc):
+    """the same lrnde_chain_desc, meant for lrnde_create_wide_chain (widths up to WIDE_CHAIN_MAX_WIDTH, no image limit)"""
+
+
 def chain_weight_image_bytes(dims, time_dep):
     """bytes of the forward weight image the chain step kernel keeps in LDS (include/lrnde.h, lrnde_create_chain)"""
     n = sum((dims[l] + int(time_dep) + 1) * (dims[l + 1] + dims[l + 1] % 2) for l in range(len(dims) - 1))
@@ -88,6 +95,7 @@ SYMBOLS = [
     ("lrnde_param_count", C.c_size_t, [C.POINTER(ModelDesc)]),
     ("lrnde_create_chain", C.c_int, [C.POINTER(_vp), C.POINTER(ChainDesc), C.c_int, _vp]),
     ("lrnde_chain_param_count", C.c_size_t, [C.POINTER(ChainDesc)]),
+    ("lrnde_create_wide_chain", C.c_int, [C.POINTER(_vp), C.POINTER(ChainDesc), C.c_int, _vp]),
     ("lrnde_version", C.c_char_p, []),
     ("lrnde_set_params", C.c_int, [_vp, _vp, C.c_size_t]),
     ("lrnde_set_solver", C.c_int, [_vp, _i32]),

@@ -1624,6 +1624,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 #include "lrnde_adjoint.hpp"
 #include "lrnde_backward.hpp"
 #include "lrnde_chain.hpp"
+#include "lrnde_wide_chain.hpp"
 #include "lrnde_chain_adjoint.hpp"
 
 // single-step modes: EEst and the two regularisation values from the partial sums
@@ -1835,15 +1836,22 @@ struct lrnde_ctx {
   std::chrono::steady_clock::time_point hp_t[8];
   double hp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long hp_n = 0;
   bool adj_stage7_reused = false;   // the last stage-7 launch of the adjoint loop took y / h from stage 6's scratch set (its GEMM must too)
-  // field kind: 0 the two-layer MLP (lrnde_create), 1 the small Dense chain (lrnde_create_chain, lrnde_chain.hpp).  A
-  // chain handle keeps desc.state_dim = D (every state-sized buffer) and its own layer table / weight images here.
+  // field kind: 0 the two-layer MLP (lrnde_create), 1 the small Dense chain (lrnde_create_chain, lrnde_chain.hpp), 2 the
+  // wide Dense chain (lrnde_create_wide_chain, lrnde_wide_chain.hpp).  A chain handle of either kind keeps
+  // desc.state_dim = D (every state-sized buffer), its descriptor in `chain` and its own layer table / weight images here.
   int field = 0;
   lrnde_chain_desc chain{};
   ChainDev cd{};
   DevBuf<int> ch_meta; DevBuf<float> ch_wf, ch_wg;  // layer table, forward / backward weight images
   int ch_gfloats = 0;
   size_t ch_vjp_lds = 0;                                             // dynamic LDS of k_vjp_chain
-  DevBuf<float> ch_part;                   // per-workgroup parameter cotangents of k_vjp_chain
+  DevBuf<float> ch_part;                   // per-workgroup parameter cotangents of k_vjp_chain / k_vjp_wide
+  // the wide chain's layer table, forward / transposed weight images, t-column and bias vectors, and the VJP's
+  // per-workgroup activation records (scratch, bounded by wide_vjp_plan)
+  WideDev wd{};
+  DevBuf<int> w_meta; DevBuf<float> w_wf, w_wg, w_vec, w_rec;
+  int w_ftot = 0, w_gtot = 0, w_vtot = 0;
+  size_t w_lds = 0;                        // dynamic LDS of every wide-chain kernel
   // the chain handle's device-controlled adjoint loop (lrnde_chain_adjoint.hpp): control blocks, per-(stage, workgroup)
   // parameter cotangents, norm partials, tstop / impulse tables — allocated on first use, regrown only for a larger batch
   DevBuf<ChAdjCtrl> cha_ctl;
@@ -1967,7 +1975,7 @@ bool use_qtile(const lrnde_ctx* c, int B) {
   const bool no_qtile = opt(OPT_NO_QTILE) != 0;
   return shape_ok && ((double)B * D * 40.0 < 2147483000.0) && B <= qmax && !no_qtile;
 }
-inline int tile_nb(const lrnde_ctx* c, int B) { return c->field ? CNB : (use_qtile(c, B) ? QNB : NB); }
+inline int tile_nb(const lrnde_ctx* c, int B) { return c->field == 1 ? CNB : (c->field == 2 ? NB : (use_qtile(c, B) ? QNB : NB)); }
 // parameters of the handle's field (the flat Lux vector)
 size_t param_count(const lrnde_ctx* c) {
   return c->field ? lrnde_chain_param_count(&c->chain) : lrnde_param_count(&c->desc);
@@ -2046,6 +2054,13 @@ template <class K> int launch_tile_kernel(lrnde_ctx* c, K kern, int B, const Ste
 }
 
 int launch_step(lrnde_ctx* c, int B, const StepArgs& a, int j, bool spec = false) {
+  if (c->field == 2) {
+    const int nwg = (B + NB - 1) / NB;
+    if (spec) hipLaunchKernelGGL(k_step_wide<true>, dim3(nwg), dim3(NT), c->w_lds, c->stream, a, c->wd, j);
+    else hipLaunchKernelGGL(k_step_wide<false>, dim3(nwg), dim3(NT), c->w_lds, c->stream, a, c->wd, j);
+    HIPCHK(c, hipGetLastError());
+    return LRNDE_OK;
+  }
   if (c->field) {
     const int nwg = (B + CNB - 1) / CNB;
     const size_t sm = chain_smem_bytes(c->cd.wfloats);
@@ -2096,6 +2111,15 @@ int run_init(lrnde_ctx* c, int B, const StepArgs& a) {
   const size_t cnt = (size_t)a.nwg_global * PSTRIDE;
   const bool qt = use_qtile(c, B);
   const int nq = (B + QNB - 1) / QNB;
+  if (c->field == 2) {
+    const int nwg = (B + NB - 1) / NB;
+    hipLaunchKernelGGL(k_init1_wide, dim3(nwg), dim3(NT), c->w_lds, c->stream, a, c->wd);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = exchange(c, c->pinit, c->pinit_rx, cnt))) return rc;
+    hipLaunchKernelGGL(k_init2_wide, dim3(nwg), dim3(NT), c->w_lds, c->stream, a, c->wd);
+    HIPCHK(c, hipGetLastError());
+    return exchange(c, c->pinit + cnt, c->pinit_rx + cnt, cnt);
+  }
   if (c->field) {
     const int nwg = (B + CNB - 1) / CNB;
     const size_t sm = chain_smem_bytes(c->cd.wfloats);
@@ -2152,6 +2176,12 @@ int set_smem_attr() {
   hipFuncSetAttribute((const void*)k_rhs_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_vjp_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_chadj_step, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_step_wide<false>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_step_wide<true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_init1_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_init2_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_rhs_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_vjp_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   done = true;
   return 0;
 }
@@ -2194,6 +2224,8 @@ int side_get(lrnde_ctx* c, int B, lrnde_ctx** out) {
   s->W1q.borrow(c->W1q); s->W2q.borrow(c->W2q); s->V1p.borrow(c->V1p); s->U2p.borrow(c->U2p); s->V1q.borrow(c->V1q); s->U2q.borrow(c->U2q);
   s->field = c->field; s->chain = c->chain; s->cd = c->cd; s->ch_meta.borrow(c->ch_meta); s->ch_wf.borrow(c->ch_wf); s->ch_wg.borrow(c->ch_wg);
   s->ch_gfloats = c->ch_gfloats; s->ch_vjp_lds = c->ch_vjp_lds;
+  s->wd = c->wd; s->w_meta.borrow(c->w_meta); s->w_wf.borrow(c->w_wf); s->w_wg.borrow(c->w_wg); s->w_vec.borrow(c->w_vec);
+  s->w_ftot = c->w_ftot; s->w_gtot = c->w_gtot; s->w_vtot = c->w_vtot; s->w_lds = c->w_lds;
   const int rc = ensure_workspace(s, B);
   if (rc) { c->err = s->err; return rc; }
   *out = s;
@@ -2301,7 +2333,8 @@ static int chain_refuse(int code, const char* fmt, ...) {
   return code;
 }
 
-int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int device, void* stream) {
+// what both Dense-chain handles check of a descriptor (maxw, what: the handle's width limit and the name of its kernels)
+static int chain_desc_check(lrnde_ctx** out, const lrnde_chain_desc* d, int maxw, const char* what) {
   if (!out || !d) return chain_refuse(LRNDE_BADARG, "null pointer");
   *out = nullptr;
   g_create_err.clear();
@@ -2314,12 +2347,17 @@ int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int device, v
     return chain_refuse(LRNDE_BADARG, "dims[0] = %d != dims[nlayers] = %d: the field must map the state onto itself", d->dims[0], d->dims[L]);
   for (int l = 0; l <= L; ++l) {
     if (d->dims[l] <= 0) return chain_refuse(LRNDE_BADARG, "dims[%d] = %d must be positive", l, d->dims[l]);
-    if (d->dims[l] > LRNDE_CHAIN_MAX_WIDTH)
-      return chain_refuse(LRNDE_UNSUPPORTED, "dims[%d] = %d exceeds the chain kernels' width limit of %d (+1 for the t row)", l, d->dims[l],
-                          LRNDE_CHAIN_MAX_WIDTH);
+    if (d->dims[l] > maxw)
+      return chain_refuse(LRNDE_UNSUPPORTED, "dims[%d] = %d exceeds the %s kernels' width limit of %d (+1 for the t row)", l, d->dims[l], what, maxw);
   }
   for (int l = 0; l < L; ++l)
     if (d->act[l] < 0 || d->act[l] > 2) return chain_refuse(LRNDE_BADARG, "act[%d] must be identity, tanh or gelu", l);
+  return LRNDE_OK;
+}
+
+int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int device, void* stream) {
+  { const int rc = chain_desc_check(out, d, LRNDE_CHAIN_MAX_WIDTH, "chain"); if (rc) return rc; }
+  const int L = d->nlayers;
   const int td = d->time_dep;
   // the layer table and the two weight images (lrnde_chain.hpp); the forward image must fit LDS for the whole launch
   std::vector<int> meta((size_t)L * CMETA, 0);
@@ -2373,6 +2411,65 @@ int lrnde_create_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int device, v
   return LRNDE_OK;
 }
 
+int lrnde_create_wide_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int device, void* stream) {
+  { const int rc = chain_desc_check(out, d, LRNDE_WIDE_CHAIN_MAX_WIDTH, "wide chain"); if (rc) return rc; }
+  const int L = d->nlayers;
+  static_assert(LRNDE_WIDE_CHAIN_MAX_WIDTH == WMAXW, "header and kernels agree on the width limit");
+  const int td = d->time_dep;
+  // the layer table (lrnde_wide_chain.hpp): images, vectors, record offsets; the segment-partial region takes what the
+  // layers want of the LDS the two activation buffers leave (a layer whose partials do not fit keeps its segments in one wave)
+  std::vector<int> meta((size_t)L * WMETA, 0);
+  size_t wf = 0, wg = 0, wv = 0, poff = 0, roff = 0;
+  int maxw = 0, want = 0;
+  for (int l = 0; l <= L; ++l) maxw = std::max(maxw, d->dims[l]);
+  for (int l = 0; l < L; ++l) {
+    const int in = d->dims[l], o = d->dims[l + 1], MT = ceil16(o) / 16, KG = ceil16(in) / 16;
+    int* m = meta.data() + (size_t)l * WMETA;
+    m[WM_IN] = in; m[WM_OUT] = o; m[WM_ACT] = d->act[l]; m[WM_MT] = MT; m[WM_KG] = KG;
+    m[WM_WOFF] = (int)wf; m[WM_GOFF] = (int)wg; m[WM_VOFF] = (int)wv; m[WM_POFF] = (int)poff;
+    m[WM_RAOFF] = (int)roff; roff += (size_t)KG * 16 * NB;
+    m[WM_RZOFF] = (int)roff; roff += (size_t)MT * 16 * NB;
+    wf += (size_t)((MT + WT - 1) / WT) * WT * KG * 256;
+    wg += (size_t)((KG + WT - 1) / WT) * WT * MT * 256;
+    wv += (size_t)2 * MT * 16;
+    poff += (size_t)o * (in + td) + o;
+    want = std::max(want, std::max(wide_part_want(MT, KG), wide_part_want(KG, MT)));
+  }
+  const int rduoff = (int)roff;
+  roff += (size_t)ceil16(d->dims[0]) * NB;
+  const int bufw = ceil16(maxw) * NB;
+  const size_t fixed = wide_smem_bytes(bufw, 0);
+  const int partcap = (int)std::min<size_t>((size_t)want, ((WIDE_LDS_MAX - fixed) / sizeof(float)) & ~(size_t)255);
+  if (poff * sizeof(float) + roff * sizeof(float) > WIDE_SCRATCH_MAX)
+    return chain_refuse(LRNDE_UNSUPPORTED, "one workgroup's parameter-cotangent partial and activation record (%zu bytes) exceed the %zu bytes of "
+                        "scratch a wide-chain VJP launch may use", (poff + roff) * sizeof(float), WIDE_SCRATCH_MAX);
+  lrnde_ctx* c = new lrnde_ctx();
+  c->device = device;
+  c->stream = (hipStream_t)stream;
+  c->field = 2;
+  c->chain = *d;
+  c->desc.state_dim = d->dims[0]; c->desc.hidden_dim = maxw; c->desc.time_dep = td; c->desc.act = d->act[0];
+  ModelDev& m = c->m;
+  m.D = d->dims[0]; m.H = maxw; m.Dp = ceil16(m.D); m.Hp = ceil16(maxw); m.td = td; m.act = d->act[0];
+  m.MT1 = m.Hp / 16; m.KG1 = m.Dp / 16; m.MT2 = m.Dp / 16; m.KG2 = m.Hp / 16;
+  if (hipSetDevice(device) != hipSuccess) { delete c; return chain_refuse(LRNDE_HIP_ERROR, "hipSetDevice(%d) failed", device); }
+  set_smem_attr();
+  c->w_ftot = (int)wf; c->w_gtot = (int)wg; c->w_vtot = (int)wv;
+  c->w_lds = wide_smem_bytes(bufw, partcap);
+  bool ok = c->w_meta.once(meta.size()) == hipSuccess && c->w_wf.once(wf) == hipSuccess && c->w_wg.once(wg) == hipSuccess &&
+            c->w_vec.once(wv) == hipSuccess &&
+            c->ev0.create() == hipSuccess && c->ev1.create() == hipSuccess &&
+            c->evp[0].create() == hipSuccess && c->evp[1].create() == hipSuccess;
+  ok = ok && hipMemcpy(c->w_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) { lrnde_destroy(c); return chain_refuse(LRNDE_HIP_ERROR, "device allocation failed"); }
+  WideDev& w = c->wd;
+  w.L = L; w.td = td; w.in_act = d->input_act; w.D = d->dims[0]; w.P = (int)poff;
+  w.bufw = bufw; w.partcap = partcap; w.recfloats = (int)roff; w.rduoff = rduoff;
+  w.meta = c->w_meta; w.wf = c->w_wf; w.wg = c->w_wg; w.vec = c->w_vec;
+  *out = c;
+  return LRNDE_OK;
+}
+
 int lrnde_destroy(lrnde_ctx* c) {
   if (!c) return LRNDE_OK;
   hipSetDevice(c->device);
@@ -2397,6 +2494,12 @@ int lrnde_set_params(lrnde_ctx* c, const float* p, size_t n) {
   HIPCHK(c, hipSetDevice(c->device));
   { const int rq = side_quiesce(c); if (rq) return rq; }
   c->rec.reset_side_work();
+  if (c->field == 2) {
+    hipLaunchKernelGGL(k_pack_wide, dim3(512), dim3(256), 0, c->stream, p, c->wd, c->w_ftot, c->w_gtot, c->w_vtot, c->w_wf, c->w_wg, c->w_vec);
+    HIPCHK(c, hipGetLastError());
+    c->have_params = true;
+    return LRNDE_OK;
+  }
   if (c->field) {
     hipLaunchKernelGGL(k_pack_chain, dim3(128), dim3(256), 0, c->stream, p, c->cd, c->ch_gfloats, c->ch_wf, c->ch_wg);
     HIPCHK(c, hipGetLastError());
@@ -2430,6 +2533,11 @@ int lrnde_rhs(lrnde_ctx* c, const float* u, float t, int32_t B, float* du) {
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!u || !du) return fail(c, LRNDE_BADARG, "null state pointer");
+  if (c->field == 2) {
+    hipLaunchKernelGGL(k_rhs_wide, dim3((B + NB - 1) / NB), dim3(NT), c->w_lds, c->stream, c->wd, B, u, t, du);
+    HIPCHK(c, hipGetLastError());
+    return LRNDE_OK;
+  }
   if (c->field) {
     hipLaunchKernelGGL(k_rhs_chain, dim3((B + CNB - 1) / CNB), dim3(NT), chain_smem_bytes(c->cd.wfloats), c->stream, c->cd, B, u, t, du);
     HIPCHK(c, hipGetLastError());
@@ -3794,8 +3902,42 @@ static int launch_vjp_chain(lrnde_ctx* c, const float* y, const float* dense, fl
   }
   return LRNDE_OK;
 }
+// The wide chain's VJP scratch, stated once: a launch over `chunk` workgroups holds chunk activation records and (with a
+// parameter cotangent) chunk partial vectors of P floats, together at most WIDE_SCRATCH_MAX bytes.  A batch of more
+// workgroups runs as consecutive launches (lrnde_create_wide_chain refuses a chain one workgroup of which exceeds it).
+static int wide_vjp_chunk(const lrnde_ctx* c, int nwg, bool with_gp) {
+  const size_t per = ((size_t)c->wd.recfloats + (with_gp ? (size_t)c->wd.P : 0)) * sizeof(float);
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)nwg, WIDE_SCRATCH_MAX / per));
+}
+static int launch_vjp_wide(lrnde_ctx* c, const float* y, const float* dense, float theta, float dense_dt, float t,
+                           const float* lam, int B, float* dy, float* gp) {
+  const int nwg = (B + NB - 1) / NB;
+  const size_t P = param_count(c);
+  const int chunk = wide_vjp_chunk(c, nwg, gp != nullptr);
+  HIPCHK(c, c->w_rec.grow((size_t)chunk * c->wd.recfloats));
+  if (gp) HIPCHK(c, c->ch_part.grow((size_t)chunk * P));
+  for (int w0 = 0; w0 < nwg; w0 += chunk) {
+    const int nw = std::min(chunk, nwg - w0);
+    VjpWideArgs v{};
+    v.B = B; v.wg0 = w0; v.t = t; v.y = y; v.dense = dense; v.theta = theta; v.dense_dt = dense_dt; v.lam = lam; v.dy = dy;
+    v.gpart = gp ? c->ch_part.get() : nullptr; v.rec = c->w_rec;
+    hipLaunchKernelGGL(k_vjp_wide, dim3(nw), dim3(NT), c->w_lds, c->stream, c->wd, v);
+    HIPCHK(c, hipGetLastError());
+    c->adj_launches += gp ? 2 : 1;
+    if (gp) {  // workgroup order across the launches too: every launch after the first adds to gp
+      hipLaunchKernelGGL(k_chain_pgsum, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->ch_part, nw, (int)P, gp,
+                         (c->pg_accumulate || w0 > 0) ? 1 : 0);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
+  return LRNDE_OK;
+}
 static int launch_vjp(lrnde_ctx* c, const float* y, const float* dense, float theta, float dense_dt, float t,
                       const float* lam, int B, float* dy, float* gp, const StageIn* sin = nullptr) {
+  if (c->field == 2) {
+    if (sin) return fail(c, LRNDE_BADARG, "fused stage input needs the 4-column VJP kernel");
+    return launch_vjp_wide(c, y, dense, theta, dense_dt, t, lam, B, dy, gp);
+  }
   if (c->field) {
     if (sin) return fail(c, LRNDE_BADARG, "fused stage input needs the 4-column VJP kernel");
     return launch_vjp_chain(c, y, dense, theta, dense_dt, t, lam, B, dy, gp);
@@ -4412,7 +4554,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
 // parameter cotangents (7 x workgroups x P floats) within CHADJ_SCRATCH_MAX.  Outside it the host loop runs.
 struct ChAdjPlan { int nwg, nmu, wg_lds; size_t lds; };
 bool chadj_fits(const lrnde_ctx* c, int B, ChAdjPlan* pl) {
-  if (!c->field) return false;
+  if (c->field != 1) return false;   // (a wide chain's adjoint takes the host loop)
   const size_t P = param_count(c);
   const int nwg = (B + CNB - 1) / CNB;
   const size_t lds0 = chadj_smem_bytes(c->cd.wfloats, 0, c->ch_vjp_lds);

@@ -75,9 +75,9 @@ def _mlp_desc(model):
     return L.ModelDesc(D, H, int(td), L.ACT[l1.activation])
 
 
-def _chain_desc(model):
-    """lrnde_chain_desc of a Chain / TDChain of Dense layers, optionally led by an Activation (plain Chain only); the
-    shape checks and limits of lrnde_create_chain (include/lrnde.h)."""
+def _chain_structure(model):
+    """(td, input activation, Dense layers, dims) of a Chain / TDChain of Dense layers, optionally led by an Activation
+    (plain Chain only): the structural checks both Dense-chain fields share."""
     if not isinstance(model, (Chain, TDChain)):
         raise NotImplementedError("the Dense-chain field takes a Chain or TDChain of Dense layers")
     td = isinstance(model, TDChain)
@@ -103,19 +103,39 @@ def _chain_desc(model):
         dims.append(l.out_dims)
     if dims[-1] != dims[0]:
         raise ValueError(f"the chain maps {dims[0]} states to {dims[-1]}: a vector field needs the same width")
-    if max(dims) > L.CHAIN_MAX_WIDTH or min(dims) < 1:
-        raise NotImplementedError(f"every width of a Dense chain must be in 1..{L.CHAIN_MAX_WIDTH} (+1 for the t row); got {dims}")
-    nb = L.chain_weight_image_bytes(dims, td)
-    if nb > L.CHAIN_MAX_WEIGHT_BYTES:
-        raise NotImplementedError(f"the chain's weight image ({nb} bytes) exceeds the {L.CHAIN_MAX_WEIGHT_BYTES} bytes its step "
-                                  "kernel keeps on chip")
-    d = L.ChainDesc()
+    return td, in_act, dense, dims
+
+
+def _fill_chain_desc(d, td, in_act, dense, dims):
     d.nlayers, d.time_dep, d.input_act = len(dense), int(td), L.ACT[in_act]
     for i, v in enumerate(dims):
         d.dims[i] = v
     for i, l in enumerate(dense):
         d.act[i] = L.ACT[l.activation]
     return d
+
+
+def _chain_desc(model):
+    """lrnde_chain_desc of a Chain / TDChain of Dense layers, optionally led by an Activation (plain Chain only); the
+    shape checks and limits of lrnde_create_chain (include/lrnde.h)."""
+    td, in_act, dense, dims = _chain_structure(model)
+    if max(dims) > L.CHAIN_MAX_WIDTH or min(dims) < 1:
+        raise NotImplementedError(f"every width of a Dense chain must be in 1..{L.CHAIN_MAX_WIDTH} (+1 for the t row); got {dims}")
+    nb = L.chain_weight_image_bytes(dims, td)
+    if nb > L.CHAIN_MAX_WEIGHT_BYTES:
+        raise NotImplementedError(f"the chain's weight image ({nb} bytes) exceeds the {L.CHAIN_MAX_WEIGHT_BYTES} bytes its step "
+                                  "kernel keeps on chip")
+    return _fill_chain_desc(L.ChainDesc(), td, in_act, dense, dims)
+
+
+def _wide_chain_desc(model):
+    """the descriptor of the wide Dense-chain field (lrnde_create_wide_chain): the structural checks of _chain_desc, every
+    width in 1..WIDE_CHAIN_MAX_WIDTH, no weight-image limit (the weights are streamed, not held on chip)."""
+    td, in_act, dense, dims = _chain_structure(model)
+    if max(dims) > L.WIDE_CHAIN_MAX_WIDTH or min(dims) < 1:
+        raise NotImplementedError(f"every width of a wide Dense chain must be in 1..{L.WIDE_CHAIN_MAX_WIDTH} (+1 for the t row); "
+                                  f"got {dims}")
+    return _fill_chain_desc(L.WideChainDesc(), td, in_act, dense, dims)
 
 
 def chain_param_count(desc):
@@ -134,12 +154,13 @@ def flatten_chain_params(layers):
 
 def glorot_chain_params(model, seed=0, scale=1.0):
     """glorot_params for a Dense chain (same stream order: each layer's weight, then its zero bias); for the 2-layer
-    shape it equals glorot_params.  `scale` multiplies the weights (step-count tests at larger weight scales)."""
-    d = _chain_desc(model)
+    shape it equals glorot_params.  `scale` multiplies the weights (step-count tests at larger weight scales).  Any
+    chain either Dense-chain field takes (no width or image limit applies here)."""
+    td, _, dense, dims = _chain_structure(model)
     rng = np.random.default_rng(seed)
     out = []
-    for l in range(d.nlayers):
-        inn, o = d.dims[l] + d.time_dep, d.dims[l + 1]
+    for l in range(len(dense)):
+        inn, o = dims[l] + int(td), dims[l + 1]
         W = ((rng.random((inn, o), dtype=np.float32) - np.float32(0.5)) * np.float32(np.sqrt(24.0 / (inn + o)))).astype(np.float32)
         out += [(W * np.float32(scale)).ravel(), np.zeros(o, np.float32)]
     return np.concatenate(out)
@@ -190,8 +211,8 @@ def _solver_name(solver):
 
 
 class Handle:
-    """lrnde_ctx of the MLP field (desc: ModelDesc, lrnde_create) or of a Dense chain (desc: ChainDesc,
-    lrnde_create_chain)."""
+    """lrnde_ctx of the MLP field (desc: ModelDesc, lrnde_create), of a small Dense chain (desc: ChainDesc,
+    lrnde_create_chain) or of a wide one (desc: WideChainDesc, lrnde_create_wide_chain)."""
 
     def __init__(self, desc, device=None, stream=None):
         if not torch.cuda.is_available():
@@ -204,9 +225,12 @@ class Handle:
         self._stream = torch.cuda.current_stream(self.device) if stream is None else stream
         self._ctx = C.c_void_p()
         if self.is_chain:
-            rc = L.lib.lrnde_create_chain(C.byref(self._ctx), C.byref(desc), self.device, C.c_void_p(self._stream.cuda_stream))
+            wide = isinstance(desc, L.WideChainDesc)
+            create = L.lib.lrnde_create_wide_chain if wide else L.lib.lrnde_create_chain
+            rc = create(C.byref(self._ctx), C.byref(desc), self.device, C.c_void_p(self._stream.cuda_stream))
             if rc != 0:
-                raise L.LrndeError(rc, "lrnde_create_chain failed: " + L.lib.lrnde_last_error(None).decode())
+                raise L.LrndeError(rc, ("lrnde_create_wide_chain" if wide else "lrnde_create_chain") + " failed: " +
+                                   L.lib.lrnde_last_error(None).decode())
         else:
             rc = L.lib.lrnde_create(C.byref(self._ctx), C.byref(desc), self.device,
                                     C.c_void_p(self._stream.cuda_stream))
@@ -539,13 +563,14 @@ class NeuralODE:
         from .conv import conv_topology
         # field: "auto" routes the CIFAR node_core to the conv handle and the two-layer Dense field to the MLP handle (anything
         # else raises); "dense_chain" sends any Chain / TDChain of Dense layers (optionally led by an Activation) to the
-        # Dense-chain handle (lrnde_create_chain), the two-layer shape included
-        if field not in ("auto", "dense_chain"):
-            raise ValueError(f"field must be 'auto' or 'dense_chain' (got {field!r})")
+        # Dense-chain handle (lrnde_create_chain), the two-layer shape included; "wide_chain" sends the same models, with
+        # widths up to 1024 and weights of any size, to the wide Dense-chain handle (lrnde_create_wide_chain)
+        if field not in ("auto", "dense_chain", "wide_chain"):
+            raise ValueError(f"field must be 'auto', 'dense_chain' or 'wide_chain' (got {field!r})")
         self.field = field
-        if field == "dense_chain":
+        if field in ("dense_chain", "wide_chain"):
             self._conv = None
-            self.desc = _chain_desc(model)
+            self.desc = _chain_desc(model) if field == "dense_chain" else _wide_chain_desc(model)
             if self.solver != "tsit5":
                 raise NotImplementedError("VCAB3 / VCABM3 are built for the MLP field's handle (csrc/lrnde_adams.hpp)")
             self._handle = None
