@@ -455,12 +455,15 @@ __global__ __launch_bounds__(NT) void k_vjp_chain(ChainDev cd, VjpChainArgs v) {
     if (sl.valid[i]) v.dy[sl.g[i]] = gc[sl.lidx[i]] * du[sl.lidx[i]];
 }
 
-// gp = (accumulate ? gp : 0) + sum over the workgroups of their partial, in workgroup order
-__global__ void k_chain_pgsum(const float* part, int nwg, int P, float* gp, int accumulate) {
+// gp = (accumulate ? gp : 0) + sum over the workgroups of their partial, in workgroup order from 0.  A sum over several
+// launches' partials (the wide chain's chunked VJP) is one chain all the same: it starts from carry_in instead of 0 and,
+// but for the last launch, goes to carry_out instead of gp.
+__global__ void k_chain_pgsum(const float* part, int nwg, int P, float* gp, int accumulate, const float* carry_in, float* carry_out) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P; i += gridDim.x * blockDim.x) {
-    float acc = 0.f;
+    float acc = carry_in ? carry_in[i] : 0.f;
     for (int w = 0; w < nwg; ++w) acc = acc + part[(size_t)w * P + i];
-    gp[i] = accumulate ? gp[i] + acc : acc;
+    if (carry_out) carry_out[i] = acc;
+    else gp[i] = accumulate ? gp[i] + acc : acc;
   }
 }
 

@@ -1847,9 +1847,10 @@ struct lrnde_ctx {
   size_t ch_vjp_lds = 0;                                             // dynamic LDS of k_vjp_chain
   DevBuf<float> ch_part;                   // per-workgroup parameter cotangents of k_vjp_chain / k_vjp_wide
   // the wide chain's layer table, forward / transposed weight images, t-column and bias vectors, and the VJP's
-  // per-workgroup activation records (scratch, bounded by wide_vjp_plan)
+  // per-workgroup activation records (scratch, bounded by wide_vjp_chunk)
   WideDev wd{};
   DevBuf<int> w_meta; DevBuf<float> w_wf, w_wg, w_vec, w_rec;
+  DevBuf<float> w_gpsum;                   // P floats: the running workgroup-order sum of a VJP that takes several launches
   int w_ftot = 0, w_gtot = 0, w_vtot = 0;
   size_t w_lds = 0;                        // dynamic LDS of every wide-chain kernel
   // the chain handle's device-controlled adjoint loop (lrnde_chain_adjoint.hpp): control blocks, per-(stage, workgroup)
@@ -1878,14 +1879,14 @@ namespace {
 // path in the same process as the default one and holds the two to the same bits.
 enum {
   OPT_NO_QTILE, OPT_QTILE_MAX_B, OPT_NO_FUSE, OPT_DENSE_COPY, OPT_NO_OVERLAP, OPT_NO_SDE_FAST, OPT_SDE_HOST_LOOP, OPT_NO_QVJP,
-  OPT_ADJ_ERR_ONE_LAUNCH, OPT_ADJ_MU_FOLD, OPT_ADJ_OVERLAP, OPT_ADJ_HOST, OPT_VJP_QCOLS, OPT_PGRAD_TS, OPT_ADJ_NO_REUSE, OPT_NO_SDE_BWD_FUSED, OPT_SDE_NO_PERSIST, OPT_SDE_COOP_LAUNCH, OPT_SDE_PERSIST_STALL, OPT_SDE_HOST_INITDT, OPT_SDE_BWD_LDSACC, OPT_SDE_BWD_NO_DEFER, OPT_SDE_BWD_NO_RESIDENT, OPT_SDE_NO_MARCH, OPT_FEED_T, OPT_FEED_E, OPT_FEED_M, OPT_GATHER_TILES, OPT_FORCE_COMM, N_OPT
+  OPT_ADJ_ERR_ONE_LAUNCH, OPT_ADJ_MU_FOLD, OPT_ADJ_OVERLAP, OPT_ADJ_HOST, OPT_VJP_QCOLS, OPT_PGRAD_TS, OPT_ADJ_NO_REUSE, OPT_NO_SDE_BWD_FUSED, OPT_SDE_NO_PERSIST, OPT_SDE_COOP_LAUNCH, OPT_SDE_PERSIST_STALL, OPT_SDE_HOST_INITDT, OPT_SDE_BWD_LDSACC, OPT_SDE_BWD_NO_DEFER, OPT_SDE_BWD_NO_RESIDENT, OPT_SDE_NO_MARCH, OPT_FEED_T, OPT_FEED_E, OPT_FEED_M, OPT_GATHER_TILES, OPT_FORCE_COMM, OPT_WIDE_VJP_CHUNK, N_OPT
 };
 struct OptDef { const char* name; int dflt; bool flag; };   // flag: present in the environment = 1
 const OptDef g_optdef[N_OPT] = {
     {"LRNDE_NO_QTILE", 0, true}, {"LRNDE_QTILE_MAX_B", 2048, false}, {"LRNDE_NO_FUSE", 0, true}, {"LRNDE_DENSE_COPY", 0, true},
     {"LRNDE_NO_OVERLAP", 0, true}, {"LRNDE_NO_SDE_FAST", 0, true}, {"LRNDE_SDE_HOST_LOOP", 0, true}, {"LRNDE_NO_QVJP", 0, true},
     {"LRNDE_ADJ_ERR_ONE_LAUNCH", 0, true}, {"LRNDE_ADJ_MU_FOLD", 0, true}, {"LRNDE_ADJ_OVERLAP", 0, false}, {"LRNDE_ADJ_HOST", 0, true}, {"LRNDE_VJP_QCOLS", 4, false}, {"LRNDE_PGRAD_TS", 0, false}, {"LRNDE_ADJ_NO_REUSE", 0, true}, {"LRNDE_NO_SDE_BWD_FUSED", 0, true}, {"LRNDE_SDE_NO_PERSIST", 0, true}, {"LRNDE_SDE_COOP_LAUNCH", 0, true}, {"LRNDE_SDE_PERSIST_STALL", 0, true}, {"LRNDE_SDE_HOST_INITDT", 0, true}, {"LRNDE_SDE_BWD_LDSACC", 0, true}, {"LRNDE_SDE_BWD_NO_DEFER", 0, true}, {"LRNDE_SDE_BWD_NO_RESIDENT", 0, true}, {"LRNDE_SDE_NO_MARCH", 0, true}, {"LRNDE_FEED_T", 3, false}, {"LRNDE_FEED_E", 1, false},
-    {"LRNDE_FEED_M", 2, false}, {"LRNDE_GATHER_TILES", 0, true}, {"LRNDE_FORCE_COMM", 0, true}};
+    {"LRNDE_FEED_M", 2, false}, {"LRNDE_GATHER_TILES", 0, true}, {"LRNDE_FORCE_COMM", 0, true}, {"LRNDE_WIDE_VJP_CHUNK", 0, false}};
 int g_opt[N_OPT];
 bool g_opt_set[N_OPT];     // set by the hook: the environment no longer counts
 std::once_flag g_opt_once;
@@ -2440,9 +2441,10 @@ int lrnde_create_wide_chain(lrnde_ctx** out, const lrnde_chain_desc* d, int devi
   const int bufw = ceil16(maxw) * NB;
   const size_t fixed = wide_smem_bytes(bufw, 0);
   const int partcap = (int)std::min<size_t>((size_t)want, ((WIDE_LDS_MAX - fixed) / sizeof(float)) & ~(size_t)255);
-  if (poff * sizeof(float) + roff * sizeof(float) > WIDE_SCRATCH_MAX)
-    return chain_refuse(LRNDE_UNSUPPORTED, "one workgroup's parameter-cotangent partial and activation record (%zu bytes) exceed the %zu bytes of "
-                        "scratch a wide-chain VJP launch may use", (poff + roff) * sizeof(float), WIDE_SCRATCH_MAX);
+  // (one workgroup's partial vector and record always fit a launch's scratch: <= 16 layers of <= 1024 x 1025 weights are
+  // 67 MB of parameters and 2 MB of record against WIDE_SCRATCH_MAX = 256 MiB, so wide_vjp_chunk is >= 1 without a refusal)
+  static_assert(((size_t)16 * ((size_t)WMAXW * (WMAXW + 1) + WMAXW) + (size_t)(2 * 16 + 1) * WMAXW * NB) * sizeof(float) <= WIDE_SCRATCH_MAX,
+                "one workgroup of the largest wide chain fits a VJP launch's scratch");
   lrnde_ctx* c = new lrnde_ctx();
   c->device = device;
   c->stream = (hipStream_t)stream;
@@ -3897,17 +3899,21 @@ static int launch_vjp_chain(lrnde_ctx* c, const float* y, const float* dense, fl
   c->adj_launches += gp ? 2 : 1;
   if (gp) {
     hipLaunchKernelGGL(k_chain_pgsum, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->ch_part, nwg, (int)P, gp,
-                       c->pg_accumulate ? 1 : 0);
+                       c->pg_accumulate ? 1 : 0, (const float*)nullptr, (float*)nullptr);
     HIPCHK(c, hipGetLastError());
   }
   return LRNDE_OK;
 }
 // The wide chain's VJP scratch, stated once: a launch over `chunk` workgroups holds chunk activation records and (with a
 // parameter cotangent) chunk partial vectors of P floats, together at most WIDE_SCRATCH_MAX bytes.  A batch of more
-// workgroups runs as consecutive launches (lrnde_create_wide_chain refuses a chain one workgroup of which exceeds it).
+// workgroups runs as consecutive launches.  LRNDE_WIDE_VJP_CHUNK > 0 caps the chunk (the tests' way to the
+// several-launch path at a small batch).
 static int wide_vjp_chunk(const lrnde_ctx* c, int nwg, bool with_gp) {
   const size_t per = ((size_t)c->wd.recfloats + (with_gp ? (size_t)c->wd.P : 0)) * sizeof(float);
-  return (int)std::max<size_t>(1, std::min<size_t>((size_t)nwg, WIDE_SCRATCH_MAX / per));
+  size_t chunk = std::max<size_t>(1, std::min<size_t>((size_t)nwg, WIDE_SCRATCH_MAX / per));
+  const int cap = opt(OPT_WIDE_VJP_CHUNK);
+  if (cap > 0) chunk = std::min<size_t>(chunk, (size_t)cap);
+  return (int)chunk;
 }
 static int launch_vjp_wide(lrnde_ctx* c, const float* y, const float* dense, float theta, float dense_dt, float t,
                            const float* lam, int B, float* dy, float* gp) {
@@ -3916,6 +3922,10 @@ static int launch_vjp_wide(lrnde_ctx* c, const float* y, const float* dense, flo
   const int chunk = wide_vjp_chunk(c, nwg, gp != nullptr);
   HIPCHK(c, c->w_rec.grow((size_t)chunk * c->wd.recfloats));
   if (gp) HIPCHK(c, c->ch_part.grow((size_t)chunk * P));
+  // several launches: the workgroup-order sum runs on through them in w_gpsum (one chain 0 + p_0 + p_1 + ... whatever the
+  // chunk) and meets gp after the last, so gp has the bits of the single launch
+  const bool carry = gp && chunk < nwg;
+  if (carry) HIPCHK(c, c->w_gpsum.grow(P));
   for (int w0 = 0; w0 < nwg; w0 += chunk) {
     const int nw = std::min(chunk, nwg - w0);
     VjpWideArgs v{};
@@ -3924,9 +3934,11 @@ static int launch_vjp_wide(lrnde_ctx* c, const float* y, const float* dense, flo
     hipLaunchKernelGGL(k_vjp_wide, dim3(nw), dim3(NT), c->w_lds, c->stream, c->wd, v);
     HIPCHK(c, hipGetLastError());
     c->adj_launches += gp ? 2 : 1;
-    if (gp) {  // workgroup order across the launches too: every launch after the first adds to gp
+    if (gp) {
+      const float* cin = (carry && w0 > 0) ? c->w_gpsum.get() : nullptr;
+      float* cout = (carry && w0 + nw < nwg) ? c->w_gpsum.get() : nullptr;
       hipLaunchKernelGGL(k_chain_pgsum, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, c->stream, (const float*)c->ch_part, nw, (int)P, gp,
-                         (c->pg_accumulate || w0 > 0) ? 1 : 0);
+                         c->pg_accumulate ? 1 : 0, cin, cout);
       HIPCHK(c, hipGetLastError());
     }
   }

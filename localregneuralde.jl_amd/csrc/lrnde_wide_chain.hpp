@@ -28,13 +28,18 @@
 // VJP: the forward pass writes every layer's input and act' to a per-workgroup record in global scratch; then per layer
 // delta = g .* act', the tile's parameter cotangent (an MFMA over the tile's 16 columns: an fma chain in column order) goes
 // to a per-workgroup partial vector, and g <- W^T delta.  k_chain_pgsum adds the partials in workgroup order.  No atomics.
+// Stated exactly (tests/wide_chain_vjp_host.cpp restates it on the host, lrnde_vjp gives its bits): g <- W^T delta is
+// wide_gemm on the transposed image, i.e. 112-row segments over the layer's OUTPUTS, o ascending, segment sums left to
+// right; gW[o][k] is the fma chain from 0 over the tile's columns n = 0..15 (the columns past B are y = 0, lam = 0) of
+// a[k][n] * delta[o][n]; the t column the fma chain over n of delta[o][n] * t; the bias 0 + delta[o][0] + ...; gp the
+// partials added in workgroup order from 0, also when the batch takes several launches.
 
 constexpr int WT = 4;                    // row tiles a wave runs as independent accumulator chains
 constexpr int WMAXW = 1024;              // widest layer (LRNDE_WIDE_CHAIN_MAX_WIDTH)
 constexpr int WMETA = 12;                // ints per layer in the layer table
 constexpr size_t WIDE_LDS_MAX = 160 * 1024;
 // scratch of one VJP launch (activation records + parameter-cotangent partials of the workgroups it runs); a batch that
-// needs more runs as several launches over consecutive workgroups, a parameter vector that alone exceeds it is refused
+// needs more runs as several launches over consecutive workgroups (one workgroup's share always fits: lrnde_create_wide_chain)
 constexpr size_t WIDE_SCRATCH_MAX = (size_t)256 << 20;
 
 // per layer: in, out, act, MT = row tiles, KG = k-groups, woff / goff (forward / transposed image, floats), voff (t column

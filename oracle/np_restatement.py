@@ -244,9 +244,17 @@ def init_dt(f, u0, t0, t1, abstol, reltol):
     return min(f32(f32(100) * dt0), dt1, dtmax), f0
 
 
-def solve(f, u0, t0, t1, abstol, reltol, maxiters=10000, save_t=None, fast=False):
-    """adaptive Tsit5 from t0 to t1; returns dict(u, naccept, nreject, nf, dts[, u_save = sol(save_t) by dense output])"""
+def solve(f, u0, t0, t1, abstol, reltol, maxiters=10000, save_t=None, fast=False, saveat=None, save_start=False,
+          save_everystep=False):
+    """adaptive Tsit5 from t0 to t1; returns dict(u, naccept, nreject, nf, dts[, u_save = sol(save_t) by dense output]).
+    saveat (ascending times in (t0, t1]), save_start, save_everystep: savevalues! of every accepted step
+    — the saveat times it passes in order (dense output of the step, the step's u where the time is its end), then u at
+    the step's end if save_everystep — as t_saved / u_saved, with t_steps = every accepted step's (tprev, t)."""
     u_save = None
+    sv = [] if saveat is None else [f32(s) for s in saveat]
+    isave, t_saved, u_saved, t_steps = 0, [], [], []
+    if save_start:
+        t_saved.append(f32(t0)); u_saved.append(u0)
     t0, t1 = f32(t0), f32(t1)
     dt, k1 = init_dt(f, u0, t0, t1, abstol, reltol)
     gamma, qmin, qmax, qoldinit = f32(0.9), f32(0.2), f32(10), f32(1e-4)
@@ -289,10 +297,19 @@ def solve(f, u0, t0, t1, abstol, reltol, maxiters=10000, save_t=None, fast=False
             t = t1 if abs(f32(ttmp - t1)) < f32(f32(100) * _eps(max(t, t1))) else ttmp
             if save_t is not None and u_save is None and f32(save_t) <= t:
                 u_save = u if f32(save_t) == t else tsit5_interp(uprev, r["ks"], dt, f32(f32(f32(save_t) - tprev) / dt))
+            t_steps.append((tprev, t))
+            while isave < len(sv) and sv[isave] <= t:
+                ts = sv[isave]
+                u_saved.append(u if ts == t else tsit5_interp(uprev, r["ks"], dt, f32(f32(ts - tprev) / dt)))
+                t_saved.append(ts)
+                isave += 1
+            if save_everystep:
+                t_saved.append(t); u_saved.append(u)
             dtpropose = max(min(dtmax, dtnew), max(_eps(t), dtmin))
         else:
             nreject += 1
-    return dict(u=u, naccept=naccept, nreject=nreject, nf=nf, dts=np.array(dts, dtype=f32), u_save=u_save)
+    return dict(u=u, naccept=naccept, nreject=nreject, nf=nf, dts=np.array(dts, dtype=f32), u_save=u_save,
+                t_saved=np.array(t_saved, dtype=f32), u_saved=u_saved, t_steps=t_steps)
 
 
 def node_forward(f, x, t0, t2, abstol, reltol, t1, fast=False):

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 DEFAULTS = {"LRNDE_NO_QTILE": 0, "LRNDE_QTILE_MAX_B": 2048, "LRNDE_NO_FUSE": 0, "LRNDE_DENSE_COPY": 0, "LRNDE_NO_OVERLAP": 0,
             "LRNDE_NO_SDE_FAST": 0, "LRNDE_SDE_HOST_LOOP": 0, "LRNDE_NO_QVJP": 0, "LRNDE_ADJ_ERR_ONE_LAUNCH": 0, "LRNDE_ADJ_MU_FOLD": 0,
             "LRNDE_ADJ_HOST": 0, "LRNDE_VJP_QCOLS": 4, "LRNDE_ADJ_OVERLAP": 0, "LRNDE_PGRAD_TS": 0, "LRNDE_ADJ_NO_REUSE": 0, "LRNDE_SDE_NO_PERSIST": 0, "LRNDE_SDE_COOP_LAUNCH": 0, "LRNDE_SDE_PERSIST_STALL": 0, "LRNDE_SDE_HOST_INITDT": 0, "LRNDE_SDE_BWD_LDSACC": 0, "LRNDE_SDE_BWD_NO_DEFER": 0, "LRNDE_SDE_BWD_NO_RESIDENT": 0, "LRNDE_SDE_NO_MARCH": 0, "LRNDE_NO_SDE_BWD_FUSED": 0,
-            "LRNDE_FEED_T": 3, "LRNDE_FEED_E": 1, "LRNDE_FEED_M": 2}
+            "LRNDE_FEED_T": 3, "LRNDE_FEED_E": 1, "LRNDE_FEED_M": 2, "LRNDE_WIDE_VJP_CHUNK": 0}
 
 
 @pytest.fixture
@@ -153,6 +153,50 @@ def test_sde_layer_switch_gives_the_default_bits(gpu_pkg, options, switch, mode)
             x, y = base.pop(k), got.pop(k)
             assert np.allclose(x, y, rtol=2e-5, atol=2e-5 * float(np.abs(x).max())), (switch, mode, k)
     _same(base, got, (switch, mode))
+
+
+def _wide_vjp_pass(P):
+    """the wide chain's VJP at B = 33 (three workgroups) and B = 80, and a pullback whose regulariser sweep adds to the adjoint's
+    parameter gradient (pg_accumulate)"""
+    import torch
+    import wide_chain_cases as WC
+    out = {}
+    for name in ("mnist3", "odd_td"):
+        model = WC.shapes(P)[name]
+        h, p, x = WC.mk(P, model, 33)
+        xd = torch.from_numpy(x).cuda()
+        lam = torch.from_numpy(np.random.default_rng(7).standard_normal(x.shape).astype(np.float32)).cuda()
+        dy, gp = h.vjp(xd, 0.61, lam)
+        out[name + "_dy"], out[name + "_gp"] = dy.cpu().numpy(), gp.cpu().numpy()
+        out[name + "_dy_alone"] = h.vjp(xd, 0.61, lam, want_gp=False)[0].cpu().numpy()
+        if name == "odd_td":   # five workgroups: with a chunk of 2 a later launch holds two, where summing each launch from 0 shows
+            x5 = torch.from_numpy(WC.mk_inputs(P, model, 80)[1]).cuda()
+            l5 = torch.from_numpy(np.random.default_rng(8).standard_normal(tuple(x5.shape)).astype(np.float32)).cuda()
+            out["odd_td_gp_80"] = h.vjp(x5, 0.61, l5)[1].cpu().numpy()
+        h.close()
+    node = P.NeuralODE(model, regularize="unbiased", abstol=1e-5, reltol=1e-5, saveat=[0.25, 0.5, 1.0], save_start=False,
+                       field="wide_chain")
+    st = node.initialstates(np.random.default_rng(1))
+    cots = torch.from_numpy(np.random.default_rng(4).standard_normal((3,) + x.shape).astype(np.float32)).cuda()
+    dx, dp, info = node.pullback(xd, torch.from_numpy(p).cuda(), st, cots, w_reg=2.0)
+    out.update(dx=dx.cpu().numpy(), dp=dp.cpu().numpy(), reg_val=info["reg_val"])
+    node.handle().close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def wide_vjp_baseline(gpu_pkg):
+    for k, v in DEFAULTS.items():
+        gpu_pkg.set_option(k, v)
+    return _wide_vjp_pass(gpu_pkg)
+
+
+@pytest.mark.parametrize("chunk", [1, 2])
+def test_wide_vjp_chunk_gives_the_default_bits(gpu_pkg, options, wide_vjp_baseline, chunk):
+    """a VJP over several launches (1 + 1 + 1 and 2 + 1 workgroups) carries the workgroup-order sum through them"""
+    assert wide_vjp_baseline["reg_val"] > 0 and np.abs(wide_vjp_baseline["dp"]).max() > 0
+    options("LRNDE_WIDE_VJP_CHUNK", chunk)
+    _same(wide_vjp_baseline, _wide_vjp_pass(gpu_pkg), ("LRNDE_WIDE_VJP_CHUNK", chunk))
 
 
 def test_unknown_option_is_rejected(gpu_pkg):

@@ -1,7 +1,9 @@
 """The wide Dense-chain vector field (lrnde_create_wide_chain, csrc/lrnde_wide_chain.hpp; NeuralODE(field="wide_chain")):
 Dense chains wider than 128 — the MNIST TDChain with two hidden layers among them — with weights streamed as MFMA operands.
 
-Yardsticks.  Bits: the float32 host restatement in the canonical order (tests/wide_chain_host.cpp), the MLP handle and the
+Yardsticks.  Bits: the float32 host restatements in the canonical order (tests/wide_chain_host.cpp for the field,
+tests/wide_chain_vjp_host.cpp for its vector-Jacobian product) on shapes that between them take every branch of wide_gemm
+in both directions (tests/test_host_wide_chain.py holds wide_chain_cases.gemm_paths to that), the MLP handle and the
 C oracle on the two-layer MNIST shape, the small chain handle on the PhysioNet shape.  Everything else: float64
 restatements (a numpy field rounded once to float32 under np_restatement's Tsit5 step / solve) and float64 torch autograd
 through a fine RK4 integration — no code shared with the kernels.  Tolerances are tests/test_gpu_chain.py's: 1e-5
@@ -20,7 +22,7 @@ import wide_chain_cases as WC
 
 pytestmark = pytest.mark.gpu
 
-ALL = ["mnist2", "mnist3", "seg_edges", "odd_td", "deep16", "w1024", "physionet"]
+ALL = ["mnist2", "mnist3", "seg_edges", "odd_td", "deep16", "w1024", "physionet", "sq520", "cap_mixed", "cap_fwd", "full1024"]
 
 
 def cu(a):
@@ -38,6 +40,54 @@ def test_rhs_is_the_host_restatement_bit_for_bit(gpu_pkg, name):
             got = h.rhs(cu(x[:B]), t).cpu().numpy()
             want = WC.run_host(model, p, x[:B], t)
             assert np.array_equal(got, want), (name, B, t, WC.err(got, want))
+
+
+def _vjp_inputs(P, name, B):
+    model = WC.shapes(P)[name]
+    h, p, x = WC.mk(P, model, B)
+    lam = np.random.default_rng(7).standard_normal(x.shape).astype(np.float32)
+    return model, h, p, x, lam
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_vjp_is_the_host_restatement_bit_for_bit(gpu_pkg, name):
+    """dy and the parameter cotangent in the order the header states: 112-output segments of W^T delta left to right, the
+    tile's columns 0..15 as one fma chain per weight, the t column by fma, the bias a plain sum, tiles in tile order"""
+    P = gpu_pkg
+    t = 0.61
+    model, h, p, x, lam = _vjp_inputs(P, name, max(WC.BATCHES))
+    for B in WC.BATCHES:
+        dy, gp = h.vjp(cu(x[:B]), t, cu(lam[:B]))
+        wdy, wgp = WC.run_vjp_host(model, p, x[:B], lam[:B], t)
+        dy, gp = dy.cpu().numpy(), gp.cpu().numpy()
+        assert np.array_equal(dy, wdy), (name, B, "dy", WC.err(dy, wdy), int((dy != wdy).sum()))
+        assert np.array_equal(gp, wgp), (name, B, "gp", WC.err(gp, wgp), int((gp != wgp).sum()))
+        dy2, none = h.vjp(cu(x[:B]), t, cu(lam[:B]), want_gp=False)
+        assert none is None and np.array_equal(dy2.cpu().numpy(), wdy), (name, B, "dy without gp")
+
+
+def test_vjp_over_two_launches_is_the_host_restatement(gpu_pkg):
+    """full1024 at B = 497: 32 workgroups, of which one launch's scratch (256 MiB: a record and a P-float partial each)
+    holds 30; the second launch runs workgroups 30 and 31, the last with one column"""
+    P = gpu_pkg
+    name, B, t = "full1024", 497, 0.61
+    dims = WC.model_dims(WC.shapes(P)[name])
+    nwg, chunk = -(-B // WC.NB), WC.vjp_chunk(dims, 0)
+    assert chunk == 30 < nwg == 32 and B - 31 * WC.NB == 1
+    model, h, p, x, lam = _vjp_inputs(P, name, B)
+    dy, gp = h.vjp(cu(x), t, cu(lam))
+    dy, gp = dy.cpu().numpy(), gp.cpu().numpy()
+    wdy, wgp = WC.run_vjp_host(model, p, x, lam, t)
+    assert np.array_equal(dy, wdy), ("dy", WC.err(dy, wdy), int((dy != wdy).sum()))
+    assert np.array_equal(gp, wgp), ("gp", WC.err(gp, wgp), int((gp != wgp).sum()))
+    # (what each launch summing from 0 would have given is another vector)
+    assert not np.array_equal(WC.run_vjp_host(model, p, x[:64], lam[:64], t, chunk=2)[1], WC.run_vjp_host(model, p, x[:64], lam[:64], t)[1])
+    (dy64, gp64), (bar_dy, bar_gp), e32 = WC.vjp_bars(model, p, x, lam, t)
+    edy, egp = WC.err(dy, dy64), WC.err(gp, gp64)
+    print(f"{name} B={B}: dy err {edy:.2e} gp err {egp:.2e}; float32 autograd {e32[0]:.2e} {e32[1]:.2e}; bars {bar_dy:.2e} {bar_gp:.2e}")
+    assert edy <= bar_dy and egp <= bar_gp
+    dy2, none = h.vjp(cu(x), t, cu(lam), want_gp=False)   # 32 records fit one launch
+    assert none is None and np.array_equal(dy2.cpu().numpy(), wdy)
 
 
 @pytest.mark.parametrize("B", [16, 33])
@@ -110,7 +160,7 @@ def test_forward_and_pullback_repeat_bitwise(gpu_pkg, name):
 
 
 # ---- 3. perform_step and init_dt ----
-@pytest.mark.parametrize("name", ["mnist3", "seg_edges", "odd_td", "deep16"])
+@pytest.mark.parametrize("name", ["mnist3", "seg_edges", "odd_td", "deep16", "sq520", "cap_mixed"])
 @pytest.mark.parametrize("scale", [1.0, 3.0])
 def test_perform_step_and_init_dt_vs_float64(gpu_pkg, name, scale):
     P = gpu_pkg
@@ -161,6 +211,67 @@ def test_solve_counts_and_states_vs_float64(gpu_pkg, name, scale, tol):
     assert WC.err(got["u"][0].cpu().numpy(), ref["u_save"]) <= max(1e-5, 0.5 * tol, 4.0 * WC.err(r32["u_save"], ref["u_save"]))
 
 
+def _saved_bar(tol, u32, u64):
+    return max(1e-5, 0.5 * tol, 4.0 * WC.err(u32, u64))
+
+
+@pytest.mark.parametrize("name,scale,tol", WC.FOOTER_CASES)
+def test_save_footer_saveat_and_save_start_vs_float64(gpu_pkg, name, scale, tol):
+    """k_step_wide's savevalues footer: the start value, two save times inside one accepted step (its slot loop), one in
+    another step, the end copy; odd130 at D % 4 != 0 and with a rejected step between"""
+    P = gpu_pkg
+    model, B = WC.count_shapes(P)[name]
+    h, p, x = WC.mk(P, model, B, scale=scale)
+    f64, f32 = WC.Chain64(model, p), WC.Chain32(model, p)
+    saves = WC.footer_saves(R.solve(f64, x, 0.0, 1.0, tol, tol)["t_steps"]) + [1.0]
+    ref = R.solve(f64, x, 0.0, 1.0, tol, tol, saveat=saves, save_start=True)
+    r32 = R.solve(f32, x, 0.0, 1.0, tol, tol, saveat=saves, save_start=True)
+    hold = WC.steps_holding(ref["t_steps"], saves[:3])
+    assert hold[1] == hold[2] != hold[0]
+    got = h.solve(cu(x), 0.0, 1.0, tol, tol, saveat=saves, save_start=True, save_everystep=False, maxiters=10000)
+    assert (got["stats"]["naccept"], got["stats"]["nreject"]) == (ref["naccept"], ref["nreject"])
+    assert np.array_equal(got["t"], ref["t_saved"]) and len(got["t"]) == 5
+    assert torch.equal(got["u"][0], cu(x))
+    for i in range(5):
+        e, bar = WC.err(got["u"][i].cpu().numpy(), ref["u_saved"][i]), _saved_bar(tol, r32["u_saved"][i], ref["u_saved"][i])
+        print(f"{name} x{scale} t={got['t'][i]:.4f}: gpu err {e:.2e} bar {bar:.2e}")
+        assert e <= bar, (i, e, bar)
+
+
+@pytest.mark.parametrize("name,scale,tol", WC.FOOTER_CASES)
+def test_save_footer_everystep_vs_float64(gpu_pkg, name, scale, tol):
+    """save_everystep beside save times and save_start: per accepted step the save times it passes, then its end.  The
+    times the call gives (start, save times, t1) are exact and sit at the restatement's places in the series; a step's end
+    is where the float32 controller put it (the float64 restatement's differs in the last digits), so its state is held
+    to the float64 solution at that very time"""
+    P = gpu_pkg
+    model, B = WC.count_shapes(P)[name]
+    h, p, x = WC.mk(P, model, B, scale=scale)
+    f64, f32 = WC.Chain64(model, p), WC.Chain32(model, p)
+    saves = WC.footer_saves(R.solve(f64, x, 0.0, 1.0, tol, tol)["t_steps"])
+    ref = R.solve(f64, x, 0.0, 1.0, tol, tol, saveat=saves, save_start=True, save_everystep=True)
+    got = h.solve(cu(x), 0.0, 1.0, tol, tol, saveat=saves, save_start=True, save_everystep=True, maxiters=10000)
+    assert (got["stats"]["naccept"], got["stats"]["nreject"]) == (ref["naccept"], ref["nreject"])
+    tg = got["t"]
+    assert len(tg) == len(ref["t_saved"]) == 1 + 3 + ref["naccept"]
+    given = np.isin(ref["t_saved"], np.array([0.0] + saves, np.float32))
+    assert np.array_equal(tg[given], ref["t_saved"][given]) and tg[-1] == np.float32(1.0) and np.all(np.diff(tg) > 0)
+    print(f"{name} x{scale}: step ends differ from the float64 solve's by at most {np.abs(tg - ref['t_saved']).max():.2e}")
+    ends = [float(v) for v in tg[~given]]
+    at64 = R.solve(f64, x, 0.0, 1.0, tol, tol, saveat=ends)["u_saved"]
+    at32 = R.solve(f32, x, 0.0, 1.0, tol, tol, saveat=ends)["u_saved"]
+    assert len(at64) == len(ends) == ref["naccept"]
+    want = iter(at64); w32 = iter(at32)
+    r32 = R.solve(f32, x, 0.0, 1.0, tol, tol, saveat=saves, save_start=True, save_everystep=True)
+    worst = 0.0
+    for i in range(len(tg)):
+        u64, u32 = (ref["u_saved"][i], r32["u_saved"][i]) if given[i] else (next(want), next(w32))
+        e, bar = WC.err(got["u"][i].cpu().numpy(), u64), _saved_bar(tol, u32, u64)
+        worst = max(worst, e / bar)
+        assert e <= bar, (i, float(tg[i]), bool(given[i]), e, bar)
+    print(f"{name} x{scale}: {len(tg)} saved states, worst err / bar {worst:.2f}")
+
+
 # ---- 5. layer forward ----
 @pytest.fixture(scope="module")
 def mnist3_rk4(gpu_pkg):
@@ -193,9 +304,7 @@ def test_layer_forward_modes_vs_float64(gpu_pkg, mnist3_rk4, mode):
 @pytest.mark.parametrize("name", ALL)
 def test_vjp_vs_float64_autograd(gpu_pkg, name):
     P = gpu_pkg
-    model = WC.shapes(P)[name]
-    h, p, x = WC.mk(P, model, 17)
-    lam = np.random.default_rng(7).standard_normal(x.shape).astype(np.float32)
+    model, h, p, x, lam = _vjp_inputs(P, name, 17)
     t = 0.61
     dy, gp = h.vjp(cu(x), t, cu(lam))
     pt = torch.tensor(p, dtype=torch.float64, requires_grad=True)
