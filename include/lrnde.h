@@ -137,9 +137,19 @@ size_t lrnde_chain_param_count(const lrnde_chain_desc* desc);
  * A wide-chain handle is accepted by every entry point listed above for a chain handle, and by
  * lrnde_node_forward_record_ce and lrnde_classifier_ce; it is refused with LRNDE_UNSUPPORTED by the same calls that refuse
  * a chain handle (communicator entry points, lrnde_set_solver with VCAB3 / VCABM3, lrnde_set_overlap, lrnde_bench_step,
- * lrnde_bench_exchange).  Its continuous adjoint runs the host-controlled loop. */
+ * lrnde_bench_exchange).  Its continuous adjoint runs the host-controlled loop by default and, after
+ * lrnde_set_adjoint_loop(ctx, LRNDE_ADJ_LOOP_DEVICE), the device-controlled loop of two launches per attempted step. */
 #define LRNDE_WIDE_CHAIN_MAX_WIDTH 1024
 int lrnde_create_wide_chain(lrnde_ctx** out, const lrnde_chain_desc* desc, int device, void* stream);
+
+/* Which loop runs the reversed solve of lrnde_node_backward_recorded(_ts) / lrnde_node_backward on this handle.
+ * LRNDE_ADJ_LOOP_AUTO (the default): every handle's own routing; a wide-chain handle takes the host-controlled loop.
+ * LRNDE_ADJ_LOOP_DEVICE: a wide-chain handle takes its device-controlled loop (same bits as the host loop); a backward
+ * call whose batch is outside that loop's gate (LDS, workgroups, 256 MiB of stage records) returns LRNDE_UNSUPPORTED with
+ * a message naming the limit and leaves the handle and its forward record usable.  On a handle whose AUTO routing already
+ * is a device loop it is accepted and changes nothing.  The diagnostic switch LRNDE_ADJ_HOST=1 still forces the host loop. */
+enum { LRNDE_ADJ_LOOP_AUTO = 0, LRNDE_ADJ_LOOP_DEVICE = 1 };
+int lrnde_set_adjoint_loop(lrnde_ctx* ctx, int32_t loop);
 
 /* Hands the flat parameter vector `ps` (what ODEProblem(dudt, x, tspan, ps)
  * carries, src/layers/neural_ode.jl:50) to the library; repacked on device

@@ -60,7 +60,8 @@ int lrnde_set_adjoint_trace(lrnde_ctx* ctx, lrnde_trace_row* rows_host, int32_t 
 int lrnde_adjoint_trace_rows(lrnde_ctx* ctx, int32_t* n_host);
 /* Diagnostic: how the reversed solve of the last lrnde_node_backward_recorded(_ts) / lrnde_node_backward ran.
  * kind: 0 the host-controlled loop (vec_tsit5_solve; LRNDE_ADJ_HOST=1, sharded handles, shapes outside the device loops'
- * gates), 1 the MLP handle's device-controlled loop, 2 the chain handle's (lrnde_chain_adjoint.hpp).  launches: kernels the
+ * gates), 1 the MLP handle's device-controlled loop, 2 the chain handle's (lrnde_chain_adjoint.hpp), 3 the wide-chain
+ * handle's (lrnde_wide_adjoint.hpp, lrnde_set_adjoint_loop).  launches: kernels the
  * solve enqueued, from its first launch to k_adj_out (the regulariser's sweep is not counted).  host_waits: stream
  * synchronisations and blocking copies the host made before the solve's end with nothing enqueued behind them, i.e. waits
  * during which the GPU idles; the final wait is not counted, and polling the pinned progress word while an attempt is

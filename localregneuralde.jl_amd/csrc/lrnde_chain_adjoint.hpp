@@ -36,6 +36,8 @@ struct ChAdjCtrl {
   int hit;         // the step accepted by this prologue landed on impulses [imp0, imp1): lambda += du, K1 re-evaluated
   int imp0, imp1;
   AdjStage st_hit; // the dense-record position of that re-evaluation
+  // the wide handle's stage record (lrnde_wide_adjoint.hpp): the slot that holds K1's evaluation and its forward time
+  int k1slot; float k1t;
 };
 
 struct ChAdjArgs {
@@ -115,13 +117,14 @@ __device__ __forceinline__ ChAdjCtrl chadj_prologue(const ChAdjArgs& a, int j) {
         t = snap_magnitude(c.t, c.dt, c.tstop);
         c.dtpropose = pi_propose(c.dt, ps.q, dtmax, dt_floor(t, dtmin));
         c.cur ^= 1;  // z <- z_new, K1 <- K7 (FSAL)
+        cc.k1slot = (cc.k1slot + 6) & 7; cc.k1t = c.st[5].t;
         dt = c.dtpropose;
         // a cotangent impulse at the saved time just reached (vec_tsit5_solve: lambda += du, K1 re-evaluated, nf += 1)
         while (cc.iimp < a.nimp && a.imp[cc.iimp].s < t) ++cc.iimp;
         cc.imp0 = cc.iimp;
         while (cc.iimp < a.nimp && a.imp[cc.iimp].s == t && t < g.s1) ++cc.iimp;
         cc.imp1 = cc.iimp;
-        if (cc.imp1 > cc.imp0) { cc.hit = 1; c.nf += 1; cc.st_hit = adj_lookup_lanes(g, rec, -t); }
+        if (cc.imp1 > cc.imp0) { cc.hit = 1; c.nf += 1; cc.st_hit = adj_lookup_lanes(g, rec, -t); cc.k1t = cc.st_hit.t; }
       } else {
         c.nreject++;
         dt = pi_reject_dt(pi, c.dt, c.q11);
@@ -131,6 +134,24 @@ __device__ __forceinline__ ChAdjCtrl chadj_prologue(const ChAdjArgs& a, int j) {
   adj_header(g, c, rec, stop_l, t, dt);
   if (c.status == ST_DONE) cc.hit = 0;
   if (pub) chadj_report(a, cc, j);
+  return cc;
+}
+
+// ode_determine_initdt's evaluation point (one wave; every lane returns it): the start for CHADJ_INIT_A; for CHADJ_INIT_B
+// s0 + dt0 with dt0 from the partials of d0 and d1.  st_hit is its dense-record position.
+__device__ __forceinline__ ChAdjCtrl chadj_init_ctrl(const ChAdjArgs& a, int mode) {
+  const AdjArgs& g = a.g;
+  const AdjRecLanes rec = adj_rec_load(g);
+  ChAdjCtrl cc = a.cc[0];
+  float ts = g.s0;
+  if (mode == CHADJ_INIT_B) {
+    const double ntot = (double)g.n_lam + (double)g.P;
+    const float d0 = (float)sqrt(chadj_sum(chadj_set(a, 0), a.np) / ntot);
+    const float d1 = (float)sqrt(chadj_sum(chadj_set(a, 1), a.np) / ntot);
+    cc.c.dt0 = initdt_dt0(d0, d1, g.dtmax);
+    ts = g.s0 + cc.c.dt0;
+  }
+  cc.st_hit = adj_lookup_lanes(g, rec, -ts);
   return cc;
 }
 
@@ -244,17 +265,7 @@ __global__ __launch_bounds__(NT) void k_chadj_step(ChAdjArgs a, ChainDev cd, int
   if (mode != CHADJ_STEP) {
     // ---- ode_determine_initdt's evaluations (vec_tsit5_solve's first block) ----
     if (threadIdx.x < 64) {
-      const AdjRecLanes rec = adj_rec_load(g);
-      ChAdjCtrl cc = a.cc[0];
-      float ts = g.s0;
-      if (mode == CHADJ_INIT_B) {
-        const double ntot = (double)g.n_lam + (double)g.P;
-        const float d0 = (float)sqrt(chadj_sum(chadj_set(a, 0), a.np) / ntot);
-        const float d1 = (float)sqrt(chadj_sum(chadj_set(a, 1), a.np) / ntot);
-        cc.c.dt0 = initdt_dt0(d0, d1, g.dtmax);
-        ts = g.s0 + cc.c.dt0;
-      }
-      cc.st_hit = adj_lookup_lanes(g, rec, -ts);
+      const ChAdjCtrl cc = chadj_init_ctrl(a, mode);
       if ((threadIdx.x & 63) == 0) *s.bc = cc;
     }
     __syncthreads();
@@ -481,5 +492,6 @@ __global__ __launch_bounds__(64) void k_chadj_begin(ChAdjBegin b) {
   ChAdjCtrl c;
   memset(&c, 0, sizeof(c));
   c.c.status = ST_RUNNING; c.c.first = 1; c.c.t = b.s0; c.c.qold = QOLDINIT; c.c.q11 = 1.0f;
+  c.k1t = -b.s0;
   b.cc[0] = c; b.cc[1] = c;
 }

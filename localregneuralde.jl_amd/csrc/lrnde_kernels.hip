@@ -1626,6 +1626,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 #include "lrnde_chain.hpp"
 #include "lrnde_wide_chain.hpp"
 #include "lrnde_chain_adjoint.hpp"
+#include "lrnde_wide_adjoint.hpp"
 
 // single-step modes: EEst and the two regularisation values from the partial sums
 __global__ void k_finalize(StepArgs a, int j) {
@@ -1860,7 +1861,11 @@ struct lrnde_ctx {
   DevBuf<double> cha_dpart;
   DevBuf<float> cha_stops;
   DevBuf<ChAdjImp> cha_imp;
-  // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device), the kernels it
+  // the wide handle's device-controlled adjoint loop (lrnde_wide_adjoint.hpp) shares the control blocks, norm partials and
+  // tables above; its eight stage-record slots are its own
+  DevBuf<float> wa_rec;
+  int adj_loop = LRNDE_ADJ_LOOP_AUTO;      // lrnde_set_adjoint_loop
+  // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device, 3 wide-chain device), the kernels it
   // enqueued and the waits the host made with nothing enqueued behind them
   int adj_kind = 0, adj_launches = 0, adj_waits = 0;
   int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp)
@@ -2183,6 +2188,7 @@ int set_smem_attr() {
   hipFuncSetAttribute((const void*)k_init2_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_rhs_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_vjp_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_wadj_step, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   done = true;
   return 0;
 }
@@ -4566,7 +4572,7 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
 // parameter cotangents (7 x workgroups x P floats) within CHADJ_SCRATCH_MAX.  Outside it the host loop runs.
 struct ChAdjPlan { int nwg, nmu, wg_lds; size_t lds; };
 bool chadj_fits(const lrnde_ctx* c, int B, ChAdjPlan* pl) {
-  if (c->field != 1) return false;   // (a wide chain's adjoint takes the host loop)
+  if (c->field != 1) return false;   // (a wide chain's device loop has its own gate, wadj_fits, and is opt-in)
   const size_t P = param_count(c);
   const int nwg = (B + CNB - 1) / CNB;
   const size_t lds0 = chadj_smem_bytes(c->cd.wfloats, 0, c->ch_vjp_lds);
@@ -4582,21 +4588,84 @@ bool chadj_fits(const lrnde_ctx* c, int B, ChAdjPlan* pl) {
   return true;
 }
 
+// The wide handle's gate, stated once: the step kernel's LDS (the forward kernels' carve, its segment-partial region cut
+// back by what the control block takes) within WIDE_LDS_MAX; at most CHADJ_MAX_WG workgroups; eight stage-record slots
+// for the batch plus the control blocks and the norm partials within WIDE_SCRATCH_MAX.  why (may be null): the limit missed.
+struct WAdjPlan { int nwg, nitems, nmu, partcap; size_t lds, rec_floats; };
+bool wadj_fits(const lrnde_ctx* c, int B, WAdjPlan* pl, std::string* why) {
+  char msg[200];
+  auto no = [&](void) { if (why) *why = msg; return false; };
+  if (c->field != 2) { snprintf(msg, sizeof msg, "not a wide-chain handle"); return no(); }
+  const WideDev& wd = c->wd;
+  const int nwg = (B + NB - 1) / NB;
+  const size_t fixed = wadj_smem_bytes(wd.bufw, 0);
+  const int partcap = fixed > WIDE_LDS_MAX ? 0 : (int)std::min<size_t>((size_t)wd.partcap, ((WIDE_LDS_MAX - fixed) / sizeof(float)) & ~(size_t)255);
+  const size_t lds = wadj_smem_bytes(wd.bufw, partcap);
+  if (lds > WIDE_LDS_MAX) { snprintf(msg, sizeof msg, "the step kernel needs %zu bytes of LDS, WIDE_LDS_MAX is %zu", lds, WIDE_LDS_MAX); return no(); }
+  if (nwg > CHADJ_MAX_WG) { snprintf(msg, sizeof msg, "B = %d is %d workgroups, CHADJ_MAX_WG is %d", B, nwg, CHADJ_MAX_WG); return no(); }
+  int nitems = 0;
+  for (int l = 0; l < c->chain.nlayers; ++l) {
+    const int MT = ceil16(c->chain.dims[l + 1]) / 16, KG = ceil16(c->chain.dims[l]) / 16;
+    nitems += ((MT + WADJ_MB - 1) / WADJ_MB) * ((KG + WADJ_MB - 1) / WADJ_MB) + (c->chain.dims[l + 1] + 63) / 64;
+  }
+  const int nmu = std::min(nitems, CHADJ_MAX_MU_BLOCKS);
+  const size_t rec_floats = (size_t)WADJ_SLOTS * nwg * wd.recfloats;
+  const size_t bytes = rec_floats * sizeof(float) + 2 * sizeof(ChAdjCtrl) + 5 * (size_t)(nwg + nmu) * sizeof(double);
+  if (bytes > WIDE_SCRATCH_MAX) {
+    snprintf(msg, sizeof msg, "B = %d needs %zu bytes of stage records (%d slots), WIDE_SCRATCH_MAX is %zu", B, bytes, WADJ_SLOTS, WIDE_SCRATCH_MAX);
+    return no();
+  }
+  if (pl) { pl->nwg = nwg; pl->nitems = nitems; pl->nmu = nmu; pl->partcap = partcap; pl->lds = lds; pl->rec_floats = rec_floats; }
+  return true;
+}
+
+// What chadj_solve_device needs of a handle kind: the grid of its two launches (their norm partials), its scratch, and the
+// launch pair of one attempt or init phase (a: the shared arguments filled in; mode: CHADJ_STEP / CHADJ_INIT_A / _B)
+struct ChAdjDriver {
+  const char* what;
+  int nwg, nmu;
+  std::function<int()> scratch;
+  std::function<void(ChAdjArgs a, int jj, int mode)> launch_pair;
+};
+ChAdjDriver chadj_driver(lrnde_ctx* c, const ChAdjPlan& pl) {
+  ChAdjDriver d;
+  d.what = "chain adjoint loop"; d.nwg = pl.nwg; d.nmu = pl.nmu;
+  d.scratch = [c, pl]() -> int { HIPCHK(c, c->cha_gpart.grow(7 * (size_t)pl.nwg * param_count(c))); return LRNDE_OK; };
+  d.launch_pair = [c, pl](ChAdjArgs a, int jj, int mode) {
+    a.gpart = c->cha_gpart; a.wg_lds = pl.wg_lds; a.gfloats = c->ch_gfloats;
+    hipLaunchKernelGGL(k_chadj_step, dim3(pl.nwg), dim3(NT), pl.lds, c->stream, a, c->cd, jj, mode);
+    hipLaunchKernelGGL(k_chadj_mu, dim3(pl.nmu), dim3(CHADJ_MU_NT), 0, c->stream, a, jj, mode);
+  };
+  return d;
+}
+ChAdjDriver wadj_driver(lrnde_ctx* c, const WAdjPlan& pl) {
+  ChAdjDriver d;
+  d.what = "wide adjoint loop"; d.nwg = pl.nwg; d.nmu = pl.nmu;
+  d.scratch = [c, pl]() -> int { HIPCHK(c, c->wa_rec.grow(pl.rec_floats)); return LRNDE_OK; };
+  d.launch_pair = [c, pl](ChAdjArgs a, int jj, int mode) {
+    WAdjArgs w{};
+    w.a = a; w.rec = c->wa_rec;
+    WideDev wd = c->wd;
+    wd.partcap = pl.partcap;
+    hipLaunchKernelGGL(k_wadj_step, dim3(pl.nwg), dim3(NT), pl.lds, c->stream, w, wd, jj, mode);
+    hipLaunchKernelGGL(k_wadj_mu, dim3(pl.nmu), dim3(WADJ_MU_NT), 0, c->stream, w, wd, pl.nitems, jj, mode);
+  };
+  return d;
+}
+
 // Launches: 1 (k_chadj_begin; one more per 64 further tstops / impulses) + 4 (initdt: two evaluations, each a step-family
 // and a mu-family launch) + 2 per attempted step + 2 (the launch pair whose prologue reports the end) here; the caller
 // adds k_adj_out and at most two k_axpy for cotangents at the two end points of the solve.
-int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float abstol, float reltol, int maxiters, int exact_pow,
-                       const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st,
+int chadj_solve_device(lrnde_ctx* c, const ChAdjDriver& drv, AdjVec& v, int B, float s0, float s1, float abstol, float reltol, int maxiters,
+                       int exact_pow, const std::vector<float>& tstops, const std::vector<AdjImpulse>& impulses, int nrec, lrnde_stats* st,
                        std::function<int()>& after_first_attempt) {
   int rc;
   memset(st, 0, sizeof(*st));
-  ChAdjPlan pl{};
-  if (!chadj_fits(c, B, &pl)) return fail(c, LRNDE_UNSUPPORTED, "chain adjoint loop: shape outside the gate");
   const size_t P = v.P, N = v.N, n = v.n_lam;
-  const int np = pl.nwg + pl.nmu;
+  const int np = drv.nwg + drv.nmu;
   HIPCHK(c, c->cha_ctl.once(2));
   if ((rc = adj_report_block(c))) return rc;
-  HIPCHK(c, c->cha_gpart.grow(7 * (size_t)pl.nwg * P));
+  if ((rc = drv.scratch())) return rc;
   HIPCHK(c, c->cha_dpart.grow(5 * (size_t)np));
   // impulses strictly inside (s0, s1) go to the device table; those at the end time are added after the solve (a cotangent
   // at the start time is the caller's lambda(s0))
@@ -4638,11 +4707,10 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
   g.nranks = 1;
   g.hstat = c->adj_hstat.dev(); g.seq0 = c->adj_seq;
   a.cc = c->cha_ctl; a.imp = c->cha_imp; a.nimp = (int)tab.size();
-  a.gpart = c->cha_gpart; a.dpart = c->cha_dpart;
-  a.B = B; a.nwg = pl.nwg; a.nmu = pl.nmu; a.np = np; a.wg_lds = pl.wg_lds; a.gfloats = c->ch_gfloats;
+  a.dpart = c->cha_dpart;
+  a.B = B; a.nwg = drv.nwg; a.nmu = drv.nmu; a.np = np;
   auto enqueue = [&](int jj, int mode) -> int {
-    hipLaunchKernelGGL(k_chadj_step, dim3(pl.nwg), dim3(NT), pl.lds, c->stream, a, c->cd, jj, mode);
-    hipLaunchKernelGGL(k_chadj_mu, dim3(pl.nmu), dim3(CHADJ_MU_NT), 0, c->stream, a, jj, mode);
+    drv.launch_pair(a, jj, mode);
     HIPCHK(c, hipGetLastError());
     c->adj_launches += 2;
     return LRNDE_OK;
@@ -4665,7 +4733,7 @@ int chadj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float
     if ((rc = enqueue(j, CHADJ_STEP))) return bail(rc);
     if ((rc = adj_after_first_attempt(after_first_attempt))) return bail(rc);
     ++j;
-    if ((rc = adj_await_report(c, "chain adjoint loop", g.seq0, j, bail, trace, &fin))) return rc;
+    if ((rc = adj_await_report(c, drv.what, g.seq0, j, bail, trace, &fin))) return rc;
     if (fin.status != ST_RUNNING) done = true;
     if (j > maxiters + 16) break;
   }
@@ -4859,13 +4927,20 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   const int nsteps = R.naccept;
   // adjoint solve on z = [lambda; mu] in s = -t from -t2 to -t0, tstops at the saved times
   const size_t N = n + P;
+  WAdjPlan wpl{};
+  if (c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DEVICE && !sharded(c) && !opt(OPT_ADJ_HOST)) {
+    std::string why;   // (refused before anything is touched: the handle and its record stay usable)
+    if (!wadj_fits(c, B, &wpl, &why)) return fail(c, LRNDE_UNSUPPORTED, "wide adjoint loop: %s", why.c_str());
+  }
   AdjVec v;
   if ((rc = adj_alloc(c, N, v))) return rc;
   v.n_lam = n; v.P = P;
   const bool adj_host = opt(OPT_ADJ_HOST) != 0;  // diagnostic: the round-1 host-controlled loop
-  const bool chain_loop = c->field && chadj_fits(c, B, nullptr) && !sharded(c) && !adj_host;
+  ChAdjPlan cpl{};
+  const bool chain_loop = c->field && chadj_fits(c, B, &cpl) && !sharded(c) && !adj_host;
+  const bool wide_loop = c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DEVICE && !sharded(c) && !adj_host;   // opt-in (lrnde_set_adjoint_loop)
   const bool dev_loop = vjp_uses_qtile(c, B) && !sharded(c) && !adj_host;
-  c->adj_kind = chain_loop ? 2 : (dev_loop ? 1 : 0); c->adj_launches = 0; c->adj_waits = 0;
+  c->adj_kind = wide_loop ? 3 : (chain_loop ? 2 : (dev_loop ? 1 : 0)); c->adj_launches = 0; c->adj_waits = 0;
   const bool begin_in_solve = dev_loop && !du_series;  // the device loop's first launch sets z = [du_end; 0] itself
   if (!begin_in_solve) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
   std::vector<AdjImpulse> impulses;  // ascending in s = -t
@@ -4904,8 +4979,8 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     if (vjp_uses_qtile(c, B) && !sharded(c) && !adj_host) after_first_attempt = pending_sweep;
     else if ((rc = pending_sweep())) return rc;
   }
-  if (chain_loop) {
-    rc = chadj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
+  if (chain_loop || wide_loop) {
+    rc = chadj_solve_device(c, wide_loop ? wadj_driver(c, wpl) : chadj_driver(c, cpl), v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
                             after_first_attempt);
   } else if (dev_loop) {
     rc = adj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
@@ -5143,6 +5218,13 @@ int lrnde_sde_last_solve_info(lrnde_sde* s, int32_t* kind_host, int32_t* launche
   *kind_host = s->info_kind; *launches_host = s->info_launches; *host_waits_host = s->info_waits;
   return LRNDE_OK;
 }
+int lrnde_set_adjoint_loop(lrnde_ctx* c, int32_t loop) {
+  if (!c) return LRNDE_BADARG;
+  if (loop != LRNDE_ADJ_LOOP_AUTO && loop != LRNDE_ADJ_LOOP_DEVICE) return fail(c, LRNDE_BADARG, "adjoint loop %d (0 auto, 1 device)", loop);
+  c->adj_loop = loop;
+  return LRNDE_OK;
+}
+
 int lrnde_last_adjoint_info(lrnde_ctx* c, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host) {
   if (!c || !kind_host || !launches_host || !host_waits_host) return LRNDE_BADARG;
   *kind_host = c->adj_kind; *launches_host = c->adj_launches; *host_waits_host = c->adj_waits;

@@ -375,10 +375,21 @@ class Handle:
         return [(r[i].t, r[i].dt, r[i].eest, r[i].accepted) for i in range(int(n.value))]
 
     ADJOINT_LOOPS = ("host", "device", "chain_device")
+    # every kind lrnde_last_adjoint_info reports: the three above and the wide-chain handle's opt-in device loop
+    ADJOINT_LOOP_NAMES = ADJOINT_LOOPS + ("wide_device",)
+    ADJOINT_LOOP_CHOICES = {"auto": 0, "device": 1}
+
+    def set_adjoint_loop(self, loop):
+        """lrnde_set_adjoint_loop: "auto" (every handle's own routing; a wide-chain handle takes the host loop) or
+        "device" (a wide-chain handle takes its device-controlled loop; no change for the other handles)"""
+        if loop not in self.ADJOINT_LOOP_CHOICES:
+            raise ValueError(f"adjoint_loop must be 'auto' or 'device' (got {loop!r})")
+        self._chk(L.lib.lrnde_set_adjoint_loop(self._ctx, self.ADJOINT_LOOP_CHOICES[loop]))
 
     def last_adjoint_info(self):
         """how the last reversed solve ran (lrnde_last_adjoint_info): kind 0 host loop / 1 the MLP device loop / 2 the
-        chain device loop, the kernels it enqueued, and the host waits during which the GPU idled"""
+        chain device loop / 3 the wide-chain device loop, the kernels it enqueued, and the host waits during which the GPU
+        idled"""
         k, n, w = C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(L.lib.lrnde_last_adjoint_info(self._ctx, C.byref(k), C.byref(n), C.byref(w)))
         return dict(kind=int(k.value), launches=int(n.value), host_waits=int(w.value))
@@ -550,7 +561,7 @@ class NeuralODE:
     """src/layers/neural_ode.jl:1-116.  `(sol, st) = node(x, ps, st)`."""
 
     def __init__(self, model, *, solver="Tsit5", sensealg=None, tspan=(0.0, 1.0), regularize=True,
-                 maxiters=1000, regularize_type="error_estimate", field="auto", **kwargs):
+                 maxiters=1000, regularize_type="error_estimate", field="auto", adjoint_loop="auto", **kwargs):
         if isinstance(regularize, bool):  # :14-16
             regularize = "unbiased" if regularize else "none"
         regularize, regularize_type = _sym(regularize), _sym(regularize_type)
@@ -568,6 +579,11 @@ class NeuralODE:
         if field not in ("auto", "dense_chain", "wide_chain"):
             raise ValueError(f"field must be 'auto', 'dense_chain' or 'wide_chain' (got {field!r})")
         self.field = field
+        # adjoint_loop: "auto" keeps every handle's own routing of the reversed solve; "device" opts a wide-chain handle into
+        # its device-controlled loop (Handle.set_adjoint_loop) and changes nothing for the other fields
+        if adjoint_loop not in Handle.ADJOINT_LOOP_CHOICES:
+            raise ValueError(f"adjoint_loop must be 'auto' or 'device' (got {adjoint_loop!r})")
+        self.adjoint_loop = adjoint_loop
         if field in ("dense_chain", "wide_chain"):
             self._conv = None
             self.desc = _chain_desc(model) if field == "dense_chain" else _wide_chain_desc(model)
@@ -606,6 +622,7 @@ class NeuralODE:
         if self._handle is None:
             self._handle = Handle(self.desc)
             self._handle.set_solver(self.solver)
+            self._handle.set_adjoint_loop(self.adjoint_loop)
         return self._handle
 
     def _bind(self, ps, x=None, changed=True):
@@ -689,8 +706,9 @@ class NeuralODE:
         src/utils.jl:42-46, experiments/src/construct.jl:244-249).  One forward with the dense record, then the backward
         from it; t1 comes from the same single draw of st['rng'] as in `__call__` (biased_index), so info['reg_val'] /
         info['t1'] are `__call__`'s.  info['adjoint_loop'] names the loop that ran the reversed solve: "host" (the
-        host-controlled loop), "device" (the MLP handle's device-controlled loop) or "chain_device" (the Dense-chain
-        handle's); the conv field's own backward reports None."""
+        host-controlled loop), "device" (the MLP handle's device-controlled loop), "chain_device" (the Dense-chain
+        handle's) or "wide_device" (the wide Dense-chain handle's, which runs only for a layer built with
+        adjoint_loop="device"); the conv field's own backward reports None."""
         h = self._bind(ps, x)
         t0, t2 = self.tspan
         kw = self.kwargs
@@ -719,5 +737,5 @@ class NeuralODE:
             bw = h.node_backward_recorded(du, w_reg=w_reg) if not self._conv else h.node_backward_recorded(x.shape[0], du, w_reg=w_reg)
         info = dict(bw, reg_val=fw["reg_val"], t1=fw["t1"], nfe=fw["nfe"], u_end=fw["u_end"], stats_fwd=fw["stats"],
                     sol_t=fw.get("t"), sol_u=fw.get("u"),
-                    adjoint_loop=None if self._conv else Handle.ADJOINT_LOOPS[h.last_adjoint_info()["kind"]])
+                    adjoint_loop=None if self._conv else Handle.ADJOINT_LOOP_NAMES[h.last_adjoint_info()["kind"]])
         return bw["dx"], bw["dp"], info

@@ -7,11 +7,16 @@ Prints one JSON line (and writes it to --out) with, each the median of --reps ru
   (c) mnist3  TDChain [784,100,100,784] through the wide handle: step, layer forward, forward + pullback;
   (d) mnist3's adaptive Tsit5 solve written in eager torch fp32 on the same GPU (host-side controller, one EEst read-back
       per attempted step).
+  (e) --only adjoint: case (c)'s forward + pullback with the host-controlled adjoint loop (adjoint_loop="auto") and with the
+      device-controlled one (adjoint_loop="device") in the same process: attempts of the reversed solve,
+      launches per attempt, host waits, and us per attempt = (forward + pullback - layer forward) / attempts.
 "us per attempted step" is the solve's kernel time (the library's event bracket around its launches,
 lrnde_last_solve_kernel_ms) over accepted + rejected steps.
 
     python tools/bench/wide_chain_bench.py [--reps 30] [--B 512] [--out profiles/wide_chain/wide_chain_bench.json]
     rocprofv3 --kernel-trace --stats -- python tools/bench/wide_chain_bench.py --only mnist3 --reps 5 --no-eager
+    python tools/bench/wide_chain_bench.py --only adjoint --out profiles/wide_chain/wide_adjoint_bench.json
+    rocprofv3 --kernel-trace --stats -- python tools/bench/wide_chain_bench.py --only adjoint --reps 5
 """
 import argparse
 import json
@@ -80,6 +85,31 @@ def leg(model, field, xd, ps, reps, pullback):
     return out
 
 
+def adjoint_legs(model, xd, ps, reps):
+    """case (c)'s forward + pullback under both adjoint loops of the wide handle, host loop first"""
+    cot = torch.from_numpy(np.random.default_rng(1).standard_normal(tuple(xd.shape)).astype(np.float32)).cuda()
+    out = {}
+    for loop in ("auto", "device"):
+        node = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, save_start=False, maxiters=100000,
+                           field="wide_chain", adjoint_loop=loop)
+        st = node.initialstates(np.random.default_rng(0))
+        fwd = timed(lambda: node(xd, ps, st), reps)
+        both = timed(lambda: node.pullback(xd, ps, st, cot, w_reg=10.0), reps)
+        _, _, info = node.pullback(xd, ps, st, cot, w_reg=10.0)
+        ai, sb = node.handle().last_adjoint_info(), info["stats_bwd"]
+        attempts = sb["naccept"] + sb["nreject"]
+        out["host_loop" if loop == "auto" else "device_loop"] = dict(
+            adjoint_loop=info["adjoint_loop"], layer_forward_ms=fwd, layer_forward_pullback_ms=both, attempts=attempts,
+            naccept=sb["naccept"], nreject=sb["nreject"], launches=ai["launches"],
+            launches_per_attempt=round(ai["launches"] / max(attempts, 1), 2), host_waits=ai["host_waits"],
+            us_per_attempt=round(1e3 * (both["median"] - fwd["median"]) / max(attempts, 1), 2))
+        node._handle.close()
+    h, d = out["host_loop"]["layer_forward_pullback_ms"], out["device_loop"]["layer_forward_pullback_ms"]
+    out["device_over_host_pullback"] = round(d["median"] / h["median"], 3)
+    out["device_below_host_by_more_than_the_spread"] = bool(d["max"] < h["min"])
+    return out
+
+
 def eager_solve(Ws, acts, x, t0, t1, tol, maxiters=100000):
     """adaptive Tsit5 (initdt, PI controller with the same constants) over the TDChain in eager torch fp32: the baseline"""
     fa = {"tanh": torch.tanh, "identity": lambda z: z}
@@ -128,7 +158,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--B", type=int, default=512)
-    ap.add_argument("--only", choices=["all", "mnist2", "mnist3"], default="all")
+    ap.add_argument("--only", choices=["all", "mnist2", "mnist3", "adjoint"], default="all")
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -167,6 +197,11 @@ def main():
                 info["u"], info["na"], info["nr"] = eager_solve(Ws, acts, xd, 0.0, 1.0, TOL)
             res["d_mnist3_eager_torch_fp32_solve_ms"] = timed(run, args.reps)
             res["d_eager_naccept"], res["d_eager_nreject"] = info["na"], info["nr"]
+    if args.only == "adjoint":
+        m3 = td_chain([784, 100, 100, 784], ["tanh", "tanh", "identity"])
+        ps3 = torch.from_numpy(P.glorot_chain_params(m3, seed=0)).cuda()
+        res["workload"] = "wide_dense_chain_adjoint"
+        res["c_mnist3_wide_adjoint"] = adjoint_legs(m3, xd, ps3, args.reps)
     line = json.dumps(res)
     print(line)
     if args.out:
