@@ -5,7 +5,9 @@ adjoint's parameter-cotangent and norm sums all run; only the transport differs 
 instead of ncclAllReduce, which RCCL refuses for two ranks on one device).
 
 Bars: forward — dt trace, accept/reject decisions, nfe, reg_val and every element of sol.u[end] EQUAL to the unsharded
-run of the same library and to the oracle; backward — tolerance (the sharded sums over the batch are grouped by rank).
+run of the same library and to the oracle; backward — tolerance (the sharded sums over the batch are grouped by rank);
+the bars of everything else a sharded handle runs backwards (lrnde_vjp, the regulariser's sweep, the time-series pullback,
+the Adams solvers, the fused forward + head; steps as well as gradients) are in tests/test_gpu_sharded_paths.py.
 BASELINE.json config 3 (B=4096 over 8 ranks of 512) runs here as 8 ranks on one device."""
 import os
 
