@@ -45,6 +45,7 @@
 #include "lrnde_buf.hpp"
 #include "lrnde_stepctl.hpp"
 #include "lrnde_layer_plan.hpp"
+#include "lrnde_conv_geom.hpp"
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
               "header_status returns lrnde_status values");
@@ -1730,11 +1731,7 @@ int cfail(lrnde_conv* c, int code, const char* fmt, ...) {
 inline size_t state_n(const lrnde_conv* c, int B) { return (size_t)B * c->d.width * c->d.height * c->d.channels; }
 inline int strip_rows(const lrnde_conv* c) {
   // largest TR dividing H with TR*W <= 128 pixels (8 M tiles)
-  const int maxpx = 16 * MAXMT;
-  int best = 0;
-  for (int tr = 1; tr <= c->d.height; ++tr)
-    if (c->d.height % tr == 0 && tr * c->d.width <= maxpx) best = tr;
-  return best ? best : 1;
+  return conv_strip_rows(c->d.width, c->d.height, 16 * MAXMT);
 }
 inline int cinp_of(int cin) { return cin == 8 ? 12 : cin; }  // 64-channel tiles are swizzled, not padded
 
@@ -1935,9 +1932,7 @@ int launch_vjp(lrnde_conv* c, const float* y, float t, const float* lam, int B, 
     WgradArgs w{};
     memset(&w, 0, sizeof(w));
     // strips of <= 128 pixels (64 gives two workgroups per CU and measured the same)
-    const int wpx = 128;
-    int trw = 1;
-    for (int tr = 1; tr <= H; ++tr) if (H % tr == 0 && tr * W <= wpx) trw = tr;
+    const int trw = conv_strip_rows(W, H, 16 * MAXMT);
     const int nstrips_w = B * (H / trw);
     const int GS = GM ? 80 : 16, IS = IM ? 80 : 16, GC = GM ? 64 : 16, IC = IM ? 64 : 16;
     size_t sm = sizeof(float) * ((size_t)trw * W * GS + (size_t)(trw + 2) * WP * IS);
