@@ -77,6 +77,16 @@ int lrnde_last_adjoint_info(lrnde_ctx* ctx, int32_t* kind_host, int32_t* launche
  * included — plus waits for a report that found the queue drained, i.e. with nothing enqueued behind them; polling the
  * pinned progress word while launches are still queued is not a wait.  A device-controlled solve reports 1. */
 int lrnde_sde_last_solve_info(lrnde_sde* s, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host);
+/* Diagnostic: how the last lrnde_sde_node_backward_recorded of the handle ran (the model's pullback calls it), for all three
+ * step kinds.  kind: 0 launch sequences per recorded step (a time input, sharded handles, shapes outside the one-launch
+ * sweep's gate — D <= 64, H <= 128, the weights and the workgroup's parameter cotangent within 160 KB of LDS, at most 512
+ * series entries — LRNDE_NO_SDE_BWD_FUSED=1, or an SRI record that route has already swept since its forward when a
+ * regulariser is asked for: it used the record's scratch), 1 the one-launch sweep (Euler-Heun: lrnde_sde_bwd_fused.hpp; Milstein and
+ * SRI: lrnde_sde_bwd_alg_fused.hpp).  launches: kernels the call enqueued — the sweep, the regulariser's kernel when there is
+ * one, and what sums their partials; it does not depend on the number of recorded steps.  host_waits: stream
+ * synchronisations inside the call — 1, or 0 when lrnde_sde_model_backward_recorded leaves the wait to its own end.  On
+ * the per-step route launches and host_waits are not counted and read -1. */
+int lrnde_sde_last_backward_info(lrnde_sde* s, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host);
 /* Diagnostic: mean host-side microseconds per lrnde_node_forward call since the last reset, by phase: [0] entry -> the main
  * solve's init launches enqueued, [1] -> its last report read (the feed loop: the GPU is busy throughout), [2] -> the final
  * synchronisation returned, [3] -> the call returned (local-step results, bookkeeping).  tools/bench/host_phases.py */

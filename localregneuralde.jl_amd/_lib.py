@@ -199,6 +199,7 @@ SYMBOLS = [
     ("lrnde_set_adjoint_trace", C.c_int, [_vp, C.POINTER(TraceRow), _i32]),
     ("lrnde_last_adjoint_info", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("lrnde_sde_last_solve_info", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("lrnde_sde_last_backward_info", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("lrnde_adjoint_trace_rows", C.c_int, [_vp, C.POINTER(_i32)]),
     ("lrnde_host_phases", C.c_int, [_vp, C.POINTER(C.c_double), _i32]),
     ("lrnde_last_solve_kernel_ms", C.c_int, [_vp, _fp, C.POINTER(_i32)]),

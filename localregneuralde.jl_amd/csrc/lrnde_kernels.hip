@@ -3237,6 +3237,9 @@ struct lrnde_sde {
   // synchronisations, and waits for a report that found the queue drained (nothing enqueued behind them).  The entry points
   // reset it; a layer call's automatic initial dt of the main solve counts, its local step does not
   int info_kind = 0, info_launches = 0, info_waits = 0;
+  // lrnde_sde_last_backward_info: how the last lrnde_sde_node_backward_recorded ran (0 launch sequences per recorded step, 1 the
+  // one-launch sweep), the kernels it enqueued and its stream synchronisations (both -1 on the per-step route: not counted)
+  int bwd_kind = 0, bwd_launches = 0, bwd_waits = 0;
 };
 
 int lrnde_sde_create(lrnde_sde** out, const lrnde_model_desc* drift, int32_t diffusion_bias, int device, void* stream) {
@@ -4029,6 +4032,7 @@ int lrnde_vjp(lrnde_ctx* c, const float* y, float t, const float* lam, int32_t B
 }  // extern "C"
 #include "lrnde_sde_bwd.hpp"
 #include "lrnde_sde_bwd_fused.hpp"
+#include "lrnde_sde_bwd_alg_fused.hpp"
 #include "lrnde_sde_node.hpp"
 #include "lrnde_noise.hpp"
 extern "C" {
@@ -5216,6 +5220,11 @@ int lrnde_set_adjoint_trace(lrnde_ctx* c, lrnde_trace_row* rows_host, int32_t ca
 int lrnde_sde_last_solve_info(lrnde_sde* s, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host) {
   if (!s || !kind_host || !launches_host || !host_waits_host) return LRNDE_BADARG;
   *kind_host = s->info_kind; *launches_host = s->info_launches; *host_waits_host = s->info_waits;
+  return LRNDE_OK;
+}
+int lrnde_sde_last_backward_info(lrnde_sde* s, int32_t* kind_host, int32_t* launches_host, int32_t* host_waits_host) {
+  if (!s || !kind_host || !launches_host || !host_waits_host) return LRNDE_BADARG;
+  *kind_host = s->bwd_kind; *launches_host = s->bwd_launches; *host_waits_host = s->bwd_waits;
   return LRNDE_OK;
 }
 int lrnde_set_adjoint_loop(lrnde_ctx* c, int32_t loop) {

@@ -67,13 +67,15 @@ __host__ __device__ inline SbfOff sbf_off(int D, int H, bool own_xg) {
   return o;
 }
 __host__ __device__ inline int sbf_up4(int n) { return (n + 3) & ~3; }
-// nev evaluation points per sample: 2 in the sweep, 3 (with their own x_g) in the regulariser's kernel
-inline size_t sbf_smem_bytes(int D, int H, int nev) {
-  const SbfOff o = sbf_off(D, H, nev == 3);
+// nev evaluation points per sample: 2 in the sweep, 3 (with their own x_g) in the regulariser's kernel; the Milstein / SRI
+// kernels (lrnde_sde_bwd_alg_fused.hpp) say themselves whether the diffusion's input has its own vector
+inline size_t sbf_smem_bytes_xg(int D, int H, int nev, bool own_xg) {
+  const SbfOff o = sbf_off(D, H, own_xg);
   return sizeof(float) * ((size_t)sbf_up4((H + 1) * o.Dq + 4) + sbf_up4((D + 1) * o.Hq + 4) + sbf_up4((D + 1) * o.Dq + 4) + o.Hq + 2 * o.Dq   // weights, biases
                           + (size_t)SBF_NS * nev * o.VS                                                // the evaluation points' vectors
                           + (size_t)((size_t)D * H * 2 + H + D + (size_t)D * D + D));                  // the workgroup's parameter cotangent
 }
+inline size_t sbf_smem_bytes(int D, int H, int nev) { return sbf_smem_bytes_xg(D, H, nev, nev == 3); }
 
 // what both kernels share: the LDS image of the weights, this wave's sample, the products
 struct SbfDev {
@@ -85,9 +87,10 @@ struct SbfDev {
   int lh0, lh1, ld_;
   size_t nst, g;
 
-  __device__ __forceinline__ void setup(const SdeBwdFusedArgs& a, float* sm, int nev_) {
+  __device__ __forceinline__ void setup(const SdeBwdFusedArgs& a, float* sm, int nev_) { setup(a, sm, nev_, nev_ == 3); }
+  __device__ __forceinline__ void setup(const SdeBwdFusedArgs& a, float* sm, int nev_, bool own_xg) {
     D = a.D; H = a.H; act = a.act; Pf = a.Pf; Ptot = a.Ptot; nev = nev_;
-    o = sbf_off(D, H, nev == 3);
+    o = sbf_off(D, H, own_xg);
     Dq = o.Dq; Hq = o.Hq; ld1 = H + 1; ld2 = D + 1;   // leading dimensions of W1 (H x D) and of W2 (D x H) / Wg (D x D)
     W1s = sm;                                  // W1[h + ld1 * d], d < Dq (zero columns beyond D)
     W2s = W1s + sbf_up4(ld1 * Dq + 4);         // W2[d + ld2 * h], h < Hq

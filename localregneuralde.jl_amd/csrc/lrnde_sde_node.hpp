@@ -33,6 +33,7 @@ struct SdeNodeRecord {
   // the step kind the record was made with (0 Euler-Heun, 1 Milstein, 2 SRI): the backward sweeps it with that kind's
   // reverse kernels.  SRI: its tableau, the second path (the caller's, alive until the backward) and the local step's dZ
   int which = 0; lrnde_sri_tableau tab{}; const float* Z = nullptr; DevBuf<float> dZloc;
+  bool un_scratch = false;   // the per-step SRI sweep has used tmp as scratch since the forward: the local step's u' is gone
 };
 
 // out = (1 - theta) * a + theta * b   (StochasticDiffEq's linear sde_interpolant)
@@ -394,7 +395,7 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   if (nfe_diffusion_host) *nfe_diffusion_host = nfe_g;
   if (t1_used_host) *t1_used_host = t1;
   r.valid = true; ++r.gen; r.B = B; r.nfine = nfine; r.K = K; r.mode = mode; r.t0 = t0; r.t2 = t2; r.h = h; r.o = *o; r.W = W;
-  r.which = which; r.Z = Z;
+  r.which = which; r.Z = Z; r.un_scratch = false;
   if (which == 2) r.tab = *tab;
   return LRNDE_OK;
 }
@@ -456,6 +457,7 @@ int sde_sweep_fused_core(lrnde_sde* s, const SdeSweepSrc& r, int B, const float*
     const size_t smr = SbfR<32, 64>::smem_bytes(2, 1, 1);   // (no cotangent vector in this kernel)
     if (opt(OPT_SDE_BWD_NO_RESIDENT)) hipLaunchKernelGGL((k_sde_eh_bwd_fused_r<32, 64, true>), dim3(nwg), dim3(SBF_NT), smr, c->stream, a);
     else hipLaunchKernelGGL((k_sde_eh_bwd_sweep_res<32, 64>), dim3(nwg), dim3(SBF_NT), smr, c->stream, a);
+    s->bwd_launches += 2 + (reg ? 1 : 0);   // (the sweep, the history GEMM, the regulariser's records)
     if (reg) {   // the regulariser's step: four records per sample behind the sweep's, seeded with w_reg
       SdeBwdFusedArgs g = a;
       g.u1 = reg->u1; g.dW1 = reg->dWloc; g.un1 = reg->tmp; g.dt1 = reg->dt_loc; g.eest = reg->ee_loc;
@@ -475,15 +477,18 @@ int sde_sweep_fused_core(lrnde_sde* s, const SdeSweepSrc& r, int B, const float*
     const size_t smr = SbfR<32, 64>::smem_bytes(2, D, H);
     SDE_LDS_LIMIT(c, (k_sde_eh_bwd_fused_r<32, 64, false>), smr);
     hipLaunchKernelGGL((k_sde_eh_bwd_fused_r<32, 64>), dim3(nwg), dim3(SBF_NT), smr, c->stream, a);
+    ++s->bwd_launches;
   } else {
     const size_t sm = sbf_smem_bytes(D, H, 2);
     // (the kernel also has 4 KB of static LDS: the limit asked for is what this launch needs, not the CU's 160 KB)
     SDE_LDS_LIMIT(c, k_sde_eh_bwd_fused, sm);
     hipLaunchKernelGGL(k_sde_eh_bwd_fused, dim3(nwg), dim3(SBF_NT), sm, c->stream, a);
+    ++s->bwd_launches;
   }
   hipLaunchKernelGGL(k_sde_bwd_reduce, dim3((Ptot + 31) / 32), dim3(256), 0, c->stream, (const float*)s->bwf_part, nwg_red, Ptot, Pf, Pg, dp_drift, dp_diff, 1.0f, 0);
+  ++s->bwd_launches;
   HIPCHK(c, hipGetLastError());
-  if (sync_after && !s->defer_wait) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (sync_after && !s->defer_wait) { HIPCHK(c, hipStreamSynchronize(c->stream)); ++s->bwd_waits; }
   return LRNDE_OK;
 }
 int sde_node_sweep_fused(lrnde_sde* s, SdeNodeRecord& r, int B, const float* du_series, int nseries, float* dx, float* dp_drift,
@@ -514,8 +519,9 @@ int sde_node_reg_fused(lrnde_sde* s, SdeNodeRecord& r, int B, float w_reg, float
     hipLaunchKernelGGL(k_sde_eh_reg_fused, dim3(nwg), dim3(SBF_NT), sm, c->stream, a);
   }
   hipLaunchKernelGGL(k_sde_bwd_reduce, dim3((Ptot + 31) / 32), dim3(256), 0, c->stream, (const float*)s->bwf_part, nwg, Ptot, Pf, Pg, dp_drift, dp_diff, w_reg, 1);
+  s->bwd_launches += 2;
   HIPCHK(c, hipGetLastError());
-  if (!s->defer_wait) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!s->defer_wait) { HIPCHK(c, hipStreamSynchronize(c->stream)); ++s->bwd_waits; }
   return LRNDE_OK;
 }
 int sde_sri_step_backward_core(lrnde_sde* s, const lrnde_sri_tableau* tab, const float* uprev, const float* dW, const float* dZ, int32_t B,
@@ -525,7 +531,8 @@ int sde_sri_step_backward_core(lrnde_sde* s, const lrnde_sri_tableau* tab, const
 // accepted steps newest first, each with its own dt = m h and increments from the path(s), through the per-step reverse
 // kernels of lrnde_sde_solve_fixed_backward_rkmil / lrnde_sde_sri_step_backward (w_reg = 0, dx wanted); cotangents of
 // interpolated series values split (1 - theta, theta) onto the two step ends as in the Euler-Heun sweep.  Then the
-// regulariser's parameter gradient scaled by w_reg (no dx from it).  One launch sequence per recorded step.
+// regulariser's parameter gradient scaled by w_reg (no dx from it).  One launch sequence per recorded step: the route of
+// records outside sde_alg_bwd_fused_ok's gate (and of LRNDE_NO_SDE_BWD_FUSED=1); inside it sde_node_sweep_alg_fused runs.
 int sde_node_backward_alg(lrnde_sde* s, SdeNodeRecord& r, int B, const float* du_series, int nseries, float w_reg, float* dx,
                           float* dp_drift, float* dp_diff) {
   lrnde_ctx* c = s->drift; lrnde_ctx* cg = s->diff;
@@ -587,6 +594,72 @@ bool sde_bwd_fused_ok(const lrnde_sde* s, int nseries) {
   return !opt(OPT_NO_SDE_BWD_FUSED) && sde_uses_fast(s) && s->pdr && nseries <= SBF_MAXSER &&
          sbf_smem_bytes(D, H, 2) + 8 * SBF_MAXSER + 1024 <= 160 * 1024;   // (64 x 128 does not fit: weights 98 KB + cotangent 83 KB)
 }
+// ... and its counterpart for a Milstein (which = 1) or SRI (which = 2) record: the same handle conditions, the dynamic LDS of
+// lrnde_sde_bwd_alg_fused.hpp's kernels computed for that kind's evaluation points (Milstein 2, SRI 4 with their own x_g)
+bool sde_alg_bwd_fused_ok(const lrnde_sde* s, int which, int nseries) {
+  const lrnde_ctx* c = s->drift;
+  const int D = c->desc.state_dim, H = c->desc.hidden_dim;
+  return (which == 1 || which == 2) && !opt(OPT_NO_SDE_BWD_FUSED) && sde_uses_fast(s) && s->pdr && nseries <= SBF_MAXSER &&
+         sba_smem_bytes(D, H, which) + 8 * SBF_MAXSER + 1024 <= 160 * 1024;
+}
+// The reverse sweep of a Milstein / SRI record as one launch + the fixed-order sum of the workgroups' partials, then — with a
+// regulariser — its local step as one more launch whose partials are scaled by w_reg and added.  One synchronisation at the
+// end (none under defer_wait: lrnde_sde_model_backward_recorded waits once for everything).
+int sde_node_sweep_alg_fused(lrnde_sde* s, SdeNodeRecord& r, int B, const float* du_series, int nseries, float w_reg, float* dx,
+                             float* dp_drift, float* dp_diff) {
+  lrnde_ctx* c = s->drift;
+  const int D = c->desc.state_dim, H = c->desc.hidden_dim;
+  const int Pf = (int)lrnde_param_count(&c->desc), Pg = D * D + (s->diff_bias ? D : 0), Ptot = Pf + D * D + D;
+  const int nwg = (B + SBF_NS - 1) / SBF_NS;
+  HIPCHK(c, s->bwf_part.grow((size_t)nwg * Ptot));
+  const size_t meta = (size_t)2 * SBF_MAXSER + 2 * (size_t)(r.K > 0 ? r.K : 1);
+  HIPCHK(c, s->bwf_meta.grow(meta));
+  HIPCHK(c, s->bwf_meta_pin.grow(meta));
+  // [series k][series theta][(i, m) of the K steps] through pinned memory, as sde_sweep_fused_core stages them
+  int* hm = s->bwf_meta_pin;
+  for (int j = 0; j < nseries; ++j) { hm[j] = r.series[j].k; hm[SBF_MAXSER + j] = __builtin_bit_cast(int, r.series[j].theta); }
+  for (int k = 0; k < r.K; ++k) { hm[2 * SBF_MAXSER + 2 * k] = r.im[k].x; hm[2 * SBF_MAXSER + 2 * k + 1] = r.im[k].y; }
+  HIPCHK(c, hipMemcpyAsync(s->bwf_meta, hm, sizeof(int) * ((size_t)2 * SBF_MAXSER + 2 * (size_t)r.K), hipMemcpyHostToDevice, c->stream));
+  SdeAlgBwdArgs q{};
+  SdeBwdFusedArgs& a = q.a;
+  a.pdr = s->pdr; a.Wg = s->p2 + (size_t)D * D + D; a.bg = a.Wg + (size_t)D * D;
+  a.D = D; a.H = H; a.act = c->m.act; a.B = B; a.K = r.K;
+  a.x = r.x; a.rec_u = r.rec_u; a.im = reinterpret_cast<const int2*>(s->bwf_meta + 2 * SBF_MAXSER); a.W = r.W; a.h = r.h;
+  a.du_series = du_series; a.nseries = nseries; a.ser_k = s->bwf_meta; a.ser_theta = reinterpret_cast<const float*>(s->bwf_meta + SBF_MAXSER);
+  a.dx = dx; a.part = s->bwf_part; a.Pf = Pf; a.Ptot = Ptot;
+  // (r.tmp: the local step's u' as the forward left it; a record whose tmp the per-step SRI route has used since does not
+  //  come here with a regulariser: lrnde_sde_node_backward_recorded)
+  a.u1 = r.u1; a.dW1 = r.dWloc; a.un1 = r.tmp; a.dt1 = r.dt_loc; a.eest = r.ee_loc;
+  a.abstol = r.o.abstol; a.reltol = r.o.reltol; a.delta = r.o.delta;
+  q.Z = r.Z; q.dZ1 = r.dZloc;
+  if (r.which == 2) q.T = r.tab;
+  const size_t sm = sba_smem_bytes(D, H, r.which);   // (the sweep also has 4 KB of static LDS for the series table)
+  const bool reg = r.mode != LRNDE_MODE_NONE && w_reg != 0.0f;
+  const dim3 gred((Ptot + 31) / 32);
+  if (r.which == 1) {
+    SDE_LDS_LIMIT(c, k_sde_alg_bwd_fused<1>, sm);
+    hipLaunchKernelGGL(k_sde_alg_bwd_fused<1>, dim3(nwg), dim3(SBF_NT), sm, c->stream, q);
+  } else {
+    SDE_LDS_LIMIT(c, k_sde_alg_bwd_fused<2>, sm);
+    hipLaunchKernelGGL(k_sde_alg_bwd_fused<2>, dim3(nwg), dim3(SBF_NT), sm, c->stream, q);
+  }
+  hipLaunchKernelGGL(k_sde_bwd_reduce, gred, dim3(256), 0, c->stream, (const float*)s->bwf_part, nwg, Ptot, Pf, Pg, dp_drift, dp_diff, 1.0f, 0);
+  s->bwd_launches += 2;
+  if (reg) {   // (w.r.t. the parameters only: the local step's integrator is a constant of the tape, neural_sde.jl:42)
+    if (r.which == 1) {
+      SDE_LDS_LIMIT(c, k_sde_alg_reg_fused<1>, sm);
+      hipLaunchKernelGGL(k_sde_alg_reg_fused<1>, dim3(nwg), dim3(SBF_NT), sm, c->stream, q);
+    } else {
+      SDE_LDS_LIMIT(c, k_sde_alg_reg_fused<2>, sm);
+      hipLaunchKernelGGL(k_sde_alg_reg_fused<2>, dim3(nwg), dim3(SBF_NT), sm, c->stream, q);
+    }
+    hipLaunchKernelGGL(k_sde_bwd_reduce, gred, dim3(256), 0, c->stream, (const float*)s->bwf_part, nwg, Ptot, Pf, Pg, dp_drift, dp_diff, w_reg, 1);
+    s->bwd_launches += 2;
+  }
+  HIPCHK(c, hipGetLastError());
+  if (!s->defer_wait) { HIPCHK(c, hipStreamSynchronize(c->stream)); ++s->bwd_waits; }
+  return LRNDE_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -603,7 +676,18 @@ int lrnde_sde_node_backward_recorded(lrnde_sde* s, int32_t B, const float* du_se
   if (nseries != (int)r.series.size()) return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nseries, r.series.size());
   if (cg->stream != c->stream) return fail(c, LRNDE_BADARG, "drift and diffusion contexts must share a stream");
   // a record is swept by the kind that made it (the Euler-Heun sweeps below never see a Milstein or SRI record)
-  if (r.which != 0) return sde_node_backward_alg(s, r, B, du_series, nseries, w_reg, dx, dp_drift, dp_diff);
+  s->bwd_kind = 0; s->bwd_launches = 0; s->bwd_waits = 0;   // (lrnde_sde_last_backward_info)
+  if (r.which != 0) {
+    // one launch for the whole record where the gate allows it (lrnde_sde_bwd_alg_fused.hpp), else a launch sequence per step
+    const bool need_un = r.mode != LRNDE_MODE_NONE && w_reg != 0.0f;   // (the regulariser's kernel reads the recorded u')
+    if (sde_alg_bwd_fused_ok(s, r.which, nseries) && !(need_un && r.un_scratch)) {
+      s->bwd_kind = 1;
+      return sde_node_sweep_alg_fused(s, r, B, du_series, nseries, w_reg, dx, dp_drift, dp_diff);
+    }
+    s->bwd_launches = s->bwd_waits = -1;
+    if (r.which == 2) r.un_scratch = true;   // (its per-step calls recompute every step's u' into r.tmp)
+    return sde_node_backward_alg(s, r, B, du_series, nseries, w_reg, dx, dp_drift, dp_diff);
+  }
   const int D = c->desc.state_dim;
   const size_t n = (size_t)B * D, Pf = lrnde_param_count(&c->desc), Pg2 = lrnde_param_count(&cg->desc);
   const size_t Pg = (size_t)D * D + (s->diff_bias ? D : 0), goff = (size_t)D * D + D;
@@ -616,9 +700,11 @@ int lrnde_sde_node_backward_recorded(lrnde_sde* s, int32_t B, const float* du_se
   // (the regulariser's one-launch kernel follows on the stream and ends in the call's one synchronisation)
   const bool reg_fused = r.mode != LRNDE_MODE_NONE && w_reg != 0.0f && fused && sbf_smem_bytes(D, c->desc.hidden_dim, 3) + 1024 <= 160 * 1024;
   bool reg_done = false;
+  s->bwd_kind = fused ? 1 : 0;
+  if (!fused) s->bwd_launches = s->bwd_waits = -1;
   if (fused) {
     if ((rc = sde_node_sweep_fused(s, r, B, du_series, nseries, dx, dp_drift, dp_diff, !reg_fused, reg_fused, w_reg, &reg_done))) return rc;
-    if (reg_done && !s->defer_wait) HIPCHK(c, hipStreamSynchronize(c->stream));   // (the sweep left the closing wait to the regulariser's part)
+    if (reg_done && !s->defer_wait) { HIPCHK(c, hipStreamSynchronize(c->stream)); ++s->bwd_waits; }   // (the sweep left the closing wait to the regulariser's part)
   }
   else {
   HIPCHK(c, hipMemsetAsync(dx, 0, sizeof(float) * n, c->stream));   // dx doubles as ub, the cotangent of the current step's end state
@@ -661,6 +747,7 @@ int lrnde_sde_node_backward_recorded(lrnde_sde* s, int32_t B, const float* du_se
     if ((rc = sde_node_reg_fused(s, r, B, w_reg, dp_drift, dp_diff))) return rc;
   } else if (r.mode != LRNDE_MODE_NONE && w_reg != 0.0f) {
     float rv = 0.f;
+    s->bwd_launches = s->bwd_waits = -1;   // (the regulariser's launch sequence is not counted)
     if ((rc = lrnde_sde_euler_heun_reg_grad(s, r.u1, r.dWloc, B, r.t1, r.dt_loc, r.o.abstol, r.o.reltol, r.o.delta, r.gdr, r.gdf, &rv))) return rc;
     hipLaunchKernelGGL(k_sde_axpy, dim3(sde_nb(Pf)), dim3(256), 0, c->stream, Pf, dp_drift, (const float*)r.gdr, w_reg);
     hipLaunchKernelGGL(k_sde_axpy, dim3(sde_nb(Pg)), dim3(256), 0, c->stream, Pg, dp_diff, (const float*)r.gdf, w_reg);

@@ -10,7 +10,9 @@ step (:49-106); the last two are adaptive with `adaptive=True` and march the fix
 (`adaptive=False` gives Euler-Heun that grid too).  The controller runs on the device for all three steps at the one-launch
 kernels' shape (D <= 64, H <= 128, no time input, unsharded: one launch per attempted step, one stream sync per solve); outside
 that shape Milstein and SRI are host-controlled (one stream sync per attempted step).  `SdeHandle.last_solve_info()` says
-which loop ran.  SOSRI's tableau and its RSWM noise process live in un-vendored StochasticDiffEq and are not restated:
+which loop ran.  The pullback sweeps the record newest-first in ONE launch for all three steps at that shape (Milstein and SRI:
+csrc/lrnde_sde_bwd_alg_fused.hpp) and with launch sequences per recorded step outside it; `SdeHandle.last_backward_info()`
+says which.  SOSRI's tableau and its RSWM noise process live in un-vendored StochasticDiffEq and are not restated:
 `solver="SOSRI"` raises, `solver="SRI"` takes the tableau from the caller.
 """
 import copy
@@ -164,6 +166,17 @@ class SdeHandle:
         enqueued; host_waits: stream synchronisations plus waits for a report with nothing enqueued behind them"""
         k, n, w = C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(L.lib.lrnde_sde_last_solve_info(self._h, C.byref(k), C.byref(n), C.byref(w)))
+        return dict(kind=int(k.value), launches=int(n.value), host_waits=int(w.value))
+
+    BACKWARD_ROUTES = ("per-step", "one-launch sweep")
+
+    def last_backward_info(self):
+        """how the last `node_backward_recorded` (or the model's pullback around it) of this handle ran
+        (lrnde_sde_last_backward_info): kind 0 launch sequences per recorded step / 1 the one-launch sweep, for all three step
+        kinds; launches: kernels the call enqueued (kind 1; -1 for kind 0); host_waits: stream synchronisations inside the
+        call (kind 1: 1, or 0 when the model's pullback waits for it; -1 for kind 0)"""
+        k, n, w = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(L.lib.lrnde_sde_last_backward_info(self._h, C.byref(k), C.byref(n), C.byref(w)))
         return dict(kind=int(k.value), launches=int(n.value), host_waits=int(w.value))
 
     def draw_noise(self, seed, stream, nsteps, B, scale, cumulative):
@@ -636,4 +649,5 @@ class NeuralDSDE:
             du_series = torch.zeros((ns,) + tuple(x.shape), dtype=torch.float32, device=x.device)
             du_series[ns - 1] = du_end
         bw = self.handle().node_backward_recorded(du_series, w_reg=w_reg)
-        return bw["dx"], dict(drift=bw["dp_drift"], diffusion=bw["dp_diff"]), dict(sol=sol, st=st2, dx_reg=None)
+        return bw["dx"], dict(drift=bw["dp_drift"], diffusion=bw["dp_diff"]), dict(sol=sol, st=st2, dx_reg=None,
+                                                                                  backward=self.handle().last_backward_info())
