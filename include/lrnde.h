@@ -491,6 +491,36 @@ int lrnde_sde_record_generation(lrnde_sde* sde, uint64_t* gen_host);
 int lrnde_sde_draw_noise(lrnde_sde* sde, uint64_t seed, uint32_t stream, int32_t nsteps, int32_t B, float scale,
                          int32_t cumulative, float* out);
 
+/* The Brownian path of the adaptive entry points as a VIRTUAL TREE: W at a grid index is a pure function of (seed, stream,
+ * column, index) — a Levy / Brownian-bridge construction on lrnde_sde_draw_noise's normals — so a solve needs no
+ * (nfine+1) x B x D array, its resolution is not tied to memory, and a rejected step re-queries the same path.
+ * Definition (the kernels are held to it bit for bit; tests/brownian_tree_np.py restates it):  nfine = 2^L, 0 <= L <= 20;
+ * span = t2 - t0 in float32; column c = b*D + d; z[n], n = 0 .. nfine-1, is standard normal n of column c in the stream exactly
+ * as lrnde_sde_draw_noise(seed, stream, nfine, B, 1.0, increments) returns it (counter (n >> 2, c, stream, 0), word n & 3,
+ * float64 Box-Muller rounded once).  Streams: 6 is the tree of W, 7 the tree of SRI's second path Z (0..5 keep their meaning).
+ * Every operation is a single float32 operation, no contraction:
+ *   W[0] = 0;  W[nfine] = sT * z[0], sT = (float)sqrt((double)span);
+ *   for level l = 1 .. L and node j = 0 .. 2^(l-1) - 1:  a = j * 2^(L-l+1), b = a + 2^(L-l+1), mid = a + 2^(L-l), n = 2^(l-1) + j,
+ *     W[mid] = (0.5 * (W[a] + W[b])) + (s_l * z[n]),  s_l = (float)(0.5 * sqrt((double)span * 2^-(l-1))).
+ * A query for index k descends from (0, nfine) computing only the midpoints on its way: L - ctz(k) levels.  A column's path
+ * depends on (seed, stream, b, d, k / nfine, span) only — not on B or the launch — and the tree is refinement-consistent:
+ * W_L[k] == W_L'[k * 2^(L'-L)] bit for bit.
+ * lrnde_sde_tree_path: the whole array of that definition, out (device, (2^levels + 1) x B x D), on the handle's stream (no host
+ *   sync) — to look at a path, and the yardstick of the tests.
+ * lrnde_sde_set_path_tree(enable = 1, seed): from then on lrnde_sde_solve_adaptive(_alg), lrnde_sde_node_forward_record(_alg)
+ *   and lrnde_sde_model_forward_record_ce IGNORE their W and Z arguments (NULL is fine) and take the path from the tree of `seed`
+ *   at L = log2(nfine) over the call's (t0, t2), stream 6 for W and 7 for Z.  nfine that is no power of two, or above 2^20, is
+ *   LRNDE_BADARG with a message.  The recorded forward keeps the accepted steps' increments beside their end states (the record
+ *   starts at 64 steps and is replaced by one four times as large, up to min(nfine, maxiters), when a solve ends with
+ *   LRNDE_CAPACITY — the solve then runs again on the same path) and every backward route reads them from there: no backward call regenerates noise or reads a
+ *   path.  enable = 0 (the default): the caller's arrays, as before — including the refusal of a NULL W.  A record remembers the
+ *   source it was made with.  A sharded handle refuses the tree with LRNDE_BADARG: a shard numbers its columns from its own
+ *   first sample, and the path of a sample must not depend on the sharding.
+ * The grid-quantised adaptive loop that consumes the path is UPSTREAM-RECALL like its neighbours above (StochasticDiffEq's own
+ * rejection sampling with memory is un-vendored and not restated). */
+int lrnde_sde_tree_path(lrnde_sde* sde, uint64_t seed, uint32_t stream, int32_t levels, int32_t B, float t0, float t2, float* out);
+int lrnde_sde_set_path_tree(lrnde_sde* sde, int32_t enable, uint64_t seed);
+
 /* `_perform_step(integrator, cache::FourStageSRIConstantCache, p)`, src/perform_step.jl:49-106 — the step the
  * reference's default SDE solver SOSRI runs — diagonal noise: four drift and four diffusion evaluations, the
  * increments dW and dZ of the caller's noise process (device, B x D each), u, EEst from the 7-argument

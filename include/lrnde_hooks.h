@@ -100,6 +100,10 @@ int lrnde_conv_bench_rhs(lrnde_conv* c, const float* u, float t, int32_t B, int3
 /* Test hook: the device Philox-4x32-10 of lrnde_sde_draw_noise on ONE block (host arrays in and out; current device,
  * synchronous), so the published known-answer vectors can be checked on the GPU. */
 int lrnde_hook_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* Test hook: the drift context an SDE handle owns (not a new reference; it dies with the handle).  No entry point of lrnde.h
+ * attaches a communicator to an SDE handle; with this one a test can (lrnde_comm_init_local) and see what the SDE entry points
+ * refuse on a sharded handle — the path tree, for one. */
+int lrnde_hook_sde_drift_ctx(lrnde_sde* s, lrnde_ctx** out);
 
 /* Diagnostic: kernels the last lrnde_latent_encode / lrnde_latent_encode_backward enqueued (1; 2 = the reverse walk and
  * the sum of its per-workgroup partials). */

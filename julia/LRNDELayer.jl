@@ -310,8 +310,13 @@ lrnde_sde_supported(n::NeuralDSDE, x) = _lrnde_sde_which(n.solver) !== nothing &
 
 const LRNDE_SDE_NFINE = Ref(256)    # grid intervals of the Brownian path drawn per layer call
 # :host — W and z drawn with randn from st.rng and copied over; :device — one seed = rand(rng, UInt64), then W (stream 0) and
-# z (stream 1) drawn on the device by lrnde_sde_draw_noise (the same streams and scale as the Python layer's noise_source="device")
+# z (stream 1) drawn on the device by lrnde_sde_draw_noise (the same streams and scale as the Python layer's noise_source="device");
+# :tree — the same seed, but no path array: lrnde_sde_set_path_tree makes the solve query the virtual Brownian tree of the seed
+# (include/lrnde.h; LRNDE_SDE_NFINE[] must be a power of two <= 2^20), z from stream 1 as with :device
 const LRNDE_SDE_NOISE = Ref(:host)
+lrnde_sde_set_path_tree(h, enable::Bool, seed::UInt64) =
+    LRNDEBackend.sde_check(h, ccall((:lrnde_sde_set_path_tree, LRNDEBackend.lib), Cint, (Ptr{Cvoid}, Int32, UInt64),
+                                    h, Int32(enable), seed))
 
 function lrnde_sde_layer_forward(n::NeuralDSDE, x, ps, st)
     h = lrnde_sde_handle(n)
@@ -322,12 +327,20 @@ function lrnde_sde_layer_forward(n::NeuralDSDE, x, ps, st)
     nfine = LRNDE_SDE_NFINE[]
     hh = (t2 - t0) / nfine
     # the Brownian path on the grid (W[0] = 0) and the local step's standard-normal draw, from the layer's own stream
-    if LRNDE_SDE_NOISE[] === :device
+    if LRNDE_SDE_NOISE[] === :tree
+        seed = rand(rng, UInt64)
+        B = Int(LRNDEBackend.nbatch(x))
+        lrnde_sde_set_path_tree(h, true, seed)
+        W = x      # (ignored by the library while the tree is on: any device pointer serves)
+        z = reshape(LRNDEBackend.sde_draw_noise(h, x, seed, 1, 1, B, 1f0, false), size(x))
+    elseif LRNDE_SDE_NOISE[] === :device
+        lrnde_sde_set_path_tree(h, false, UInt64(0))
         seed = rand(rng, UInt64)
         B = Int(LRNDEBackend.nbatch(x))
         W = LRNDEBackend.sde_draw_noise(h, x, seed, 0, nfine, B, sqrt(hh), true)
         z = reshape(LRNDEBackend.sde_draw_noise(h, x, seed, 1, 1, B, 1f0, false), size(x))
     else
+        lrnde_sde_set_path_tree(h, false, UInt64(0))
         inc = randn(rng, Float32, size(x)..., nfine) .* sqrt(hh)
         Wh = cat(zeros(Float32, size(x)..., 1), cumsum(inc; dims=ndims(inc)); dims=ndims(inc))
         W = copyto!(similar(x, size(Wh)...), Wh)
@@ -338,7 +351,7 @@ function lrnde_sde_layer_forward(n::NeuralDSDE, x, ps, st)
     saveat = Float32.(collect(get(n.kwargs, :saveat, Float32[])))
     opts = SdeAdaptOpts(Float32(get(n.kwargs, :abstol, 1f-2)), Float32(get(n.kwargs, :reltol, 1f-2)), Float32(1 / 6), 0f0,
                         0.9f0, 0.2f0, 1.125f0, 0.14f0, 0.08f0, Int32(n.maxiters))
-    cap = length(saveat) + 3 + (isempty(saveat) && mode === :biased ? nfine + 1 : 0)
+    cap = length(saveat) + 3 + (isempty(saveat) && mode === :biased ? min(nfine, max(Int(n.maxiters), 1)) + 1 : 0)   # (every accepted step: never more)
     useries = similar(x, size(x)..., cap); tseries = zeros(Float32, cap)
     ns = Ref{Int32}(); reg = Ref{Float32}(); nf = Ref{Int32}(); ng = Ref{Int32}(); stats = Stats(); t1u = Ref{Float32}()
     save_start = haskey(n.kwargs, :save_start) ? Int32(n.kwargs[:save_start]) : Int32(-1)

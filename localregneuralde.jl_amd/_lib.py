@@ -134,6 +134,9 @@ SYMBOLS = [
     ("lrnde_conv_record_generation", C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     ("lrnde_sde_record_generation", C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     ("lrnde_sde_draw_noise", C.c_int, [_vp, C.c_uint64, C.c_uint32, _i32, _i32, _f, _i32, _vp]),
+    ("lrnde_sde_tree_path", C.c_int, [_vp, C.c_uint64, C.c_uint32, _i32, _i32, _f, _f, _vp]),
+    ("lrnde_sde_set_path_tree", C.c_int, [_vp, _i32, C.c_uint64]),
+    ("lrnde_hook_sde_drift_ctx", C.c_int, [_vp, C.POINTER(_vp)]),
     ("lrnde_hook_philox4x32_10", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("lrnde_sde_solve_fixed_backward_rkmil", C.c_int, [_vp, _vp, _vp, _vp, _i32, _f, _f, _i32, _vp, _vp, _vp, _vp]),
     ("lrnde_sde_rkmil_reg_grad", C.c_int, [_vp, _vp, _vp, _i32, _f, _f, _f, _f, _vp, _vp, _fp]),

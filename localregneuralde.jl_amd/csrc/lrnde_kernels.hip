@@ -1617,6 +1617,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
   }
 }
 
+#include "lrnde_sde_tree.hpp"
 #include "lrnde_sde_fast.hpp"
 #include "lrnde_sde_mil_fast.hpp"
 #include "lrnde_sde_sri_fast.hpp"
@@ -3240,7 +3241,24 @@ struct lrnde_sde {
   // lrnde_sde_last_backward_info: how the last lrnde_sde_node_backward_recorded ran (0 launch sequences per recorded step, 1 the
   // one-launch sweep), the kernels it enqueued and its stream synchronisations (both -1 on the per-step route: not counted)
   int bwd_kind = 0, bwd_launches = 0, bwd_waits = 0;
+  // lrnde_sde_set_path_tree: the adaptive entry points take the Brownian path from the virtual tree of this seed
+  // (lrnde_sde_tree.hpp) and ignore their W / Z arguments
+  bool tree_on = false; uint64_t tree_seed = 0;
 };
+// the path source of one adaptive call on this handle: the tree of the handle's seed at L = log2(nfine) over (t0, t1), or off
+static int sde_tree_source(lrnde_sde* s, int32_t nfine, float t0, float t1, SdeTree& T) {
+  memset(&T, 0, sizeof(T));
+  if (!s->tree_on) return LRNDE_OK;
+  // (a shard would number its columns from its own first sample: the path of a sample must not depend on the sharding)
+  if (sharded(s->drift)) return fail(s->drift, LRNDE_BADARG, "the path tree is not available on a sharded handle");
+  if (nfine < 1 || nfine > (1 << TREE_MAXL) || (nfine & (nfine - 1)) != 0)
+    return fail(s->drift, LRNDE_BADARG, "the path tree needs nfine = 2^L with L <= %d (got %d)", TREE_MAXL, nfine);
+  T.on = 1; T.k0 = (uint32_t)(s->tree_seed & 0xffffffffu); T.k1 = (uint32_t)(s->tree_seed >> 32);
+  T.L = 0;
+  while ((1 << T.L) < nfine) ++T.L;
+  sde_tree_scales(T, t1 - t0);
+  return LRNDE_OK;
+}
 
 int lrnde_sde_create(lrnde_sde** out, const lrnde_model_desc* drift, int32_t diffusion_bias, int device, void* stream) {
   if (!out || !drift) return LRNDE_BADARG;
@@ -3497,7 +3515,8 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
                                const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                                int32_t cap_trace, float* ua, float* ub, float* rec_u = nullptr, int2* rec_im = nullptr,
                                int rec_cap = 0, int2* rec_im_host = nullptr, const float* dt0_dev = nullptr, bool no_persist = false,
-                               int which = 0, const lrnde_sri_tableau* tab = nullptr, const float* Z = nullptr) {
+                               int which = 0, const lrnde_sri_tableau* tab = nullptr, const float* Z = nullptr,
+                               const SdeTree* tree = nullptr) {
   lrnde_ctx* c = s->drift;
   if (which != 0) no_persist = true;   // (the Milstein and SRI steps have the launch-per-attempt form only: lrnde_sde_mil_fast.hpp, lrnde_sde_sri_fast.hpp)
   const size_t n = (size_t)B * c->desc.state_dim;
@@ -3531,6 +3550,7 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   f.trace = trace_host ? s->ad_trace : nullptr; f.cap_trace = trace_host ? cap_trace : 0;
   f.prog = s->ad_prog.dev();
   if (which == 2) { f.Zpath = Z; f.tab = *tab; }
+  if (tree && tree->on) { f.tree = *tree; f.Wpath = nullptr; f.Zpath = nullptr; }   // (the TREE instantiations: no path pointer is read)
   const int nwg = (B + NB - 1) / NB;
   // The whole solve as ONE cooperative launch (k_sde_eh_fast<DT, HT, true>: state and weights stay in registers, a grid barrier
   // per step) when every workgroup fits on the chip at once; LRNDE_SDE_NO_PERSIST=1, a launch the runtime refuses or more than
@@ -3588,7 +3608,7 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   s->info_kind = persisted ? 2 : 1;
   const SdeCtl fin = *reinterpret_cast<const SdeCtl*>(s->ad_ctl_host.get());
   if (persisted && plain && (fin.status == LRNDE_HIP_ERROR || fin.status == ST_RUNNING))   // the barrier gave up waiting (busy device): the loop
-    return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true, which, tab, Z);
+    return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true, which, tab, Z, tree);
   if (pairs_home && fin.naccept > 0)
     memcpy(rec_im_host, s->ad_ctl_host + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
   st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iters; st->nf = fin.nf; st->eest_last = fin.eest_last;
@@ -3609,13 +3629,13 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
                                    const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                                    int32_t cap_trace, float* rec_u, int2* rec_im_dev, int2* rec_im_host, int rec_cap,
                                    const float* dt0_dev = nullptr, int which = 0, const lrnde_sri_tableau* tab = nullptr,
-                                   const float* Z = nullptr);
+                                   const float* Z = nullptr, float* rec_dw = nullptr, float* rec_dz = nullptr);
 // the step kinds of the adaptive entry points: 0 Euler-Heun, 1 Milstein, 2 four-stage SRI (which needs its tableau and the
 // second Brownian path)
 static int sde_alg_check(lrnde_sde* s, int32_t which, const lrnde_sri_tableau* tab, const float* Z) {
   if (!s) return LRNDE_BADARG;
   if (which < 0 || which > 2) return fail(s->drift, LRNDE_BADARG, "which: 0 Euler-Heun, 1 Milstein, 2 SRI");
-  if (which == 2 && (!tab || !Z)) return fail(s->drift, LRNDE_BADARG, "the SRI step needs its tableau and the second Brownian path Z");
+  if (which == 2 && (!tab || (!Z && !s->tree_on))) return fail(s->drift, LRNDE_BADARG, "the SRI step needs its tableau and the second Brownian path Z");
   return LRNDE_OK;
 }
 int lrnde_sde_solve_adaptive_alg(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
@@ -3636,11 +3656,16 @@ int lrnde_sde_solve_adaptive(lrnde_sde* s, const float* u0, const float* W, int3
 static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
                                    const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                                    int32_t cap_trace, float* rec_u, int2* rec_im_dev, int2* rec_im_host, int rec_cap,
-                                   const float* dt0_dev, int which, const lrnde_sri_tableau* tab, const float* Z) {
-  int rc = sde_check(s, u0, W, u_end ? u_end : u0, B, 1.0f);   // (u_end may be NULL from the layer: no end state asked for)
+                                   const float* dt0_dev, int which, const lrnde_sri_tableau* tab, const float* Z, float* rec_dw,
+                                   float* rec_dz) {
+  // (the path tree: W and Z are ignored and may be NULL — the check sees u0 in W's place)
+  int rc = sde_check(s, u0, s && s->tree_on ? u0 : W, u_end ? u_end : u0, B, 1.0f);   // (u_end may be NULL from the layer: no end state asked for)
   if (rc) return rc;
   lrnde_ctx* c = s->drift;
   if (!o || !st || nfine < 1 || !(t1 > t0)) return fail(c, LRNDE_BADARG, "bad arguments (nfine >= 1, t1 > t0)");
+  SdeTree tree{};
+  if ((rc = sde_tree_source(s, nfine, t0, t1, tree))) return rc;
+  tree.rec_dw = tree.on ? rec_dw : nullptr; tree.rec_dz = tree.on && which == 2 ? rec_dz : nullptr;
   memset(st, 0, sizeof(*st));
   const size_t n = (size_t)B * c->desc.state_dim;
   HIPCHK(c, s->ad_ws.resize_exact(4 * n));
@@ -3651,7 +3676,7 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
     const bool host_loop = opt(OPT_SDE_HOST_LOOP) != 0;  // diagnostic: the host-controlled loop below
     if (sde_uses_fast(s) && !host_loop) {
       return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im_dev, rec_cap,
-                                 rec_im_host, dt0_dev, false, which, tab, Z);
+                                 rec_im_host, dt0_dev, false, which, tab, Z, &tree);
     }
   }
   s->info_kind = 0;
@@ -3668,10 +3693,12 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
     if (m > nfine - i) m = nfine - i;
     if (++st->iters > o->maxiters) { st->retcode = LRNDE_MAXITERS; break; }
     const float t = t0 + (float)i * h, dt = (float)m * h;
-    hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, W + (size_t)i * n, W + (size_t)(i + m) * n, dW);
+    if (tree.on) hipLaunchKernelGGL(k_sde_dw_tree, dim3(nb), dim3(256), 0, c->stream, n, tree, TREE_STREAM_W, i, m, dW);
+    else hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, W + (size_t)i * n, W + (size_t)(i + m) * n, dW);
     float eest = 0.f;
     if (which == 2) {   // k_sri_chi / k_sri_stage / k_sri_final around the eight evaluations; the call ends in the attempt's synchronisation
-      hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, Z + (size_t)i * n, Z + (size_t)(i + m) * n, dZ);
+      if (tree.on) hipLaunchKernelGGL(k_sde_dw_tree, dim3(nb), dim3(256), 0, c->stream, n, tree, TREE_STREAM_Z, i, m, dZ);
+      else hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, Z + (size_t)i * n, Z + (size_t)(i + m) * n, dZ);
       if ((rc = lrnde_sde_sri_step(s, tab, ua, dW, dZ, B, t, dt, o->abstol, o->reltol, o->delta, ub, &eest, nullptr))) return rc;
     } else {
       if ((rc = sde_step_enqueue(s, which, ua, dW, B, t, dt, o->abstol, o->reltol, o->delta, ub, c->ctrl_host))) return rc;
@@ -3693,6 +3720,9 @@ static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W
       if (rec_u) {
         if (st->naccept >= rec_cap) { st->retcode = LRNDE_CAPACITY; break; }
         HIPCHK(c, hipMemcpyAsync(rec_u + (size_t)st->naccept * n, ub, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+        // (the tree: the accepted step's increments beside its end state — the backward reads them from there)
+        if (tree.rec_dw) HIPCHK(c, hipMemcpyAsync(tree.rec_dw + (size_t)st->naccept * n, dW, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+        if (tree.rec_dz) HIPCHK(c, hipMemcpyAsync(tree.rec_dz + (size_t)st->naccept * n, dZ, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
         rec_im_host[st->naccept] = make_int2(i, m);
       }
       st->naccept++;

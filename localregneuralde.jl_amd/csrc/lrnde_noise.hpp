@@ -8,6 +8,7 @@
 // in (0, 1); Box-Muller runs in float64 and rounds once to float32, so a float64 restatement (tests/philox_np.py) agrees
 // to within one float32 ulp and almost always bit for bit.  The scale and the path's running sum are single fp32
 // operations in sequential order: exactly np.cumsum(z.astype(f32) * f32(scale), dtype=f32).
+// Also here: the C entry points of the virtual path tree (lrnde_sde_tree_path, lrnde_sde_set_path_tree; lrnde_sde_tree.hpp).
 
 namespace {
 
@@ -15,27 +16,7 @@ constexpr int NZ_COLS = 64;    // columns of one workgroup (one wave wide)
 constexpr int NZ_ROWS = 128;   // steps generated into LDS per pass (32 KB)
 constexpr int NZ_NT = 256;
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t x[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-  }
-  x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
-
-__device__ __forceinline__ double noise_u01(uint32_t x) { return ((double)(x >> 8) + 0.5) * 0x1p-24; }
-
-// (z0, z1) = sqrt(-2 ln u_a) (cos, sin)(2 pi u_b), float64, rounded once
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-  const double r = sqrt(-2.0 * log(noise_u01(a)));
-  const double th = 6.283185307179586 * noise_u01(b);
-  z0 = (float)(r * cos(th));
-  z1 = (float)(r * sin(th));
-}
+// (philox4x32_10, noise_u01 and box_muller: lrnde_sde_tree.hpp, which draws the same normals)
 
 // One workgroup per 64 columns.  Per pass of NZ_ROWS steps its four waves generate the standard normals into LDS (a wave
 // covers the 64 columns of one counter block: conflict-free LDS rows), then either every thread writes scale * z row by
@@ -105,6 +86,39 @@ int lrnde_sde_draw_noise(lrnde_sde* s, uint64_t seed, uint32_t stream, int32_t n
   hipLaunchKernelGGL(k_sde_noise, dim3(nwg), dim3(NZ_NT), 0, c->stream, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32),
                      stream, nsteps, (uint32_t)ncols, scale, cumulative, out);
   HIPCHK(c, hipGetLastError());
+  return LRNDE_OK;
+}
+
+// the virtual path tree (lrnde_sde_tree.hpp) as an array: what every tree-mode solve queries, for callers that want to look at it
+int lrnde_sde_tree_path(lrnde_sde* s, uint64_t seed, uint32_t stream, int32_t levels, int32_t B, float t0, float t2, float* out) {
+  if (!s) return LRNDE_BADARG;
+  lrnde_ctx* c = s->drift;
+  if (levels < 0 || levels > TREE_MAXL) return fail(c, LRNDE_BADARG, "levels must lie in 0..%d (got %d)", TREE_MAXL, levels);
+  if (B <= 0) return fail(c, LRNDE_BADARG, "batch must be positive (got %d)", B);
+  if (!out) return fail(c, LRNDE_BADARG, "null output pointer");
+  if (!(t2 > t0) || !isfinite(t2 - t0)) return fail(c, LRNDE_BADARG, "t2 must lie after t0");
+  const uint64_t ncols = (uint64_t)B * (uint64_t)c->desc.state_dim;
+  if (ncols > (1ull << 30)) return fail(c, LRNDE_BADARG, "B x D = %llu columns: at most 2^30", (unsigned long long)ncols);
+  HIPCHK(c, hipSetDevice(c->device));
+  SdeTree T{};
+  T.on = 1; T.k0 = (uint32_t)(seed & 0xffffffffu); T.k1 = (uint32_t)(seed >> 32); T.L = levels;
+  sde_tree_scales(T, t2 - t0);
+  hipLaunchKernelGGL(k_sde_tree_path, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, c->stream, T, stream, (uint32_t)ncols, out);
+  HIPCHK(c, hipGetLastError());
+  return LRNDE_OK;
+}
+
+int lrnde_sde_set_path_tree(lrnde_sde* s, int32_t enable, uint64_t seed) {
+  if (!s) return LRNDE_BADARG;
+  if (enable != 0 && enable != 1) return fail(s->drift, LRNDE_BADARG, "enable must be 0 or 1 (got %d)", enable);
+  s->tree_on = enable != 0;
+  s->tree_seed = enable ? seed : 0;
+  return LRNDE_OK;
+}
+
+int lrnde_hook_sde_drift_ctx(lrnde_sde* s, lrnde_ctx** out) {
+  if (!s || !out) return LRNDE_BADARG;
+  *out = s->drift;
   return LRNDE_OK;
 }
 

@@ -11,7 +11,8 @@ namespace {
 
 // the one-launch reverse sweep (lrnde_sde_bwd_fused.hpp; launcher in lrnde_sde_node.hpp): what it walks — K steps given as
 // (start index, length) on a grid of interval h, the state at each step's start, and either the Brownian PATH (dW formed as a
-// difference) or the array of increments itself (dw_direct: the fixed-grid solve)
+// difference) or the array of increments itself (dw_direct 1: the fixed-grid solve, block im.x; 2: a record made on the path
+// tree, block k — lrnde_sde_node.hpp)
 struct SdeSweepSrc {
   int K; const int2* im; float h; const float* x; const float* rec_u; const float* W; int dw_direct;
   int nseries; const int* ser_k; const float* ser_theta;   // host arrays: which step a cotangent's state was taken in, and where

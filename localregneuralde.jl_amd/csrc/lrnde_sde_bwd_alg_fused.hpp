@@ -188,8 +188,9 @@ __device__ __forceinline__ float sba_sri_step(const SbfDev& c, const SdeBwdFused
   return live ? upb : 0.f;
 }
 
-// The sweep.  KIND: 1 Milstein, 2 SRI.
-template <int KIND>
+// The sweep.  KIND: 1 Milstein, 2 SRI.  DIRECT: a.W / q.Z hold the INCREMENTS of the recorded steps, step k's in slot k (a record
+// made on the virtual path tree: lrnde_sde_node.hpp) — no path is read, (i, m) still gives dt.
+template <int KIND, bool DIRECT = false>
 __global__ __launch_bounds__(SBF_NT) void k_sde_alg_bwd_fused(SdeAlgBwdArgs q) {
   static_assert(KIND == 1 || KIND == 2, "1 Milstein, 2 SRI");
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -210,8 +211,13 @@ __global__ __launch_bounds__(SBF_NT) void k_sde_alg_bwd_fused(SdeAlgBwdArgs q) {
     const int2 im = a.im[k];
     const float* up = (k == 0) ? a.x : a.rec_u + (size_t)(k - 1) * nst;
     u = up[g]; m = im.y;
+    if constexpr (DIRECT) {
+      wlo = 0.f; whi = a.W[(size_t)k * nst + g];
+      if constexpr (KIND == 2) { zlo = 0.f; zhi = q.Z[(size_t)k * nst + g]; }
+    } else {
     wlo = a.W[(size_t)im.x * nst + g]; whi = a.W[(size_t)(im.x + im.y) * nst + g];
     if constexpr (KIND == 2) { zlo = q.Z[(size_t)im.x * nst + g]; zhi = q.Z[(size_t)(im.x + im.y) * nst + g]; }
+    }
   };
   float u_n = 0.f, wlo_n = 0.f, whi_n = 0.f, zlo_n = 0.f, zhi_n = 0.f;
   int m_n = 0;

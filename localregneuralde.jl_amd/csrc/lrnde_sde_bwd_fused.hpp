@@ -42,7 +42,8 @@ struct SdeBwdFusedArgs {
   const int2* im;                   // (start index, length) of step k on the path's grid
   const float* W;                   // the caller's Brownian path ((nfine + 1), B, D)
   float h;                          // grid interval
-  int dw_direct;                    // 1: W is the array of INCREMENTS, one (B, D) block per step (fixed-grid solve): dW = W[im.x]
+  int dw_direct;                    // non-zero: W is the array of INCREMENTS, one (B, D) block per step: dW = W[im.x] (1: the fixed-grid
+                                    // solve; 2: a record made on the path tree, whose staged pairs carry the record slot in im.x)
   const float* du_series; int nseries; const int* ser_k; const float* ser_theta;   // cotangents of the caller's series
   float* dx;                        // (B, D): cotangent of the input
   float* part;                      // [gridDim.x][Ptot] parameter-cotangent partials of the workgroups

@@ -70,6 +70,9 @@ struct SdeFastArgs {
   // the four-stage SRI step (k_sde_sri_fast, lrnde_sde_sri_fast.hpp): the second Brownian path on W's grid and the caller's
   // tableau, by value (last: the other kernels' argument offsets are what they were)
   const float* Zpath; lrnde_sri_tableau tab;
+  // the path source of the TREE instantiations (lrnde_sde_tree.hpp): W (and SRI's Z) by descent instead of Wpath / Zpath, the
+  // accepted step's increments recorded beside rec_u.  Behind everything else: no other field moves
+  SdeTree tree;
 };
 // dtc: the controller's step proposal as a REAL number; the step taken is its floor on the path's grid (m intervals, at least
 // one).  Growth accumulates in dtc — with qmax = 1.125 a proposal quantised after every step could never leave m = 1.
@@ -208,6 +211,46 @@ struct SdeFrame {
     for (int r = 0; r < 4; ++r) d[r] = hi[r] - lo[r];
     return d;
   }
+  // this lane's four rows of W[k] of the virtual tree (stream 6: W, 7: Z; lrnde_sde_tree.hpp) — rows past D zero, as ld4s leaves them
+  __device__ __forceinline__ f32x4 wtree(const SdeTree& T, uint32_t stream, int k) const {
+    const uint32_t c[4] = {(uint32_t)g, (uint32_t)g + 1u, (uint32_t)g + 2u, (uint32_t)g + 3u};   // column b D + d
+    float w[4];
+    tree_query<4>(T, stream, c, k, w);
+    f32x4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = row0 + r < D ? w[r] : 0.f;
+    return v;
+  }
+  // ... and the increment W[i + m] - W[i] from it: dpath's subtraction on the tree's two values
+  __device__ __forceinline__ f32x4 dtree(const SdeTree& T, uint32_t stream, int i, int m) const {
+    const f32x4 hi = wtree(T, stream, i + m);
+    const f32x4 lo = wtree(T, stream, i);
+    f32x4 d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d[r] = hi[r] - lo[r];
+    return d;
+  }
+  // The descent spread over the WHOLE workgroup (the live lanes above are the Dense-2 waves only: DT of four): thread x takes
+  // column x & 15 and the rows (x >> 4) + 16 j, j < DT, of the 16 DT x 16 tile — DT elements instead of four on DT / 4 of the
+  // waves — and leaves W[k] in wt ([row][16 columns], LDS; zero outside B / D).  Every thread of the workgroup calls it; after
+  // a barrier the Dense-2 lanes read their four rows with wtree_rd.  Same normals, same operations: the bits of wtree.
+  __device__ __forceinline__ void wtree_fill(const SdeTree& T, uint32_t stream, int k, int B, float* wt) const {
+    const int ne = threadIdx.x & 15, r0 = threadIdx.x >> 4;
+    const int be = blockIdx.x * 16 + ne;
+    uint32_t c[DT];
+    float w[DT];
+#pragma unroll
+    for (int j = 0; j < DT; ++j) c[j] = (uint32_t)be * (uint32_t)D + (uint32_t)(r0 + 16 * j);   // (outside B / D: some other column's value, discarded)
+    tree_query<DT>(T, stream, c, k, w);
+#pragma unroll
+    for (int j = 0; j < DT; ++j) wt[(r0 + 16 * j) * 16 + ne] = (be < B && r0 + 16 * j < D) ? w[j] : 0.f;
+  }
+  __device__ __forceinline__ f32x4 wtree_rd(const float* wt) const {   // (live lanes: row0 + 3 < 16 DT)
+    f32x4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = wt[(row0 + r) * 16 + n];
+    return v;
+  }
   // B-operand image of rows 16 t + 4 rq + r, column n: float4 index t*64 + r*16 + n, component rq (Dense-2 waves)
   __device__ __forceinline__ void put(f32x4* x, const f32x4& v) const {
     float* p = reinterpret_cast<float*>(x) + ((t * 64 + n) << 2) + rq;
@@ -290,7 +333,10 @@ template <int DT> __device__ __forceinline__ void sde_step_footer(const SdeFastA
 // their columns' state in registers; a step ends in a grid barrier (tagged partial-sum slots + bounded polling) after which EVERY
 // workgroup adds the partial sums in the same fixed order and runs the same controller on its own copy of the control
 // block — the same decisions everywhere, no broadcast, and the arithmetic of a step is the code of the one-launch form.
-template <int DT, int HT, bool PERSIST = false>
+// TREE: the adaptive solve's increments come from the virtual tree instead of a.Wpath, the descent spread over all four waves
+// (F.wtree_fill -> 1 KB of LDS per 16 rows -> F.wtree_rd behind the step's first barrier).  W[i] is carried in registers: an
+// accepted step's W[i + m] is the next step's W[i], a rejected step keeps it — one descent per attempt in the persistent form.
+template <int DT, int HT, bool PERSIST = false, bool TREE = false>
 __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
   const bool adapt = a.ctl != nullptr;
   int ad_i = 0, ad_m = 0, ad_slot = 0;
@@ -314,12 +360,25 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
   const size_t nn = F.nn;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 u4 = zero4, w4 = zero4;
+  [[maybe_unused]] f32x4 wlo4 = zero4, whi4 = zero4;
   if (live) u4 = F.ld4s(a.u);
+  [[maybe_unused]] float* wt = nullptr;   // TREE: W[k] of the workgroup's 16 DT x 16 tile
+  if constexpr (TREE) {
+    __shared__ float wt_[DT * 256];
+    wt = wt_;
+    if (adapt) {   // W[i] at the launch's position (zero without a descent at i = 0)
+      F.wtree_fill(a.tree, TREE_STREAM_W, ad_i, a.B, wt);
+      __syncthreads();
+      if (live) wlo4 = F.wtree_rd(wt);
+      __syncthreads();   // (wt is refilled below)
+    }
+  }
   for (int it = 0;; ++it) {   // (one trip unless PERSIST)
   SDE_STAMP(0);
+  if constexpr (TREE) { if (adapt) F.wtree_fill(a.tree, TREE_STREAM_W, ad_i + ad_m, a.B, wt); }   // (every thread; read behind the barrier below)
   if (live) {
     if (adapt) {  // dW = W[i + m] - W[i], the path's own increment (the expression of k_sde_dw)
-      w4 = F.dpath(a.Wpath, ad_i, ad_m);
+      if constexpr (!TREE) w4 = F.dpath(a.Wpath, ad_i, ad_m);
     } else {
       w4 = F.ld4s(a.dW);
       if (a.dW_scaled) {
@@ -332,6 +391,13 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
   }
   if (has_d2) F.put(xA, u4);
   __syncthreads();
+  if constexpr (TREE) {
+    if (adapt && live) {   // (wt is next written at the top of the next step, barriers away)
+      whi4 = F.wtree_rd(wt);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) w4[r] = whi4[r] - wlo4[r];
+    }
+  }
   const float dt = a.dt, hdt = dt / 2.0f, sqdt = __builtin_sqrtf(dt);
 
   if constexpr (!PERSIST) {
@@ -456,6 +522,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
     if (live) {
       if (!PERSIST) F.st4s(a.un, un);   // (PERSIST: the state lives in registers until the solve ends)
       if (a.rec_u && ad_slot < a.rec_cap) F.st4s(a.rec_u + (size_t)ad_slot * nn, un);
+      if constexpr (TREE) { if (a.tree.rec_dw && ad_slot < a.rec_cap) F.st4s(a.tree.rec_dw + (size_t)ad_slot * nn, w4); }
     }
     F.put(xA, Kv);   // xA is free: every wave has read it (barrier above)
   }
@@ -544,6 +611,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_eh_fast(SdeFastArgs a) {
     SDE_STAMP(6);
     const int nacc0 = cc.naccept;
     cc = sh_cc;
+    if constexpr (TREE) { if (cc.naccept != nacc0) wlo4 = whi4; }
     if (cc.naccept != nacc0) u4 = un;   // accepted: the end state is the next step's start state (rows of the Dense-2 waves)
     if (cc.status != ST_RUNNING) {
       if (live) F.st4s(cc.cur ? a.ub : a.ua, u4);
@@ -591,7 +659,10 @@ template <class F> inline bool sde_fast_dispatch(int D, int H, F fn) {
   return sde_fast_dispatch_(((D + 15) / 16 - 1) * 8 + (H + 15) / 16 - 1, fn, std::make_integer_sequence<int, 32>{});
 }
 inline void sde_fast_launch(int D, int H, int nwg, hipStream_t st, const SdeFastArgs& f) {
-  sde_fast_dispatch(D, H, [&](auto dt, auto ht) { hipLaunchKernelGGL((k_sde_eh_fast<dt.value, ht.value>), dim3(nwg), dim3(SF_NT), 0, st, f); });
+  sde_fast_dispatch(D, H, [&](auto dt, auto ht) {
+    if (f.tree.on) hipLaunchKernelGGL((k_sde_eh_fast<dt.value, ht.value, false, true>), dim3(nwg), dim3(SF_NT), 0, st, f);
+    else hipLaunchKernelGGL((k_sde_eh_fast<dt.value, ht.value>), dim3(nwg), dim3(SF_NT), 0, st, f);
+  });
 }
 
 // the persistent form.  coop: a cooperative launch (all workgroups resident, or the call fails and the caller takes the
@@ -602,6 +673,10 @@ inline hipError_t sde_persist_launch(int D, int H, int nwg, hipStream_t st, SdeF
   hipError_t e = hipErrorInvalidValue;   // (a shape outside the gate: nothing is launched)
   sde_fast_dispatch(D, H, [&](auto dt, auto ht) {
     void* args[] = {&f};
+    if (f.tree.on) {
+      if (!coop) { hipLaunchKernelGGL((k_sde_eh_fast<dt.value, ht.value, true, true>), dim3(nwg), dim3(SF_NT), 0, st, f); e = hipGetLastError(); }
+      else e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k_sde_eh_fast<dt.value, ht.value, true, true>), dim3(nwg), dim3(SF_NT), args, 0, st);
+    } else
     if (!coop) { hipLaunchKernelGGL((k_sde_eh_fast<dt.value, ht.value, true>), dim3(nwg), dim3(SF_NT), 0, st, f); e = hipGetLastError(); }
     else e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k_sde_eh_fast<dt.value, ht.value, true>), dim3(nwg), dim3(SF_NT), args, 0, st);
   });

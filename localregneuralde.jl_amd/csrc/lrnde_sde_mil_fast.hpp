@@ -17,7 +17,8 @@
 // Footer: sde_step_footer with one drift evaluation per attempt.  The host keeps launches enqueued (sde_adaptive_device);
 // there is no persistent form of this kernel.
 
-template <int DT, int HT>
+// TREE: dW from the virtual tree (lrnde_sde_tree.hpp) instead of a.Wpath, recorded beside rec_u.
+template <int DT, int HT, bool TREE = false>
 __global__ __launch_bounds__(SF_NT) void k_sde_mil_fast(SdeFastArgs a) {
   if (!a.ctl) return;                // (the adaptive loop is this kernel's only caller)
   const SdeCtl cc = *a.ctl;          // written by the previous launch's last workgroup (kernel boundary in between) / by k_sde_ctl_init
@@ -35,7 +36,11 @@ __global__ __launch_bounds__(SF_NT) void k_sde_mil_fast(SdeFastArgs a) {
   const size_t nn = F.nn;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 u4 = zero4, w4 = zero4;
-  if (live) { u4 = F.ld4s(up); w4 = F.dpath(a.Wpath, ad_i, ad_m); }
+  if (live) {
+    u4 = F.ld4s(up);
+    if constexpr (TREE) w4 = F.dtree(a.tree, TREE_STREAM_W, ad_i, ad_m);
+    else w4 = F.dpath(a.Wpath, ad_i, ad_m);
+  }
   if (has_d2) F.put(xA, u4);
   __syncthreads();
   const float sqdt = __builtin_sqrtf(dt), hdt = 0.5f * __builtin_fabsf(dt);
@@ -78,6 +83,7 @@ __global__ __launch_bounds__(SF_NT) void k_sde_mil_fast(SdeFastArgs a) {
     if (live) {
       F.st4s(unp, un);
       if (a.rec_u && ad_slot < a.rec_cap) F.st4s(a.rec_u + (size_t)ad_slot * nn, un);
+      if constexpr (TREE) { if (a.tree.rec_dw && ad_slot < a.rec_cap) F.st4s(a.tree.rec_dw + (size_t)ad_slot * nn, w4); }
     }
     acc = wave_sum_dpp(acc);
     if (lane == 0) red[wave] = acc;
@@ -87,5 +93,8 @@ __global__ __launch_bounds__(SF_NT) void k_sde_mil_fast(SdeFastArgs a) {
 }
 
 inline void sde_mil_fast_launch(int D, int H, int nwg, hipStream_t st, const SdeFastArgs& f) {
-  sde_fast_dispatch(D, H, [&](auto dt, auto ht) { hipLaunchKernelGGL((k_sde_mil_fast<dt.value, ht.value>), dim3(nwg), dim3(SF_NT), 0, st, f); });
+  sde_fast_dispatch(D, H, [&](auto dt, auto ht) {
+    if (f.tree.on) hipLaunchKernelGGL((k_sde_mil_fast<dt.value, ht.value, true>), dim3(nwg), dim3(SF_NT), 0, st, f);
+    else hipLaunchKernelGGL((k_sde_mil_fast<dt.value, ht.value>), dim3(nwg), dim3(SF_NT), 0, st, f);
+  });
 }

@@ -34,6 +34,11 @@ struct SdeNodeRecord {
   // reverse kernels.  SRI: its tableau, the second path (the caller's, alive until the backward) and the local step's dZ
   int which = 0; lrnde_sri_tableau tab{}; const float* Z = nullptr; DevBuf<float> dZloc;
   bool un_scratch = false;   // the per-step SRI sweep has used tmp as scratch since the forward: the local step's u' is gone
+  // a record made on the virtual path tree (lrnde_sde_set_path_tree): W and Z are null, accepted step k's increments are slot k of
+  // rec_dw (SRI: and rec_dz), sized and replaced with rec_u — the only noise a backward route reads
+  bool tree = false; DevBuf<float> rec_dw, rec_dz;
+  const float* dw_of(int k, size_t n) const { return rec_dw.get() + (size_t)k * n; }
+  const float* dz_of(int k, size_t n) const { return rec_dz.get() + (size_t)k * n; }
 };
 
 // out = (1 - theta) * a + theta * b   (StochasticDiffEq's linear sde_interpolant)
@@ -167,7 +172,8 @@ int sde_init_dt_dev(lrnde_sde* s, const float* u, int B, float t, float tend, fl
   return LRNDE_OK;
 }
 
-int sde_node_alloc(lrnde_sde* s, SdeNodeRecord& r, int B, int nfine) {
+// nfine: the record's capacity in accepted steps.  ntree: increment buffers a tree record needs beside rec_u (0 none, 1 dW, 2 dW and dZ)
+int sde_node_alloc(lrnde_sde* s, SdeNodeRecord& r, int B, int nfine, int ntree = 0) {
   lrnde_ctx* c = s->drift;
   const size_t n = (size_t)B * c->desc.state_dim;
   if (r.n_alloc != n) {
@@ -180,6 +186,9 @@ int sde_node_alloc(lrnde_sde* s, SdeNodeRecord& r, int B, int nfine) {
     HIPCHK(c, r.tmp.once(6 * n));
     r.n_alloc = n;
   }
+  // rec_cap is what every guard of the record's slots trusts (the step kernels, the controller, the host loop): it must be the
+  // slots rec_u holds at THIS n — a buffer sized for a smaller batch holds fewer of them than it did
+  if ((size_t)r.rec_cap * n > r.rec_u.size()) r.rec_cap = (int)(r.rec_u.size() / n);
   if (r.rec_u.size() < (size_t)nfine * n || r.rec_cap < nfine) {   // the states and their (i, m) pairs are replaced together
     r.rec_cap = 0;
     (void)r.rec_u.reset(); (void)r.rec_im_dev.reset();
@@ -187,6 +196,8 @@ int sde_node_alloc(lrnde_sde* s, SdeNodeRecord& r, int B, int nfine) {
     HIPCHK(c, r.rec_im_dev.once(nfine));
     r.rec_cap = nfine;
   }
+  if (ntree >= 1 && r.rec_dw.size() < (size_t)r.rec_cap * n) { (void)r.rec_dw.reset(); HIPCHK(c, r.rec_dw.once((size_t)r.rec_cap * n)); }
+  if (ntree >= 2 && r.rec_dz.size() < (size_t)r.rec_cap * n) { (void)r.rec_dz.reset(); HIPCHK(c, r.rec_dz.once((size_t)r.rec_cap * n)); }
   const size_t Pf = lrnde_param_count(&c->desc), Pg = (size_t)c->desc.state_dim * c->desc.state_dim + (s->diff_bias ? c->desc.state_dim : 0);
   HIPCHK(c, r.gdr.resize_exact(Pf));
   HIPCHK(c, r.gdf.resize_exact(Pg));
@@ -223,7 +234,10 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   lrnde_ctx* c = s->drift;
   int rc = sde_alg_check(s, which, tab, Z);
   if (rc) return rc;
-  if ((rc = sde_check(s, x, W, u_series, B, 1.0f))) return rc;
+  const bool tree = s->tree_on;   // the path tree: W and Z are ignored (and recorded as null), the check sees x in W's place
+  if (tree) { W = nullptr; Z = nullptr; }
+  if ((rc = sde_check(s, x, tree ? x : W, u_series, B, 1.0f))) return rc;
+  { SdeTree probe{}; if ((rc = sde_tree_source(s, nfine, t0, t2, probe))) return rc; }   // (nfine = 2^L: refused before anything is allocated)
   if (which == 2 && mode != LRNDE_MODE_NONE && !z2_local)
     return fail(c, LRNDE_BADARG, "z2_local (the local SRI step's second standard-normal draw) is required when regularising");
   // per attempted step: (drift, diffusion) evaluations, and the strong order the automatic initial dt takes (UPSTREAM-RECALL)
@@ -239,12 +253,16 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   if (!s->node) s->node = new SdeNodeRecord();
   SdeNodeRecord& r = *s->node;
   r.valid = false;
-  if ((rc = sde_node_alloc(s, r, B, nfine))) return rc;
+  // (a tree record holds the accepted steps' states AND increments.  No solve accepts more steps than it may attempt, so
+  //  min(nfine, maxiters) slots always suffice — the array form's nfine slots would be the array the tree exists to avoid — but
+  //  a solve rarely takes that many: the record starts at 64 slots and, when a solve ends with LRNDE_CAPACITY, is replaced by one
+  //  four times as large and the solve runs again — the same path, the same bits)
+  const int rcap_max = tree ? std::max(1, std::min(nfine, o->maxiters)) : nfine;
+  int rcap = tree ? std::min(rcap_max, 64) : nfine;
   const int D = c->desc.state_dim;
   const size_t n = (size_t)B * D;
   const float h = (t2 - t0) / (float)nfine;
   int nfe_f = 0, nfe_g = 0;
-  HIPCHK(c, hipMemcpyAsync(r.x, x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   // the main solve (src/layers/neural_sde.jl:50-72): dt0 <= 0 -> automatic initial dt
   // (the one-launch steps' shape keeps the main solve's automatic initial dt on the device for all three step kinds, with the
   //  kind's strong order: the solve's closing synchronisation is then the main solve's only one; LRNDE_SDE_HOST_INITDT=1: the
@@ -253,11 +271,20 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   //  the generic step kernels, which take dt from the host)
   const bool devdt = sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT);
   const bool devdt_local = devdt && which == 0;
-  s->info_kind = s->info_launches = s->info_waits = 0;   // (lrnde_sde_last_solve_info: the main solve with its initial dt)
   if (devdt) {
     HIPCHK(c, s->idt_scal.once(8));
     HIPCHK(c, s->idt_scal_host.once(8));
   }
+  // No regulariser, no saveat, no start value: the caller's series is the end state alone — the solve leaves it in u_series itself
+  // (picked on the device) and its closing synchronisation is the call's only one.  Otherwise the end state is not asked for
+  // (it is the record's last slot).
+  const bool end_only = which == 0 && mode == LRNDE_MODE_NONE && nsave == 0 && save_start <= 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP);
+  float* u_end = end_only ? u_series : nullptr;
+  for (;;) {   // (one trip, unless a tree record has to grow)
+  nfe_f = nfe_g = 0;
+  if ((rc = sde_node_alloc(s, r, B, rcap, tree ? (which == 2 ? 2 : 1) : 0))) return rc;
+  HIPCHK(c, hipMemcpyAsync(r.x, x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+  s->info_kind = s->info_launches = s->info_waits = 0;   // (lrnde_sde_last_solve_info: the main solve with its initial dt)
   lrnde_sde_adapt_opts oo = *o;
   const float* dt0_dev = nullptr;
   if (!(oo.dt0 > 0.f)) {
@@ -273,14 +300,12 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
     nfe_f += 2; nfe_g += 2;
   }
   r.im.assign((size_t)nfine, make_int2(0, 0));
-  // No regulariser, no saveat, no start value: the caller's series is the end state alone — the solve leaves it in u_series itself
-  // (picked on the device) and its closing synchronisation is the call's only one.  Otherwise the end state is not asked for
-  // (it is the record's last slot).
-  const bool end_only = which == 0 && mode == LRNDE_MODE_NONE && nsave == 0 && save_start <= 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP);
-  float* u_end = end_only ? u_series : nullptr;
   rc = sde_solve_adaptive_impl(s, r.x, W, nfine, B, t0, t2, &oo, u_end, st, nullptr, 0, r.rec_u, r.rec_im_dev, r.im.data(), r.rec_cap, dt0_dev,
-                               which, tab, Z);
+                               which, tab, Z, tree ? r.rec_dw.get() : nullptr, tree && which == 2 ? r.rec_dz.get() : nullptr);
+  if (rc == LRNDE_CAPACITY && tree && r.rec_cap < rcap_max) { rcap = (int)std::min<long long>(rcap_max, 4ll * r.rec_cap); continue; }
   if (rc) return rc;
+  break;
+  }
   const int K = st->naccept;
   nfe_f += nfa * (st->naccept + st->nreject); nfe_g += nga * (st->naccept + st->nreject);
   // sol.t / sol.u as StochasticDiffEq would hold them (UPSTREAM-RECALL): saveat values by linear interpolation inside the
@@ -395,7 +420,7 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
   if (nfe_diffusion_host) *nfe_diffusion_host = nfe_g;
   if (t1_used_host) *t1_used_host = t1;
   r.valid = true; ++r.gen; r.B = B; r.nfine = nfine; r.K = K; r.mode = mode; r.t0 = t0; r.t2 = t2; r.h = h; r.o = *o; r.W = W;
-  r.which = which; r.Z = Z; r.un_scratch = false;
+  r.which = which; r.Z = Z; r.un_scratch = false; r.tree = tree;
   if (which == 2) r.tab = *tab;
   return LRNDE_OK;
 }
@@ -433,7 +458,9 @@ int sde_sweep_fused_core(lrnde_sde* s, const SdeSweepSrc& r, int B, const float*
   // wait (every call that uses the buffer ends in a synchronisation of this stream before the next one fills it)
   int* hm = s->bwf_meta_pin;
   for (int j = 0; j < nseries; ++j) { hm[j] = r.ser_k[j]; hm[SBF_MAXSER + j] = __builtin_bit_cast(int, r.ser_theta[j]); }
-  for (int k = 0; k < r.K; ++k) { hm[2 * SBF_MAXSER + 2 * k] = r.im[k].x; hm[2 * SBF_MAXSER + 2 * k + 1] = r.im[k].y; }
+  // (dw_direct = 2, a tree record: W holds step k's increments in slot k, and the kernels address increments by the pair's first
+  //  entry — their only use of it — so the staged pair is (k, m))
+  for (int k = 0; k < r.K; ++k) { hm[2 * SBF_MAXSER + 2 * k] = r.dw_direct == 2 ? k : r.im[k].x; hm[2 * SBF_MAXSER + 2 * k + 1] = r.im[k].y; }
   HIPCHK(c, hipMemcpyAsync(s->bwf_meta, hm, sizeof(int) * ((size_t)2 * SBF_MAXSER + 2 * (size_t)r.K), hipMemcpyHostToDevice, c->stream));
   SdeBwdFusedArgs a{};
   a.pdr = s->pdr; a.Wg = s->p2 + (size_t)D * D + D; a.bg = a.Wg + (size_t)D * D;
@@ -495,7 +522,7 @@ int sde_node_sweep_fused(lrnde_sde* s, SdeNodeRecord& r, int B, const float* du_
                          float* dp_diff, bool sync_after, bool reg, float w_reg, bool* reg_done) {
   std::vector<int> sk(nseries); std::vector<float> sth(nseries);
   for (int j = 0; j < nseries; ++j) { sk[j] = r.series[j].k; sth[j] = r.series[j].theta; }
-  SdeSweepSrc src{r.K, r.im.data(), r.h, r.x, r.rec_u, r.W, 0, nseries, sk.data(), sth.data()};
+  SdeSweepSrc src{r.K, r.im.data(), r.h, r.x, r.rec_u, r.tree ? r.rec_dw.get() : r.W, r.tree ? 2 : 0, nseries, sk.data(), sth.data()};
   return sde_sweep_fused_core(s, src, B, du_series, dx, dp_drift, dp_diff, sync_after, reg ? &r : nullptr, w_reg, reg_done);
 }
 // the regulariser's parameter cotangent, w_reg * d(EEst*dt)/dp of the recorded local step, ADDED to dp_drift / dp_diff
@@ -557,12 +584,15 @@ int sde_node_backward_alg(lrnde_sde* s, SdeNodeRecord& r, int B, const float* du
     const int i0 = r.im[k].x, m = r.im[k].y;
     const float t = r.t0 + (float)i0 * r.h, dt = (float)m * r.h;
     const float* u = (k == 0) ? r.x : r.rec_u + (size_t)(k - 1) * n;
-    hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.W + (size_t)i0 * n, r.W + (size_t)(i0 + m) * n, w);
+    // (a tree record: the recorded increments themselves, no path is read)
+    const float* wk = r.tree ? r.dw_of(k, n) : w;
+    const float* zk = r.tree && r.which == 2 ? r.dz_of(k, n) : z;
+    if (!r.tree) hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.W + (size_t)i0 * n, r.W + (size_t)(i0 + m) * n, w);
     if (r.which == 1) {
-      if ((rc = sde_rkmil_step_sweep(s, u, w, B, t, dt, dx, v, gpf, gpg, dp_drift, dp_diff))) return rc;
+      if ((rc = sde_rkmil_step_sweep(s, u, wk, B, t, dt, dx, v, gpf, gpg, dp_drift, dp_diff))) return rc;
     } else {
-      hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.Z + (size_t)i0 * n, r.Z + (size_t)(i0 + m) * n, z);
-      if ((rc = sde_sri_step_backward_core(s, &r.tab, u, w, z, B, t, dt, r.o.abstol, r.o.reltol, r.o.delta, dx, 0.f, dx, dp_drift, dp_diff,
+      if (!r.tree) hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.Z + (size_t)i0 * n, r.Z + (size_t)(i0 + m) * n, z);
+      if ((rc = sde_sri_step_backward_core(s, &r.tab, u, wk, zk, B, t, dt, r.o.abstol, r.o.reltol, r.o.delta, dx, 0.f, dx, dp_drift, dp_diff,
                                            nullptr, r.tmp))) return rc;
     }
     for (int j = 0; j < nseries; ++j)
@@ -632,11 +662,20 @@ int sde_node_sweep_alg_fused(lrnde_sde* s, SdeNodeRecord& r, int B, const float*
   a.u1 = r.u1; a.dW1 = r.dWloc; a.un1 = r.tmp; a.dt1 = r.dt_loc; a.eest = r.ee_loc;
   a.abstol = r.o.abstol; a.reltol = r.o.reltol; a.delta = r.o.delta;
   q.Z = r.Z; q.dZ1 = r.dZloc;
+  if (r.tree) {   // the DIRECT instantiations: step k's increments are slot k of the record (the staged pairs stay (i, m))
+    a.W = r.rec_dw; q.Z = r.which == 2 ? r.rec_dz.get() : nullptr;
+  }
   if (r.which == 2) q.T = r.tab;
   const size_t sm = sba_smem_bytes(D, H, r.which);   // (the sweep also has 4 KB of static LDS for the series table)
   const bool reg = r.mode != LRNDE_MODE_NONE && w_reg != 0.0f;
   const dim3 gred((Ptot + 31) / 32);
-  if (r.which == 1) {
+  if (r.tree && r.which == 1) {
+    SDE_LDS_LIMIT(c, (k_sde_alg_bwd_fused<1, true>), sm);
+    hipLaunchKernelGGL((k_sde_alg_bwd_fused<1, true>), dim3(nwg), dim3(SBF_NT), sm, c->stream, q);
+  } else if (r.tree) {
+    SDE_LDS_LIMIT(c, (k_sde_alg_bwd_fused<2, true>), sm);
+    hipLaunchKernelGGL((k_sde_alg_bwd_fused<2, true>), dim3(nwg), dim3(SBF_NT), sm, c->stream, q);
+  } else if (r.which == 1) {
     SDE_LDS_LIMIT(c, k_sde_alg_bwd_fused<1>, sm);
     hipLaunchKernelGGL(k_sde_alg_bwd_fused<1>, dim3(nwg), dim3(SBF_NT), sm, c->stream, q);
   } else {
@@ -718,7 +757,8 @@ int lrnde_sde_node_backward_recorded(lrnde_sde* s, int32_t B, const float* du_se
     const int i0 = r.im[k].x, m = r.im[k].y;
     const float t = r.t0 + (float)i0 * r.h, dt = (float)m * r.h;
     const float* u = (k == 0) ? r.x : r.rec_u + (size_t)(k - 1) * n;
-    hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.W + (size_t)i0 * n, r.W + (size_t)(i0 + m) * n, w);
+    if (r.tree) w = const_cast<float*>(r.dw_of(k, n));   // (read only below: the recorded increments themselves)
+    else hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, r.W + (size_t)i0 * n, r.W + (size_t)(i0 + m) * n, w);
     if ((rc = lrnde_rhs(c, u, t, B, du1))) return rc;
     if ((rc = lrnde_rhs(cg, u, t, B, L))) return rc;
     hipLaunchKernelGGL(k_sdeb_seed, dim3(nb), dim3(256), 0, c->stream, n, u, (const float*)du1, (const float*)L, (const float*)w, (const float*)dx, dt, tmp, fb2, gb2);

@@ -130,11 +130,12 @@ class SdeHandle:
 
 
     def solve_adaptive(self, u0, W, t0, t1, abstol, reltol, delta=1.0 / 6.0, dt0=None, gamma=0.9, qmin=0.2, qmax=1.125,
-                       beta1=7.0 / 50.0, beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None):
+                       beta1=7.0 / 50.0, beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, nfine=None):
         """adaptive solve on the caller's Brownian path W ((nfine+1, B, D), W[0] = 0, uniform grid over (t0, t1)):
         dict(u_end, stats, trace) — steps are whole grid intervals, EEst drives a PI controller (lrnde.h).  solver: "EulerHeun",
-        "RKMil" or "SRI" (with tableau= and the second path path_z=, same shape as W)"""
-        nfine = int(W.shape[0]) - 1
+        "RKMil" or "SRI" (with tableau= and the second path path_z=, same shape as W).  After `set_path_tree`: W=None with
+        nfine= (a power of two), the path is the handle's virtual tree"""
+        nfine = self._nfine_of(W, nfine)
         B = u0.numel() // self.D
         o = L.SdeAdaptOpts(float(abstol), float(reltol), float(delta), float((t1 - t0) / nfine if dt0 is None else dt0),
                            float(gamma), float(qmin), float(qmax), float(beta1), float(beta2), int(maxiters))
@@ -144,18 +145,73 @@ class SdeHandle:
         tr = (L.TraceRow * ntr)()
         which = _which(solver)
         if which == 0:
-            self._chk(L.lib.lrnde_sde_solve_adaptive(self._h, _dev_ptr(u0, "u0", self.D), _dev_ptr(W.contiguous(), "W"), nfine, B,
+            self._chk(L.lib.lrnde_sde_solve_adaptive(self._h, _dev_ptr(u0, "u0", self.D), self._path_ptr(W, "W"), nfine, B,
                                                      float(t0), float(t1), C.byref(o), _dev_ptr(u_end, "u_end"), C.byref(st), tr, ntr))
         else:
             tab = None if tableau is None else C.byref(_sri_tab(tableau))
             Z = None if path_z is None else _dev_ptr(path_z.contiguous(), "path_z")
-            self._chk(L.lib.lrnde_sde_solve_adaptive_alg(self._h, _dev_ptr(u0, "u0", self.D), _dev_ptr(W.contiguous(), "W"), nfine, B,
+            self._chk(L.lib.lrnde_sde_solve_adaptive_alg(self._h, _dev_ptr(u0, "u0", self.D), self._path_ptr(W, "W"), nfine, B,
                                                          float(t0), float(t1), C.byref(o), _dev_ptr(u_end, "u_end"), C.byref(st), tr, ntr,
                                                          which, tab, Z))
         nt = st.naccept + st.nreject
         trace = np.array([(tr[i].t, tr[i].dt, tr[i].eest, tr[i].accepted) for i in range(nt)],
                          dtype=[("t", "f4"), ("dt", "f4"), ("eest", "f4"), ("accepted", "i4")])
         return dict(u_end=u_end, stats=st.asdict(), trace=trace)
+
+    @staticmethod
+    def _nfine_of(W, nfine):
+        if W is not None:
+            return int(W.shape[0]) - 1
+        if nfine is None:
+            raise ValueError("W=None (the path tree, after set_path_tree) needs nfine=")
+        return int(nfine)
+
+    @staticmethod
+    def _series_cap(sv, nfine, maxiters, mode, tree):
+        """states the series buffer of a recorded forward starts with.  :biased without a saveat saves every accepted step: at most
+        min(nfine, maxiters) of them — never a grid-sized buffer.  On the path tree (a grid of up to 2^20 intervals, of which a solve
+        takes few) the buffer starts at 64 steps; a forward whose series does not fit says how many states it has
+        (LRNDE_CAPACITY) and is run again with exactly that many — the same path, the same bits"""
+        every = min(int(nfine), max(int(maxiters), 1)) + 1 if (mode == "biased" and not sv.size) else 0
+        return int(sv.size) + 3 + (min(every, 65) if tree else every)
+
+    def _run_series(self, cap, shape, device, ns, call):
+        """allocate the (cap,) + shape series and run call(us, ts, cap) -> status; a series that does not fit (LRNDE_CAPACITY, ns
+        says how many states there are) is run once more with exactly ns states.  Returns (us, ts)"""
+        for _ in range(2):
+            us = torch.empty((cap,) + tuple(shape), dtype=torch.float32, device=device)
+            ts = np.empty(cap, dtype=np.float32)
+            rc = call(us, ts, cap)
+            if rc == 5 and int(ns.value) > cap:   # LRNDE_CAPACITY
+                cap = int(ns.value)
+                continue
+            break
+        self._chk(rc)
+        return us, ts
+
+    @staticmethod
+    def _path_ptr(W, name):
+        return None if W is None else _dev_ptr(W.contiguous(), name)
+
+    # ---- the virtual Brownian tree (lrnde_sde_set_path_tree / lrnde_sde_tree_path; csrc/lrnde_sde_tree.hpp) ----
+    def set_path_tree(self, seed):
+        """from now on the adaptive calls of this handle ignore W / path_z (pass None and nfine=, a power of two <= 2^20) and take
+        the path from the tree of `seed`: W[k] is a function of (seed, column, k) — no (nfine+1, B, D) array exists"""
+        self._chk(L.lib.lrnde_sde_set_path_tree(self._h, 1, int(seed) & (2 ** 64 - 1)))
+
+    def clear_path_tree(self):
+        """back to the caller's arrays (the default)"""
+        self._chk(L.lib.lrnde_sde_set_path_tree(self._h, 0, 0))
+
+    def tree_path(self, seed, stream, levels, B, t0, t2):
+        """the tree's whole array (2^levels + 1, B, D) for the span (t0, t2): stream 6 is W, 7 the SRI solve's Z"""
+        levels = int(levels)
+        if not 0 <= levels <= 20:
+            raise ValueError("levels must lie in 0..20")
+        out = torch.empty(((1 << levels) + 1, int(B), self.D), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._chk(L.lib.lrnde_sde_tree_path(self._h, int(seed) & (2 ** 64 - 1), int(stream), levels, int(B), float(np.float32(t0)),
+                                            float(np.float32(t2)), C.c_void_p(out.data_ptr())))
+        return out
 
     SOLVE_LOOPS = ("host", "device", "device-persistent")
 
@@ -241,21 +297,19 @@ class SdeHandle:
 
     def model_forward_record_ce(self, x, pd, W, t0, t2, abstol, reltol, pc, K, labels, mode="unbiased", t1_or_rand=0.5, z_local=None,
                                 saveat=(), save_start=-1, delta=1.0 / 6.0, dt0=0.0, gamma=0.9, qmin=0.2, qmax=1.125, beta1=7.0 / 50.0,
-                                beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, z_local2=None):
+                                beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, z_local2=None, nfine=None):
         """downsample -> `node_forward_record` -> head on sol.u[end] in one call with one wait (lrnde_sde_model_forward_record_ce):
         the layer's dict plus loss, logits, dpc; keeps the record for one `model_backward_recorded`"""
         B, Din = int(x.shape[0]), int(x.shape[1])
         if pd.numel() != self.D * (Din + 1):
             raise ValueError(f"downsample parameters must have {self.D * (Din + 1)} entries")
         self._head_args(B, pc, K, labels)
-        nfine = int(W.shape[0]) - 1
-        W = W.contiguous()
+        nfine = self._nfine_of(W, nfine)   # (W=None with nfine=: the path tree, after set_path_tree)
+        W = None if W is None else W.contiguous()
         sv = np.ascontiguousarray(saveat, dtype=np.float32)
         o = L.SdeAdaptOpts(float(abstol), float(reltol), float(delta), float(dt0), float(gamma), float(qmin), float(qmax),
                            float(beta1), float(beta2), int(maxiters))
-        cap = int(sv.size) + 3 + (nfine + 1 if (mode == "biased" and not sv.size) else 0)
-        us = torch.empty((cap, B, self.D), dtype=torch.float32, device=x.device)
-        ts = np.empty(cap, dtype=np.float32)
+        cap = self._series_cap(sv, nfine, maxiters, mode, W is None)
         ns, reg, nf, ng, st, t1u, loss = C.c_int32(), C.c_float(), C.c_int32(), C.c_int32(), L.Stats(), C.c_float(), C.c_float()
         logits = torch.empty((B, K), dtype=torch.float32, device=x.device)
         dpc = torch.empty_like(pc)
@@ -263,8 +317,8 @@ class SdeHandle:
         path_z = None if path_z is None else path_z.contiguous()
         z_local2 = None if z_local2 is None else z_local2.contiguous()
         which = _which(solver)
-        self._chk(L.lib.lrnde_sde_model_forward_record_ce(
-            self._h, _dev_ptr(x, "x"), Din, _dev_ptr(pd, "pd"), _dev_ptr(W, "W"), nfine, B, float(t0), float(t2), C.byref(o), L.MODE[mode],
+        us, ts = self._run_series(cap, (B, self.D), x.device, ns, lambda us, ts, cap: L.lib.lrnde_sde_model_forward_record_ce(
+            self._h, _dev_ptr(x, "x"), Din, _dev_ptr(pd, "pd"), self._path_ptr(W, "W"), nfine, B, float(t0), float(t2), C.byref(o), L.MODE[mode],
             float(t1_or_rand), None if z_local is None else _dev_ptr(z_local, "z_local", self.D), int(save_start),
             sv.ctypes.data_as(C.POINTER(C.c_float)) if sv.size else None, int(sv.size), C.c_void_p(us.data_ptr()),
             ts.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns), C.byref(reg), C.byref(nf), C.byref(ng), C.byref(st), C.byref(t1u),
@@ -294,36 +348,37 @@ class SdeHandle:
 
     def node_forward_record(self, x, W, t0, t2, abstol, reltol, mode="unbiased", t1_or_rand=0.5, z_local=None, saveat=(),
                             save_start=-1, delta=1.0 / 6.0, dt0=0.0, gamma=0.9, qmin=0.2, qmax=1.125, beta1=7.0 / 50.0,
-                            beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, z_local2=None):
+                            beta2=2.0 / 25.0, maxiters=10000, solver="EulerHeun", tableau=None, path_z=None, z_local2=None, nfine=None):
         """the NeuralDSDE layer forward (lrnde_sde_node_forward_record[_alg]): adaptive solve on the path W ((nfine+1, B, D),
         W[0] = 0), sol.u / sol.t as the layer's caller sees them, reg_val of the local step; keeps the record for one
         `node_backward_recorded`.  dt0 = 0: automatic initial dt.  solver: "EulerHeun", "RKMil" or "SRI" (with tableau=, the
-        second path path_z= and the local step's second draw z_local2=)."""
-        nfine = int(W.shape[0]) - 1
+        second path path_z= and the local step's second draw z_local2=).  After `set_path_tree`: W=None (and path_z=None) with nfine=."""
+        nfine = self._nfine_of(W, nfine)
         B = x.numel() // self.D
-        W = W.contiguous()
+        W = None if W is None else W.contiguous()
         sv = np.ascontiguousarray(saveat, dtype=np.float32)
         o = L.SdeAdaptOpts(float(abstol), float(reltol), float(delta), float(dt0), float(gamma), float(qmin), float(qmax),
                            float(beta1), float(beta2), int(maxiters))
-        cap = int(sv.size) + 3 + (nfine + 1 if (mode == "biased" and not sv.size) else 0)
-        us = torch.empty((cap,) + tuple(x.shape), dtype=torch.float32, device=x.device)
-        ts = np.empty(cap, dtype=np.float32)
+        cap = self._series_cap(sv, nfine, maxiters, mode, W is None)
         ns, reg, nf, ng, st, t1u = C.c_int32(), C.c_float(), C.c_int32(), C.c_int32(), L.Stats(), C.c_float()
         if z_local is not None:
             z_local = z_local.contiguous()
-        args = (self._h, _dev_ptr(x, "x", self.D), _dev_ptr(W, "W"), nfine, B, float(t0), float(t2), C.byref(o), L.MODE[mode],
-                float(t1_or_rand), None if z_local is None else _dev_ptr(z_local, "z_local", self.D), int(save_start),
-                sv.ctypes.data_as(C.POINTER(C.c_float)) if sv.size else None, int(sv.size), C.c_void_p(us.data_ptr()),
-                ts.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns), C.byref(reg), C.byref(nf), C.byref(ng), C.byref(st), C.byref(t1u))
         which = _which(solver)
-        if which == 0:
-            self._chk(L.lib.lrnde_sde_node_forward_record(*args))
-        else:
-            path_z = None if path_z is None else path_z.contiguous()
-            z_local2 = None if z_local2 is None else z_local2.contiguous()
-            self._chk(L.lib.lrnde_sde_node_forward_record_alg(
+        path_z = None if path_z is None else path_z.contiguous()
+        z_local2 = None if z_local2 is None else z_local2.contiguous()
+
+        def call(us, ts, cap):
+            args = (self._h, _dev_ptr(x, "x", self.D), self._path_ptr(W, "W"), nfine, B, float(t0), float(t2), C.byref(o), L.MODE[mode],
+                    float(t1_or_rand), None if z_local is None else _dev_ptr(z_local, "z_local", self.D), int(save_start),
+                    sv.ctypes.data_as(C.POINTER(C.c_float)) if sv.size else None, int(sv.size), C.c_void_p(us.data_ptr()),
+                    ts.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(ns), C.byref(reg), C.byref(nf), C.byref(ng), C.byref(st), C.byref(t1u))
+            if which == 0:
+                return L.lib.lrnde_sde_node_forward_record(*args)
+            return L.lib.lrnde_sde_node_forward_record_alg(
                 *args, which, None if tableau is None else C.byref(_sri_tab(tableau)),
-                None if path_z is None else _dev_ptr(path_z, "path_z"), None if z_local2 is None else _dev_ptr(z_local2, "z_local2", self.D)))
+                None if path_z is None else _dev_ptr(path_z, "path_z"), None if z_local2 is None else _dev_ptr(z_local2, "z_local2", self.D))
+
+        us, ts = self._run_series(cap, tuple(x.shape), x.device, ns, call)
         self._node_keep = (W, x, path_z)   # the record refers to the caller's path(s): keep them alive until the backward
         n = int(ns.value)
         return dict(u=us[:n], t=ts[:n].copy(), u_end=us[n - 1], reg_val=np.float32(reg.value), nfe_drift=int(nf.value),
@@ -408,16 +463,19 @@ class NeuralDSDE:
     draw z2, given as `path_z=` / `z_local2=` or drawn after W and z).
     noise_source="device": the noise is drawn on the device (SdeHandle.draw_noise) from one uint64 seed taken from st["rng"]
     before its other draws — streams 0 (path W), 1 (local-step z), 2 (fixed-grid dW), 3 (fixed-grid dZ), 4 (adaptive SRI: path
-    Z), 5 (adaptive SRI: local-step z2); arrays given explicitly still win."""
+    Z), 5 (adaptive SRI: local-step z2); arrays given explicitly still win.
+    noise_source="tree" (adaptive only, nfine a power of two <= 2^20): the same seed, but no path array at all — the solve queries
+    the virtual Brownian tree of the seed (streams 6: W, 7: SRI's Z; SdeHandle.set_path_tree), the record keeps the accepted
+    steps' increments for the pullback; z / z2 from streams 1 / 5 as with "device".  `path=` / `path_z=` still win."""
 
     def __init__(self, drift, diffusion, *, solver="EulerHeun", sensealg=None, tspan=(0.0, 1.0),
                  regularize="unbiased", maxiters=1000, nsteps=20, delta=1.0 / 6.0, tableau=None, adaptive=None, nfine=256,
                  dt0=0.0, noise_source="host", **kwargs):
         regularize = _sym(regularize)
         _check_valid_regularize(regularize)
-        if noise_source not in ("host", "device"):
-            raise ValueError("noise_source must be 'host' (numpy draws from st['rng']) or 'device' (lrnde_sde_draw_noise from a "
-                             "seed drawn from st['rng'])")
+        if noise_source not in ("host", "device", "tree"):
+            raise ValueError("noise_source must be 'host' (numpy draws from st['rng']), 'device' (lrnde_sde_draw_noise from a "
+                             "seed drawn from st['rng']) or 'tree' (the virtual Brownian tree of that seed: no path array)")
         self.noise_source = noise_source
         if solver in ("SRI", "FourStageSRI"):
             if tableau is None:
@@ -439,6 +497,11 @@ class NeuralDSDE:
         self.regularize, self.maxiters, self.nsteps, self.delta = regularize, int(maxiters), int(nsteps), float(delta)
         self.adaptive = (self.solver == "EulerHeun") if adaptive is None else bool(adaptive)
         self.nfine, self.dt0 = int(nfine), float(dt0)
+        if noise_source == "tree":
+            if not self.adaptive:
+                raise ValueError("noise_source='tree' is the adaptive solve's path source: adaptive must be true")
+            if self.nfine < 1 or self.nfine > 2 ** 20 or self.nfine & (self.nfine - 1):
+                raise ValueError(f"noise_source='tree' needs nfine = 2^L <= 2^20 (got {self.nfine})")
         self.kwargs = dict(kwargs)
         self._handle = None
         self._last_adaptive = None
@@ -473,6 +536,29 @@ class NeuralDSDE:
         shape = tuple(shape)
         t0, t2 = self.tspan
         rng = copy.deepcopy(st["rng"])
+        if self.noise_source == "tree":   # the seed where "device" takes it; z / z2 from its streams 1 / 5; the path is not drawn
+            seed = self._draw_seed(rng)
+            B = int(np.prod(shape)) // h.D
+            need_z = self.solver == "SRI"
+            if path is None and (path_z is None or not need_z):
+                h.set_path_tree(seed)          # no array: the solve queries the tree (node_forward_record: W=None, nfine=)
+            else:                              # an explicit array wins; the other path of an SRI solve is then the tree's array
+                h.clear_path_tree()
+                L2 = self.nfine.bit_length() - 1
+                if path is None:
+                    path = h.tree_path(seed, 6, L2, B, t0, t2).view((self.nfine + 1,) + shape)
+                if need_z and path_z is None:
+                    path_z = h.tree_path(seed, 7, L2, B, t0, t2).view((self.nfine + 1,) + shape)
+            if z_local is None:
+                z_local = h.draw_noise(seed, 1, 1, B, 1.0, False)[0].view(shape)
+            if need_z and z_local2 is None:
+                z_local2 = h.draw_noise(seed, 5, 1, B, 1.0, False)[0].view(shape)
+            if path is None:
+                mode = self.regularize if st["training"] else "none"
+                r01 = np.float32(rng.random(dtype=np.float32)) if mode != "none" else np.float32(0)
+                t1_or_rand = np.float32(r01 * (t2 - t0) + t0) if mode == "unbiased" else r01     # :92 / :114
+                self._last_path_z = None
+                return rng, None, z_local, None, z_local2, mode, t1_or_rand
         if self.noise_source == "device":   # W (stream 0) and z (stream 1) on the device; node_forward_record keeps W alive
             seed = self._draw_seed(rng)
             B = int(np.prod(shape)) // h.D
@@ -518,7 +604,8 @@ class NeuralDSDE:
         r = h.node_forward_record(x, path, t0, t2, abstol, reltol, mode=mode, t1_or_rand=float(t1_or_rand), z_local=z_local,
                                   saveat=() if saveat is None else saveat, save_start=int(self.kwargs.get("save_start", -1)),
                                   delta=self.delta, dt0=self.dt0, maxiters=self.maxiters, solver=self.solver,
-                                  tableau=self.tableau if self.solver == "SRI" else None, path_z=path_z, z_local2=z_local2)
+                                  tableau=self.tableau if self.solver == "SRI" else None, path_z=path_z, z_local2=z_local2,
+                                  nfine=self.nfine)
         self._last_adaptive = dict(nseries=int(r["u"].shape[0]), mode=mode)
         sol = ODESolution([r["u"][i] for i in range(r["u"].shape[0])], [np.float32(t) for t in r["t"]], r["nfe_drift"])
         sol.stats = r["stats"]

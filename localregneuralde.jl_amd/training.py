@@ -108,7 +108,7 @@ def run_sde_training_step(model, ps, st, x, labels, w_reg, path=None, z_local=No
                                    t1_or_rand=float(t1_or_rand), z_local=z_local, saveat=() if saveat is None else saveat,
                                    save_start=int(kw.get("save_start", -1)), delta=nsde.delta, dt0=nsde.dt0, maxiters=nsde.maxiters,
                                    solver=nsde.solver, tableau=nsde.tableau if nsde.solver == "SRI" else None, path_z=path_z,
-                                   z_local2=z_local2)
+                                   z_local2=z_local2, nfine=nsde.nfine)
     loss = np.float32(fw["loss"] + np.float32(w_reg) * fw["reg_val"])
     torch.cuda.synchronize()
     fwd_time = time.perf_counter() - tic
