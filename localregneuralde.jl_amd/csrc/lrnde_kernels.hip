@@ -2080,9 +2080,10 @@ int launch_step(lrnde_ctx* c, int B, const StepArgs& a, int j, bool spec = false
     const int nq = (B + QNB - 1) / QNB;
     // KT: real k-quads in the last Dense-2 stream block (lrnde_qtile.hpp); 1 for H = 97..100, else the generic form
     const bool kt1 = (c->desc.hidden_dim + 3) / 4 == (QSB2 - 1) * QSQ + 1;
-    // KT = 1 keeps the stage operands in registers (q_regops); the generic form adds the LDS buffer for them (both
-    // candidate (uprev, k1) pairs, k2..k6; one padded row group of slack)
-    const size_t smq = smem_q(c) + (q_regops(kt1 ? 1 : 4) ? 0 : (size_t)9 * c->m.KQ1p * 4 * 16 + 64 * 16 + 16);
+    // KT = 1 keeps the stage operands in registers (q_regops) and parks weight blocks behind the forward layout
+    // (QPARK); the generic form adds the LDS buffer for the operands (both candidate (uprev, k1) pairs, k2..k6; one
+    // padded row group of slack)
+    const size_t smq = smem_q(c) + (q_regops(kt1 ? 1 : 4) ? q_park_bytes(QPARK) : (size_t)9 * c->m.KQ1p * 4 * 16 + 64 * 16 + 16);
     if (kt1) {
       if (spec) hipLaunchKernelGGL((k_step_q<true, 1>), dim3(nq), dim3(QNT), smq, c->stream, a, j);
       else hipLaunchKernelGGL((k_step_q<false, 1>), dim3(nq), dim3(QNT), smq, c->stream, a, j);

@@ -73,7 +73,7 @@ __device__ __forceinline__ f32x4* q_extra_smem(const SmemQ& s) {
   const unsigned off = (unsigned)(reinterpret_cast<const char*>(s.bc + 1) - smem);
   return reinterpret_cast<f32x4*>(smem + ((off + 15u) & ~15u));
 }
-static size_t smem_bytes_q(int KQ1p, int KQ2p, int RG1, int RG2) {
+static constexpr size_t smem_bytes_q(int KQ1p, int KQ2p, int RG1, int RG2) {
   const size_t nseg1 = (size_t)((KQ1p + QSEG - 1) / QSEG);
   return ((size_t)KQ1p * 4 + (size_t)KQ2p * 4 + nseg1 * RG1 * 64) * 16 + 128 * (size_t)(RG1 + RG2) * 4 +
          QNW * 3 * sizeof(double) + sizeof(Bcast) + 16;
@@ -392,6 +392,32 @@ constexpr int QSB = QSB1 + QSB2;
 constexpr int QRING = LRNDE_QRING;   // ring slots; QRING - 1 blocks are in flight
 constexpr int QAHEAD = QRING - 1;
 constexpr int VRING = 3;             // ring of the VJP kernel's stream (lrnde_backward.hpp)
+// Parked stream blocks: bit B of the mask = the 8 fragments of stream block B (0..QSB-1) of every wave stay in LDS for the
+// whole launch of the register form of k_step_q (q_regops), filled once at its head (q_park_fill) and read back with
+// ds_read_b128 by all six f-evals, instead of six buffer loads through the CU's vector-memory address path.  The form
+// has the room since its stage operands left LDS: 16 KiB per wave (two blocks) behind the forward layout.  0 = nothing
+// is parked, the kernels are instruction for instruction the ones without the switch.
+// Default: the last Dense-1 block (6) and the last full Dense-2 block (12), the blocks whose MFMAs the late wave of each
+// SIMD waits for before the two barriers (DESIGN.md 4.1 "parked weight blocks", profiles/qpark; 0x81u, the first block
+// of each phase, was measured slower with the first form of the fill).
+#ifndef LRNDE_QPARK
+#define LRNDE_QPARK 0x1040u
+#endif
+constexpr unsigned QPARK = LRNDE_QPARK;
+__host__ __device__ constexpr int q_popcount(unsigned v) { int n = 0; for (; v; v &= v - 1) ++n; return n; }
+__host__ __device__ constexpr int q_park_nb(unsigned mask) { return q_popcount(mask & ((1u << QSB) - 1)); }
+// index of parked block B among the parked blocks / the P-th parked block
+__host__ __device__ constexpr int q_park_index(unsigned mask, int B) { return q_popcount(mask & ((1u << B) - 1)); }
+__host__ __device__ constexpr int q_park_block(unsigned mask, int P) {
+  for (int B = 0; B < QSB; ++B) if ((mask >> B) & 1u) { if (P == 0) return B; --P; }
+  return -1;
+}
+constexpr int QPARK_FRAG = QSQ * 2;  // fragments (one-KiB wave-loads) per block
+__host__ __device__ constexpr size_t q_park_bytes(unsigned mask) { return (size_t)QNW * q_park_nb(mask) * QPARK_FRAG * 1024; }
+static_assert((QPARK >> QSB) == 0, "LRNDE_QPARK is a mask over the QSB stream blocks of an f-eval");
+// the family's largest shape (D = 784: KQ1p = 196, KQ2p = 28, RG1 = 2, RG2 = 13) with the park region behind it
+static_assert(smem_bytes_q(7 * QSEG, QSEG, 2, 13) + q_park_bytes(QPARK) <= 160 * 1024,
+              "forward layout + park region exceed the 160 KiB of LDS of a CU: park fewer blocks");
 
 template <int I> struct IC { static constexpr int value = I; };
 template <int I0, int I1, class F> __device__ __forceinline__ void static_for(F&& f) {
@@ -404,6 +430,8 @@ struct StreamQ {
   int s1[2], s2[2];          // scalar byte offsets of the first quad of those row groups
   int kq2_real;              // ceil(H/4): Dense-2 quads at/after it are not fetched
   f32x4 ring[QRING][QSQ][2];
+  const f32x4* park;         // parked blocks (QPARK): this lane's quad of the wave's own fragment 0, in LDS; fragment f is
+                             // 64 quads (1 KiB) further on each.  Set by k_step_q only
 };
 
 __device__ __forceinline__ void q_barrier() {
@@ -436,14 +464,23 @@ __device__ __forceinline__ void q_stream_load(StreamQ& st) {
 // fetched with an out-of-range offset and return 0).  With KT < 4 the missing quads are neither loaded nor multiplied:
 // an out-of-range load still costs its slot in the SIMD's return path (tools/oor_probe.hip), and for H = 100 (25 real
 // quads) 3 of the 28 loads of every Dense-2 row group were of that kind.
-template <int B, int SLOT, int J, int KT = 4>
+// PARK = the mask of parked blocks (QPARK; 0 in every kernel but the register form of k_step_q): the two fragments of a
+// parked block come from the wave's own LDS region — what q_park_fill's same two buffer loads returned, lane for lane —
+// into the same ring registers at the same point of the interleave
+template <int B, int SLOT, int J, int KT = 4, unsigned PARK = 0>
 __device__ __forceinline__ void q_stream_load_quad(StreamQ& st) {
 #ifdef LRNDE_QABL_NOLOAD  // diagnostic ablation: no weight stream (results are meaningless)
   st.ring[SLOT][J][0] = f32x4{0.f, 0.f, 0.f, 0.f}; st.ring[SLOT][J][1] = f32x4{0.f, 0.f, 0.f, 0.f};
   asm volatile("" : "+v"(st.ring[SLOT][J][0]), "+v"(st.ring[SLOT][J][1]));
   return;
 #endif
-  if constexpr (B < QSB1) {
+  if constexpr (((PARK >> B) & 1u) != 0) {
+    if constexpr (B < QSB - 1 || J < KT) {
+      constexpr int f = (q_park_index(PARK, B) * QSQ + J) * 2;
+      st.ring[SLOT][J][0] = st.park[f * 64];
+      st.ring[SLOT][J][1] = st.park[(f + 1) * 64];
+    }
+  } else if constexpr (B < QSB1) {
     st.ring[SLOT][J][0] = wload(st.rs1, st.v1[0], st.s1[0] + (B * QSQ + J) * 1024);
     st.ring[SLOT][J][1] = wload(st.rs1, st.v1[1], st.s1[1] + (B * QSQ + J) * 1024);
   } else if constexpr (B < QSB - 1 || J < KT) {
@@ -484,7 +521,7 @@ __device__ __forceinline__ void stream_init_q(const ModelDev& m, StreamQ& st) {
 // queue behind the other waves' bursts before it could start its MFMAs (56.5 -> 53.0 us per step).  -DLRNDE_QBURST
 // builds the burst form.
 #ifndef LRNDE_QBURST
-#define LRNDE_QLOAD_QUAD(BB, SS, JJ) q_stream_load_quad<BB, SS, JJ, KT>(st)
+#define LRNDE_QLOAD_QUAD(BB, SS, JJ) q_stream_load_quad<BB, SS, JJ, KT, PARK>(st)
 #define LRNDE_QPIN() __builtin_amdgcn_sched_barrier(0)
 #else
 #define LRNDE_QLOAD_QUAD(BB, SS, JJ) do {} while (0)
@@ -497,7 +534,7 @@ __device__ __forceinline__ f32x4 qmfma(float a, float b, f32x4 c) { asm volatile
 #else
 __device__ __forceinline__ f32x4 qmfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 #endif
-template <class Epi, int SLOT0, int KT = 4>
+template <class Epi, int SLOT0, int KT = 4, unsigned PARK = 0>
 __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, StreamQ& st, float ts, const Epi& epi) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -781,6 +818,84 @@ __global__ __launch_bounds__(QNT) void k_init2_q(StepArgs a) {
   publish_partial(a, 3, a0, 0.0, 0.0);
 }
 
+// stream_init_q's per-lane offset (or out of range) and scalar byte offset of the first quad of row group c of the Dense-1
+// and Dense-2 streams, for any wave: the park fill (q_park_fill) issues other waves' loads.  (Its own function and not
+// a part of stream_init_q: hipcc compiled the shared form of it to other code in every kernel of the family, and the
+// kernels without a park stay instruction for instruction what they were.)
+struct QRowOff { int v1, s1, v2, s2; };
+__device__ __forceinline__ QRowOff q_row_off(const ModelDev& m, int wave, int lane, int c) {
+  const int voff = lane * 16;
+  const bool has1 = wave < q_nseg1(m);
+  QRowOff r;
+#ifdef LRNDE_X_FULLROWS
+  r.v1 = (has1 && c < m.RG1) ? voff : 0x7ffffff0;
+#else
+  r.v1 = (has1 && c < m.RG1 && c * 64 + lane < m.H) ? voff : 0x7ffffff0;
+#endif
+  r.s1 = (c * m.KQ1p + (has1 ? wave * QSEG : 0)) * 1024;
+  const int rb = wave * (QSEG * 4) + c * 64;
+  r.v2 = (has1 && (c == 0 || lane < QSEG * 4 - 64) && rb + lane < m.D) ? voff : 0x7ffffff0;
+  r.s2 = (has1 ? 2 * wave + c : 0) * m.KQ2p * 1024;
+  return r;
+}
+
+// The fill of the park region, by waves 1..6 at the head of k_step_q (wave 0 runs the controller prologue and gets nothing
+// added).  Fragment (P * QSQ + J) * 2 + c of a wave — quad J, row group c of its P-th parked block — lies at
+// park[(wave * NF + fragment) * 64 + lane].  A filling wave parks its own fragments with the very loads of its stream
+// (q_stream_load_quad into the ring slot that is still free at the head) and, per block, one or two of wave 0's eight
+// with wave 0's offsets (q_row_off): an out-of-range lane parks the zero the stream load returns.  Ten loads are in
+// flight per block; the addresses of the own fragments cost nothing, which matters: a first form that gave every load a
+// runtime (wave, fragment) spent 60 scalar instructions per load and 10 k cycles in the head.  The __syncthreads() at
+// the end of the head orders the writes before any parked read.
+//
+// fragment e (= quad e / 2, row group e % 2) of stream block B of wave 0, whose row offsets are ra (group 0), rb (group 1)
+template <int B>
+__device__ __forceinline__ f32x4 q_park_load0(const StreamQ& st, const QRowOff& ra, const QRowOff& rb, int e, bool on) {
+  const int J = e >> 1;
+  const bool c1 = (e & 1) != 0;
+  if constexpr (B < QSB1) {
+    return wload(st.rs1, on ? (c1 ? rb.v1 : ra.v1) : 0x7ffffff0, (c1 ? rb.s1 : ra.s1) + (B * QSQ + J) * 1024);
+  } else {
+    const int kq = (B - QSB1) * QSQ + J;
+    return wload(st.rs2, on && kq < st.kq2_real ? (c1 ? rb.v2 : ra.v2) : 0x7ffffff0, (c1 ? rb.s2 : ra.s2) + kq * 1024);
+  }
+}
+template <unsigned PARK, int KT, int P>
+__device__ __forceinline__ void q_park_fill_block(StreamQ& st, const QRowOff& ra, const QRowOff& rb, int fw, f32x4* own, f32x4* w0) {
+  if constexpr (P < q_park_nb(PARK)) {
+    constexpr int B = q_park_block(PARK, P), FREE = QRING - 1;
+    // wave 0's fragment e of this block: e = fw for every wave, and e = 6, 7 for two waves that rotate with P
+    const int e2 = QNW - 1 + fw - 2 * (P % 3);
+    const bool on2 = e2 >= QNW - 1 && e2 < QPARK_FRAG;
+    q_stream_load_quad<B, FREE, 0, KT, 0>(st);
+    q_stream_load_quad<B, FREE, 1, KT, 0>(st);
+    q_stream_load_quad<B, FREE, 2, KT, 0>(st);
+    q_stream_load_quad<B, FREE, 3, KT, 0>(st);
+    const f32x4 va = q_park_load0<B>(st, ra, rb, fw, true), vb = q_park_load0<B>(st, ra, rb, on2 ? e2 : 0, on2);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int J = 0; J < QSQ; ++J) {
+      if (B < QSB - 1 || J < KT) {  // (the quads the stream itself never loads stay unwritten and unread)
+        own[((P * QSQ + J) * 2) * 64] = st.ring[FREE][J][0];
+        own[((P * QSQ + J) * 2 + 1) * 64] = st.ring[FREE][J][1];
+      }
+    }
+    w0[(P * QPARK_FRAG + fw) * 64] = va;
+    if (on2) w0[(P * QPARK_FRAG + e2) * 64] = vb;
+    __builtin_amdgcn_sched_barrier(0);
+    q_park_fill_block<PARK, KT, P + 1>(st, ra, rb, fw, own, w0);
+  }
+}
+template <unsigned PARK, int KT>
+__device__ __forceinline__ void q_park_fill(const ModelDev& m, StreamQ& st, f32x4* park) {
+  static_assert(QSQ == 4, "q_park_fill_block issues the four quads of a block by name");
+  constexpr int NF = q_park_nb(PARK) * QPARK_FRAG;
+  const int lane = threadIdx.x & 63;
+  const int fw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) - 1;  // 0..5
+  const QRowOff ra = q_row_off(m, 0, lane, 0), rb = q_row_off(m, 0, lane, 1);
+  q_park_fill_block<PARK, KT, 0>(st, ra, rb, fw, park + (size_t)(fw + 1) * (NF * 64) + lane, park + lane);
+}
+
 // one attempted Tsit5 step, 4 columns per workgroup (same flow as k_step's fused path)
 template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(StepArgs a, int j) {
   STAMP(9);
@@ -817,6 +932,11 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
   constexpr bool REGS = q_regops(KT);
   f32x4* kl = REGS ? nullptr : q_extra_smem(s);  // LDS form: [9][KL]: 0,1 = pair 0; 2,3 = pair 1; 4..8 = k2..k6
   const int KL = a.m.KQ1p * 4;
+  constexpr bool PARKED = REGS && QPARK != 0;
+  if constexpr (PARKED) {  // the wave's own 16 KiB of the park region, behind the forward layout
+    constexpr int NF = q_park_nb(QPARK) * QPARK_FRAG;
+    fc.park = q_extra_smem(s) + (size_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (NF * 64) + (threadIdx.x & 63);
+  }
   if (threadIdx.x < 64) {
     if constexpr (REGS) preload();  // in flight while the wave decides
     step_prologue(a, j, s.bc);
@@ -826,6 +946,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     smem_init_q<true>(a.m, s);
     if constexpr (REGS) {
       preload();
+      if constexpr (PARKED) q_park_fill<QPARK, KT>(a.m, fc, q_extra_smem(s));
     } else {  // LDS form: the six waves load both pairs of the whole tile into kl, ordered by the barrier below
 #ifndef LRNDE_NO_PRELOAD
     constexpr int NTH = QNT - 64;
@@ -993,7 +1114,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
       EpiStageQ<S> e;                                                                   \
       e.io = io; e.off_out = off_out; e.off_x = off_x;                                  \
       e.dt = dt; e.xl = s.xl; e.R = &R; e.store_k = bc.store_k;                         \
-      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT>(a.m, s, fc, (TS), e);         \
+      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT, QPARK>(a.m, s, fc, (TS), e);  \
     } else {                                                                            \
       EpiStageQL<S> e;                                                                  \
       e.io = io; e.off_up = o_up; e.off_k[0] = o_k1;                                    \
@@ -1020,7 +1141,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
     ef.xl = s.xl; ef.R = &R;
     ef.rec = rec; ef.nstB = (int)(a.n_local * 4); ef.rsD = rsD;
-    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT>(a.m, s, fc, t + dt, ef);
+    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT, QPARK>(a.m, s, fc, t + dt, ef);
   } else {
     EpiFinalQL ef;
     ef.io = io; ef.off_up = o_up; ef.off_u = o_un; ef.off_k[0] = o_k1;
