@@ -56,6 +56,8 @@
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
               "header_status returns lrnde_status values");
+static_assert((int)lrnde::STEP_CAPACITY == (int)LRNDE_CAPACITY && (int)lrnde::STEP_DONE == (int)lrnde::ST_DONE &&
+              (int)lrnde::STEP_OK == (int)lrnde::ST_RUNNING, "sde_grid_update leaves a control block's status");
 
 namespace {
 
@@ -3246,6 +3248,25 @@ struct lrnde_sde {
   // (lrnde_sde_tree.hpp) and ignore their W / Z arguments
   bool tree_on = false; uint64_t tree_seed = 0;
 };
+// One adaptive solve, as sde_solve_adaptive_impl and sde_adaptive_device take it: the problem (Z, tab: the SRI step's second
+// path and tableau; with the path tree on, W and Z are ignored), the outputs (u_end may be NULL: the layer reads the end state
+// from its record) and, for the layer's recorded forward, the dense record of the accepted steps.
+struct SdeRecSink {
+  float* u = nullptr;         // device, cap x B x D: the end state of accepted step k in slot k (NULL: a plain solve, no record)
+  int2* im_dev = nullptr;     // device: its (start index, length) on the path's grid ...
+  int2* im_host = nullptr;    // ... and where the host gets them
+  int cap = 0;
+  float* dw = nullptr; float* dz = nullptr;   // a record on the path tree: the accepted steps' increments beside u (dz: SRI)
+};
+struct SdeSolveReq {
+  const float* u0 = nullptr; const float* W = nullptr; const float* Z = nullptr;
+  int32_t nfine = 0, B = 0; float t0 = 0.f, t1 = 0.f;
+  const lrnde_sde_adapt_opts* opts = nullptr;
+  int which = 0; const lrnde_sri_tableau* tab = nullptr;
+  float* u_end = nullptr; lrnde_stats* st = nullptr; lrnde_trace_row* trace_host = nullptr; int32_t cap_trace = 0;
+  SdeRecSink rec;
+  const float* dt0_dev = nullptr;   // sde_init_dt_dev's result: its closing launch has initialised the control block from it
+};
 // the path source of one adaptive call on this handle: the tree of the handle's seed at L = log2(nfine) over (t0, t1), or off
 static int sde_tree_source(lrnde_sde* s, int32_t nfine, float t0, float t1, SdeTree& T) {
   memset(&T, 0, sizeof(T));
@@ -3464,25 +3485,11 @@ __global__ void k_sde_dw(size_t n, const float* Wlo, const float* Whi, float* dW
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dW[i] = Whi[i] - Wlo[i];
 }
 
-__global__ void k_sde_ctl_init(SdeCtl* ctl, int m0, float dtc0) {
+// a fresh control block from the caller's dt0, or (dt_dev) from the initial dt on the device (sde_init_dt_dev's result): the
+// rerun of a solve whose control block k_sde_initdt_fin had initialised
+__global__ void k_sde_ctl_init(SdeCtl* ctl, const float* dt_dev, float dt0, float h, int nfine) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  SdeCtl c;
-  c.status = ST_RUNNING; c.i = 0; c.m = m0; c.cur = 0; c.naccept = 0; c.nreject = 0; c.iters = 1; c.nf = 0;
-  c.qold = QOLDINIT; c.eest_last = 0.f; c.dtc = dtc0;
-  *ctl = c;
-}
-
-// ... the initial dt read from the device (sde_init_dt_dev's result), quantised to the path's grid as the host does: the rerun of
-// a solve whose control block k_sde_initdt_fin had initialised
-__global__ void k_sde_ctl_init_dtdev(SdeCtl* ctl, const float* dt_dev, float h, int nfine) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const float dt0 = *dt_dev;
-  int m0 = (int)(dt0 / h); if (m0 < 1) m0 = 1;
-  if (m0 > nfine) m0 = nfine;
-  SdeCtl c;
-  c.status = ST_RUNNING; c.i = 0; c.m = m0; c.cur = 0; c.naccept = 0; c.nreject = 0; c.iters = 1; c.nf = 0;
-  c.qold = QOLDINIT; c.eest_last = 0.f; c.dtc = dt0;
-  *ctl = c;
+  *ctl = sde_grid_begin(dt_dev ? *dt_dev : dt0, h, nfine);
 }
 // the end state of a device-controlled solve (the control block says which of the two buffers holds it) -> out
 __global__ void k_sde_pick_end(size_t n, const SdeCtl* ctl, const float* ua, const float* ub, float* out) {
@@ -3490,11 +3497,17 @@ __global__ void k_sde_pick_end(size_t n, const SdeCtl* ctl, const float* ua, con
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = src[i];
 }
 
+// what a finished solve's control block says, as the caller's lrnde_stats
+static void sde_stats_from(const SdeCtl& fin, float t0, float h, lrnde_stats* st) {
+  st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iters; st->nf = fin.nf; st->eest_last = fin.eest_last;
+  st->t_final = t0 + (float)fin.i * h; st->dt_final = (float)fin.m * h;
+  st->retcode = status_retcode(fin.status);
+}
+
 // lrnde_sde_solve_adaptive on the one-launch kernel's shape: the controller runs in the step kernel's footer (SdeCtl,
 // lrnde_sde_fast.hpp), the host only keeps launches enqueued and watches a pinned progress word — one launch per attempted
 // step, no synchronisation inside the solve (the host-controlled loop below paid one per step: ~45 us for a 10-us step).
-// rec_u / rec_im / rec_cap: the layer's dense record of the accepted steps (device; NULL / 0 for a plain solve)
-// the device-controlled loop's control block and progress word.  The block heads one allocation with room for the record's
+// The device-controlled loop's control block and progress word.  The block heads one allocation with room for the record's
 // (start, length) pairs behind it (64 bytes in): control block and pairs come home in ONE copy.  rec_cap: pairs to hold
 // (a call that grows the allocation must come before anything initialises the block: the layer calls it ahead of its initial dt).
 static int sde_adaptive_prepare(lrnde_sde* s, int rec_cap = 0) {
@@ -3512,46 +3525,42 @@ static int sde_adaptive_prepare(lrnde_sde* s, int rec_cap = 0) {
   }
   return LRNDE_OK;
 }
-static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
-                               const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
-                               int32_t cap_trace, float* ua, float* ub, float* rec_u = nullptr, int2* rec_im = nullptr,
-                               int rec_cap = 0, int2* rec_im_host = nullptr, const float* dt0_dev = nullptr, bool no_persist = false,
-                               int which = 0, const lrnde_sri_tableau* tab = nullptr, const float* Z = nullptr,
-                               const SdeTree* tree = nullptr) {
+// ua, ub: the solve's two state buffers; tree: the resolved path source (off: the request's W and Z); no_persist: the
+// launch-per-attempt loop (the rerun of a persistent launch whose barrier gave up)
+static int sde_adaptive_device(lrnde_sde* s, const SdeSolveReq& q, float* ua, float* ub, const SdeTree& tree, bool no_persist) {
+  const int32_t nfine = q.nfine, B = q.B, cap_trace = q.cap_trace, which = q.which, rec_cap = q.rec.cap; const float t0 = q.t0;
+  const lrnde_sde_adapt_opts* o = q.opts; lrnde_stats* st = q.st; lrnde_trace_row* trace_host = q.trace_host; int2* rec_im = q.rec.im_dev;
   lrnde_ctx* c = s->drift;
   if (which != 0) no_persist = true;   // (the Milstein and SRI steps have the launch-per-attempt form only: lrnde_sde_mil_fast.hpp, lrnde_sde_sri_fast.hpp)
   const size_t n = (size_t)B * c->desc.state_dim;
-  const bool pairs_home = rec_im_host && rec_im && rec_cap > 0;   // the layer's record: its pairs live behind the control block
+  const bool pairs_home = q.rec.im_host && rec_im && rec_cap > 0;   // the layer's record: its pairs live behind the control block
   int rc0 = sde_adaptive_prepare(s, pairs_home ? rec_cap : 0);
   if (rc0) return rc0;
   if (pairs_home) rec_im = reinterpret_cast<int2*>(s->ad_ctl + 64);
   if (trace_host) HIPCHK(c, s->ad_trace.grow(std::max(cap_trace, 0)));
   if (!s->arrive) { HIPCHK(c, s->arrive.once(1)); HIPCHK(c, hipMemsetAsync(s->arrive, 0, sizeof(int), c->stream)); }
-  const float h = (t1 - t0) / (float)nfine;
-  int m0 = (int)(o->dt0 / h); if (m0 < 1) m0 = 1;
-  if (m0 > nfine) m0 = nfine;
+  const float h = (q.t1 - t0) / (float)nfine;
   if (1 > o->maxiters) { st->iters = 1; st->retcode = LRNDE_MAXITERS; return fail(c, LRNDE_MAXITERS, "adaptive SDE solve stopped with retcode %d at t=%g", LRNDE_MAXITERS, (double)t0); }
-  HIPCHK(c, hipMemcpyAsync(ua, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  if (dt0_dev && no_persist) hipLaunchKernelGGL(k_sde_ctl_init_dtdev, dim3(1), dim3(1), 0, c->stream, s->ctl(), dt0_dev, h, nfine);  // (the rerun)
-  else if (!dt0_dev)   // (dt0_dev: sde_init_dt_dev's closing launch has initialised the control block from its dt)
-    hipLaunchKernelGGL(k_sde_ctl_init, dim3(1), dim3(1), 0, c->stream, s->ctl(), m0, o->dt0);
+  HIPCHK(c, hipMemcpyAsync(ua, q.u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+  if (!q.dt0_dev || no_persist)   // (dt0_dev: sde_init_dt_dev's closing launch has initialised the control block from its dt — but not the rerun's)
+    hipLaunchKernelGGL(k_sde_ctl_init, dim3(1), dim3(1), 0, c->stream, s->ctl(), q.dt0_dev, o->dt0, h, nfine);
   volatile unsigned long long* pw = s->ad_prog;
   *pw = 0ull;
   StepArgs a{};
   fill_args(c, a, B, NB);
   SdeFastArgs f{};
   sde_fast_args(s, f);
-  f.rec_u = rec_u; f.rec_im = rec_im; f.rec_cap = rec_cap;
+  f.rec_u = q.rec.u; f.rec_im = rec_im; f.rec_cap = rec_cap;
   f.B = B; f.abstol = o->abstol; f.reltol = o->reltol; f.delta = o->delta;
   f.part = c->part + (size_t)a.nwg_global * PSTRIDE;
   f.n_norm = a.n_global;
   f.arrive = s->arrive;
-  f.ctl = s->ctl(); f.Wpath = W; f.ua = ua; f.ub = ub; f.nfine = nfine; f.t0 = t0; f.h = h;
+  f.ctl = s->ctl(); f.Wpath = q.W; f.ua = ua; f.ub = ub; f.nfine = nfine; f.t0 = t0; f.h = h;
   f.gamma = o->gamma; f.qmin = o->qmin; f.qmax = o->qmax; f.beta1 = o->beta1; f.beta2 = o->beta2; f.maxiters = o->maxiters;
   f.trace = trace_host ? s->ad_trace : nullptr; f.cap_trace = trace_host ? cap_trace : 0;
   f.prog = s->ad_prog.dev();
-  if (which == 2) { f.Zpath = Z; f.tab = *tab; }
-  if (tree && tree->on) { f.tree = *tree; f.Wpath = nullptr; f.Zpath = nullptr; }   // (the TREE instantiations: no path pointer is read)
+  if (which == 2) { f.Zpath = q.Z; f.tab = *q.tab; }
+  if (tree.on) { f.tree = tree; f.Wpath = nullptr; f.Zpath = nullptr; }   // (the TREE instantiations: no path pointer is read)
   const int nwg = (B + NB - 1) / NB;
   // The whole solve as ONE cooperative launch (k_sde_eh_fast<DT, HT, true>: state and weights stay in registers, a grid barrier
   // per step) when every workgroup fits on the chip at once; LRNDE_SDE_NO_PERSIST=1, a launch the runtime refuses or more than
@@ -3599,9 +3608,9 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   // one synchronisation ends the solve: the control block, the end state (picked on the device) and the record's
   // (start, length) pairs are all enqueued before it
   HIPCHK(c, hipMemcpyAsync(s->ad_ctl_host, s->ad_ctl, 64 + (pairs_home ? sizeof(int2) * (size_t)rec_cap : 0), hipMemcpyDeviceToHost, c->stream));
-  if (u_end) {   // (the layer does not ask for it: the end state is its record's last slot)
+  if (q.u_end) {   // (the layer does not ask for it: the end state is its record's last slot)
     int nb = (int)((n + 255) / 256); if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(k_sde_pick_end, dim3(nb), dim3(256), 0, c->stream, n, (const SdeCtl*)s->ctl(), (const float*)ua, (const float*)ub, u_end);
+    hipLaunchKernelGGL(k_sde_pick_end, dim3(nb), dim3(256), 0, c->stream, n, (const SdeCtl*)s->ctl(), (const float*)ua, (const float*)ub, q.u_end);
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3609,12 +3618,10 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   s->info_kind = persisted ? 2 : 1;
   const SdeCtl fin = *reinterpret_cast<const SdeCtl*>(s->ad_ctl_host.get());
   if (persisted && plain && (fin.status == LRNDE_HIP_ERROR || fin.status == ST_RUNNING))   // the barrier gave up waiting (busy device): the loop
-    return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im, rec_cap, rec_im_host, dt0_dev, true, which, tab, Z, tree);
+    return sde_adaptive_device(s, q, ua, ub, tree, true);
   if (pairs_home && fin.naccept > 0)
-    memcpy(rec_im_host, s->ad_ctl_host + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
-  st->naccept = fin.naccept; st->nreject = fin.nreject; st->iters = fin.iters; st->nf = fin.nf; st->eest_last = fin.eest_last;
-  st->t_final = t0 + (float)fin.i * h; st->dt_final = (float)fin.m * h;
-  st->retcode = status_retcode(fin.status);
+    memcpy(q.rec.im_host, s->ad_ctl_host + 64, sizeof(int2) * (size_t)(fin.naccept < rec_cap ? fin.naccept : rec_cap));
+  sde_stats_from(fin, t0, h, st);
   if (trace_host) {
     int nt = fin.naccept + fin.nreject;
     if (nt > cap_trace) nt = cap_trace;
@@ -3624,19 +3631,83 @@ static int sde_adaptive_device(lrnde_sde* s, const float* u0, const float* W, in
   return LRNDE_OK;
 }
 
-// rec_u (device, rec_cap x B x D) / rec_im_dev (device) / rec_im_host (host): the dense record of the accepted steps —
-// end state, (start index, length) on the path's grid — for the layer's recorded forward; all NULL for a plain solve
-static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
-                                   const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
-                                   int32_t cap_trace, float* rec_u, int2* rec_im_dev, int2* rec_im_host, int rec_cap,
-                                   const float* dt0_dev = nullptr, int which = 0, const lrnde_sri_tableau* tab = nullptr,
-                                   const float* Z = nullptr, float* rec_dw = nullptr, float* rec_dz = nullptr);
 // the step kinds of the adaptive entry points: 0 Euler-Heun, 1 Milstein, 2 four-stage SRI (which needs its tableau and the
 // second Brownian path)
 static int sde_alg_check(lrnde_sde* s, int32_t which, const lrnde_sri_tableau* tab, const float* Z) {
   if (!s) return LRNDE_BADARG;
   if (which < 0 || which > 2) return fail(s->drift, LRNDE_BADARG, "which: 0 Euler-Heun, 1 Milstein, 2 SRI");
   if (which == 2 && (!tab || (!Z && !s->tree_on))) return fail(s->drift, LRNDE_BADARG, "the SRI step needs its tableau and the second Brownian path Z");
+  return LRNDE_OK;
+}
+static int sde_solve_adaptive_impl(lrnde_sde* s, const SdeSolveReq& q) {
+  const float* u0 = q.u0; const int32_t nfine = q.nfine, B = q.B, which = q.which; const float t0 = q.t0, t1 = q.t1;
+  const lrnde_sde_adapt_opts* o = q.opts; lrnde_stats* st = q.st;
+  // (the path tree: W and Z are ignored and may be NULL — the check sees u0 in W's place)
+  int rc = sde_check(s, u0, s && s->tree_on ? u0 : q.W, q.u_end ? q.u_end : u0, B, 1.0f);   // (u_end may be NULL from the layer: no end state asked for)
+  if (rc) return rc;
+  lrnde_ctx* c = s->drift;
+  if (!o || !st || nfine < 1 || !(t1 > t0)) return fail(c, LRNDE_BADARG, "bad arguments (nfine >= 1, t1 > t0)");
+  SdeTree tree{};
+  if ((rc = sde_tree_source(s, nfine, t0, t1, tree))) return rc;
+  tree.rec_dw = tree.on ? q.rec.dw : nullptr; tree.rec_dz = tree.on && which == 2 ? q.rec.dz : nullptr;
+  memset(st, 0, sizeof(*st));
+  const size_t n = (size_t)B * c->desc.state_dim;
+  HIPCHK(c, s->ad_ws.resize_exact(4 * n));
+  float *ua = s->ad_ws, *ub = s->ad_ws + n, *dW = s->ad_ws + 2 * n, *dZ = s->ad_ws + 3 * n;
+  // the controller on the device: Euler-Heun (k_sde_eh_fast), Milstein (k_sde_mil_fast) and SRI (k_sde_sri_fast) at the
+  // one-launch kernels' shape.  Everything outside that shape, and LRNDE_SDE_HOST_LOOP (diagnostic), runs the host-controlled loop below
+  if (sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP)) return sde_adaptive_device(s, q, ua, ub, tree, false);
+  s->info_kind = 0;
+  const int nfa = which == 2 ? 4 : (which == 1 ? 1 : 3);   // drift evaluations of one attempted step
+  HIPCHK(c, hipMemcpyAsync(ua, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+  const float h = (t1 - t0) / (float)nfine;
+  const SdeGrid grid = {{o->gamma, o->qmin, o->qmax, o->beta1, o->beta2}, h, nfine, o->maxiters};
+  // position i and step length m on the path's grid, the proposal as a real number, the counters: the device loops' control block
+  SdeCtl k = sde_grid_begin(o->dt0, h, nfine);
+  if (k.iters > o->maxiters) k.status = LRNDE_MAXITERS;
+  int nb = (int)((n + 255) / 256); if (nb > 1024) nb = 1024;
+  while (k.status == ST_RUNNING) {
+    const int i = k.i, m = k.m;
+    const float t = t0 + (float)i * h, dt = (float)m * h;
+    if (tree.on) hipLaunchKernelGGL(k_sde_dw_tree, dim3(nb), dim3(256), 0, c->stream, n, tree, TREE_STREAM_W, i, m, dW);
+    else hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, q.W + (size_t)i * n, q.W + (size_t)(i + m) * n, dW);
+    float eest = 0.f;
+    if (which == 2) {   // k_sri_chi / k_sri_stage / k_sri_final around the eight evaluations; the call ends in the attempt's synchronisation
+      if (tree.on) hipLaunchKernelGGL(k_sde_dw_tree, dim3(nb), dim3(256), 0, c->stream, n, tree, TREE_STREAM_Z, i, m, dZ);
+      else hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, q.Z + (size_t)i * n, q.Z + (size_t)(i + m) * n, dZ);
+      if ((rc = lrnde_sde_sri_step(s, q.tab, ua, dW, dZ, B, t, dt, o->abstol, o->reltol, o->delta, ub, &eest, nullptr))) return rc;
+    } else {
+      if ((rc = sde_step_enqueue(s, which, ua, dW, B, t, dt, o->abstol, o->reltol, o->delta, ub, c->ctrl_host))) return rc;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      eest = c->ctrl_host[0].eest_last;
+    }
+    ++s->info_launches; ++s->info_waits;   // (SRI: the step's launch sequence counts as one; its synchronisation is lrnde_sde_sri_step's)
+    // An accepted step that finds the record full: this loop stops BEFORE the controller counts it (naccept, i and m stay),
+    // sde_grid_update — the device loops' order — would count it first.  So the check stands here, and the update is told "no record".
+    if (q.rec.u && eest <= 1.0f && k.naccept >= q.rec.cap) { k.nf += nfa; k.eest_last = eest; k.status = LRNDE_CAPACITY; break; }
+    // PI controller on EEst (the form of SURVEY.md 3.5; StochasticDiffEq's constants are the caller's options)
+    const SdeVerdict v = sde_grid_update(k, eest, dt, pi_pow(0, k.qold, grid.pi.beta2), nfa, grid, -1);
+    if (q.trace_host && v.trace >= 0 && v.trace < q.cap_trace) {
+      lrnde_trace_row& r = q.trace_host[v.trace];
+      r.t = t; r.dt = dt; r.eest = eest; r.accepted = v.accepted;
+    }
+    if (v.accepted) {
+      if (q.rec.u) {
+        const int slot = k.naccept - 1;
+        HIPCHK(c, hipMemcpyAsync(q.rec.u + (size_t)slot * n, ub, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+        // (the tree: the accepted step's increments beside its end state — the backward reads them from there)
+        if (tree.rec_dw) HIPCHK(c, hipMemcpyAsync(tree.rec_dw + (size_t)slot * n, dW, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+        if (tree.rec_dz) HIPCHK(c, hipMemcpyAsync(tree.rec_dz + (size_t)slot * n, dZ, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+        q.rec.im_host[slot] = make_int2(i, m);
+      }
+      std::swap(ua, ub);
+    }
+  }
+  sde_stats_from(k, t0, h, st);
+  if (q.u_end) HIPCHK(c, hipMemcpyAsync(q.u_end, ua, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ++s->info_waits;
+  if (st->retcode != LRNDE_OK) return fail(c, st->retcode, "adaptive SDE solve stopped with retcode %d at t=%g", st->retcode, (double)st->t_final);
   return LRNDE_OK;
 }
 int lrnde_sde_solve_adaptive_alg(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
@@ -3646,103 +3717,15 @@ int lrnde_sde_solve_adaptive_alg(lrnde_sde* s, const float* u0, const float* W, 
   if (rc) return rc;
   if (!u_end) return fail(s->drift, LRNDE_BADARG, "null pointer");
   s->info_kind = s->info_launches = s->info_waits = 0;
-  return sde_solve_adaptive_impl(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, nullptr, nullptr, nullptr, 0, nullptr,
-                                 which, tab, Z);
+  SdeSolveReq q{};
+  q.u0 = u0; q.W = W; q.Z = Z; q.nfine = nfine; q.B = B; q.t0 = t0; q.t1 = t1; q.opts = o; q.which = which; q.tab = tab;
+  q.u_end = u_end; q.st = st; q.trace_host = trace_host; q.cap_trace = cap_trace;
+  return sde_solve_adaptive_impl(s, q);
 }
 int lrnde_sde_solve_adaptive(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
                              const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
                              int32_t cap_trace) {
   return lrnde_sde_solve_adaptive_alg(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, 0, nullptr, nullptr);
-}
-static int sde_solve_adaptive_impl(lrnde_sde* s, const float* u0, const float* W, int32_t nfine, int32_t B, float t0, float t1,
-                                   const lrnde_sde_adapt_opts* o, float* u_end, lrnde_stats* st, lrnde_trace_row* trace_host,
-                                   int32_t cap_trace, float* rec_u, int2* rec_im_dev, int2* rec_im_host, int rec_cap,
-                                   const float* dt0_dev, int which, const lrnde_sri_tableau* tab, const float* Z, float* rec_dw,
-                                   float* rec_dz) {
-  // (the path tree: W and Z are ignored and may be NULL — the check sees u0 in W's place)
-  int rc = sde_check(s, u0, s && s->tree_on ? u0 : W, u_end ? u_end : u0, B, 1.0f);   // (u_end may be NULL from the layer: no end state asked for)
-  if (rc) return rc;
-  lrnde_ctx* c = s->drift;
-  if (!o || !st || nfine < 1 || !(t1 > t0)) return fail(c, LRNDE_BADARG, "bad arguments (nfine >= 1, t1 > t0)");
-  SdeTree tree{};
-  if ((rc = sde_tree_source(s, nfine, t0, t1, tree))) return rc;
-  tree.rec_dw = tree.on ? rec_dw : nullptr; tree.rec_dz = tree.on && which == 2 ? rec_dz : nullptr;
-  memset(st, 0, sizeof(*st));
-  const size_t n = (size_t)B * c->desc.state_dim;
-  HIPCHK(c, s->ad_ws.resize_exact(4 * n));
-  float *ua = s->ad_ws, *ub = s->ad_ws + n, *dW = s->ad_ws + 2 * n, *dZ = s->ad_ws + 3 * n;
-  {
-    // the controller on the device: Euler-Heun (k_sde_eh_fast), Milstein (k_sde_mil_fast) and SRI (k_sde_sri_fast) at the
-    // one-launch kernels' shape.  Everything outside that shape runs the host-controlled loop below
-    const bool host_loop = opt(OPT_SDE_HOST_LOOP) != 0;  // diagnostic: the host-controlled loop below
-    if (sde_uses_fast(s) && !host_loop) {
-      return sde_adaptive_device(s, u0, W, nfine, B, t0, t1, o, u_end, st, trace_host, cap_trace, ua, ub, rec_u, rec_im_dev, rec_cap,
-                                 rec_im_host, dt0_dev, false, which, tab, Z, &tree);
-    }
-  }
-  s->info_kind = 0;
-  const int nfa = which == 2 ? 4 : (which == 1 ? 1 : 3);   // drift evaluations of one attempted step
-  HIPCHK(c, hipMemcpyAsync(ua, u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  const float h = (t1 - t0) / (float)nfine;
-  const PiConsts pi = {o->gamma, o->qmin, o->qmax, o->beta1, o->beta2};
-  int i = 0;                                                  // position on the path's grid
-  int m = (int)(o->dt0 / h); if (m < 1) m = 1;                // step length in grid intervals
-  float qold = QOLDINIT;
-  float dtc = o->dt0;   // the controller's proposal as a real number; the step taken is its floor on the grid (SdeCtl::dtc)
-  int nb = (int)((n + 255) / 256); if (nb > 1024) nb = 1024;
-  while (i < nfine) {
-    if (m > nfine - i) m = nfine - i;
-    if (++st->iters > o->maxiters) { st->retcode = LRNDE_MAXITERS; break; }
-    const float t = t0 + (float)i * h, dt = (float)m * h;
-    if (tree.on) hipLaunchKernelGGL(k_sde_dw_tree, dim3(nb), dim3(256), 0, c->stream, n, tree, TREE_STREAM_W, i, m, dW);
-    else hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, W + (size_t)i * n, W + (size_t)(i + m) * n, dW);
-    float eest = 0.f;
-    if (which == 2) {   // k_sri_chi / k_sri_stage / k_sri_final around the eight evaluations; the call ends in the attempt's synchronisation
-      if (tree.on) hipLaunchKernelGGL(k_sde_dw_tree, dim3(nb), dim3(256), 0, c->stream, n, tree, TREE_STREAM_Z, i, m, dZ);
-      else hipLaunchKernelGGL(k_sde_dw, dim3(nb), dim3(256), 0, c->stream, n, Z + (size_t)i * n, Z + (size_t)(i + m) * n, dZ);
-      if ((rc = lrnde_sde_sri_step(s, tab, ua, dW, dZ, B, t, dt, o->abstol, o->reltol, o->delta, ub, &eest, nullptr))) return rc;
-    } else {
-      if ((rc = sde_step_enqueue(s, which, ua, dW, B, t, dt, o->abstol, o->reltol, o->delta, ub, c->ctrl_host))) return rc;
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      eest = c->ctrl_host[0].eest_last;
-    }
-    ++s->info_launches; ++s->info_waits;   // (SRI: the step's launch sequence counts as one; its synchronisation is lrnde_sde_sri_step's)
-    st->nf += nfa; st->eest_last = eest;
-    if (eest != eest) { st->retcode = LRNDE_DT_NAN; break; }
-    // PI controller on EEst (the form of SURVEY.md 3.5; StochasticDiffEq's constants are the caller's options)
-    const float q = pi_step(pi, 0, eest, pi_pow(0, qold, pi.beta2), 1.0f).q;
-    const int accepted = eest <= 1.0f;
-    const int ntr = st->naccept + st->nreject;
-    if (trace_host && ntr < cap_trace) { trace_host[ntr].t = t; trace_host[ntr].dt = dt; trace_host[ntr].eest = eest; trace_host[ntr].accepted = accepted; }
-    dtc = (accepted ? fmaxf(dtc, dt) : dt) / q;
-    int mnew = (int)(dtc / h);
-    if (mnew < 1) mnew = 1;
-    if (accepted) {
-      if (rec_u) {
-        if (st->naccept >= rec_cap) { st->retcode = LRNDE_CAPACITY; break; }
-        HIPCHK(c, hipMemcpyAsync(rec_u + (size_t)st->naccept * n, ub, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-        // (the tree: the accepted step's increments beside its end state — the backward reads them from there)
-        if (tree.rec_dw) HIPCHK(c, hipMemcpyAsync(tree.rec_dw + (size_t)st->naccept * n, dW, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-        if (tree.rec_dz) HIPCHK(c, hipMemcpyAsync(tree.rec_dz + (size_t)st->naccept * n, dZ, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-        rec_im_host[st->naccept] = make_int2(i, m);
-      }
-      st->naccept++;
-      qold = pi_qold(eest);
-      i += m;
-      std::swap(ua, ub);
-      m = mnew;
-    } else {
-      st->nreject++;
-      if (m == 1) { st->retcode = LRNDE_DT_LESS_THAN_MIN; break; }  // the path's grid cannot be refined further
-      m = mnew < m ? mnew : m - 1;
-    }
-  }
-  st->t_final = t0 + (float)i * h; st->dt_final = (float)m * h;
-  if (u_end) HIPCHK(c, hipMemcpyAsync(u_end, ua, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  ++s->info_waits;
-  if (st->retcode != LRNDE_OK) return fail(c, st->retcode, "adaptive SDE solve stopped with retcode %d at t=%g", st->retcode, (double)st->t_final);
-  return LRNDE_OK;
 }
 
 // ---- four-stage SRI step (src/perform_step.jl:49-106), diagonal noise, caller-supplied tableau ----

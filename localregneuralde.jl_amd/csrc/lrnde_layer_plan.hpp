@@ -1,11 +1,12 @@
 // lrnde_layer_plan.hpp — the bookkeeping of `(n::NeuralODE)(x, ps, st)` / `(n::NeuralDSDE)(...)` that every layer forward
 // shares, stated once (src/layers/neural_ode.jl:56-116, src/utils.jl:31-33): the `saveat` the global
 // solve gets for :none / :unbiased / :biased, the save slot that will hold sol(t1), the index one uniform draw selects
-// in :biased, the entries _CorrectedDESolution removes from the caller's series, and the stop list of the backward pass.
+// in :biased, the entries _CorrectedDESolution removes from the caller's series, the stop list of the backward pass, and
+// the SDE layer's series on its accepted steps (save_start rule, interpolated entries, where the local step starts).
 //
 // Like lrnde_stepctl.hpp: values in, values out, no HIP call and no handle, so the host compiler builds it alone
 // (tests/test_host_layer_plan.py).  The MLP / Dense-chain handles (lrnde_kernels.hip), the conv handle (lrnde_conv.hip)
-// and the SDE layer (lrnde_sde_node.hpp) call it; the SDE's save_start rule and its interpolated entries stay there.
+// and the SDE layer (lrnde_sde_node.hpp) call it.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -48,6 +49,66 @@ inline int biased_pick(float r, int m) {
 
 // ---- _CorrectedDESolution: `sol.u[t1 .!= sol.t]`, only where t1 was added to the user's saveat (a NaN t1 drops nothing) ----
 inline bool series_keeps(bool needs_correction, float t1, float t) { return !(needs_correction && t == t1); }
+
+// ---- the NeuralDSDE layer's series on the accepted steps of its solve (src/layers/neural_sde.jl:50-123) ----
+// sol.t / sol.u as StochasticDiffEq would hold them (UPSTREAM-RECALL): accepted step k covers im[k].x .. im[k].x + im[k].y on
+// the path's grid of nfine intervals over (t0, t2) (Step: anything with int members x, y); a saveat value lies inside the
+// step that contains it, by the solvers' linear interpolant; saveat = [] saves every step; save_start < 0: DiffEq's default
+// rule.  The times are float32 products in this order, the end of the grid is t2 itself.
+struct SdeSeriesEntry { float t; int k; float theta; };  // value = (1-theta) * state_before(step k) + theta * rec_u[k]; k = -1: the start value
+enum { SERIES_OK = 0, SERIES_T1_OUTSIDE, SERIES_SAVES_NOTHING, SERIES_BIASED_NEEDS_TWO, SERIES_T1_AT_END };   // refusals, in the order they are found
+struct SdeSeriesPlan {
+  int status = SERIES_OK;
+  std::vector<SdeSeriesEntry> sol;      // what the solve saves
+  SdeSeriesEntry e1{}; float t1 = 0.f;  // where the local step starts (t1 = t2 for :none, which has none)
+  std::vector<SdeSeriesEntry> series;   // the caller's view: sol after the _CorrectedDESolution filter
+};
+template <class Step>
+inline SdeSeriesPlan sde_series_plan(float t0, float t2, int nfine, const Step* im, int K, int mode, float t1_or_rand, int save_start,
+                                     const float* user, int nuser) {
+  SdeSeriesPlan p;
+  const float h = (t2 - t0) / (float)nfine;
+  auto tk = [&](int k) { return t0 + (float)im[k].x * h; };                       // start of accepted step k
+  auto tk1 = [&](int k) { return (im[k].x + im[k].y >= nfine) ? t2 : t0 + (float)(im[k].x + im[k].y) * h; };
+  auto entry_at = [&](float ts) {
+    SdeSeriesEntry e; e.t = ts; e.k = -1; e.theta = 0.f;
+    if (!(ts > t0)) return e;
+    int k = 0;
+    while (k < K - 1 && tk1(k) < ts) ++k;
+    e.k = k;
+    e.theta = (ts >= tk1(k)) ? 1.0f : (ts - tk(k)) / ((float)im[k].y * h);
+    return e;
+  };
+  p.t1 = t2;
+  if (mode == LRNDE_MODE_UNBIASED) {
+    p.t1 = t1_or_rand;
+    if (!(p.t1 >= t0 && p.t1 <= t2)) { p.status = SERIES_T1_OUTSIDE; return p; }
+  }
+  const SolveSaveat plan = solve_saveat(mode, p.t1, t2, user, nuser);
+  const std::vector<float>& sv = plan.saveat;   // the solve's saveat
+  const bool everystep = plan.save_everystep != 0;
+  bool with_start = save_start > 0;
+  if (save_start < 0) with_start = everystep || (!sv.empty() && sv.front() == t0);   // DiffEq: save_everystep || isempty(saveat) || tspan[1] in saveat
+  if (with_start) { SdeSeriesEntry e; e.t = t0; e.k = -1; e.theta = 0.f; p.sol.push_back(e); }
+  if (everystep) {
+    for (int k = 0; k < K; ++k) { SdeSeriesEntry e; e.t = tk1(k); e.k = k; e.theta = 1.0f; p.sol.push_back(e); }
+  } else {
+    for (float ts : sv) { if (ts == t0 && with_start) continue; p.sol.push_back(entry_at(ts)); }
+  }
+  if (p.sol.empty()) { p.status = SERIES_SAVES_NOTHING; return p; }
+  p.e1.t = t2; p.e1.k = K - 1; p.e1.theta = 1.0f;
+  if (mode == LRNDE_MODE_BIASED) {      // :114-115  t1 = rand(rng, sol.t[1:(end - 1)])
+    const int m = (int)p.sol.size() - 1;
+    if (m < 1) { p.status = SERIES_BIASED_NEEDS_TWO; return p; }
+    p.e1 = p.sol[biased_pick(t1_or_rand, m)]; p.t1 = p.e1.t;
+  } else if (mode == LRNDE_MODE_UNBIASED) {
+    p.e1 = entry_at(p.t1);
+  }
+  if (mode != LRNDE_MODE_NONE && !(p.t1 < t2)) { p.status = SERIES_T1_AT_END; return p; }
+  // the caller's view: _CorrectedDESolution drops the entries at t1 (src/utils.jl:31-33: `sol.u[t1 .!= sol.t]`)
+  for (const SdeSeriesEntry& e : p.sol) if (series_keeps(plan.needs_correction, p.t1, e.t)) p.series.push_back(e);
+  return p;
+}
 
 // ---- save-slot predictions of the ODE solves (lrnde_solve, lrnde_conv_solve) ----
 // The slot of the LAST saveat entry equal to t1: its index among the entries inside the span (those at or before t0 are

@@ -56,7 +56,7 @@ struct SdeFastArgs {
   // adaptive solves: the controller lives on the device.  The launch reads the control block (grid position i, step
   // length m in grid intervals, which of the two state buffers is current), forms dW from the caller's path itself, and
   // its last workgroup runs the PI controller and writes the block for the next launch.
-  struct SdeCtl* ctl; const float* Wpath; float* ua; float* ub; int nfine; float t0, h;
+  SdeCtl* ctl; const float* Wpath; float* ua; float* ub; int nfine; float t0, h;
   float gamma, qmin, qmax, beta1, beta2; int maxiters;
   lrnde_trace_row* trace; int cap_trace;
   unsigned long long* prog;  // pinned host word: sde_report_pack(launches whose footer ran, status)
@@ -74,10 +74,6 @@ struct SdeFastArgs {
   // accepted step's increments recorded beside rec_u.  Behind everything else: no other field moves
   SdeTree tree;
 };
-// dtc: the controller's step proposal as a REAL number; the step taken is its floor on the path's grid (m intervals, at least
-// one).  Growth accumulates in dtc — with qmax = 1.125 a proposal quantised after every step could never leave m = 1.
-struct SdeCtl { int status, i, m, cur, naccept, nreject, iters, nf; float qold, eest_last, dtc; };
-
 // canonical dot product over NKG k-groups of 16 rows: fma chains over segments of SEGK k-groups, partials left to right
 template <int NKG>
 __device__ __forceinline__ f32x4 sf_chain(const f32x4 (&frag)[NKG], const f32x4* xb, int lane) {
@@ -100,6 +96,10 @@ __device__ __forceinline__ f32x4 sf_chain(const f32x4 (&frag)[NKG], const f32x4*
 // qpow = fastpow(c.qold, a.beta2): does not depend on this step's EEst — the cooperative form computes it while the partial
 // sums are still in flight.
 // nfa: drift evaluations of one attempted step (Euler-Heun 3, Milstein 1, SRI 4): what SdeCtl::nf counts.
+// (The same controller as sde_grid_update, lrnde_stepctl.hpp — the host loop's, and what tests/test_host_gridctl.py holds to the
+// numpy loop.  It stays written out here: with the trace row and the pair written by the caller of the shared function the
+// step kernels' footers compiled to other code than before — more SGPR spills in the persistent tree kernels.  A change to
+// either statement goes into both; tests/test_gpu_switches.py holds the two loops to the same bits.)
 __device__ __forceinline__ void sde_ctl_update(SdeCtl& c, float eest, float dt, const SdeFastArgs& a, bool writer, float qpow, int nfa) {
   c.nf += nfa; c.eest_last = eest;
   if (eest != eest) { c.status = LRNDE_DT_NAN; return; }

@@ -15,7 +15,6 @@
 
 namespace {
 
-struct SdeSeriesEntry { float t; int k; float theta; };  // value = (1-theta) * state_before(step k) + theta * rec_u[k]; k = -1: the start value
 struct SdeNodeRecord {
   bool valid = false;
   unsigned long long gen = 0;
@@ -124,35 +123,28 @@ int sde_init_dt(lrnde_sde* s, const float* u, int B, float t, float tend, float 
 // (no time input: the evaluations at t + dt0 do not need dt0 on the host).  The four evaluations and the three norms run on
 // k_sde_eh_fast's tiles (its idt_phase 1 / 2: lrnde_sde_fast.hpp), the scalar tail in k_sde_initdt_fin — the expressions of
 // the host code above, fp64 sums in the partial-vector order every reduction here uses — and the result stays on the
-// device: scal[0] = dt0, scal[1] = d1, scal[2] = the initial dt.  The tail also starts what consumes the dt: the adaptive
-// solve's control block (ctl) or the single step's (ctrl).
-__global__ void k_sde_initdt_fin(const double* part2, int nwg, double n, float dtmax, float order, float* scal, SdeCtl* ctl, float h,
-                                 int nfine, Ctrl* ctrl, float t0) {
+// device: scal[0] = dt0, scal[1] = d1, scal[2] = the initial dt.  The tail also starts what consumes the dt (SdeInitDtFor):
+// the adaptive solve's control block on its grid of nfine intervals of h, a single step's Ctrl pair, or nothing.
+struct SdeInitDtFor { SdeCtl* ctl = nullptr; float h = 0.f; int nfine = 0; Ctrl* ctrl = nullptr; };
+__global__ void k_sde_initdt_fin(const double* part2, int nwg, double n, float dtmax, float order, float* scal, SdeInitDtFor use, float t0) {
   if (threadIdx.x >= 64 || blockIdx.x != 0) return;
   const Sum3 s = reduce_partials3(part2, nwg);
   if (threadIdx.x != 0) return;
   const float dt0 = scal[0], d1 = scal[1];
   const float dt = initdt_tail(dt0, d1, (float)sqrt(s.a / n), order + 0.5f, dtmax);
   scal[2] = dt;
-  if (ctl) {      // k_sde_ctl_init with the host's quantisation of dt to the path's grid
-    int m0 = (int)(dt / h); if (m0 < 1) m0 = 1;
-    if (m0 > nfine) m0 = nfine;
-    SdeCtl c;
-    c.status = ST_RUNNING; c.i = 0; c.m = m0; c.cur = 0; c.naccept = 0; c.nreject = 0; c.iters = 1; c.nf = 0;
-    c.qold = QOLDINIT; c.eest_last = 0.f; c.dtc = dt;
-    *ctl = c;
-  }
-  if (ctrl) {     // k_ctrl_init
+  if (use.ctl) *use.ctl = sde_grid_begin(dt, use.h, use.nfine);   // k_sde_ctl_init
+  if (use.ctrl) {     // k_ctrl_init
     Ctrl c;
     memset(&c, 0, sizeof(c));
     c.status = ST_RUNNING; c.first = 1;
     c.t = t0; c.dt = dt; c.qold = QOLDINIT; c.q11 = 1.0f; c.dtpropose = dt;
-    ctrl[0] = c;
-    ctrl[1] = c;
+    use.ctrl[0] = c;
+    use.ctrl[1] = c;
   }
 }
 int sde_init_dt_dev(lrnde_sde* s, const float* u, int B, float t, float tend, float abstol, float reltol, float order, float* scal,
-                    SdeCtl* ctl, float h, int nfine, Ctrl* ctrl) {
+                    const SdeInitDtFor use) {
   lrnde_ctx* c = s->drift;
   const int nwg = (B + NB - 1) / NB;
   HIPCHK(c, s->idt_pp.grow(2 * (size_t)nwg * PSTRIDE));
@@ -166,8 +158,7 @@ int sde_init_dt_dev(lrnde_sde* s, const float* u, int B, float t, float tend, fl
   sde_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
   f.idt_phase = 2;
   sde_fast_launch(f.D, c->desc.hidden_dim, nwg, c->stream, f);
-  hipLaunchKernelGGL(k_sde_initdt_fin, dim3(1), dim3(64), 0, c->stream, (const double*)f.idt_part2, nwg, f.n_norm, tend - t, order, scal, ctl, h,
-                     nfine, ctrl, t);
+  hipLaunchKernelGGL(k_sde_initdt_fin, dim3(1), dim3(64), 0, c->stream, (const double*)f.idt_part2, nwg, f.n_norm, tend - t, order, scal, use, t);
   HIPCHK(c, hipGetLastError());
   return LRNDE_OK;
 }
@@ -210,6 +201,195 @@ void sde_node_release(lrnde_sde* s) {
   s->node = nullptr;
 }
 
+// ---- lrnde_sde_node_forward_record_alg in pieces ----
+// What the layer's call adds to its solve request (the request: x, the path, the grid, tspan, the caller's options, the step
+// kind, st): the regulariser's mode and draws, the saveat, the caller's outputs — and the evaluation counts as the pieces add them up.
+struct SdeNodeCall {
+  int mode = 0; float t1_or_rand = 0.f; const float* z_local = nullptr; const float* z2_local = nullptr;
+  int save_start = 0; const float* saveat_host = nullptr; int nsave = 0;
+  float* u_series = nullptr; float* t_series_host = nullptr; int cap_series = 0; int32_t* nseries_host = nullptr;
+  float* reg_val_host = nullptr; int32_t* nfe_drift_host = nullptr; int32_t* nfe_diffusion_host = nullptr; float* t1_used_host = nullptr;
+  int nfe_f = 0, nfe_g = 0;
+};
+// per attempted step: (drift, diffusion) evaluations, and the strong order the automatic initial dt takes (UPSTREAM-RECALL)
+struct SdeKind { int nfa, nga; float order; };
+SdeKind sde_kind(int which) { return which == 2 ? SdeKind{4, 4, 1.5f} : (which == 1 ? SdeKind{1, 2, 1.0f} : SdeKind{3, 3, 0.5f}); }
+// (the one-launch steps' shape keeps the main solve's automatic initial dt on the device for all three step kinds, with the
+//  kind's strong order: the solve's closing synchronisation is then the main solve's only one; LRNDE_SDE_HOST_INITDT=1: the
+//  host form, two more.  Euler-Heun keeps its local step's initial dt there too: two host synchronisations per call — the end
+//  of the solve and the end of the forward.  The local step of Milstein and SRI takes the host form: it runs the generic
+//  step kernels, which take dt from the host)
+bool sde_node_devdt(const lrnde_sde* s) { return sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT); }
+// No regulariser, no saveat, no start value: the caller's series is the end state alone — the solve leaves it in u_series itself
+// (picked on the device) and its closing synchronisation is the call's only one.  Otherwise the end state is not asked for
+// (it is the record's last slot).
+bool sde_node_end_only(const lrnde_sde* s, const SdeSolveReq& q, const SdeNodeCall& a) {
+  return q.which == 0 && a.mode == LRNDE_MODE_NONE && a.nsave == 0 && a.save_start <= 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP);
+}
+
+int sde_node_check(lrnde_sde* s, SdeSolveReq& q, const SdeNodeCall& a) {
+  lrnde_ctx* c = s->drift;
+  int rc = sde_alg_check(s, q.which, q.tab, q.Z);
+  if (rc) return rc;
+  const bool tree = s->tree_on;   // the path tree: W and Z are ignored (and recorded as null), the check sees x in W's place
+  if (tree) { q.W = nullptr; q.Z = nullptr; }
+  if ((rc = sde_check(s, q.u0, tree ? q.u0 : q.W, a.u_series, q.B, 1.0f))) return rc;
+  { SdeTree probe{}; if ((rc = sde_tree_source(s, q.nfine, q.t0, q.t1, probe))) return rc; }   // (nfine = 2^L: refused before anything is allocated)
+  if (q.which == 2 && a.mode != LRNDE_MODE_NONE && !a.z2_local)
+    return fail(c, LRNDE_BADARG, "z2_local (the local SRI step's second standard-normal draw) is required when regularising");
+  if (!q.opts || !q.st || !a.t_series_host || !a.nseries_host || !a.reg_val_host || q.nfine < 1 || !(q.t1 > q.t0) || a.nsave < 0 || a.cap_series < 1)
+    return fail(c, LRNDE_BADARG, "bad arguments (nfine >= 1, t2 > t0, non-null outputs)");
+  if (a.mode < LRNDE_MODE_NONE || a.mode > LRNDE_MODE_BIASED) return fail(c, LRNDE_BADARG, "mode");
+  if (a.mode != LRNDE_MODE_NONE && !a.z_local) return fail(c, LRNDE_BADARG, "z_local (the local step's standard-normal draw) is required when regularising");
+  for (int i = 0; i < a.nsave; ++i)
+    if (!(a.saveat_host[i] >= q.t0 && a.saveat_host[i] <= q.t1) || (i > 0 && a.saveat_host[i] < a.saveat_host[i - 1]))
+      return fail(c, LRNDE_BADARG, "saveat must be ascending and inside tspan");
+  return LRNDE_OK;
+}
+
+// the main solve (src/layers/neural_sde.jl:50-72) from q.u0 into the record: dt0 <= 0 -> automatic initial dt
+int sde_node_main_solve(lrnde_sde* s, SdeNodeRecord& r, const SdeSolveReq& q, SdeNodeCall& a) {
+  lrnde_ctx* c = s->drift;
+  const bool tree = s->tree_on, devdt = sde_node_devdt(s);
+  const int nfine = q.nfine, B = q.B;
+  const size_t n = (size_t)B * c->desc.state_dim;
+  const SdeKind kind = sde_kind(q.which);
+  // (a tree record holds the accepted steps' states AND increments.  No solve accepts more steps than it may attempt, so
+  //  min(nfine, maxiters) slots always suffice — the array form's nfine slots would be the array the tree exists to avoid — but
+  //  a solve rarely takes that many: the record starts at 64 slots and, when a solve ends with LRNDE_CAPACITY, is replaced by one
+  //  four times as large and the solve runs again — the same path, the same bits)
+  const int rcap_max = tree ? std::max(1, std::min(nfine, q.opts->maxiters)) : nfine;
+  int rcap = tree ? std::min(rcap_max, 64) : nfine;
+  if (devdt) {
+    HIPCHK(c, s->idt_scal.once(8));
+    HIPCHK(c, s->idt_scal_host.once(8));
+  }
+  int rc;
+  for (;;) {   // (one trip, unless a tree record has to grow)
+    a.nfe_f = a.nfe_g = 0;
+    if ((rc = sde_node_alloc(s, r, B, rcap, tree ? (q.which == 2 ? 2 : 1) : 0))) return rc;
+    HIPCHK(c, hipMemcpyAsync(r.x, q.u0, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+    s->info_kind = s->info_launches = s->info_waits = 0;   // (lrnde_sde_last_solve_info: the main solve with its initial dt)
+    lrnde_sde_adapt_opts oo = *q.opts;
+    SdeSolveReq m = q;
+    m.u0 = r.x; m.opts = &oo;
+    m.u_end = sde_node_end_only(s, q, a) ? a.u_series : nullptr;
+    if (!(oo.dt0 > 0.f)) {
+      if (devdt) {
+        if ((rc = sde_adaptive_prepare(s, r.rec_cap))) return rc;   // (before the initial dt initialises the control block)
+        SdeInitDtFor use{};
+        use.ctl = s->ctl(); use.h = (q.t1 - q.t0) / (float)nfine; use.nfine = nfine;
+        if ((rc = sde_init_dt_dev(s, r.x, B, q.t0, q.t1, oo.abstol, oo.reltol, kind.order, s->idt_scal, use))) return rc;
+        m.dt0_dev = s->idt_scal + 2;
+        oo.dt0 = q.t1 - q.t0;   // (placeholder for the argument checks; the control block is initialised from the device value)
+      } else {
+        if ((rc = sde_init_dt(s, r.x, B, q.t0, q.t1, oo.abstol, oo.reltol, kind.order, r.tmp, &oo.dt0))) return rc;
+        s->info_waits += 2;
+      }
+      a.nfe_f += 2; a.nfe_g += 2;
+    }
+    r.im.assign((size_t)nfine, make_int2(0, 0));
+    m.rec.u = r.rec_u; m.rec.im_dev = r.rec_im_dev; m.rec.im_host = r.im.data(); m.rec.cap = r.rec_cap;
+    m.rec.dw = tree ? r.rec_dw.get() : nullptr; m.rec.dz = tree && q.which == 2 ? r.rec_dz.get() : nullptr;
+    rc = sde_solve_adaptive_impl(s, m);
+    if (rc == LRNDE_CAPACITY && tree && r.rec_cap < rcap_max) { rcap = (int)std::min<long long>(rcap_max, 4ll * r.rec_cap); continue; }
+    if (rc) return rc;
+    break;
+  }
+  a.nfe_f += kind.nfa * (q.st->naccept + q.st->nreject); a.nfe_g += kind.nga * (q.st->naccept + q.st->nreject);
+  return LRNDE_OK;
+}
+
+// the value of a series entry on the record's states -> out
+int sde_node_value(lrnde_sde* s, const SdeNodeRecord& r, size_t n, const SdeSeriesEntry& e, float* out) {
+  lrnde_ctx* c = s->drift;
+  if (e.k < 0) { HIPCHK(c, hipMemcpyAsync(out, r.x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream)); return LRNDE_OK; }
+  const float* b = r.rec_u + (size_t)e.k * n;
+  if (e.theta == 1.0f) { HIPCHK(c, hipMemcpyAsync(out, b, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream)); return LRNDE_OK; }
+  const float* a = e.k == 0 ? r.x : r.rec_u + (size_t)(e.k - 1) * n;
+  hipLaunchKernelGGL(k_sde_lerp, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, a, b, e.theta, out);
+  HIPCHK(c, hipGetLastError());
+  return LRNDE_OK;
+}
+
+// the local step (:94-98, :116-118): fresh integrator at (sol(t1), t1) on (t1, t2) -> its own initial dt; one step of the
+// solve's kind with a fresh increment sqrt(dt) z (SRI: and a second one, sqrt(dt) z2).  *pending: the step's record is still
+// in flight (device-side initial dt) and comes back with the forward's closing synchronisation
+int sde_node_local_step(lrnde_sde* s, SdeNodeRecord& r, const SdeSolveReq& q, SdeNodeCall& a, const SdeSeriesEntry& e1, bool* pending) {
+  lrnde_ctx* c = s->drift;
+  const lrnde_sde_adapt_opts* o = q.opts;
+  const int B = q.B, which = q.which;
+  const float t1 = r.t1, t2 = q.t1;
+  const size_t n = (size_t)B * c->desc.state_dim;
+  const SdeKind kind = sde_kind(which);
+  int rc;
+  if ((rc = sde_node_value(s, r, n, e1, r.u1))) return rc;
+  float dtl = o->dt0;
+  if (!(dtl > 0.f) && sde_node_devdt(s) && which == 0) {
+    // dt, sqrt(dt) z and the step itself from the device value (sde_init_dt_dev clamps to t2 - t1 as the line below does);
+    // EEst, EEst * dt and dt come back with the forward's closing synchronisation
+    float* scal = s->idt_scal + 4;
+    if ((rc = sde_init_dt_dev(s, r.u1, B, t1, t2, o->abstol, o->reltol, 0.5f, scal, SdeInitDtFor{}))) return rc;
+    a.nfe_f += 2; a.nfe_g += 2;
+    // ONE launch: sqrt(dt) z formed and left in dWloc by the step itself, the step's footer (last workgroup) fills the record slot
+    if ((rc = sde_step_enqueue(s, 0, r.u1, a.z_local, B, t1, t2 - t1, o->abstol, o->reltol, o->delta, r.tmp, nullptr, c->ctrl + 1, scal + 2, r.dWloc))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->ctrl_host, c->ctrl + 1, sizeof(Ctrl), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s->idt_scal_host, s->idt_scal, sizeof(float) * 8, hipMemcpyDeviceToHost, c->stream));
+    *pending = true;
+  } else {
+    if (!(dtl > 0.f)) {
+      if ((rc = sde_init_dt(s, r.u1, B, t1, t2, o->abstol, o->reltol, kind.order, r.tmp, &dtl))) return rc;
+      a.nfe_f += 2; a.nfe_g += 2;
+    }
+    dtl = fminf(dtl, t2 - t1);
+    hipLaunchKernelGGL(k_sde_scale, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, a.z_local, sqrtf(dtl), r.dWloc);
+    float ee = 0.f, rv = 0.f;
+    if (which == 2) {
+      hipLaunchKernelGGL(k_sde_scale, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, a.z2_local, sqrtf(dtl), r.dZloc);
+      if ((rc = lrnde_sde_sri_step(s, q.tab, r.u1, r.dWloc, r.dZloc, B, t1, dtl, o->abstol, o->reltol, o->delta, r.tmp, &ee, &rv))) return rc;
+    } else if ((rc = sde_step_impl(s, which, r.u1, r.dWloc, B, t1, dtl, o->abstol, o->reltol, o->delta, r.tmp, &ee, &rv))) return rc;
+    *a.reg_val_host = rv;
+    r.ee_loc = ee;
+    r.dt_loc = dtl;
+  }
+  a.nfe_f += kind.nfa; a.nfe_g += kind.nga;
+  return LRNDE_OK;
+}
+
+// the caller's series (r.series) into its arrays, the model's head behind it, the closing wait and what comes back with it
+int sde_node_copy_out(lrnde_sde* s, SdeNodeRecord& r, const SdeSolveReq& q, const SdeNodeCall& a, bool local_pending) {
+  lrnde_ctx* c = s->drift;
+  const size_t n = (size_t)q.B * c->desc.state_dim;
+  const int ns = (int)r.series.size(), K = q.st->naccept;
+  int rc;
+  *a.nseries_host = ns;
+  if (ns > a.cap_series) return fail(c, LRNDE_CAPACITY, "series buffer too small (%d > %d)", ns, a.cap_series);
+  const bool series_done = sde_node_end_only(s, q, a) && ns == 1 && r.series[0].k == K - 1 && r.series[0].theta == 1.0f;   // (u_series[0] holds it already)
+  for (int i = 0; i < ns; ++i) {
+    if (!series_done && (rc = sde_node_value(s, r, n, r.series[i], a.u_series + (size_t)i * n))) return rc;
+    a.t_series_host[i] = r.series[i].t;
+  }
+  // (the model's head goes into the queue here, behind the series and ahead of the one wait: lrnde_sde_model.hpp)
+  const bool hooked = (bool)s->fwd_hook;
+  if (hooked && (rc = s->fwd_hook(a.u_series + (size_t)(ns - 1) * n, ns))) return rc;
+  if (!series_done || hooked) HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (local_pending) {
+    *a.reg_val_host = c->ctrl_host[0].reg_error;   // EEst * dt (src/perform_step.jl:205)
+    r.ee_loc = c->ctrl_host[0].eest_last;
+    r.dt_loc = s->idt_scal_host[6];
+  }
+  if (a.nfe_drift_host) *a.nfe_drift_host = a.nfe_f;
+  if (a.nfe_diffusion_host) *a.nfe_diffusion_host = a.nfe_g;
+  if (a.t1_used_host) *a.t1_used_host = r.t1;
+  return LRNDE_OK;
+}
+
+// the four refusals of the series plan (SERIES_*, in that order) with the layer's code and texts
+int sde_node_refusal(lrnde_ctx* c, int status) {
+  static const char* const text[] = {"", "t1 outside tspan", "the solve saves nothing", ":biased needs at least two saved times", "t1 must lie before the end of tspan"};
+  return fail(c, LRNDE_BADARG, "%s", text[status]);
+}
+
 }  // namespace
 
 extern "C" {
@@ -231,196 +411,29 @@ int lrnde_sde_node_forward_record_alg(lrnde_sde* s, const float* x, const float*
                                       int32_t* nfe_drift_host, int32_t* nfe_diffusion_host, lrnde_stats* st, float* t1_used_host,
                                       int32_t which, const lrnde_sri_tableau* tab, const float* Z, const float* z2_local) {
   if (!s) return LRNDE_BADARG;
-  lrnde_ctx* c = s->drift;
-  int rc = sde_alg_check(s, which, tab, Z);
+  SdeSolveReq q{};
+  q.u0 = x; q.W = W; q.Z = Z; q.nfine = nfine; q.B = B; q.t0 = t0; q.t1 = t2; q.opts = o; q.which = which; q.tab = tab; q.st = st;
+  SdeNodeCall a{};
+  a.mode = mode; a.t1_or_rand = t1_or_rand; a.z_local = z_local; a.z2_local = z2_local;
+  a.save_start = save_start; a.saveat_host = saveat_host; a.nsave = nsave;
+  a.u_series = u_series; a.t_series_host = t_series_host; a.cap_series = cap_series; a.nseries_host = nseries_host;
+  a.reg_val_host = reg_val_host; a.nfe_drift_host = nfe_drift_host; a.nfe_diffusion_host = nfe_diffusion_host; a.t1_used_host = t1_used_host;
+  int rc = sde_node_check(s, q, a);
   if (rc) return rc;
-  const bool tree = s->tree_on;   // the path tree: W and Z are ignored (and recorded as null), the check sees x in W's place
-  if (tree) { W = nullptr; Z = nullptr; }
-  if ((rc = sde_check(s, x, tree ? x : W, u_series, B, 1.0f))) return rc;
-  { SdeTree probe{}; if ((rc = sde_tree_source(s, nfine, t0, t2, probe))) return rc; }   // (nfine = 2^L: refused before anything is allocated)
-  if (which == 2 && mode != LRNDE_MODE_NONE && !z2_local)
-    return fail(c, LRNDE_BADARG, "z2_local (the local SRI step's second standard-normal draw) is required when regularising");
-  // per attempted step: (drift, diffusion) evaluations, and the strong order the automatic initial dt takes (UPSTREAM-RECALL)
-  const int nfa = which == 2 ? 4 : (which == 1 ? 1 : 3), nga = which == 2 ? 4 : (which == 1 ? 2 : 3);
-  const float order = which == 2 ? 1.5f : (which == 1 ? 1.0f : 0.5f);
-  if (!o || !st || !t_series_host || !nseries_host || !reg_val_host || nfine < 1 || !(t2 > t0) || nsave < 0 || cap_series < 1)
-    return fail(c, LRNDE_BADARG, "bad arguments (nfine >= 1, t2 > t0, non-null outputs)");
-  if (mode < LRNDE_MODE_NONE || mode > LRNDE_MODE_BIASED) return fail(c, LRNDE_BADARG, "mode");
-  if (mode != LRNDE_MODE_NONE && !z_local) return fail(c, LRNDE_BADARG, "z_local (the local step's standard-normal draw) is required when regularising");
-  for (int i = 0; i < nsave; ++i)
-    if (!(saveat_host[i] >= t0 && saveat_host[i] <= t2) || (i > 0 && saveat_host[i] < saveat_host[i - 1]))
-      return fail(c, LRNDE_BADARG, "saveat must be ascending and inside tspan");
   if (!s->node) s->node = new SdeNodeRecord();
   SdeNodeRecord& r = *s->node;
   r.valid = false;
-  // (a tree record holds the accepted steps' states AND increments.  No solve accepts more steps than it may attempt, so
-  //  min(nfine, maxiters) slots always suffice — the array form's nfine slots would be the array the tree exists to avoid — but
-  //  a solve rarely takes that many: the record starts at 64 slots and, when a solve ends with LRNDE_CAPACITY, is replaced by one
-  //  four times as large and the solve runs again — the same path, the same bits)
-  const int rcap_max = tree ? std::max(1, std::min(nfine, o->maxiters)) : nfine;
-  int rcap = tree ? std::min(rcap_max, 64) : nfine;
-  const int D = c->desc.state_dim;
-  const size_t n = (size_t)B * D;
-  const float h = (t2 - t0) / (float)nfine;
-  int nfe_f = 0, nfe_g = 0;
-  // the main solve (src/layers/neural_sde.jl:50-72): dt0 <= 0 -> automatic initial dt
-  // (the one-launch steps' shape keeps the main solve's automatic initial dt on the device for all three step kinds, with the
-  //  kind's strong order: the solve's closing synchronisation is then the main solve's only one; LRNDE_SDE_HOST_INITDT=1: the
-  //  host form, two more.  Euler-Heun keeps its local step's initial dt there too (devdt_local): two host synchronisations per
-  //  call — the end of the solve and the end of this function.  The local step of Milstein and SRI takes the host form: it runs
-  //  the generic step kernels, which take dt from the host)
-  const bool devdt = sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP) && !opt(OPT_SDE_HOST_INITDT);
-  const bool devdt_local = devdt && which == 0;
-  if (devdt) {
-    HIPCHK(c, s->idt_scal.once(8));
-    HIPCHK(c, s->idt_scal_host.once(8));
-  }
-  // No regulariser, no saveat, no start value: the caller's series is the end state alone — the solve leaves it in u_series itself
-  // (picked on the device) and its closing synchronisation is the call's only one.  Otherwise the end state is not asked for
-  // (it is the record's last slot).
-  const bool end_only = which == 0 && mode == LRNDE_MODE_NONE && nsave == 0 && save_start <= 0 && sde_uses_fast(s) && !opt(OPT_SDE_HOST_LOOP);
-  float* u_end = end_only ? u_series : nullptr;
-  for (;;) {   // (one trip, unless a tree record has to grow)
-  nfe_f = nfe_g = 0;
-  if ((rc = sde_node_alloc(s, r, B, rcap, tree ? (which == 2 ? 2 : 1) : 0))) return rc;
-  HIPCHK(c, hipMemcpyAsync(r.x, x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  s->info_kind = s->info_launches = s->info_waits = 0;   // (lrnde_sde_last_solve_info: the main solve with its initial dt)
-  lrnde_sde_adapt_opts oo = *o;
-  const float* dt0_dev = nullptr;
-  if (!(oo.dt0 > 0.f)) {
-    if (devdt) {
-      if ((rc = sde_adaptive_prepare(s, r.rec_cap))) return rc;   // (before the initial dt initialises the control block)
-      if ((rc = sde_init_dt_dev(s, r.x, B, t0, t2, oo.abstol, oo.reltol, order, s->idt_scal, s->ctl(), h, nfine, nullptr))) return rc;
-      dt0_dev = s->idt_scal + 2;
-      oo.dt0 = t2 - t0;   // (placeholder for the argument checks; the control block is initialised from the device value)
-    } else {
-      if ((rc = sde_init_dt(s, r.x, B, t0, t2, oo.abstol, oo.reltol, order, r.tmp, &oo.dt0))) return rc;
-      s->info_waits += 2;
-    }
-    nfe_f += 2; nfe_g += 2;
-  }
-  r.im.assign((size_t)nfine, make_int2(0, 0));
-  rc = sde_solve_adaptive_impl(s, r.x, W, nfine, B, t0, t2, &oo, u_end, st, nullptr, 0, r.rec_u, r.rec_im_dev, r.im.data(), r.rec_cap, dt0_dev,
-                               which, tab, Z, tree ? r.rec_dw.get() : nullptr, tree && which == 2 ? r.rec_dz.get() : nullptr);
-  if (rc == LRNDE_CAPACITY && tree && r.rec_cap < rcap_max) { rcap = (int)std::min<long long>(rcap_max, 4ll * r.rec_cap); continue; }
-  if (rc) return rc;
-  break;
-  }
-  const int K = st->naccept;
-  nfe_f += nfa * (st->naccept + st->nreject); nfe_g += nga * (st->naccept + st->nreject);
-  // sol.t / sol.u as StochasticDiffEq would hold them (UPSTREAM-RECALL): saveat values by linear interpolation inside the
-  // accepted step that contains them; saveat = [] saves every step; save_start < 0: DiffEq's default rule
-  auto tk = [&](int k) { return t0 + (float)r.im[k].x * h; };                       // start of accepted step k
-  auto tk1 = [&](int k) { return (r.im[k].x + r.im[k].y >= nfine) ? t2 : t0 + (float)(r.im[k].x + r.im[k].y) * h; };
-  auto entry_at = [&](float ts) {
-    SdeSeriesEntry e; e.t = ts; e.k = -1; e.theta = 0.f;
-    if (!(ts > t0)) return e;
-    int k = 0;
-    while (k < K - 1 && tk1(k) < ts) ++k;
-    e.k = k;
-    e.theta = (ts >= tk1(k)) ? 1.0f : (ts - tk(k)) / ((float)r.im[k].y * h);
-    return e;
-  };
-  float t1 = t2;
-  if (mode == LRNDE_MODE_UNBIASED) {
-    t1 = t1_or_rand;
-    if (!(t1 >= t0 && t1 <= t2)) return fail(c, LRNDE_BADARG, "t1 outside tspan");
-  }
-  const SolveSaveat plan = solve_saveat(mode, t1, t2, saveat_host, nsave);
-  const std::vector<float>& sv = plan.saveat;   // the solve's saveat
-  const bool everystep = plan.save_everystep != 0;
-  bool with_start = save_start > 0;
-  if (save_start < 0) with_start = everystep || (!sv.empty() && sv.front() == t0);   // DiffEq: save_everystep || isempty(saveat) || tspan[1] in saveat
-  std::vector<SdeSeriesEntry> sol;
-  if (with_start) { SdeSeriesEntry e; e.t = t0; e.k = -1; e.theta = 0.f; sol.push_back(e); }
-  if (everystep) {
-    for (int k = 0; k < K; ++k) { SdeSeriesEntry e; e.t = tk1(k); e.k = k; e.theta = 1.0f; sol.push_back(e); }
-  } else {
-    for (float ts : sv) { if (ts == t0 && with_start) continue; sol.push_back(entry_at(ts)); }
-  }
-  if (sol.empty()) return fail(c, LRNDE_BADARG, "the solve saves nothing");
-  SdeSeriesEntry e1; e1.t = t2; e1.k = K - 1; e1.theta = 1.0f;
-  if (mode == LRNDE_MODE_BIASED) {      // :114-115  t1 = rand(rng, sol.t[1:(end - 1)])
-    const int m = (int)sol.size() - 1;
-    if (m < 1) return fail(c, LRNDE_BADARG, ":biased needs at least two saved times");
-    e1 = sol[biased_pick(t1_or_rand, m)]; t1 = e1.t;
-  } else if (mode == LRNDE_MODE_UNBIASED) {
-    e1 = entry_at(t1);
-  }
-  auto value_of = [&](const SdeSeriesEntry& e, float* out) -> int {
-    const int nb = sde_nb(n);
-    if (e.k < 0) { HIPCHK(c, hipMemcpyAsync(out, r.x, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream)); return LRNDE_OK; }
-    const float* b = r.rec_u + (size_t)e.k * n;
-    if (e.theta == 1.0f) { HIPCHK(c, hipMemcpyAsync(out, b, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream)); return LRNDE_OK; }
-    const float* a = e.k == 0 ? r.x : r.rec_u + (size_t)(e.k - 1) * n;
-    hipLaunchKernelGGL(k_sde_lerp, dim3(nb), dim3(256), 0, c->stream, n, a, b, e.theta, out);
-    HIPCHK(c, hipGetLastError());
-    return LRNDE_OK;
-  };
-  // the local step (:94-98, :116-118): fresh integrator at (sol(t1), t1) on (t1, t2) -> its own initial dt; one step of the
-  // solve's kind with a fresh increment sqrt(dt) z (SRI: and a second one, sqrt(dt) z2)
+  if ((rc = sde_node_main_solve(s, r, q, a))) return rc;
+  SdeSeriesPlan plan = sde_series_plan(t0, t2, nfine, r.im.data(), st->naccept, mode, t1_or_rand, save_start, saveat_host, nsave);
+  if (plan.status) return sde_node_refusal(s->drift, plan.status);
   *reg_val_host = 0.f;
-  r.t1 = t1; r.dt_loc = 0.f;
-  bool local_pending = false;   // the local step's record is still in flight (device-side initial dt)
-  if (mode != LRNDE_MODE_NONE) {
-    if (!(t1 < t2)) return fail(c, LRNDE_BADARG, "t1 must lie before the end of tspan");
-    if ((rc = value_of(e1, r.u1))) return rc;
-    float dtl = o->dt0;
-    if (!(dtl > 0.f) && devdt_local) {
-      // dt, sqrt(dt) z and the step itself from the device value (sde_init_dt_dev clamps to t2 - t1 as the line below does);
-      // EEst, EEst * dt and dt come back with this function's closing synchronisation
-      float* scal = s->idt_scal + 4;
-      if ((rc = sde_init_dt_dev(s, r.u1, B, t1, t2, o->abstol, o->reltol, 0.5f, scal, nullptr, 0.f, 0, nullptr))) return rc;
-      nfe_f += 2; nfe_g += 2;
-      // ONE launch: sqrt(dt) z formed and left in dWloc by the step itself, the step's footer (last workgroup) fills the record slot
-      if ((rc = sde_step_enqueue(s, 0, r.u1, z_local, B, t1, t2 - t1, o->abstol, o->reltol, o->delta, r.tmp, nullptr, c->ctrl + 1, scal + 2, r.dWloc))) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->ctrl_host, c->ctrl + 1, sizeof(Ctrl), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipMemcpyAsync(s->idt_scal_host, s->idt_scal, sizeof(float) * 8, hipMemcpyDeviceToHost, c->stream));
-      local_pending = true;
-    } else {
-      if (!(dtl > 0.f)) {
-        if ((rc = sde_init_dt(s, r.u1, B, t1, t2, o->abstol, o->reltol, order, r.tmp, &dtl))) return rc;
-        nfe_f += 2; nfe_g += 2;
-      }
-      dtl = fminf(dtl, t2 - t1);
-      hipLaunchKernelGGL(k_sde_scale, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, z_local, sqrtf(dtl), r.dWloc);
-      float ee = 0.f, rv = 0.f;
-      if (which == 2) {
-        hipLaunchKernelGGL(k_sde_scale, dim3(sde_nb(n)), dim3(256), 0, c->stream, n, z2_local, sqrtf(dtl), r.dZloc);
-        if ((rc = lrnde_sde_sri_step(s, tab, r.u1, r.dWloc, r.dZloc, B, t1, dtl, o->abstol, o->reltol, o->delta, r.tmp, &ee, &rv))) return rc;
-      } else
-      if ((rc = sde_step_impl(s, which, r.u1, r.dWloc, B, t1, dtl, o->abstol, o->reltol, o->delta, r.tmp, &ee, &rv))) return rc;
-      *reg_val_host = rv;
-      r.ee_loc = ee;
-      r.dt_loc = dtl;
-    }
-    nfe_f += nfa; nfe_g += nga;
-  }
-  // the caller's view: _CorrectedDESolution drops the entries at t1 (src/utils.jl:31-33: `sol.u[t1 .!= sol.t]`)
-  r.series.clear();
-  for (const SdeSeriesEntry& e : sol) if (series_keeps(plan.needs_correction, t1, e.t)) r.series.push_back(e);
-  const int ns = (int)r.series.size();
-  *nseries_host = ns;
-  if (ns > cap_series) return fail(c, LRNDE_CAPACITY, "series buffer too small (%d > %d)", ns, cap_series);
-  const bool series_done = end_only && ns == 1 && r.series[0].k == K - 1 && r.series[0].theta == 1.0f;   // (u_series[0] holds it already)
-  for (int i = 0; i < ns; ++i) {
-    if (!series_done && (rc = value_of(r.series[i], u_series + (size_t)i * n))) return rc;
-    t_series_host[i] = r.series[i].t;
-  }
-  // (the model's head goes into the queue here, behind the series and ahead of the one wait: lrnde_sde_model.hpp)
-  const bool hooked = (bool)s->fwd_hook;
-  if (hooked && (rc = s->fwd_hook(u_series + (size_t)(ns - 1) * n, ns))) return rc;
-  if (!series_done || hooked) HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (local_pending) {
-    *reg_val_host = c->ctrl_host[0].reg_error;   // EEst * dt (src/perform_step.jl:205)
-    r.ee_loc = c->ctrl_host[0].eest_last;
-    r.dt_loc = s->idt_scal_host[6];
-  }
-  if (nfe_drift_host) *nfe_drift_host = nfe_f;
-  if (nfe_diffusion_host) *nfe_diffusion_host = nfe_g;
-  if (t1_used_host) *t1_used_host = t1;
-  r.valid = true; ++r.gen; r.B = B; r.nfine = nfine; r.K = K; r.mode = mode; r.t0 = t0; r.t2 = t2; r.h = h; r.o = *o; r.W = W;
-  r.which = which; r.Z = Z; r.un_scratch = false; r.tree = tree;
+  r.t1 = plan.t1; r.dt_loc = 0.f;
+  bool local_pending = false;
+  if (mode != LRNDE_MODE_NONE && (rc = sde_node_local_step(s, r, q, a, plan.e1, &local_pending))) return rc;
+  r.series = std::move(plan.series);
+  if ((rc = sde_node_copy_out(s, r, q, a, local_pending))) return rc;
+  r.valid = true; ++r.gen; r.B = B; r.nfine = nfine; r.K = st->naccept; r.mode = mode; r.t0 = t0; r.t2 = t2; r.h = (t2 - t0) / (float)nfine;
+  r.o = *o; r.W = q.W; r.which = which; r.Z = q.Z; r.un_scratch = false; r.tree = s->tree_on;
   if (which == 2) r.tab = *tab;
   return LRNDE_OK;
 }

@@ -1,6 +1,7 @@
 // lrnde_stepctl.hpp — the scalar arithmetic of every adaptive loop (device + host), stated once: OrdinaryDiffEq's PI
 // step-size controller, the accept snap onto the end time, the proposal floor, loopheader!'s clamp and status checks,
-// and ode_determine_initdt's dt0 rule and tail (DESIGN.md §2 lists which loop uses which form).
+// ode_determine_initdt's dt0 rule and tail, and the SDE loops' controller on the grid of the caller's Brownian path
+// (DESIGN.md §2 lists which loop uses which form).
 //
 // Like lrnde_math.hpp: fixed sequences of IEEE-754 fp32 operations (pow / log10 in fp64 where upstream calls libm),
 // compiled with -ffp-contract=off, so an expression has the same bits wherever it is inlined.  Everything takes and
@@ -122,6 +123,64 @@ LRNDE_HD bool attempt_judge(AttemptLoop& L, float eest) {
     L.dtpropose = pi_propose(L.dt, ps.q, L.dtmax, dt_floor(L.t, L.dtmin));
   }
   return L.accept;
+}
+
+// ---- the SDE loops' controller on the grid of the caller's Brownian path ----
+// Steps are whole grid intervals of length h: position i, step length m intervals, at least one.  dtc: the proposal as a
+// REAL number; the step taken is its floor on the grid.  Growth accumulates in dtc — with qmax = 1.125 a proposal quantised
+// after every step could never leave m = 1.  The block is the device loops' control block (cur: which of the two state
+// buffers is current) and the host loop's state.  status: STEP_OK while running, STEP_DONE at the end of the grid, else an
+// lrnde_status error (STEP_CAPACITY is LRNDE_CAPACITY; asserted where the headers meet).
+enum { STEP_CAPACITY = 5, STEP_DONE = 100 };
+struct SdeCtl { int status, i, m, cur, naccept, nreject, iters, nf; float qold, eest_last, dtc; };
+struct SdeGrid { PiConsts pi; float h; int nfine, maxiters; };
+// a fresh solve: dt0 quantised to the grid; iters counts the first attempt (the caller refuses maxiters < 1)
+LRNDE_HD SdeCtl sde_grid_begin(float dt0, float h, int nfine) {
+  int m0 = (int)(dt0 / h); if (m0 < 1) m0 = 1;
+  if (m0 > nfine) m0 = nfine;
+  SdeCtl c;
+  c.status = STEP_OK; c.i = 0; c.m = m0; c.cur = 0; c.naccept = 0; c.nreject = 0; c.iters = 1; c.nf = 0;
+  c.qold = QOLDINIT; c.eest_last = 0.f; c.dtc = dt0;
+  return c;
+}
+// One attempt's verdict.  eest, dt: the attempt's estimate and length; qpow = fastpow(c.qold, g.pi.beta2) (it does not depend on
+// eest: a loop that waits for the estimate computes it meanwhile); nfa: the attempt's drift evaluations, what nf counts;
+// rec_cap: slots of the caller's record of accepted steps, negative for none.  The caller writes what the result names, with
+// the i and m the block held BEFORE the call: trace row `trace` (-1: none, a NaN estimate) and the pair (i, m) into record
+// slot `rec` (-1: none).  An accepted step that finds the record full sets STEP_CAPACITY and is still counted (naccept, i),
+// iters is not, and neither STEP_DONE nor STEP_MAXITERS replaces the status.
+struct SdeVerdict { int accepted, rec, trace; };
+LRNDE_HD SdeVerdict sde_grid_update(SdeCtl& c, float eest, float dt, float qpow, int nfa, const SdeGrid g, int rec_cap) {
+  SdeVerdict v = {0, -1, -1};
+  c.nf += nfa; c.eest_last = eest;
+  if (eest != eest) { c.status = STEP_DT_NAN; return v; }
+  const float q = pi_step(g.pi, 0, eest, qpow, 1.0f).q;
+  v.accepted = eest <= 1.0f;
+  v.trace = c.naccept + c.nreject;
+  c.dtc = (v.accepted ? fmaxf_(c.dtc, dt) : dt) / q;
+  int mnew = (int)(c.dtc / g.h);
+  if (mnew < 1) mnew = 1;
+  if (v.accepted) {
+    if (rec_cap >= 0) {
+      if (c.naccept < rec_cap) v.rec = c.naccept;
+      else c.status = STEP_CAPACITY;
+    }
+    c.naccept++;
+    c.qold = pi_qold(eest);
+    c.i += c.m;
+    c.cur ^= 1;
+    c.m = mnew;
+    if (c.i >= g.nfine && c.status == STEP_OK) c.status = STEP_DONE;
+  } else {
+    c.nreject++;
+    if (c.m == 1) c.status = STEP_DT_LESS_THAN_MIN;  // the path's grid cannot be refined further
+    else c.m = mnew < c.m ? mnew : c.m - 1;
+  }
+  if (c.status == STEP_OK) {
+    if (c.m > g.nfine - c.i) c.m = g.nfine - c.i;
+    if (++c.iters > g.maxiters) c.status = STEP_MAXITERS;
+  }
+  return v;
 }
 
 // ---- tstops of a solve over (s0, s1), ascending: the end time of the attempt that starts at t ----

@@ -282,6 +282,43 @@ def test_a_grown_record_serves_a_larger_batch(gpu_pkg, first):
     assert all(torch.equal(ba[k], bb[k]) for k in ("dx", "dp_drift", "dp_diff")) and torch.isfinite(ba["dx"]).all() and (ba["dx"] != 0).any()
 
 
+@pytest.mark.parametrize("mode", ["unbiased", "biased"])
+def test_host_loop_grows_a_tree_record_to_the_default_routes_bits(oracle, gpu_pkg, mode):
+    """LRNDE_SDE_HOST_LOOP on the tree: the host-controlled loop finds its 64-slot record full (its own capacity check, ahead of
+    the controller), the layer replaces the record and the solve runs again — series, times, reg_val and counts of the default
+    route (the device controller) bit for bit.  nfine = 256 with the automatic initial dt at tolerance 0.05: the step length
+    grows from one interval under qmax = 1.125 and tests/sde_adaptive_np.py's loop accepts 117 steps on the definition's path
+    (chosen with it on the CPU); the test holds it to > 64 on the materialised path of the device's own normals."""
+    P = gpu_pkg
+    D, H, B, L, tol = 4, 8, 3, 8, 0.05
+    pd, pg = S.sde_params(D, H, 7)
+    pd = (pd * f32(2.0)).astype(f32)
+    x = np.random.default_rng(107).standard_normal((B, D)).astype(f32)
+    h = P.SdeHandle(_desc(P, D, H))
+    h.set_params(pd, pg)
+    z = h.draw_noise(SEED, 1, 1, B, 1.0, False)[0]
+    drift, diff = S.oracle_fields(oracle, D, H, pd, pg)
+    ref = S.sde_node_forward(oracle, "EulerHeun", drift, diff, x, _np_tree(h, SEED, TW, L, B, f32(1.0)), 0.0, 1.0, tol, tol, mode=mode,
+                             t1_or_rand=0.43, z_local=z.cpu().numpy(), maxiters=1000)
+    assert ref["naccept"] > 64, ref["naccept"]
+    h.set_path_tree(SEED)
+
+    def run():
+        r = h.node_forward_record(torch.from_numpy(x).cuda(), None, 0.0, 1.0, tol, tol, mode=mode, t1_or_rand=0.43, z_local=z, nfine=1 << L,
+                                  maxiters=1000)
+        return r, h.last_solve_info()
+
+    (a, ia), (b, ib) = _with_option(P, "LRNDE_SDE_HOST_LOOP", run), run()
+    print(f"{mode}: host loop accepted {a['stats']['naccept']}, rejected {a['stats']['nreject']}, series {len(a['t'])}, reg_val {a['reg_val']:.4g}")
+    assert ia["kind"] == 0 and ib["kind"] == 2
+    assert a["stats"]["naccept"] == b["stats"]["naccept"] == ref["naccept"] and a["stats"]["nreject"] == b["stats"]["nreject"] == ref["nreject"]
+    assert a["stats"] == b["stats"] and a["stats"]["retcode"] == 0
+    assert np.array_equal(_bits(a["t"]), _bits(b["t"])) and len(a["t"]) == (ref["naccept"] + 1 if mode == "biased" else 2)
+    assert torch.equal(a["u"], b["u"]) and torch.isfinite(a["u"]).all()
+    assert _bits(a["reg_val"]) == _bits(b["reg_val"]) and a["reg_val"] != 0
+    assert a["nfe_drift"] == b["nfe_drift"] and a["nfe_diffusion"] == b["nfe_diffusion"]
+
+
 # ---- 4. the model ----
 def test_tree_model_training_step_equals_the_explicit_arrays(gpu_pkg):
     P = gpu_pkg

@@ -1,10 +1,14 @@
 """csrc/lrnde_layer_plan.hpp on the host: the one statement of the layer forwards' bookkeeping (the solve's saveat for a
 mode, the save slot of sol(t1), the "end slot known before the solve" rule, the slot count, the :biased pick, the
 corrected-solution filter, the backward pass's stop list) against an independent restatement in plain Python lists,
-sorted, bisect and np.float32.  Integers and float bit patterns are compared exactly; no tolerances."""
+sorted, bisect and np.float32; and the SDE layer's series plan on its accepted steps against the series rules of
+tests/sde_adaptive_np.py (series_plan: the function that helper's forward calls).  Integers and float bit patterns are
+compared exactly; no tolerances."""
 import bisect, itertools, os, subprocess, textwrap
 import numpy as np
 import pytest
+
+import sde_adaptive_np as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -14,6 +18,7 @@ SRC = textwrap.dedent(r'''
     #include "lrnde_layer_plan.hpp"
     #include <cstdio>
     #include <cstring>
+    #include <initializer_list>
     using namespace lrnde;
     static float rd() { unsigned u = 0; if (scanf("%x", &u) != 1) u = 0; float x; memcpy(&x, &u, 4); return x; }
     static unsigned bits(float x) { unsigned u; memcpy(&u, &x, 4); return u; }
@@ -36,6 +41,27 @@ SRC = textwrap.dedent(r'''
           std::vector<float> ts(n);
           for (float& x : ts) x = rd();
           row(backward_stops(ts, t0, t2));
+        } else if (kind[0] == 'E') {   // E t0 t2 nfine mode save_start t1_or_rand K (i m)[K] nuser user[nuser] -> the SDE layer's series plan
+          struct Step { int x, y; };
+          const float t0 = rd(), t2 = rd(); int nfine, mode, save_start, K, nuser;
+          if (scanf("%d %d %d", &nfine, &mode, &save_start) != 3) return 2;
+          const float r = rd();
+          if (scanf("%d", &K) != 1) return 2;
+          std::vector<Step> im(K);
+          for (Step& e : im) if (scanf("%d %d", &e.x, &e.y) != 2) return 2;
+          if (scanf("%d", &nuser) != 1) return 2;
+          std::vector<float> user(nuser);
+          for (float& x : user) x = rd();
+          const SdeSeriesPlan p = sde_series_plan(t0, t2, nfine, im.data(), K, mode, r, save_start, user.data(), nuser);
+          printf("%d", p.status);
+          if (p.status == SERIES_OK) {
+            printf(" %08x %08x %d %08x", bits(p.t1), bits(p.e1.t), p.e1.k, bits(p.e1.theta));
+            for (const std::vector<SdeSeriesEntry>* v : {&p.sol, &p.series}) {
+              printf(" %d", (int)v->size());
+              for (const SdeSeriesEntry& e : *v) printf(" %08x %d %08x", bits(e.t), e.k, bits(e.theta));
+            }
+          }
+          printf("\n");
         } else {   // P mode save_start maxiters t0 t1 t2 nuser user[nuser]
           int mode, save_start, maxiters, nuser;
           if (scanf("%d %d %d", &mode, &save_start, &maxiters) != 3) return 2;
@@ -219,3 +245,70 @@ def test_backward_stops(driver):
         assert ln == vec(stops(ts, T0, T2)), (name, ln)
     assert stops(cases["at_t0_and_t2"], T0, T2) == [-0.25] and stops(cases["repeated"], T0, T2) == [-0.75, -0.5, -0.5, -0.5, -0.25]
     assert stops(cases["only_ends"], T0, T2) == []
+
+
+# ---- the SDE layer's series on the accepted steps of its solve ----
+ST0, ST2, NF = 0.25, 1.75, 24    # h = 1/16
+SERIES_OK, T1_OUTSIDE, SAVES_NOTHING, BIASED_NEEDS_TWO, T1_AT_END = range(5)
+REFUSALS = {"t1 outside tspan": T1_OUTSIDE, "the solve saves nothing": SAVES_NOTHING, ":biased needs at least two saved times": BIASED_NEEDS_TWO,
+            "t1 must lie before the end of tspan": T1_AT_END}
+MODES = {NONE: "none", UNBIASED: "unbiased", BIASED: "biased"}
+STEPS = {"single": [(0, 24)], "uneven": [(0, 1), (1, 5), (6, 2), (8, 11), (19, 5)], "overshoot": [(0, 7), (7, 9), (16, 11)]}
+T1 = 0.8125   # inside a step of every list, on a grid point of none's end
+
+
+def series_saveats(steps):
+    h = f32(f32(f32(ST2) - f32(ST0)) / f32(NF))
+    i, m = steps[len(steps) // 2]
+    inside = f32(f32(ST0) + f32(f32(i) + f32(0.5) * f32(m)) * h)      # strictly inside the middle step
+    i0, m0 = steps[0]
+    end0 = f32(ST2) if i0 + m0 >= NF else f32(f32(ST0) + f32(i0 + m0) * h)   # the first step's end as the plan computes it
+    il, ml = steps[-1]
+    behind = float(np.nextafter(f32(f32(ST0) + f32(min(il + ml, NF)) * h), f32(-1)))   # just behind the grid's end, where tk1 is t2 itself
+    return {"none": [], "ends_and_mid": [ST0, 1.0, ST2], "equals_t1": [0.5, T1, 1.5], "inside_a_step": [float(inside)],
+            "a_steps_end": sorted([float(end0), 1.5]), "behind_the_last_step": [behind, ST2]}
+
+
+def series_line(t0, t2, nfine, mode, save_start, r, steps, user):
+    return "E %s %s %d %d %d %s %d %s %s\n" % (hx(t0), hx(t2), nfine, mode, save_start, hx(r), len(steps), " ".join("%d %d" % s for s in steps), vec(user))
+
+
+def series_want(t0, t2, nfine, mode, save_start, r, steps, user):
+    try:
+        sol, e1, t1, series = S.series_plan(t0, t2, nfine, steps, MODES[mode], r, save_start, user)
+    except AssertionError as e:
+        return str(REFUSALS[str(e)]), None
+    if e1 is None:
+        e1 = (f32(t2), len(steps) - 1, f32(1))   # (:none has no local step: the end of the solve)
+    ent = lambda e: "%s %d %s" % (hx(e[0]), e[1], hx(e[2]))
+    return " ".join([str(SERIES_OK), hx(t1), ent(e1)] + [" ".join([str(len(v))] + [ent(e) for e in v]) for v in (sol, series)]), (sol, e1, series)
+
+
+def test_sde_series_plan(driver):
+    cases = [(mode, ss, r, sn, un) for mode, ss, sn in itertools.product((NONE, UNBIASED, BIASED), (-1, 0, 1), STEPS)
+             for un in series_saveats(STEPS[sn]) for r in ((T1,) if mode == UNBIASED else (0.0, 0.6) if mode == BIASED else (0.5,))]
+    out = driver("".join(series_line(ST0, ST2, NF, mode, ss, r, STEPS[sn], series_saveats(STEPS[sn])[un]) for mode, ss, r, sn, un in cases))
+    seen = set()
+    for (mode, ss, r, sn, un), ln in zip(cases, out):
+        want, parts = series_want(ST0, ST2, NF, mode, ss, r, STEPS[sn], series_saveats(STEPS[sn])[un])
+        assert ln == want, ((mode, ss, r, sn, un), ln, want)
+        if parts is None:
+            seen.add(("refused", int(want)))
+            continue
+        sol, e1, series = parts
+        seen.add(("start", sol[0][1] == -1)), seen.add(("dropped", len(sol) - len(series)))
+        seen |= {("theta", "inside" if 0 < e[2] < 1 else "end") for e in sol if e[1] >= 0}
+        seen |= {("e1", "inside" if 0 < e1[2] < 1 else "end" if e1[1] >= 0 else "start")}
+        if un == "a_steps_end" and ss == 0:   # an entry equal to a step's end is that step's end state, not the next step's start
+            assert [(e[1], e[2]) for e in sol if e[0] == series_saveats(STEPS[sn])[un][0 if sn != "single" else 1]] == [(0, 1)]
+        if un == "behind_the_last_step" and mode == NONE and ss == 0:   # inside the last step, then t2 itself: theta < 1, then 1
+            assert sol[0][1] == sol[1][1] == len(STEPS[sn]) - 1 and 0 < sol[0][2] < 1 and sol[1][2] == 1 and sol[1][0] == f32(ST2)
+    assert seen >= {("start", True), ("start", False), ("dropped", 0), ("dropped", 1), ("dropped", 2), ("theta", "inside"), ("theta", "end"),
+                    ("e1", "inside"), ("e1", "end"), ("e1", "start"), ("refused", BIASED_NEEDS_TWO)}, seen
+    # the four refusals, each alone: t1 past the span; every step of a solve that took none; one saved time; t1 at the end
+    refusals = [((UNBIASED, -1, 2.0, [(0, 24)], []), T1_OUTSIDE), ((UNBIASED, -1, float("nan"), [(0, 24)], []), T1_OUTSIDE),
+                ((BIASED, 0, 0.5, [], []), SAVES_NOTHING), ((BIASED, 0, 0.5, [(0, 24)], [1.0]), BIASED_NEEDS_TWO),
+                ((UNBIASED, -1, ST2, [(0, 24)], []), T1_AT_END), ((UNBIASED, 1, ST2, [(0, 24)], [0.5]), T1_AT_END)]
+    out = driver("".join(series_line(ST0, ST2, NF, mode, ss, r, steps, user) for (mode, ss, r, steps, user), _ in refusals))
+    for ((mode, ss, r, steps, user), code), ln in zip(refusals, out):
+        assert ln == str(code) == series_want(ST0, ST2, NF, mode, ss, r, steps, user)[0], (mode, ss, r, steps, user, ln)
