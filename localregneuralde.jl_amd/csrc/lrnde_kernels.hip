@@ -53,6 +53,9 @@
 #include "lrnde_report.hpp"
 #include "lrnde_buf.hpp"
 #include "lrnde_comm.hpp"
+#include "lrnde_dev.hpp"       // f32x4, Ctrl, PSTRIDE, SEGK, mfma4, the partial-sum reduction: shared with the SDE step kernels
+#include "lrnde_sde_tree.hpp"  // SdeTree and the tree descent
+#include "lrnde_sde_fast.hpp"  // SdeFastArgs and the four launch functions of lrnde_sde_{eh,mil,sri}_fast.hip
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
               "header_status returns lrnde_status values");
@@ -66,10 +69,6 @@ using namespace lrnde;
 constexpr int NB = 16;       // batch columns per workgroup tile = MFMA N
 constexpr int NW = 8;        // waves per workgroup
 constexpr int NT = NW * 64;  // threads per workgroup
-constexpr int PSTRIDE = 4;   // doubles per workgroup in a partial-sum vector
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 enum { MODE_SOLVE = 0, MODE_SINGLE_GIVEN_DT = 1, MODE_SINGLE_INIT_DT = 2, MODE_BENCH = 3 };
 
 struct ModelDev {
@@ -117,18 +116,6 @@ __device__ unsigned long long g_wstamps[8 * 8];
 #define STAMPW(i) __builtin_amdgcn_sched_barrier(0)
 #define PSTAMP(i) do { } while (0)
 #endif
-
-struct Ctrl {  // device-resident integrator state, double-buffered by attempt parity
-  int status, first;
-  int iter, naccept, nreject, nf;
-  int cur;  // uprev = ubuf[cur], k1 = kfsal[cur]; the step writes u -> ubuf[cur^1], k7 -> kfsal[cur^1]
-  int isave, nsaved;
-  float t, dt;  // start time and dt of the last attempted step
-  float qold, q11, dtpropose;
-  float eest_last, dt_init;
-  float reg_error, reg_stiff;  // single-step modes: filled by k_finalize
-  float stiff_num, stiff_den;  // ||k7-k6||_rms, ||u-g6||_rms (for the regulariser's reverse sweep)
-};
 
 // The controller's part of Ctrl: exactly 16 dwords, one s_load_dwordx16.  The step prologue reads and writes only this
 // (as a whole Ctrl the last four floats came through a vector load that was waited for — and spilled — before the
@@ -283,25 +270,6 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// The same sum with DPP row operations instead of ds_bpermute shuffles (a double is two of them per step, six dependent
-// steps): four v_add_f64 on DPP-moved halves give every lane its 16-lane row total, the four row totals are read with
-// v_readlane and added in row order.  The total is wave-uniform.  (A different — still fixed — order of fp64 adds.)
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double wave_sum_dpp(double v) {
-  v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);  // row_half_mirror
-  v += dpp_f64<0x140>(v);  // row_mirror
-  return ((readlane_f64(v, 0) + readlane_f64(v, 16)) + readlane_f64(v, 32)) + readlane_f64(v, 48);
-}
-
 // fixed-order block reduction of up to 3 doubles; result valid on thread 0
 __device__ __forceinline__ void block_sum3(double* red, double& a, double& b, double& c) {
   const int lane = threadIdx.x & 63;
@@ -317,74 +285,14 @@ __device__ __forceinline__ void block_sum3(double* red, double& a, double& b, do
   __syncthreads();
 }
 
-// every workgroup reduces the global partial vector in the same fixed order (wave 0)
-struct Sum3 { double a, b, c; };
-__device__ __forceinline__ Sum3 reduce_partials3(const double* p, int nwg);
+// every workgroup reduces the global partial vector in the same fixed order (wave 0; reduce_partials3: lrnde_dev.hpp)
 __device__ __forceinline__ void reduce_partials(const double* p, int nwg, double out[3]) {
   const Sum3 r = reduce_partials3(p, nwg);
   out[0] = r.a; out[1] = r.b; out[2] = r.c;
 }
-// (the loads and the sum are separate calls so that a caller can put other loads in flight between them; ALL = false
-// reads the first sum of each triple only — the step prologue's error norm.  A loaded-but-unused value is not free here:
-// its destination register is reused at once and the reuse waits for the load.)
-struct PartLoads { double va[4], vb[4], vc[4]; };
-template <bool ALL> __device__ __forceinline__ void part_issue(PartLoads& L, const double* p, int nwg) {
-  const int lane = threadIdx.x & 63;
-  // agent-scope loads (the vector was written by the previous launch / by RCCL), four workgroups' triples per lane in
-  // flight at once: this reduction opens every step launch, one round trip per loop trip was on its critical path.
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int i = lane + 64 * u;
-    const size_t o = (size_t)(i < nwg ? i : 0) * PSTRIDE;
-    L.va[u] = __hip_atomic_load(p + o + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (ALL) {
-      L.vb[u] = __hip_atomic_load(p + o + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      L.vc[u] = __hip_atomic_load(p + o + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-template <bool ALL> __device__ __forceinline__ Sum3 part_finish(const PartLoads& L, const double* p, int nwg) {
-  const int lane = threadIdx.x & 63;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  // The adds run in the same order as a plain loop over i = lane, lane + 64, ...
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-    if (lane + 64 * u < nwg) { s0 += L.va[u]; if (ALL) { s1 += L.vb[u]; s2 += L.vc[u]; } }
-  for (int i0 = lane + 256; i0 < nwg; i0 += 256) {
-    double va[4], vb[4] = {0.0, 0.0, 0.0, 0.0}, vc[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + 64 * u;
-      const size_t o = (size_t)(i < nwg ? i : i0) * PSTRIDE;
-      va[u] = __hip_atomic_load(p + o + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (ALL) {
-        vb[u] = __hip_atomic_load(p + o + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        vc[u] = __hip_atomic_load(p + o + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (i0 + 64 * u < nwg) { s0 += va[u]; if (ALL) { s1 += vb[u]; s2 += vc[u]; } }
-  }
-  // lane totals -> wave total with DPP row operations (wave-uniform result; fp64 sums of fp32 squares: the rounded fp32
-  // norm does not depend on the order of these adds)
-  Sum3 r;
-  r.a = wave_sum_dpp(s0);
-  r.b = ALL ? wave_sum_dpp(s1) : 0.0;
-  r.c = ALL ? wave_sum_dpp(s2) : 0.0;
-  return r;
-}
-__device__ __forceinline__ Sum3 reduce_partials3(const double* p, int nwg) {
-  PartLoads L;
-  part_issue<true>(L, p, nwg);
-  return part_finish<true>(L, p, nwg);
-}
-
 // A workgroup hands in its three fp64 partial sums (valid on thread 0).  which = 0/1: the step's parity block of
 // part_send; 2/3: init phase 1/2 block of pinit_send.  Gather mode: thread 0 writes the tile's entry of the exchanged
 // vector.  prered mode: see StepArgs — the last workgroup to arrive reduces the rank's tiles and writes the rank's slot.
-__device__ __forceinline__ float rms_from(double sumsq, double n) { return (float)sqrt(sumsq / n); }
-
 __device__ __forceinline__ void publish_partial(const StepArgs& a, int which, double s0, double s1, double s2) {
   const size_t blk = (size_t)(which & 1);
   double* send = (which < 2 ? a.part_send : a.pinit_send) + blk * (size_t)a.nwg_global * PSTRIDE;
@@ -443,16 +351,7 @@ __device__ __forceinline__ void publish_partial(const StepArgs& a, int which, do
 #else
 #define LRNDE_D2ACC() do {} while (0)
 #endif
-constexpr int SEGK = 7;  // k-groups (of 16 rows) per canonical segment
 constexpr int TG = 7;    // M tiles run concurrently by one wave in Dense 1
-
-__device__ __forceinline__ f32x4 mfma4(const f32x4& a, const f32x4& b, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-  return acc;
-}
 
 struct Smem {
   float* xl;   // x tile, B-operand image of Dense 1            [KG1][64][4]
@@ -1619,10 +1518,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
   }
 }
 
-#include "lrnde_sde_tree.hpp"
-#include "lrnde_sde_fast.hpp"
-#include "lrnde_sde_mil_fast.hpp"
-#include "lrnde_sde_sri_fast.hpp"
+#include "lrnde_sde_tree_kernels.hpp"
 #include "lrnde_qtile.hpp"
 #include "lrnde_adjoint.hpp"
 #include "lrnde_backward.hpp"

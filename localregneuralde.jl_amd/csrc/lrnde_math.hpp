@@ -67,7 +67,7 @@ LRNDE_HD float tanhf_c(float x) {
 
 // tanhf_c without control flow: both pieces evaluated, the result selected — the same operations on the same inputs for the
 // piece that counts, so the same bits.  For code that applies the activation to several independent elements per lane: the
-// branches of tanhf_c keep the compiler from interleaving the elements' dependent chains (lrnde_sde_fast.hpp: 1.9k of a
+// branches of tanhf_c keep the compiler from interleaving the elements' dependent chains (lrnde_sde_eh_fast.hip: 1.9k of a
 // round's 3.5k cycles were four serial tanh).
 LRNDE_HD float tanhf_sel(float x) {
   const float ax = __builtin_fabsf(x);

@@ -15,7 +15,7 @@
 // GEMM pairs, elementwise joins): 112 us per step at the MNIST-SDE shape against ~1 us here.
 //
 // Shapes: drift Chain(Dense(D => H, act), Dense(H => D)) without a time input, diffusion Dense(D => D), D <= 64, H <= 128 —
-// those of the one-launch forward kernel (lrnde_sde_fast.hpp).  Arithmetic: plain fp32 fma chains over the input index in
+// those of the one-launch forward kernel (lrnde_sde_frame.hpp).  Arithmetic: plain fp32 fma chains over the input index in
 // increasing order; the forward values are RECOMPUTED here in that order (the forward kernel's canonical MFMA chains differ
 // in the last bits), which is inside the gradient's bar — tests/test_gpu_sde_layer.py holds the result to 5e-6 of float64
 // autograd over the recorded grid, and to the generic path (LRNDE_NO_SDE_BWD_FUSED=1).

@@ -1,10 +1,11 @@
-// lrnde_sde_mil_fast.hpp — one ATTEMPTED step of the adaptive Milstein solve (RKMilCommute, diagonal noise, Ito:
+// lrnde_sde_mil_fast.hip — one ATTEMPTED step of the adaptive Milstein solve (RKMilCommute, diagonal noise, Ito:
 // src/perform_step.jl:108-170) as ONE launch with the step-size controller in its footer, for the shapes of
 // lrnde_sde_fast.hpp (drift Chain(Dense(D => H, act), Dense(H => D)) without a time input, diffusion Dense(D => D),
-// D <= 64, H <= 128).  Included by lrnde_kernels.hip inside its anonymous namespace, after lrnde_sde_fast.hpp, whose
-// argument struct (SdeFastArgs), control block (SdeCtl), workgroup frame (SdeFrame: the layout, the resident weight fragments,
-// dense1 / diffusion / dense2), footer (sde_step_footer) and launch dispatch (sde_fast_dispatch) it uses; nothing goes through
-// global memory between the first load of (u, W[i], W[i + m]) and the store of u_new.
+// D <= 64, H <= 128).  A translation unit of its own: the library calls sde_mil_fast_launch (lrnde_sde_fast.hpp, with the
+// argument struct SdeFastArgs); the control block (SdeCtl) is lrnde_stepctl.hpp's, the workgroup frame (SdeFrame: the layout, the
+// resident weight fragments, dense1 / diffusion / dense2), the footer (sde_step_footer) and the launch dispatch
+// (sde_fast_dispatch) are lrnde_sde_frame.hpp's; nothing goes through global memory between the first load of
+// (u, W[i], W[i + m]) and the store of u_new.
 // The step is two rounds instead of Euler-Heun's three:
 //   1. du1 = f(u), L = g(u)                                  (:130-131)
 //   2. gtmp = g(K + sqrt(dt) L),  K = u + dt du1             (:133-138; no drift evaluation: du2 / En are dead code in the
@@ -16,6 +17,13 @@
 // of k_sde_rkmil and of the oracle's rkmil_step.
 // Footer: sde_step_footer with one drift evaluation per attempt.  The host keeps launches enqueued (sde_adaptive_device);
 // there is no persistent form of this kernel.
+#include <hip/hip_runtime.h>
+
+#include "lrnde_sde_frame.hpp"
+
+namespace {
+
+using namespace lrnde;
 
 // TREE: dW from the virtual tree (lrnde_sde_tree.hpp) instead of a.Wpath, recorded beside rec_u.
 template <int DT, int HT, bool TREE = false>
@@ -92,9 +100,15 @@ __global__ __launch_bounds__(SF_NT) void k_sde_mil_fast(SdeFastArgs a) {
   sde_step_footer<DT>(a, red, dt, true, 1);
 }
 
-inline void sde_mil_fast_launch(int D, int H, int nwg, hipStream_t st, const SdeFastArgs& f) {
+}  // namespace
+
+namespace lrnde {
+
+void sde_mil_fast_launch(int D, int H, int nwg, hipStream_t st, const SdeFastArgs& f) {
   sde_fast_dispatch(D, H, [&](auto dt, auto ht) {
     if (f.tree.on) hipLaunchKernelGGL((k_sde_mil_fast<dt.value, ht.value, true>), dim3(nwg), dim3(SF_NT), 0, st, f);
     else hipLaunchKernelGGL((k_sde_mil_fast<dt.value, ht.value>), dim3(nwg), dim3(SF_NT), 0, st, f);
   });
 }
+
+}  // namespace lrnde

@@ -121,7 +121,7 @@ int sde_init_dt(lrnde_sde* s, const float* u, int B, float t, float tend, float 
 
 // sde_init_dt without the two host synchronisations and in three launches instead of nine, for the one-launch step's shape
 // (no time input: the evaluations at t + dt0 do not need dt0 on the host).  The four evaluations and the three norms run on
-// k_sde_eh_fast's tiles (its idt_phase 1 / 2: lrnde_sde_fast.hpp), the scalar tail in k_sde_initdt_fin — the expressions of
+// k_sde_eh_fast's tiles (its idt_phase 1 / 2: lrnde_sde_eh_fast.hip), the scalar tail in k_sde_initdt_fin — the expressions of
 // the host code above, fp64 sums in the partial-vector order every reduction here uses — and the result stays on the
 // device: scal[0] = dt0, scal[1] = d1, scal[2] = the initial dt.  The tail also starts what consumes the dt (SdeInitDtFor):
 // the adaptive solve's control block on its grid of nfine intervals of h, a single step's Ctrl pair, or nothing.

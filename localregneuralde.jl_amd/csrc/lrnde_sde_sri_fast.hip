@@ -1,10 +1,10 @@
-// lrnde_sde_sri_fast.hpp — one ATTEMPTED step of the adaptive four-stage SRI solve (FourStageSRIConstantCache, diagonal
+// lrnde_sde_sri_fast.hip — one ATTEMPTED step of the adaptive four-stage SRI solve (FourStageSRIConstantCache, diagonal
 // noise: src/perform_step.jl:49-106 — the step the reference's default solver SOSRI runs) as ONE launch with the step-size
 // controller in its footer, for the shapes of lrnde_sde_fast.hpp (drift Chain(Dense(D => H, act), Dense(H => D)) without a
-// time input, diffusion Dense(D => D), D <= 64, H <= 128).  Included by lrnde_kernels.hip inside its anonymous namespace,
-// after lrnde_sde_mil_fast.hpp; argument struct (SdeFastArgs, whose `tab` is the caller's tableau by value), control block
-// (SdeCtl), workgroup frame (SdeFrame: the layout, the resident weight fragments, dense1 / diffusion / dense2), footer
-// (sde_step_footer) and launch dispatch (sde_fast_dispatch) are lrnde_sde_fast.hpp's.
+// time input, diffusion Dense(D => D), D <= 64, H <= 128).  A translation unit of its own: the library calls
+// sde_sri_fast_launch (lrnde_sde_fast.hpp, with the argument struct SdeFastArgs, whose `tab` is the caller's tableau by value);
+// the control block (SdeCtl) is lrnde_stepctl.hpp's, the workgroup frame (SdeFrame: the layout, the resident weight fragments,
+// dense1 / diffusion / dense2), the footer (sde_step_footer) and the launch dispatch (sde_fast_dispatch) are lrnde_sde_frame.hpp's.
 //
 // Nothing goes through global memory between the loads of (u, W[i], W[i + m], Z[i], Z[i + m]) and the store of
 // u_new.  The step is four rounds; round j = 1..4:
@@ -19,6 +19,13 @@
 // padded rows and columns contribute nothing.
 // Footer: sde_step_footer with four drift evaluations per attempt.  The host keeps launches enqueued (sde_adaptive_device);
 // there is no persistent form of this kernel.
+#include <hip/hip_runtime.h>
+
+#include "lrnde_sde_frame.hpp"
+
+namespace {
+
+using namespace lrnde;
 
 // TREE: dW and dZ from the virtual trees of streams 6 and 7 (lrnde_sde_tree.hpp) instead of a.Wpath / a.Zpath, recorded beside rec_u.
 template <int DT, int HT, bool TREE = false>
@@ -153,9 +160,15 @@ __global__ __launch_bounds__(SF_NT) void k_sde_sri_fast(SdeFastArgs a) {
   sde_step_footer<DT>(a, red, dt, true, 4);
 }
 
-inline void sde_sri_fast_launch(int D, int H, int nwg, hipStream_t st, const SdeFastArgs& f) {
+}  // namespace
+
+namespace lrnde {
+
+void sde_sri_fast_launch(int D, int H, int nwg, hipStream_t st, const SdeFastArgs& f) {
   sde_fast_dispatch(D, H, [&](auto dt, auto ht) {
     if (f.tree.on) hipLaunchKernelGGL((k_sde_sri_fast<dt.value, ht.value, true>), dim3(nwg), dim3(SF_NT), 0, st, f);
     else hipLaunchKernelGGL((k_sde_sri_fast<dt.value, ht.value>), dim3(nwg), dim3(SF_NT), 0, st, f);
   });
 }
+
+}  // namespace lrnde

@@ -1,7 +1,8 @@
 // lrnde_sde_tree.hpp — the Brownian path of the adaptive SDE solves as a VIRTUAL tree: W at a grid index is a
-// pure function of (seed, stream, column, index), so no (nfine + 1) x B x D array has to exist.  Included by lrnde_kernels.hip
-// inside its anonymous namespace, ahead of lrnde_sde_fast.hpp; also the home of the Philox-4x32-10 block and the Box-Muller
-// pair that lrnde_noise.hpp draws with (one definition for both).
+// pure function of (seed, stream, column, index), so no (nfine + 1) x B x D array has to exist.  Included by every translation
+// unit that queries the tree (lrnde_kernels.hip and the TREE instantiations of the one-launch step kernels); also the home of
+// the Philox-4x32-10 block and the Box-Muller pair that lrnde_noise.hpp draws with (one definition for both).  The two kernels
+// that only lrnde_kernels.hip launches are in lrnde_sde_tree_kernels.hpp.
 //
 // Definition (include/lrnde.h states it for callers; tests/brownian_tree_np.py restates it in numpy).  nfine = 2^L, L <= 20,
 // span = t2 - t0 (float32), column c = b*D + d, z[n] = standard normal n of column c in the stream — counter (n >> 2, c, stream, 0),
@@ -13,9 +14,37 @@
 // s_l on the device: a power of four under the square root leaves it as a power of two, and a power of two commutes with both
 // roundings, so s_l = s_1 2^-((l-1)/2) for odd l and s_2 2^-((l-2)/2) for even l, exactly (no span whose s_20 is subnormal is
 // of interest: span > 2^-100).  The host computes sT, s_1 and s_2 in float64 and the kernels scale them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+namespace lrnde {
 
 constexpr uint32_t TREE_STREAM_W = 6, TREE_STREAM_Z = 7;   // the trees of W and of SRI's second path Z (streams 0..5: lrnde.h)
 constexpr int TREE_MAXL = 20;
+
+// the path source of a launch, by value in its arguments.  rec_dw / rec_dz: the recording forward leaves the accepted step's
+// increments in slot naccept (beside rec_u), which is all a backward route reads
+struct SdeTree {
+  int on;             // 0: the caller's array (every field below unused)
+  uint32_t k0, k1;    // Philox key: (seed & 0xffffffff, seed >> 32)
+  int L;              // nfine = 2^L
+  float sT, s1, s2;   // sqrt(span), s_1, s_2 (host float64, rounded once)
+  float* rec_dw; float* rec_dz;
+};
+inline void sde_tree_scales(SdeTree& T, float span) {
+  T.sT = (float)sqrt((double)span);
+  T.s1 = (float)(0.5 * sqrt((double)span));
+  T.s2 = (float)(0.5 * sqrt((double)span * 0.5));
+}
+
+}  // namespace lrnde
+
+namespace {
+
+using namespace lrnde;
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t x[4]) {
@@ -37,21 +66,6 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, fl
   const double th = 6.283185307179586 * noise_u01(b);
   z0 = (float)(r * cos(th));
   z1 = (float)(r * sin(th));
-}
-
-// the path source of a launch, by value in its arguments.  rec_dw / rec_dz: the recording forward leaves the accepted step's
-// increments in slot naccept (beside rec_u), which is all a backward route reads
-struct SdeTree {
-  int on;             // 0: the caller's array (every field below unused)
-  uint32_t k0, k1;    // Philox key: (seed & 0xffffffff, seed >> 32)
-  int L;              // nfine = 2^L
-  float sT, s1, s2;   // sqrt(span), s_1, s_2 (host float64, rounded once)
-  float* rec_dw; float* rec_dz;
-};
-inline void sde_tree_scales(SdeTree& T, float span) {
-  T.sT = (float)sqrt((double)span);
-  T.s1 = (float)(0.5 * sqrt((double)span));
-  T.s2 = (float)(0.5 * sqrt((double)span * 0.5));
 }
 
 // standard normal n of column c (lrnde_sde_draw_noise's normal n: the pair of its word, cos for even words and sin for odd)
@@ -95,43 +109,4 @@ __device__ __forceinline__ void tree_query(const SdeTree& T, uint32_t stream, co
   for (int r = 0; r < R; ++r) w[r] = wb[r];
 }
 
-// dW[e] = W[i + m] - W[i] of element e = column e of a (B, D) array (k_sde_dw's subtraction): the host-controlled loops' increment
-__global__ __launch_bounds__(256) void k_sde_dw_tree(size_t n, SdeTree T, uint32_t stream, int i, int m, float* __restrict__ dW) {
-  for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-    const uint32_t c[1] = {(uint32_t)e};
-    float hi[1], lo[1];
-    tree_query<1>(T, stream, c, i + m, hi);
-    tree_query<1>(T, stream, c, i, lo);
-    dW[e] = hi[0] - lo[0];
-  }
-}
-
-// The whole array the definition gives, out (nfine + 1) x ncols row-major: one thread per column walks the nodes in heap order
-// (parents before children), four normals per Philox block; rows are written one column per thread (coalesced), a node's
-// two ends are this thread's own earlier stores.  64-bit indexing.
-__global__ __launch_bounds__(256) void k_sde_tree_path(SdeTree T, uint32_t stream, uint32_t ncols, float* __restrict__ out) {
-  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-  if (c >= ncols) return;
-  const uint32_t nfine = 1u << T.L;
-  volatile float* o = out;   // (read back below: no value is kept across the stores)
-  o[c] = 0.f;
-  for (uint32_t q = 0; q < (nfine + 3u) >> 2; ++q) {
-    uint32_t x[4];
-    philox4x32_10(q, c, stream, 0u, T.k0, T.k1, x);
-    float z[4];
-    box_muller(x[0], x[1], z[0], z[1]);
-    box_muller(x[2], x[3], z[2], z[3]);
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const uint32_t n = 4u * q + (uint32_t)w;
-      if (n >= nfine) break;
-      if (n == 0u) { o[(size_t)nfine * ncols + c] = __fmul_rn(T.sT, z[0]); continue; }
-      const int l = 32 - __clz((int)n);                 // level: 2^(l-1) <= n < 2^l
-      const uint32_t j = n - (1u << (l - 1));
-      const uint32_t half = nfine >> l, a = j * (2u * half), mid = a + half, b = mid + half;
-      const float sl = ldexpf((l & 1) ? T.s1 : T.s2, -((l - 1) >> 1));
-      const float wa = o[(size_t)a * ncols + c], wb = o[(size_t)b * ncols + c];
-      o[(size_t)mid * ncols + c] = __fadd_rn(__fmul_rn(0.5f, __fadd_rn(wa, wb)), __fmul_rn(sl, z[w]));
-    }
-  }
-}
+}  // namespace

@@ -1,5 +1,5 @@
 """The adaptive SRI solve as one launch per attempted step with the controller on the device (k_sde_sri_fast,
-csrc/lrnde_sde_sri_fast.hpp), through the C ABI.
+csrc/lrnde_sde_sri_fast.hip), through the C ABI.
 
 * the same bits on three routes: the fused kernel under the device controller (default), the host-controlled loop on
   lrnde_sde_sri_step (LRNDE_SDE_HOST_LOOP=1, the route every SRI solve took before), and lrnde_sde_sri_step fed the recorded

@@ -91,7 +91,7 @@ def expected(fp, dt0, h, nfine, maxiters, consts, rec_cap, nfa, eests):
     every update while the solve runs.  The controller is sde_adaptive_np's; around it, what the control block keeps beside it:
     nf and eest_last of every attempt (a NaN one too), the buffer flip, maxiters as a status, and the record slot.
     rec_cap >= 0: an accepted step that finds the record full is the device loops' CAPACITY — written from the
-    device form (sde_ctl_update, lrnde_sde_fast.hpp): the step is still counted (naccept, i, the buffer flip, m = the proposal's floor, NOT clamped to the rest of
+    device form (sde_ctl_update, lrnde_sde_frame.hpp): the step is still counted (naccept, i, the buffer flip, m = the proposal's floor, NOT clamped to the rest of
     the grid), iters is not, and neither DONE nor MAXITERS replaces the status."""
     consts = tuple(f32(v) for v in consts)
     h = f32(h)

@@ -7,6 +7,9 @@
 // segments of 112 rows, partials added left to right, then the time column by fma, then the bias).
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I include tools/cluster_probe.hip -o tools/tmp/cluster_probe -lrccl
 #include "../localregneuralde.jl_amd/csrc/lrnde_kernels.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_eh_fast.hip"   // (the library's other translation units: one-launch SDE step kernels)
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_mil_fast.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_sri_fast.hip"
 #include <vector>
 #include <cstdio>
 

@@ -2,6 +2,9 @@
 // that every launch but the trailing ones is a full step: HIP-event time of the solve / attempted steps, next to the
 // timing hook's back-to-back figure.  Build twice to A/B a compile-time switch (e.g. -DLRNDE_NO_PRELOAD).
 #include "../localregneuralde.jl_amd/csrc/lrnde_kernels.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_eh_fast.hip"   // (the library's other translation units: one-launch SDE step kernels)
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_mil_fast.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_sri_fast.hip"
 #include <vector>
 #include <cstdio>
 #include <algorithm>

@@ -1,6 +1,9 @@
 // Diagnostic probe (not shipped): builds the library source with -DLRNDE_STAMPS and prints where
 // workgroup 0 of k_rhs spends its cycles, plus the shader clock it ran at.
 #include "../localregneuralde.jl_amd/csrc/lrnde_kernels.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_eh_fast.hip"   // (the library's other translation units: one-launch SDE step kernels)
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_mil_fast.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_sri_fast.hip"
 #include <vector>
 #include <cstdio>
 int main(int argc, char** argv) {

@@ -1,5 +1,8 @@
 // Diagnostic: perform_step with W = 0 and constant biases, so every k_j == b2 and u is analytic.
 #include "../localregneuralde.jl_amd/csrc/lrnde_kernels.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_eh_fast.hip"   // (the library's other translation units: one-launch SDE step kernels)
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_mil_fast.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_sri_fast.hip"
 #include <vector>
 #include <cstdio>
 int main(int argc, char** argv) {

@@ -1,6 +1,9 @@
 // Diagnostic (not shipped): library source with -DLRNDE_STAMPS; runs the layer's forward + continuous adjoint at the MNIST
 // shape and prints where workgroup 0 of a stage-5 launch of the adjoint loop (k_vjp_q_pg) spends its cycles.
 #include "../localregneuralde.jl_amd/csrc/lrnde_kernels.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_eh_fast.hip"   // (the library's other translation units: one-launch SDE step kernels)
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_mil_fast.hip"
+#include "../localregneuralde.jl_amd/csrc/lrnde_sde_sri_fast.hip"
 #include <vector>
 #include <cstdio>
 int main(int argc, char** argv) {

@@ -1,6 +1,6 @@
 // Diagnostic (not shipped): what does a grid barrier that carries one fp64 value per workgroup cost among 32 workgroups
 //   (A) spread over all eight XCDs, agent-scope (sc1) 16-byte store + polling loads — the barrier of the cooperative SDE solve
-//       (k_sde_eh_fast<DT, HT, true>, csrc/lrnde_sde_fast.hpp), and
+//       (k_sde_eh_fast<DT, HT, true>, csrc/lrnde_sde_eh_fast.hip), and
 //   (B) placed on ONE XCD (workgroup k of a 256-workgroup launch goes to XCD k mod 8: the workers are the workgroups with
 //       k mod 8 == 0, the rest exit), exchanging through that XCD's L2 with atomics that carry no scope bit: they execute in
 //       the L2, which every CU of the XCD shares — publish = two 64-bit swaps {sum bits; tag | checksum}, poll = 64-bit
