@@ -53,6 +53,67 @@ __device__ __forceinline__ float q_segment_sum(const float* plf, int ne, int e, 
   return v;
 }
 
+// Epilogue 1 (segment sum, time column, bias, activation of the Dense-1 rows) as straight-line code.  A thread owns the
+// C-fragment element e = threadIdx.x of the RG1 * 256 (r = e & 3, lane l = (e >> 2) & 63, row group e >> 8: row
+// o = 64 rg + 4 (l >> 2) + r of sample l & 3), and what it needs besides the partials depends on the launch alone:
+struct Epi1Q {
+  const float* p0;  // its element of segment 0's partial (LDS); element 0 for a thread that owns none
+  int seg[QNW];     // float offset of segment s's partial from p0, the segments past nseg1 clamped to the last (wave-uniform)
+  unsigned add;     // bit s: segment s exists and is added (wave-uniform)
+  float* h;         // its h slot
+  float w1, b1;     // time column and bias of its row
+  bool valid;       // it owns an element, and the row lies in a Dense-2 quad (o >= H inside the padded quads included)
+  bool two;         // wave-uniform: the wave's threads own a second element, threadIdx.x + QNT, that can hold such a row
+};
+// row of element e / float index of its h slot
+__device__ __forceinline__ int q_epi1_row(int e) { return (e >> 8) * 64 + (((e >> 2) & 63) >> 2) * 4 + (e & 3); }
+__device__ __forceinline__ int q_epi1_slot(int e) { return ((q_epi1_row(e) >> 2) * 4 + ((e >> 2) & 3)) * 4 + (e & 3); }
+// (reads the staged bias vectors: after the barrier that orders smem_init_q / bias_write_q)
+__device__ __forceinline__ Epi1Q q_epi1_make(const ModelDev& m, const SmemQ& sm) {
+  static_assert(2 * QNT >= 512, "two elements per thread cover the 512 of RG1 = 2, the family's limit");
+  const int ne = m.RG1 * 256, nseg1 = q_nseg1(m), h64 = m.RG1 * 64;
+  const bool has = (int)threadIdx.x < ne;
+  const int e = has ? (int)threadIdx.x : 0, o = q_epi1_row(e);
+  Epi1Q ep;
+  ep.p0 = reinterpret_cast<const float*>(sm.pl) + e;
+#pragma unroll
+  for (int sgi = 0; sgi < QNW; ++sgi) ep.seg[sgi] = (sgi < nseg1 ? sgi : nseg1 - 1) * ne;
+  ep.add = (1u << nseg1) - 1u;
+  ep.h = reinterpret_cast<float*>(sm.hl) + q_epi1_slot(e);
+  ep.w1 = sm.bias[o]; ep.b1 = sm.bias[h64 + o];
+  ep.valid = has && (o >> 2) < m.KQ2p;
+  // the second elements are QNT .. ne - 1, all in wave 0, and their rows ascend from q_epi1_row(QNT): with RG1 = 2 and
+  // KQ2p = 28 (every shape of the family today) that row is 112 = 4 KQ2p and no second element is real
+  ep.two = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0 && ne > QNT && (q_epi1_row(QNT) >> 2) < m.KQ2p;
+  return ep;
+}
+// the h value of one element: the K-segment partials summed in segment order, all reads issued before the first add
+// (q_segment_sum), then the same expression as ever; the activation in its select form (lrnde_math.hpp: the same bits)
+__device__ __forceinline__ float q_epi1_value(const ModelDev& m, const float* p0, const int (&seg)[QNW], unsigned add,
+                                              float w1, float b1, float ts) {
+  float vals[QNW];
+#pragma unroll
+  for (int sgi = 0; sgi < QNW; ++sgi) vals[sgi] = p0[seg[sgi]];
+  float v = vals[0];
+#pragma unroll
+  for (int sgi = 1; sgi < QNW; ++sgi) v = ((add >> sgi) & 1u) ? v + vals[sgi] : v;
+  float pre = m.td ? fma_(w1, ts, v) : v;
+  pre = pre + b1;
+  return act_apply_sel(m.act, pre);
+}
+__device__ __forceinline__ void q_epilogue1(const ModelDev& m, const SmemQ& sm, const Epi1Q& ep, float ts) {
+  const float hv = q_epi1_value(m, ep.p0, ep.seg, ep.add, ep.w1, ep.b1, ts);
+  if (ep.valid) *ep.h = hv;
+  if (ep.two) {  // (nothing of it is kept from the head: no shape takes this today)
+    const int e = (int)threadIdx.x + QNT, o = q_epi1_row(e);
+    const bool ok = e < m.RG1 * 256 && (o >> 2) < m.KQ2p;
+    const int e2 = ok ? e : 0, o2 = ok ? o : 0;
+    const float hv2 = q_epi1_value(m, reinterpret_cast<const float*>(sm.pl) + e2, ep.seg, ep.add, sm.bias[o2],
+                                   sm.bias[m.RG1 * 64 + o2], ts);
+    if (ok) reinterpret_cast<float*>(sm.hl)[q_epi1_slot(e2)] = hv2;
+  }
+}
+
 
 __device__ __forceinline__ SmemQ carve_q(const ModelDev& m) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -534,15 +595,17 @@ __device__ __forceinline__ f32x4 qmfma(float a, float b, f32x4 c) { asm volatile
 #else
 __device__ __forceinline__ f32x4 qmfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 #endif
+// ep1 = epilogue 1's invariants where the caller made them once for all the f-evals of its launch (k_step_q's register
+// form); nullptr (a constant at every call): they are made here, behind the first barrier
 template <class Epi, int SLOT0, int KT = 4, unsigned PARK = 0>
-__device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, StreamQ& st, float ts, const Epi& epi) {
+__device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, StreamQ& st, float ts, const Epi& epi,
+                                         const Epi1Q* ep1 = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sidx = lane & 3, q = lane >> 2;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const int h64 = m.RG1 * 64, d64 = m.RG2 * 64;
-  const float* w1t = sm.bias; const float* b1 = w1t + h64;
-  const float* w2t = b1 + h64; const float* b2 = w2t + d64;
+  const float* w2t = sm.bias + 2 * h64; const float* b2 = w2t + d64;
   const int nseg1 = q_nseg1(m);
   f32x4 acc0 = zero4, acc1 = zero4;
   STAMP(1); STAMPW(0);
@@ -589,21 +652,9 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
   STAMP(2); STAMPW(1);
   q_barrier();
   STAMP(3);
-  // epilogue 1 (one C-fragment element per thread)
-  {
-    const float* plf = reinterpret_cast<const float*>(sm.pl);
-    float* hlf = reinterpret_cast<float*>(sm.hl);
-    const int ne = m.RG1 * 256;
-    for (int e = threadIdx.x; e < ne; e += QNT) {
-      const int r = e & 3, l = (e >> 2) & 63, rg = e >> 8;
-      const int o = rg * 64 + (l >> 2) * 4 + r;
-      if ((o >> 2) >= m.KQ2p) continue;
-      const float v = q_segment_sum(plf, ne, e, nseg1);
-      float pre = m.td ? fma_(w1t[o], ts, v) : v;
-      pre = pre + b1[o];
-      hlf[((o >> 2) * 4 + (l & 3)) * 4 + r] = act_apply(m.act, pre);
-    }
-  }
+  // epilogue 1 (one C-fragment element per thread, Epi1Q)
+  if (ep1) q_epilogue1(m, sm, *ep1, ts);
+  else q_epilogue1(m, sm, q_epi1_make(m, sm), ts);
   STAMPW(2);
   q_barrier();
   STAMP(4); STAMPW(3);
@@ -1048,6 +1099,10 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
   }
   if (!bc.do_step) return;
 
+  // register form: epilogue 1's invariants once for the six f-evals (the bias vectors are staged: the head's barrier).
+  // The LDS form makes them in each f-eval (feval_qs): it has no registers to keep them in
+  const Epi1Q ep1v = REGS ? q_epi1_make(a.m, s) : Epi1Q{};
+  const Epi1Q* ep1 = REGS ? &ep1v : nullptr;
   const float t = bc.t, dt = bc.dt;
   const float c1 = (float)Tsit5::C[0], c2 = (float)Tsit5::C[1], c3 = (float)Tsit5::C[2],
               c4 = (float)Tsit5::C[3];
@@ -1114,7 +1169,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
       EpiStageQ<S> e;                                                                   \
       e.io = io; e.off_out = off_out; e.off_x = off_x;                                  \
       e.dt = dt; e.xl = s.xl; e.R = &R; e.store_k = bc.store_k;                         \
-      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT, QPARK>(a.m, s, fc, (TS), e);  \
+      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT, QPARK>(a.m, s, fc, (TS), e, ep1); \
     } else {                                                                            \
       EpiStageQL<S> e;                                                                  \
       e.io = io; e.off_up = o_up; e.off_k[0] = o_k1;                                    \
@@ -1141,7 +1196,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
     ef.xl = s.xl; ef.R = &R;
     ef.rec = rec; ef.nstB = (int)(a.n_local * 4); ef.rsD = rsD;
-    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT, QPARK>(a.m, s, fc, t + dt, ef);
+    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT, QPARK>(a.m, s, fc, t + dt, ef, ep1);
   } else {
     EpiFinalQL ef;
     ef.io = io; ef.off_up = o_up; ef.off_u = o_un; ef.off_k[0] = o_k1;
