@@ -151,6 +151,26 @@ int lrnde_create_wide_chain(lrnde_ctx** out, const lrnde_chain_desc* desc, int d
 enum { LRNDE_ADJ_LOOP_AUTO = 0, LRNDE_ADJ_LOOP_DEVICE = 1 };
 int lrnde_set_adjoint_loop(lrnde_ctx* ctx, int32_t loop);
 
+/* The `sensealg` field of NeuralODE (src/layers/neural_ode.jl:1-23): the method of lrnde_node_backward_recorded(_ts) and
+ * lrnde_node_backward on this handle.
+ * LRNDE_SENSE_INTERPOLATING (the default): the continuous adjoint, the InterpolatingAdjoint restatement described below.
+ * LRNDE_SENSE_DISCRETE: the discrete adjoint of the recorded Tsit5 solve, what a tape (TrackerAdjoint / ReverseDiffAdjoint)
+ * gives upstream — UPSTREAM-RECALL (frozen grid): DiffEqBase's norm of tracked arrays works on values, so a tape does not
+ * differentiate the step-size controller.  loss = <cotangents, saved states> + w_reg * reg_val; the gradient is the exact
+ * derivative of the discrete forward map over the accepted steps of the record, their times and step sizes constants.
+ * Rejected attempts do not appear; the first-same-as-last derivative is differentiated (k1 of step n+1 is k7 of step n); a
+ * state saved inside a step is that step's Tsit5 interpolant, whose cotangent flows into the step's uprev and k1..k7 with the
+ * weights dt * b_i(theta), theta = (ts - t_n) / dt_n in fp32 as the forward forms it; a state saved at a step's end is a
+ * copy of u; sol(t1) of the local step stays a constant and the regulariser's gradient is unchanged.  One launch walks
+ * the record (csrc/lrnde_chain_discrete.hpp: the sweep, its fixed order of summation, its gate); two calls give the same
+ * bits.  lrnde_stats of the backward: naccept = iters = the record's steps, nreject = 0, nf = 6 * steps + 1.
+ * Returns LRNDE_BADARG for any other code and LRNDE_UNSUPPORTED for DISCRETE on a handle that is not an unsharded small
+ * Dense-chain handle (lrnde_create_chain); the handle stays usable after either.  A backward call whose batch is outside
+ * the sweep's gate (160 KiB of LDS, 4096 workgroups, 256 MiB of parameter partials) returns LRNDE_UNSUPPORTED with a
+ * message naming the limit, touches nothing and leaves the record usable; it never runs the other method instead. */
+enum { LRNDE_SENSE_INTERPOLATING = 0, LRNDE_SENSE_DISCRETE = 1 };
+int lrnde_set_sensealg(lrnde_ctx* ctx, int32_t sensealg);
+
 /* Hands the flat parameter vector `ps` (what ODEProblem(dudt, x, tspan, ps)
  * carries, src/layers/neural_ode.jl:50) to the library; repacked on device
  * into the MFMA operand layout.  Call again whenever ps changes. */

@@ -160,37 +160,30 @@ static size_t chadj_smem_bytes(int wfloats, int gfloats_lds, size_t vjp_lds) {
   return ((size_t)wfloats + (size_t)((gfloats_lds + 3) & ~3)) * sizeof(float) + vjp_lds + NW * 3 * sizeof(double) + sizeof(ChAdjCtrl) + 32;
 }
 
-// K = [J^T lam; the tile's (df/dp)^T lam] at (y(t) of the dense record, t): k_vjp_chain's arithmetic with lam and the
-// result in the registers of the element's thread and the weights in LDS
-__device__ __forceinline__ void chadj_eval(const ChainDev& cd, const ChAdjSmem& s, const ChainSlots& sl, const ChAdjArgs& a,
-                                           const AdjStage& st, const float* lam, float* kout, float* gp) {
+// One element of the tile enters the VJP once its y is known: a_0 = act0(y), act0'(y) and the cotangent lam of f at its LDS
+// slot (the element's thread; a barrier follows in chadj_eval_tail)
+__device__ __forceinline__ void chadj_put(const ChainDev& cd, const ChAdjSmem& s, int lidx, float y, float lam) {
+  float* lds = s.v;
+  const float h = act_apply(cd.in_act, y);
+  (lds + cd.meta[CM_AOFF])[lidx] = h;
+  (lds + cd.uoff)[lidx] = act_deriv_c(cd.in_act, y, h);
+  (lds + cd.gboff)[lidx] = lam;
+}
+
+// The part after "y is known" (every in-tile element went through chadj_put): forward through the L layers at time t
+// keeping every layer's input and act', backward, and the tile's parameter cotangent: gp[q] = the tile's sum (ACC false,
+// the continuous loop) or gp[q] + the tile's sum (ACC true, the discrete sweep: element q always has the same thread)
+template <bool ACC>
+__device__ __forceinline__ void chadj_eval_tail(const ChainDev& cd, const ChAdjSmem& s, const ChainSlots& sl, float t, float* kout, float* gp) {
   float* lds = s.v;
   float* du = lds + cd.uoff;
   float* ga = lds + cd.gboff;
   float* gb = ga + CMAXW * CNB;
-  {
-    const size_t nst = a.g.n_lam;
-    const float* dense = a.g.dense + (size_t)st.lo * REC_ARRAYS * nst;
-    float* a0 = lds + cd.meta[CM_AOFF];
-#pragma unroll
-    for (int i = 0; i < CEPT; ++i) {
-      if (!sl.in[i]) continue;
-      float y = 0.f;
-      if (sl.valid[i]) {
-        const size_t g = sl.g[i];
-        y = tsit5_rec_eval(dense[g], dense[nst + g], dense[2 * nst + g], dense[3 * nst + g], dense[4 * nst + g], st.theta, st.ddt);
-      }
-      const float h = act_apply(cd.in_act, y);
-      a0[sl.lidx[i]] = h;
-      du[sl.lidx[i]] = act_deriv_c(cd.in_act, y, h);
-      ga[sl.lidx[i]] = lam[i];
-    }
-  }
   __syncthreads();
   for (int l = 0; l < cd.L; ++l) {
     const int* mt = cd.meta + l * CMETA;
     float* xout = (l + 1 < cd.L) ? lds + mt[CMETA + CM_AOFF] : gb;
-    chain_layer(s.w + mt[CM_WOFF], mt[CM_IN], mt[CM_OUT], mt[CM_OUTP], cd.td, mt[CM_ACT], lds + mt[CM_AOFF], xout, lds + mt[CM_ZOFF], st.t);
+    chain_layer(s.w + mt[CM_WOFF], mt[CM_IN], mt[CM_OUT], mt[CM_OUTP], cd.td, mt[CM_ACT], lds + mt[CM_AOFF], xout, lds + mt[CM_ZOFF], t);
     __syncthreads();
   }
   float* gc = ga;
@@ -214,14 +207,14 @@ __device__ __forceinline__ void chadj_eval(const ChainDev& cd, const ChAdjSmem& 
             for (int n = 0; n < CNB; ++n) acc = fma_(gc[o * CNB + n], al[k * CNB + n], acc);
           } else {
 #pragma unroll
-            for (int n = 0; n < CNB; ++n) acc = fma_(gc[o * CNB + n], st.t, acc);
+            for (int n = 0; n < CNB; ++n) acc = fma_(gc[o * CNB + n], t, acc);
           }
         } else {
           const int o = q - nw;
 #pragma unroll
           for (int n = 0; n < CNB; ++n) acc = acc + gc[o * CNB + n];
         }
-        gpl[q] = acc;
+        gpl[q] = ACC ? gpl[q] + acc : acc;
       }
     }
     // g_prev[k][n] = sum_o W[o][k] delta[o][n]  (o ascending)
@@ -239,6 +232,25 @@ __device__ __forceinline__ void chadj_eval(const ChainDev& cd, const ChAdjSmem& 
 #pragma unroll
   for (int i = 0; i < CEPT; ++i) kout[i] = sl.in[i] ? gc[sl.lidx[i]] * du[sl.lidx[i]] : 0.f;
   __syncthreads();
+}
+
+// K = [J^T lam; the tile's (df/dp)^T lam] at (y(t) of the dense record, t): k_vjp_chain's arithmetic with lam and the
+// result in the registers of the element's thread and the weights in LDS
+__device__ __forceinline__ void chadj_eval(const ChainDev& cd, const ChAdjSmem& s, const ChainSlots& sl, const ChAdjArgs& a,
+                                           const AdjStage& st, const float* lam, float* kout, float* gp) {
+  const size_t nst = a.g.n_lam;
+  const float* dense = a.g.dense + (size_t)st.lo * REC_ARRAYS * nst;
+#pragma unroll
+  for (int i = 0; i < CEPT; ++i) {
+    if (!sl.in[i]) continue;
+    float y = 0.f;
+    if (sl.valid[i]) {
+      const size_t g = sl.g[i];
+      y = tsit5_rec_eval(dense[g], dense[nst + g], dense[2 * nst + g], dense[3 * nst + g], dense[4 * nst + g], st.theta, st.ddt);
+    }
+    chadj_put(cd, s, sl.lidx[i], y, lam[i]);
+  }
+  chadj_eval_tail<false>(cd, s, sl, st.t, kout, gp);
 }
 
 // mode CHADJ_STEP: attempt j.  CHADJ_INIT_A: K1 = rhs(z, s0) and the lambda partials of d0, d1.  CHADJ_INIT_B: initdt's

@@ -1525,6 +1525,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 #include "lrnde_chain.hpp"
 #include "lrnde_wide_chain.hpp"
 #include "lrnde_chain_adjoint.hpp"
+#include "lrnde_chain_discrete.hpp"
 #include "lrnde_wide_adjoint.hpp"
 
 // single-step modes: EEst and the two regularisation values from the partial sums
@@ -1764,7 +1765,12 @@ struct lrnde_ctx {
   // tables above; its eight stage-record slots are its own
   DevBuf<float> wa_rec;
   int adj_loop = LRNDE_ADJ_LOOP_AUTO;      // lrnde_set_adjoint_loop
-  // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device, 3 wide-chain device), the kernels it
+  // the small chain's discrete adjoint (lrnde_chain_discrete.hpp): the series times on the device; the per-workgroup
+  // parameter partials share cha_gpart
+  int sensealg = LRNDE_SENSE_INTERPOLATING;   // lrnde_set_sensealg
+  DevBuf<float> chd_ser;
+  // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device, 3 wide-chain device,
+  // 4 the small chain's discrete sweep), the kernels it
   // enqueued and the waits the host made with nothing enqueued behind them
   int adj_kind = 0, adj_launches = 0, adj_waits = 0;
   int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp)
@@ -2082,6 +2088,7 @@ int set_smem_attr() {
   hipFuncSetAttribute((const void*)k_rhs_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_vjp_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_chadj_step, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_chain_dsweep, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_step_wide<false>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_step_wide<true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_init1_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
@@ -4502,6 +4509,69 @@ bool chadj_fits(const lrnde_ctx* c, int B, ChAdjPlan* pl) {
   return true;
 }
 
+// ---- the small chain handle's discrete adjoint as one launch over the step record (lrnde_chain_discrete.hpp) ----------
+// The gate, stated once: a small-chain handle, not sharded; the sweep's LDS (forward image + activation record; the backward
+// image and then the workgroup's parameter partial ride along when they fit too) within CHADJ_LDS_MAX, at most CHADJ_MAX_WG
+// workgroups, and the per-workgroup parameter partials (workgroups x P floats) within CHADJ_SCRATCH_MAX.  Outside it the call
+// is refused (why: the limit missed); the continuous adjoint is never run in its place.
+struct ChDiscPlan { int nwg, wg_lds, p_lds; size_t lds; };
+bool chdisc_fits(const lrnde_ctx* c, int B, ChDiscPlan* pl, std::string* why) {
+  char msg[200];
+  auto no = [&](void) { if (why) *why = msg; return false; };
+  if (c->field != 1) { snprintf(msg, sizeof msg, "not a small Dense-chain handle"); return no(); }
+  if (sharded(c)) { snprintf(msg, sizeof msg, "the handle is sharded"); return no(); }
+  const size_t P = param_count(c);
+  const int nwg = (B + CNB - 1) / CNB;
+  const size_t lds0 = chdisc_smem_bytes(c->cd.wfloats, 0, c->ch_vjp_lds, 0);
+  const size_t lds1 = chdisc_smem_bytes(c->cd.wfloats, c->ch_gfloats, c->ch_vjp_lds, 0);
+  const size_t lds2 = chdisc_smem_bytes(c->cd.wfloats, c->ch_gfloats, c->ch_vjp_lds, P);
+  if (lds0 > CHADJ_LDS_MAX) { snprintf(msg, sizeof msg, "the sweep needs %zu bytes of LDS, CHADJ_LDS_MAX is %zu", lds0, CHADJ_LDS_MAX); return no(); }
+  if (nwg > CHADJ_MAX_WG) { snprintf(msg, sizeof msg, "B = %d is %d workgroups, CHADJ_MAX_WG is %d", B, nwg, CHADJ_MAX_WG); return no(); }
+  if ((size_t)nwg * P * sizeof(float) > CHADJ_SCRATCH_MAX) {
+    snprintf(msg, sizeof msg, "B = %d needs %zu bytes of parameter partials, CHADJ_SCRATCH_MAX is %zu", B, (size_t)nwg * P * sizeof(float), CHADJ_SCRATCH_MAX);
+    return no();
+  }
+  if (pl) {
+    pl->nwg = nwg;
+    pl->wg_lds = lds1 <= CHADJ_LDS_MAX ? 1 : 0;
+    pl->p_lds = lds2 <= CHADJ_LDS_MAX ? 1 : 0;
+    pl->lds = pl->p_lds ? lds2 : (pl->wg_lds ? lds1 : lds0);
+  }
+  return true;
+}
+
+// Launches: one k_chdisc_begin per 64 series times, the sweep, k_chain_pgsum; the caller adds k_adj_out.  No host wait.
+// lambda(t0) goes to z[0, n), the parameter cotangent to z[n, n + P): where the continuous loops leave them.
+// du: nser cotangents of B*D floats at the times ser (ascending).
+int chdisc_run(lrnde_ctx* c, const ChDiscPlan& pl, AdjVec& v, int B, float t2, const std::vector<float>& ser, const float* du, int nrec,
+               lrnde_stats* st) {
+  memset(st, 0, sizeof(*st));
+  const size_t P = v.P, n = v.n_lam;
+  HIPCHK(c, c->cha_gpart.grow((size_t)pl.nwg * P));
+  if (ser.size() > c->chd_ser.size() || !c->chd_ser) HIPCHK(c, c->chd_ser.grow(ser.size() + 64));
+  for (size_t off = 0; off < ser.size(); off += 64) {
+    ChDiscBegin b{};
+    b.dst = c->chd_ser; b.off = (int)off; b.n = (int)std::min<size_t>(64, ser.size() - off);
+    for (int k = 0; k < b.n; ++k) b.v[k] = ser[off + k];
+    hipLaunchKernelGGL(k_chdisc_begin, dim3(1), dim3(64), 0, c->stream, b);
+    HIPCHK(c, hipGetLastError());
+    ++c->adj_launches;
+  }
+  ChDiscArgs a{};
+  a.dense = c->dense; a.dense_t = c->dense_t; a.dense_dt = c->dense_dt; a.nrec = nrec; a.n_lam = n;
+  a.ser_t = c->chd_ser; a.du = du; a.nser = (int)ser.size(); a.t2 = t2;
+  a.lam_out = v.z; a.gpart = c->cha_gpart; a.B = B;
+  a.wg_lds = pl.wg_lds; a.gfloats = c->ch_gfloats; a.p_lds = pl.p_lds;
+  hipLaunchKernelGGL(k_chain_dsweep, dim3(pl.nwg), dim3(NT), pl.lds, c->stream, a, c->cd);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_chain_pgsum, dim3((unsigned)std::min<size_t>((P + 255) / 256, 1024)), dim3(256), 0, c->stream, (const float*)c->cha_gpart,
+                     pl.nwg, (int)P, v.z + n, 0, (const float*)nullptr, (float*)nullptr);
+  HIPCHK(c, hipGetLastError());
+  c->adj_launches += 2;
+  st->naccept = nrec; st->nreject = 0; st->iters = nrec; st->nf = 6 * nrec + 1; st->retcode = LRNDE_OK;
+  return LRNDE_OK;
+}
+
 // The wide handle's gate, stated once: the step kernel's LDS (the forward kernels' carve, its segment-partial region cut
 // back by what the control block takes) within WIDE_LDS_MAX; at most CHADJ_MAX_WG workgroups; eight stage-record slots
 // for the batch plus the control blocks and the norm partials within WIDE_SCRATCH_MAX.  why (may be null): the limit missed.
@@ -4846,6 +4916,14 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     std::string why;   // (refused before anything is touched: the handle and its record stay usable)
     if (!wadj_fits(c, B, &wpl, &why)) return fail(c, LRNDE_UNSUPPORTED, "wide adjoint loop: %s", why.c_str());
   }
+  const bool discrete = c->sensealg == LRNDE_SENSE_DISCRETE;   // (lrnde_set_sensealg: a small-chain handle)
+  ChDiscPlan dpl{};
+  if (discrete) {
+    std::string why;   // (refused before anything is touched: the handle and its record stay usable)
+    if (!chdisc_fits(c, B, &dpl, &why)) return fail(c, LRNDE_UNSUPPORTED, "discrete adjoint: %s", why.c_str());
+    if (du_series && nser != (int)R.series_t.size())
+      return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
+  }
   AdjVec v;
   if ((rc = adj_alloc(c, N, v))) return rc;
   v.n_lam = n; v.P = P;
@@ -4854,11 +4932,13 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   const bool chain_loop = c->field && chadj_fits(c, B, &cpl) && !sharded(c) && !adj_host;
   const bool wide_loop = c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DEVICE && !sharded(c) && !adj_host;   // opt-in (lrnde_set_adjoint_loop)
   const bool dev_loop = vjp_uses_qtile(c, B) && !sharded(c) && !adj_host;
-  c->adj_kind = wide_loop ? 3 : (chain_loop ? 2 : (dev_loop ? 1 : 0)); c->adj_launches = 0; c->adj_waits = 0;
+  c->adj_kind = discrete ? 4 : (wide_loop ? 3 : (chain_loop ? 2 : (dev_loop ? 1 : 0))); c->adj_launches = 0; c->adj_waits = 0;
   const bool begin_in_solve = dev_loop && !du_series;  // the device loop's first launch sets z = [du_end; 0] itself
-  if (!begin_in_solve) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
+  if (!begin_in_solve && !discrete) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
   std::vector<AdjImpulse> impulses;  // ascending in s = -t
-  if (du_series) {
+  if (discrete) {
+    // (the sweep takes the cotangents from the caller's array at the series' times; it writes all of z)
+  } else if (du_series) {
     if (nser != (int)R.series_t.size()) return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
     for (int i = nser - 1; i >= 0; --i) {
       const float tv = R.series_t[i];
@@ -4893,7 +4973,9 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     if (vjp_uses_qtile(c, B) && !sharded(c) && !adj_host) after_first_attempt = pending_sweep;
     else if ((rc = pending_sweep())) return rc;
   }
-  if (chain_loop || wide_loop) {
+  if (discrete) {
+    rc = chdisc_run(c, dpl, v, B, t2, du_series ? R.series_t : std::vector<float>{t2}, du_series ? du_series : du_end, nsteps, st_bwd);
+  } else if (chain_loop || wide_loop) {
     rc = chadj_solve_device(c, wide_loop ? wadj_driver(c, wpl) : chadj_driver(c, cpl), v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
                             after_first_attempt);
   } else if (dev_loop) {
@@ -5141,6 +5223,16 @@ int lrnde_set_adjoint_loop(lrnde_ctx* c, int32_t loop) {
   if (!c) return LRNDE_BADARG;
   if (loop != LRNDE_ADJ_LOOP_AUTO && loop != LRNDE_ADJ_LOOP_DEVICE) return fail(c, LRNDE_BADARG, "adjoint loop %d (0 auto, 1 device)", loop);
   c->adj_loop = loop;
+  return LRNDE_OK;
+}
+
+int lrnde_set_sensealg(lrnde_ctx* c, int32_t alg) {
+  if (!c) return LRNDE_BADARG;
+  if (alg != LRNDE_SENSE_INTERPOLATING && alg != LRNDE_SENSE_DISCRETE)
+    return fail(c, LRNDE_BADARG, "sensealg %d (0 interpolating adjoint, 1 discrete adjoint)", alg);
+  if (alg == LRNDE_SENSE_DISCRETE && (c->field != 1 || sharded(c)))
+    return fail(c, LRNDE_UNSUPPORTED, "the discrete adjoint is built for the small Dense-chain handle (lrnde_create_chain), unsharded");
+  c->sensealg = alg;
   return LRNDE_OK;
 }
 

@@ -376,8 +376,17 @@ class Handle:
 
     ADJOINT_LOOPS = ("host", "device", "chain_device")
     # every kind lrnde_last_adjoint_info reports: the three above and the wide-chain handle's opt-in device loop
-    ADJOINT_LOOP_NAMES = ADJOINT_LOOPS + ("wide_device",)
+    # and the small chain's discrete sweep (set_sensealg("discrete"))
+    ADJOINT_LOOP_NAMES = ADJOINT_LOOPS + ("wide_device", "chain_discrete")
     ADJOINT_LOOP_CHOICES = {"auto": 0, "device": 1}
+    SENSEALGS = {"interpolating": 0, "discrete": 1}
+
+    def set_sensealg(self, sensealg):
+        """lrnde_set_sensealg: "interpolating" (the default: the continuous adjoint) or "discrete" (a small Dense-chain
+        handle: the discrete adjoint of the recorded solve on its frozen step grid, one launch over the record)"""
+        if sensealg not in self.SENSEALGS:
+            raise ValueError(f"sensealg must be 'interpolating' or 'discrete' (got {sensealg!r})")
+        self._chk(L.lib.lrnde_set_sensealg(self._ctx, self.SENSEALGS[sensealg]))
 
     def set_adjoint_loop(self, loop):
         """lrnde_set_adjoint_loop: "auto" (every handle's own routing; a wide-chain handle takes the host loop) or
@@ -388,8 +397,8 @@ class Handle:
 
     def last_adjoint_info(self):
         """how the last reversed solve ran (lrnde_last_adjoint_info): kind 0 host loop / 1 the MLP device loop / 2 the
-        chain device loop / 3 the wide-chain device loop, the kernels it enqueued, and the host waits during which the GPU
-        idled"""
+        chain device loop / 3 the wide-chain device loop / 4 the small chain's discrete sweep, the kernels it enqueued, and
+        the host waits during which the GPU idled"""
         k, n, w = C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(L.lib.lrnde_last_adjoint_info(self._ctx, C.byref(k), C.byref(n), C.byref(w)))
         return dict(kind=int(k.value), launches=int(n.value), host_waits=int(w.value))
@@ -557,6 +566,22 @@ def diffeqsol_to_timeseries(sol):
     return torch.stack(list(sol.u), dim=0)
 
 
+def _sensealg_choice(sensealg):
+    """the layer's `sensealg` -> a key of Handle.SENSEALGS.  None / "InterpolatingAdjoint": the continuous adjoint;
+    "TrackerAdjoint" / "ReverseDiffAdjoint" (what a tape gives upstream) / "discrete": the discrete adjoint on the frozen
+    step grid (UPSTREAM-RECALL); a trailing "()" is accepted; anything else is a ValueError."""
+    if sensealg is None:
+        return "interpolating"
+    name = str(sensealg).strip()
+    name = name[:-2] if name.endswith("()") else name
+    if name == "InterpolatingAdjoint":
+        return "interpolating"
+    if name in ("TrackerAdjoint", "ReverseDiffAdjoint", "discrete"):
+        return "discrete"
+    raise ValueError(f"unknown sensealg {sensealg!r} (have None, 'InterpolatingAdjoint', 'TrackerAdjoint', "
+                     "'ReverseDiffAdjoint', 'discrete')")
+
+
 class NeuralODE:
     """src/layers/neural_ode.jl:1-116.  `(sol, st) = node(x, ps, st)`."""
 
@@ -584,6 +609,12 @@ class NeuralODE:
         if adjoint_loop not in Handle.ADJOINT_LOOP_CHOICES:
             raise ValueError(f"adjoint_loop must be 'auto' or 'device' (got {adjoint_loop!r})")
         self.adjoint_loop = adjoint_loop
+        # sensealg (src/layers/neural_ode.jl:1-23): the method of `pullback` (_sensealg_choice); the discrete adjoint is
+        # built for the small Dense-chain handle alone
+        self.sense = _sensealg_choice(sensealg)
+        if self.sense == "discrete" and field != "dense_chain":
+            raise NotImplementedError(f"sensealg={sensealg!r} (the discrete adjoint) is built for field='dense_chain' "
+                                      f"(got field={field!r})")
         if field in ("dense_chain", "wide_chain"):
             self._conv = None
             self.desc = _chain_desc(model) if field == "dense_chain" else _wide_chain_desc(model)
@@ -623,6 +654,8 @@ class NeuralODE:
             self._handle = Handle(self.desc)
             self._handle.set_solver(self.solver)
             self._handle.set_adjoint_loop(self.adjoint_loop)
+            if self.sense != "interpolating":
+                self._handle.set_sensealg(self.sense)
         return self._handle
 
     def _bind(self, ps, x=None, changed=True):
@@ -707,8 +740,10 @@ class NeuralODE:
         from it; t1 comes from the same single draw of st['rng'] as in `__call__` (biased_index), so info['reg_val'] /
         info['t1'] are `__call__`'s.  info['adjoint_loop'] names the loop that ran the reversed solve: "host" (the
         host-controlled loop), "device" (the MLP handle's device-controlled loop), "chain_device" (the Dense-chain
-        handle's) or "wide_device" (the wide Dense-chain handle's, which runs only for a layer built with
-        adjoint_loop="device"); the conv field's own backward reports None."""
+        handle's), "wide_device" (the wide Dense-chain handle's, which runs only for a layer built with
+        adjoint_loop="device") or "chain_discrete" (a layer built with sensealg="TrackerAdjoint" / "ReverseDiffAdjoint" /
+        "discrete": no reversed solve, the discrete adjoint of the record in one launch, UPSTREAM-RECALL frozen grid); the
+        conv field's own backward reports None."""
         h = self._bind(ps, x)
         t0, t2 = self.tspan
         kw = self.kwargs

@@ -9,8 +9,10 @@ The pullback legs (4-time series and the experiment's 49-time series): node.pull
 and the backward alone from a record, ms per batch (median of --bwd-reps after warm-up) with the run's min / max, the
 reversed solve's attempted steps, us per attempt of the backward alone, which loop ran it (adjoint_loop), its launches per
 attempt and host waits.  LRNDE_ADJ_HOST=1 in the environment selects the host-controlled loop: the comparison path.
+--sensealg TrackerAdjoint (or ReverseDiffAdjoint / discrete) builds the layers with the discrete adjoint (one launch over
+the record); the default is the continuous adjoint.
 
-    python tools/bench/chain_bench.py [--reps 5] [--B 512] [--bwd-reps 30]
+    python tools/bench/chain_bench.py [--reps 5] [--B 512] [--bwd-reps 30] [--sensealg TrackerAdjoint]
     rocprofv3 --kernel-trace --stats -- python tools/bench/chain_bench.py      (us per k_step_chain launch)
 """
 import argparse
@@ -116,6 +118,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--bwd-reps", type=int, default=30)
     ap.add_argument("--B", type=int, default=512)
+    ap.add_argument("--sensealg", default=None)
     args = ap.parse_args()
     torch.cuda.set_device(0)
     B = args.B
@@ -124,7 +127,7 @@ def main():
     x = (np.random.default_rng(2).random((B, 20), dtype=np.float32) - np.float32(0.5)) * np.float32(2)
     xd, ps = torch.from_numpy(x).cuda(), torch.from_numpy(p).cuda()
     node = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, saveat=SAVEAT, save_start=False, maxiters=100000,
-                       field="dense_chain")
+                       field="dense_chain", sensealg=args.sensealg)
     st = node.initialstates(np.random.default_rng(0))
     cots = torch.from_numpy(np.random.default_rng(1).standard_normal((len(SAVEAT), B, 20)).astype(np.float32)).cuda()
     h = node._bind(ps)
@@ -146,7 +149,7 @@ def main():
     legs = []
     for times in (SAVEAT, [(i + 1) / 49.0 for i in range(49)]):
         nd = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, saveat=times, save_start=False, maxiters=100000,
-                         field="dense_chain")
+                         field="dense_chain", sensealg=args.sensealg)
         legs.append(pullback_leg(nd, nd._bind(ps), xd, ps, st, times, B, args.bwd_reps))
     Ws, o = [], 0
     for l in model.layers[1:]:
@@ -164,7 +167,7 @@ def main():
         us_per_attempt_solve=round(1e3 * solve_ms / max(attempts, 1), 2),
         layer_forward_ms=round(statistics.median(fwd), 3), layer_forward_pullback_ms=round(statistics.median(fb), 3),
         eager_torch_fp32_solve_ms=round(eager_ms, 2), eager_naccept=ena, eager_nreject=enr, eager_vs_hip_u_end=err,
-        adj_host=bool(os.environ.get("LRNDE_ADJ_HOST")), pullback_series4=legs[0], pullback_series49=legs[1])))
+        adj_host=bool(os.environ.get("LRNDE_ADJ_HOST")), sensealg=args.sensealg, pullback_series4=legs[0], pullback_series49=legs[1])))
 
 
 if __name__ == "__main__":
