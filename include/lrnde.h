@@ -147,8 +147,19 @@ int lrnde_create_wide_chain(lrnde_ctx** out, const lrnde_chain_desc* desc, int d
  * LRNDE_ADJ_LOOP_DEVICE: a wide-chain handle takes its device-controlled loop (same bits as the host loop); a backward
  * call whose batch is outside that loop's gate (LDS, workgroups, 256 MiB of stage records) returns LRNDE_UNSUPPORTED with
  * a message naming the limit and leaves the handle and its forward record usable.  On a handle whose AUTO routing already
- * is a device loop it is accepted and changes nothing.  The diagnostic switch LRNDE_ADJ_HOST=1 still forces the host loop. */
+ * is a device loop it is accepted and changes nothing.  The diagnostic switch LRNDE_ADJ_HOST=1 still forces the host loop.
+ * LRNDE_ADJ_LOOP_DISCRETE: a wide-chain handle takes the discrete adjoint of its recorded Tsit5 solve: what the comment
+ * of lrnde_set_sensealg below states for LRNDE_SENSE_DISCRETE, computed for the wide handle by two launches per recorded
+ * step, newest first, all enqueued up front with no host wait (csrc/lrnde_wide_discrete.hpp: the kernels and their fixed
+ * order of summation; two calls give the same bits).  lrnde_stats of the backward: naccept = iters = the record's steps,
+ * nreject = 0, nf = 6 * steps + 1; the adjoint-info hook (lrnde_hooks.h) reports kind 5 and no host wait.  A backward call whose batch is
+ * outside the gate (160 KiB of LDS, 4096 tiles of 16 columns, 256 MiB of stage records and sweep vectors) returns
+ * LRNDE_UNSUPPORTED with a message naming the limit, touches nothing and leaves the record usable; it never runs the other
+ * method instead, and LRNDE_ADJ_HOST=1 does not override it.  On a handle that is not an unsharded wide-chain handle the
+ * setter returns LRNDE_UNSUPPORTED (a small Dense-chain handle selects its discrete adjoint with lrnde_set_sensealg, which
+ * in turn stays closed for the wide handle) and the handle stays usable.  Any other code: LRNDE_BADARG. */
 enum { LRNDE_ADJ_LOOP_AUTO = 0, LRNDE_ADJ_LOOP_DEVICE = 1 };
+enum { LRNDE_ADJ_LOOP_DISCRETE = 2 };
 int lrnde_set_adjoint_loop(lrnde_ctx* ctx, int32_t loop);
 
 /* The `sensealg` field of NeuralODE (src/layers/neural_ode.jl:1-23): the method of lrnde_node_backward_recorded(_ts) and

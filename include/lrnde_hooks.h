@@ -62,7 +62,8 @@ int lrnde_adjoint_trace_rows(lrnde_ctx* ctx, int32_t* n_host);
  * kind: 0 the host-controlled loop (vec_tsit5_solve; LRNDE_ADJ_HOST=1, sharded handles, shapes outside the device loops'
  * gates), 1 the MLP handle's device-controlled loop, 2 the chain handle's (lrnde_chain_adjoint.hpp), 3 the wide-chain
  * handle's (lrnde_wide_adjoint.hpp, lrnde_set_adjoint_loop), 4 no reversed solve: the small chain handle's discrete sweep over
- * the record (lrnde_chain_discrete.hpp, lrnde_set_sensealg).  launches: kernels the
+ * the record (lrnde_chain_discrete.hpp, lrnde_set_sensealg), 5 no reversed solve either: the wide-chain handle's discrete
+ * adjoint, two launches per recorded step (lrnde_wide_discrete.hpp, lrnde_set_adjoint_loop).  launches: kernels the
  * solve enqueued, from its first launch to k_adj_out (the regulariser's sweep is not counted).  host_waits: stream
  * synchronisations and blocking copies the host made before the solve's end with nothing enqueued behind them, i.e. waits
  * during which the GPU idles; the final wait is not counted, and polling the pinned progress word while an attempt is

@@ -117,7 +117,10 @@ set_params!(ctx, ps) = check(ctx, ccall((:lrnde_set_params, lib), Cint, (Ptr{Cvo
 # n.solver of the layer's global solve: 0 Tsit5, 1 VCAB3, 2 VCABM3 (experiments/src/construct.jl:154-164)
 set_solver!(ctx, alg) = check(ctx, ccall((:lrnde_set_solver, lib), Cint, (Ptr{Cvoid}, Int32), ctx, alg))
 
-# which loop runs the reversed solve: 0 the handle's own routing, 1 the device-controlled loop (a wide-chain handle's opt-in)
+# which loop runs the reversed solve: 0 the handle's own routing, 1 the device-controlled loop (a wide-chain handle's opt-in),
+# 2 a wide-chain handle's discrete adjoint over its step record (two launches per recorded step; any other handle refuses it,
+# a small Dense-chain handle selects its discrete adjoint with lrnde_set_sensealg)
+const ADJ_LOOP_AUTO, ADJ_LOOP_DEVICE, ADJ_LOOP_DISCRETE = Int32(0), Int32(1), Int32(2)
 set_adjoint_loop!(ctx, loop) = check(ctx, ccall((:lrnde_set_adjoint_loop, lib), Cint, (Ptr{Cvoid}, Int32), ctx, loop))
 
 # dudt(u, p, t) — src/layers/neural_ode.jl:44-48

@@ -1527,6 +1527,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 #include "lrnde_chain_adjoint.hpp"
 #include "lrnde_chain_discrete.hpp"
 #include "lrnde_wide_adjoint.hpp"
+#include "lrnde_wide_discrete.hpp"
 
 // single-step modes: EEst and the two regularisation values from the partial sums
 __global__ void k_finalize(StepArgs a, int j) {
@@ -1764,13 +1765,16 @@ struct lrnde_ctx {
   // the wide handle's device-controlled adjoint loop (lrnde_wide_adjoint.hpp) shares the control blocks, norm partials and
   // tables above; its eight stage-record slots are its own
   DevBuf<float> wa_rec;
+  // the wide handle's discrete adjoint (lrnde_wide_discrete.hpp): its six stage-record slots are wa_rec's, the series times
+  // chd_ser's; the sweep's B*D vectors
+  DevBuf<float> wd_vec;
   int adj_loop = LRNDE_ADJ_LOOP_AUTO;      // lrnde_set_adjoint_loop
   // the small chain's discrete adjoint (lrnde_chain_discrete.hpp): the series times on the device; the per-workgroup
   // parameter partials share cha_gpart
   int sensealg = LRNDE_SENSE_INTERPOLATING;   // lrnde_set_sensealg
   DevBuf<float> chd_ser;
   // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device, 3 wide-chain device,
-  // 4 the small chain's discrete sweep), the kernels it
+  // 4 the small chain's discrete sweep, 5 the wide chain's discrete sweep), the kernels it
   // enqueued and the waits the host made with nothing enqueued behind them
   int adj_kind = 0, adj_launches = 0, adj_waits = 0;
   int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp)
@@ -2096,6 +2100,7 @@ int set_smem_attr() {
   hipFuncSetAttribute((const void*)k_rhs_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_vjp_wide, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_wadj_step, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_wdisc_step, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   done = true;
   return 0;
 }
@@ -4603,6 +4608,73 @@ bool wadj_fits(const lrnde_ctx* c, int B, WAdjPlan* pl, std::string* why) {
   return true;
 }
 
+// ---- the wide handle's discrete adjoint: two launches per recorded step (lrnde_wide_discrete.hpp) ----------------------
+// The gate, stated once: a wide-chain handle, not sharded; the step kernel's LDS (the forward kernels' carve) within
+// WIDE_LDS_MAX; at most CHADJ_MAX_WG tiles; the six stage-record slots plus the sweep's WDISC_VECS B*D vectors within
+// WIDE_SCRATCH_MAX.  Outside it the call is refused (why: the limit missed); the continuous adjoint is never run in its place.
+struct WDiscPlan { int nwg, nitems, nmu; size_t lds, rec_floats, vec_floats; };
+bool wdisc_fits(const lrnde_ctx* c, int B, WDiscPlan* pl, std::string* why) {
+  char msg[200];
+  auto no = [&](void) { if (why) *why = msg; return false; };
+  if (c->field != 2) { snprintf(msg, sizeof msg, "not a wide-chain handle"); return no(); }
+  if (sharded(c)) { snprintf(msg, sizeof msg, "the handle is sharded"); return no(); }
+  const WideDev& wd = c->wd;
+  const int nwg = (B + NB - 1) / NB;
+  const size_t lds = wide_smem_bytes(wd.bufw, wd.partcap);
+  if (lds > WIDE_LDS_MAX) { snprintf(msg, sizeof msg, "the step kernel needs %zu bytes of LDS, WIDE_LDS_MAX is %zu", lds, WIDE_LDS_MAX); return no(); }
+  if (nwg > CHADJ_MAX_WG) { snprintf(msg, sizeof msg, "B = %d is %d workgroups, CHADJ_MAX_WG is %d", B, nwg, CHADJ_MAX_WG); return no(); }
+  int nitems = 0;
+  for (int l = 0; l < c->chain.nlayers; ++l) {
+    const int MT = ceil16(c->chain.dims[l + 1]) / 16, KG = ceil16(c->chain.dims[l]) / 16;
+    nitems += ((MT + WADJ_MB - 1) / WADJ_MB) * ((KG + WADJ_MB - 1) / WADJ_MB) + (c->chain.dims[l + 1] + 63) / 64;
+  }
+  const size_t rec_floats = (size_t)WDISC_SLOTS * nwg * wd.recfloats;
+  const size_t vec_floats = (size_t)WDISC_VECS * B * c->desc.state_dim;
+  const size_t bytes = (rec_floats + vec_floats) * sizeof(float);
+  if (bytes > WIDE_SCRATCH_MAX) {
+    snprintf(msg, sizeof msg, "B = %d needs %zu bytes of stage records (%d slots) and sweep vectors (%d), WIDE_SCRATCH_MAX is %zu", B, bytes,
+             WDISC_SLOTS, WDISC_VECS, WIDE_SCRATCH_MAX);
+    return no();
+  }
+  if (pl) {
+    pl->nwg = nwg; pl->nitems = nitems; pl->nmu = std::min(nitems, CHADJ_MAX_MU_BLOCKS); pl->lds = lds;
+    pl->rec_floats = rec_floats; pl->vec_floats = vec_floats;
+  }
+  return true;
+}
+
+// Launches: one k_chdisc_begin per 64 series times, a k_wdisc_step / k_wdisc_mu pair per recorded step (newest first), the
+// tail pair; the caller zeroes z before (a memset: mu starts at zero, lam is written by the newest step) and adds k_adj_out.
+// No host wait.  lambda(t0) goes to z[0, n), the parameter cotangent to z[n, n + P): where the continuous loops leave them.
+int wdisc_run(lrnde_ctx* c, const WDiscPlan& pl, AdjVec& v, int B, float t2, const std::vector<float>& ser, const float* du, int nrec,
+              lrnde_stats* st) {
+  memset(st, 0, sizeof(*st));
+  if (nrec <= 0) return fail(c, LRNDE_BADARG, "the record holds no step");
+  HIPCHK(c, c->wa_rec.grow(pl.rec_floats));
+  HIPCHK(c, c->wd_vec.grow(pl.vec_floats));
+  if (ser.size() > c->chd_ser.size() || !c->chd_ser) HIPCHK(c, c->chd_ser.grow(ser.size() + 64));
+  for (size_t off = 0; off < ser.size(); off += 64) {
+    ChDiscBegin b{};
+    b.dst = c->chd_ser; b.off = (int)off; b.n = (int)std::min<size_t>(64, ser.size() - off);
+    for (int k = 0; k < b.n; ++k) b.v[k] = ser[off + k];
+    hipLaunchKernelGGL(k_chdisc_begin, dim3(1), dim3(64), 0, c->stream, b);
+    HIPCHK(c, hipGetLastError());
+    ++c->adj_launches;
+  }
+  WDiscArgs a{};
+  a.dense = c->dense; a.dense_t = c->dense_t; a.dense_dt = c->dense_dt; a.nrec = nrec; a.n_lam = v.n_lam;
+  a.ser_t = c->chd_ser; a.du = du; a.nser = (int)ser.size(); a.t2 = t2;
+  a.B = B; a.nwg = pl.nwg; a.z = v.z; a.vec = c->wd_vec; a.rec = c->wa_rec;
+  for (int n = nrec - 1; n >= -1; --n) {   // (-1: the tail)
+    hipLaunchKernelGGL(k_wdisc_step, dim3(pl.nwg), dim3(NT), pl.lds, c->stream, a, c->wd, n);
+    hipLaunchKernelGGL(k_wdisc_mu, dim3(pl.nmu), dim3(WADJ_MU_NT), 0, c->stream, a, c->wd, pl.nitems, n);
+    c->adj_launches += 2;
+  }
+  HIPCHK(c, hipGetLastError());
+  st->naccept = nrec; st->nreject = 0; st->iters = nrec; st->nf = 6 * nrec + 1; st->retcode = LRNDE_OK;
+  return LRNDE_OK;
+}
+
 // What chadj_solve_device needs of a handle kind: the grid of its two launches (their norm partials), its scratch, and the
 // launch pair of one attempt or init phase (a: the shared arguments filled in; mode: CHADJ_STEP / CHADJ_INIT_A / _B)
 struct ChAdjDriver {
@@ -4916,11 +4988,16 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     std::string why;   // (refused before anything is touched: the handle and its record stay usable)
     if (!wadj_fits(c, B, &wpl, &why)) return fail(c, LRNDE_UNSUPPORTED, "wide adjoint loop: %s", why.c_str());
   }
-  const bool discrete = c->sensealg == LRNDE_SENSE_DISCRETE;   // (lrnde_set_sensealg: a small-chain handle)
+  // (lrnde_set_sensealg: a small-chain handle; lrnde_set_adjoint_loop(LRNDE_ADJ_LOOP_DISCRETE): a wide-chain handle, and
+  //  LRNDE_ADJ_HOST does not override it)
+  const bool wide_disc = c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DISCRETE;
+  const bool discrete = c->sensealg == LRNDE_SENSE_DISCRETE || wide_disc;
   ChDiscPlan dpl{};
+  WDiscPlan wdpl{};
   if (discrete) {
     std::string why;   // (refused before anything is touched: the handle and its record stay usable)
-    if (!chdisc_fits(c, B, &dpl, &why)) return fail(c, LRNDE_UNSUPPORTED, "discrete adjoint: %s", why.c_str());
+    if (wide_disc ? !wdisc_fits(c, B, &wdpl, &why) : !chdisc_fits(c, B, &dpl, &why))
+      return fail(c, LRNDE_UNSUPPORTED, "%s: %s", wide_disc ? "wide discrete adjoint" : "discrete adjoint", why.c_str());
     if (du_series && nser != (int)R.series_t.size())
       return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
   }
@@ -4932,12 +5009,13 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   const bool chain_loop = c->field && chadj_fits(c, B, &cpl) && !sharded(c) && !adj_host;
   const bool wide_loop = c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DEVICE && !sharded(c) && !adj_host;   // opt-in (lrnde_set_adjoint_loop)
   const bool dev_loop = vjp_uses_qtile(c, B) && !sharded(c) && !adj_host;
-  c->adj_kind = discrete ? 4 : (wide_loop ? 3 : (chain_loop ? 2 : (dev_loop ? 1 : 0))); c->adj_launches = 0; c->adj_waits = 0;
+  c->adj_kind = wide_disc ? 5 : discrete ? 4 : (wide_loop ? 3 : (chain_loop ? 2 : (dev_loop ? 1 : 0))); c->adj_launches = 0; c->adj_waits = 0;
   const bool begin_in_solve = dev_loop && !du_series;  // the device loop's first launch sets z = [du_end; 0] itself
-  if (!begin_in_solve && !discrete) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
+  if ((!begin_in_solve && !discrete) || wide_disc) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
   std::vector<AdjImpulse> impulses;  // ascending in s = -t
   if (discrete) {
-    // (the sweep takes the cotangents from the caller's array at the series' times; it writes all of z)
+    // (the sweep takes the cotangents from the caller's array at the series' times; the small chain's writes all of z, the
+    //  wide chain's adds its parameter cotangents to the zeroed mu)
   } else if (du_series) {
     if (nser != (int)R.series_t.size()) return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
     for (int i = nser - 1; i >= 0; --i) {
@@ -4973,7 +5051,9 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
     if (vjp_uses_qtile(c, B) && !sharded(c) && !adj_host) after_first_attempt = pending_sweep;
     else if ((rc = pending_sweep())) return rc;
   }
-  if (discrete) {
+  if (wide_disc) {
+    rc = wdisc_run(c, wdpl, v, B, t2, du_series ? R.series_t : std::vector<float>{t2}, du_series ? du_series : du_end, nsteps, st_bwd);
+  } else if (discrete) {
     rc = chdisc_run(c, dpl, v, B, t2, du_series ? R.series_t : std::vector<float>{t2}, du_series ? du_series : du_end, nsteps, st_bwd);
   } else if (chain_loop || wide_loop) {
     rc = chadj_solve_device(c, wide_loop ? wadj_driver(c, wpl) : chadj_driver(c, cpl), v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
@@ -5221,7 +5301,11 @@ int lrnde_sde_last_backward_info(lrnde_sde* s, int32_t* kind_host, int32_t* laun
 }
 int lrnde_set_adjoint_loop(lrnde_ctx* c, int32_t loop) {
   if (!c) return LRNDE_BADARG;
-  if (loop != LRNDE_ADJ_LOOP_AUTO && loop != LRNDE_ADJ_LOOP_DEVICE) return fail(c, LRNDE_BADARG, "adjoint loop %d (0 auto, 1 device)", loop);
+  if (loop != LRNDE_ADJ_LOOP_AUTO && loop != LRNDE_ADJ_LOOP_DEVICE && loop != LRNDE_ADJ_LOOP_DISCRETE)
+    return fail(c, LRNDE_BADARG, "adjoint loop %d (0 auto, 1 device, 2 discrete)", loop);
+  if (loop == LRNDE_ADJ_LOOP_DISCRETE && (c->field != 2 || sharded(c)))
+    return fail(c, LRNDE_UNSUPPORTED, "LRNDE_ADJ_LOOP_DISCRETE is built for the wide Dense-chain handle (lrnde_create_wide_chain), unsharded; "
+                                      "a small Dense-chain handle takes its discrete adjoint through lrnde_set_sensealg");
   c->adj_loop = loop;
   return LRNDE_OK;
 }

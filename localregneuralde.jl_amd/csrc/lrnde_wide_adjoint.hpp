@@ -253,6 +253,89 @@ __device__ __forceinline__ double wadj_mu_finish(const AdjArgs& g, const float (
   return (double)(r * r);
 }
 
+// One work item of the parameter cotangent over the whole batch (the block engine k_wadj_mu and k_wdisc_mu share): wave s
+// (active: it has a stage) forms K_s of the item from the stage record whose tile 0 starts at slot0 (tiles recfloats apart)
+// into ks[s], with its stage's forward time ts; then finish(i, e) is called by one thread for every real parameter i of
+// the item, e its place in ks[.].  All WADJ_MU_NT threads of the workgroup call it; the caller synchronises before the next.
+template <class Fin>
+__device__ __forceinline__ void wadj_mu_item(const WideDev& wd, const float* slot0, int nwg, bool active, int wave, int lane, float ts,
+                                             int it, float (*ks)[WADJ_MB * WADJ_MB * 256], Fin&& finish) {
+  constexpr int MB = WADJ_MB, NBLK = MB * MB;
+  const int lr = lane & 15, lq = lane >> 4;
+  const WAdjItem wi = wadj_item(wd, it);
+  const int* mt_ = wd.meta + wi.l * WMETA;
+  const int in = mt_[WM_IN], out = mt_[WM_OUT], MT = mt_[WM_MT], KG = mt_[WM_KG];
+  const size_t pl = (size_t)mt_[WM_POFF];
+  if (!wi.vec) {
+    const int ngo = (MT + MB - 1) / MB;
+    const int ot0 = (wi.i % ngo) * MB, kt0 = (wi.i / ngo) * MB;
+    if (active) {
+      // K_s[o][k] of the MB x MB blocks: per tile the four MFMAs from zero (columns as their K dimension), then one add
+      const float* base = slot0;
+      int aoff[MB], doff[MB];
+#pragma unroll
+      for (int u = 0; u < MB; ++u) {   // (a block past the layer's edge repeats the last one; it is not stored)
+        aoff[u] = mt_[WM_RAOFF] + (min(kt0 + u, KG - 1) * 16 + lr) * NB + lq;
+        doff[u] = mt_[WM_RZOFF] + (min(ot0 + u, MT - 1) * 16 + lr) * NB + lq;
+      }
+      f32x4 sum[NBLK];
+#pragma unroll
+      for (int b = 0; b < NBLK; ++b) sum[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < nwg; ++t) {
+        const float* r = base + (size_t)t * wd.recfloats;
+        float av[MB][4], dv[MB][4];
+#pragma unroll
+        for (int u = 0; u < MB; ++u)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { av[u][q] = r[aoff[u] + 4 * q]; dv[u][q] = r[doff[u] + 4 * q]; }
+#pragma unroll
+        for (int uo = 0; uo < MB; ++uo)
+#pragma unroll
+          for (int uk = 0; uk < MB; ++uk) {
+            f32x4 p = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) p = __builtin_amdgcn_mfma_f32_16x16x4f32(av[uk][q], dv[uo][q], p, 0, 0, 0);
+            f32x4& sm = sum[uo * MB + uk];
+            sm.x = sm.x + p.x; sm.y = sm.y + p.y; sm.z = sm.z + p.z; sm.w = sm.w + p.w;
+          }
+      }
+#pragma unroll
+      for (int b = 0; b < NBLK; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ks[wave][((b * 4 + r) * 4 + lq) * 16 + lr] = sum[b][r];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < NBLK * 256; e += WADJ_MU_NT) {
+      const int b = e >> 8, r = (e >> 6) & 3, q = (e >> 4) & 3, x = e & 15;
+      const int o = (ot0 + b / MB) * 16 + x, k = (kt0 + b % MB) * 16 + q * 4 + r;
+      if (o < out && k < in) finish(pl + (size_t)out * k + o, e);
+    }
+  } else {
+    // the t column (k = in) and the bias (k = in + td) of outputs wi.i*64 ..: lane = output, wave = stage
+    const int o = wi.i * 64 + lane;
+    if (active && o < out) {
+      const float* base = slot0 + mt_[WM_RZOFF] + o * NB;
+      float st_ = 0.f, sb_ = 0.f;
+      for (int t = 0; t < nwg; ++t) {
+        const f32x4* d4 = reinterpret_cast<const f32x4*>(base + (size_t)t * wd.recfloats);
+        float dl[NB];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const f32x4 v = d4[q]; dl[4 * q] = v.x; dl[4 * q + 1] = v.y; dl[4 * q + 2] = v.z; dl[4 * q + 3] = v.w; }
+        float pt = 0.f, pb = 0.f;
+#pragma unroll
+        for (int c = 0; c < NB; ++c) { pt = fma_(dl[c], ts, pt); pb = pb + dl[c]; }
+        st_ = st_ + pt; sb_ = sb_ + pb;
+      }
+      ks[wave][lane] = st_; ks[wave][64 + lane] = sb_;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 128; e += WADJ_MU_NT) {
+      const int which = e >> 6, oo = wi.i * 64 + (e & 63);
+      if (oo < out && (which == 1 || wd.td)) finish(pl + (size_t)out * (in + (which ? wd.td : 0)) + oo, e);
+    }
+  }
+}
+
 __global__ __launch_bounds__(WADJ_MU_NT) void k_wadj_mu(WAdjArgs w, WideDev wd, int nitems, int j, int mode) {
   constexpr int MB = WADJ_MB, NBLK = MB * MB;
   __shared__ float ks[7][NBLK * 256];
@@ -281,7 +364,6 @@ __global__ __launch_bounds__(WADJ_MU_NT) void k_wadj_mu(WAdjArgs w, WideDev wd, 
     ts = ci.st_hit.t;
   }
   const bool active = wave < nstage;
-  const int lr = lane & 15, lq = lane >> 4;
   double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
   const float* z = adj_zb(g, cur) + n;
   float* zn = adj_zb(g, cur ^ 1) + n;
@@ -311,78 +393,7 @@ __global__ __launch_bounds__(WADJ_MU_NT) void k_wadj_mu(WAdjArgs w, WideDev wd, 
   };
 #pragma unroll 1
   for (int it = blockIdx.x; it < nitems; it += gridDim.x) {
-    const WAdjItem wi = wadj_item(wd, it);
-    const int* mt_ = wd.meta + wi.l * WMETA;
-    const int in = mt_[WM_IN], out = mt_[WM_OUT], MT = mt_[WM_MT], KG = mt_[WM_KG];
-    const size_t pl = (size_t)mt_[WM_POFF];
-    if (!wi.vec) {
-      const int ngo = (MT + MB - 1) / MB;
-      const int ot0 = (wi.i % ngo) * MB, kt0 = (wi.i / ngo) * MB;
-      if (active) {
-        // K_s[o][k] of the MB x MB blocks: per tile the four MFMAs from zero (columns as their K dimension), then one add
-        const float* base = wadj_rec(w, wd, slot, 0);
-        int aoff[MB], doff[MB];
-#pragma unroll
-        for (int u = 0; u < MB; ++u) {   // (a block past the layer's edge repeats the last one; it is not stored)
-          aoff[u] = mt_[WM_RAOFF] + (min(kt0 + u, KG - 1) * 16 + lr) * NB + lq;
-          doff[u] = mt_[WM_RZOFF] + (min(ot0 + u, MT - 1) * 16 + lr) * NB + lq;
-        }
-        f32x4 sum[NBLK];
-#pragma unroll
-        for (int b = 0; b < NBLK; ++b) sum[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int t = 0; t < a.nwg; ++t) {
-          const float* r = base + (size_t)t * wd.recfloats;
-          float av[MB][4], dv[MB][4];
-#pragma unroll
-          for (int u = 0; u < MB; ++u)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { av[u][q] = r[aoff[u] + 4 * q]; dv[u][q] = r[doff[u] + 4 * q]; }
-#pragma unroll
-          for (int uo = 0; uo < MB; ++uo)
-#pragma unroll
-            for (int uk = 0; uk < MB; ++uk) {
-              f32x4 p = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-              for (int q = 0; q < 4; ++q) p = __builtin_amdgcn_mfma_f32_16x16x4f32(av[uk][q], dv[uo][q], p, 0, 0, 0);
-              f32x4& sm = sum[uo * MB + uk];
-              sm.x = sm.x + p.x; sm.y = sm.y + p.y; sm.z = sm.z + p.z; sm.w = sm.w + p.w;
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < NBLK; ++b)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ks[wave][((b * 4 + r) * 4 + lq) * 16 + lr] = sum[b][r];
-      }
-      __syncthreads();
-      for (int e = threadIdx.x; e < NBLK * 256; e += WADJ_MU_NT) {
-        const int b = e >> 8, r = (e >> 6) & 3, q = (e >> 4) & 3, x = e & 15;
-        const int o = (ot0 + b / MB) * 16 + x, k = (kt0 + b % MB) * 16 + q * 4 + r;
-        if (o < out && k < in) finish(pl + (size_t)out * k + o, e);
-      }
-    } else {
-      // the t column (k = in) and the bias (k = in + td) of outputs wi.i*64 ..: lane = output, wave = stage
-      const int o = wi.i * 64 + lane;
-      if (active && o < out) {
-        const float* base = wadj_rec(w, wd, slot, 0) + mt_[WM_RZOFF] + o * NB;
-        float st_ = 0.f, sb_ = 0.f;
-        for (int t = 0; t < a.nwg; ++t) {
-          const f32x4* d4 = reinterpret_cast<const f32x4*>(base + (size_t)t * wd.recfloats);
-          float dl[NB];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) { const f32x4 v = d4[q]; dl[4 * q] = v.x; dl[4 * q + 1] = v.y; dl[4 * q + 2] = v.z; dl[4 * q + 3] = v.w; }
-          float pt = 0.f, pb = 0.f;
-#pragma unroll
-          for (int c = 0; c < NB; ++c) { pt = fma_(dl[c], ts, pt); pb = pb + dl[c]; }
-          st_ = st_ + pt; sb_ = sb_ + pb;
-        }
-        ks[wave][lane] = st_; ks[wave][64 + lane] = sb_;
-      }
-      __syncthreads();
-      for (int e = threadIdx.x; e < 128; e += WADJ_MU_NT) {
-        const int which = e >> 6, oo = wi.i * 64 + (e & 63);
-        if (oo < out && (which == 1 || wd.td)) finish(pl + (size_t)out * (in + (which ? wd.td : 0)) + oo, e);
-      }
-    }
+    wadj_mu_item(wd, wadj_rec(w, wd, slot, 0), a.nwg, active, wave, lane, ts, it, ks, finish);
     __syncthreads();
   }
   // one fp64 partial (three in init A / B's sets) per workgroup: the waves' sums in wave order

@@ -359,6 +359,10 @@ struct WideStepEpi {
   // after k_S (S = 2..6): store it, x_{S+1} = uprev + dt*(a_{S+1,1} k1 + ... + a_{S+1,S} k_S) left to right -> xl (and u / g6)
   template <int S> __device__ __forceinline__ void stage(int mt, int l, const f32x4& kv, float* xl) const {
     const WideQuad q = wide_quad(mt, l, D, b0, nvalid);
+    wide_put(xl, mt, q, in_act, stage_x<S>(q, kv));
+  }
+  // the same without the LDS store: x_{S+1} of the quad (k_wdisc_step also keeps act0 and act0' of it in its stage record)
+  template <int S> __device__ __forceinline__ f32x4 stage_x(const WideQuad& q, const f32x4& kv) const {
     constexpr int off = (S - 1) * S / 2;
     wide_st4(ks0 + (size_t)(S - 2) * nst, q.g, q.nrow, v4, kv);
     const f32x4 up = wide_ld4(uprev, q.g, q.nrow, v4);
@@ -377,7 +381,7 @@ struct WideStepEpi {
     }
     if (S == 5 && want_stiff) wide_st4(g6, q.g, q.nrow, v4, x);
     if (S == 6) wide_st4(unew, q.g, q.nrow, v4, x);
-    wide_put(xl, mt, q, in_act, x);
+    return x;
   }
   // after k7: store it; utilde, the scaled residual and the stiffness differences in fp64 per lane
   __device__ __forceinline__ void final(int mt, int l, const f32x4& kv, double& aerr, double& anum, double& aden) const {

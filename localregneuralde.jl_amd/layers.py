@@ -376,9 +376,9 @@ class Handle:
 
     ADJOINT_LOOPS = ("host", "device", "chain_device")
     # every kind lrnde_last_adjoint_info reports: the three above and the wide-chain handle's opt-in device loop
-    # and the small chain's discrete sweep (set_sensealg("discrete"))
-    ADJOINT_LOOP_NAMES = ADJOINT_LOOPS + ("wide_device", "chain_discrete")
-    ADJOINT_LOOP_CHOICES = {"auto": 0, "device": 1}
+    # and the small chain's discrete sweep (set_sensealg("discrete")) and the wide chain's (set_adjoint_loop("discrete"))
+    ADJOINT_LOOP_NAMES = ADJOINT_LOOPS + ("wide_device", "chain_discrete", "wide_discrete")
+    ADJOINT_LOOP_CHOICES = {"auto": 0, "device": 1, "discrete": 2}
     SENSEALGS = {"interpolating": 0, "discrete": 1}
 
     def set_sensealg(self, sensealg):
@@ -390,15 +390,17 @@ class Handle:
 
     def set_adjoint_loop(self, loop):
         """lrnde_set_adjoint_loop: "auto" (every handle's own routing; a wide-chain handle takes the host loop) or
-        "device" (a wide-chain handle takes its device-controlled loop; no change for the other handles)"""
+        "device" (a wide-chain handle takes its device-controlled loop; no change for the other handles) or "discrete" (a
+        wide-chain handle alone: the discrete adjoint of the recorded solve on its frozen step grid, two launches per
+        recorded step; any other handle refuses it)"""
         if loop not in self.ADJOINT_LOOP_CHOICES:
-            raise ValueError(f"adjoint_loop must be 'auto' or 'device' (got {loop!r})")
+            raise ValueError(f"adjoint_loop must be 'auto', 'device' or 'discrete' (got {loop!r})")
         self._chk(L.lib.lrnde_set_adjoint_loop(self._ctx, self.ADJOINT_LOOP_CHOICES[loop]))
 
     def last_adjoint_info(self):
         """how the last reversed solve ran (lrnde_last_adjoint_info): kind 0 host loop / 1 the MLP device loop / 2 the
-        chain device loop / 3 the wide-chain device loop / 4 the small chain's discrete sweep, the kernels it enqueued, and
-        the host waits during which the GPU idled"""
+        chain device loop / 3 the wide-chain device loop / 4 the small chain's discrete sweep / 5 the wide chain's discrete
+        sweep, the kernels it enqueued, and the host waits during which the GPU idled"""
         k, n, w = C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(L.lib.lrnde_last_adjoint_info(self._ctx, C.byref(k), C.byref(n), C.byref(w)))
         return dict(kind=int(k.value), launches=int(n.value), host_waits=int(w.value))
@@ -605,9 +607,14 @@ class NeuralODE:
             raise ValueError(f"field must be 'auto', 'dense_chain' or 'wide_chain' (got {field!r})")
         self.field = field
         # adjoint_loop: "auto" keeps every handle's own routing of the reversed solve; "device" opts a wide-chain handle into
-        # its device-controlled loop (Handle.set_adjoint_loop) and changes nothing for the other fields
+        # its device-controlled loop (Handle.set_adjoint_loop) and changes nothing for the other fields; "discrete" gives a
+        # wide-chain handle the discrete adjoint over its step record (the method of sensealg="TrackerAdjoint" on the small
+        # chain; the `sensealg` keyword itself stays closed for field="wide_chain") and is built for that field alone
         if adjoint_loop not in Handle.ADJOINT_LOOP_CHOICES:
-            raise ValueError(f"adjoint_loop must be 'auto' or 'device' (got {adjoint_loop!r})")
+            raise ValueError(f"adjoint_loop must be 'auto', 'device' or 'discrete' (got {adjoint_loop!r})")
+        if adjoint_loop == "discrete" and field != "wide_chain":
+            raise NotImplementedError(f"adjoint_loop='discrete' is built for field='wide_chain' (got field={field!r}); "
+                                      f"field='dense_chain' takes its discrete adjoint with sensealg='TrackerAdjoint'")
         self.adjoint_loop = adjoint_loop
         # sensealg (src/layers/neural_ode.jl:1-23): the method of `pullback` (_sensealg_choice); the discrete adjoint is
         # built for the small Dense-chain handle alone
@@ -742,8 +749,9 @@ class NeuralODE:
         host-controlled loop), "device" (the MLP handle's device-controlled loop), "chain_device" (the Dense-chain
         handle's), "wide_device" (the wide Dense-chain handle's, which runs only for a layer built with
         adjoint_loop="device") or "chain_discrete" (a layer built with sensealg="TrackerAdjoint" / "ReverseDiffAdjoint" /
-        "discrete": no reversed solve, the discrete adjoint of the record in one launch, UPSTREAM-RECALL frozen grid); the
-        conv field's own backward reports None."""
+        "discrete": no reversed solve, the discrete adjoint of the record in one launch, UPSTREAM-RECALL frozen grid) or
+        "wide_discrete" (a field="wide_chain" layer built with adjoint_loop="discrete": the same discrete adjoint, two
+        launches per recorded step and no host wait); the conv field's own backward reports None."""
         h = self._bind(ps, x)
         t0, t2 = self.tspan
         kw = self.kwargs

@@ -9,13 +9,15 @@ Prints one JSON line (and writes it to --out) with, each the median of --reps ru
       per attempted step).
   (e) --only adjoint: case (c)'s forward + pullback with the host-controlled adjoint loop (adjoint_loop="auto") and with the
       device-controlled one (adjoint_loop="device") in the same process: attempts of the reversed solve,
-      launches per attempt, host waits, and us per attempt = (forward + pullback - layer forward) / attempts.
+      launches per attempt, host waits, and us per attempt = (forward + pullback - layer forward) / attempts; and, third,
+      with the discrete adjoint over the step record (adjoint_loop="discrete"): recorded steps walked,
+      launches, host waits, us per recorded step.  Same process, same inputs.
 "us per attempted step" is the solve's kernel time (the library's event bracket around its launches,
 lrnde_last_solve_kernel_ms) over accepted + rejected steps.
 
     python tools/bench/wide_chain_bench.py [--reps 30] [--B 512] [--out profiles/wide_chain/wide_chain_bench.json]
     rocprofv3 --kernel-trace --stats -- python tools/bench/wide_chain_bench.py --only mnist3 --reps 5 --no-eager
-    python tools/bench/wide_chain_bench.py --only adjoint --out profiles/wide_chain/wide_adjoint_bench.json
+    python tools/bench/wide_chain_bench.py --only adjoint --out profiles/wide_chain/wide_discrete_bench.json
     rocprofv3 --kernel-trace --stats -- python tools/bench/wide_chain_bench.py --only adjoint --reps 5
 """
 import argparse
@@ -86,10 +88,12 @@ def leg(model, field, xd, ps, reps, pullback):
 
 
 def adjoint_legs(model, xd, ps, reps):
-    """case (c)'s forward + pullback under both adjoint loops of the wide handle, host loop first"""
+    """case (c)'s forward + pullback under both continuous adjoint loops of the wide handle, host loop first, then under its
+    discrete adjoint"""
     cot = torch.from_numpy(np.random.default_rng(1).standard_normal(tuple(xd.shape)).astype(np.float32)).cuda()
     out = {}
-    for loop in ("auto", "device"):
+    keys = {"auto": "host_loop", "device": "device_loop", "discrete": "discrete_sweep"}
+    for loop in ("auto", "device", "discrete"):
         node = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, save_start=False, maxiters=100000,
                            field="wide_chain", adjoint_loop=loop)
         st = node.initialstates(np.random.default_rng(0))
@@ -98,7 +102,7 @@ def adjoint_legs(model, xd, ps, reps):
         _, _, info = node.pullback(xd, ps, st, cot, w_reg=10.0)
         ai, sb = node.handle().last_adjoint_info(), info["stats_bwd"]
         attempts = sb["naccept"] + sb["nreject"]
-        out["host_loop" if loop == "auto" else "device_loop"] = dict(
+        out[keys[loop]] = dict(
             adjoint_loop=info["adjoint_loop"], layer_forward_ms=fwd, layer_forward_pullback_ms=both, attempts=attempts,
             naccept=sb["naccept"], nreject=sb["nreject"], launches=ai["launches"],
             launches_per_attempt=round(ai["launches"] / max(attempts, 1), 2), host_waits=ai["host_waits"],
@@ -107,6 +111,10 @@ def adjoint_legs(model, xd, ps, reps):
     h, d = out["host_loop"]["layer_forward_pullback_ms"], out["device_loop"]["layer_forward_pullback_ms"]
     out["device_over_host_pullback"] = round(d["median"] / h["median"], 3)
     out["device_below_host_by_more_than_the_spread"] = bool(d["max"] < h["min"])
+    # (the discrete row's "attempts" are the recorded steps it walked: naccept = the forward's, nreject = 0)
+    s = out["discrete_sweep"]["layer_forward_pullback_ms"]
+    out["discrete_over_device_pullback"] = round(s["median"] / d["median"], 3)
+    out["discrete_below_device_by_more_than_the_spread"] = bool(s["max"] < d["min"] and d["min"] - s["max"] > max(s["max"] - s["min"], d["max"] - d["min"]))
     return out
 
 
