@@ -480,17 +480,33 @@ static_assert((QPARK >> QSB) == 0, "LRNDE_QPARK is a mask over the QSB stream bl
 static_assert(smem_bytes_q(7 * QSEG, QSEG, 2, 13) + q_park_bytes(QPARK) <= 160 * 1024,
               "forward layout + park region exceed the 160 KiB of LDS of a CU: park fewer blocks");
 
+// Register-parked stream block: bit B of the mask = the 8 fragments of stream block B of every wave stay in 32 VGPRs of
+// the wave (StreamQ::rpark) for the whole launch of the register form of k_step_q, loaded once at its head and taken
+// by the block's MFMAs as operands where they lie: no load, no LDS traffic and no copy into the ring in any f-eval.
+// The registers are the ones the stream's addresses held before they moved into the loads' immediate offsets
+// (q_stream_fetch_quad).  At most one block, disjoint from LRNDE_QPARK, not the (partial) last one; 0 = none, the
+// kernels are the ones of the immediate-offset stream alone.  Default: block 5, just ahead of the LDS-parked last
+// Dense-1 block (DESIGN.md 4.1 "Register-parked block / immediate-offset stream", profiles/rpark).
+#ifndef LRNDE_QRPARK
+#define LRNDE_QRPARK 0x20u
+#endif
+constexpr unsigned QRPARK = LRNDE_QRPARK;
+static_assert((QRPARK >> (QSB - 1)) == 0 && q_popcount(QRPARK) <= 1, "LRNDE_QRPARK names at most one of the stream blocks 0..QSB-2");
+static_assert((QRPARK & QPARK) == 0, "a block is parked in LDS (LRNDE_QPARK) or in registers (LRNDE_QRPARK), not both");
+__host__ __device__ constexpr bool q_parked(unsigned mask, int B) { return ((mask >> B) & 1u) != 0; }
+
 template <int I> struct IC { static constexpr int value = I; };
 template <int I0, int I1, class F> __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I0 < I1) { f(IC<I0>{}); static_for<I0 + 1, I1>(f); }
 }
 
 struct StreamQ {
-  __amdgpu_buffer_rsrc_t rs1, rs2;
-  int v1[2], v2[2];          // per-lane offsets of the wave's Dense-1 / Dense-2 row groups (or out of range)
-  int s1[2], s2[2];          // scalar byte offsets of the first quad of those row groups
+  __amdgpu_buffer_rsrc_t rs1[2], rs2[2];  // descriptors of the wave's Dense-1 / Dense-2 row groups: they begin at the group's
+                             // first quad of this wave (q_stream_rsrc), so a fragment's offset is a compile-time constant
+  int v1[2], v2[2];          // per-lane offsets of those row groups (or out of range)
   int kq2_real;              // ceil(H/4): Dense-2 quads at/after it are not fetched
   f32x4 ring[QRING][QSQ][2];
+  f32x4 rpark[QSQ][2];       // the register-parked block (QRPARK).  Set by k_step_q only
   const f32x4* park;         // parked blocks (QPARK): this lane's quad of the wave's own fragment 0, in LDS; fragment f is
                              // 64 quads (1 KiB) further on each.  Set by k_step_q only
 };
@@ -499,56 +515,86 @@ __device__ __forceinline__ void q_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// Addressing of the stream.  Fragment (block B, quad J, row group c) lies (B' * QSQ + J) * 1024 bytes behind the first
+// quad of its row group, B' = the block's index inside its layer, and the row group's descriptor begins at that first
+// quad.  The load takes the fragment as
+//   vector offset  v[c] + J * 1024    the lane's offset, the quad in the instruction's 12-bit immediate (at most 3072;
+//                                     the sum is unsigned: an out-of-range 0x7ffffff0 becomes 0x800003f0 .. 0x80000bf0,
+//                                     out of range as well, and does not wrap)
+//   scalar offset  B' * 4096          one of six constants, the same for both layers and row groups,
+// so no address lives in a register of its own.  Written as rs + v[c] + (s[c] + constant) with s[c] the wave's runtime
+// offset, the 90 offsets of an f-eval were launch invariants that hipcc kept in registers: 45 SGPRs (spilled into VGPR
+// lanes and read back ahead of each load) and, for Dense-2, whose select below it folded the constant into, 42 VGPRs.
+//
+// lane offset + quad, as an unsigned sum (0x7ffffff0 + 3072 overflows an int)
+__device__ __forceinline__ int q_lane_off(int v, int quad_bytes) { return (int)((unsigned)v + (unsigned)quad_bytes); }
+// descriptor of `bytes` of weights from byte `first` on (on = false: a row group or a wave that has none, every lane of
+// it is out of range: any valid descriptor)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t q_stream_rsrc(const float* W, int bytes, int first, bool on) {
+  const int f = on ? first : 0;
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(W) + f), 0, bytes - f, 0x00020000);
+}
+// the two loads (row groups 0 and 1) of quad J of stream block B.
+// KT = number of k-quads of the LAST Dense-2 block that exist.  launch_step instantiates two values: KT = 1 exactly when
+// ceil(H/4) == 25 (kq2_real = 25: the callers emit quads 0..24 and every emitted Dense-2 load is real, which is the only
+// reason the KT < 4 branch below may drop the test), and KT = 4 otherwise, the generic form: quads at or after kq2_real
+// are fetched with an out-of-range offset and return 0 without touching memory.  KT = 2, 3 are never instantiated, and
+// would need a launch rule of the same kind (KT = kq2_real - 24) before they could be.
+template <int B, int J, int KT>
+__device__ __forceinline__ void q_stream_fetch_quad(const StreamQ& st, f32x4& r0, f32x4& r1) {
+#ifdef LRNDE_QABL_NOLOAD  // diagnostic ablation: no weight stream (results are meaningless)
+  r0 = f32x4{0.f, 0.f, 0.f, 0.f}; r1 = f32x4{0.f, 0.f, 0.f, 0.f};
+  asm volatile("" : "+v"(r0), "+v"(r1));
+  return;
+#endif
+  // (the generic form keeps the quad in the scalar constant: the 12 sums v[c] + J * 1024, which hipcc forms once per
+  //  launch where a load sits in another basic block than the first one, are VGPRs k_step_q<*, 4> does not have)
+  constexpr int BL = B < QSB1 ? B : B - QSB1;
+  constexpr int voff = KT < 4 ? J * 1024 : 0, soff = KT < 4 ? BL * (QSQ * 1024) : (BL * QSQ + J) * 1024;
+  if constexpr (B < QSB1) {
+    r0 = wload(st.rs1[0], q_lane_off(st.v1[0], voff), soff);
+    r1 = wload(st.rs1[1], q_lane_off(st.v1[1], voff), soff);
+  } else if constexpr (KT < 4) {
+    r0 = wload(st.rs2[0], q_lane_off(st.v2[0], voff), soff);
+    r1 = wload(st.rs2[1], q_lane_off(st.v2[1], voff), soff);
+  } else {
+    // wave-uniform; as an OR with a scalar (v2 is lane * 16 < 1024 or 0x7ffffff0 itself: the OR is 0x7ffffff0 exactly)
+    const int oor = (BL * QSQ + J) < st.kq2_real ? 0 : 0x7ffffff0;
+    r0 = wload(st.rs2[0], st.v2[0] | oor, soff);
+    r1 = wload(st.rs2[1], st.v2[1] | oor, soff);
+  }
+}
+
 // issue the 8 loads of stream block B (0..QSB-1) into ring slot SLOT
 template <int B, int SLOT>
 __device__ __forceinline__ void q_stream_load(StreamQ& st) {
-  if constexpr (B < QSB1) {
-#pragma unroll
-    for (int j = 0; j < QSQ; ++j) {
-      st.ring[SLOT][j][0] = wload(st.rs1, st.v1[0], st.s1[0] + (B * QSQ + j) * 1024);
-      st.ring[SLOT][j][1] = wload(st.rs1, st.v1[1], st.s1[1] + (B * QSQ + j) * 1024);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < QSQ; ++j) {
-      constexpr int kq = (B - QSB1) * QSQ;
-      const bool real = (kq + j) < st.kq2_real;  // wave-uniform
-      st.ring[SLOT][j][0] = wload(st.rs2, real ? st.v2[0] : 0x7ffffff0, st.s2[0] + (kq + j) * 1024);
-      st.ring[SLOT][j][1] = wload(st.rs2, real ? st.v2[1] : 0x7ffffff0, st.s2[1] + (kq + j) * 1024);
-    }
-  }
+  static_for<0, QSQ>([&](auto Jc) {
+    constexpr int J = decltype(Jc)::value;
+    q_stream_fetch_quad<B, J, 4>(st, st.ring[SLOT][J][0], st.ring[SLOT][J][1]);
+  });
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// the two loads (row groups 0 and 1) of quad J of stream block B: the pieces of q_stream_load, for interleaving with MFMAs
-// KT = number of k-quads of the LAST Dense-2 block that exist (1..4; 4 = generic: quads beyond the real matrix are
-// fetched with an out-of-range offset and return 0).  With KT < 4 the missing quads are neither loaded nor multiplied:
-// an out-of-range load still costs its slot in the SIMD's return path (tools/oor_probe.hip), and for H = 100 (25 real
-// quads) 3 of the 28 loads of every Dense-2 row group were of that kind.
-// PARK = the mask of parked blocks (QPARK; 0 in every kernel but the register form of k_step_q): the two fragments of a
-// parked block come from the wave's own LDS region — what q_park_fill's same two buffer loads returned, lane for lane —
-// into the same ring registers at the same point of the interleave
-template <int B, int SLOT, int J, int KT = 4, unsigned PARK = 0>
+// the two loads of quad J of stream block B into ring slot SLOT: the pieces of q_stream_load, for interleaving with
+// MFMAs.
+// With KT < 4 the missing quads of the last Dense-2 block are neither loaded nor multiplied: an out-of-range load still
+// costs its slot in the SIMD's return path (tools/oor_probe.hip), and for H = 100 (25 real quads) 3 of the 28 loads of
+// every Dense-2 row group were of that kind.
+// PARK = the mask of LDS-parked blocks (QPARK; 0 in every kernel but the register form of k_step_q): the two fragments
+// of a parked block come from the wave's own LDS region — what q_park_fill's same two buffer loads returned, lane for
+// lane — into the same ring registers at the same point of the interleave.
+// RPARK = the mask of the register-parked block (QRPARK, likewise): nothing is issued for it, its MFMAs read StreamQ::rpark
+template <int B, int SLOT, int J, int KT = 4, unsigned PARK = 0, unsigned RPARK = 0>
 __device__ __forceinline__ void q_stream_load_quad(StreamQ& st) {
-#ifdef LRNDE_QABL_NOLOAD  // diagnostic ablation: no weight stream (results are meaningless)
-  st.ring[SLOT][J][0] = f32x4{0.f, 0.f, 0.f, 0.f}; st.ring[SLOT][J][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  asm volatile("" : "+v"(st.ring[SLOT][J][0]), "+v"(st.ring[SLOT][J][1]));
-  return;
-#endif
-  if constexpr (((PARK >> B) & 1u) != 0) {
+  if constexpr (q_parked(RPARK, B)) {
+  } else if constexpr (q_parked(PARK, B)) {
     if constexpr (B < QSB - 1 || J < KT) {
       constexpr int f = (q_park_index(PARK, B) * QSQ + J) * 2;
       st.ring[SLOT][J][0] = st.park[f * 64];
       st.ring[SLOT][J][1] = st.park[(f + 1) * 64];
     }
-  } else if constexpr (B < QSB1) {
-    st.ring[SLOT][J][0] = wload(st.rs1, st.v1[0], st.s1[0] + (B * QSQ + J) * 1024);
-    st.ring[SLOT][J][1] = wload(st.rs1, st.v1[1], st.s1[1] + (B * QSQ + J) * 1024);
   } else if constexpr (B < QSB - 1 || J < KT) {
-    constexpr int kq = (B - QSB1) * QSQ;
-    const bool real = (kq + J) < st.kq2_real;  // wave-uniform
-    st.ring[SLOT][J][0] = wload(st.rs2, real ? st.v2[0] : 0x7ffffff0, st.s2[0] + (kq + J) * 1024);
-    st.ring[SLOT][J][1] = wload(st.rs2, real ? st.v2[1] : 0x7ffffff0, st.s2[1] + (kq + J) * 1024);
+    q_stream_fetch_quad<B, J, KT>(st, st.ring[SLOT][J][0], st.ring[SLOT][J][1]);
   }
 }
 
@@ -556,22 +602,21 @@ __device__ __forceinline__ void stream_init_q(const ModelDev& m, StreamQ& st) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int voff = lane * 16;
-  st.rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)m.W1q, 0, m.RG1 * m.KQ1p * 1024, 0x00020000);
-  st.rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)m.W2q, 0, q_w2_groups(m.KQ1p) * m.KQ2p * 1024, 0x00020000);
   const bool has1 = wave < q_nseg1(m);
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
+    // the wave's K-segment of W1q's row group c / its packed group 2w + c of W2q
+    st.rs1[c] = q_stream_rsrc(m.W1q, m.RG1 * m.KQ1p * 1024, (c * m.KQ1p + wave * QSEG) * 1024, has1 && c < m.RG1);
+    st.rs2[c] = q_stream_rsrc(m.W2q, q_w2_groups(m.KQ1p) * m.KQ2p * 1024, (2 * wave + c) * m.KQ2p * 1024, has1);
 #ifdef LRNDE_X_FULLROWS  // experiment: rows H..64*RG1-1 of W1q are real (zero) memory instead of out-of-range lanes
     st.v1[c] = (has1 && c < m.RG1) ? voff : 0x7ffffff0;
 #else
     st.v1[c] = (has1 && c < m.RG1 && c * 64 + lane < m.H) ? voff : 0x7ffffff0;
 #endif
-    st.s1[c] = (c * m.KQ1p + (has1 ? wave * QSEG : 0)) * 1024;
     // Dense-2: packed groups 2w, 2w+1 = rows 112w + 64c + lane (q_w2_row); the second group's last 16 rows are the next
     // wave's, packed as zeros and out of range here as well
     const int rb = wave * (QSEG * 4) + c * 64;
     st.v2[c] = (has1 && (c == 0 || lane < QSEG * 4 - 64) && rb + lane < m.D) ? voff : 0x7ffffff0;
-    st.s2[c] = (has1 ? 2 * wave + c : 0) * m.KQ2p * 1024;
   }
   st.kq2_real = (m.H + 3) / 4;
   static_for<0, QAHEAD>([&](auto Bc) { constexpr int B = decltype(Bc)::value; q_stream_load<B, B>(st); });
@@ -582,7 +627,7 @@ __device__ __forceinline__ void stream_init_q(const ModelDev& m, StreamQ& st) {
 // queue behind the other waves' bursts before it could start its MFMAs (56.5 -> 53.0 us per step).  -DLRNDE_QBURST
 // builds the burst form.
 #ifndef LRNDE_QBURST
-#define LRNDE_QLOAD_QUAD(BB, SS, JJ) q_stream_load_quad<BB, SS, JJ, KT, PARK>(st)
+#define LRNDE_QLOAD_QUAD(BB, SS, JJ) q_stream_load_quad<BB, SS, JJ, KT, PARK, RPARK>(st)
 #define LRNDE_QPIN() __builtin_amdgcn_sched_barrier(0)
 #else
 #define LRNDE_QLOAD_QUAD(BB, SS, JJ) do {} while (0)
@@ -597,7 +642,8 @@ __device__ __forceinline__ f32x4 qmfma(float a, float b, f32x4 c) { return __bui
 #endif
 // ep1 = epilogue 1's invariants where the caller made them once for all the f-evals of its launch (k_step_q's register
 // form); nullptr (a constant at every call): they are made here, behind the first barrier
-template <class Epi, int SLOT0, int KT = 4, unsigned PARK = 0>
+// RPARK: the MFMAs of the register-parked block take StreamQ::rpark where those of the others take their ring slot
+template <class Epi, int SLOT0, int KT = 4, unsigned PARK = 0, unsigned RPARK = 0>
 __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, StreamQ& st, float ts, const Epi& epi,
                                          const Epi1Q* ep1 = nullptr) {
   const int lane = threadIdx.x & 63;
@@ -628,17 +674,18 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
         for (int j = 0; j < QSQ; ++j) bq[(B + 1) & 1][j] = xp[((B + 1) * QSQ + j) * 4];
       }
       const f32x4 (&b_)[QSQ] = bq[B & 1];
+      const f32x4 (&w_)[QSQ][2] = q_parked(RPARK, B) ? st.rpark : st.ring[SL];
       static_for<0, QSQ>([&](auto Jc) {
         constexpr int j = decltype(Jc)::value;
         LRNDE_QLOAD_QUAD((B + QAHEAD) % QSB, NSL, j);
-        acc0 = qmfma(st.ring[SL][j][0].x, b_[j].x, acc0);
-        acc1 = qmfma(st.ring[SL][j][1].x, b_[j].x, acc1);
-        acc0 = qmfma(st.ring[SL][j][0].y, b_[j].y, acc0);
-        acc1 = qmfma(st.ring[SL][j][1].y, b_[j].y, acc1);
-        acc0 = qmfma(st.ring[SL][j][0].z, b_[j].z, acc0);
-        acc1 = qmfma(st.ring[SL][j][1].z, b_[j].z, acc1);
-        acc0 = qmfma(st.ring[SL][j][0].w, b_[j].w, acc0);
-        acc1 = qmfma(st.ring[SL][j][1].w, b_[j].w, acc1);
+        acc0 = qmfma(w_[j][0].x, b_[j].x, acc0);
+        acc1 = qmfma(w_[j][1].x, b_[j].x, acc1);
+        acc0 = qmfma(w_[j][0].y, b_[j].y, acc0);
+        acc1 = qmfma(w_[j][1].y, b_[j].y, acc1);
+        acc0 = qmfma(w_[j][0].z, b_[j].z, acc0);
+        acc1 = qmfma(w_[j][1].z, b_[j].z, acc1);
+        acc0 = qmfma(w_[j][0].w, b_[j].w, acc0);
+        acc1 = qmfma(w_[j][1].w, b_[j].w, acc1);
         LRNDE_QPIN();
       });
       __builtin_amdgcn_sched_barrier(0);
@@ -685,18 +732,19 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
         for (int j = 0; j < QSQ; ++j) bq[(B + 1) & 1][j] = hp[((B + 1) * QSQ + j) * 4];
       }
       const f32x4 (&b_)[QSQ] = bq[B & 1];
+      const f32x4 (&w_)[QSQ][2] = q_parked(RPARK, QSB1 + B) ? st.rpark : st.ring[SL];
       static_for<0, QSQ>([&](auto Jc) {
         constexpr int j = decltype(Jc)::value;
         LRNDE_QLOAD_QUAD((QSB1 + B + QAHEAD) % QSB, NSL, j);
         if constexpr (B < QSB2 - 1 || j < KT) {
-          acc0 = qmfma(st.ring[SL][j][0].x, b_[j].x, acc0);
-          acc1 = qmfma(st.ring[SL][j][1].x, b_[j].x, acc1);
-          acc0 = qmfma(st.ring[SL][j][0].y, b_[j].y, acc0);
-          acc1 = qmfma(st.ring[SL][j][1].y, b_[j].y, acc1);
-          acc0 = qmfma(st.ring[SL][j][0].z, b_[j].z, acc0);
-          acc1 = qmfma(st.ring[SL][j][1].z, b_[j].z, acc1);
-          acc0 = qmfma(st.ring[SL][j][0].w, b_[j].w, acc0);
-          acc1 = qmfma(st.ring[SL][j][1].w, b_[j].w, acc1);
+          acc0 = qmfma(w_[j][0].x, b_[j].x, acc0);
+          acc1 = qmfma(w_[j][1].x, b_[j].x, acc1);
+          acc0 = qmfma(w_[j][0].y, b_[j].y, acc0);
+          acc1 = qmfma(w_[j][1].y, b_[j].y, acc1);
+          acc0 = qmfma(w_[j][0].z, b_[j].z, acc0);
+          acc1 = qmfma(w_[j][1].z, b_[j].z, acc1);
+          acc0 = qmfma(w_[j][0].w, b_[j].w, acc0);
+          acc1 = qmfma(w_[j][1].w, b_[j].w, acc1);
         }
         LRNDE_QPIN();
       });
@@ -874,6 +922,8 @@ __global__ __launch_bounds__(QNT) void k_init2_q(StepArgs a) {
 // a part of stream_init_q: hipcc compiled the shared form of it to other code in every kernel of the family, and the
 // kernels without a park stay instruction for instruction what they were.)
 struct QRowOff { int v1, s1, v2, s2; };
+// ... through descriptors of the whole matrices (the stream's own begin at the issuing wave's rows, StreamQ)
+struct QParkSrc { __amdgpu_buffer_rsrc_t rs1, rs2; int kq2_real; };
 __device__ __forceinline__ QRowOff q_row_off(const ModelDev& m, int wave, int lane, int c) {
   const int voff = lane * 16;
   const bool has1 = wave < q_nseg1(m);
@@ -901,7 +951,7 @@ __device__ __forceinline__ QRowOff q_row_off(const ModelDev& m, int wave, int la
 //
 // fragment e (= quad e / 2, row group e % 2) of stream block B of wave 0, whose row offsets are ra (group 0), rb (group 1)
 template <int B>
-__device__ __forceinline__ f32x4 q_park_load0(const StreamQ& st, const QRowOff& ra, const QRowOff& rb, int e, bool on) {
+__device__ __forceinline__ f32x4 q_park_load0(const QParkSrc& st, const QRowOff& ra, const QRowOff& rb, int e, bool on) {
   const int J = e >> 1;
   const bool c1 = (e & 1) != 0;
   if constexpr (B < QSB1) {
@@ -912,17 +962,18 @@ __device__ __forceinline__ f32x4 q_park_load0(const StreamQ& st, const QRowOff& 
   }
 }
 template <unsigned PARK, int KT, int P>
-__device__ __forceinline__ void q_park_fill_block(StreamQ& st, const QRowOff& ra, const QRowOff& rb, int fw, f32x4* own, f32x4* w0) {
+__device__ __forceinline__ void q_park_fill_block(StreamQ& st, const QParkSrc& src, const QRowOff& ra, const QRowOff& rb, int fw,
+                                                  f32x4* own, f32x4* w0) {
   if constexpr (P < q_park_nb(PARK)) {
     constexpr int B = q_park_block(PARK, P), FREE = QRING - 1;
     // wave 0's fragment e of this block: e = fw for every wave, and e = 6, 7 for two waves that rotate with P
     const int e2 = QNW - 1 + fw - 2 * (P % 3);
     const bool on2 = e2 >= QNW - 1 && e2 < QPARK_FRAG;
-    q_stream_load_quad<B, FREE, 0, KT, 0>(st);
-    q_stream_load_quad<B, FREE, 1, KT, 0>(st);
-    q_stream_load_quad<B, FREE, 2, KT, 0>(st);
-    q_stream_load_quad<B, FREE, 3, KT, 0>(st);
-    const f32x4 va = q_park_load0<B>(st, ra, rb, fw, true), vb = q_park_load0<B>(st, ra, rb, on2 ? e2 : 0, on2);
+    static_for<0, QSQ>([&](auto Jc) {
+      constexpr int J = decltype(Jc)::value;
+      if constexpr (B < QSB - 1 || J < KT) q_stream_fetch_quad<B, J, KT>(st, st.ring[FREE][J][0], st.ring[FREE][J][1]);
+    });
+    const f32x4 va = q_park_load0<B>(src, ra, rb, fw, true), vb = q_park_load0<B>(src, ra, rb, on2 ? e2 : 0, on2);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int J = 0; J < QSQ; ++J) {
@@ -934,17 +985,33 @@ __device__ __forceinline__ void q_park_fill_block(StreamQ& st, const QRowOff& ra
     w0[(P * QPARK_FRAG + fw) * 64] = va;
     if (on2) w0[(P * QPARK_FRAG + e2) * 64] = vb;
     __builtin_amdgcn_sched_barrier(0);
-    q_park_fill_block<PARK, KT, P + 1>(st, ra, rb, fw, own, w0);
+    q_park_fill_block<PARK, KT, P + 1>(st, src, ra, rb, fw, own, w0);
   }
 }
 template <unsigned PARK, int KT>
 __device__ __forceinline__ void q_park_fill(const ModelDev& m, StreamQ& st, f32x4* park) {
-  static_assert(QSQ == 4, "q_park_fill_block issues the four quads of a block by name");
   constexpr int NF = q_park_nb(PARK) * QPARK_FRAG;
   const int lane = threadIdx.x & 63;
   const int fw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) - 1;  // 0..5
   const QRowOff ra = q_row_off(m, 0, lane, 0), rb = q_row_off(m, 0, lane, 1);
-  q_park_fill_block<PARK, KT, 0>(st, ra, rb, fw, park + (size_t)(fw + 1) * (NF * 64) + lane, park + lane);
+  QParkSrc src;
+  src.rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)m.W1q, 0, m.RG1 * m.KQ1p * 1024, 0x00020000);
+  src.rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)m.W2q, 0, q_w2_groups(m.KQ1p) * m.KQ2p * 1024, 0x00020000);
+  src.kq2_real = st.kq2_real;
+  q_park_fill_block<PARK, KT, 0>(st, src, ra, rb, fw, park + (size_t)(fw + 1) * (NF * 64) + lane, park + lane);
+}
+
+// the eight loads of the register-parked block, at the head of k_step_q: the stream's own loads of that block, into
+// StreamQ::rpark.  An out-of-range lane (or a wave without rows) keeps the zeros the stream would have fed its MFMAs.
+template <unsigned RPARK, int KT>
+__device__ __forceinline__ void q_rpark_load(StreamQ& st) {
+  if constexpr (RPARK != 0) {
+    constexpr int B = q_park_block(RPARK, 0);
+    static_for<0, QSQ>([&](auto Jc) {
+      constexpr int J = decltype(Jc)::value;
+      q_stream_fetch_quad<B, J, KT>(st, st.rpark[J][0], st.rpark[J][1]);
+    });
+  }
 }
 
 // one attempted Tsit5 step, 4 columns per workgroup (same flow as k_step's fused path)
@@ -984,12 +1051,13 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
   f32x4* kl = REGS ? nullptr : q_extra_smem(s);  // LDS form: [9][KL]: 0,1 = pair 0; 2,3 = pair 1; 4..8 = k2..k6
   const int KL = a.m.KQ1p * 4;
   constexpr bool PARKED = REGS && QPARK != 0;
+  constexpr unsigned RPARK = REGS ? QRPARK : 0u;
   if constexpr (PARKED) {  // the wave's own 16 KiB of the park region, behind the forward layout
     constexpr int NF = q_park_nb(QPARK) * QPARK_FRAG;
     fc.park = q_extra_smem(s) + (size_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (NF * 64) + (threadIdx.x & 63);
   }
   if (threadIdx.x < 64) {
-    if constexpr (REGS) preload();  // in flight while the wave decides
+    if constexpr (REGS) { preload(); q_rpark_load<RPARK, KT>(fc); }  // in flight while the wave decides
     step_prologue(a, j, s.bc);
   } else {
     // (LDS init first: the prologue's own loads are already on their way when these 48 (LDS form: 72) wave-loads reach
@@ -997,6 +1065,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     smem_init_q<true>(a.m, s);
     if constexpr (REGS) {
       preload();
+      q_rpark_load<RPARK, KT>(fc);
       if constexpr (PARKED) q_park_fill<QPARK, KT>(a.m, fc, q_extra_smem(s));
     } else {  // LDS form: the six waves load both pairs of the whole tile into kl, ordered by the barrier below
 #ifndef LRNDE_NO_PRELOAD
@@ -1169,7 +1238,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
       EpiStageQ<S> e;                                                                   \
       e.io = io; e.off_out = off_out; e.off_x = off_x;                                  \
       e.dt = dt; e.xl = s.xl; e.R = &R; e.store_k = bc.store_k;                         \
-      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT, QPARK>(a.m, s, fc, (TS), e, ep1); \
+      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT, QPARK, RPARK>(a.m, s, fc, (TS), e, ep1); \
     } else {                                                                            \
       EpiStageQL<S> e;                                                                  \
       e.io = io; e.off_up = o_up; e.off_k[0] = o_k1;                                    \
@@ -1196,7 +1265,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
     ef.xl = s.xl; ef.R = &R;
     ef.rec = rec; ef.nstB = (int)(a.n_local * 4); ef.rsD = rsD;
-    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT, QPARK>(a.m, s, fc, t + dt, ef, ep1);
+    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT, QPARK, RPARK>(a.m, s, fc, t + dt, ef, ep1);
   } else {
     EpiFinalQL ef;
     ef.io = io; ef.off_up = o_up; ef.off_u = o_un; ef.off_k[0] = o_k1;
