@@ -7,7 +7,11 @@ Measured (printed by the tests):
   sigmoid_c max abs error 8.87e-08 (at x = 7.38) against tanhf_c's 7.75e-08 over the same sweep: bound 4 x 7.75e-08;
   host float32 restatement vs float64: 3e-08..2.7e-07 of each output's norm at both shapes, the torch float32 run the same:
   every bound is the rule's floor 1e-5;
-  RK4 200 vs 400 steps, tiny shape: at most 1.1e-10 of a gradient block's norm (bound 1e-4)."""
+  RK4 200 vs 400 steps, tiny shape: at most 1.1e-10 of a gradient block's norm (bound 1e-4); at the experiment's shape
+  1.2e-10..2.4e-10, gen_to_data 2.7e-11;
+  LC.ENVELOPE (the shapes of tests/test_gpu_latent_envelope.py): torch float32 against float64 per LC.sub_blocks / LC.dx_rows
+  entry and forward output at most 5.5e-7 on the envelope, 6.5e-7 on the optional-argument runs, 1.7e-6 on the merged cases
+  (update_gate.l2_b of 3/5/3/2 B = 9 T = 4): asserted <= 2.5e-6, where max(1e-5, 4 x twin) is still its floor."""
 import os
 import subprocess
 import textwrap
@@ -189,3 +193,139 @@ def test_end_to_end_yardstick_error():
     print("RK4 200 vs 400 steps, relative to each block's norm:", {k: f"{v:.2e}" for k, v in errs.items()})
     assert all(np.linalg.norm(gb[k]) > 0 for k in LC.BLOCKS)
     assert max(errs.values()) <= 1e-4, errs
+
+
+# ---- the shape envelope of tests/test_gpu_latent_envelope.py (LC.ENVELOPE) ---------------------------------------------------
+TWIN_CAP = 2.5e-6   # 4 x this is the floor 1e-5 of LC.bound: while every twin distance is below it the rule cannot widen
+
+
+@pytest.mark.parametrize("name,dims,B,T", LC.ENVELOPE)
+def test_envelope_batches_meet_their_selection_conditions(name, dims, B, T):
+    c = LC.envelope_inputs(dims, B, T)
+    obs = LC.observed(c["x"], dims[0])                                  # (B, T)
+    nt = (B + LC.LNB - 1) // LC.LNB
+    tile = np.stack([obs[i * LC.LNB:(i + 1) * LC.LNB].any(axis=0) for i in range(nt)])   # (tiles, T): the tile runs the step
+    assert (~obs).all(axis=0).any()                                     # a step unobserved everywhere
+    assert not obs[B - 1].any() and obs[:B - 1].any(axis=1).all()       # only the last column is never observed
+    if B >= 16:
+        assert (~tile[0] & tile[1]).any() and (tile[0] & ~tile[1]).any()   # the tiles skip different steps
+        assert obs[:16].any(axis=0)[:2].all()                           # ... which the other tile runs
+    if name in ("lwide", "nwide"):
+        assert (~tile.any(axis=1)).any()                                # a tile that skips every step
+    assert (B % LC.LNB == 0) == (name in ("min", "hmax", "physionet3"))  # full last tiles
+    assert set(np.unique(c["x"][:, :, dims[0]:2 * dims[0]])) <= {0.0, 1.0}
+
+
+@pytest.mark.parametrize("name", LC.ENVELOPE_NAMES)
+@pytest.mark.parametrize("training", [True, False])
+def test_host_restatement_on_the_envelope(name, training):
+    c = LC.envelope_case(name)
+    dims, B = c["dims"], c["B"]
+    zero = [np.zeros_like(c["eps"])] * 3
+    if training:
+        r64, r32 = c["r64"], c["r32"]
+    else:
+        r64, r32 = (LC.encoder_reference(dims, c["flat"], c["x"], c["eps"], zero, dt, False) for dt in (torch.float64, torch.float32))
+    got = LC.run_host(dims, c["flat"], c["x"], c["eps"], training)
+    for k in ("y", "mu", "logvar", "z0"):
+        b, e = LC.bound(r32[k], r64[k]), LC.rel(got[k], r64[k])
+        print(f"{name} training={training} {k}: host {e:.2e} torch-f32 {LC.rel(r32[k], r64[k]):.2e} bound {b:.2e}")
+        assert e <= b, (k, e, b)
+    L = dims[2]
+    assert np.array_equal(got["y"][B - 1], np.concatenate([np.zeros(L, np.float32), np.ones(L, np.float32)]))
+
+
+def _twin_rows(c):
+    rows = [(n, twin) for n, _, twin, _ in LC.sub_block_errors(c["dims"], c["r64"]["dp"], c["r64"]["dx"], c["r64"], c["r32"])]
+    return rows + [(k, LC.rel(c["r32"][k], c["r64"][k])) for k in ("y", "mu", "logvar", "z0")]
+
+
+def _assert_twin(label, rows):
+    worst = max(rows, key=lambda r: r[1])
+    print(f"{label}: worst float32 twin distance {worst[1]:.2e} ({worst[0]}) of {len(rows)} entries")
+    assert worst[1] <= TWIN_CAP, (label, worst)
+
+
+@pytest.mark.parametrize("name", LC.ENVELOPE_NAMES)
+def test_the_yardstick_binds_on_the_envelope(name):
+    """a condition, not a measurement: the float32 torch run is within 2.5e-6 of the float64 run on every sub-block, dx row
+    group and forward output, so max(1e-5, 4 x twin) is its floor 1e-5 wherever the GPU tests apply it"""
+    _assert_twin(name, _twin_rows(LC.envelope_case(name)))
+
+
+@pytest.mark.parametrize("run", [r[0] for r in LC.OPTIONAL_RUNS])
+def test_the_yardstick_binds_on_the_optional_argument_runs(run):
+    _assert_twin("hmax run " + run, _twin_rows(LC.optional_case(run)))
+
+
+def test_the_yardstick_binds_on_the_merged_cases():
+    import test_gpu_latent as TG
+    for dims, B, T in TG.CASES:
+        _assert_twin(f"{dims} B={B} T={T}", _twin_rows(dict(TG.case(dims, B, T), dims=dims)))
+
+
+@pytest.mark.parametrize("name", LC.ENVELOPE_NAMES)
+def test_exact_zeros_of_the_float64_restatement_on_the_envelope(name):
+    c = LC.envelope_case(name)
+    dims = c["dims"]
+    obs = LC.observed(c["x"], dims[0])
+    dx, dp = c["r64"]["dx"], c["r64"]["dp"]
+    assert np.all(dx[~obs] == 0) and np.any(dx[obs] != 0)
+    dead = LC.dead_rows(dims)
+    assert dead.size == dims[2] * dims[1] + dims[2] and np.all(dp[dead] == 0)
+    for n, a, b in LC.sub_blocks(dims):   # every sub-block is reached by the cotangents: none of the GPU's bounds is vacuous
+        assert np.any(dp[a:b] != 0), n
+
+
+def test_sub_blocks_tile_the_encoder_vector():
+    for dims in (LC.TINY, LC.PHYSIONET, (1, 1, 1, 1)):
+        I, H, L, N = dims
+        sb = LC.sub_blocks(dims)
+        assert sb[0][1] == 0 and all(a[2] == b[1] for a, b in zip(sb, sb[1:])) and sb[-1][2] == LC.param_count(dims) - (I * N + I)
+        sizes, pos = LN.block_sizes(*dims), 0
+        for blk in LC.BLOCKS[:4]:   # the sub-blocks of a block tile that block
+            mine = [s for s in sb if s[0].startswith(blk + ".")]
+            assert mine[0][1] == pos and mine[-1][2] == pos + sizes[blk]
+            pos += sizes[blk]
+        # the named ranges are what unflatten reads: mark new_state's first layer and look at (out, in)
+        flat = torch.zeros(LC.param_count(dims))
+        rng = {n: (a, b) for n, a, b in sb}
+        for v, n in enumerate(("new_state.l1_carry", "new_state.l1_x", "new_state.l1_b", "new_state.l2_W", "new_state.l2_b"), 1):
+            flat[rng[n][0]:rng[n][1]] = v
+        (W1, b1), (W2, b2) = LN.unflatten(flat, *dims)["new_state"]
+        assert torch.all(W1[:, :2 * L] == 1) and torch.all(W1[:, 2 * L:] == 2) and torch.all(b1 == 3)
+        assert torch.all(W2 == 4) and torch.all(b2 == 5)
+        marked = torch.zeros(LC.param_count(dims))
+        marked[torch.from_numpy(LC.dead_rows(dims))] = 1
+        (_, _), (W2, b2) = LN.unflatten(marked, *dims)["new_state"]
+        assert torch.all(W2[:L] == 1) and torch.all(W2[L:] == 0) and torch.all(b2[:L] == 1) and torch.all(b2[L:] == 0)
+        assert marked.sum() == L * H + L
+    assert LC.dx_rows(3) == [("dx.data", 0, 3), ("dx.mask", 3, 6), ("dx.dt", 6, 7)]
+
+
+def test_lds_bytes_and_the_largest_T():
+    """lat_smem_bytes / the encode gate of csrc/lrnde_latent.hpp restated: the header's "37/40/50/20 needs 143 KiB"; derived
+    here, run by tests/test_gpu_latent_envelope.py (the refusal prints the byte count)"""
+    assert LC.lat_smem_bytes(LC.PHYSIONET, True, 1) == 146048 + 8 * 2 + 16
+    assert LC.lat_smem_bytes(LC.PHYSIONET, True, 1) // 1024 == 142 and round(LC.lat_smem_bytes(LC.PHYSIONET, True, 1) / 1024) == 143
+    assert LC.lat_smem_bytes(LC.PHYSIONET, False, 1) < LC.lat_smem_bytes(LC.PHYSIONET, True, 1)
+    assert LC.t_fit(LC.TINY) == 4096
+    tf = LC.t_fit(LC.PHYSIONET)
+    assert tf == 2221 and tf < 4096
+    assert LC.lat_smem_bytes(LC.PHYSIONET, True, tf) <= 160 * 1024 < LC.lat_smem_bytes(LC.PHYSIONET, True, tf + 1)
+    for _, dims, _, T in LC.ENVELOPE:   # every envelope case is inside both limits
+        assert T <= LC.t_fit(dims)
+
+
+def test_end_to_end_yardstick_error_at_the_experiments_shape():
+    """RK4 with 200 steps against 400 at 37/40/50/20, B = 9, 4 saved times: within 1e-4 of every gradient block's norm, three
+    orders of magnitude inside the 3e-4 bar of tests/test_gpu_latent_envelope.py's end-to-end check"""
+    a, b = LC.e2e_physionet(200), LC.e2e_physionet(400)
+    dims = a["dims"]
+    ga, gb = LC.split_blocks(a["ref"]["dp"], dims), LC.split_blocks(b["ref"]["dp"], dims)
+    errs = {k: LC.rel(ga[k], gb[k]) for k in LC.BLOCKS}
+    errs["neural_ode"] = LC.rel(a["ref"]["dnode"], b["ref"]["dnode"])
+    print("RK4 200 vs 400 steps, relative to each block's norm:", {k: f"{v:.2e}" for k, v in errs.items()})
+    assert all(np.linalg.norm(gb[k]) > 0 for k in LC.BLOCKS)
+    assert max(errs.values()) <= 1e-4, errs
+    assert abs(a["ref"]["loss"] - b["ref"]["loss"]) <= 1e-4 * abs(b["ref"]["loss"])
