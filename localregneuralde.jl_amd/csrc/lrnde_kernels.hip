@@ -50,6 +50,7 @@
 #include "lrnde_math.hpp"
 #include "lrnde_stepctl.hpp"
 #include "lrnde_layer_plan.hpp"
+#include "lrnde_qsched.hpp"     // the compile-time issue schedule of the 4-column kernels' weight stream
 #include "lrnde_report.hpp"
 #include "lrnde_buf.hpp"
 #include "lrnde_comm.hpp"

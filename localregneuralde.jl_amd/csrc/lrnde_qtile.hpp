@@ -437,7 +437,8 @@ struct EpiFinalQL {
 // Streaming fast path (nseg1 <= QNW, RG1 <= 2, RG2 <= 2*QNW: one work item per GEMM phase per
 // wave — MNIST-ODE).  A wave's weights for one f-eval are ONE fixed stream of QSB blocks
 // (7 Dense-1 + 7 Dense-2) of 8 one-KiB buffer loads (4 k-quads x 2 row groups).  The blocks
-// rotate through a 3-slot register ring that always has two blocks in flight: the stream is
+// rotate through a 3-slot register ring that has two blocks in flight or, in the register form of
+// k_step_q, as many quads as its issue schedule finds dead registers for (QSchedEarly): the stream is
 // carried across the GEMM phases, across the barriers (raw s_barrier + lgkmcnt(0): a
 // __syncthreads() would drain vmcnt) and across f-evals (the next f-eval streams the same
 // addresses), so the L2 -> CU pipe does not idle at phase boundaries.  Everything is straight
@@ -460,9 +461,11 @@ constexpr int VRING = 3;             // ring of the VJP kernel's stream (lrnde_b
 // is parked, the kernels are instruction for instruction the ones without the switch.
 // Default: the last Dense-1 block (6) and the last full Dense-2 block (12), the blocks whose MFMAs the late wave of each
 // SIMD waits for before the two barriers (DESIGN.md 4.1 "parked weight blocks", profiles/qpark; 0x81u, the first block
-// of each phase, was measured slower with the first form of the fill).
+// of each phase, was measured slower with the first form of the fill).  Under the issue schedule (QSchedEarly) the blocks a
+// wave waits for first behind a barrier were measured as well: {9, 10} slower in every run, {9, 12} inside the default's
+// range (profiles/qsched/bench_ab.txt).
 #ifndef LRNDE_QPARK
-#define LRNDE_QPARK 0x1040u
+#define LRNDE_QPARK qsched::DEFAULT_PARK  // 0x1040u
 #endif
 constexpr unsigned QPARK = LRNDE_QPARK;
 __host__ __device__ constexpr int q_popcount(unsigned v) { int n = 0; for (; v; v &= v - 1) ++n; return n; }
@@ -488,12 +491,54 @@ static_assert(smem_bytes_q(7 * QSEG, QSEG, 2, 13) + q_park_bytes(QPARK) <= 160 *
 // kernels are the ones of the immediate-offset stream alone.  Default: block 5, just ahead of the LDS-parked last
 // Dense-1 block (DESIGN.md 4.1 "Register-parked block / immediate-offset stream", profiles/rpark).
 #ifndef LRNDE_QRPARK
-#define LRNDE_QRPARK 0x20u
+#define LRNDE_QRPARK qsched::DEFAULT_RPARK  // 0x20u
 #endif
 constexpr unsigned QRPARK = LRNDE_QRPARK;
 static_assert((QRPARK >> (QSB - 1)) == 0 && q_popcount(QRPARK) <= 1, "LRNDE_QRPARK names at most one of the stream blocks 0..QSB-2");
 static_assert((QRPARK & QPARK) == 0, "a block is parked in LDS (LRNDE_QPARK) or in registers (LRNDE_QRPARK), not both");
 __host__ __device__ constexpr bool q_parked(unsigned mask, int B) { return ((mask >> B) & 1u) != 0; }
+
+// The issue schedule of an f-eval: which quad of which block is requested at which of its 56 points, and the slot each
+// block's MFMAs read, as a compile-time table (lrnde_qsched.hpp).  QSchedLegacy<SLOT0> is the closed form every kernel of
+// the family had (block B + QAHEAD into slot (SLOT0 + B + QAHEAD) % QRING at block B) and all but one still have.
+// QSchedEarly<F> is f-eval F (0..5) of the register form of k_step_q: a quad is requested as soon as the registers that
+// receive it are dead, the parked blocks hold no slot of their own, and the last f-eval requests nothing for a seventh.
+// -DLRNDE_QSCHED=0 builds the closed form there too (so do the burst form and every ring size but three);
+// -DLRNDE_QLEAD=n reads an LDS-parked quad n points (1..4) ahead of its MFMAs, -DLRNDE_QWRAP=n lets n blocks of the
+// next f-eval be requested before the stage epilogue.
+#ifndef LRNDE_QSCHED
+#define LRNDE_QSCHED 1
+#endif
+#ifndef LRNDE_QLEAD
+#define LRNDE_QLEAD 2
+#endif
+// LRNDE_QCAP and LRNDE_QWRAP are what ONE compiler's register allocation leaves (253 of 256 VGPRs, profiles/qsched/
+// resource_usage.txt); tests/test_host_qstep_resources.py reads the built kernels' metadata and fails on a spill or a
+// private segment: re-derive the caps then, the late f-evals first.
+#ifndef LRNDE_QCAP   // busy slot quads allowed in each of the six f-evals (qsched::Params::cap)
+#define LRNDE_QCAP LRNDE_QSCHED_DEFAULT_CAP
+#endif
+#ifndef LRNDE_QWRAP  // blocks of the next f-eval requested across a stage epilogue (qsched::Params::wrap)
+#define LRNDE_QWRAP 2
+#endif
+static_assert(QSB == qsched::NB && QSQ == qsched::NQ && QRING <= qsched::MAXSLOT && qsched::NFEVAL == 6, "lrnde_qsched.hpp describes this stream");
+static_assert(LRNDE_QLEAD >= 1 && LRNDE_QLEAD <= QSQ, "LRNDE_QLEAD is a number of points, at most one block");
+#ifdef LRNDE_QBURST  // (the burst form takes its slots from the closed form's origin, qsched::Table::slot0)
+constexpr bool QEARLY = false;
+#else
+constexpr bool QEARLY = LRNDE_QSCHED != 0 && QRING == 3;
+#endif
+template <int SLOT0, int KT = 4, unsigned PARK = 0, unsigned RPARK = 0> struct QSchedLegacy {
+  static constexpr qsched::Table tab = qsched::legacy_table_at(qsched::Params{PARK, RPARK, KT, QRING, qsched::LEGACY, 0, 0, {}}, SLOT0);
+};
+template <int F, int KT, unsigned PARK, unsigned RPARK> struct QSchedEarly {
+  static constexpr qsched::Params par = qsched::Params{PARK, RPARK, KT, QRING, qsched::EARLY, LRNDE_QLEAD, LRNDE_QWRAP, LRNDE_QCAP};
+  static_assert(qsched::check_launch(par, qsched::EPI_INFLIGHT) == 0, "the issue schedule of these masks breaks an invariant (lrnde_qsched.hpp check_launch)");
+  static constexpr qsched::Table tab = qsched::launch_table(par, F);
+};
+// f-eval F of a step launch (stage F + 2)
+template <int F, int KT, unsigned PARK, unsigned RPARK>
+using QSchedStep = std::conditional_t<QEARLY, QSchedEarly<F, KT, PARK, RPARK>, QSchedLegacy<(QSB * F) % QRING, KT, PARK, RPARK>>;
 
 template <int I> struct IC { static constexpr int value = I; };
 template <int I0, int I1, class F> __device__ __forceinline__ void static_for(F&& f) {
@@ -622,15 +667,27 @@ __device__ __forceinline__ void stream_init_q(const ModelDev& m, StreamQ& st) {
   static_for<0, QAHEAD>([&](auto Bc) { constexpr int B = decltype(Bc)::value; q_stream_load<B, B>(st); });
 }
 
-// The loads of the block two ahead are issued two at a time between the quads' MFMAs (eight MFMAs per pair of loads),
+// The loads the schedule asks for are issued two at a time between the quads' MFMAs (eight MFMAs per pair of loads),
 // pinned by sched_barriers: as a burst of eight ahead of the block's 32 MFMAs a wave sat in the CU's address-issue
 // queue behind the other waves' bursts before it could start its MFMAs (56.5 -> 53.0 us per step).  -DLRNDE_QBURST
 // builds the burst form.
+// (what is requested at a point, in front of its MFMAs and behind them, is the schedule's: q_sched_issue)
+template <class SCH, int PT, bool POST, int KT, unsigned PARK, unsigned RPARK>
+__device__ __forceinline__ void q_sched_issue(StreamQ& st) {
+  constexpr int src = POST ? SCH::tab.post[PT].src : SCH::tab.pre[PT].src;
+  if constexpr (src != qsched::SRC_NONE) {
+    constexpr int B = (POST ? SCH::tab.post[PT].block : SCH::tab.pre[PT].block) % QSB;
+    constexpr int SLOT = POST ? SCH::tab.post[PT].slot : SCH::tab.pre[PT].slot;
+    constexpr int J = POST ? SCH::tab.post[PT].quad : SCH::tab.pre[PT].quad;
+    static_assert((src == qsched::SRC_LDS) == q_parked(PARK, B) && !q_parked(RPARK, B), "the schedule and q_stream_load_quad agree on the source");
+    q_stream_load_quad<B, SLOT, J, KT, PARK, RPARK>(st);
+  }
+}
 #ifndef LRNDE_QBURST
-#define LRNDE_QLOAD_QUAD(BB, SS, JJ) q_stream_load_quad<BB, SS, JJ, KT, PARK, RPARK>(st)
+#define LRNDE_QISSUE(PT, POST) q_sched_issue<SCH, PT, POST, KT, PARK, RPARK>(st)
 #define LRNDE_QPIN() __builtin_amdgcn_sched_barrier(0)
 #else
-#define LRNDE_QLOAD_QUAD(BB, SS, JJ) do {} while (0)
+#define LRNDE_QISSUE(PT, POST) do {} while (0)
 #define LRNDE_QPIN() do {} while (0)
 #endif
 // diagnostic ablation (-DLRNDE_QABL_NOMFMA): the MFMAs of feval_qs are replaced by an empty asm that keeps their
@@ -643,7 +700,8 @@ __device__ __forceinline__ f32x4 qmfma(float a, float b, f32x4 c) { return __bui
 // ep1 = epilogue 1's invariants where the caller made them once for all the f-evals of its launch (k_step_q's register
 // form); nullptr (a constant at every call): they are made here, behind the first barrier
 // RPARK: the MFMAs of the register-parked block take StreamQ::rpark where those of the others take their ring slot
-template <class Epi, int SLOT0, int KT = 4, unsigned PARK = 0, unsigned RPARK = 0>
+// SCH: the issue schedule (QSchedLegacy / QSchedEarly)
+template <class Epi, class SCH, int KT = 4, unsigned PARK = 0, unsigned RPARK = 0>
 __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, StreamQ& st, float ts, const Epi& epi,
                                          const Epi1Q* ep1 = nullptr) {
   const int lane = threadIdx.x & 63;
@@ -665,9 +723,9 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
     for (int j = 0; j < QSQ; ++j) bq[0][j] = xp[j * 4];
     static_for<0, QSB1>([&](auto Bc) {
       constexpr int B = decltype(Bc)::value;
-      constexpr int SL = (SLOT0 + B) % QRING, NSL = (SLOT0 + B + QAHEAD) % QRING;
+      constexpr int SL = q_parked(RPARK, B) ? 0 : SCH::tab.slot_of[B];
 #ifdef LRNDE_QBURST
-      q_stream_load<(B + QAHEAD) % QSB, NSL>(st);
+      q_stream_load<(B + QAHEAD) % QSB, (SCH::tab.slot0 + B + QAHEAD) % QRING>(st);  // (the burst form is LEGACY's)
 #endif
       if constexpr (B + 1 < QSB1) {
 #pragma unroll
@@ -677,7 +735,7 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
       const f32x4 (&w_)[QSQ][2] = q_parked(RPARK, B) ? st.rpark : st.ring[SL];
       static_for<0, QSQ>([&](auto Jc) {
         constexpr int j = decltype(Jc)::value;
-        LRNDE_QLOAD_QUAD((B + QAHEAD) % QSB, NSL, j);
+        LRNDE_QISSUE(B * QSQ + j, false);
         acc0 = qmfma(w_[j][0].x, b_[j].x, acc0);
         acc1 = qmfma(w_[j][1].x, b_[j].x, acc1);
         acc0 = qmfma(w_[j][0].y, b_[j].y, acc0);
@@ -686,6 +744,7 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
         acc1 = qmfma(w_[j][1].z, b_[j].z, acc1);
         acc0 = qmfma(w_[j][0].w, b_[j].w, acc0);
         acc1 = qmfma(w_[j][1].w, b_[j].w, acc1);
+        LRNDE_QISSUE(B * QSQ + j, true);
         LRNDE_QPIN();
       });
       __builtin_amdgcn_sched_barrier(0);
@@ -718,9 +777,9 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
     for (int j = 0; j < QSQ; ++j) bq[0][j] = hp[j * 4];
     static_for<0, QSB2>([&](auto Bc) {
       constexpr int B = decltype(Bc)::value;
-      constexpr int SL = (SLOT0 + QSB1 + B) % QRING, NSL = (SLOT0 + QSB1 + B + QAHEAD) % QRING;
+      constexpr int SL = q_parked(RPARK, QSB1 + B) ? 0 : SCH::tab.slot_of[QSB1 + B];
 #ifdef LRNDE_QBURST
-      q_stream_load<(QSB1 + B + QAHEAD) % QSB, NSL>(st);  // wraps into the next f-eval's Dense-1 blocks
+      q_stream_load<(QSB1 + B + QAHEAD) % QSB, (SCH::tab.slot0 + QSB1 + B + QAHEAD) % QRING>(st);  // wraps into the next f-eval's Dense-1 blocks
 #endif
       if constexpr (B == QSB2 - 3) {  // epilogue operands: issued ~3 blocks before they are needed
         if (g0 < m.D) epi.pre(IC<0>{}, g0, own0, pb0);
@@ -735,7 +794,7 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
       const f32x4 (&w_)[QSQ][2] = q_parked(RPARK, QSB1 + B) ? st.rpark : st.ring[SL];
       static_for<0, QSQ>([&](auto Jc) {
         constexpr int j = decltype(Jc)::value;
-        LRNDE_QLOAD_QUAD((QSB1 + B + QAHEAD) % QSB, NSL, j);
+        LRNDE_QISSUE((QSB1 + B) * QSQ + j, false);
         if constexpr (B < QSB2 - 1 || j < KT) {
           acc0 = qmfma(w_[j][0].x, b_[j].x, acc0);
           acc1 = qmfma(w_[j][1].x, b_[j].x, acc1);
@@ -746,6 +805,7 @@ __device__ __forceinline__ void feval_qs(const ModelDev& m, const SmemQ& sm, Str
           acc0 = qmfma(w_[j][0].w, b_[j].w, acc0);
           acc1 = qmfma(w_[j][1].w, b_[j].w, acc1);
         }
+        LRNDE_QISSUE((QSB1 + B) * QSQ + j, true);
         LRNDE_QPIN();
       });
       __builtin_amdgcn_sched_barrier(0);
@@ -808,7 +868,7 @@ __device__ __forceinline__ void q_feval_store(const ModelDev& m, const SmemQ& sm
                                               float* kout, int b0, int nvalid) {
   EpiStoreKQ e;
   e.m = &m; e.kout = kout; e.b0 = b0; e.nvalid = nvalid;
-  feval_qs<EpiStoreKQ, 0>(m, sm, fc, ts, e);
+  feval_qs<EpiStoreKQ, QSchedLegacy<0>>(m, sm, fc, ts, e);
   __syncthreads();  // full barrier: the k stores are read back through other lanes by the caller
 }
 
@@ -1238,14 +1298,14 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
       EpiStageQ<S> e;                                                                   \
       e.io = io; e.off_out = off_out; e.off_x = off_x;                                  \
       e.dt = dt; e.xl = s.xl; e.R = &R; e.store_k = bc.store_k;                         \
-      feval_qs<EpiStageQ<S>, (QSB * (S - 2)) % QRING, KT, QPARK, RPARK>(a.m, s, fc, (TS), e, ep1); \
+      feval_qs<EpiStageQ<S>, QSchedStep<S - 2, KT, QPARK, RPARK>, KT, QPARK, RPARK>(a.m, s, fc, (TS), e, ep1); \
     } else {                                                                            \
       EpiStageQL<S> e;                                                                  \
       e.io = io; e.off_up = o_up; e.off_k[0] = o_k1;                                    \
       _Pragma("unroll") for (int qq = 0; qq < 5; ++qq) e.off_k[1 + qq] = arr_off(a, 4 + qq); \
       e.off_out = off_out; e.off_x = off_x;                                             \
       e.dt = dt; e.xl = s.xl; e.kl = kl; e.KL = KL; e.klu = klu; e.klk = klk; e.store_k = bc.store_k; \
-      feval_qs<EpiStageQL<S>, (QSB * (S - 2)) % QRING, KT>(a.m, s, fc, (TS), e);        \
+      feval_qs<EpiStageQL<S>, QSchedLegacy<(QSB * (S - 2)) % QRING, KT>, KT>(a.m, s, fc, (TS), e); \
     }                                                                                   \
     STAMP(11 + S);                                                                      \
   } while (0)
@@ -1265,7 +1325,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
     ef.xl = s.xl; ef.R = &R;
     ef.rec = rec; ef.nstB = (int)(a.n_local * 4); ef.rsD = rsD;
-    feval_qs<EpiFinalQ, (QSB * 5) % QRING, KT, QPARK, RPARK>(a.m, s, fc, t + dt, ef, ep1);
+    feval_qs<EpiFinalQ, QSchedStep<5, KT, QPARK, RPARK>, KT, QPARK, RPARK>(a.m, s, fc, t + dt, ef, ep1);
   } else {
     EpiFinalQL ef;
     ef.io = io; ef.off_up = o_up; ef.off_u = o_un; ef.off_k[0] = o_k1;
@@ -1277,7 +1337,7 @@ template <bool SPEC, int KT> __global__ __launch_bounds__(QNT) void k_step_q(Ste
     ef.aerr = &aerr; ef.anum = &anum; ef.aden = &aden;
     ef.xl = s.xl; ef.kl = kl; ef.KL = KL; ef.klu = klu; ef.klk = klk;
     ef.rec = rec; ef.nstB = (int)(a.n_local * 4); ef.rsD = rsD;
-    feval_qs<EpiFinalQL, (QSB * 5) % QRING, KT>(a.m, s, fc, t + dt, ef);
+    feval_qs<EpiFinalQL, QSchedLegacy<(QSB * 5) % QRING, KT>, KT>(a.m, s, fc, t + dt, ef);
   }
   STAMP(18);
   block_sum3_q(s.red, aerr, anum, aden, a.want_stiff != 0);
