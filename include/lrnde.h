@@ -414,6 +414,23 @@ int lrnde_cifar_stem_backward(lrnde_conv* c, const float* x, int32_t B, const fl
 int lrnde_cifar_head_ce(lrnde_conv* c, const float* u, int32_t B, const float* ph, int32_t K, const int32_t* labels,
                         float* loss_host, float* logits, float* du, float* dph);
 
+/* ---- batch-sharded conv handle: rank r owns images [r*B, (r+1)*B) of a global batch of nranks*B (the
+ * same B on every rank), parameters and BatchNorm running statistics are replicated, and every rank calls the same
+ * lrnde_conv_* / lrnde_cifar_* entry point concurrently.  A sharded handle computes what one handle on the global batch
+ * computes: global batch statistics (training mode), global error norms and identical accept / reject decisions on
+ * every rank; lrnde_cifar_head_ce returns the global mean loss.  gp of lrnde_conv_vjp, dp of lrnde_conv_node_backward*,
+ * dps and dph come out summed over ranks and replicated; dy / dx / du stay sharded.  Every exchange is a stream-ordered
+ * SUM all-reduce of per-rank slots; all argument checks precede a call's first exchange and every data-dependent
+ * failure is decided from exchanged values, so no rank is left waiting.  Ranks called with different B all return
+ * LRNDE_BADARG from any call that exchanges something (the check rides in the call's first exchange; a call that couples
+ * nothing across ranks - a test-mode f-eval, a test-mode VJP without gp - exchanges nothing and is not checked).
+ * nranks == 1 builds no communicator unless LRNDE_FORCE_COMM is set; LRNDE_GATHER_TILES (both read when
+ * the communicator is made) exchanges the per-workgroup BatchNorm partials themselves, which reproduces the unsharded
+ * statistics bit for bit.  uid: the 128 bytes of lrnde_comm_unique_id.  lrnde_conv_destroy leaves the communicator. */
+int lrnde_conv_comm_init(lrnde_conv* c, const void* uid, int32_t rank, int32_t nranks);
+int lrnde_conv_comm_destroy(lrnde_conv* c);
+int lrnde_conv_comm_count(lrnde_conv* c, int32_t* nranks_host, int32_t* kind_host);      /* 0 none, 1 RCCL, 2 local */
+
 /* `_perform_step(integrator, cache::RKMilCommuteConstantCache, p)`, src/perform_step.jl:108-170, diagonal noise,
  * Ito interpretation: u = K + L*dW + Dgj*J with J = dW^2/2 - |dt|/2, EEst from the 4-argument
  * _calculate_residuals (:218-220); returns u, EEst and EEst*dt.  The reference's du2/En are dead code there

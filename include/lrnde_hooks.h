@@ -26,6 +26,11 @@ typedef struct lrnde_local_comm lrnde_local_comm;
 int lrnde_local_comm_create(lrnde_local_comm** out, int32_t nranks);
 int lrnde_local_comm_destroy(lrnde_local_comm* lc);
 int lrnde_comm_init_local(lrnde_ctx* ctx, lrnde_local_comm* lc, int32_t rank);
+/* the same for a conv handle (lrnde_conv_comm_init's in-process counterpart; lrnde_conv_comm_destroy or
+ * lrnde_conv_destroy leaves) */
+int lrnde_conv_comm_init_local(lrnde_conv* c, lrnde_local_comm* lc, int32_t rank);
+/* exchanges issued and bytes sent by this handle since creation (tests count them) */
+int lrnde_conv_comm_stats(lrnde_conv* c, uint64_t* exchanges_host, uint64_t* bytes_host);
 
 /* ---- timing hooks (bench.py) ---- */
 /* `reps` back-to-back launches of the full Tsit5 step kernel on fixed (uprev, k1, t, dt), timed

@@ -275,6 +275,15 @@ end
 comm_unique_id() = (id = zeros(UInt8, 128); ccall((:lrnde_comm_unique_id, lib), Cint, (Ptr{UInt8},), id) == 0 || error("unique id"); id)
 comm_init!(ctx, id::Vector{UInt8}, rank, nranks) = check(ctx, ccall((:lrnde_comm_init, lib), Cint,
     (Ptr{Cvoid}, Ptr{UInt8}, Cint, Cint), ctx, id, rank, nranks))
+# the conv field's handle: rank r owns images [r*B, (r+1)*B) of the global batch (the same B on every rank)
+conv_comm_init!(ctx, id::Vector{UInt8}, rank, nranks) = conv_check(ctx, ccall((:lrnde_conv_comm_init, lib), Cint,
+    (Ptr{Cvoid}, Ptr{UInt8}, Int32, Int32), ctx, id, rank, nranks))
+conv_comm_destroy!(ctx) = conv_check(ctx, ccall((:lrnde_conv_comm_destroy, lib), Cint, (Ptr{Cvoid},), ctx))
+function conv_comm_count(ctx)   # (ranks of the communicator the handle holds, kind: 0 none, 1 RCCL, 2 local)
+    n = Ref{Int32}(); kind = Ref{Int32}()
+    conv_check(ctx, ccall((:lrnde_conv_comm_count, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), ctx, n, kind))
+    return Int(n[]), Int(kind[])
+end
 
 # the same for the Milstein step (solver = RKMilCommute(), src/perform_step.jl:108-170): pullback of the fixed-grid solve and
 # d(EEst*dt)/dp of one local step

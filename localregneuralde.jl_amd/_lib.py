@@ -196,6 +196,11 @@ SYMBOLS = [
     ("lrnde_cifar_stem_backward", C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     ("lrnde_cifar_head_ce", C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _fp, _vp, _vp, _vp]),
     ("lrnde_conv_bench_rhs", C.c_int, [_vp, _vp, _f, _i32, _i32, _fp]),
+    ("lrnde_conv_comm_init", C.c_int, [_vp, _vp, _i32, _i32]),
+    ("lrnde_conv_comm_destroy", C.c_int, [_vp]),
+    ("lrnde_conv_comm_count", C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    ("lrnde_conv_comm_init_local", C.c_int, [_vp, _vp, _i32]),
+    ("lrnde_conv_comm_stats", C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("lrnde_bench_step", C.c_int, [_vp, _vp, _vp, _i32, _f, _f, _f, _f, _i32, _fp]),
     ("lrnde_set_overlap", C.c_int, [_vp, _i32]),
     ("lrnde_set_reports", C.c_int, [_vp, _i32]),

@@ -133,6 +133,19 @@ class ConvHandle:
         self._chk(L.lib.lrnde_conv_get_bn_state(self._ctx, C.c_void_p(out.data_ptr()), out.numel()))
         return out
 
+    def comm_count(self):
+        """(ranks of the communicator this handle holds, kind: 0 none, 1 RCCL, 2 the in-process local communicator);
+        join one with `sharding.init_comm` or `LocalComm.join`"""
+        n, kind = C.c_int32(), C.c_int32()
+        self._chk(L.lib.lrnde_conv_comm_count(self._ctx, C.byref(n), C.byref(kind)))
+        return int(n.value), int(kind.value)
+
+    def comm_stats(self):
+        """(exchanges issued, bytes sent) by this handle since creation"""
+        n, b = C.c_uint64(), C.c_uint64()
+        self._chk(L.lib.lrnde_conv_comm_stats(self._ctx, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
     def rhs(self, u, t):
         du = torch.empty_like(u)
         self._chk(L.lib.lrnde_conv_rhs(self._ctx, _ptr(u, "u"), float(t), self._B(u), _ptr(du, "du")))

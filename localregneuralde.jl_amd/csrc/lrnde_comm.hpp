@@ -7,7 +7,8 @@
 //     lrnde_comm_init_local.  It performs the same reduction with stream-ordered kernels and events, so that the
 //     nranks > 1 code of the library (offsets into the partial-sum vectors, receive buffers, the sharded adjoint's
 //     norm and parameter-cotangent sums) runs on a one-GPU box, where RCCL refuses two ranks on one device.
-// Included by lrnde_kernels.hip at file scope (before the anonymous-namespace host helpers).
+// Included by lrnde_kernels.hip and lrnde_conv.hip at file scope (before the anonymous-namespace host helpers); it does
+// not depend on the handle type.
 #pragma once
 
 #include <chrono>

@@ -46,6 +46,8 @@
 #include "lrnde_stepctl.hpp"
 #include "lrnde_layer_plan.hpp"
 #include "lrnde_conv_geom.hpp"
+#include <rccl/rccl.h>
+#include "lrnde_comm.hpp"
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
               "header_status returns lrnde_status values");
@@ -1237,6 +1239,101 @@ __global__ void k_bn_from_state(const float* mean_var, int ch, float eps, float*
   }
 }
 
+// ---- batch-sharded handle: a rank's share of a cross-sample sum ------------------
+// Every scalar exchange has one form: the rank reduces its own partials in a fixed order, writes the result into its
+// slot of a zero-padded nranks-slot vector, one SUM all-reduce follows (every element has exactly one non-zero term, so
+// the transport's summation order cannot matter), and the unchanged finalize kernel adds the slots in rank order.
+//
+// (S1, S2) per channel of the rank's part[ch][nwg][2], in k_bn_finalize_t's own order (thread-strided loads, then the
+// 256-wide tree) -> slot `rank` of out[ch][nranks][2]; k_bn_finalize_t then runs on `out` with nwg = nranks
+__global__ __launch_bounds__(256) void k_bn_rank_sums(const double* part, int nwg, int nranks, int rank, double* out) {
+  __shared__ double r1[256], r2[256];
+  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const f64x2* p = reinterpret_cast<const f64x2*>(part) + (size_t)c * nwg;
+  double s1 = 0.0, s2 = 0.0;
+  for (int w = tid; w < nwg; w += 256) { const f64x2 v = p[w]; s1 += v.x; s2 += v.y; }
+  r1[tid] = s1; r2[tid] = s2;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) { r1[tid] += r1[tid + o]; r2[tid] += r2[tid + o]; }
+    __syncthreads();
+  }
+  for (int r = tid; r < nranks; r += 256) {
+    double* q = out + ((size_t)c * nranks + r) * 2;
+    q[0] = r == rank ? r1[0] : 0.0; q[1] = r == rank ? r2[0] : 0.0;
+  }
+}
+// the same for partials laid out part[nblk][ch][2] (k_bn_bwd1, k_stem_raw, k_stem_bwd1), in the order of k_bn_finalize /
+// k_bn_bwd_finalize -> slot `rank` of out[nranks][ch][2]; those finalize kernels then run on `out` with nblk = nranks
+__global__ __launch_bounds__(256) void k_blk_rank_sums(const double* part, int nblk, int ch, int nranks, int rank, double* out) {
+  __shared__ double r1[256], r2[256];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  double s1 = 0.0, s2 = 0.0;
+  for (int w = tid; w < nblk; w += 256) { const double* p = part + ((size_t)w * ch + c) * 2; s1 += p[0]; s2 += p[1]; }
+  r1[tid] = s1; r2[tid] = s2;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) { r1[tid] += r1[tid + o]; r2[tid] += r2[tid + o]; }
+    __syncthreads();
+  }
+  for (int r = tid; r < nranks; r += 256) {
+    double* q = out + ((size_t)r * ch + c) * 2;
+    q[0] = r == rank ? r1[0] : 0.0; q[1] = r == rank ? r2[0] : 0.0;
+  }
+}
+// the same with the sequential order of k_stem_bwd_finalize (one thread per channel walks the blocks)
+__global__ void k_blk_rank_sums_seq(const double* part, int nblk, int ch, int nranks, int rank, double* out) {
+  const int c = threadIdx.x;
+  if (c >= ch) return;
+  double s1 = 0.0, s2 = 0.0;
+  for (int w = 0; w < nblk; ++w) { s1 += part[((size_t)w * ch + c) * 2]; s2 += part[((size_t)w * ch + c) * 2 + 1]; }
+  for (int r = 0; r < nranks; ++r) {
+    double* q = out + ((size_t)r * ch + c) * 2;
+    q[0] = r == rank ? s1 : 0.0; q[1] = r == rank ? s2 : 0.0;
+  }
+}
+// gather form (LRNDE_GATHER_TILES): the per-workgroup partials themselves in the global layout out[ch][nwg * nranks][2],
+// the rank's at columns [rank * nwg, (rank + 1) * nwg) and zeros elsewhere.  A workgroup is one (image, strip), so the
+// finalize over nwg * nranks columns adds what the unsharded run adds, in its order.
+__global__ void k_bn_gather_cols(const double* part, int nwg, int nranks, int rank, int ch, double* out) {
+  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  const size_t ng = (size_t)nwg * nranks, total = (size_t)ch * ng;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = i / ng, w = i % ng;
+    f64x2 v = {0.0, 0.0};
+    if (w / nwg == (size_t)rank) v = reinterpret_cast<const f64x2*>(part)[c * nwg + (w - (size_t)rank * nwg)];
+    reinterpret_cast<f64x2*>(out)[i] = v;
+  }
+}
+// `nblk` block triples of k_sums_init / k_sums_err -> one triple, added in the order the host loop of fetch_sums adds
+// them (so one rank gives the unsharded bits) -> slot `rank` of out[nranks][3]
+__global__ void k_sums_rank(const double* part, int nblk, int nranks, int rank, double* out) {
+  const int j = threadIdx.x;
+  if (j >= 3) return;
+  double s = 0.0;
+  for (int i = 0; i < nblk; ++i) s += part[3 * i + j];
+  for (int r = 0; r < nranks; ++r) out[3 * r + j] = r == rank ? s : 0.0;
+}
+// (B, B^2) of the call in slot `rank` of tail[nranks][2]: rides behind the first exchange of every entry-point call
+__global__ void k_batch_slot(double* tail, int nranks, int rank, int B) {
+  for (int r = threadIdx.x; r < nranks; r += blockDim.x) {
+    tail[2 * r] = r == rank ? (double)B : 0.0;
+    tail[2 * r + 1] = r == rank ? (double)B * (double)B : 0.0;
+  }
+}
+// head of the sharded loss exchange: (sum of the rank's per-sample losses in sample order, its bad-label flag) -> slot
+__global__ void k_loss_slot(const float* loss_b, int B, int nranks, int rank, double* out) {
+  if (threadIdx.x != 0) return;
+  double s = 0.0;
+  for (int b = 0; b < B; ++b) s += (double)loss_b[b];
+  const int32_t bad = reinterpret_cast<const int32_t*>(loss_b)[B];
+  for (int r = 0; r < nranks; ++r) { out[2 * r] = r == rank ? s : 0.0; out[2 * r + 1] = r == rank ? (bad ? 1.0 : 0.0) : 0.0; }
+}
+__global__ void k_scale(float* v, float s, size_t n) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) v[i] = v[i] * s;
+}
+
 // ---- backward of BatchNorm(ch, act): dz = dh * act'(z) in place, per-block partial sums of dz and dz*xn ----
 struct BnBwdArgs {
   float* g; const float* a; size_t npix;  // g: (npix, 64) cotangent in/out; a: raw forward activation
@@ -1708,6 +1805,14 @@ struct lrnde_conv {
   DevBuf<float> rec_u1;
   LayerRecord rec;   // arguments and generation of the recorded forward; rec.ts: sol.t of the last solve, recorded or not
   DevBuf<float> adj;
+  // batch-sharded handle: rank r owns images [r*B, (r+1)*B) of a global batch of nranks*B
+  ncclComm_t comm = nullptr;           // RCCL communicator (one process per GPU)
+  lrnde_local_comm* lcomm = nullptr;   // in-process local communicator (lrnde_hooks.h), not owned
+  int rank = 0, nranks = 1;
+  bool gather = false;                 // LRNDE_GATHER_TILES at comm-init time: exchange the per-workgroup partials themselves
+  DevBuf<double> xv;                   // the exchange vector (slots; in place)
+  int curB = 0; bool bcheck = false;   // this call's batch; its first exchange still has to carry (B, B^2)
+  uint64_t xchg_n = 0, xchg_bytes = 0; // exchanges issued / bytes sent since creation (lrnde_conv_comm_stats)
 };
 
 namespace {
@@ -1735,6 +1840,77 @@ inline int strip_rows(const lrnde_conv* c) {
 }
 inline int cinp_of(int cin) { return cin == 8 ? 12 : cin; }  // 64-channel tiles are swizzled, not padded
 
+// ---- batch-sharded handle: the exchange layer -----------------------------------
+inline bool sharded(const lrnde_conv* c) { return c->comm != nullptr || c->lcomm != nullptr; }
+// the one collective of the conv path: SUM all-reduce of `count` doubles / floats on the handle's stream (send may equal
+// recv).  The only caller of ncclAllReduce / lc_allreduce in this file, and what lrnde_conv_comm_stats counts.
+int conv_allreduce(lrnde_conv* c, const void* send, void* recv, size_t count, bool is_double) {
+  if (c->comm) {
+    const ncclResult_t r = ncclAllReduce(send, recv, count, is_double ? ncclDouble : ncclFloat, ncclSum, c->comm, c->stream);
+    if (r != ncclSuccess) return cfail(c, LRNDE_NCCL_ERROR, "ncclAllReduce failed: %s", ncclGetErrorString(r));
+  } else if (c->lcomm) {
+    const int rc = lc_allreduce(c->lcomm, c->rank, c->stream, send, recv, count, is_double);
+    if (rc) return cfail(c, rc, "local communicator all-reduce failed (rank %d of %d): %s", c->rank, c->nranks,
+                         rc == LRNDE_NCCL_ERROR ? "a peer did not arrive (timeout) or the communicator is broken" : "HIP error");
+  } else {
+    return LRNDE_OK;
+  }
+  ++c->xchg_n;
+  c->xchg_bytes += count * (is_double ? sizeof(double) : sizeof(float));
+  return LRNDE_OK;
+}
+// room for `count` doubles and the (B, B^2) tail in the exchange vector
+int ensure_xv(lrnde_conv* c, size_t count) {
+  CHK(c, c->xv.grow(count + 2 * (size_t)c->nranks));
+  return LRNDE_OK;
+}
+// every rank was called with one B?  Read from the exchanged tail, so all ranks return alike and none is left waiting.
+int batch_verify(lrnde_conv* c, const double* tail) {
+  const int R = c->nranks;
+  c->bcheck = false;
+  CHK(c, hipMemcpyAsync(c->sums_host, tail, sizeof(double) * 2 * R, hipMemcpyDeviceToHost, c->stream));
+  CHK(c, hipStreamSynchronize(c->stream));
+  bool same = true;
+  for (int r = 0; r < R; ++r) {
+    const double b = c->sums_host[2 * r];
+    same = same && b == c->sums_host[0] && c->sums_host[2 * r + 1] == b * b;
+  }
+  if (same) return LRNDE_OK;
+  std::string s;
+  for (int r = 0; r < R; ++r) s += (r ? ", " : "") + std::to_string((long long)c->sums_host[2 * r]);
+  return cfail(c, LRNDE_BADARG, "the ranks of a sharded handle must be called with one batch size; got B = [%s]", s.c_str());
+}
+// the batch check as an exchange of its own: before a float all-reduce that opens a call, and in the gather form, whose
+// counts depend on B
+int batch_check(lrnde_conv* c) {
+  if (!c->bcheck) return LRNDE_OK;
+  int rc;
+  if ((rc = ensure_xv(c, 0))) return rc;
+  double* tail = c->xv + (c->xv.size() - 2 * (size_t)c->nranks);  // behind any payload already packed (ensure_xv)
+  hipLaunchKernelGGL(k_batch_slot, dim3(1), dim3(64), 0, c->stream, tail, c->nranks, c->rank, c->curB);
+  if ((rc = conv_allreduce(c, tail, tail, 2 * (size_t)c->nranks, true))) return rc;
+  return batch_verify(c, tail);
+}
+// in-place exchange of the `count` doubles at the head of the exchange vector; the first exchange of an entry-point call
+// also carries (B, B^2) per slot behind them
+int exchange(lrnde_conv* c, size_t count) {
+  int rc;
+  if (c->bcheck && c->gather && (rc = batch_check(c))) return rc;
+  const bool ride = c->bcheck;
+  double* v = c->xv;
+  if (ride) hipLaunchKernelGGL(k_batch_slot, dim3(1), dim3(64), 0, c->stream, v + count, c->nranks, c->rank, c->curB);
+  if ((rc = conv_allreduce(c, v, v, count + (ride ? 2 * (size_t)c->nranks : 0), true))) return rc;
+  return ride ? batch_verify(c, v + count) : LRNDE_OK;
+}
+// all-reduce of a per-rank float block (a weight-gradient block, the head's dph, the stem's dps), in place
+int allreduce_block(lrnde_conv* c, float* v, size_t count) {
+  int rc;
+  if ((rc = batch_check(c))) return rc;
+  return conv_allreduce(c, v, v, count, false);
+}
+// cross-sample sums are over the global batch
+inline double nranks_of(const lrnde_conv* c) { return sharded(c) ? (double)c->nranks : 1.0; }
+
 int ensure_ws(lrnde_conv* c, int B) {
   if (B == c->wsB) return LRNDE_OK;
   c->wsB = 0;
@@ -1755,7 +1931,11 @@ int check_ready(lrnde_conv* c, int B) {
   if (B <= 0) return cfail(c, LRNDE_BADARG, "batch must be positive");
   if (!c->have_params) return cfail(c, LRNDE_BADARG, "lrnde_conv_set_params has not been called");
   CHK(c, hipSetDevice(c->device));
-  return ensure_ws(c, B);
+  c->curB = B; c->bcheck = sharded(c);
+  const int rc = ensure_ws(c, B);
+  if (rc || !sharded(c)) return rc;
+  // the largest exchange of the field: [ch][nranks][2] sums, or the gather form's [ch][nwg * nranks][2] (grow-only)
+  return ensure_xv(c, (size_t)c->d.hidden * 2 * c->nranks * (c->gather ? (size_t)c->nwg : 1));
 }
 
 ConvArgs base_args(const lrnde_conv* c, int B) {
@@ -1835,10 +2015,24 @@ int launch_rhs_ex(lrnde_conv* c, const float* u, float t, int B, float* du, bool
   else launch_mt(c, 0, a, std::max(sizeof(float) * rows * WP * a.CINP, stg_bytes));
   CHK(c, hipGetLastError());
   float* rs = (train && last) ? c->bn_state : nullptr;  // the VJP's recompute does not advance the running statistics
-  auto finalize = [&](float* mean, float* inv, float* rm, float* rv) {
-    hipLaunchKernelGGL(k_bn_finalize_t, dim3(Hc), dim3(256), 0, c->stream, c->part, c->nwg, count, c->d.bn_eps, mean, inv, rm, rv, 0.1f);
+  auto finalize = [&](float* mean, float* inv, float* rm, float* rv) -> int {
+    if (!sharded(c)) {
+      hipLaunchKernelGGL(k_bn_finalize_t, dim3(Hc), dim3(256), 0, c->stream, c->part, c->nwg, count, c->d.bn_eps, mean, inv, rm, rv, 0.1f);
+      return LRNDE_OK;
+    }
+    // global batch statistics: the rank's sums (or, gather form, its partial columns) in its slot, one exchange, and the
+    // same finalize over the slots with the global pixel count
+    const int R = c->nranks;
+    const int cols = c->gather ? c->nwg * R : R;
+    if (c->gather) hipLaunchKernelGGL(k_bn_gather_cols, dim3(64), dim3(256), 0, c->stream, (const double*)c->part, c->nwg, R, c->rank, Hc, c->xv.get());
+    else hipLaunchKernelGGL(k_bn_rank_sums, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->part, c->nwg, R, c->rank, c->xv.get());
+    const int rx = exchange(c, (size_t)Hc * cols * 2);
+    if (rx) return rx;
+    hipLaunchKernelGGL(k_bn_finalize_t, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->xv, cols, count * R, c->d.bn_eps, mean, inv, rm, rv, 0.1f);
+    return LRNDE_OK;
   };
-  if (train) finalize(c->stat, c->stat + Hc, rs, rs ? rs + Hc : nullptr);
+  int rcf;
+  if (train && (rcf = finalize(c->stat, c->stat + Hc, rs, rs ? rs + Hc : nullptr))) return rcf;
   // conv2: BN1+act(y1) -> y2
   a.CIN = Hc; a.CINP = cinp_of(Hc); a.in = c->y1; a.out = c->y2; a.wpk = f32_of_bf ? c->w2f : c->w2; a.tsum = c->ts2; a.wpk2 = nullptr;
   if (c->split) { a.wpk = c->w2h; a.wpk2 = c->w2l; }
@@ -1846,7 +2040,7 @@ int launch_rhs_ex(lrnde_conv* c, const float* u, float t, int B, float* du, bool
   const size_t esz = bf ? 2 : 4;
   launch_mt(c, 1, a, bf ? TSL_BYTES + esz * rows * WP * a.CINP : std::max(esz * rows * WP * a.CINP, stg_bytes));
   CHK(c, hipGetLastError());
-  if (train) finalize(c->stat + 2 * Hc, c->stat + 3 * Hc, rs ? rs + 2 * Hc : nullptr, rs ? rs + 3 * Hc : nullptr);
+  if (train && (rcf = finalize(c->stat + 2 * Hc, c->stat + 3 * Hc, rs ? rs + 2 * Hc : nullptr, rs ? rs + 3 * Hc : nullptr))) return rcf;
   if (!last) return LRNDE_OK;
   // conv3: BN2+act(y2) -> du (planar)
   a.COUT = C; a.in = c->y2; a.out = du; a.wpk = f32_of_bf ? c->w3f : c->w3; a.tsum = c->ts3; a.part = nullptr; a.wpk2 = nullptr;
@@ -1922,7 +2116,15 @@ int launch_vjp(lrnde_conv* c, const float* y, float t, const float* lam, int B, 
     b.scale = c->bn + 2 * layer * Hc; b.bias = c->bn + (2 * layer + 1) * Hc; b.act = c->d.act; b.part = c->part_bw;
     hipLaunchKernelGGL(k_bn_bwd1, dim3(NBW1), dim3(256), 0, c->stream, b);
     const size_t og = layer == 0 ? o_g1 : o_g2;
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->part_bw, NBW1, count, train,
+    const double* pb = c->part_bw; int nblk = NBW1; double cnt = count;
+    if (sharded(c) && (train || gp)) {  // global m1 / m2, and dscale / dbias summed over ranks (test mode without gp needs neither)
+      const int R = c->nranks;
+      hipLaunchKernelGGL(k_blk_rank_sums, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->part_bw, NBW1, Hc, R, c->rank, c->xv.get());
+      const int rx = exchange(c, (size_t)R * Hc * 2);
+      if (rx) return rx;
+      pb = c->xv; nblk = R; cnt = count * R;
+    }
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3(Hc), dim3(256), 0, c->stream, pb, nblk, cnt, train,
                        c->bwm + 2 * layer * Hc, c->bwm + (2 * layer + 1) * Hc, gp ? gp + og : nullptr, gp ? gp + og + Hc : nullptr);
     CHK(c, hipGetLastError());
     return LRNDE_OK;
@@ -1956,6 +2158,8 @@ int launch_vjp(lrnde_conv* c, const float* y, float t, const float* lam, int B, 
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((9 * GC * IC + 63) / 64), dim3(256), 0, c->stream, (const float*)c->pw, nwgw, GC, IC, CINr, COUTr, gw);
     hipLaunchKernelGGL(k_wgrad_reduce_t, dim3(GC), dim3(256), 0, c->stream, (const float*)c->pt, nwgw, GC, CINr, COUTr, t, gw);
     CHK(c, hipGetLastError());
+    // a weight block is per-rank: all-reduced exactly once (the BatchNorm blocks leave their finalize already summed)
+    if (sharded(c)) return allreduce_block(c, gw, (size_t)9 * (CINr + 1) * COUTr);
     return LRNDE_OK;
   };
   // conv3^T: lam (planar) -> g2 = d h2
@@ -1999,7 +2203,22 @@ int lincomb(lrnde_conv* c, float* out, const float* base, float dt, int nk, cons
   return LRNDE_OK;
 }
 
+// what a norm runs over: the sums kernels add `local` elements on this rank, the mean divides by `global`
+struct NormSpan { size_t local; double global; };
+inline NormSpan state_span(const lrnde_conv* c, size_t n) { return NormSpan{n, (double)n * nranks_of(c)}; }
+
 int fetch_sums(lrnde_conv* c, double* s3) {
+  if (sharded(c)) {  // the rank's triple in its slot, one exchange, the slots added in rank order: no rank decides from a local number
+    const int R = c->nranks;
+    int rc;
+    hipLaunchKernelGGL(k_sums_rank, dim3(1), dim3(64), 0, c->stream, (const double*)c->sums, NSUMB, R, c->rank, c->xv.get());
+    if ((rc = exchange(c, 3 * (size_t)R))) return rc;
+    CHK(c, hipMemcpyAsync(c->sums_host, c->xv, sizeof(double) * 3 * R, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    s3[0] = s3[1] = s3[2] = 0.0;
+    for (int r = 0; r < R; ++r) { s3[0] += c->sums_host[3 * r]; s3[1] += c->sums_host[3 * r + 1]; s3[2] += c->sums_host[3 * r + 2]; }
+    return LRNDE_OK;
+  }
   CHK(c, hipMemcpyAsync(c->sums_host, c->sums, sizeof(double) * NSUMB * 3, hipMemcpyDeviceToHost, c->stream));
   CHK(c, hipStreamSynchronize(c->stream));
   s3[0] = s3[1] = s3[2] = 0.0;
@@ -2009,34 +2228,34 @@ int fetch_sums(lrnde_conv* c, double* s3) {
 
 // ode_determine_initdt (OrdinaryDiffEq, un-vendored): f0 -> k1 (= fsalfirst)
 template <class RHS>
-int init_dt_g(lrnde_conv* c, size_t n, RHS&& rhs, const float* u0, float t0, float tend, float abstol, float reltol, float* f0,
+int init_dt_g(lrnde_conv* c, size_t n, NormSpan sp, RHS&& rhs, const float* u0, float t0, float tend, float abstol, float reltol, float* f0,
               float* tmp, float* f1, float* dt_out) {
   const float dtmax = tend - t0;
   int rc;
   double s[3];
   if ((rc = rhs(u0, t0, f0))) return rc;
-  hipLaunchKernelGGL(k_sums_init, dim3(NSUMB), dim3(256), 0, c->stream, u0, f0, (const float*)nullptr, abstol, reltol, n, c->sums);
+  hipLaunchKernelGGL(k_sums_init, dim3(NSUMB), dim3(256), 0, c->stream, u0, f0, (const float*)nullptr, abstol, reltol, sp.local, c->sums);
   if ((rc = fetch_sums(c, s))) return rc;
-  const float d0 = (float)sqrt(s[0] / (double)n), d1 = (float)sqrt(s[1] / (double)n);
+  const float d0 = (float)sqrt(s[0] / sp.global), d1 = (float)sqrt(s[1] / sp.global);
   const float dt0 = initdt_dt0(d0, d1, dtmax);
   const float* kk[1] = {f0};
   if ((rc = lincomb(c, tmp, u0, 0.f, 1, kk, &dt0, n))) return rc;
   if ((rc = rhs(tmp, t0 + dt0, f1))) return rc;
-  hipLaunchKernelGGL(k_sums_init, dim3(NSUMB), dim3(256), 0, c->stream, u0, f0, (const float*)f1, abstol, reltol, n, c->sums);
+  hipLaunchKernelGGL(k_sums_init, dim3(NSUMB), dim3(256), 0, c->stream, u0, f0, (const float*)f1, abstol, reltol, sp.local, c->sums);
   if ((rc = fetch_sums(c, s))) return rc;
-  *dt_out = initdt_tail(dt0, d1, (float)sqrt(s[2] / (double)n), 5.0f, dtmax);
+  *dt_out = initdt_tail(dt0, d1, (float)sqrt(s[2] / sp.global), 5.0f, dtmax);
   return LRNDE_OK;
 }
 
 int init_dt(lrnde_conv* c, const float* u0, int B, float t0, float tend, float abstol, float reltol, float* f0,
             float* tmp, float* f1, float* dt_out) {
   auto rhs = [&](const float* x, float tt, float* k) { return launch_rhs(c, x, tt, B, k); };
-  return init_dt_g(c, state_n(c, B), rhs, u0, t0, tend, abstol, reltol, f0, tmp, f1, dt_out);
+  return init_dt_g(c, state_n(c, B), state_span(c, state_n(c, B)), rhs, u0, t0, tend, abstol, reltol, f0, tmp, f1, dt_out);
 }
 
 // one Tsit5 step (src/perform_step.jl:3-32) on vectors of length n: ks = k2..k6 (5 vectors), g6, tmp work vectors
 template <class RHS>
-int tsit5_step_g(lrnde_conv* c, size_t n, RHS&& rhs, const float* uprev, const float* k1, float t, float dt, float abstol,
+int tsit5_step_g(lrnde_conv* c, size_t n, NormSpan sp, RHS&& rhs, const float* uprev, const float* k1, float t, float dt, float abstol,
                  float reltol, float* u, float* k7, float* ks, float* g6, float* tmp, double* sums3) {
   const Tsit5F tb = tsit5_f32();
   const float *A = tb.A, *cs = tb.cs;
@@ -2052,8 +2271,10 @@ int tsit5_step_g(lrnde_conv* c, size_t n, RHS&& rhs, const float* uprev, const f
   }
   ErrArgs e{};
   e.uprev = uprev; e.u = u; for (int j = 0; j < 7; ++j) e.k[j] = K[j];
-  e.g6 = g6; e.dt = dt; e.abstol = abstol; e.reltol = reltol; e.n = n; e.part = c->sums;
-  bool v4 = n % 4 == 0 && ((uintptr_t)uprev % 16) == 0 && ((uintptr_t)u % 16) == 0 && ((uintptr_t)g6 % 16) == 0;
+  e.g6 = g6; e.dt = dt; e.abstol = abstol; e.reltol = reltol; e.n = sp.local; e.part = c->sums;
+  // sp.local <= n elements are summed from the FRONT of the vectors (the sharded adjoint: lambda sits before mu in Z, and
+  // ranks > 0 stop at n_lambda); the 16-byte path is chosen from n and the pointers, so it needs sp.local % 4 == 0 too
+  bool v4 = n % 4 == 0 && sp.local % 4 == 0 && ((uintptr_t)uprev % 16) == 0 && ((uintptr_t)u % 16) == 0 && ((uintptr_t)g6 % 16) == 0;
   for (int j = 0; j < 7; ++j) v4 = v4 && ((uintptr_t)K[j] % 16) == 0;
   e.vec4 = v4 ? 1 : 0;
   hipLaunchKernelGGL(k_sums_err, dim3(NSUMB), dim3(256), 0, c->stream, e);
@@ -2063,17 +2284,17 @@ int tsit5_step_g(lrnde_conv* c, size_t n, RHS&& rhs, const float* uprev, const f
 int tsit5_step(lrnde_conv* c, const float* uprev, const float* k1, int B, float t, float dt, float abstol, float reltol,
                float* u, float* k7, float* ks, float* g6, float* tmp, double* sums3) {
   auto rhs = [&](const float* x, float tt, float* k) { return launch_rhs(c, x, tt, B, k); };
-  return tsit5_step_g(c, state_n(c, B), rhs, uprev, k1, t, dt, abstol, reltol, u, k7, ks, g6, tmp, sums3);
+  return tsit5_step_g(c, state_n(c, B), state_span(c, state_n(c, B)), rhs, uprev, k1, t, dt, abstol, reltol, u, k7, ks, g6, tmp, sums3);
 }
 
-void reg_values(const double* s, size_t n, float dt, float* eest, float* re, float* rs) {
-  const float ee = (float)sqrt(s[0] / (double)n);
+void reg_values(const double* s, double n, float dt, float* eest, float* re, float* rs) {
+  const float ee = (float)sqrt(s[0] / n);
   if (eest) *eest = ee;
   if (re) *re = ee * dt;
   if (rs) {
-    const float den = (float)sqrt(s[2] / (double)n);
+    const float den = (float)sqrt(s[2] / n);
     if (den == 0.0f) *rs = 0.0f;
-    else { const float num = (float)sqrt(s[1] / (double)n); *rs = fabsf(num / (den + 1.1920929e-7f)) / 3.5068f; }
+    else { const float num = (float)sqrt(s[1] / n); *rs = fabsf(num / (den + 1.1920929e-7f)) / 3.5068f; }
   }
 }
 
@@ -2135,7 +2356,88 @@ int lrnde_conv_destroy(lrnde_conv* c) {
   if (!c) return LRNDE_OK;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream); else hipDeviceSynchronize();
+  if (c->comm) ncclCommDestroy(c->comm);  // leaves its communicator (a local one is owned by its creator)
   delete c;
+  return LRNDE_OK;
+}
+
+// ---- batch-sharded handle: joining and leaving a communicator ----
+// (the stream is drained first: an exchange still queued on it must not outlive its communicator)
+static int conv_comm_leave(lrnde_conv* c) {
+  if (c->comm || c->lcomm) {
+    if (c->stream) CHK(c, hipStreamSynchronize(c->stream)); else CHK(c, hipDeviceSynchronize());
+  }
+  if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
+  c->lcomm = nullptr;
+  c->rank = 0; c->nranks = 1; c->gather = false; c->bcheck = false;
+  return LRNDE_OK;
+}
+static bool env_on(const char* name) { const char* v = getenv(name); return v && *v && strcmp(v, "0") != 0; }
+
+int lrnde_conv_comm_init(lrnde_conv* c, const void* uid, int32_t rank, int32_t nranks) {
+  if (!c) return LRNDE_BADARG;
+  if (!uid || nranks < 1 || nranks > NSUMB || rank < 0 || rank >= nranks)
+    return cfail(c, LRNDE_BADARG, "bad communicator arguments (rank %d of %d; at most %d ranks)", rank, nranks, NSUMB);
+  CHK(c, hipSetDevice(c->device));
+  { const int rl = conv_comm_leave(c); if (rl) return rl; }
+  if (nranks > 1 || env_on("LRNDE_FORCE_COMM")) {
+    ncclUniqueId id;
+    memcpy(&id, uid, sizeof(id));
+    const ncclResult_t r = ncclCommInitRank(&c->comm, nranks, id, rank);
+    if (r != ncclSuccess) { c->comm = nullptr; return cfail(c, LRNDE_NCCL_ERROR, "ncclCommInitRank failed: %s", ncclGetErrorString(r)); }
+    c->rank = rank; c->nranks = nranks;
+    c->gather = env_on("LRNDE_GATHER_TILES");
+  }
+  return LRNDE_OK;
+}
+
+int lrnde_conv_comm_destroy(lrnde_conv* c) {
+  if (!c) return LRNDE_BADARG;
+  CHK(c, hipSetDevice(c->device));
+  return conv_comm_leave(c);
+}
+
+int lrnde_conv_comm_count(lrnde_conv* c, int32_t* nranks_host, int32_t* kind_host) {
+  if (!c || !nranks_host) return LRNDE_BADARG;
+  int n = 1, kind = 0;
+  if (c->comm) {
+    const ncclResult_t r = ncclCommCount(c->comm, &n);
+    if (r != ncclSuccess) return cfail(c, LRNDE_NCCL_ERROR, "ncclCommCount failed: %s", ncclGetErrorString(r));
+    kind = 1;
+  } else if (c->lcomm) { n = c->lcomm->n; kind = 2; }
+  *nranks_host = n;
+  if (kind_host) *kind_host = kind;  // 0 none, 1 RCCL, 2 in-process local communicator
+  return LRNDE_OK;
+}
+
+int lrnde_conv_comm_init_local(lrnde_conv* c, lrnde_local_comm* lc, int32_t rank) {
+  if (!c) return LRNDE_BADARG;
+  if (!lc || rank < 0 || rank >= lc->n) return cfail(c, LRNDE_BADARG, "bad local communicator arguments (rank %d)", rank);
+  CHK(c, hipSetDevice(c->device));
+  if (c->lcomm == lc) return cfail(c, LRNDE_BADARG, "the handle has already joined this local communicator (rank %d)", c->rank);
+  { const int rl = conv_comm_leave(c); if (rl) return rl; }   // whatever other communicator the handle held before
+  {
+    std::lock_guard<std::mutex> lk(lc->mu);
+    if (lc->joined[rank]) return cfail(c, LRNDE_BADARG, "rank %d has already joined this local communicator", rank);
+    // one device only: the sum kernel reads the peers' send buffers directly, and no peer access is set up between devices
+    for (int r = 0; r < lc->n; ++r)
+      if (lc->joined[r] && lc->device[r] != c->device)
+        return cfail(c, LRNDE_UNSUPPORTED, "the in-process local communicator is single-device (rank %d is on device %d, rank %d on %d); "
+                     "use lrnde_conv_comm_init (RCCL) across devices", r, lc->device[r], rank, c->device);
+    CHK(c, hipEventCreateWithFlags(&lc->ready[rank], hipEventDisableTiming));
+    CHK(c, hipEventCreateWithFlags(&lc->done[rank], hipEventDisableTiming));
+    lc->device[rank] = c->device;
+    lc->joined[rank] = true;
+  }
+  c->lcomm = lc; c->rank = rank; c->nranks = lc->n;
+  c->gather = env_on("LRNDE_GATHER_TILES");
+  return LRNDE_OK;
+}
+
+int lrnde_conv_comm_stats(lrnde_conv* c, uint64_t* exchanges_host, uint64_t* bytes_host) {
+  if (!c) return LRNDE_BADARG;
+  if (exchanges_host) *exchanges_host = c->xchg_n;
+  if (bytes_host) *bytes_host = c->xchg_bytes;
   return LRNDE_OK;
 }
 
@@ -2257,7 +2559,7 @@ int lrnde_conv_perform_step(lrnde_conv* c, const float* uprev, const float* k1, 
   float* uo = u ? u : V; float* k7o = k7 ? k7 : V + n;
   double s[3];
   if ((rc = tsit5_step(c, uprev, k1, B, t, dt, abstol, reltol, uo, k7o, V + 2 * n, V + 7 * n, V + 8 * n, s))) return rc;
-  reg_values(s, n, dt, eest_host, reg_error_host, reg_stiff_host);
+  reg_values(s, state_span(c, n).global, dt, eest_host, reg_error_host, reg_stiff_host);
   return LRNDE_OK;
 }
 
@@ -2301,7 +2603,7 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
     int r2;
     if ((r2 = tsit5_step(c, uprev, k1, B, t, dt, abstol, reltol, u, k7, ks, g6, tmp, s))) return r2;
     st->nf += 6;
-    const float eest = (float)sqrt(s[0] / (double)n);
+    const float eest = (float)sqrt(s[0] / state_span(c, n).global);
     st->eest_last = eest;
     const float tprev = t;
     const bool accept = attempt_judge(L, eest);
@@ -2415,7 +2717,7 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
   if ((rc = init_dt(c, u1, B, t1, t2, oo.abstol, oo.reltol, V + 2 * n, V + 10 * n, V + 9 * n, &dtl))) return rc;
   double s[3];
   if ((rc = tsit5_step(c, u1, V + 2 * n, B, t1, dtl, oo.abstol, oo.reltol, V + n, V + 8 * n, V + 3 * n, V + 9 * n, V + 10 * n, s))) return rc;
-  reg_values(s, n, dtl, &ee, &re, &rs);
+  reg_values(s, state_span(c, n).global, dtl, &ee, &re, &rs);
   CHK(c, hipMemcpyAsync(c->bn_state, V, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream));
   CHK(c, hipStreamSynchronize(c->stream));
   *reg_val = (reg_type == LRNDE_REG_STIFFNESS_ESTIMATE) ? rs : re;
@@ -2460,7 +2762,8 @@ int step_reg_grad(lrnde_conv* c, const float* uprev, const float* k1, int B, flo
   double sm[3];
   if ((rc = tsit5_step(c, uprev, k1, B, t, dt, abstol, reltol, u, k7, ks, g6, tmp, sm))) return rc;
   float ee, re, rs;
-  reg_values(sm, n, dt, &ee, &re, &rs);
+  const double ng = state_span(c, n).global;  // the seed's eest / num / den and its norm are the global ones
+  reg_values(sm, ng, dt, &ee, &re, &rs);
   if (reg_val_host) *reg_val_host = (reg_type == LRNDE_REG_STIFFNESS_ESTIMATE) ? rs : re;
   const float* kk[7] = {k1, ks, ks + n, ks + 2 * n, ks + 3 * n, ks + 4 * n, k7};
   float* A0 = c->adj;
@@ -2469,12 +2772,12 @@ int step_reg_grad(lrnde_conv* c, const float* uprev, const float* k1, int B, flo
   CHK(c, hipMemsetAsync(A0, 0, sizeof(float) * 8 * n, c->stream));
   CHK(c, hipMemsetAsync(gp, 0, sizeof(float) * P, c->stream));
   RegSeedArgs sa{};
-  sa.n = n; sa.n_norm = n; sa.uprev = uprev; sa.u = u; sa.g6 = g6;
+  sa.n = n; sa.n_norm = (size_t)ng; sa.uprev = uprev; sa.u = u; sa.g6 = g6;
   for (int j = 0; j < 7; ++j) sa.k[j] = kk[j];
   sa.kb[0] = nullptr;
   for (int j = 1; j < 7; ++j) sa.kb[j] = kb[j];
   sa.ub = ub; sa.g6b = g6b; sa.dt = dt; sa.abstol = abstol; sa.reltol = reltol; sa.reg_type = reg_type;
-  sa.eest = ee; sa.num = (float)sqrt(sm[1] / (double)n); sa.den = (float)sqrt(sm[2] / (double)n);
+  sa.eest = ee; sa.num = (float)sqrt(sm[1] / ng); sa.den = (float)sqrt(sm[2] / ng);
   { int nb = (int)((n + 255) / 256); if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(k_reg_seed, dim3(nb), dim3(256), 0, c->stream, sa); CHK(c, hipGetLastError()); }
   const Tsit5F tb = tsit5_f32();
@@ -2506,14 +2809,14 @@ int step_reg_grad(lrnde_conv* c, const float* uprev, const float* k1, int B, flo
 
 // adaptive Tsit5 on z = [lambda; mu] in reversed time (InterpolatingAdjoint restatement): s from s0 to s1 with tstops
 template <class RHS>
-int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float s1, const lrnde_solve_opts* o,
+int adjoint_solve(lrnde_conv* c, size_t N, NormSpan sp, RHS&& rhs, float* Z, float s0, float s1, const lrnde_solve_opts* o,
                   const std::vector<float>& tstops, lrnde_stats* st) {
   const float abstol = o->abstol, reltol = o->reltol;
   memset(st, 0, sizeof(*st));
   float *z = Z, *zn = Z + N, *k1 = Z + 2 * N, *ks = Z + 3 * N, *k7 = Z + 8 * N, *g6 = Z + 9 * N, *tmp = Z + 10 * N;
   int rc;
   float dt0;
-  if ((rc = init_dt_g(c, N, rhs, z, s0, s1, abstol, reltol, k1, tmp, g6, &dt0))) return rc;
+  if ((rc = init_dt_g(c, N, sp, rhs, z, s0, s1, abstol, reltol, k1, tmp, g6, &dt0))) return rc;
   st->nf = 3; st->dt_init = dt0;
   AttemptLoop L = attempt_begin(pi_tsit5(), o->exact_pow, o->maxiters, 1, s0, s1, dt0);  // (reversed time: magnitude snap)
   const float &t = L.t, &dt = L.dt;
@@ -2525,9 +2828,9 @@ int adjoint_solve(lrnde_conv* c, size_t N, RHS&& rhs, float* Z, float s0, float 
     double sm[3];
     int r2;
     // g6 doubles as the stage-6 state; its stiffness sums are not used here
-    if ((r2 = tsit5_step_g(c, N, rhs, z, k1, t, dt, abstol, reltol, zn, k7, ks, g6, tmp, sm))) return r2;
+    if ((r2 = tsit5_step_g(c, N, sp, rhs, z, k1, t, dt, abstol, reltol, zn, k7, ks, g6, tmp, sm))) return r2;
     st->nf += 6;
-    const float eest = (float)sqrt(sm[0] / (double)N);
+    const float eest = (float)sqrt(sm[0] / sp.global);
     st->eest_last = eest;
     const bool accept = attempt_judge(L, eest);
     if (L.status) break;  // a NaN estimate
@@ -2631,7 +2934,11 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
     if ((r = lincomb(c, ybuf, d, dds[lo], 7, K7, bw, n))) return r;
     return launch_vjp(c, ybuf, t, zs, B, K, K + n);
   };
-  rc = adjoint_solve(c, N, rhs, Z, -t2, -t0, o, stops, st_bwd);
+  // sharded: lambda is this rank's block, mu is replicated (launch_vjp returns gp summed over ranks, so every rank
+  // integrates the same mu).  The error norm runs over [lambda of all ranks; mu once]: rank 0 adds mu's terms to its
+  // lambda sums, the other ranks add lambda's only, and the mean divides by n_global + P.
+  const NormSpan sp = sharded(c) ? NormSpan{c->rank == 0 ? N : n, (double)n * c->nranks + (double)P} : NormSpan{N, (double)N};
+  rc = adjoint_solve(c, N, sp, rhs, Z, -t2, -t0, o, stops, st_bwd);
   if (rc) return cfail(c, rc, "adjoint solve stopped with retcode %d", rc);
   CHK(c, hipMemcpyAsync(dx, Z, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
   CHK(c, hipMemcpyAsync(dp, Z + n, sizeof(float) * P, hipMemcpyDeviceToDevice, c->stream));
@@ -2874,11 +3181,23 @@ __global__ void k_stem_state_copy(const float* st, float* out) {  // running [me
   const int i = threadIdx.x;
   if (i < 16) out[i] = st ? st[i] : (i < 8 ? 0.f : 1.f);
 }
+// entry of a stem / head call on a sharded handle: this call's batch, and room for its exchanges
+static int begin_layer_call(lrnde_conv* c, int B, size_t count) {
+  c->curB = B; c->bcheck = sharded(c);
+  return sharded(c) ? ensure_xv(c, count) : LRNDE_OK;
+}
 static int stem_common(lrnde_conv* c, const float* x, int B, const float* ps, const float* bn_state, float* a0, float* mi /* mean[8] inv[8] */,
                        double* part, int nblk, float* run = nullptr /* running statistics to advance (already holding bn_state) */) {
   const int H = c->d.height, W = c->d.width;
   hipLaunchKernelGGL(k_stem_raw, dim3(nblk), dim3(SH_T), 0, c->stream, x, ps, B, H, W, a0, part);
-  if (c->d.bn_train) hipLaunchKernelGGL(k_bn_finalize, dim3(8), dim3(256), 0, c->stream, (const double*)part, nblk, 8, (double)B * H * W, c->d.bn_eps, mi, mi + 8,
+  if (c->d.bn_train && sharded(c)) {  // BatchNorm(8) over the global batch: rank sums in k_bn_finalize's order, slot, exchange
+    const int R = c->nranks;
+    hipLaunchKernelGGL(k_blk_rank_sums, dim3(8), dim3(256), 0, c->stream, (const double*)part, nblk, 8, R, c->rank, c->xv.get());
+    const int rx = exchange(c, (size_t)R * 16);
+    if (rx) return rx;
+    hipLaunchKernelGGL(k_bn_finalize, dim3(8), dim3(256), 0, c->stream, (const double*)c->xv, R, 8, (double)B * H * W * R, c->d.bn_eps, mi, mi + 8,
+                       run, run ? run + 8 : (float*)nullptr, 0.1f);
+  } else if (c->d.bn_train) hipLaunchKernelGGL(k_bn_finalize, dim3(8), dim3(256), 0, c->stream, (const double*)part, nblk, 8, (double)B * H * W, c->d.bn_eps, mi, mi + 8,
                                         run, run ? run + 8 : (float*)nullptr, 0.1f);
   else hipLaunchKernelGGL(k_stem_state, dim3(1), dim3(64), 0, c->stream, bn_state, c->d.bn_eps, mi, mi + 8);
   CHK(c, hipGetLastError());
@@ -2893,6 +3212,7 @@ int lrnde_cifar_stem_forward(lrnde_conv* c, const float* x, int32_t B, const flo
   const int nblk = (int)(((long)B * plane + SH_T - 1) / SH_T);
   DevBuf<float> a0, mi; DevBuf<double> part;
   CHK(c, a0.once(total)); CHK(c, mi.once(16)); CHK(c, part.once(nblk * 16));
+  { const int rb = begin_layer_call(c, B, 16 * (size_t)c->nranks); if (rb) return rb; }
   if (bn_state_out) hipLaunchKernelGGL(k_stem_state_copy, dim3(1), dim3(64), 0, c->stream, bn_state, bn_state_out);
   int rc = stem_common(c, x, B, ps, bn_state, a0, mi, part, nblk, bn_state_out);
   if (!rc) {
@@ -2911,13 +3231,22 @@ int lrnde_cifar_stem_backward(lrnde_conv* c, const float* x, int32_t B, const fl
   DevBuf<float> a0, mi, mm, partw; DevBuf<double> part;
   CHK(c, a0.once(total)); CHK(c, mi.once(16)); CHK(c, mm.once(16));
   CHK(c, part.once(nblk * 16)); CHK(c, partw.once((size_t)nblk * 140));
-  int rc = stem_common(c, x, B, ps, bn_state, a0, mi, part, nblk);
+  int rc = begin_layer_call(c, B, 16 * (size_t)c->nranks);
+  if (!rc) rc = stem_common(c, x, B, ps, bn_state, a0, mi, part, nblk);
   if (!rc) {
     hipLaunchKernelGGL(k_stem_bwd1, dim3(nblk), dim3(SH_T), 0, c->stream, (const float*)a0, du0, (const float*)mi, (const float*)(mi + 8), B, plane, part);
-    hipLaunchKernelGGL(k_stem_bwd_finalize, dim3(1), dim3(64), 0, c->stream, (const double*)part, nblk, (double)B * plane, c->d.bn_train ? 1 : 0, mm, mm + 8, dps);
+    if (sharded(c)) {  // global m1 / m2; d scale, d bias summed over ranks by the finalize
+      const int R = c->nranks;
+      hipLaunchKernelGGL(k_blk_rank_sums_seq, dim3(1), dim3(64), 0, c->stream, (const double*)part, nblk, 8, R, c->rank, c->xv.get());
+      if ((rc = exchange(c, (size_t)R * 16))) return rc;
+      hipLaunchKernelGGL(k_stem_bwd_finalize, dim3(1), dim3(64), 0, c->stream, (const double*)c->xv, R, (double)B * plane * R, c->d.bn_train ? 1 : 0, mm, mm + 8, dps);
+    } else {
+      hipLaunchKernelGGL(k_stem_bwd_finalize, dim3(1), dim3(64), 0, c->stream, (const double*)part, nblk, (double)B * plane, c->d.bn_train ? 1 : 0, mm, mm + 8, dps);
+    }
     hipLaunchKernelGGL(k_stem_bwd2, dim3(nblk), dim3(SH_T), 0, c->stream, x, (const float*)a0, du0, (const float*)mi, (const float*)(mi + 8), ps,
                        (const float*)mm, (const float*)(mm + 8), B, H, W, partw);
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const float*)partw, nblk, 140, dps);
+    if (sharded(c) && (rc = allreduce_block(c, dps, 140))) return rc;  // conv weights and bias: per-rank sums, all-reduced once
     if (hipStreamSynchronize(c->stream) != hipSuccess) rc = cfail(c, LRNDE_HIP_ERROR, "stem backward kernels failed");
   }
   return rc;
@@ -2938,12 +3267,35 @@ int lrnde_cifar_head_ce(lrnde_conv* c, const float* u, int32_t B, const float* p
   int32_t* bad = reinterpret_cast<int32_t*>(lb + B);
   CHK(c, hipMemsetAsync(bad, 0, sizeof(int32_t), c->stream));
   hipLaunchKernelGGL(k_cls_fwd, dim3((B + 3) / 4), dim3(256), 0, c->stream, (const float*)v, pd, labels, B, D, K, logits, dl, lb, bad);
+  double loss_sum = 0.0;
+  if (sharded(c)) {
+    // the global mean loss: the rank's loss sum and its bad-label flag travel in one exchange, so a label outside [0, K)
+    // on one rank fails the call on every rank, before the dph all-reduce
+    const int R = c->nranks;
+    int rc;
+    if ((rc = begin_layer_call(c, B, 2 * (size_t)R))) return rc;
+    hipLaunchKernelGGL(k_loss_slot, dim3(1), dim3(64), 0, c->stream, (const float*)lb, B, R, c->rank, c->xv.get());
+    if ((rc = exchange(c, 2 * (size_t)R))) return rc;
+    CHK(c, hipMemcpyAsync(c->sums_host, c->xv, sizeof(double) * 2 * R, hipMemcpyDeviceToHost, c->stream));
+    CHK(c, hipStreamSynchronize(c->stream));
+    double flags = 0.0;
+    for (int r = 0; r < R; ++r) { loss_sum += c->sums_host[2 * r]; flags += c->sums_host[2 * r + 1]; }
+    if (flags != 0.0) return cfail(c, LRNDE_BADARG, "a label is outside [0, %d)", K);
+    // k_cls_fwd normalised dl by 1/B: the global normaliser is 1/(B nranks), and du, dph follow from dl
+    if (du || dph) hipLaunchKernelGGL(k_scale, dim3(64), dim3(256), 0, c->stream, dl.get(), 1.0f / (float)R, (size_t)B * K);
+  }
   if (du || dph) {
     hipLaunchKernelGGL(k_cls_bwd_x, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, (const float*)dl, pd, B, D, K, dv);
     if (dph) hipLaunchKernelGGL(k_cls_bwd_w, dim3((K * (D + 1) + 255) / 256), dim3(256), 0, c->stream, (const float*)dl, (const float*)v, B, D, K, dph + 73);
     hipLaunchKernelGGL(k_head_dz, dim3(1024), dim3(256), 0, c->stream, (const float*)z, dv, npx);
     hipLaunchKernelGGL(k_head_bwd, dim3(nblk), dim3(SH_T), 0, c->stream, u, (const float*)dv, ph, B, H, W, du, dph ? partw : (float*)nullptr);
     if (dph) hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const float*)partw, nblk, 73, dph);
+    if (dph && sharded(c)) { const int rc = allreduce_block(c, dph, (size_t)73 + (size_t)K * (D + 1)); if (rc) return rc; }
+  }
+  if (sharded(c)) {
+    CHK(c, hipStreamSynchronize(c->stream));
+    *loss_host = (float)(loss_sum / ((double)B * c->nranks));
+    return LRNDE_OK;
   }
   std::vector<float> hl((size_t)B + 1);
   hipError_t e = hipMemcpyAsync(hl.data(), lb, sizeof(float) * ((size_t)B + 1), hipMemcpyDeviceToHost, c->stream);

@@ -17,9 +17,15 @@ def shard_columns(x, rank, nranks):
     return x[rank * per:(rank + 1) * per]
 
 
+def _is_conv(handle):
+    from .conv import ConvHandle
+    return isinstance(handle, ConvHandle)
+
+
 def init_comm(handle, rank, nranks, group=None):
     """Creates the library's RCCL communicator: rank 0 makes the unique id, torch.distributed
-    (any backend) broadcasts its 128 bytes."""
+    (any backend) broadcasts its 128 bytes.  `handle` is an MLP `Handle` or a `ConvHandle` (the batch-sharded conv
+    field: lrnde_conv_comm_init)."""
     import torch.distributed as dist
     buf = (C.c_uint8 * 128)()
     if rank == 0:
@@ -35,7 +41,8 @@ def init_comm(handle, rank, nranks, group=None):
         t = t.cpu()
     raw = bytes(t.tolist())
     buf2 = (C.c_uint8 * 128).from_buffer_copy(raw)
-    handle._chk(L.lib.lrnde_comm_init(handle._ctx, buf2, int(rank), int(nranks)))
+    init = L.lib.lrnde_conv_comm_init if _is_conv(handle) else L.lib.lrnde_comm_init
+    handle._chk(init(handle._ctx, buf2, int(rank), int(nranks)))
 
 
 class LocalComm:
@@ -53,14 +60,15 @@ class LocalComm:
         self._handles = []
 
     def join(self, handle, rank):
-        handle._chk(L.lib.lrnde_comm_init_local(handle._ctx, self._lc, int(rank)))
+        join = L.lib.lrnde_conv_comm_init_local if _is_conv(handle) else L.lib.lrnde_comm_init_local
+        handle._chk(join(handle._ctx, self._lc, int(rank)))
         self._handles.append(handle)
 
     def close(self):
         if getattr(self, "_lc", None):
             for h in self._handles:
                 if getattr(h, "_ctx", None):
-                    L.lib.lrnde_comm_destroy(h._ctx)
+                    (L.lib.lrnde_conv_comm_destroy if _is_conv(h) else L.lib.lrnde_comm_destroy)(h._ctx)
             L.lib.lrnde_local_comm_destroy(self._lc)
             self._lc = None
 
