@@ -32,7 +32,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,7 +45,6 @@
 #include "lrnde_stepctl.hpp"
 #include "lrnde_layer_plan.hpp"
 #include "lrnde_conv_geom.hpp"
-#include <rccl/rccl.h>
 #include "lrnde_comm.hpp"
 static_assert((int)lrnde::STEP_OK == (int)LRNDE_OK && (int)lrnde::STEP_MAXITERS == (int)LRNDE_MAXITERS &&
               (int)lrnde::STEP_DT_LESS_THAN_MIN == (int)LRNDE_DT_LESS_THAN_MIN && (int)lrnde::STEP_DT_NAN == (int)LRNDE_DT_NAN,
@@ -1806,32 +1804,17 @@ struct lrnde_conv {
   LayerRecord rec;   // arguments and generation of the recorded forward; rec.ts: sol.t of the last solve, recorded or not
   DevBuf<float> adj;
   // batch-sharded handle: rank r owns images [r*B, (r+1)*B) of a global batch of nranks*B
-  ncclComm_t comm = nullptr;           // RCCL communicator (one process per GPU)
-  lrnde_local_comm* lcomm = nullptr;   // in-process local communicator (lrnde_hooks.h), not owned
-  int rank = 0, nranks = 1;
+  lrnde::Membership mem;               // its communicator, rank and exchange counters (lrnde_comm.hpp; lrnde_conv_comm_stats)
   bool gather = false;                 // LRNDE_GATHER_TILES at comm-init time: exchange the per-workgroup partials themselves
   DevBuf<double> xv;                   // the exchange vector (slots; in place)
   int curB = 0; bool bcheck = false;   // this call's batch; its first exchange still has to carry (B, B^2)
-  uint64_t xchg_n = 0, xchg_bytes = 0; // exchanges issued / bytes sent since creation (lrnde_conv_comm_stats)
 };
 
 namespace {
 
-int cfail(lrnde_conv* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  return code;
-}
-#define CHK(c, x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return cfail(c, LRNDE_HIP_ERROR, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+// this handle's names for the library's formatter and HIP check (lrnde_fail.hpp)
+constexpr auto cfail = &lrnde::failf<lrnde_conv>;
+#define CHK(c, x) LRNDE_HIPCHK(c, x)
 
 inline size_t state_n(const lrnde_conv* c, int B) { return (size_t)B * c->d.width * c->d.height * c->d.channels; }
 inline int strip_rows(const lrnde_conv* c) {
@@ -1841,32 +1824,19 @@ inline int strip_rows(const lrnde_conv* c) {
 inline int cinp_of(int cin) { return cin == 8 ? 12 : cin; }  // 64-channel tiles are swizzled, not padded
 
 // ---- batch-sharded handle: the exchange layer -----------------------------------
-inline bool sharded(const lrnde_conv* c) { return c->comm != nullptr || c->lcomm != nullptr; }
-// the one collective of the conv path: SUM all-reduce of `count` doubles / floats on the handle's stream (send may equal
-// recv).  The only caller of ncclAllReduce / lc_allreduce in this file, and what lrnde_conv_comm_stats counts.
-int conv_allreduce(lrnde_conv* c, const void* send, void* recv, size_t count, bool is_double) {
-  if (c->comm) {
-    const ncclResult_t r = ncclAllReduce(send, recv, count, is_double ? ncclDouble : ncclFloat, ncclSum, c->comm, c->stream);
-    if (r != ncclSuccess) return cfail(c, LRNDE_NCCL_ERROR, "ncclAllReduce failed: %s", ncclGetErrorString(r));
-  } else if (c->lcomm) {
-    const int rc = lc_allreduce(c->lcomm, c->rank, c->stream, send, recv, count, is_double);
-    if (rc) return cfail(c, rc, "local communicator all-reduce failed (rank %d of %d): %s", c->rank, c->nranks,
-                         rc == LRNDE_NCCL_ERROR ? "a peer did not arrive (timeout) or the communicator is broken" : "HIP error");
-  } else {
-    return LRNDE_OK;
-  }
-  ++c->xchg_n;
-  c->xchg_bytes += count * (is_double ? sizeof(double) : sizeof(float));
-  return LRNDE_OK;
+inline bool sharded(const lrnde_conv* c) { return c->mem.sharded(); }
+// the one collective of the conv path: SUM all-reduce of `count` doubles / floats on the handle's stream (send may equal recv)
+inline int conv_allreduce(lrnde_conv* c, const void* send, void* recv, size_t count, bool is_double) {
+  return c->mem.allreduce(c->stream, send, recv, count, is_double, &c->err);
 }
 // room for `count` doubles and the (B, B^2) tail in the exchange vector
 int ensure_xv(lrnde_conv* c, size_t count) {
-  CHK(c, c->xv.grow(count + 2 * (size_t)c->nranks));
+  CHK(c, c->xv.grow(count + 2 * (size_t)c->mem.nranks));
   return LRNDE_OK;
 }
 // every rank was called with one B?  Read from the exchanged tail, so all ranks return alike and none is left waiting.
 int batch_verify(lrnde_conv* c, const double* tail) {
-  const int R = c->nranks;
+  const int R = c->mem.nranks;
   c->bcheck = false;
   CHK(c, hipMemcpyAsync(c->sums_host, tail, sizeof(double) * 2 * R, hipMemcpyDeviceToHost, c->stream));
   CHK(c, hipStreamSynchronize(c->stream));
@@ -1886,9 +1856,9 @@ int batch_check(lrnde_conv* c) {
   if (!c->bcheck) return LRNDE_OK;
   int rc;
   if ((rc = ensure_xv(c, 0))) return rc;
-  double* tail = c->xv + (c->xv.size() - 2 * (size_t)c->nranks);  // behind any payload already packed (ensure_xv)
-  hipLaunchKernelGGL(k_batch_slot, dim3(1), dim3(64), 0, c->stream, tail, c->nranks, c->rank, c->curB);
-  if ((rc = conv_allreduce(c, tail, tail, 2 * (size_t)c->nranks, true))) return rc;
+  double* tail = c->xv + (c->xv.size() - 2 * (size_t)c->mem.nranks);  // behind any payload already packed (ensure_xv)
+  hipLaunchKernelGGL(k_batch_slot, dim3(1), dim3(64), 0, c->stream, tail, c->mem.nranks, c->mem.rank, c->curB);
+  if ((rc = conv_allreduce(c, tail, tail, 2 * (size_t)c->mem.nranks, true))) return rc;
   return batch_verify(c, tail);
 }
 // in-place exchange of the `count` doubles at the head of the exchange vector; the first exchange of an entry-point call
@@ -1898,8 +1868,8 @@ int exchange(lrnde_conv* c, size_t count) {
   if (c->bcheck && c->gather && (rc = batch_check(c))) return rc;
   const bool ride = c->bcheck;
   double* v = c->xv;
-  if (ride) hipLaunchKernelGGL(k_batch_slot, dim3(1), dim3(64), 0, c->stream, v + count, c->nranks, c->rank, c->curB);
-  if ((rc = conv_allreduce(c, v, v, count + (ride ? 2 * (size_t)c->nranks : 0), true))) return rc;
+  if (ride) hipLaunchKernelGGL(k_batch_slot, dim3(1), dim3(64), 0, c->stream, v + count, c->mem.nranks, c->mem.rank, c->curB);
+  if ((rc = conv_allreduce(c, v, v, count + (ride ? 2 * (size_t)c->mem.nranks : 0), true))) return rc;
   return ride ? batch_verify(c, v + count) : LRNDE_OK;
 }
 // all-reduce of a per-rank float block (a weight-gradient block, the head's dph, the stem's dps), in place
@@ -1909,7 +1879,7 @@ int allreduce_block(lrnde_conv* c, float* v, size_t count) {
   return conv_allreduce(c, v, v, count, false);
 }
 // cross-sample sums are over the global batch
-inline double nranks_of(const lrnde_conv* c) { return sharded(c) ? (double)c->nranks : 1.0; }
+inline double nranks_of(const lrnde_conv* c) { return sharded(c) ? (double)c->mem.nranks : 1.0; }
 
 int ensure_ws(lrnde_conv* c, int B) {
   if (B == c->wsB) return LRNDE_OK;
@@ -1935,7 +1905,7 @@ int check_ready(lrnde_conv* c, int B) {
   const int rc = ensure_ws(c, B);
   if (rc || !sharded(c)) return rc;
   // the largest exchange of the field: [ch][nranks][2] sums, or the gather form's [ch][nwg * nranks][2] (grow-only)
-  return ensure_xv(c, (size_t)c->d.hidden * 2 * c->nranks * (c->gather ? (size_t)c->nwg : 1));
+  return ensure_xv(c, (size_t)c->d.hidden * 2 * c->mem.nranks * (c->gather ? (size_t)c->nwg : 1));
 }
 
 ConvArgs base_args(const lrnde_conv* c, int B) {
@@ -2022,10 +1992,10 @@ int launch_rhs_ex(lrnde_conv* c, const float* u, float t, int B, float* du, bool
     }
     // global batch statistics: the rank's sums (or, gather form, its partial columns) in its slot, one exchange, and the
     // same finalize over the slots with the global pixel count
-    const int R = c->nranks;
+    const int R = c->mem.nranks;
     const int cols = c->gather ? c->nwg * R : R;
-    if (c->gather) hipLaunchKernelGGL(k_bn_gather_cols, dim3(64), dim3(256), 0, c->stream, (const double*)c->part, c->nwg, R, c->rank, Hc, c->xv.get());
-    else hipLaunchKernelGGL(k_bn_rank_sums, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->part, c->nwg, R, c->rank, c->xv.get());
+    if (c->gather) hipLaunchKernelGGL(k_bn_gather_cols, dim3(64), dim3(256), 0, c->stream, (const double*)c->part, c->nwg, R, c->mem.rank, Hc, c->xv.get());
+    else hipLaunchKernelGGL(k_bn_rank_sums, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->part, c->nwg, R, c->mem.rank, c->xv.get());
     const int rx = exchange(c, (size_t)Hc * cols * 2);
     if (rx) return rx;
     hipLaunchKernelGGL(k_bn_finalize_t, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->xv, cols, count * R, c->d.bn_eps, mean, inv, rm, rv, 0.1f);
@@ -2118,8 +2088,8 @@ int launch_vjp(lrnde_conv* c, const float* y, float t, const float* lam, int B, 
     const size_t og = layer == 0 ? o_g1 : o_g2;
     const double* pb = c->part_bw; int nblk = NBW1; double cnt = count;
     if (sharded(c) && (train || gp)) {  // global m1 / m2, and dscale / dbias summed over ranks (test mode without gp needs neither)
-      const int R = c->nranks;
-      hipLaunchKernelGGL(k_blk_rank_sums, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->part_bw, NBW1, Hc, R, c->rank, c->xv.get());
+      const int R = c->mem.nranks;
+      hipLaunchKernelGGL(k_blk_rank_sums, dim3(Hc), dim3(256), 0, c->stream, (const double*)c->part_bw, NBW1, Hc, R, c->mem.rank, c->xv.get());
       const int rx = exchange(c, (size_t)R * Hc * 2);
       if (rx) return rx;
       pb = c->xv; nblk = R; cnt = count * R;
@@ -2209,9 +2179,9 @@ inline NormSpan state_span(const lrnde_conv* c, size_t n) { return NormSpan{n, (
 
 int fetch_sums(lrnde_conv* c, double* s3) {
   if (sharded(c)) {  // the rank's triple in its slot, one exchange, the slots added in rank order: no rank decides from a local number
-    const int R = c->nranks;
+    const int R = c->mem.nranks;
     int rc;
-    hipLaunchKernelGGL(k_sums_rank, dim3(1), dim3(64), 0, c->stream, (const double*)c->sums, NSUMB, R, c->rank, c->xv.get());
+    hipLaunchKernelGGL(k_sums_rank, dim3(1), dim3(64), 0, c->stream, (const double*)c->sums, NSUMB, R, c->mem.rank, c->xv.get());
     if ((rc = exchange(c, 3 * (size_t)R))) return rc;
     CHK(c, hipMemcpyAsync(c->sums_host, c->xv, sizeof(double) * 3 * R, hipMemcpyDeviceToHost, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
@@ -2356,88 +2326,50 @@ int lrnde_conv_destroy(lrnde_conv* c) {
   if (!c) return LRNDE_OK;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream); else hipDeviceSynchronize();
-  if (c->comm) ncclCommDestroy(c->comm);  // leaves its communicator (a local one is owned by its creator)
+  (void)c->mem.leave(c->stream, &c->err);  // leaves its communicator (a local one is owned by its creator)
   delete c;
   return LRNDE_OK;
 }
 
-// ---- batch-sharded handle: joining and leaving a communicator ----
-// (the stream is drained first: an exchange still queued on it must not outlive its communicator)
-static int conv_comm_leave(lrnde_conv* c) {
-  if (c->comm || c->lcomm) {
-    if (c->stream) CHK(c, hipStreamSynchronize(c->stream)); else CHK(c, hipDeviceSynchronize());
-  }
-  if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-  c->lcomm = nullptr;
-  c->rank = 0; c->nranks = 1; c->gather = false; c->bcheck = false;
-  return LRNDE_OK;
-}
+// ---- batch-sharded handle: joining and leaving a communicator.  lrnde::Membership (lrnde_comm.hpp)
+// does it; what is this handle's own stays here ----
 static bool env_on(const char* name) { const char* v = getenv(name); return v && *v && strcmp(v, "0") != 0; }
+// (LRNDE_GATHER_TILES is read by a join that succeeded; a refused one leaves what the handle held, switch included)
+static int conv_comm_changed(lrnde_conv* c, int rc) {
+  if (!sharded(c)) c->gather = false;
+  else if (rc == LRNDE_OK) c->gather = env_on("LRNDE_GATHER_TILES");
+  c->bcheck = false;
+  return rc;
+}
 
 int lrnde_conv_comm_init(lrnde_conv* c, const void* uid, int32_t rank, int32_t nranks) {
   if (!c) return LRNDE_BADARG;
-  if (!uid || nranks < 1 || nranks > NSUMB || rank < 0 || rank >= nranks)
-    return cfail(c, LRNDE_BADARG, "bad communicator arguments (rank %d of %d; at most %d ranks)", rank, nranks, NSUMB);
-  CHK(c, hipSetDevice(c->device));
-  { const int rl = conv_comm_leave(c); if (rl) return rl; }
-  if (nranks > 1 || env_on("LRNDE_FORCE_COMM")) {
-    ncclUniqueId id;
-    memcpy(&id, uid, sizeof(id));
-    const ncclResult_t r = ncclCommInitRank(&c->comm, nranks, id, rank);
-    if (r != ncclSuccess) { c->comm = nullptr; return cfail(c, LRNDE_NCCL_ERROR, "ncclCommInitRank failed: %s", ncclGetErrorString(r)); }
-    c->rank = rank; c->nranks = nranks;
-    c->gather = env_on("LRNDE_GATHER_TILES");
-  }
-  return LRNDE_OK;
+  return conv_comm_changed(c, c->mem.join_rccl(uid, rank, nranks, NSUMB, env_on("LRNDE_FORCE_COMM"), c->device, c->stream, &c->err));
+}
+
+int lrnde_conv_comm_init_local(lrnde_conv* c, lrnde_local_comm* lc, int32_t rank) {
+  if (!c) return LRNDE_BADARG;
+  return conv_comm_changed(c, c->mem.join_local(lc, rank, c->device, c->stream, &c->err));
 }
 
 int lrnde_conv_comm_destroy(lrnde_conv* c) {
   if (!c) return LRNDE_BADARG;
   CHK(c, hipSetDevice(c->device));
-  return conv_comm_leave(c);
+  return conv_comm_changed(c, c->mem.leave(c->stream, &c->err));
 }
 
 int lrnde_conv_comm_count(lrnde_conv* c, int32_t* nranks_host, int32_t* kind_host) {
   if (!c || !nranks_host) return LRNDE_BADARG;
-  int n = 1, kind = 0;
-  if (c->comm) {
-    const ncclResult_t r = ncclCommCount(c->comm, &n);
-    if (r != ncclSuccess) return cfail(c, LRNDE_NCCL_ERROR, "ncclCommCount failed: %s", ncclGetErrorString(r));
-    kind = 1;
-  } else if (c->lcomm) { n = c->lcomm->n; kind = 2; }
-  *nranks_host = n;
-  if (kind_host) *kind_host = kind;  // 0 none, 1 RCCL, 2 in-process local communicator
-  return LRNDE_OK;
-}
-
-int lrnde_conv_comm_init_local(lrnde_conv* c, lrnde_local_comm* lc, int32_t rank) {
-  if (!c) return LRNDE_BADARG;
-  if (!lc || rank < 0 || rank >= lc->n) return cfail(c, LRNDE_BADARG, "bad local communicator arguments (rank %d)", rank);
-  CHK(c, hipSetDevice(c->device));
-  if (c->lcomm == lc) return cfail(c, LRNDE_BADARG, "the handle has already joined this local communicator (rank %d)", c->rank);
-  { const int rl = conv_comm_leave(c); if (rl) return rl; }   // whatever other communicator the handle held before
-  {
-    std::lock_guard<std::mutex> lk(lc->mu);
-    if (lc->joined[rank]) return cfail(c, LRNDE_BADARG, "rank %d has already joined this local communicator", rank);
-    // one device only: the sum kernel reads the peers' send buffers directly, and no peer access is set up between devices
-    for (int r = 0; r < lc->n; ++r)
-      if (lc->joined[r] && lc->device[r] != c->device)
-        return cfail(c, LRNDE_UNSUPPORTED, "the in-process local communicator is single-device (rank %d is on device %d, rank %d on %d); "
-                     "use lrnde_conv_comm_init (RCCL) across devices", r, lc->device[r], rank, c->device);
-    CHK(c, hipEventCreateWithFlags(&lc->ready[rank], hipEventDisableTiming));
-    CHK(c, hipEventCreateWithFlags(&lc->done[rank], hipEventDisableTiming));
-    lc->device[rank] = c->device;
-    lc->joined[rank] = true;
-  }
-  c->lcomm = lc; c->rank = rank; c->nranks = lc->n;
-  c->gather = env_on("LRNDE_GATHER_TILES");
-  return LRNDE_OK;
+  int kind = 0;
+  const int rc = c->mem.count(nranks_host, &kind, &c->err);
+  if (kind_host) *kind_host = kind;
+  return rc;
 }
 
 int lrnde_conv_comm_stats(lrnde_conv* c, uint64_t* exchanges_host, uint64_t* bytes_host) {
   if (!c) return LRNDE_BADARG;
-  if (exchanges_host) *exchanges_host = c->xchg_n;
-  if (bytes_host) *bytes_host = c->xchg_bytes;
+  if (exchanges_host) *exchanges_host = c->mem.exchanges;
+  if (bytes_host) *bytes_host = c->mem.bytes;
   return LRNDE_OK;
 }
 
@@ -2937,7 +2869,7 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
   // sharded: lambda is this rank's block, mu is replicated (launch_vjp returns gp summed over ranks, so every rank
   // integrates the same mu).  The error norm runs over [lambda of all ranks; mu once]: rank 0 adds mu's terms to its
   // lambda sums, the other ranks add lambda's only, and the mean divides by n_global + P.
-  const NormSpan sp = sharded(c) ? NormSpan{c->rank == 0 ? N : n, (double)n * c->nranks + (double)P} : NormSpan{N, (double)N};
+  const NormSpan sp = sharded(c) ? NormSpan{c->mem.rank == 0 ? N : n, (double)n * c->mem.nranks + (double)P} : NormSpan{N, (double)N};
   rc = adjoint_solve(c, N, sp, rhs, Z, -t2, -t0, o, stops, st_bwd);
   if (rc) return cfail(c, rc, "adjoint solve stopped with retcode %d", rc);
   CHK(c, hipMemcpyAsync(dx, Z, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
@@ -3191,8 +3123,8 @@ static int stem_common(lrnde_conv* c, const float* x, int B, const float* ps, co
   const int H = c->d.height, W = c->d.width;
   hipLaunchKernelGGL(k_stem_raw, dim3(nblk), dim3(SH_T), 0, c->stream, x, ps, B, H, W, a0, part);
   if (c->d.bn_train && sharded(c)) {  // BatchNorm(8) over the global batch: rank sums in k_bn_finalize's order, slot, exchange
-    const int R = c->nranks;
-    hipLaunchKernelGGL(k_blk_rank_sums, dim3(8), dim3(256), 0, c->stream, (const double*)part, nblk, 8, R, c->rank, c->xv.get());
+    const int R = c->mem.nranks;
+    hipLaunchKernelGGL(k_blk_rank_sums, dim3(8), dim3(256), 0, c->stream, (const double*)part, nblk, 8, R, c->mem.rank, c->xv.get());
     const int rx = exchange(c, (size_t)R * 16);
     if (rx) return rx;
     hipLaunchKernelGGL(k_bn_finalize, dim3(8), dim3(256), 0, c->stream, (const double*)c->xv, R, 8, (double)B * H * W * R, c->d.bn_eps, mi, mi + 8,
@@ -3212,7 +3144,7 @@ int lrnde_cifar_stem_forward(lrnde_conv* c, const float* x, int32_t B, const flo
   const int nblk = (int)(((long)B * plane + SH_T - 1) / SH_T);
   DevBuf<float> a0, mi; DevBuf<double> part;
   CHK(c, a0.once(total)); CHK(c, mi.once(16)); CHK(c, part.once(nblk * 16));
-  { const int rb = begin_layer_call(c, B, 16 * (size_t)c->nranks); if (rb) return rb; }
+  { const int rb = begin_layer_call(c, B, 16 * (size_t)c->mem.nranks); if (rb) return rb; }
   if (bn_state_out) hipLaunchKernelGGL(k_stem_state_copy, dim3(1), dim3(64), 0, c->stream, bn_state, bn_state_out);
   int rc = stem_common(c, x, B, ps, bn_state, a0, mi, part, nblk, bn_state_out);
   if (!rc) {
@@ -3231,13 +3163,13 @@ int lrnde_cifar_stem_backward(lrnde_conv* c, const float* x, int32_t B, const fl
   DevBuf<float> a0, mi, mm, partw; DevBuf<double> part;
   CHK(c, a0.once(total)); CHK(c, mi.once(16)); CHK(c, mm.once(16));
   CHK(c, part.once(nblk * 16)); CHK(c, partw.once((size_t)nblk * 140));
-  int rc = begin_layer_call(c, B, 16 * (size_t)c->nranks);
+  int rc = begin_layer_call(c, B, 16 * (size_t)c->mem.nranks);
   if (!rc) rc = stem_common(c, x, B, ps, bn_state, a0, mi, part, nblk);
   if (!rc) {
     hipLaunchKernelGGL(k_stem_bwd1, dim3(nblk), dim3(SH_T), 0, c->stream, (const float*)a0, du0, (const float*)mi, (const float*)(mi + 8), B, plane, part);
     if (sharded(c)) {  // global m1 / m2; d scale, d bias summed over ranks by the finalize
-      const int R = c->nranks;
-      hipLaunchKernelGGL(k_blk_rank_sums_seq, dim3(1), dim3(64), 0, c->stream, (const double*)part, nblk, 8, R, c->rank, c->xv.get());
+      const int R = c->mem.nranks;
+      hipLaunchKernelGGL(k_blk_rank_sums_seq, dim3(1), dim3(64), 0, c->stream, (const double*)part, nblk, 8, R, c->mem.rank, c->xv.get());
       if ((rc = exchange(c, (size_t)R * 16))) return rc;
       hipLaunchKernelGGL(k_stem_bwd_finalize, dim3(1), dim3(64), 0, c->stream, (const double*)c->xv, R, (double)B * plane * R, c->d.bn_train ? 1 : 0, mm, mm + 8, dps);
     } else {
@@ -3271,10 +3203,10 @@ int lrnde_cifar_head_ce(lrnde_conv* c, const float* u, int32_t B, const float* p
   if (sharded(c)) {
     // the global mean loss: the rank's loss sum and its bad-label flag travel in one exchange, so a label outside [0, K)
     // on one rank fails the call on every rank, before the dph all-reduce
-    const int R = c->nranks;
+    const int R = c->mem.nranks;
     int rc;
     if ((rc = begin_layer_call(c, B, 2 * (size_t)R))) return rc;
-    hipLaunchKernelGGL(k_loss_slot, dim3(1), dim3(64), 0, c->stream, (const float*)lb, B, R, c->rank, c->xv.get());
+    hipLaunchKernelGGL(k_loss_slot, dim3(1), dim3(64), 0, c->stream, (const float*)lb, B, R, c->mem.rank, c->xv.get());
     if ((rc = exchange(c, 2 * (size_t)R))) return rc;
     CHK(c, hipMemcpyAsync(c->sums_host, c->xv, sizeof(double) * 2 * R, hipMemcpyDeviceToHost, c->stream));
     CHK(c, hipStreamSynchronize(c->stream));
@@ -3294,7 +3226,7 @@ int lrnde_cifar_head_ce(lrnde_conv* c, const float* u, int32_t B, const float* p
   }
   if (sharded(c)) {
     CHK(c, hipStreamSynchronize(c->stream));
-    *loss_host = (float)(loss_sum / ((double)B * c->nranks));
+    *loss_host = (float)(loss_sum / ((double)B * c->mem.nranks));
     return LRNDE_OK;
   }
   std::vector<float> hl((size_t)B + 1);

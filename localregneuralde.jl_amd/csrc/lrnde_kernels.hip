@@ -27,10 +27,8 @@
 //     chain in increasing k — exactly what v_mfma_f32_16x16x4_f32 computes —
 //     so results are reproducible and equal to the CPU oracle's.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1716,10 +1714,7 @@ struct lrnde_ctx {
   PinBuf<Ctrl> ctrl_host;  // pinned [2]
   HipEvent ev_norm;  // vec_norm's read-back
   DevBuf<char> cls_ws; PinBuf<char> cls_host;  // lrnde_classifier_ce workspace (device / pinned)
-  // comm
-  ncclComm_t comm = nullptr;           // RCCL communicator (one process per GPU)
-  lrnde_local_comm* lcomm = nullptr;   // or: in-process local communicator (lrnde_hooks.h), never both
-  int rank = 0, nranks = 1;
+  lrnde::Membership mem;   // its communicator, rank and exchange counters (lrnde_comm.hpp)
   // per-rank pre-reduction of the error-norm partial sums (StepArgs::prered): default for sharded handles; with
   // LRNDE_GATHER_TILES=1 in the environment every tile's partial is exchanged instead (the exact gather)
   bool prered = false;
@@ -1825,30 +1820,9 @@ inline int vjp_qcols(int B) {
   return (q == 1 || q == 2) && B <= 256 * q ? q : QNB;
 }
 
-int fail(lrnde_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  return code;
-}
-
-#define HIPCHK(c, x)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess)                                                                     \
-      return fail(c, LRNDE_HIP_ERROR, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_),     \
-                  __FILE__, __LINE__);                                                        \
-  } while (0)
-#define NCCLCHK(c, x)                                                                         \
-  do {                                                                                        \
-    ncclResult_t r_ = (x);                                                                    \
-    if (r_ != ncclSuccess)                                                                    \
-      return fail(c, LRNDE_NCCL_ERROR, "%s failed: %s (%s:%d)", #x, ncclGetErrorString(r_),   \
-                  __FILE__, __LINE__);                                                        \
-  } while (0)
+// this handle's names for the library's formatter and HIP check (lrnde_fail.hpp)
+constexpr auto fail = &lrnde::failf<lrnde_ctx>;
+#define HIPCHK(c, x) LRNDE_HIPCHK(c, x)
 
 #define HPT(c, i) ((c)->hp_t[i] = std::chrono::steady_clock::now())
 // The host loops that spin on a report in pinned memory wait with ReportWait (lrnde_report.hpp); this is its query.  The
@@ -1861,19 +1835,10 @@ inline int queue_state(hipStream_t s) {
 #define LRNDE_HUNG(c, what) ((c)->hung = true, fail((c), LRNDE_HIP_ERROR, "%s: no report for %d s while the queue stayed busy (hung queue); destroy the handle", (what), LRNDE_SPIN_DEADLINE_S))
 
 // a batch-sharded handle: its collectives run (RCCL or the in-process local communicator, lrnde_comm.hpp)
-inline bool sharded(const lrnde_ctx* c) { return c->comm != nullptr || c->lcomm != nullptr; }
-// every collective of the library: SUM all-reduce of `count` doubles / floats on the handle's stream (send may equal recv)
-int comm_allreduce(lrnde_ctx* c, const void* send, void* recv, size_t count, bool is_double) {
-  if (c->comm) {
-    NCCLCHK(c, ncclAllReduce(send, recv, count, is_double ? ncclDouble : ncclFloat, ncclSum, c->comm, c->stream));
-    return LRNDE_OK;
-  }
-  if (c->lcomm) {
-    const int rc = lc_allreduce(c->lcomm, c->rank, c->stream, send, recv, count, is_double);
-    if (rc) return fail(c, rc, "local communicator all-reduce failed (rank %d of %d): %s", c->rank, c->nranks,
-                        rc == LRNDE_NCCL_ERROR ? "a peer did not arrive (timeout) or the communicator is broken" : "HIP error");
-  }
-  return LRNDE_OK;
+inline bool sharded(const lrnde_ctx* c) { return c->mem.sharded(); }
+// SUM all-reduce of `count` doubles / floats on the handle's stream (send may equal recv)
+inline int comm_allreduce(lrnde_ctx* c, const void* send, void* recv, size_t count, bool is_double) {
+  return c->mem.allreduce(c->stream, send, recv, count, is_double, &c->err);
 }
 
 inline int ceil16(int x) { return (x + 15) & ~15; }
@@ -1900,7 +1865,7 @@ size_t param_count(const lrnde_ctx* c) {
 int ensure_workspace(lrnde_ctx* c, int B) {
   const size_t n = (size_t)B * c->desc.state_dim;
   const int nwg = (B + QNB - 1) / QNB;  // sized for the finer tile: covers both shapes
-  const int nwg_global = nwg * c->nranks;
+  const int nwg_global = nwg * c->mem.nranks;
   if (B != c->wsB) {
     // every buffer sized by B is dropped first, then allocated anew: B changed, so none can be kept
     for (DevBuf<double>* b : {&c->part, &c->part_rx, &c->pinit, &c->pinit_rx, &c->tile_part, &c->tile_pinit}) HIPCHK(c, b->reset());
@@ -1945,13 +1910,13 @@ void fill_args(lrnde_ctx* c, StepArgs& a, int B, int force_nb = 0) {
   for (int i = 0; i < 5; ++i) a.ks[i] = c->state + (4 + i) * n;
   a.g6 = c->state + 9 * n;
   a.B = B;
-  a.nwg_global = nwg * c->nranks;
-  a.wg_offset = nwg * c->rank;
+  a.nwg_global = nwg * c->mem.nranks;
+  a.wg_offset = nwg * c->mem.rank;
   if (sharded(c) && c->prered && !force_nb) {
     a.prered = 1; a.arrive = c->arrive; a.tile_part = c->tile_part; a.tile_pinit = c->tile_pinit;
-    a.nwg_global = c->nranks; a.wg_offset = c->rank;
+    a.nwg_global = c->mem.nranks; a.wg_offset = c->mem.rank;
   }
-  a.n_global = (double)c->desc.state_dim * (double)B * (double)c->nranks;
+  a.n_global = (double)c->desc.state_dim * (double)B * (double)c->mem.nranks;
   a.ctrl = c->ctrl;
   a.part_send = c->part;
   a.part_recv = sharded(c) ? c->part_rx : c->part;
@@ -2243,15 +2208,8 @@ size_t lrnde_chain_param_count(const lrnde_chain_desc* d) {
   return n;
 }
 
-static int chain_refuse(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_create_err = buf;
-  return code;
-}
+// a refused create has no handle yet: the message goes to the thread's create-error string
+#define chain_refuse(...) lrnde::failf(&g_create_err, __VA_ARGS__)
 
 // what both Dense-chain handles check of a descriptor (maxw, what: the handle's width limit and the name of its kernels)
 static int chain_desc_check(lrnde_ctx** out, const lrnde_chain_desc* d, int maxw, const char* what) {
@@ -2402,7 +2360,7 @@ int lrnde_destroy(lrnde_ctx* c) {
     hipStreamDestroy(ss);
     c->side = nullptr;
   }
-  if (c->comm) ncclCommDestroy(c->comm);
+  (void)c->mem.leave(c->stream, &c->err);
   if (c->adj_stream2) hipStreamDestroy(c->adj_stream2);
   delete c;
   return LRNDE_OK;
@@ -2954,51 +2912,39 @@ int lrnde_node_forward(lrnde_ctx* c, const float* x, int32_t B, float t0, float 
   return rc;
 }
 
-int lrnde_comm_unique_id(void* out) {
-  if (!out) return LRNDE_BADARG;
-  static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-  ncclUniqueId id;
-  if (ncclGetUniqueId(&id) != ncclSuccess) return LRNDE_NCCL_ERROR;
-  memcpy(out, &id, sizeof(id));
-  return LRNDE_OK;
+// ---- joining and leaving a communicator: lrnde::Membership (lrnde_comm.hpp) does it; what is this handle's own stays here ----
+// (the partial-sum vectors are sized by nranks; a join that succeeded reads LRNDE_GATHER_TILES: pre-reduce unless set)
+static int comm_changed(lrnde_ctx* c, int rc) {
+  c->wsB = 0;
+  if (rc == LRNDE_OK && sharded(c)) c->prered = !opt(OPT_GATHER_TILES);
+  return rc;
 }
 
 int lrnde_comm_init(lrnde_ctx* c, const void* uid, int32_t rank, int32_t nranks) {
   if (c && c->field) return fail(c, LRNDE_UNSUPPORTED, "a Dense-chain handle is not sharded: its kernels run one rank");
-  if (!c || !uid || nranks < 1 || rank < 0 || rank >= nranks) return LRNDE_BADARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-  c->lcomm = nullptr;
-  c->rank = rank; c->nranks = nranks;
-  c->wsB = 0;  // partial vectors are sized by nranks
-  if (nranks > 1 || opt(OPT_FORCE_COMM)) {
-    ncclUniqueId id;
-    memcpy(&id, uid, sizeof(id));
-    NCCLCHK(c, ncclCommInitRank(&c->comm, nranks, id, rank));
-    c->prered = !opt(OPT_GATHER_TILES);
-  }
-  return LRNDE_OK;
+  if (!c) return LRNDE_BADARG;
+  return comm_changed(c, c->mem.join_rccl(uid, rank, nranks, 0, opt(OPT_FORCE_COMM) != 0, c->device, c->stream, &c->err));
+}
+
+int lrnde_comm_init_local(lrnde_ctx* c, lrnde_local_comm* lc, int32_t rank) {
+  if (c && c->field) return fail(c, LRNDE_UNSUPPORTED, "a Dense-chain handle is not sharded: its kernels run one rank");
+  if (!c) return LRNDE_BADARG;
+  return comm_changed(c, c->mem.join_local(lc, rank, c->device, c->stream, &c->err));
 }
 
 int lrnde_comm_destroy(lrnde_ctx* c) {
   if (!c) return LRNDE_BADARG;
-  if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-  c->lcomm = nullptr;
-  c->rank = 0; c->nranks = 1; c->wsB = 0;
-  return LRNDE_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  return comm_changed(c, c->mem.leave(c->stream, &c->err));
 }
 
-// how many ranks the handle's communicator really has: ncclCommCount for RCCL, the rendezvous size for the local
-// communicator, 1 for an unsharded handle — what bench.py prints as `rccl_nranks` (WORLD_SIZE says what was asked for,
-// this says what was built)
+// what bench.py prints as `rccl_nranks`
 int lrnde_comm_count(lrnde_ctx* c, int32_t* nranks_host, int32_t* kind_host) {
   if (!c || !nranks_host) return LRNDE_BADARG;
-  int n = 1, kind = 0;
-  if (c->comm) { NCCLCHK(c, ncclCommCount(c->comm, &n)); kind = 1; }
-  else if (c->lcomm) { n = c->lcomm->n; kind = 2; }
-  *nranks_host = n;
-  if (kind_host) *kind_host = kind;  // 0 none, 1 RCCL, 2 in-process local communicator
-  return LRNDE_OK;
+  int kind = 0;
+  const int rc = c->mem.count(nranks_host, &kind, &c->err);
+  if (kind_host) *kind_host = kind;
+  return rc;
 }
 
 // bench.py --gpus N: `reps` back-to-back exchanges of the per-step kind (the all-reduce of the error norm's partial sums,
@@ -3028,52 +2974,6 @@ int lrnde_bench_exchange(lrnde_ctx* c, int32_t B, int32_t reps, float* avg_us_ho
   hipEventDestroy(e0); hipEventDestroy(e1);
   if (rc) return rc;
   *avg_us_host = ms * 1e3f / (float)reps;
-  return LRNDE_OK;
-}
-
-// ---- in-process local communicator (include/lrnde_hooks.h; lrnde_comm.hpp) ----
-int lrnde_local_comm_create(lrnde_local_comm** out, int32_t nranks) {
-  if (!out || nranks < 1 || nranks > LRNDE_LC_MAXR) return LRNDE_BADARG;
-  lrnde_local_comm* lc = new lrnde_local_comm();
-  lc->n = nranks;
-  *out = lc;
-  return LRNDE_OK;
-}
-
-int lrnde_local_comm_destroy(lrnde_local_comm* lc) {
-  if (!lc) return LRNDE_OK;
-  for (int r = 0; r < lc->n; ++r) {
-    if (!lc->joined[r]) continue;
-    hipSetDevice(lc->device[r]);
-    (void)lc->tmp[r].reset();
-    if (lc->ready[r]) hipEventDestroy(lc->ready[r]);
-    if (lc->done[r]) hipEventDestroy(lc->done[r]);
-  }
-  delete lc;
-  return LRNDE_OK;
-}
-
-int lrnde_comm_init_local(lrnde_ctx* c, lrnde_local_comm* lc, int32_t rank) {
-  if (c && c->field) return fail(c, LRNDE_UNSUPPORTED, "a Dense-chain handle is not sharded: its kernels run one rank");
-  if (!c || !lc || rank < 0 || rank >= lc->n) return LRNDE_BADARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-  {
-    std::lock_guard<std::mutex> lk(lc->mu);
-    if (lc->joined[rank]) return fail(c, LRNDE_BADARG, "rank %d has already joined this local communicator", rank);
-    // one device only: the sum kernel reads the peers' send buffers directly, and no peer access is set up between devices
-    for (int r = 0; r < lc->n; ++r)
-      if (lc->joined[r] && lc->device[r] != c->device)
-        return fail(c, LRNDE_UNSUPPORTED, "the in-process local communicator is single-device (rank %d is on device %d, rank %d on %d); "
-                    "use lrnde_comm_init (RCCL) across devices", r, lc->device[r], rank, c->device);
-    HIPCHK(c, hipEventCreateWithFlags(&lc->ready[rank], hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&lc->done[rank], hipEventDisableTiming));
-    lc->device[rank] = c->device;
-    lc->joined[rank] = true;
-  }
-  c->lcomm = lc; c->rank = rank; c->nranks = lc->n;
-  c->prered = !opt(OPT_GATHER_TILES);
-  c->wsB = 0;  // partial vectors are sized by nranks
   return LRNDE_OK;
 }
 
@@ -4012,10 +3912,10 @@ int vec_norm(lrnde_ctx* c, const float* num, const float* num2, const float* sa,
 }
 // the per-block sums in c->adj_part (lambda part [0,256), mu part [256,512)) -> the rms over [lambda of all ranks; mu]
 int norm_readback(lrnde_ctx* c, size_t n_lam, size_t P, float* out) {
-  const int nr = sharded(c) ? c->nranks : 1;
+  const int nr = sharded(c) ? c->mem.nranks : 1;
   if (sharded(c)) {
     if (nr > 64) return fail(c, LRNDE_UNSUPPORTED, "more than 64 ranks");
-    hipLaunchKernelGGL(k_rank_slot, dim3(1), dim3(64), 0, c->stream, c->adj_part, c->adj_part + 512, c->rank, nr);
+    hipLaunchKernelGGL(k_rank_slot, dim3(1), dim3(64), 0, c->stream, c->adj_part, c->adj_part + 512, c->mem.rank, nr);
     { const int rcc = comm_allreduce(c, c->adj_part + 512, c->adj_part + 512, nr, true); if (rcc) return rcc; }
   }
   HIPCHK(c, hipMemcpyAsync(c->adj_part_host, c->adj_part, sizeof(double) * (512 + 64), hipMemcpyDeviceToHost, c->stream));
@@ -4240,9 +4140,9 @@ int adj_enqueue_pgrad(lrnde_ctx* c, int B, const AdjArgs& g, int mode, int stage
 // per-rank lambda sum -> rank slots, exact gather (sharded handles); the partial block `part` is [512 + 64] doubles
 int adj_enqueue_slots(lrnde_ctx* c, double* part) {
   if (!sharded(c)) return LRNDE_OK;
-  if (c->nranks > 64) return fail(c, LRNDE_UNSUPPORTED, "more than 64 ranks");
-  hipLaunchKernelGGL(k_rank_slot, dim3(1), dim3(64), 0, c->stream, part, part + 512, c->rank, c->nranks);
-  return comm_allreduce(c, part + 512, part + 512, c->nranks, true);
+  if (c->mem.nranks > 64) return fail(c, LRNDE_UNSUPPORTED, "more than 64 ranks");
+  hipLaunchKernelGGL(k_rank_slot, dim3(1), dim3(64), 0, c->stream, part, part + 512, c->mem.rank, c->mem.nranks);
+  return comm_allreduce(c, part + 512, part + 512, c->mem.nranks, true);
 }
 
 int adj_norm_into(lrnde_ctx* c, const float* num, const float* num2, const float* sa, float abstol, float reltol, size_t n_lam,
@@ -4843,7 +4743,7 @@ static int step_reg_sweep(lrnde_ctx* c, const float* uprev, int32_t B, float t, 
   HIPCHK(c, hipMemsetAsync(c->adj, 0, sizeof(float) * 8 * N, c->stream));
   HIPCHK(c, hipMemsetAsync(gp, 0, sizeof(float) * P, c->stream));
   RegSeedArgs sa{};
-  sa.n = n; sa.n_norm = n * (size_t)(sharded(c) ? c->nranks : 1); sa.uprev = uprev; sa.u = u; sa.g6 = g6;
+  sa.n = n; sa.n_norm = n * (size_t)(sharded(c) ? c->mem.nranks : 1); sa.uprev = uprev; sa.u = u; sa.g6 = g6;
   for (int j = 0; j < 7; ++j) sa.k[j] = kk[j];
   for (int j = 1; j < 7; ++j) sa.kb[j] = kb[j];
   sa.ub = ub; sa.g6b = g6b; sa.dt = dt; sa.abstol = abstol; sa.reltol = reltol; sa.reg_type = reg_type;
@@ -5167,7 +5067,7 @@ int cls_enqueue(lrnde_ctx* c, const float* u, int32_t B, const float* pc, int32_
   float* lb = dl + (size_t)B * K;
   // the loss is the mean over the GLOBAL batch: on a sharded handle every rank normalises by B * nranks, and the loss
   // and the classifier cotangent (sums over all samples) are all-reduced; du stays sharded like dx
-  const int nr = sharded(c) ? c->nranks : 1;
+  const int nr = sharded(c) ? c->mem.nranks : 1;
   const float Bnorm = (float)B * (float)nr;
   HIPCHK(c, hipMemsetAsync(out, 0, sizeof(ClsOut), c->stream));
   const size_t wbytes = sizeof(float) * (size_t)K * (D + 1);
@@ -5195,7 +5095,7 @@ int cls_enqueue(lrnde_ctx* c, const float* u, int32_t B, const float* pc, int32_
 }
 // after the stream has been synchronised
 int cls_finish(lrnde_ctx* c, int32_t B, int32_t K, float* loss_host) {
-  const int nr = sharded(c) ? c->nranks : 1;
+  const int nr = sharded(c) ? c->mem.nranks : 1;
   const ClsOut* ho = reinterpret_cast<const ClsOut*>(c->cls_host.get());
   if (ho->bad_label) return fail(c, LRNDE_BADARG, "a label is outside [0, %d)", K);
   *loss_host = (float)(ho->loss_sum / ((double)B * (double)nr));

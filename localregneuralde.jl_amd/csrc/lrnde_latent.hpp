@@ -715,21 +715,11 @@ struct lrnde_latent {
 namespace {
 thread_local std::string g_lat_create_err;
 
-int lat_fail(lrnde_latent* h, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  if (h) h->err = buf; else g_lat_create_err = buf;
-  return code;
-}
-#define LATCHK(h, x)                                                                                                  \
-  do {                                                                                                                \
-    hipError_t e_ = (x);                                                                                              \
-    if (e_ != hipSuccess)                                                                                             \
-      return lat_fail(h, LRNDE_HIP_ERROR, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__);     \
-  } while (0)
+// this handle's names for the library's formatter and HIP check (lrnde_fail.hpp); without a handle (a refused create)
+// the message goes to the thread's create-error string
+inline std::string* lat_err(lrnde_latent* h) { return h ? &h->err : &g_lat_create_err; }
+#define lat_fail(h, ...) lrnde::failf(lat_err(h), __VA_ARGS__)
+#define LATCHK(h, x) LRNDE_HIPCHK(lat_err(h), x)
 
 bool lat_desc_ok(const lrnde_latent_desc* d) {
   return d && d->in_dims >= 1 && d->hidden_dims >= 1 && d->latent_dims >= 1 && d->node_dims >= 1 && d->in_dims <= (1 << 14) &&

@@ -17,9 +17,11 @@ def shard_columns(x, rank, nranks):
     return x[rank * per:(rank + 1) * per]
 
 
-def _is_conv(handle):
+def _comm_fn(handle, verb):
+    """The library's `verb` ("init", "init_local", "destroy") for this handle's type: lrnde_conv_comm_<verb> for a
+    ConvHandle, lrnde_comm_<verb> for any other handle."""
     from .conv import ConvHandle
-    return isinstance(handle, ConvHandle)
+    return getattr(L.lib, ("lrnde_conv_comm_" if isinstance(handle, ConvHandle) else "lrnde_comm_") + verb)
 
 
 def init_comm(handle, rank, nranks, group=None):
@@ -41,8 +43,7 @@ def init_comm(handle, rank, nranks, group=None):
         t = t.cpu()
     raw = bytes(t.tolist())
     buf2 = (C.c_uint8 * 128).from_buffer_copy(raw)
-    init = L.lib.lrnde_conv_comm_init if _is_conv(handle) else L.lib.lrnde_comm_init
-    handle._chk(init(handle._ctx, buf2, int(rank), int(nranks)))
+    handle._chk(_comm_fn(handle, "init")(handle._ctx, buf2, int(rank), int(nranks)))
 
 
 class LocalComm:
@@ -60,15 +61,14 @@ class LocalComm:
         self._handles = []
 
     def join(self, handle, rank):
-        join = L.lib.lrnde_conv_comm_init_local if _is_conv(handle) else L.lib.lrnde_comm_init_local
-        handle._chk(join(handle._ctx, self._lc, int(rank)))
+        handle._chk(_comm_fn(handle, "init_local")(handle._ctx, self._lc, int(rank)))
         self._handles.append(handle)
 
     def close(self):
         if getattr(self, "_lc", None):
             for h in self._handles:
                 if getattr(h, "_ctx", None):
-                    (L.lib.lrnde_conv_comm_destroy if _is_conv(h) else L.lib.lrnde_comm_destroy)(h._ctx)
+                    _comm_fn(h, "destroy")(h._ctx)
             L.lib.lrnde_local_comm_destroy(self._lc)
             self._lc = None
 

@@ -172,3 +172,60 @@ def test_sharded_backward_and_training_step(gpu_pkg, nranks, Bl, gather, K):
         bad = labels.copy(); bad[3] = K
         hu.classifier_ce(u, pc, K, torch.from_numpy(bad).cuda())
     lc.close()
+
+
+def test_leaving_with_work_queued_then_joining_again(gpu_pkg):
+    """lrnde_comm_destroy right behind a sharded solve, no host synchronisation in between: leaving drains the handle's
+    stream before the membership goes, the handle is unsharded in between, and a second membership on a fresh
+    rendezvous gives the first one's bits — which are the unsharded handle's on the global batch (4-column kernels, B = 24
+    per rank)"""
+    import torch
+    from localregneuralde_jl_amd import _lib as L
+    P = gpu_pkg
+    nranks, Bl, tol, sv = 2, 24, 1e-4, [0.37, 1.0]
+    model, p, x = _setup(P, nranks * Bl)
+    ref = _unsharded(P, model, p).solve(torch.from_numpy(x).cuda(), 0.0, 1.0, tol, tol, saveat=sv, maxiters=10000)
+    xs = [torch.from_numpy(np.ascontiguousarray(P.shard_columns(x, r, nranks))).cuda() for r in range(nranks)]
+    lc, hs = _handles(P, model, p, nranks, False)
+
+    def solves():
+        return P.run_ranks([(lambda r=r: hs[r].solve(xs[r], 0.0, 1.0, tol, tol, saveat=sv, maxiters=10000)) for r in range(nranks)])
+
+    first = solves()
+    for h in hs:
+        assert L.lib.lrnde_comm_destroy(h._ctx) == 0
+    for h in hs:
+        assert h.comm_count() == (1, 0)
+    lc2 = P.LocalComm(nranks)
+    for r, h in enumerate(hs):
+        lc2.join(h, r)
+        assert h.comm_count() == (nranks, 2)
+    second = solves()
+    torch.cuda.synchronize()
+    want = ref["u"].cpu().numpy()
+    for got in (first, second):
+        for g in got:
+            assert g["stats"] == ref["stats"] and np.array_equal(g["t"], ref["t"])
+        assert np.array_equal(np.concatenate([g["u"].cpu().numpy() for g in got], axis=1), want)
+    assert ref["stats"]["naccept"] > 3
+    lc2.close()
+    lc.close()
+
+
+def test_refused_joins_leave_the_handle_as_it_was(gpu_pkg):
+    """lrnde_comm_init with a rank outside the communicator: BADARG, the handle stays unsharded, and its next f-eval is a
+    fresh handle's"""
+    import ctypes
+    import torch
+    from localregneuralde_jl_amd import _lib as L
+    P = gpu_pkg
+    model, p, x = _setup(P, 24)
+    xd = torch.from_numpy(x).cuda()
+    want = _unsharded(P, model, p).rhs(xd, 0.3)
+    h = _unsharded(P, model, p)
+    uid = (ctypes.c_uint8 * 128)()
+    assert L.lib.lrnde_comm_init(h._ctx, uid, 2, 2) == 4
+    assert h.comm_count() == (1, 0)
+    assert L.lib.lrnde_comm_init(h._ctx, uid, -1, 2) == 4
+    assert h.comm_count() == (1, 0)
+    assert torch.equal(h.rhs(xd, 0.3), want)
