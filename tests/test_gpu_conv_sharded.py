@@ -6,7 +6,8 @@ Two yardsticks, neither of them the code under test:
   (U) one unsharded handle of the same library on the global batch,
   (O) oracle.ConvField on the global batch.
 Bars against (O) are the ones tests/test_gpu_conv.py holds the unsharded handle to; each is cited where it is used.
-Inputs follow test_gpu_conv._case (seeded glorot parameters times `scale`, random BatchNorm affine), restated here.
+Inputs follow test_gpu_conv._case (seeded glorot parameters times `scale`, random BatchNorm affine), restated in
+tests/conv_sharded_cases.py with the helpers this file and tests/test_gpu_conv_sharded_envelope.py share.
 
 Seeds of the solve cases: for every seed used below the oracle's trace on the global batch was checked on the CPU
 (seeds 5, 6, 7, 8 at 16x16 B=4 for tol 1e-3 / scale 3 and tol 1e-4 / scale 1.5; 21, 22, 23 at 8x8 B=4, tol 1e-3, scale 2;
@@ -31,97 +32,8 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 pytestmark = pytest.mark.gpu
 
-C, HC = 8, 64
-N1 = 9 * (C + 1) * HC; N2 = N1 + 2 * HC; N3 = N2 + 9 * (HC + 1) * HC; N4 = N3 + 2 * HC
-BLOCKS = (("w1", slice(0, N1)), ("bn1", slice(N1, N2)), ("w2", slice(N2, N3)), ("bn2", slice(N3, N4)), ("w3", slice(N4, None)))
-BN0 = np.concatenate([np.zeros(HC), np.ones(HC), np.zeros(HC), np.ones(HC)]).astype(np.float32)
-
-
-def _mods():
-    import lrnde_amd as P
-    import oracle as O
-    return P, O
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(W, H, B, seed, train=True, scale=1.0):
-    """test_gpu_conv._case's recipe: (params, state, running statistics or None)"""
-    P, O = _mods()
-    rng = np.random.default_rng(seed)
-    p = O.glorot_conv_params(C, HC, seed=seed) * np.float32(scale)
-    p[N1:N1 + HC] = rng.uniform(0.5, 1.5, HC); p[N1 + HC:N2] = rng.uniform(-0.3, 0.3, HC)
-    p[N3:N3 + HC] = rng.uniform(0.5, 1.5, HC); p[N3 + HC:N4] = rng.uniform(-0.3, 0.3, HC)
-    p = p.astype(np.float32)
-    u = rng.standard_normal((B, C, H, W)).astype(np.float32)
-    st = None
-    if not train:
-        st = np.concatenate([rng.normal(0, 0.2, HC), rng.uniform(0.5, 2, HC), rng.normal(0, 0.2, HC),
-                             rng.uniform(0.5, 2, HC)]).astype(np.float32)
-    return p, u, st
-
-
-def _field(W, H, p, st, act="gelu", train=True):
-    P, O = _mods()
-    return O.ConvField(W, H, C, HC, p, act=act, bn_train=train, bn_state=st, nthreads=8)
-
-
-def _handle(W, H, p, st, act="gelu", train=True, dtype="f32", stream=None):
-    P, O = _mods()
-    h = P.ConvHandle(W, H, C, HC, act=act, bn_train=train, compute_dtype=dtype, stream=stream)
-    if st is not None:
-        h.set_bn_state(st)
-    h.set_params(p)
-    return h
-
-
-def _ranks(R, W, H, p, st, act="gelu", train=True, dtype="f32", gather=False):
-    """R handles on their own streams, joined to one local communicator"""
-    P, O = _mods()
-    old = os.environ.pop("LRNDE_GATHER_TILES", None)
-    if gather:
-        os.environ["LRNDE_GATHER_TILES"] = "1"
-    try:
-        lc = P.LocalComm(R)
-        hs = []
-        for r in range(R):
-            h = _handle(W, H, p, st, act, train, dtype, stream=torch.cuda.Stream())
-            lc.join(h, r)
-            hs.append(h)
-    finally:
-        os.environ.pop("LRNDE_GATHER_TILES", None)
-        if old is not None:
-            os.environ["LRNDE_GATHER_TILES"] = old
-    torch.cuda.synchronize()
-    return lc, hs
-
-
-def _shards(a, R):
-    P, O = _mods()
-    out = [torch.from_numpy(np.ascontiguousarray(P.shard_columns(a, r, R))).cuda() for r in range(R)]
-    torch.cuda.synchronize()
-    return out
-
-
-def _run(fns):
-    P, O = _mods()
-    out = P.run_ranks(fns)
-    torch.cuda.synchronize()
-    return out
-
-
-def _np(a):
-    return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-
-
-def _dist(got, ref):
-    """max abs error in units of the reference's scale (the measure of test_gpu_conv._close)"""
-    got = _np(got); ref = np.asarray(ref).reshape(got.shape)
-    return float(np.abs(got - ref).max()) / max(float(np.abs(ref).max()), 1e-30)
-
-
-def _rel(a, b):
-    a, b = _np(a).astype(np.float64).ravel(), _np(b).astype(np.float64).ravel()
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
+from conv_sharded_cases import (BLOCKS, BN0, _dist, _field, _handle, _inputs, _mods, _ranks, _rel,  # noqa: E402
+                                _run, _shards)
 
 
 # R, B per rank, W, H, activation, training mode
