@@ -109,8 +109,8 @@ const char* lrnde_version(void);
  * A chain handle is accepted by lrnde_set_params, lrnde_rhs, lrnde_init_dt, lrnde_perform_step, lrnde_solve,
  * lrnde_node_forward, lrnde_vjp, lrnde_step_reg_grad, lrnde_node_forward_record(_ts), lrnde_node_backward_recorded(_ts),
  * lrnde_node_backward, lrnde_record_generation and lrnde_destroy.  It is refused with LRNDE_UNSUPPORTED by the
- * communicator entry points (lrnde_comm_init, lrnde_comm_init_local: chain handles are one rank), by lrnde_set_solver
- * with VCAB3 / VCABM3 (Tsit5 only), and by the hooks lrnde_set_overlap, lrnde_bench_step and lrnde_bench_exchange. */
+ * communicator entry points (lrnde_comm_init, lrnde_comm_init_local: chain handles are one rank) and by the hooks
+ * lrnde_set_overlap, lrnde_bench_step and lrnde_bench_exchange.  lrnde_set_solver accepts VCAB3 / VCABM3 (see there). */
 #define LRNDE_CHAIN_MAX_LAYERS 16
 #define LRNDE_CHAIN_MAX_WIDTH 128
 #define LRNDE_CHAIN_MAX_WEIGHT_BYTES (128 * 1024)
@@ -136,8 +136,8 @@ size_t lrnde_chain_param_count(const lrnde_chain_desc* desc);
  * VJP's scratch is bounded by that figure: larger batches run as several launches).
  * A wide-chain handle is accepted by every entry point listed above for a chain handle, and by
  * lrnde_node_forward_record_ce and lrnde_classifier_ce; it is refused with LRNDE_UNSUPPORTED by the same calls that refuse
- * a chain handle (communicator entry points, lrnde_set_solver with VCAB3 / VCABM3, lrnde_set_overlap, lrnde_bench_step,
- * lrnde_bench_exchange).  Its continuous adjoint runs the host-controlled loop by default and, after
+ * a chain handle (communicator entry points, lrnde_set_overlap, lrnde_bench_step, lrnde_bench_exchange) and by
+ * lrnde_set_solver with VCAB3 / VCABM3 (Tsit5 only).  Its continuous adjoint runs the host-controlled loop by default and, after
  * lrnde_set_adjoint_loop(ctx, LRNDE_ADJ_LOOP_DEVICE), the device-controlled loop of two launches per attempted step. */
 #define LRNDE_WIDE_CHAIN_MAX_WIDTH 1024
 int lrnde_create_wide_chain(lrnde_ctx** out, const lrnde_chain_desc* desc, int device, void* stream);
@@ -192,7 +192,15 @@ int lrnde_set_params(lrnde_ctx* ctx, const float* p, size_t n);
  * It selects the method of the layer's GLOBAL solve in lrnde_solve / lrnde_node_forward* / lrnde_node_backward*; the
  * local regularisation step stays Tsit5, as in the reference (neural_ode.jl:75,93 build that integrator with Tsit5()).
  * VCAB3 / VCABM3: restated from the published algorithm, UPSTREAM-RECALL (csrc/lrnde_adams.hpp says what is recalled);
- * the backward pass of a recorded Adams forward interpolates its Hermite record and integrates the adjoint with Tsit5. */
+ * the backward pass of a recorded Adams forward interpolates its Hermite record and integrates the adjoint with Tsit5.
+ * Which handles, which loop: the MLP handle runs the host-driven loop of csrc/lrnde_adams.hpp (3-4 launches and a read-back
+ * per attempted step); an unsharded small Dense-chain handle runs one launch per attempted step with the controller on the
+ * device (csrc/lrnde_chain_adams.hpp, k_adams_chain; same bits as the host loop, which the diagnostic switch
+ * LRNDE_ADAMS_HOST=1 selects there too).  A wide Dense-chain handle refuses alg != 0 with LRNDE_UNSUPPORTED (Tsit5 only);
+ * the conv handle has no such setter.
+ * The small chain's discrete adjoint walks a Tsit5 stage record: alg != 0 on a handle whose lrnde_set_sensealg choice is
+ * DISCRETE returns LRNDE_UNSUPPORTED, and so does lrnde_set_sensealg(DISCRETE) on a handle whose solver is not Tsit5 —
+ * whichever is set second is refused, with a message, and the handle stays usable.  Any other code: LRNDE_BADARG. */
 enum { LRNDE_ALG_TSIT5 = 0, LRNDE_ALG_VCAB3 = 1, LRNDE_ALG_VCABM3 = 2 };
 int lrnde_set_solver(lrnde_ctx* ctx, int32_t alg);
 

@@ -11,7 +11,7 @@
 #     (`diffeqsol_to_timeseries`, src/utils.jl:42-46); `reg_val`'s gradient goes to `ps` only (neural_ode.jl:40).
 # Everything else (other solvers, other model shapes, CPU arrays) falls through to the reference's own methods.
 #
-# Supported models (solver `Tsit5()`; the MLP field also with `VCAB3()` / `VCABM3()`):
+# Supported models (solver `Tsit5()`; the MLP field and the small Dense chains also with `VCAB3()` / `VCABM3()`):
 #   * `TDChain(Dense(D+1 => H, act), Dense(H+1 => D))` / `Chain(Dense(D => H, act), Dense(H => D))`, act ∈ (identity, tanh,
 #     gelu) — the MNIST-ODE field of experiments/src/construct.jl:180-189;
 #   * the CIFAR10 `node_core` of experiments/src/construct.jl:213-218, `TDChain(Chain(Conv((3,3), 9 => 64; pad=1,
@@ -62,7 +62,7 @@ function lrnde_field_shape(model)
 end
 
 "lrnde_chain_desc of any other Chain / TDChain of Dense layers (a plain Chain may open with `Base.Fix1(broadcast, act)` /
-`WrappedFunction`), or nothing: a Dense-chain handle, Tsit5 only — the small one (lrnde_create_chain) within its limits,
+`WrappedFunction`), or nothing: a Dense-chain handle — the small one (lrnde_create_chain) within its limits,
 the wide one (lrnde_create_wide_chain, widths up to 1024) beyond them"
 function lrnde_chain_shape(model)
     layers = model isa TDChain ? collect(values(model.layers)) : (model isa Lux.Chain ? collect(values(model.layers)) : nothing)
@@ -93,9 +93,14 @@ _lrnde_alg(solver) = solver isa Tsit5 ? Int32(0) : nameof(typeof(solver)) === :V
 
 function lrnde_handle(n::NeuralODE)
     get!(_lrnde_handles, n) do
-        if lrnde_field_shape(n.model) === nothing   # any other Dense chain: the Dense-chain handle (Tsit5 only)
+        if lrnde_field_shape(n.model) === nothing   # any other Dense chain: the Dense-chain handle
             desc = lrnde_chain_shape(n.model)   # beyond the small handle's width / weight-image limits: the wide handle
-            return LRNDEBackend.chain_is_small(desc) ? LRNDEBackend.create_chain(desc) : LRNDEBackend.create_wide_chain(desc)
+            LRNDEBackend.chain_is_small(desc) || return LRNDEBackend.create_wide_chain(desc)   # Tsit5 only (lrnde_supported)
+            cctx = LRNDEBackend.create_chain(desc)
+            # VCAB3 / VCABM3: one launch per attempted step (csrc/lrnde_chain_adams.hpp); UPSTREAM-RECALL, parity unpinned;
+            # the reversed solve of the pullback stays Tsit5
+            LRNDEBackend.set_solver!(cctx, _lrnde_alg(n.solver))
+            return cctx
         end
         D, H, td, act = lrnde_field_shape(n.model)
         ctx = LRNDEBackend.create(D, H, td, act)
@@ -106,7 +111,8 @@ end
 
 lrnde_supported(n::NeuralODE, x) = _lrnde_alg(n.solver) !== nothing &&
                                    (lrnde_field_shape(n.model) !== nothing ||
-                                    (_lrnde_alg(n.solver) == 0 && lrnde_chain_shape(n.model) !== nothing)) &&
+                                    (lrnde_chain_shape(n.model) !== nothing &&
+                                     (_lrnde_alg(n.solver) == 0 || LRNDEBackend.chain_is_small(lrnde_chain_shape(n.model))))) &&
                                    nameof(typeof(x)) === :ROCArray && eltype(x) === Float32
 
 _lrnde_opts(n::NeuralODE) = SolveOpts(Float32(get(n.kwargs, :abstol, 1f-6)), Float32(get(n.kwargs, :reltol, 1f-3)),

@@ -19,6 +19,9 @@
 // (lrnde_node_backward_recorded).  Deviation, stated: the reversed solve is the handle's Tsit5 adjoint whatever the forward's
 // method was; the reference would hand n.solver to the adjoint problem too.
 //
+// Serves the MLP handle.  An unsharded small Dense-chain handle runs the same arithmetic as one launch per attempted step
+// (lrnde_chain_adams.hpp) and comes here only under LRNDE_ADAMS_HOST=1, the same-bits comparison path (this loop calls
+// lrnde_rhs, vec_axpy, vec_norm and the record writers, none of which knows the field).  The wide handle is Tsit5 only.
 // Host-driven: per attempted step one fused elementwise launch before the evaluation, one after it (which also leaves the
 // error norm's 256 block sums), the evaluation itself (k_rhs_q / k_rhs), and one read-back — the secondary solver of the
 // layer, not the metric's path.  Arithmetic: operation for operation what the CPU oracle's adams_solve does (tests/test_gpu_adams.py: equal bits).

@@ -849,10 +849,11 @@ __device__ __forceinline__ float init_dt0(const double s[3], double n, float dtm
   return initdt_dt0(rms_from(s[0], n), rms_from(s[1], n), dtmax);
 }
 
-__device__ __forceinline__ float init_dt_final3(const Sum3& r1, const Sum3& r2, double n, float dtmax) {
+// order: the method's (5 Tsit5, 3 VCAB3 / VCABM3)
+__device__ __forceinline__ float init_dt_final3(const Sum3& r1, const Sum3& r2, double n, float dtmax, float order) {
   const float d1 = rms_from(r1.b, n);
   const float dt0 = initdt_dt0(rms_from(r1.a, n), d1, dtmax);
-  return initdt_tail(dt0, d1, rms_from(r2.a, n), 5.0f, dtmax);
+  return initdt_tail(dt0, d1, rms_from(r2.a, n), order, dtmax);
 }
 
 // Progress of a solve, for the host loop that keeps the stream fed (lrnde_solve): ONE 64-bit store per launch into
@@ -940,7 +941,7 @@ __device__ __forceinline__ void step_prologue(const StepArgs& a_, int j, Bcast* 
     if (a.mode != MODE_SINGLE_GIVEN_DT) {
       const Sum3 r1 = reduce_partials3(a.pinit_recv, a.nwg_global);
       const Sum3 r2 = reduce_partials3(a.pinit_recv + (size_t)a.nwg_global * PSTRIDE, a.nwg_global);
-      dt = init_dt_final3(r1, r2, a.n_global, dtmax);
+      dt = init_dt_final3(r1, r2, a.n_global, dtmax, 5.0f);
       c.nf = 3;  // initdt: 2 f-evals, initialize!: fsalfirst
     }
     c.dt_init = dt;
@@ -1522,6 +1523,7 @@ template <int W> __global__ __launch_bounds__(NT) void k_sde_rkmil(StepArgs a) {
 #include "lrnde_adjoint.hpp"
 #include "lrnde_backward.hpp"
 #include "lrnde_chain.hpp"
+#include "lrnde_chain_adams.hpp"
 #include "lrnde_wide_chain.hpp"
 #include "lrnde_chain_adjoint.hpp"
 #include "lrnde_chain_discrete.hpp"
@@ -1773,7 +1775,9 @@ struct lrnde_ctx {
   // 4 the small chain's discrete sweep, 5 the wide chain's discrete sweep), the kernels it
   // enqueued and the waits the host made with nothing enqueued behind them
   int adj_kind = 0, adj_launches = 0, adj_waits = 0;
-  int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp)
+  int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp; a small
+                             // Dense-chain handle: lrnde_chain_adams.hpp)
+  DevBuf<float> adams_hh;    // k_adams_chain: the last two accepted step sizes, per launch parity
   bool hung = false;         // a host loop waited LRNDE_SPIN_DEADLINE_S for a report while the queue stayed busy: only lrnde_destroy is safe
   bool reports_off = false;  // lrnde_set_reports(ctx, 0): the solve loop polls by copies (its fall-back when no report arrives)
   // lrnde_set_adjoint_trace: per-attempt (s, dt, EEst, accepted) rows of the next adjoint solves, host memory of the caller
@@ -1789,14 +1793,14 @@ namespace {
 // path in the same process as the default one and holds the two to the same bits.
 enum {
   OPT_NO_QTILE, OPT_QTILE_MAX_B, OPT_NO_FUSE, OPT_DENSE_COPY, OPT_NO_OVERLAP, OPT_NO_SDE_FAST, OPT_SDE_HOST_LOOP, OPT_NO_QVJP,
-  OPT_ADJ_ERR_ONE_LAUNCH, OPT_ADJ_MU_FOLD, OPT_ADJ_OVERLAP, OPT_ADJ_HOST, OPT_VJP_QCOLS, OPT_PGRAD_TS, OPT_ADJ_NO_REUSE, OPT_NO_SDE_BWD_FUSED, OPT_SDE_NO_PERSIST, OPT_SDE_COOP_LAUNCH, OPT_SDE_PERSIST_STALL, OPT_SDE_HOST_INITDT, OPT_SDE_BWD_LDSACC, OPT_SDE_BWD_NO_DEFER, OPT_SDE_BWD_NO_RESIDENT, OPT_SDE_NO_MARCH, OPT_FEED_T, OPT_FEED_E, OPT_FEED_M, OPT_GATHER_TILES, OPT_FORCE_COMM, OPT_WIDE_VJP_CHUNK, N_OPT
+  OPT_ADJ_ERR_ONE_LAUNCH, OPT_ADJ_MU_FOLD, OPT_ADJ_OVERLAP, OPT_ADJ_HOST, OPT_VJP_QCOLS, OPT_PGRAD_TS, OPT_ADJ_NO_REUSE, OPT_NO_SDE_BWD_FUSED, OPT_SDE_NO_PERSIST, OPT_SDE_COOP_LAUNCH, OPT_SDE_PERSIST_STALL, OPT_SDE_HOST_INITDT, OPT_SDE_BWD_LDSACC, OPT_SDE_BWD_NO_DEFER, OPT_SDE_BWD_NO_RESIDENT, OPT_SDE_NO_MARCH, OPT_FEED_T, OPT_FEED_E, OPT_FEED_M, OPT_GATHER_TILES, OPT_FORCE_COMM, OPT_WIDE_VJP_CHUNK, OPT_ADAMS_HOST, N_OPT
 };
 struct OptDef { const char* name; int dflt; bool flag; };   // flag: present in the environment = 1
 const OptDef g_optdef[N_OPT] = {
     {"LRNDE_NO_QTILE", 0, true}, {"LRNDE_QTILE_MAX_B", 2048, false}, {"LRNDE_NO_FUSE", 0, true}, {"LRNDE_DENSE_COPY", 0, true},
     {"LRNDE_NO_OVERLAP", 0, true}, {"LRNDE_NO_SDE_FAST", 0, true}, {"LRNDE_SDE_HOST_LOOP", 0, true}, {"LRNDE_NO_QVJP", 0, true},
     {"LRNDE_ADJ_ERR_ONE_LAUNCH", 0, true}, {"LRNDE_ADJ_MU_FOLD", 0, true}, {"LRNDE_ADJ_OVERLAP", 0, false}, {"LRNDE_ADJ_HOST", 0, true}, {"LRNDE_VJP_QCOLS", 4, false}, {"LRNDE_PGRAD_TS", 0, false}, {"LRNDE_ADJ_NO_REUSE", 0, true}, {"LRNDE_NO_SDE_BWD_FUSED", 0, true}, {"LRNDE_SDE_NO_PERSIST", 0, true}, {"LRNDE_SDE_COOP_LAUNCH", 0, true}, {"LRNDE_SDE_PERSIST_STALL", 0, true}, {"LRNDE_SDE_HOST_INITDT", 0, true}, {"LRNDE_SDE_BWD_LDSACC", 0, true}, {"LRNDE_SDE_BWD_NO_DEFER", 0, true}, {"LRNDE_SDE_BWD_NO_RESIDENT", 0, true}, {"LRNDE_SDE_NO_MARCH", 0, true}, {"LRNDE_FEED_T", 3, false}, {"LRNDE_FEED_E", 1, false},
-    {"LRNDE_FEED_M", 2, false}, {"LRNDE_GATHER_TILES", 0, true}, {"LRNDE_FORCE_COMM", 0, true}, {"LRNDE_WIDE_VJP_CHUNK", 0, false}};
+    {"LRNDE_FEED_M", 2, false}, {"LRNDE_GATHER_TILES", 0, true}, {"LRNDE_FORCE_COMM", 0, true}, {"LRNDE_WIDE_VJP_CHUNK", 0, false}, {"LRNDE_ADAMS_HOST", 0, true}};
 int g_opt[N_OPT];
 bool g_opt_set[N_OPT];     // set by the hook: the environment no longer counts
 std::once_flag g_opt_once;
@@ -1942,6 +1946,16 @@ int launch_step(lrnde_ctx* c, int B, const StepArgs& a, int j, bool spec = false
     HIPCHK(c, hipGetLastError());
     return LRNDE_OK;
   }
+  if (c->field == 1 && c->solver_alg != 0 && a.mode == MODE_SOLVE) {  // VCAB3 / VCABM3 (solve_impl sends every other Adams solve to adams_solve)
+    const int nwg = (B + CNB - 1) / CNB;
+    const size_t sm = adams_chain_smem_bytes(c->cd.wfloats);
+    AdamsChainArgs aa{};
+    aa.hh = c->adams_hh; aa.moulton = c->solver_alg == 2 ? 1 : 0;
+    if (spec) hipLaunchKernelGGL(k_adams_chain<true>, dim3(nwg), dim3(NT), sm, c->stream, a, c->cd, aa, j);
+    else hipLaunchKernelGGL(k_adams_chain<false>, dim3(nwg), dim3(NT), sm, c->stream, a, c->cd, aa, j);
+    HIPCHK(c, hipGetLastError());
+    return LRNDE_OK;
+  }
   if (c->field) {
     const int nwg = (B + CNB - 1) / CNB;
     const size_t sm = chain_smem_bytes(c->cd.wfloats);
@@ -2053,6 +2067,8 @@ int set_smem_attr() {
   hipFuncSetAttribute((const void*)k_sde_rkmil<1>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_step_chain<false>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_step_chain<true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_adams_chain<false>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
+  hipFuncSetAttribute((const void*)k_adams_chain<true>, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_init1_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_init2_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
   hipFuncSetAttribute((const void*)k_rhs_chain, hipFuncAttributeMaxDynamicSharedMemorySize, maxb);
@@ -2402,7 +2418,11 @@ int lrnde_set_params(lrnde_ctx* c, const float* p, size_t n) {
 int lrnde_set_solver(lrnde_ctx* c, int32_t alg) {
   if (!c) return LRNDE_BADARG;
   if (alg < 0 || alg > 2) return fail(c, LRNDE_BADARG, "solver must be 0 (Tsit5), 1 (VCAB3) or 2 (VCABM3)");
-  if (c->field && alg != 0) return fail(c, LRNDE_UNSUPPORTED, "VCAB3 / VCABM3 are built for the MLP field's handle: a Dense-chain handle solves with Tsit5 only");
+  if (c->field == 2 && alg != 0)
+    return fail(c, LRNDE_UNSUPPORTED, "VCAB3 / VCABM3 are built for the MLP field's handle and the small Dense-chain handle: a wide Dense-chain handle solves with Tsit5 only");
+  // the small chain's discrete adjoint walks a Tsit5 stage record (whichever of the two is set second is refused)
+  if (alg != 0 && c->sensealg == LRNDE_SENSE_DISCRETE)
+    return fail(c, LRNDE_UNSUPPORTED, "VCAB3 / VCABM3 leave no Tsit5 stage record: the handle's discrete adjoint needs solver 0 (Tsit5)");
   c->solver_alg = alg;
   c->rec.invalidate();
   return LRNDE_OK;
@@ -2534,7 +2554,11 @@ static int solve_impl(lrnde_ctx* c, const float* u0, int32_t B, float t0, float 
   if (cap_saved > 0 && !u_saved) return fail(c, LRNDE_BADARG, "null save buffer");
   if ((rc = ensure_workspace(c, B))) return rc;
   if (!c->dense_on) c->rec.invalidate();
-  if (c->solver_alg != 0)   // n.solver = VCAB3() / VCABM3() (experiments/src/construct.jl:154-164)
+  // n.solver = VCAB3() / VCABM3() (experiments/src/construct.jl:154-164): host-driven (lrnde_adams.hpp), but for an unsharded
+  // small Dense-chain handle, whose step launches below are k_adams_chain (LRNDE_ADAMS_HOST=1: the host loop there too)
+  const bool adams_dev = c->solver_alg != 0 && c->field == 1 && !sharded(c) && !opt(OPT_ADAMS_HOST);
+  if (adams_dev) HIPCHK(c, c->adams_hh.once(4));
+  if (c->solver_alg != 0 && !adams_dev)
     return adams_solve(c, u0, B, t0, t1, o, saveat_host, nsave, u_saved, t_saved_host, cap_saved, st, trace_host, cap_trace, side);
   const size_t n = (size_t)B * c->desc.state_dim;
   HIPCHK(c, c->saveat_dev.grow(nsave));
@@ -5215,6 +5239,8 @@ int lrnde_set_sensealg(lrnde_ctx* c, int32_t alg) {
   if (!c) return LRNDE_BADARG;
   if (alg != LRNDE_SENSE_INTERPOLATING && alg != LRNDE_SENSE_DISCRETE)
     return fail(c, LRNDE_BADARG, "sensealg %d (0 interpolating adjoint, 1 discrete adjoint)", alg);
+  if (alg == LRNDE_SENSE_DISCRETE && c->solver_alg != 0)
+    return fail(c, LRNDE_UNSUPPORTED, "the discrete adjoint walks a Tsit5 stage record: the handle's solver is VCAB3 / VCABM3 (lrnde_set_solver)");
   if (alg == LRNDE_SENSE_DISCRETE && (c->field != 1 || sharded(c)))
     return fail(c, LRNDE_UNSUPPORTED, "the discrete adjoint is built for the small Dense-chain handle (lrnde_create_chain), unsharded");
   c->sensealg = alg;

@@ -259,7 +259,9 @@ class Handle:
         self._chk(L.lib.lrnde_set_params(self._ctx, C.c_void_p(ps.data_ptr()), ps.numel()))
 
     def set_solver(self, solver):
-        """n.solver of the layer's global solve (experiments/src/construct.jl:154-164): "tsit5" | "vcab3" | "vcabm3"."""
+        """n.solver of the layer's global solve (experiments/src/construct.jl:154-164): "tsit5" | "vcab3" | "vcabm3" — on the
+        MLP handle and the small Dense-chain handle; refused (LRNDE_UNSUPPORTED) by the wide handle, and beside the small
+        chain's discrete adjoint, which walks a Tsit5 stage record."""
         self._chk(L.lib.lrnde_set_solver(self._ctx, SOLVERS[_solver_name(solver)]))
 
     def rhs(self, u, t):
@@ -625,8 +627,15 @@ class NeuralODE:
         if field in ("dense_chain", "wide_chain"):
             self._conv = None
             self.desc = _chain_desc(model) if field == "dense_chain" else _wide_chain_desc(model)
+            # The `solver` keyword stays closed for the chain fields.  A small Dense-chain handle itself takes VCAB3 / VCABM3
+            # (csrc/lrnde_chain_adams.hpp, one launch per attempted step): `node.handle().set_solver("vcab3")` on a layer
+            # built with the default solver; every call of the layer then solves with it.  The wide handle is Tsit5 only.
+            if self.solver != "tsit5" and field == "wide_chain":
+                raise NotImplementedError("VCAB3 / VCABM3 are built for the MLP field's handle and the small Dense-chain handle; "
+                                          "a field='wide_chain' layer solves with Tsit5 only")
             if self.solver != "tsit5":
-                raise NotImplementedError("VCAB3 / VCABM3 are built for the MLP field's handle (csrc/lrnde_adams.hpp)")
+                raise NotImplementedError("the solver keyword is built for the MLP field; a field='dense_chain' layer takes "
+                                          "VCAB3 / VCABM3 on its handle: node.handle().set_solver(...) (csrc/lrnde_chain_adams.hpp)")
             self._handle = None
             self._bound = False
             return

@@ -12,7 +12,13 @@ attempt and host waits.  LRNDE_ADJ_HOST=1 in the environment selects the host-co
 --sensealg TrackerAdjoint (or ReverseDiffAdjoint / discrete) builds the layers with the discrete adjoint (one launch over
 the record); the default is the continuous adjoint.
 
-    python tools/bench/chain_bench.py [--reps 5] [--B 512] [--bwd-reps 30] [--sensealg TrackerAdjoint]
+--solver vcab3 | vcabm3 runs every leg with that global solver (one launch per attempted step, csrc/lrnde_chain_adams.hpp);
+--adams-host adds LRNDE_ADAMS_HOST=1, the host-driven loop.  --solver-sweep prints the table of DESIGN.md 4.8.1 instead:
+Tsit5, VCAB3 and VCABM3 on the device loop and both Adams methods under the switch, at tolerance 1e-3 with the 49-point
+series and at 1.4e-8 with the 4-point one (profiles/chain_adams/).
+
+    python tools/bench/chain_bench.py [--reps 5] [--B 512] [--bwd-reps 30] [--sensealg TrackerAdjoint] [--solver vcab3] [--adams-host]
+    python tools/bench/chain_bench.py --solver-sweep [--reps 5]
     rocprofv3 --kernel-trace --stats -- python tools/bench/chain_bench.py      (us per k_step_chain launch)
 """
 import argparse
@@ -31,6 +37,7 @@ import torch  # noqa: E402
 import lrnde_amd as P  # noqa: E402
 
 TOL = 1.4e-8
+MAXITERS = 20000   # of the --solver-sweep legs: a leg that does not finish within it is reported with its retcode, not timed
 SAVEAT = [0.25, 0.5, 0.75, 1.0]
 C = [0.161, 0.327, 0.9, 0.9800255409045097, 1.0, 1.0]
 A = [[0.161], [-0.008480655492356989, 0.335480655492357], [2.8971530571054935, -6.359448489975075, 4.3622954328695815],
@@ -113,12 +120,67 @@ def pullback_leg(node, h, xd, ps, st, times, B, reps):
                 host_waits=ai["host_waits"] if ai else None)
 
 
+def solver_leg(model, xd, ps, B, solver, adams_host, tol, times, reps):
+    """one solver on one (tolerance, series): attempts and f-evals per pass, us per attempted step from the solve's own
+    event bracket (lrnde_last_solve_kernel_ms), the layer forward and forward + series pullback in ms (median, min, max)"""
+    P.set_option("LRNDE_ADAMS_HOST", 1 if adams_host else 0)
+    try:
+        node = P.NeuralODE(model, regularize="unbiased", abstol=tol, reltol=tol, saveat=times, save_start=False,
+                           maxiters=MAXITERS, field="dense_chain")
+        node.handle().set_solver(solver)   # (the layer's solver keyword is closed for chain fields: the handle's setter)
+        st = node.initialstates(np.random.default_rng(0))
+        cots = torch.from_numpy(np.random.default_rng(1).standard_normal((len(times), B, 20)).astype(np.float32)).cuda()
+        h = node._bind(ps)
+        r = h.solve(xd, 0.0, 1.0, tol, tol, saveat=times, maxiters=MAXITERS, raise_on_retcode=False)
+        if r["retcode"] != 0:   # (a float32 error estimate can stall an order-3 method far below its tolerance floor)
+            return dict(solver=solver, loop="host" if adams_host else "device", tol=tol, ntimes=len(times), retcode=r["retcode"],
+                        attempts=r["stats"]["naccept"] + r["stats"]["nreject"], t_final=float(r["stats"]["t_final"]))
+        h.last_solve_kernel_ms()
+        per, launches = [], 0
+        for _ in range(reps):
+            r = h.solve(xd, 0.0, 1.0, tol, tol, saveat=times, maxiters=MAXITERS)
+            ms, launches = h.last_solve_kernel_ms()
+            per.append(1e3 * ms / max(r["stats"]["naccept"] + r["stats"]["nreject"], 1))
+        fwd, fb = [], []
+        for i in range(reps + 2):
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            node(xd, ps, st)
+            torch.cuda.synchronize(); t1 = time.perf_counter()
+            node.pullback(xd, ps, st, cots, w_reg=10.0)
+            torch.cuda.synchronize(); t2 = time.perf_counter()
+            if i >= 2:
+                fwd.append((t1 - t0) * 1e3); fb.append((t2 - t1) * 1e3)
+    finally:
+        P.set_option("LRNDE_ADAMS_HOST", 0)
+    mmm = lambda v, nd=3: dict(median=round(statistics.median(v), nd), min=round(min(v), nd), max=round(max(v), nd))
+    attempts = r["stats"]["naccept"] + r["stats"]["nreject"]
+    # (the host loop's solve is not bracketed by events: its us per attempt comes from the forward's wall time instead)
+    return dict(solver=solver, loop="host" if adams_host else ("device" if solver != "tsit5" else "tsit5"), tol=tol, ntimes=len(times),
+                attempts=attempts, naccept=r["stats"]["naccept"], nreject=r["stats"]["nreject"], nf=r["stats"]["nf"],
+                step_launches=launches, us_per_attempt=None if adams_host else mmm(per, 2),
+                layer_forward_ms=mmm(fwd), forward_us_per_attempt=round(1e3 * statistics.median(fwd) / max(attempts, 1), 2),
+                forward_series_pullback_ms=mmm(fb))
+
+
+def solver_sweep(args, model, xd, ps, B):
+    """Tsit5 against VCAB3 / VCABM3 on the device loop and under LRNDE_ADAMS_HOST=1, at the experiment's tolerance with its
+    49-point series and at 1.4e-8 with the 4-point series: one JSON line"""
+    rows = []
+    for tol, times in ((1e-3, [(i + 1) / 49.0 for i in range(49)]), (TOL, SAVEAT)):
+        for solver, host in (("tsit5", False), ("vcab3", False), ("vcabm3", False), ("vcab3", True), ("vcabm3", True)):
+            rows.append(solver_leg(model, xd, ps, B, solver, host, tol, times, args.reps))
+    print(json.dumps(dict(workload="physionet_gen_dynamics_solvers", B=B, reps=args.reps, legs=rows)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--bwd-reps", type=int, default=30)
     ap.add_argument("--B", type=int, default=512)
     ap.add_argument("--sensealg", default=None)
+    ap.add_argument("--solver", default="tsit5", help="tsit5 | vcab3 | vcabm3: the layer's global solver in every leg")
+    ap.add_argument("--adams-host", action="store_true", help="LRNDE_ADAMS_HOST=1: the host-driven Adams loop (the 'before' leg)")
+    ap.add_argument("--solver-sweep", action="store_true", help="the Tsit5 / VCAB3 / VCABM3 table of DESIGN.md 4.8.1 instead")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     B = args.B
@@ -126,8 +188,13 @@ def main():
     p = P.glorot_chain_params(model, seed=0)
     x = (np.random.default_rng(2).random((B, 20), dtype=np.float32) - np.float32(0.5)) * np.float32(2)
     xd, ps = torch.from_numpy(x).cuda(), torch.from_numpy(p).cuda()
+    if args.solver_sweep:
+        return solver_sweep(args, model, xd, ps, B)
+    if args.adams_host:
+        P.set_option("LRNDE_ADAMS_HOST", 1)
     node = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, saveat=SAVEAT, save_start=False, maxiters=100000,
                        field="dense_chain", sensealg=args.sensealg)
+    node.handle().set_solver(args.solver)
     st = node.initialstates(np.random.default_rng(0))
     cots = torch.from_numpy(np.random.default_rng(1).standard_normal((len(SAVEAT), B, 20)).astype(np.float32)).cuda()
     h = node._bind(ps)
@@ -150,6 +217,7 @@ def main():
     for times in (SAVEAT, [(i + 1) / 49.0 for i in range(49)]):
         nd = P.NeuralODE(model, regularize="unbiased", abstol=TOL, reltol=TOL, saveat=times, save_start=False, maxiters=100000,
                          field="dense_chain", sensealg=args.sensealg)
+        nd.handle().set_solver(args.solver)
         legs.append(pullback_leg(nd, nd._bind(ps), xd, ps, st, times, B, args.bwd_reps))
     Ws, o = [], 0
     for l in model.layers[1:]:
