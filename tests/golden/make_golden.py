@@ -63,3 +63,9 @@ np.savez_compressed(os.path.join(HERE, "mnist_sde_b16.npz"), p_drift=pds, p_diff
                     tableau=tab, eh_u=eh["u"], eh_eest=eh["eest"], eh_reg=eh["reg_val"], rk_u=rk["u"], rk_eest=rk["eest"],
                     rk_reg=rk["reg_val"], sri_u=sr["u"], sri_eest=sr["eest"], sri_reg=sr["reg_val"])
 print("wrote", os.path.getsize(os.path.join(HERE, "mnist_sde_b16.npz")), "bytes")
+
+# ---- float64 RK4 autograd references of the record-growth pullback tests (tests/record_growth_cases.py) ----
+sys.path[:0] = [os.path.join(HERE, "..", ".."), os.path.join(HERE, "..")]
+import record_growth_cases as G  # noqa: E402
+
+print("wrote", os.path.getsize(G.write_golden()), "bytes")
