@@ -53,10 +53,7 @@ struct ChAdjArgs {
 
 enum { CHADJ_STEP = 0, CHADJ_INIT_A = 1, CHADJ_INIT_B = 2 };
 constexpr int CHADJ_MU_NT = 7 * 64;          // k_chadj_mu: wave w sums slot w
-constexpr int CHADJ_MAX_WG = 4096;           // workgroups whose norm partials one wave sums per attempt
-constexpr int CHADJ_MAX_MU_BLOCKS = 256;
-constexpr size_t CHADJ_LDS_MAX = 160 * 1024;
-constexpr size_t CHADJ_SCRATCH_MAX = (size_t)256 << 20;   // bytes of gpart
+// (CHADJ_MAX_WG, CHADJ_MAX_MU_BLOCKS, CHADJ_LDS_MAX, CHADJ_SCRATCH_MAX: the gate's limits, lrnde_adj_route.hpp)
 
 __device__ __forceinline__ double* chadj_set(const ChAdjArgs& a, int set) { return a.dpart + (size_t)set * a.np; }
 
@@ -156,9 +153,8 @@ __device__ __forceinline__ ChAdjCtrl chadj_init_ctrl(const ChAdjArgs& a, int mod
 }
 
 struct ChAdjSmem { float* w; const float* wg; float* v; double* red; ChAdjCtrl* bc; };
-static size_t chadj_smem_bytes(int wfloats, int gfloats_lds, size_t vjp_lds) {
-  return ((size_t)wfloats + (size_t)((gfloats_lds + 3) & ~3)) * sizeof(float) + vjp_lds + NW * 3 * sizeof(double) + sizeof(ChAdjCtrl) + 32;
-}
+// dynamic LDS: chain_lds_bytes (lrnde_adj_route.hpp) with this tail behind the images and the record
+constexpr size_t CHADJ_LDS_TAIL = NW * 3 * sizeof(double) + sizeof(ChAdjCtrl) + 32;
 
 // One element of the tile enters the VJP once its y is known: a_0 = act0(y), act0'(y) and the cotangent lam of f at its LDS
 // slot (the element's thread; a barrier follows in chadj_eval_tail)

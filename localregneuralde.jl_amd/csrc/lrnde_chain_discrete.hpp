@@ -49,9 +49,8 @@ struct ChDiscArgs {
   int p_lds;             // the workgroup's parameter partial lives in LDS until the end
 };
 
-static size_t chdisc_smem_bytes(int wfloats, int gfloats_lds, size_t vjp_lds, size_t pfloats_lds) {
-  return ((size_t)wfloats + (size_t)((gfloats_lds + 3) & ~3) + ((pfloats_lds + 3) & ~(size_t)3)) * sizeof(float) + vjp_lds + 32;
-}
+// dynamic LDS: chain_lds_bytes (lrnde_adj_route.hpp) with this tail behind the images, the record and the partial
+constexpr size_t CHDISC_LDS_TAIL = 32;
 
 // the series times by value, up to 64 per launch: no copy from pageable host memory sits in front of the sweep
 struct ChDiscBegin { float* dst; int off, n; float v[64]; };

@@ -48,7 +48,8 @@
 #include "lrnde_math.hpp"
 #include "lrnde_stepctl.hpp"
 #include "lrnde_layer_plan.hpp"
-#include "lrnde_qsched.hpp"     // the compile-time issue schedule of the 4-column kernels' weight stream
+#include "lrnde_adj_route.hpp"  // AdjRoute, AdjPlan, adj_route: which way the recorded backward runs the reversed solve
+#include "lrnde_qsched.hpp"    // the compile-time issue schedule of the 4-column kernels' weight stream
 #include "lrnde_report.hpp"
 #include "lrnde_buf.hpp"
 #include "lrnde_comm.hpp"
@@ -1771,10 +1772,9 @@ struct lrnde_ctx {
   // parameter partials share cha_gpart
   int sensealg = LRNDE_SENSE_INTERPOLATING;   // lrnde_set_sensealg
   DevBuf<float> chd_ser;
-  // lrnde_last_adjoint_info: which loop ran the last reversed solve (0 host, 1 MLP device, 2 chain device, 3 wide-chain device,
-  // 4 the small chain's discrete sweep, 5 the wide chain's discrete sweep), the kernels it
-  // enqueued and the waits the host made with nothing enqueued behind them
-  int adj_kind = 0, adj_launches = 0, adj_waits = 0;
+  // lrnde_last_adjoint_info: which route ran the last reversed solve (an lrnde::AdjRoute, lrnde_adj_route.hpp), the kernels
+  // it enqueued and the waits the host made with nothing enqueued behind them
+  int adj_kind = lrnde::ADJ_ROUTE_HOST, adj_launches = 0, adj_waits = 0;
   int solver_alg = 0;        // lrnde_set_solver: 0 Tsit5 (k_step_q / k_step), 1 VCAB3, 2 VCABM3 (lrnde_adams.hpp; a small
                              // Dense-chain handle: lrnde_chain_adams.hpp)
   DevBuf<float> adams_hh;    // k_adams_chain: the last two accepted step sizes, per launch parity
@@ -4417,67 +4417,27 @@ int adj_solve_device(lrnde_ctx* c, AdjVec& v, int B, float s0, float s1, float a
   return adj_finish(c, v, fin, extra_nf, at_end, st);
 }
 
-// ---- the chain handle's adjoint solve with the controller on the device (lrnde_chain_adjoint.hpp) -----------------
-// The gate, stated once: the step kernel's LDS (forward image + activation record + reduction scratch; the backward image
-// rides along when it fits too) within CHADJ_LDS_MAX, at most CHADJ_MAX_WG workgroups, and the per-(stage, workgroup)
-// parameter cotangents (7 x workgroups x P floats) within CHADJ_SCRATCH_MAX.  Outside it the host loop runs.
-struct ChAdjPlan { int nwg, nmu, wg_lds; size_t lds; };
-bool chadj_fits(const lrnde_ctx* c, int B, ChAdjPlan* pl) {
-  if (c->field != 1) return false;   // (a wide chain's device loop has its own gate, wadj_fits, and is opt-in)
-  const size_t P = param_count(c);
-  const int nwg = (B + CNB - 1) / CNB;
-  const size_t lds0 = chadj_smem_bytes(c->cd.wfloats, 0, c->ch_vjp_lds);
-  const size_t lds1 = chadj_smem_bytes(c->cd.wfloats, c->ch_gfloats, c->ch_vjp_lds);
-  if (lds0 > CHADJ_LDS_MAX || nwg > CHADJ_MAX_WG) return false;
-  if (7 * (size_t)nwg * P * sizeof(float) > CHADJ_SCRATCH_MAX) return false;
-  if (pl) {
-    pl->nwg = nwg;
-    pl->nmu = (int)std::min<size_t>((P + 63) / 64, CHADJ_MAX_MU_BLOCKS);
-    pl->wg_lds = lds1 <= CHADJ_LDS_MAX ? 1 : 0;
-    pl->lds = pl->wg_lds ? lds1 : lds0;
+// ---- the route of a recorded backward (lrnde_adj_route.hpp: the precedence, the four gates, the plan) ------------------
+// adj_route's inputs of a handle at batch B; dev: what the device headers own of the gates' arithmetic
+AdjRouteIn adj_route_in(const lrnde_ctx* c, int B) {
+  AdjRouteIn in;
+  AdjDevSizes& d = in.dev;
+  d.chain_tile = CNB; d.wide_tile = NB; d.mu_block = WADJ_MB; d.wadj_slots = WADJ_SLOTS; d.wdisc_slots = WDISC_SLOTS; d.wdisc_vecs = WDISC_VECS;
+  d.ctrl_bytes = sizeof(ChAdjCtrl); d.chadj_tail = CHADJ_LDS_TAIL; d.chdisc_tail = CHDISC_LDS_TAIL; d.wide_tail = WIDE_LDS_TAIL; d.wadj_tail = WADJ_LDS_TAIL;
+  in.field = c->field; in.adj_loop = c->adj_loop; in.sensealg = c->sensealg;
+  in.sharded = sharded(c); in.adj_host = opt(OPT_ADJ_HOST) != 0; in.qvjp = vjp_uses_qtile(c, B);
+  in.B = B; in.D = c->desc.state_dim; in.P = param_count(c);
+  if (c->field == 1) { in.wfloats = c->cd.wfloats; in.gfloats = c->ch_gfloats; in.vjp_lds = c->ch_vjp_lds; }
+  if (c->field == 2) {
+    in.bufw = c->wd.bufw; in.partcap = c->wd.partcap; in.recfloats = c->wd.recfloats;
+    in.dims.assign(c->chain.dims, c->chain.dims + c->chain.nlayers + 1);
   }
-  return true;
+  return in;
 }
 
-// ---- the small chain handle's discrete adjoint as one launch over the step record (lrnde_chain_discrete.hpp) ----------
-// The gate, stated once: a small-chain handle, not sharded; the sweep's LDS (forward image + activation record; the backward
-// image and then the workgroup's parameter partial ride along when they fit too) within CHADJ_LDS_MAX, at most CHADJ_MAX_WG
-// workgroups, and the per-workgroup parameter partials (workgroups x P floats) within CHADJ_SCRATCH_MAX.  Outside it the call
-// is refused (why: the limit missed); the continuous adjoint is never run in its place.
-struct ChDiscPlan { int nwg, wg_lds, p_lds; size_t lds; };
-bool chdisc_fits(const lrnde_ctx* c, int B, ChDiscPlan* pl, std::string* why) {
-  char msg[200];
-  auto no = [&](void) { if (why) *why = msg; return false; };
-  if (c->field != 1) { snprintf(msg, sizeof msg, "not a small Dense-chain handle"); return no(); }
-  if (sharded(c)) { snprintf(msg, sizeof msg, "the handle is sharded"); return no(); }
-  const size_t P = param_count(c);
-  const int nwg = (B + CNB - 1) / CNB;
-  const size_t lds0 = chdisc_smem_bytes(c->cd.wfloats, 0, c->ch_vjp_lds, 0);
-  const size_t lds1 = chdisc_smem_bytes(c->cd.wfloats, c->ch_gfloats, c->ch_vjp_lds, 0);
-  const size_t lds2 = chdisc_smem_bytes(c->cd.wfloats, c->ch_gfloats, c->ch_vjp_lds, P);
-  if (lds0 > CHADJ_LDS_MAX) { snprintf(msg, sizeof msg, "the sweep needs %zu bytes of LDS, CHADJ_LDS_MAX is %zu", lds0, CHADJ_LDS_MAX); return no(); }
-  if (nwg > CHADJ_MAX_WG) { snprintf(msg, sizeof msg, "B = %d is %d workgroups, CHADJ_MAX_WG is %d", B, nwg, CHADJ_MAX_WG); return no(); }
-  if ((size_t)nwg * P * sizeof(float) > CHADJ_SCRATCH_MAX) {
-    snprintf(msg, sizeof msg, "B = %d needs %zu bytes of parameter partials, CHADJ_SCRATCH_MAX is %zu", B, (size_t)nwg * P * sizeof(float), CHADJ_SCRATCH_MAX);
-    return no();
-  }
-  if (pl) {
-    pl->nwg = nwg;
-    pl->wg_lds = lds1 <= CHADJ_LDS_MAX ? 1 : 0;
-    pl->p_lds = lds2 <= CHADJ_LDS_MAX ? 1 : 0;
-    pl->lds = pl->p_lds ? lds2 : (pl->wg_lds ? lds1 : lds0);
-  }
-  return true;
-}
-
-// Launches: one k_chdisc_begin per 64 series times, the sweep, k_chain_pgsum; the caller adds k_adj_out.  No host wait.
-// lambda(t0) goes to z[0, n), the parameter cotangent to z[n, n + P): where the continuous loops leave them.
-// du: nser cotangents of B*D floats at the times ser (ascending).
-int chdisc_run(lrnde_ctx* c, const ChDiscPlan& pl, AdjVec& v, int B, float t2, const std::vector<float>& ser, const float* du, int nrec,
-               lrnde_stats* st) {
-  memset(st, 0, sizeof(*st));
-  const size_t P = v.P, n = v.n_lam;
-  HIPCHK(c, c->cha_gpart.grow((size_t)pl.nwg * P));
+// ---- the discrete sweeps' shared head and tail (lrnde_chain_discrete.hpp, lrnde_wide_discrete.hpp) --------------------
+// the series times to c->chd_ser by value: one k_chdisc_begin per 64 of them
+int disc_upload_series(lrnde_ctx* c, const std::vector<float>& ser) {
   if (ser.size() > c->chd_ser.size() || !c->chd_ser) HIPCHK(c, c->chd_ser.grow(ser.size() + 64));
   for (size_t off = 0; off < ser.size(); off += 64) {
     ChDiscBegin b{};
@@ -4487,6 +4447,24 @@ int chdisc_run(lrnde_ctx* c, const ChDiscPlan& pl, AdjVec& v, int B, float t2, c
     HIPCHK(c, hipGetLastError());
     ++c->adj_launches;
   }
+  return LRNDE_OK;
+}
+// a sweep walks the nrec recorded steps once: six evaluations a step and the tail's
+void disc_stats(lrnde_stats* st, int nrec) {
+  st->naccept = nrec; st->nreject = 0; st->iters = nrec; st->nf = 6 * nrec + 1; st->retcode = LRNDE_OK;
+}
+
+// ---- the small chain handle's discrete adjoint as one launch over the step record (lrnde_chain_discrete.hpp) ----------
+// Launches: one k_chdisc_begin per 64 series times, the sweep, k_chain_pgsum; the caller adds k_adj_out.  No host wait.
+// lambda(t0) goes to z[0, n), the parameter cotangent to z[n, n + P): where the continuous loops leave them.
+// du: nser cotangents of B*D floats at the times ser (ascending).
+int chdisc_run(lrnde_ctx* c, const AdjPlan& pl, AdjVec& v, int B, float t2, const std::vector<float>& ser, const float* du, int nrec,
+               lrnde_stats* st) {
+  int rc;
+  memset(st, 0, sizeof(*st));
+  const size_t P = v.P, n = v.n_lam;
+  HIPCHK(c, c->cha_gpart.grow((size_t)pl.nwg * P));
+  if ((rc = disc_upload_series(c, ser))) return rc;
   ChDiscArgs a{};
   a.dense = c->dense; a.dense_t = c->dense_t; a.dense_dt = c->dense_dt; a.nrec = nrec; a.n_lam = n;
   a.ser_t = c->chd_ser; a.du = du; a.nser = (int)ser.size(); a.t2 = t2;
@@ -4498,94 +4476,22 @@ int chdisc_run(lrnde_ctx* c, const ChDiscPlan& pl, AdjVec& v, int B, float t2, c
                      pl.nwg, (int)P, v.z + n, 0, (const float*)nullptr, (float*)nullptr);
   HIPCHK(c, hipGetLastError());
   c->adj_launches += 2;
-  st->naccept = nrec; st->nreject = 0; st->iters = nrec; st->nf = 6 * nrec + 1; st->retcode = LRNDE_OK;
+  disc_stats(st, nrec);
   return LRNDE_OK;
 }
 
-// The wide handle's gate, stated once: the step kernel's LDS (the forward kernels' carve, its segment-partial region cut
-// back by what the control block takes) within WIDE_LDS_MAX; at most CHADJ_MAX_WG workgroups; eight stage-record slots
-// for the batch plus the control blocks and the norm partials within WIDE_SCRATCH_MAX.  why (may be null): the limit missed.
-struct WAdjPlan { int nwg, nitems, nmu, partcap; size_t lds, rec_floats; };
-bool wadj_fits(const lrnde_ctx* c, int B, WAdjPlan* pl, std::string* why) {
-  char msg[200];
-  auto no = [&](void) { if (why) *why = msg; return false; };
-  if (c->field != 2) { snprintf(msg, sizeof msg, "not a wide-chain handle"); return no(); }
-  const WideDev& wd = c->wd;
-  const int nwg = (B + NB - 1) / NB;
-  const size_t fixed = wadj_smem_bytes(wd.bufw, 0);
-  const int partcap = fixed > WIDE_LDS_MAX ? 0 : (int)std::min<size_t>((size_t)wd.partcap, ((WIDE_LDS_MAX - fixed) / sizeof(float)) & ~(size_t)255);
-  const size_t lds = wadj_smem_bytes(wd.bufw, partcap);
-  if (lds > WIDE_LDS_MAX) { snprintf(msg, sizeof msg, "the step kernel needs %zu bytes of LDS, WIDE_LDS_MAX is %zu", lds, WIDE_LDS_MAX); return no(); }
-  if (nwg > CHADJ_MAX_WG) { snprintf(msg, sizeof msg, "B = %d is %d workgroups, CHADJ_MAX_WG is %d", B, nwg, CHADJ_MAX_WG); return no(); }
-  int nitems = 0;
-  for (int l = 0; l < c->chain.nlayers; ++l) {
-    const int MT = ceil16(c->chain.dims[l + 1]) / 16, KG = ceil16(c->chain.dims[l]) / 16;
-    nitems += ((MT + WADJ_MB - 1) / WADJ_MB) * ((KG + WADJ_MB - 1) / WADJ_MB) + (c->chain.dims[l + 1] + 63) / 64;
-  }
-  const int nmu = std::min(nitems, CHADJ_MAX_MU_BLOCKS);
-  const size_t rec_floats = (size_t)WADJ_SLOTS * nwg * wd.recfloats;
-  const size_t bytes = rec_floats * sizeof(float) + 2 * sizeof(ChAdjCtrl) + 5 * (size_t)(nwg + nmu) * sizeof(double);
-  if (bytes > WIDE_SCRATCH_MAX) {
-    snprintf(msg, sizeof msg, "B = %d needs %zu bytes of stage records (%d slots), WIDE_SCRATCH_MAX is %zu", B, bytes, WADJ_SLOTS, WIDE_SCRATCH_MAX);
-    return no();
-  }
-  if (pl) { pl->nwg = nwg; pl->nitems = nitems; pl->nmu = nmu; pl->partcap = partcap; pl->lds = lds; pl->rec_floats = rec_floats; }
-  return true;
-}
-
 // ---- the wide handle's discrete adjoint: two launches per recorded step (lrnde_wide_discrete.hpp) ----------------------
-// The gate, stated once: a wide-chain handle, not sharded; the step kernel's LDS (the forward kernels' carve) within
-// WIDE_LDS_MAX; at most CHADJ_MAX_WG tiles; the six stage-record slots plus the sweep's WDISC_VECS B*D vectors within
-// WIDE_SCRATCH_MAX.  Outside it the call is refused (why: the limit missed); the continuous adjoint is never run in its place.
-struct WDiscPlan { int nwg, nitems, nmu; size_t lds, rec_floats, vec_floats; };
-bool wdisc_fits(const lrnde_ctx* c, int B, WDiscPlan* pl, std::string* why) {
-  char msg[200];
-  auto no = [&](void) { if (why) *why = msg; return false; };
-  if (c->field != 2) { snprintf(msg, sizeof msg, "not a wide-chain handle"); return no(); }
-  if (sharded(c)) { snprintf(msg, sizeof msg, "the handle is sharded"); return no(); }
-  const WideDev& wd = c->wd;
-  const int nwg = (B + NB - 1) / NB;
-  const size_t lds = wide_smem_bytes(wd.bufw, wd.partcap);
-  if (lds > WIDE_LDS_MAX) { snprintf(msg, sizeof msg, "the step kernel needs %zu bytes of LDS, WIDE_LDS_MAX is %zu", lds, WIDE_LDS_MAX); return no(); }
-  if (nwg > CHADJ_MAX_WG) { snprintf(msg, sizeof msg, "B = %d is %d workgroups, CHADJ_MAX_WG is %d", B, nwg, CHADJ_MAX_WG); return no(); }
-  int nitems = 0;
-  for (int l = 0; l < c->chain.nlayers; ++l) {
-    const int MT = ceil16(c->chain.dims[l + 1]) / 16, KG = ceil16(c->chain.dims[l]) / 16;
-    nitems += ((MT + WADJ_MB - 1) / WADJ_MB) * ((KG + WADJ_MB - 1) / WADJ_MB) + (c->chain.dims[l + 1] + 63) / 64;
-  }
-  const size_t rec_floats = (size_t)WDISC_SLOTS * nwg * wd.recfloats;
-  const size_t vec_floats = (size_t)WDISC_VECS * B * c->desc.state_dim;
-  const size_t bytes = (rec_floats + vec_floats) * sizeof(float);
-  if (bytes > WIDE_SCRATCH_MAX) {
-    snprintf(msg, sizeof msg, "B = %d needs %zu bytes of stage records (%d slots) and sweep vectors (%d), WIDE_SCRATCH_MAX is %zu", B, bytes,
-             WDISC_SLOTS, WDISC_VECS, WIDE_SCRATCH_MAX);
-    return no();
-  }
-  if (pl) {
-    pl->nwg = nwg; pl->nitems = nitems; pl->nmu = std::min(nitems, CHADJ_MAX_MU_BLOCKS); pl->lds = lds;
-    pl->rec_floats = rec_floats; pl->vec_floats = vec_floats;
-  }
-  return true;
-}
-
 // Launches: one k_chdisc_begin per 64 series times, a k_wdisc_step / k_wdisc_mu pair per recorded step (newest first), the
 // tail pair; the caller zeroes z before (a memset: mu starts at zero, lam is written by the newest step) and adds k_adj_out.
 // No host wait.  lambda(t0) goes to z[0, n), the parameter cotangent to z[n, n + P): where the continuous loops leave them.
-int wdisc_run(lrnde_ctx* c, const WDiscPlan& pl, AdjVec& v, int B, float t2, const std::vector<float>& ser, const float* du, int nrec,
+int wdisc_run(lrnde_ctx* c, const AdjPlan& pl, AdjVec& v, int B, float t2, const std::vector<float>& ser, const float* du, int nrec,
               lrnde_stats* st) {
+  int rc;
   memset(st, 0, sizeof(*st));
   if (nrec <= 0) return fail(c, LRNDE_BADARG, "the record holds no step");
   HIPCHK(c, c->wa_rec.grow(pl.rec_floats));
   HIPCHK(c, c->wd_vec.grow(pl.vec_floats));
-  if (ser.size() > c->chd_ser.size() || !c->chd_ser) HIPCHK(c, c->chd_ser.grow(ser.size() + 64));
-  for (size_t off = 0; off < ser.size(); off += 64) {
-    ChDiscBegin b{};
-    b.dst = c->chd_ser; b.off = (int)off; b.n = (int)std::min<size_t>(64, ser.size() - off);
-    for (int k = 0; k < b.n; ++k) b.v[k] = ser[off + k];
-    hipLaunchKernelGGL(k_chdisc_begin, dim3(1), dim3(64), 0, c->stream, b);
-    HIPCHK(c, hipGetLastError());
-    ++c->adj_launches;
-  }
+  if ((rc = disc_upload_series(c, ser))) return rc;
   WDiscArgs a{};
   a.dense = c->dense; a.dense_t = c->dense_t; a.dense_dt = c->dense_dt; a.nrec = nrec; a.n_lam = v.n_lam;
   a.ser_t = c->chd_ser; a.du = du; a.nser = (int)ser.size(); a.t2 = t2;
@@ -4596,7 +4502,7 @@ int wdisc_run(lrnde_ctx* c, const WDiscPlan& pl, AdjVec& v, int B, float t2, con
     c->adj_launches += 2;
   }
   HIPCHK(c, hipGetLastError());
-  st->naccept = nrec; st->nreject = 0; st->iters = nrec; st->nf = 6 * nrec + 1; st->retcode = LRNDE_OK;
+  disc_stats(st, nrec);
   return LRNDE_OK;
 }
 
@@ -4608,7 +4514,7 @@ struct ChAdjDriver {
   std::function<int()> scratch;
   std::function<void(ChAdjArgs a, int jj, int mode)> launch_pair;
 };
-ChAdjDriver chadj_driver(lrnde_ctx* c, const ChAdjPlan& pl) {
+ChAdjDriver chadj_driver(lrnde_ctx* c, const AdjPlan& pl) {
   ChAdjDriver d;
   d.what = "chain adjoint loop"; d.nwg = pl.nwg; d.nmu = pl.nmu;
   d.scratch = [c, pl]() -> int { HIPCHK(c, c->cha_gpart.grow(7 * (size_t)pl.nwg * param_count(c))); return LRNDE_OK; };
@@ -4619,7 +4525,7 @@ ChAdjDriver chadj_driver(lrnde_ctx* c, const ChAdjPlan& pl) {
   };
   return d;
 }
-ChAdjDriver wadj_driver(lrnde_ctx* c, const WAdjPlan& pl) {
+ChAdjDriver wadj_driver(lrnde_ctx* c, const AdjPlan& pl) {
   ChAdjDriver d;
   d.what = "wide adjoint loop"; d.nwg = pl.nwg; d.nmu = pl.nmu;
   d.scratch = [c, pl]() -> int { HIPCHK(c, c->wa_rec.grow(pl.rec_floats)); return LRNDE_OK; };
@@ -4908,56 +4814,42 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   const int nsteps = R.naccept;
   // adjoint solve on z = [lambda; mu] in s = -t from -t2 to -t0, tstops at the saved times
   const size_t N = n + P;
-  WAdjPlan wpl{};
-  if (c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DEVICE && !sharded(c) && !opt(OPT_ADJ_HOST)) {
-    std::string why;   // (refused before anything is touched: the handle and its record stay usable)
-    if (!wadj_fits(c, B, &wpl, &why)) return fail(c, LRNDE_UNSUPPORTED, "wide adjoint loop: %s", why.c_str());
+  // the route first (lrnde_adj_route.hpp): a refusal comes before anything is allocated, zeroed or enqueued, so the handle
+  // and its record stay usable
+  const AdjRouteIn rin = adj_route_in(c, B);
+  AdjPlan plan;
+  {
+    std::string refusal;
+    if ((rc = adj_route(rin, &plan, &refusal))) return fail(c, rc, "%s", refusal.c_str());
   }
-  // (lrnde_set_sensealg: a small-chain handle; lrnde_set_adjoint_loop(LRNDE_ADJ_LOOP_DISCRETE): a wide-chain handle, and
-  //  LRNDE_ADJ_HOST does not override it)
-  const bool wide_disc = c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DISCRETE;
-  const bool discrete = c->sensealg == LRNDE_SENSE_DISCRETE || wide_disc;
-  ChDiscPlan dpl{};
-  WDiscPlan wdpl{};
-  if (discrete) {
-    std::string why;   // (refused before anything is touched: the handle and its record stay usable)
-    if (wide_disc ? !wdisc_fits(c, B, &wdpl, &why) : !chdisc_fits(c, B, &dpl, &why))
-      return fail(c, LRNDE_UNSUPPORTED, "%s: %s", wide_disc ? "wide discrete adjoint" : "discrete adjoint", why.c_str());
-    if (du_series && nser != (int)R.series_t.size())
-      return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
-  }
+  const AdjRoute route = plan.route;
+  if (du_series && nser != (int)R.series_t.size())
+    return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
   AdjVec v;
   if ((rc = adj_alloc(c, N, v))) return rc;
   v.n_lam = n; v.P = P;
-  const bool adj_host = opt(OPT_ADJ_HOST) != 0;  // diagnostic: the round-1 host-controlled loop
-  ChAdjPlan cpl{};
-  const bool chain_loop = c->field && chadj_fits(c, B, &cpl) && !sharded(c) && !adj_host;
-  const bool wide_loop = c->field == 2 && c->adj_loop == LRNDE_ADJ_LOOP_DEVICE && !sharded(c) && !adj_host;   // opt-in (lrnde_set_adjoint_loop)
-  const bool dev_loop = vjp_uses_qtile(c, B) && !sharded(c) && !adj_host;
-  c->adj_kind = wide_disc ? 5 : discrete ? 4 : (wide_loop ? 3 : (chain_loop ? 2 : (dev_loop ? 1 : 0))); c->adj_launches = 0; c->adj_waits = 0;
-  const bool begin_in_solve = dev_loop && !du_series;  // the device loop's first launch sets z = [du_end; 0] itself
-  if ((!begin_in_solve && !discrete) || wide_disc) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
+  c->adj_kind = route; c->adj_launches = 0; c->adj_waits = 0;
+  const bool begin_in_solve = route == ADJ_ROUTE_MLP_DEVICE && !du_series;  // the MLP device loop's first launch sets z = [du_end; 0] itself
+  if (adj_caller_zeroes_z(route, !du_series)) HIPCHK(c, hipMemsetAsync(v.z, 0, sizeof(float) * N, c->stream));
   std::vector<AdjImpulse> impulses;  // ascending in s = -t
-  if (discrete) {
-    // (the sweep takes the cotangents from the caller's array at the series' times; the small chain's writes all of z, the
-    //  wide chain's adds its parameter cotangents to the zeroed mu)
-  } else if (du_series) {
-    if (nser != (int)R.series_t.size()) return fail(c, LRNDE_BADARG, "%d cotangents for a series of %zu states", nser, R.series_t.size());
-    for (int i = nser - 1; i >= 0; --i) {
-      const float tv = R.series_t[i];
-      const float* du = du_series + (size_t)i * n;
-      if (tv >= t2) {  // cotangents at the end time: lambda(s0)
-        const float* gi[1] = {du}; const float one = 1.0f;
-        if ((rc = vec_axpy(c, v.z, v.z, 1.0f, 1, gi, &one, n))) return rc;
-      } else {
-        impulses.push_back(AdjImpulse{-tv, du});
-      }
-    }
-  } else if (!begin_in_solve) {
-    HIPCHK(c, hipMemcpyAsync(v.z, du_end, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
-  }
   std::vector<float> stops;
-  if (mode != LRNDE_MODE_NONE || du_series) stops = backward_stops(R.ts, t0, t2);
+  if (adj_builds_impulses(route)) {
+    if (du_series) {
+      for (int i = nser - 1; i >= 0; --i) {
+        const float tv = R.series_t[i];
+        const float* du = du_series + (size_t)i * n;
+        if (tv >= t2) {  // cotangents at the end time: lambda(s0)
+          const float* gi[1] = {du}; const float one = 1.0f;
+          if ((rc = vec_axpy(c, v.z, v.z, 1.0f, 1, gi, &one, n))) return rc;
+        } else {
+          impulses.push_back(AdjImpulse{-tv, du});
+        }
+      }
+    } else if (!begin_in_solve) {
+      HIPCHK(c, hipMemcpyAsync(v.z, du_end, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (mode != LRNDE_MODE_NONE || du_series) stops = backward_stops(R.ts, t0, t2);
+  }
   auto pending_sweep = [c]() -> int {  // the forward left the regulariser's sweep to us (NodeRecord::sweep_pending)
     lrnde_ctx* sd = c->side;
     NodeRecord& R = c->rec;
@@ -4973,28 +4865,36 @@ static int node_backward_recorded_impl(lrnde_ctx* c, int32_t B, const float* du_
   const bool want_sweep = mode != LRNDE_MODE_NONE && w_reg != 0.0f && R.sweep_pending && c->side != nullptr;
   std::function<int()> after_first_attempt;  // the device loops call it once, after enqueuing their first attempt
   if (want_sweep) {
-    if (vjp_uses_qtile(c, B) && !sharded(c) && !adj_host) after_first_attempt = pending_sweep;
+    if (adj_sweep_rides_first_attempt(route)) after_first_attempt = pending_sweep;
     else if ((rc = pending_sweep())) return rc;
   }
-  if (wide_disc) {
-    rc = wdisc_run(c, wdpl, v, B, t2, du_series ? R.series_t : std::vector<float>{t2}, du_series ? du_series : du_end, nsteps, st_bwd);
-  } else if (discrete) {
-    rc = chdisc_run(c, dpl, v, B, t2, du_series ? R.series_t : std::vector<float>{t2}, du_series ? du_series : du_end, nsteps, st_bwd);
-  } else if (chain_loop || wide_loop) {
-    rc = chadj_solve_device(c, wide_loop ? wadj_driver(c, wpl) : chadj_driver(c, cpl), v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
-                            after_first_attempt);
-  } else if (dev_loop) {
-    rc = adj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
-                          begin_in_solve ? du_end : nullptr, after_first_attempt);
-  } else {
-    std::vector<float> dts(nsteps), dds(nsteps);
-    HIPCHK(c, hipMemcpy(dts.data(), c->dense_t, sizeof(float) * nsteps, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(dds.data(), c->dense_dt, sizeof(float) * nsteps, hipMemcpyDeviceToHost));
-    c->adj_waits += 2;
-    auto rhs = [&](const float* zs, float sg, float* K) { return adj_rhs(c, dts, dds, B, n, zs, sg, K); };
-    auto rhs_fused = [&](const StageIn& sin, float sg, float* K) { return adj_rhs(c, dts, dds, B, n, nullptr, sg, K, &sin); };
-    rc = vec_tsit5_solve(c, v, rhs, rhs_fused, vjp_uses_qtile(c, B), -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow,
-                         stops, impulses, st_bwd);
+  switch (route) {
+    // (a discrete sweep takes the cotangents from the caller's array at the series' times)
+    case ADJ_ROUTE_WIDE_DISCRETE:
+      rc = wdisc_run(c, plan, v, B, t2, du_series ? R.series_t : std::vector<float>{t2}, du_series ? du_series : du_end, nsteps, st_bwd);
+      break;
+    case ADJ_ROUTE_CHAIN_DISCRETE:
+      rc = chdisc_run(c, plan, v, B, t2, du_series ? R.series_t : std::vector<float>{t2}, du_series ? du_series : du_end, nsteps, st_bwd);
+      break;
+    case ADJ_ROUTE_WIDE_DEVICE:
+    case ADJ_ROUTE_CHAIN_DEVICE:
+      rc = chadj_solve_device(c, route == ADJ_ROUTE_WIDE_DEVICE ? wadj_driver(c, plan) : chadj_driver(c, plan), v, B, -t2, -t0, o->abstol, o->reltol,
+                              o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd, after_first_attempt);
+      break;
+    case ADJ_ROUTE_MLP_DEVICE:
+      rc = adj_solve_device(c, v, B, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, nsteps, st_bwd,
+                            begin_in_solve ? du_end : nullptr, after_first_attempt);
+      break;
+    case ADJ_ROUTE_HOST: {
+      std::vector<float> dts(nsteps), dds(nsteps);
+      HIPCHK(c, hipMemcpy(dts.data(), c->dense_t, sizeof(float) * nsteps, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(dds.data(), c->dense_dt, sizeof(float) * nsteps, hipMemcpyDeviceToHost));
+      c->adj_waits += 2;
+      auto rhs = [&](const float* zs, float sg, float* K) { return adj_rhs(c, dts, dds, B, n, zs, sg, K); };
+      auto rhs_fused = [&](const StageIn& sin, float sg, float* K) { return adj_rhs(c, dts, dds, B, n, nullptr, sg, K, &sin); };
+      rc = vec_tsit5_solve(c, v, rhs, rhs_fused, rin.qvjp, -t2, -t0, o->abstol, o->reltol, o->maxiters, o->exact_pow, stops, impulses, st_bwd);
+      break;
+    }
   }
   // (+ k_adj_out; what the regulariser's sweep enqueues behind the solve is not the solve's)
   struct InfoGuard { lrnde_ctx* c; int n; ~InfoGuard() { c->adj_launches = n; } } info_guard{c, c->adj_launches + 1};

@@ -36,10 +36,10 @@ constexpr int WADJ_SLOTS = 8;
 constexpr int WADJ_MU_NT = 7 * 64;        // k_wadj_mu: wave s forms stage s + 1
 // (its grid is at most CHADJ_MAX_MU_BLOCKS workgroups, one norm partial each, as k_chadj_mu's; more work items than that
 //  take further trips)
-static_assert(sizeof(ChAdjCtrl) == 53 * 4, "wadj_fits counts two control blocks; tests/wide_chain_adjoint_cases.py restates it with this size");
+static_assert(sizeof(ChAdjCtrl) == 53 * 4, "wide_device_gate counts two control blocks; tests/wide_chain_adjoint_cases.py restates it with this size");
 constexpr int WADJ_MB = 2;                // output blocks per side of a work item: 2 x 2 blocks of 16 x 16 share their operands
 
-static size_t wadj_smem_bytes(int bufw, int partcap) { return wide_smem_bytes(bufw, partcap) + sizeof(ChAdjCtrl); }
+constexpr size_t WADJ_LDS_TAIL = WIDE_LDS_TAIL + sizeof(ChAdjCtrl);   // the control block sits behind the forward carve's tail (wadj_ctrl)
 __device__ __forceinline__ ChAdjCtrl* wadj_ctrl(const WideSmem& s) { return reinterpret_cast<ChAdjCtrl*>(s.bc + 1); }
 __device__ __forceinline__ float* wadj_rec(const WAdjArgs& w, const WideDev& wd, int slot, int tile) {
   return w.rec + ((size_t)slot * w.a.nwg + tile) * wd.recfloats;

@@ -37,10 +37,9 @@
 constexpr int WT = 4;                    // row tiles a wave runs as independent accumulator chains
 constexpr int WMAXW = 1024;              // widest layer (LRNDE_WIDE_CHAIN_MAX_WIDTH)
 constexpr int WMETA = 12;                // ints per layer in the layer table
-constexpr size_t WIDE_LDS_MAX = 160 * 1024;
-// scratch of one VJP launch (activation records + parameter-cotangent partials of the workgroups it runs); a batch that
-// needs more runs as several launches over consecutive workgroups (one workgroup's share always fits: lrnde_create_wide_chain)
-constexpr size_t WIDE_SCRATCH_MAX = (size_t)256 << 20;
+// (WIDE_LDS_MAX, WIDE_SCRATCH_MAX: lrnde_adj_route.hpp.)  Scratch of one VJP launch (activation records + parameter-cotangent
+// partials of the workgroups it runs) stays within WIDE_SCRATCH_MAX; a batch that needs more runs as several launches over
+// consecutive workgroups (one workgroup's share always fits: lrnde_create_wide_chain)
 
 // per layer: in, out, act, MT = row tiles, KG = k-groups, woff / goff (forward / transposed image, floats), voff (t column
 // then bias, MT*16 floats each), poff (flat Lux vector), raoff / rzoff (VJP record: layer input, act'; [row][NB])
@@ -69,9 +68,8 @@ __device__ __forceinline__ WideSmem wide_carve(const WideDev& wd) {
   s.bc = reinterpret_cast<Bcast*>(s.red + NW * 3);
   return s;
 }
-static size_t wide_smem_bytes(int bufw, int partcap) {
-  return (2 * (size_t)bufw + (size_t)partcap) * sizeof(float) + NW * 3 * sizeof(double) + sizeof(Bcast) + 16;
-}
+constexpr size_t WIDE_LDS_TAIL = NW * 3 * sizeof(double) + sizeof(Bcast) + 16;   // behind the buffers: red, bc, padding
+static size_t wide_smem_bytes(int bufw, int partcap) { return wide_lds_bytes(bufw, partcap, WIDE_LDS_TAIL); }
 // floats of segment partials a (MT row tiles) x (KG k-groups) product wants when its segments are spread over the waves
 static int wide_part_want(int MT, int KG) {
   const int ngrp = (MT + WT - 1) / WT, nseg = (KG + SEGK - 1) / SEGK;

@@ -544,7 +544,7 @@ def test_80_saved_times_take_two_begin_launches_and_the_serial_tstop_scan(gpu_pk
 def test_backward_image_in_l2_and_two_parameter_chunks_per_mu_block(gpu_pkg, host_loop):
     """Chain(Dense(128, 96, tanh), Dense(96, 128)), by lrnde_create_chain's formulas: forward image (129 x 96 + 97 x 128)
     = 24800 floats = 99.2 KB; activation record ch_vjp_lds = ((128 + 96) + (96 + 128) + 128 + 2 x 128) x 8 floats =
-    26.6 KB; chadj_smem_bytes without the backward image = 99.2 + 26.6 + 0.4 KB <= 160 KB, so chadj_fits accepts; the
+    26.6 KB; the step kernel's LDS without the backward image = 99.2 + 26.6 + 0.4 KB <= 160 KB, so chain_device_gate accepts; the
     backward image is 128 x 96 + 96 x 128 = 24576 floats = 98.3 KB and with it 224 KB > 160 KB: wg_lds = 0, k_chadj_step
     reads W^T from L2.  P = 24800 > 64 x CHADJ_MAX_MU_BLOCKS = 16384: 388 chunks of 64 parameters on 256 blocks, so blocks
     0..131 of k_chadj_mu go round their chunk loop twice."""

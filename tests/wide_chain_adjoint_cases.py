@@ -1,6 +1,6 @@
 """Shared by tests/test_host_wide_chain_adjoint.py and tests/test_gpu_wide_chain_adjoint.py: the cases of the wide
 Dense-chain handle's device-controlled adjoint loop (csrc/lrnde_wide_adjoint.hpp), the gate's arithmetic
-(lrnde_kernels.hip wadj_fits) restated, and the branch table of its two kernels.  No code is shared with the kernels."""
+(csrc/lrnde_adj_route.hpp wide_device_gate) restated, and the branch table of its two kernels.  No code is shared with the kernels."""
 import numpy as np
 import torch
 
@@ -12,7 +12,7 @@ import wide_chain_cases as WC
 LAUNCH_C = 10
 TOL = 1e-5
 
-# ---- the gate (wadj_fits) ----
+# ---- the gate (wide_device_gate) ----
 SLOTS = 8                       # stage-record slots: K1's and stages 2..7, plus one so that FSAL needs no copy
 MB = 2                          # k_wadj_mu: a work item is MB x MB output blocks of 16 x 16
 MAX_MU_BLOCKS = 256             # its grid (CHADJ_MAX_MU_BLOCKS)
@@ -36,7 +36,7 @@ def mu_items(dims):
 
 
 def gate(dims, B):
-    """dict(fits, why, nwg, nitems, nmu, lds, bytes) of wadj_fits for a chain of these widths at batch B"""
+    """dict(fits, why, nwg, nitems, nmu, lds, bytes) of wide_device_gate for a chain of these widths at batch B"""
     nwg = -(-B // WC.NB)
     fixed = 2 * WC.ceil16(max(dims)) * WC.NB * 4 + WC.LDS_TAIL + CTRL_BYTES
     cap = min(WC.partcap(dims), ((WC.WIDE_LDS_MAX - fixed) // 4) & ~255)

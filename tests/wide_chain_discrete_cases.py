@@ -1,6 +1,6 @@
 """Shared by tests/test_host_wide_chain_discrete.py and tests/test_gpu_wide_chain_discrete.py: the cases of the wide
 Dense-chain handle's discrete adjoint (csrc/lrnde_wide_discrete.hpp), the gate's arithmetic
-(lrnde_kernels.hip wdisc_fits) restated, the fixed launches, and the branch table of its two kernels.  No code is shared
+(csrc/lrnde_adj_route.hpp wide_discrete_gate) restated, the fixed launches, and the branch table of its two kernels.  No code is shared
 with the kernels.  The method's yardsticks are tests/chain_discrete_np.py's (frozen_grads, sweep64, place, bound)."""
 import numpy as np
 import torch
@@ -12,7 +12,7 @@ f32 = np.float32
 TOL = 1e-4
 TIMES = [0.3, 0.7, 1.0]
 
-# ---- the gate (wdisc_fits) ----
+# ---- the gate (wide_discrete_gate) ----
 SLOTS = 6                       # stage-record slots: stages 2..7 of a step (the tail's one evaluation reuses slot 0)
 VECS = 14                       # B*D vectors beside z: k2..k6, u_new, ck[1..7], cu
 MAX_WG = WA.MAX_WG              # CHADJ_MAX_WG
@@ -20,7 +20,7 @@ SCRATCH_MAX = WA.SCRATCH_MAX    # WIDE_SCRATCH_MAX
 
 
 def gate(dims, B):
-    """dict(fits, why, nwg, nitems, nmu, lds, bytes) of wdisc_fits for a chain of these widths at batch B"""
+    """dict(fits, why, nwg, nitems, nmu, lds, bytes) of wide_discrete_gate for a chain of these widths at batch B"""
     nwg = -(-B // WC.NB)
     lds = 2 * WC.ceil16(max(dims)) * WC.NB * 4 + WC.LDS_TAIL + 4 * WC.partcap(dims)   # the forward kernels' carve
     nitems = sum(g + c for g, c in WA.mu_items(dims))
