@@ -2645,13 +2645,17 @@ int lrnde_conv_node_forward(lrnde_conv* c, const float* x, int32_t B, float t0, 
   float* V = c->vec;
   float dtl, ee, re, rs;
   const int Hc4 = 4 * c->d.hidden;
-  CHK(c, hipMemcpyAsync(V, c->bn_state, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream));  // V[0..n) is free here
+  // kept in a buffer of its own: the head of V is free only up to n floats, and a state can be smaller than the 4*hidden
+  // statistics (4x2 at B <= 3), where the step's u, k1, k2 at V+n.. would overwrite the copy
+  DevBuf<float> bn_keep;
+  if (bn_keep.once(Hc4) != hipSuccess) return cfail(c, LRNDE_HIP_ERROR, "allocation failed");
+  CHK(c, hipMemcpyAsync(bn_keep, c->bn_state, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream));
   if ((rc = init_dt(c, u1, B, t1, t2, oo.abstol, oo.reltol, V + 2 * n, V + 10 * n, V + 9 * n, &dtl))) return rc;
   double s[3];
   if ((rc = tsit5_step(c, u1, V + 2 * n, B, t1, dtl, oo.abstol, oo.reltol, V + n, V + 8 * n, V + 3 * n, V + 9 * n, V + 10 * n, s))) return rc;
   reg_values(s, state_span(c, n).global, dtl, &ee, &re, &rs);
-  CHK(c, hipMemcpyAsync(c->bn_state, V, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream));
-  CHK(c, hipStreamSynchronize(c->stream));
+  CHK(c, hipMemcpyAsync(c->bn_state, bn_keep, sizeof(float) * Hc4, hipMemcpyDeviceToDevice, c->stream));
+  CHK(c, hipStreamSynchronize(c->stream));   // bn_keep is released only behind this
   *reg_val = (reg_type == LRNDE_REG_STIFFNESS_ESTIMATE) ? rs : re;
   *nfe = st->nf + (6 + 3);
   return LRNDE_OK;
