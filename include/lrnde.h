@@ -196,8 +196,9 @@ int lrnde_set_params(lrnde_ctx* ctx, const float* p, size_t n);
  * Which handles, which loop: the MLP handle runs the host-driven loop of csrc/lrnde_adams.hpp (3-4 launches and a read-back
  * per attempted step); an unsharded small Dense-chain handle runs one launch per attempted step with the controller on the
  * device (csrc/lrnde_chain_adams.hpp, k_adams_chain; same bits as the host loop, which the diagnostic switch
- * LRNDE_ADAMS_HOST=1 selects there too).  A wide Dense-chain handle refuses alg != 0 with LRNDE_UNSUPPORTED (Tsit5 only);
- * the conv handle has no such setter.
+ * LRNDE_ADAMS_HOST=1 selects there too).  A wide Dense-chain handle refuses alg != 0 with LRNDE_UNSUPPORTED (Tsit5 only).
+ * The conv handle has a setter of its own, lrnde_conv_set_solver (host-driven loop with fused 16-byte elementwise kernels,
+ * csrc/lrnde_conv_adams.hpp).
  * The small chain's discrete adjoint walks a Tsit5 stage record: alg != 0 on a handle whose lrnde_set_sensealg choice is
  * DISCRETE returns LRNDE_UNSUPPORTED, and so does lrnde_set_sensealg(DISCRETE) on a handle whose solver is not Tsit5 —
  * whichever is set second is refused, with a message, and the handle stays usable.  Any other code: LRNDE_BADARG. */
@@ -369,6 +370,13 @@ int lrnde_conv_set_bn_state(lrnde_conv* c, const float* mean_var, size_t n);    
 int lrnde_conv_get_bn_state(lrnde_conv* c, float* mean_var, size_t n);            /* device */
 /* Lux.trainmode / Lux.testmode for the field's BatchNorm layers after creation (overrides desc.bn_train) */
 int lrnde_conv_set_bn_mode(lrnde_conv* c, int32_t bn_train);
+/* lrnde_set_solver for the conv handle: the method of the GLOBAL solve in lrnde_conv_solve / lrnde_conv_node_forward* /
+ * lrnde_conv_node_backward* (LRNDE_ALG_TSIT5 default, LRNDE_ALG_VCAB3, LRNDE_ALG_VCABM3; UPSTREAM-RECALL, parity unpinned:
+ * csrc/lrnde_conv_adams.hpp).  The local regularisation step and the reversed solve of the pullback stay Tsit5; a recorded
+ * Adams forward leaves a Hermite record [uprev, k1, P2, P3] per accepted step, which the pullback interpolates.  Every
+ * f-eval of an Adams solve advances the running statistics once, as a Tsit5 solve's do.  Works on sharded handles (every
+ * rank sets the same method).  Invalidates the forward record.  Any other code: LRNDE_BADARG, the handle stays usable. */
+int lrnde_conv_set_solver(lrnde_conv* c, int32_t alg);
 int lrnde_conv_rhs(lrnde_conv* c, const float* u, float t, int32_t B, float* du);
 int lrnde_conv_init_dt(lrnde_conv* c, const float* u0, int32_t B, float t0, float t1, float abstol,
                        float reltol, float* k1, float* dt_host);

@@ -194,6 +194,8 @@ end
 conv_check(ctx, rc) = check(ctx, rc; last_error=:lrnde_conv_last_error)
 conv_set_params!(ctx, ps) = conv_check(ctx, ccall((:lrnde_conv_set_params, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t),
                                                   ctx, pointer(ps), length(ps)))
+# n.solver on the conv handle (LRNDE_ALG_*: 0 Tsit5, 1 VCAB3, 2 VCABM3); the local step and the adjoint stay Tsit5
+conv_set_solver!(ctx, alg) = conv_check(ctx, ccall((:lrnde_conv_set_solver, lib), Cint, (Ptr{Cvoid}, Int32), ctx, alg))
 conv_set_bn_state!(ctx, st) = conv_check(ctx, ccall((:lrnde_conv_set_bn_state, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t),
                                                     ctx, pointer(st), length(st)))
 function conv_get_bn_state(ctx, like)   # like: a device vector of 4*hidden Float32 ([μ1; σ²1; μ2; σ²2] of st.model)

@@ -213,10 +213,14 @@ const _lrnde_conv_handles = IdDict{Any, Ptr{Cvoid}}()
 function lrnde_conv_handle(n::NeuralODE, x)
     get!(_lrnde_conv_handles, n) do
         W, H, C, Hc, act = lrnde_conv_field_shape(n.model, x)
-        LRNDEBackend.conv_create(W, H; channels=C, hidden=Hc, act, bn_train=true)
+        cctx = LRNDEBackend.conv_create(W, H; channels=C, hidden=Hc, act, bn_train=true)
+        # VCAB3 / VCABM3 for the global solve (csrc/lrnde_conv_adams.hpp); UPSTREAM-RECALL, parity unpinned; the local step and the
+        # pullback's reversed solve stay Tsit5
+        LRNDEBackend.conv_set_solver!(cctx, _lrnde_alg(n.solver))
+        cctx
     end
 end
-lrnde_conv_supported(n::NeuralODE, x) = n.solver isa Tsit5 && ndims(x) == 4 && nameof(typeof(x)) === :ROCArray && eltype(x) === Float32 &&
+lrnde_conv_supported(n::NeuralODE, x) = _lrnde_alg(n.solver) !== nothing && ndims(x) == 4 && nameof(typeof(x)) === :ROCArray && eltype(x) === Float32 &&
                                         !haskey(n.kwargs, :saveat) && lrnde_conv_field_shape(n.model, x) !== nothing
 
 # st.model of the TDChain: (layer_1 = (layer_1 = (;), layer_2 = (running_mean, running_var, training)), layer_2 = ..., layer_3 = (;))

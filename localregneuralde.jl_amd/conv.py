@@ -85,6 +85,7 @@ class ConvHandle:
                                      C.c_void_p(self._stream.cuda_stream))
         if rc != 0:
             raise L.LrndeError(rc, "lrnde_conv_create failed (shape or dtype not supported by the kernels)")
+        self.solver = "tsit5"
         self._keep = {}  # name -> the tensor a pending async copy reads (one slot per kind: overwritten, never appended)
 
     def close(self):
@@ -126,6 +127,14 @@ class ConvHandle:
     def set_bn_mode(self, train):
         """Lux.trainmode / Lux.testmode of the BatchNorm layers"""
         self._chk(L.lib.lrnde_conv_set_bn_mode(self._ctx, int(bool(train))))
+
+    def set_solver(self, solver):
+        """the method of the handle's global solve (solve, node_forward*, node_backward*): "tsit5" (default), "vcab3" or
+        "vcabm3" — the names Handle.set_solver takes (csrc/lrnde_conv_adams.hpp; UPSTREAM-RECALL).  The local
+        regularisation step and the pullback's reversed solve stay Tsit5.  Invalidates the forward record."""
+        from .layers import SOLVERS, _solver_name
+        self._chk(L.lib.lrnde_conv_set_solver(self._ctx, SOLVERS[_solver_name(solver)]))
+        self.solver = _solver_name(solver)
 
     def get_bn_state(self):
         """running [mean1 var1 mean2 var2] (st.model of the layer), advanced by every training-mode f-eval"""

@@ -19,27 +19,23 @@
 // (lrnde_node_backward_recorded).  Deviation, stated: the reversed solve is the handle's Tsit5 adjoint whatever the forward's
 // method was; the reference would hand n.solver to the adjoint problem too.
 //
-// Serves the MLP handle.  An unsharded small Dense-chain handle runs the same arithmetic as one launch per attempted step
+// Serves the MLP handle (the conv handle has a loop of its own over the same formulas, lrnde_conv_adams.hpp; the formulas
+// themselves and the coefficient recurrence: lrnde_adams_math.hpp).  An unsharded small Dense-chain handle runs the same arithmetic as one launch per attempted step
 // (lrnde_chain_adams.hpp) and comes here only under LRNDE_ADAMS_HOST=1, the same-bits comparison path (this loop calls
 // lrnde_rhs, vec_axpy, vec_norm and the record writers, none of which knows the field).  The wide handle is Tsit5 only.
 // Host-driven: per attempted step one fused elementwise launch before the evaluation, one after it (which also leaves the
 // error norm's 256 block sums), the evaluation itself (k_rhs_q / k_rhs), and one read-back — the secondary solver of the
 // layer, not the metric's path.  Arithmetic: operation for operation what the CPU oracle's adams_solve does (tests/test_gpu_adams.py: equal bits).
 
-struct AdamsPre { const float *uprev, *k1, *kprev, *sp2; float *s2, *s3, *u; float b2, b3, dt, g2, g3; int three, only_s2; size_t n; };
+// (the per-element formulas and the coefficient recurrences: lrnde_adams_math.hpp, shared with the conv handle's loop)
+struct AdamsPre { const float *uprev, *k1, *kprev, *sp2; float *s2, *s3, *u; lrnde::AdamsCoef k; float dt; int three, only_s2; size_t n; };
 __global__ void k_adams_pre(AdamsPre a) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-    const float k1 = a.k1[i];
-    const float p2 = k1 - a.kprev[i];
-    const float v2 = a.b2 * p2;
-    a.s2[i] = v2;
-    if (a.only_s2) continue;   // second start-up step: phi*_1 for the first multistep step
-    const float p3 = p2 - a.sp2[i];
-    const float v3 = a.b3 * p3;
-    a.s3[i] = v3;
-    float sm = k1 + a.g2 * v2;
-    if (a.three) sm = sm + a.g3 * v3;
-    a.u[i] = a.uprev[i] + a.dt * sm;
+    if (a.only_s2) { a.s2[i] = lrnde::adams_phi1(a.k1[i], a.kprev[i], a.k.b2); continue; }   // second start-up step: phi*_1 for the first multistep step
+    const lrnde::AdamsPred r = lrnde::adams_predict(a.uprev[i], a.k1[i], a.kprev[i], a.sp2[i], a.k, a.dt, a.three);
+    a.s2[i] = r.v2;
+    a.s3[i] = r.v3;
+    a.u[i] = r.u;
   }
 }
 
@@ -49,15 +45,10 @@ __global__ __launch_bounds__(256) void k_adams_post(AdamsPost a) {
   __shared__ double red[4];
   double acc = 0.0;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-    const float q2 = a.du[i] - a.k1[i];
-    const float q3 = q2 - a.s2[i];
-    const float q4 = q3 - a.s3[i];
     float u = a.u[i];
-    if (a.moulton) { u = u + a.cu * q3; a.u[i] = u; }
-    const float ut = a.ce * q4;
-    const float sc = a.abstol + fmaxf_(__builtin_fabsf(a.uprev[i]), __builtin_fabsf(u)) * a.reltol;
-    const float r = ut / sc;
-    acc += (double)(r * r);
+    const float sq = lrnde::adams_correct(a.du[i], a.k1[i], a.s2[i], a.s3[i], a.uprev[i], u, a.cu, a.ce, a.moulton, a.abstol, a.reltol);
+    if (a.moulton) a.u[i] = u;
+    acc += (double)sq;
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
@@ -69,10 +60,10 @@ __global__ __launch_bounds__(256) void k_adams_post(AdamsPost a) {
 struct AdamsRec { const float *uprev, *u, *k1, *kend; float *P2, *P3; float dt; size_t n; float* rec_t; float* rec_dt; int idx; float tprev; };
 __global__ void k_adams_hermite(AdamsRec a) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
-    const float d = (a.u[i] - a.uprev[i]) / a.dt;
-    const float k1 = a.k1[i], ke = a.kend[i];
-    a.P2[i] = (3.0f * d - 2.0f * k1) - ke;
-    a.P3[i] = (k1 + ke) - 2.0f * d;
+    float P2, P3;
+    lrnde::adams_hermite(a.uprev[i], a.u[i], a.k1[i], a.kend[i], a.dt, P2, P3);
+    a.P2[i] = P2;
+    a.P3[i] = P3;
   }
   if (a.rec_t && blockIdx.x == 0 && threadIdx.x == 0) { a.rec_t[a.idx] = a.tprev; a.rec_dt[a.idx] = a.dt; }
 }
@@ -137,7 +128,6 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
   const float a21 = 0.5f, a32 = 0.75f;
   const float a4[3] = {(float)(2.0 / 9.0), (float)(1.0 / 3.0), (float)(4.0 / 9.0)};
   const float bt[4] = {(float)(5.0 / 72.0), (float)(-1.0 / 12.0), (float)(-1.0 / 9.0), 0.125f};
-  const float c21 = 0.5f, c22 = (float)(1.0 / 6.0), c23 = (float)(1.0 / 12.0);
   int launches = 0;
   while (t < t1) {
     if (L.iter > 0 && L.accept) {
@@ -147,8 +137,7 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
     }
     if (!attempt_header(L, t1)) break;
     const int nacc = st->naccept;
-    const float b2 = nacc >= 1 ? dt / h1 : 0.0f;
-    const float b3 = nacc >= 2 ? b2 * ((dt + h1) / (h1 + h2)) : 0.0f;
+    const lrnde::AdamsCoef kc = lrnde::adams_coef(nacc, moulton ? 1 : 0, dt, h1, h2);
     float eest;
     if (nacc < 2) {   // Bogacki-Shampine 3(2)
       const float* k_1[1] = {k1};
@@ -165,22 +154,16 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
       if ((rc = vec_axpy(c, tmp, nullptr, dt, 4, k_4, bt, n))) return rc;
       if (nacc == 1) {
         AdamsPre p{};
-        p.uprev = uprev; p.k1 = k1; p.kprev = kprev; p.sp2 = sp2; p.s2 = s2; p.s3 = s3; p.u = u; p.b2 = b2; p.only_s2 = 1; p.n = n;
+        p.uprev = uprev; p.k1 = k1; p.kprev = kprev; p.sp2 = sp2; p.s2 = s2; p.s3 = s3; p.u = u; p.k = kc; p.only_s2 = 1; p.n = n;
         hipLaunchKernelGGL(k_adams_pre, dim3(nb), dim3(256), 0, sq, p);
         HIPCHK(c, hipGetLastError());
       }
       if ((rc = vec_norm(c, tmp, nullptr, uprev, u, abstol, reltol, n, 0, &eest))) return rc;
       launches += 9;
     } else {
-      const float r1 = dt / (dt + h1);
-      const float g2 = c21;
-      const float g3 = c21 - r1 * c22;
-      const float c32 = c22 - r1 * c23;
-      const float r2 = dt / ((dt + h1) + h2);
-      const float g4 = g3 - r2 * c32;
       AdamsPre p{};
       p.uprev = uprev; p.k1 = k1; p.kprev = kprev; p.sp2 = sp2; p.s2 = s2; p.s3 = s3; p.u = u;
-      p.b2 = b2; p.b3 = b3; p.dt = dt; p.g2 = g2; p.g3 = g3; p.three = moulton ? 0 : 1; p.only_s2 = 0; p.n = n;
+      p.k = kc; p.dt = dt; p.three = moulton ? 0 : 1; p.only_s2 = 0; p.n = n;
       hipLaunchKernelGGL(k_adams_pre, dim3(nb), dim3(256), 0, sq, p);
       HIPCHK(c, hipGetLastError());
       float* dnew = moulton ? du : kend;   // VCAB3: the evaluation at the new state is fsallast itself
@@ -188,7 +171,7 @@ int adams_solve(lrnde_ctx* c, const float* u0, int32_t B, float t0, float t1, co
       st->nf += 1;
       AdamsPost q{};
       q.du = dnew; q.k1 = k1; q.s2 = s2; q.s3 = s3; q.uprev = uprev; q.u = u;
-      q.cu = dt * g3; q.ce = moulton ? dt * (g4 - g3) : dt * g4; q.abstol = abstol; q.reltol = reltol; q.moulton = moulton ? 1 : 0;
+      q.cu = kc.cu; q.ce = kc.ce; q.abstol = abstol; q.reltol = reltol; q.moulton = moulton ? 1 : 0;
       q.n = n; q.part = c->adj_part;
       hipLaunchKernelGGL(k_adams_post, dim3(256), dim3(256), 0, sq, q);
       HIPCHK(c, hipGetLastError());

@@ -137,19 +137,8 @@ __device__ __forceinline__ void adams_prologue(const StepArgs& a, const AdamsCha
   ab.phase = nacc < 2 ? nacc : 2;
   ab.fresh = accepted;
   if (do_step) {
-    const float c21 = 0.5f, c22 = (float)(1.0 / 6.0), c23 = (float)(1.0 / 12.0);
-    ab.b2 = nacc >= 1 ? dt / h1 : 0.0f;
-    ab.b3 = nacc >= 2 ? ab.b2 * ((dt + h1) / (h1 + h2)) : 0.0f;
-    if (nacc >= 2) {
-      const float r1 = dt / (dt + h1);
-      const float g3 = c21 - r1 * c22;
-      const float c32 = c22 - r1 * c23;
-      const float r2 = dt / ((dt + h1) + h2);
-      const float g4 = g3 - r2 * c32;
-      ab.g2 = c21; ab.g3 = g3;
-      ab.cu = dt * g3;
-      ab.ce = aa.moulton ? dt * (g4 - g3) : dt * g4;
-    }
+    const lrnde::AdamsCoef kc = lrnde::adams_coef(nacc, aa.moulton, dt, h1, h2);   // lrnde_adams_math.hpp
+    ab.b2 = kc.b2; ab.b3 = kc.b3; ab.g2 = kc.g2; ab.g3 = kc.g3; ab.cu = kc.cu; ab.ce = kc.ce;
   }
   if (lane == 0) {
     *out = ab;

@@ -43,6 +43,7 @@
 #include "lrnde_math.hpp"
 #include "lrnde_buf.hpp"
 #include "lrnde_stepctl.hpp"
+#include "lrnde_adams_math.hpp"
 #include "lrnde_layer_plan.hpp"
 #include "lrnde_conv_geom.hpp"
 #include "lrnde_comm.hpp"
@@ -1786,7 +1787,8 @@ struct lrnde_conv {
   int wsB = 0;
   DevBuf<float> y1, y2;
   DevBuf<double> part; int nwg = 0;
-  DevBuf<float> vec;      // 11 state-sized vectors
+  DevBuf<float> vec;      // 11 state-sized vectors (Tsit5), CAD_VECS for VCAB3 / VCABM3 (lrnde_conv_adams.hpp)
+  int solver_alg = 0;     // lrnde_conv_set_solver: the method of the layer's global solve (LRNDE_ALG_*)
   DevBuf<double> sums; PinBuf<double> sums_host;
   HipEvent ev0, ev1;
   int num_cu = 256;
@@ -1881,8 +1883,9 @@ int allreduce_block(lrnde_conv* c, float* v, size_t count) {
 // cross-sample sums are over the global batch
 inline double nranks_of(const lrnde_conv* c) { return sharded(c) ? (double)c->mem.nranks : 1.0; }
 
+constexpr int CAD_VECS = 14;   // state-sized work vectors of conv_adams_solve (lrnde_conv_adams.hpp)
 int ensure_ws(lrnde_conv* c, int B) {
-  if (B == c->wsB) return LRNDE_OK;
+  if (B == c->wsB) return LRNDE_OK;   // (lrnde_conv_set_solver resets wsB: the vector count depends on the solver)
   c->wsB = 0;
   for (DevBuf<float>* b : {&c->y1, &c->y2, &c->vec}) CHK(c, b->reset());
   CHK(c, c->part.reset());
@@ -1891,7 +1894,7 @@ int ensure_ws(lrnde_conv* c, int B) {
   CHK(c, c->y1.once(px * c->d.hidden));
   CHK(c, c->y2.once(px * c->d.hidden));
   CHK(c, c->part.once((size_t)c->nwg * c->d.hidden * 2));
-  CHK(c, c->vec.once(11 * state_n(c, B)));
+  CHK(c, c->vec.once((c->solver_alg != LRNDE_ALG_TSIT5 ? CAD_VECS : 11) * state_n(c, B)));
   c->wsB = B;
   return LRNDE_OK;
 }
@@ -2199,7 +2202,7 @@ int fetch_sums(lrnde_conv* c, double* s3) {
 // ode_determine_initdt (OrdinaryDiffEq, un-vendored): f0 -> k1 (= fsalfirst)
 template <class RHS>
 int init_dt_g(lrnde_conv* c, size_t n, NormSpan sp, RHS&& rhs, const float* u0, float t0, float tend, float abstol, float reltol, float* f0,
-              float* tmp, float* f1, float* dt_out) {
+              float* tmp, float* f1, float* dt_out, float order = 5.0f) {   // order: 5 Tsit5, 3 VCAB3 / VCABM3
   const float dtmax = tend - t0;
   int rc;
   double s[3];
@@ -2213,7 +2216,7 @@ int init_dt_g(lrnde_conv* c, size_t n, NormSpan sp, RHS&& rhs, const float* u0, 
   if ((rc = rhs(tmp, t0 + dt0, f1))) return rc;
   hipLaunchKernelGGL(k_sums_init, dim3(NSUMB), dim3(256), 0, c->stream, u0, f0, (const float*)f1, abstol, reltol, sp.local, c->sums);
   if ((rc = fetch_sums(c, s))) return rc;
-  *dt_out = initdt_tail(dt0, d1, (float)sqrt(s[2] / sp.global), 5.0f, dtmax);
+  *dt_out = initdt_tail(dt0, d1, (float)sqrt(s[2] / sp.global), order, dtmax);
   return LRNDE_OK;
 }
 
@@ -2267,6 +2270,8 @@ void reg_values(const double* s, double n, float dt, float* eest, float* re, flo
     else { const float num = (float)sqrt(s[1] / n); *rs = fabsf(num / (den + 1.1920929e-7f)) / 3.5068f; }
   }
 }
+
+#include "lrnde_conv_adams.hpp"   // VCAB3 / VCABM3: conv_adams_solve, cad_eval
 
 }  // namespace
 
@@ -2413,6 +2418,16 @@ int lrnde_conv_set_params(lrnde_conv* c, const float* p, size_t n) {
   return LRNDE_OK;
 }
 
+int lrnde_conv_set_solver(lrnde_conv* c, int32_t alg) {
+  if (!c) return LRNDE_BADARG;
+  if (alg != LRNDE_ALG_TSIT5 && alg != LRNDE_ALG_VCAB3 && alg != LRNDE_ALG_VCABM3)
+    return cfail(c, LRNDE_BADARG, "solver must be 0 (Tsit5), 1 (VCAB3) or 2 (VCABM3)");
+  if ((alg != LRNDE_ALG_TSIT5) != (c->solver_alg != LRNDE_ALG_TSIT5)) c->wsB = 0;   // the work vectors are sized per solver (ensure_ws)
+  c->solver_alg = alg;
+  c->rec.invalidate();
+  return LRNDE_OK;
+}
+
 int lrnde_conv_set_bn_state(lrnde_conv* c, const float* mean_var, size_t n) {
   if (!c || !mean_var) return LRNDE_BADARG;
   const int Hc = c->d.hidden;
@@ -2512,6 +2527,8 @@ int lrnde_conv_solve(lrnde_conv* c, const float* u0, int32_t B, float t0, float 
   c->rec.ts.clear();
   if (c->dense_on) { c->dense_t.clear(); c->dense_dt.clear(); }
   else c->rec.invalidate();  // a plain solve overwrites the saved times the recorded backward pass reads
+  if (c->solver_alg != LRNDE_ALG_TSIT5)
+    return conv_adams_solve(c, u0, B, t0, t1, o, saveat, nsave, u_saved, t_saved, cap_saved, st, trace, cap_trace);
   auto push = [&](float tt, const float* uu) -> int {
     if (nsaved >= cap_saved || !u_saved) return cfail(c, LRNDE_CAPACITY, "u_saved capacity %d exhausted", cap_saved);
     CHK(c, hipMemcpyAsync(u_saved + (size_t)nsaved * n, uu, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream));
@@ -2808,7 +2825,7 @@ int lrnde_conv_node_forward_record(lrnde_conv* c, const float* x, int32_t B, flo
   c->dense_on = false;
   if (rc) return rc;
   if (t1_used_host) *t1_used_host = t1;
-  c->rec.set(B, mode, reg_type, t0, t2, t1, *o);
+  c->rec.set(B, mode, reg_type, t0, t2, t1, *o, c->solver_alg);
   return LRNDE_OK;
 }
 
@@ -2862,9 +2879,14 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
     const float t = -sg;
     const RecAt at = rec_locate(dts.data(), dds.data(), (int)dts.size(), t);
     const int lo = at.idx;
+    const float* d = c->dense[lo];
+    if (R.solver_alg != LRNDE_ALG_TSIT5) {   // a Hermite slot [uprev, k1, P2, P3] of an Adams forward (lrnde_conv_adams.hpp)
+      int r;
+      if ((r = cad_eval(c, d, n, at.theta, dds[lo], ybuf))) return r;
+      return launch_vjp(c, ybuf, t, zs, B, K, K + n);
+    }
     float bw[7];
     tsit5_bweights(at.theta, bw);
-    const float* d = c->dense[lo];
     const float* K7[7] = {d + n, d + 2 * n, d + 3 * n, d + 4 * n, d + 5 * n, d + 6 * n, d + 7 * n};
     int r;
     if ((r = lincomb(c, ybuf, d, dds[lo], 7, K7, bw, n))) return r;

@@ -47,6 +47,7 @@
 #include "lrnde_hooks.h"
 #include "lrnde_math.hpp"
 #include "lrnde_stepctl.hpp"
+#include "lrnde_adams_math.hpp"
 #include "lrnde_layer_plan.hpp"
 #include "lrnde_adj_route.hpp"  // AdjRoute, AdjPlan, adj_route: which way the recorded backward runs the reversed solve
 #include "lrnde_qsched.hpp"    // the compile-time issue schedule of the 4-column kernels' weight stream

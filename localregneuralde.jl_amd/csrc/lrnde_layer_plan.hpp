@@ -151,12 +151,13 @@ struct LayerRecord {
   unsigned long long gen = 0;   // counts the recorded forwards of the handle
   int B = 0, mode = 0, reg_type = 0;
   float t0 = 0.f, t2 = 0.f, t1 = 0.f;
+  int solver_alg = 0;           // LRNDE_ALG_* of the solve that made the record: what form its dense slots have
   lrnde_solve_opts opts{};
   std::vector<float> ts;        // sol.t of the solve: the cotangent times of the adjoint
   void invalidate() { valid = false; }
   unsigned long long generation() const { return valid ? gen : 0; }   // 0: no usable record
-  void set(int B_, int mode_, int reg_type_, float t0_, float t2_, float t1_, const lrnde_solve_opts& o) {
-    valid = true; ++gen; B = B_; mode = mode_; reg_type = reg_type_; t0 = t0_; t2 = t2_; t1 = t1_; opts = o;
+  void set(int B_, int mode_, int reg_type_, float t0_, float t2_, float t1_, const lrnde_solve_opts& o, int solver_alg_ = 0) {
+    valid = true; ++gen; B = B_; mode = mode_; reg_type = reg_type_; t0 = t0_; t2 = t2_; t1 = t1_; opts = o; solver_alg = solver_alg_;
   }
 };
 

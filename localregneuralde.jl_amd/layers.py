@@ -642,7 +642,9 @@ class NeuralODE:
         self._conv = conv_topology(model)  # (C, Hc, act, eps) for the CIFAR node_core, else None
         self.desc = None if self._conv else _mlp_desc(model)
         if self._conv and self.solver != "tsit5":
-            raise NotImplementedError("VCAB3 / VCABM3 are built for the MLP field's handle (csrc/lrnde_adams.hpp)")
+            # as for the chain fields: the layer is built with the default solver and the handle is told
+            raise NotImplementedError("the solver keyword is built for the MLP field; a conv-field layer takes VCAB3 / VCABM3 "
+                                      "on its handle: node.handle(x).set_solver(...) (csrc/lrnde_conv_adams.hpp)")
         self._handle = None
         self._bound = False
 
@@ -662,8 +664,10 @@ class NeuralODE:
                 hw = (int(x.shape[3]), int(x.shape[2]))
                 if self._handle is None or self._hw != hw:
                     Cst, Hc, act, eps = self._conv
+                    solver = self._handle.solver if self._handle is not None else "tsit5"
                     self._handle = ConvHandle(hw[0], hw[1], Cst, Hc, act=act, bn_train=True, bn_eps=eps,
                                               compute_dtype=self.kwargs.get("compute_dtype", "f32"))
+                    self._handle.set_solver(solver)   # a handle rebuilt for another image size keeps the old one's solver
                     self._hw, self._bound = hw, False
             return self._handle
         if self._handle is None:
