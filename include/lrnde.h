@@ -408,6 +408,28 @@ int lrnde_conv_node_forward_record(lrnde_conv* c, const float* x, int32_t B, flo
                                    int32_t* nfe_host, lrnde_stats* st, float* t1_used_host);
 int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_end, float w_reg, float* dx, float* dp,
                                       lrnde_stats* st_bwd);
+/* lrnde_set_sensealg for the conv handle: the method of lrnde_conv_node_backward and lrnde_conv_node_backward_recorded.
+ * LRNDE_SENSE_INTERPOLATING (the default): the reversed Tsit5 solve of [lambda; mu] over the interpolated record.
+ * LRNDE_SENSE_DISCRETE: the discrete adjoint of the recorded Tsit5 solve with the meaning lrnde_set_sensealg states
+ * (UPSTREAM-RECALL, frozen grid): loss = <du_end, sol.u[end]> + w_reg * reg_val, the exact derivative of the discrete
+ * forward map over the accepted steps of the record, their times and step sizes constants, rejected attempts absent, the
+ * first-same-as-last evaluation differentiated; u(t1) of the local step (every saved state of `unbiased` / `biased` mode)
+ * stays a constant and the regulariser's gradient is the continuous method's, unchanged.  A reverse sweep over the record
+ * (csrc/lrnde_conv_discrete.hpp: the sweep, its order of summation, its workspace): six VJPs per recorded step, no
+ * controller, no norm; every launch goes to the handle's stream and the call waits once at the end.  Two calls give the same
+ * bits.  lrnde_stats of the backward: naccept = iters = the record's steps, nreject = 0, nf = 6 * steps (the VJPs run).
+ * The running statistics are left alone.  Sharded handles take the same method (every rank sets it): the sweep adds no
+ * exchange to those of the VJPs; dx stays sharded, dp comes out replicated.
+ * The setter does not invalidate the forward record: one record can be pulled back by either method.  It returns
+ * LRNDE_BADARG for an unknown code and LRNDE_UNSUPPORTED for DISCRETE on a LRNDE_BF16 or LRNDE_F32_SPLIT handle; the handle
+ * stays usable after either.  A backward call with DISCRETE set whose record (or, for the one-call form, whose solver) is
+ * VCAB3 / VCABM3 returns LRNDE_UNSUPPORTED ("not a Tsit5 stage record"), touches nothing, never runs the continuous method
+ * instead, and leaves the record usable once the setting is changed back. */
+int lrnde_conv_set_sensealg(lrnde_conv* c, int32_t sensealg);
+/* The accepted steps of the current forward record (lrnde_conv_node_forward_record, any solver): t_host[i], dt_host[i] of
+ * step i, *n_host steps — the grid the discrete adjoint holds constant.  LRNDE_BADARG if there is no valid record or
+ * cap < the step count (*n_host then holds the count, nothing else is written). */
+int lrnde_conv_record_steps(lrnde_conv* c, float* t_host, float* dt_host, int32_t cap, int32_t* n_host);
 /* ---- layers around the CIFAR10 NeuralODE (experiments/src/construct.jl:224-227) ----
  * stem: AugmenterLayer(Conv((3,3), 3=>5; pad=1), 3) (src/layers/common.jl:80-92: cat(x, conv(x); dims=3)) + BatchNorm(8);
  * ps (device, 156) = [conv.weight 3x3x3x5 column-major; conv.bias 5; bn.scale 8; bn.bias 8]; x (B,3,H,W) -> u0 (B,8,H,W).

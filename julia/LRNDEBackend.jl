@@ -196,6 +196,16 @@ conv_set_params!(ctx, ps) = conv_check(ctx, ccall((:lrnde_conv_set_params, lib),
                                                   ctx, pointer(ps), length(ps)))
 # n.solver on the conv handle (LRNDE_ALG_*: 0 Tsit5, 1 VCAB3, 2 VCABM3); the local step and the adjoint stay Tsit5
 conv_set_solver!(ctx, alg) = conv_check(ctx, ccall((:lrnde_conv_set_solver, lib), Cint, (Ptr{Cvoid}, Int32), ctx, alg))
+# n.sensealg on the conv handle (LRNDE_SENSE_*: 0 the continuous adjoint, 1 the discrete adjoint of the recorded Tsit5 solve:
+# six VJPs per recorded step, frozen grid; fp32 handles, Tsit5 records); does not invalidate the forward record
+const SENSE_INTERPOLATING, SENSE_DISCRETE = Int32(0), Int32(1)
+conv_set_sensealg!(ctx, sense) = conv_check(ctx, ccall((:lrnde_conv_set_sensealg, lib), Cint, (Ptr{Cvoid}, Int32), ctx, sense))
+function conv_record_steps(ctx; cap=1024)   # (t_n, dt_n) of the accepted steps of the current forward record
+    t = Vector{Float32}(undef, cap); dt = Vector{Float32}(undef, cap); n = Ref{Int32}(0)
+    conv_check(ctx, ccall((:lrnde_conv_record_steps, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Int32, Ptr{Int32}),
+                          ctx, t, dt, Int32(cap), n))
+    return t[1:n[]], dt[1:n[]]
+end
 conv_set_bn_state!(ctx, st) = conv_check(ctx, ccall((:lrnde_conv_set_bn_state, lib), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t),
                                                     ctx, pointer(st), length(st)))
 function conv_get_bn_state(ctx, like)   # like: a device vector of 4*hidden Float32 ([μ1; σ²1; μ2; σ²2] of st.model)

@@ -209,6 +209,8 @@ function lrnde_conv_field_shape(model, x)
     return (size(x, 1), size(x, 2), C, Hc, _LRNDE_ACT[b1.activation])
 end
 
+_lrnde_sense(sensealg) = nameof(typeof(sensealg)) in (:TrackerAdjoint, :ReverseDiffAdjoint) ? LRNDEBackend.SENSE_DISCRETE :
+                          LRNDEBackend.SENSE_INTERPOLATING
 const _lrnde_conv_handles = IdDict{Any, Ptr{Cvoid}}()
 function lrnde_conv_handle(n::NeuralODE, x)
     get!(_lrnde_conv_handles, n) do
@@ -217,6 +219,10 @@ function lrnde_conv_handle(n::NeuralODE, x)
         # VCAB3 / VCABM3 for the global solve (csrc/lrnde_conv_adams.hpp); UPSTREAM-RECALL, parity unpinned; the local step and the
         # pullback's reversed solve stay Tsit5
         LRNDEBackend.conv_set_solver!(cctx, _lrnde_alg(n.solver))
+        # n.sensealg: a tape (TrackerAdjoint / ReverseDiffAdjoint) is the discrete adjoint of the recorded solve on its frozen
+        # grid (csrc/lrnde_conv_discrete.hpp; UPSTREAM-RECALL); anything else keeps the reversed solve.  The handle refuses the
+        # discrete adjoint of a VCAB3 / VCABM3 record at the pullback.
+        LRNDEBackend.conv_set_sensealg!(cctx, _lrnde_sense(n.sensealg))
         cctx
     end
 end

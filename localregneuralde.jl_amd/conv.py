@@ -86,6 +86,7 @@ class ConvHandle:
         if rc != 0:
             raise L.LrndeError(rc, "lrnde_conv_create failed (shape or dtype not supported by the kernels)")
         self.solver = "tsit5"
+        self.sensealg = "interpolating"
         self._keep = {}  # name -> the tensor a pending async copy reads (one slot per kind: overwritten, never appended)
 
     def close(self):
@@ -135,6 +136,32 @@ class ConvHandle:
         from .layers import SOLVERS, _solver_name
         self._chk(L.lib.lrnde_conv_set_solver(self._ctx, SOLVERS[_solver_name(solver)]))
         self.solver = _solver_name(solver)
+
+    SENSEALGS = {"interpolating": 0, "discrete": 1}
+
+    def set_sensealg(self, sensealg):
+        """lrnde_conv_set_sensealg: the method of node_backward / node_backward_recorded.  "interpolating" (the default:
+        the reversed Tsit5 solve of the continuous adjoint) or "discrete" (the discrete adjoint of the recorded Tsit5
+        solve on its frozen step grid: a reverse sweep of six VJPs per recorded step, csrc/lrnde_conv_discrete.hpp;
+        UPSTREAM-RECALL).  Does not invalidate the forward record.  bf16 / f32_split handles refuse "discrete"."""
+        if sensealg not in self.SENSEALGS:
+            raise ValueError(f"sensealg must be 'interpolating' or 'discrete' (got {sensealg!r})")
+        self._chk(L.lib.lrnde_conv_set_sensealg(self._ctx, self.SENSEALGS[sensealg]))
+        self.sensealg = sensealg
+
+    def record_steps(self):
+        """(t, dt) float32 arrays of the accepted steps of the current forward record (node_forward_record): the grid the
+        discrete adjoint holds constant"""
+        cap = 64
+        while True:
+            t, dt, n = np.empty(cap, np.float32), np.empty(cap, np.float32), C.c_int32(-1)
+            rc = L.lib.lrnde_conv_record_steps(self._ctx, t.ctypes.data_as(C.POINTER(C.c_float)),
+                                               dt.ctypes.data_as(C.POINTER(C.c_float)), cap, C.byref(n))
+            if rc != 0 and n.value > cap:   # the record is longer: the count came back, nothing else was written
+                cap = int(n.value)
+                continue
+            self._chk(rc)
+            return t[:n.value].copy(), dt[:n.value].copy()
 
     def get_bn_state(self):
         """running [mean1 var1 mean2 var2] (st.model of the layer), advanced by every training-mode f-eval"""

@@ -1789,6 +1789,7 @@ struct lrnde_conv {
   DevBuf<double> part; int nwg = 0;
   DevBuf<float> vec;      // 11 state-sized vectors (Tsit5), CAD_VECS for VCAB3 / VCABM3 (lrnde_conv_adams.hpp)
   int solver_alg = 0;     // lrnde_conv_set_solver: the method of the layer's global solve (LRNDE_ALG_*)
+  int sensealg = 0;       // lrnde_conv_set_sensealg: the method of the backward pass (LRNDE_SENSE_*)
   DevBuf<double> sums; PinBuf<double> sums_host;
   HipEvent ev0, ev1;
   int num_cu = 256;
@@ -2796,6 +2797,26 @@ int adjoint_solve(lrnde_conv* c, size_t N, NormSpan sp, RHS&& rhs, float* Z, flo
   return rc;
 }
 
+#include "lrnde_conv_discrete.hpp"   // LRNDE_SENSE_DISCRETE: conv_discrete_sweep
+
+// dp += w_reg * d reg_val / d p at the record's local step (both methods of the backward pass end with it)
+int backward_reg_term(lrnde_conv* c, int B, float w_reg, float* dp) {
+  const LayerRecord& R = c->rec;
+  const lrnde_solve_opts* o = &R.opts;
+  const size_t n = state_n(c, B), P = lrnde_conv_param_count(&c->d);
+  int rc;
+  DevBuf<float> k1, gr;
+  CHK(c, k1.once(n));
+  CHK(c, gr.once(P));
+  float dtl = 0.f, rv = 0.f;
+  float* V = c->vec;
+  rc = init_dt(c, c->rec_u1, B, R.t1, R.t2, o->abstol, o->reltol, k1, V + 10 * n, V + 9 * n, &dtl);
+  if (!rc) rc = step_reg_grad(c, c->rec_u1, k1, B, R.t1, dtl, o->abstol, o->reltol, R.reg_type, gr, &rv);
+  if (!rc) { const float* g1[1] = {gr}; rc = lincomb(c, dp, dp, 0.f, 1, g1, &w_reg, P); }
+  if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LRNDE_HIP_ERROR;
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2838,6 +2859,9 @@ int lrnde_conv_node_backward(lrnde_conv* c, const float* x, int32_t B, float t0,
   int rc = check_ready(c, B);
   if (rc) return rc;
   if (!x || !o || !du_end || !dx || !dp || !st_fwd || !st_bwd) return cfail(c, LRNDE_BADARG, "null pointer");
+  if (c->sensealg == LRNDE_SENSE_DISCRETE && c->solver_alg != LRNDE_ALG_TSIT5)   // before the forward: nothing is touched
+    return cfail(c, LRNDE_UNSUPPORTED, "the discrete adjoint walks a Tsit5 stage record; the record of solver %d is not a Tsit5 stage "
+                 "record: select the continuous adjoint with lrnde_conv_set_sensealg or solve with Tsit5", c->solver_alg);
   // 1. forward with the dense record
   DevBuf<float> u_end;   // scratch of this call: released as soon as the forward has returned
   CHK(c, u_end.once(state_n(c, B)));
@@ -2862,9 +2886,17 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
   const LayerRecord& R = c->rec;
   if (!R.valid || R.B != B) return cfail(c, LRNDE_BADARG, "no forward record for this batch (call lrnde_conv_node_forward_record first)");
   const lrnde_solve_opts* o = &R.opts;
-  const float t0 = R.t0, t2 = R.t2, t1 = R.t1;
-  const int mode = R.mode, reg_type = R.reg_type;
+  const float t0 = R.t0, t2 = R.t2;
+  const int mode = R.mode;
   const size_t n = state_n(c, B), P = lrnde_conv_param_count(&c->d), N = n + P;
+  if (c->sensealg == LRNDE_SENSE_DISCRETE) {   // the reverse sweep over the record; never the reversed solve instead
+    if (R.solver_alg != LRNDE_ALG_TSIT5 || c->dense_t.empty() || c->dense_n != n)
+      return cfail(c, LRNDE_UNSUPPORTED, "the discrete adjoint walks a Tsit5 stage record; this record is not a Tsit5 stage record "
+                   "(solver %d): select the continuous adjoint with lrnde_conv_set_sensealg or record a Tsit5 forward", R.solver_alg);
+    if ((rc = conv_discrete_sweep(c, B, du_end, dx, dp, st_bwd))) return rc;
+    if (mode != LRNDE_MODE_NONE && w_reg != 0.0f) return backward_reg_term(c, B, w_reg, dp);
+    return LRNDE_OK;
+  }
   // the local step of node_forward re-solved nothing: rec.ts / dense_t describe the main solve (dense record is
   // only appended inside lrnde_conv_solve)
   const std::vector<float> dts = c->dense_t, dds = c->dense_dt;
@@ -2902,18 +2934,29 @@ int lrnde_conv_node_backward_recorded(lrnde_conv* c, int32_t B, const float* du_
   CHK(c, hipMemcpyAsync(dp, Z + n, sizeof(float) * P, hipMemcpyDeviceToDevice, c->stream));
   CHK(c, hipStreamSynchronize(c->stream));
   // 3. regulariser: dp += w_reg * d reg_val / d p
-  if (mode != LRNDE_MODE_NONE && w_reg != 0.0f) {
-    DevBuf<float> k1, gr;
-    CHK(c, k1.once(n));
-    CHK(c, gr.once(P));
-    float dtl = 0.f, rv = 0.f;
-    float* V = c->vec;
-    rc = init_dt(c, c->rec_u1, B, t1, t2, o->abstol, o->reltol, k1, V + 10 * n, V + 9 * n, &dtl);
-    if (!rc) rc = step_reg_grad(c, c->rec_u1, k1, B, t1, dtl, o->abstol, o->reltol, reg_type, gr, &rv);
-    if (!rc) { const float* g1[1] = {gr}; rc = lincomb(c, dp, dp, 0.f, 1, g1, &w_reg, P); }
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = LRNDE_HIP_ERROR;
-    if (rc) return rc;
-  }
+  if (mode != LRNDE_MODE_NONE && w_reg != 0.0f) return backward_reg_term(c, B, w_reg, dp);
+  return LRNDE_OK;
+}
+
+int lrnde_conv_set_sensealg(lrnde_conv* c, int32_t sensealg) {
+  if (!c) return LRNDE_BADARG;
+  if (sensealg != LRNDE_SENSE_INTERPOLATING && sensealg != LRNDE_SENSE_DISCRETE)
+    return cfail(c, LRNDE_BADARG, "sensealg must be 0 (the continuous adjoint) or 1 (the discrete adjoint of the record)");
+  if (sensealg == LRNDE_SENSE_DISCRETE && c->d.compute_dtype != LRNDE_F32)
+    return cfail(c, LRNDE_UNSUPPORTED, "the discrete adjoint is built for fp32 conv handles (this one is %s)",
+                 c->d.compute_dtype == LRNDE_BF16 ? "bf16" : "f32_split");
+  c->sensealg = sensealg;
+  return LRNDE_OK;
+}
+
+int lrnde_conv_record_steps(lrnde_conv* c, float* t_host, float* dt_host, int32_t cap, int32_t* n_host) {
+  if (!c) return LRNDE_BADARG;
+  if (!t_host || !dt_host || !n_host) return cfail(c, LRNDE_BADARG, "null pointer");
+  if (!c->rec.valid) return cfail(c, LRNDE_BADARG, "no forward record (call lrnde_conv_node_forward_record first)");
+  const size_t N = c->dense_t.size();
+  *n_host = (int32_t)N;
+  if (cap < 0 || (size_t)cap < N) return cfail(c, LRNDE_BADARG, "the record has %zu steps, room for %d", N, (int)cap);
+  for (size_t i = 0; i < N; ++i) { t_host[i] = c->dense_t[i]; dt_host[i] = c->dense_dt[i]; }
   return LRNDE_OK;
 }
 

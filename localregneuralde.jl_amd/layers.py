@@ -619,11 +619,12 @@ class NeuralODE:
                                       f"field='dense_chain' takes its discrete adjoint with sensealg='TrackerAdjoint'")
         self.adjoint_loop = adjoint_loop
         # sensealg (src/layers/neural_ode.jl:1-23): the method of `pullback` (_sensealg_choice); the discrete adjoint is
-        # built for the small Dense-chain handle alone
+        # built for the small Dense-chain handle and, with field="auto", for the conv field (ConvHandle.set_sensealg)
         self.sense = _sensealg_choice(sensealg)
-        if self.sense == "discrete" and field != "dense_chain":
+        conv_auto = field == "auto" and conv_topology(model) is not None
+        if self.sense == "discrete" and field != "dense_chain" and not conv_auto:
             raise NotImplementedError(f"sensealg={sensealg!r} (the discrete adjoint) is built for field='dense_chain' "
-                                      f"(got field={field!r})")
+                                      f"and for the conv field (got field={field!r})")
         if field in ("dense_chain", "wide_chain"):
             self._conv = None
             self.desc = _chain_desc(model) if field == "dense_chain" else _wide_chain_desc(model)
@@ -665,9 +666,12 @@ class NeuralODE:
                 if self._handle is None or self._hw != hw:
                     Cst, Hc, act, eps = self._conv
                     solver = self._handle.solver if self._handle is not None else "tsit5"
+                    sense = self._handle.sensealg if self._handle is not None else self.sense
                     self._handle = ConvHandle(hw[0], hw[1], Cst, Hc, act=act, bn_train=True, bn_eps=eps,
                                               compute_dtype=self.kwargs.get("compute_dtype", "f32"))
                     self._handle.set_solver(solver)   # a handle rebuilt for another image size keeps the old one's solver
+                    if sense != "interpolating":      # ... and its sensealg; a new one is told the layer's
+                        self._handle.set_sensealg(sense)
                     self._hw, self._bound = hw, False
             return self._handle
         if self._handle is None:
@@ -764,7 +768,8 @@ class NeuralODE:
         adjoint_loop="device") or "chain_discrete" (a layer built with sensealg="TrackerAdjoint" / "ReverseDiffAdjoint" /
         "discrete": no reversed solve, the discrete adjoint of the record in one launch, UPSTREAM-RECALL frozen grid) or
         "wide_discrete" (a field="wide_chain" layer built with adjoint_loop="discrete": the same discrete adjoint, two
-        launches per recorded step and no host wait); the conv field's own backward reports None."""
+        launches per recorded step and no host wait); the conv field's own backward reports None, and "conv_discrete" for a
+        conv layer built with one of those sensealg names (a reverse sweep of six VJPs per recorded step)."""
         h = self._bind(ps, x)
         t0, t2 = self.tspan
         kw = self.kwargs
@@ -793,5 +798,6 @@ class NeuralODE:
             bw = h.node_backward_recorded(du, w_reg=w_reg) if not self._conv else h.node_backward_recorded(x.shape[0], du, w_reg=w_reg)
         info = dict(bw, reg_val=fw["reg_val"], t1=fw["t1"], nfe=fw["nfe"], u_end=fw["u_end"], stats_fwd=fw["stats"],
                     sol_t=fw.get("t"), sol_u=fw.get("u"),
-                    adjoint_loop=None if self._conv else Handle.ADJOINT_LOOP_NAMES[h.last_adjoint_info()["kind"]])
+                    adjoint_loop=(("conv_discrete" if h.sensealg == "discrete" else None) if self._conv else
+                                  Handle.ADJOINT_LOOP_NAMES[h.last_adjoint_info()["kind"]]))
         return bw["dx"], bw["dp"], info
